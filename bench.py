@@ -109,12 +109,6 @@ def run(args):
     if "WORLD_SIZE" in os.environ:  # one line per rank: what the launcher handed over
         log(f"rank {rank} local_rank {local_rank} world_size {world} master "
             f"{os.environ.get('MASTER_ADDR', '?')}:{os.environ.get('MASTER_PORT', '?')}")
-    if world > 1:
-        # a rank holds the null stream, the main, weight-gradient and communication streams plus whatever RCCL and
-        # torch.distributed create; the HIP runtime multiplexes streams onto GPU_MAX_HW_QUEUES (default 4) hardware queues,
-        # and a communication stream that lands in the main stream's queue would serialise the all-reduce behind the
-        # backward pass it is meant to overlap.  Read at runtime initialisation: set before torch loads.
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
     import torch  # (first: libaleppo.so must bind to the HIP runtime torch ships, not load a second one)
     import torch.distributed as dist
     load_package().device_check(local_rank)  # fails loudly (ALEPPO_ERR_NO_DEVICE) before anything else touches a device
@@ -230,6 +224,8 @@ def run(args):
     log(f"timed {args.steps} steps in {dt:.3f} s -> {value:.0f} env-steps/s; per step: slots "
         f"{split[0] / args.steps * 1e3:.2f} ms, finish_rollout {split[1] / args.steps * 1e3:.2f} ms, "
         f"train {split[2] / args.steps * 1e3:.2f} ms")
+    if args.dump_outputs and rank == 0:  # before the profiling passes below roll out and train again
+        dump_outputs(args.dump_outputs, eng, metrics)
 
     # ---- separate profiling passes (HIP events around every launch, on the stream the kernels run on):
     # one rollout (acting shapes) and one update (training shapes) are profiled separately
@@ -443,6 +439,32 @@ def run(args):
         dist.destroy_process_group()
 
 
+DUMP_SAMPLE = 1 << 20  # elements kept of a batch plane larger than this (a fixed, seeded sample)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, eng, metrics):
+    """what the last timed step handed its caller, as <out_dir>/<name>.npy (float32): the update's per-minibatch metrics,
+    the updated parameters and the rollout batch (observation planes as a seeded sample of DUMP_SAMPLE elements)"""
+    arrays = {f"train_{k}": v for k, v in metrics.items()}
+    arrays["params"] = eng.export_params()
+    for name in ("actions", "rewards", "masks", "terminals", "truncations", "logits", "log_probs", "values", "next_values",
+                 "advantages", "returns", "observations", "current_obs"):
+        a = eng.read_batch(name)
+        if a.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(1234).integers(0, a.size, DUMP_SAMPLE))
+            a, name = a.ravel()[idx], name + "_sample"
+        arrays[name] = a
+    arrays = {k: np.asarray(v, np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_MAX_BYTES})")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    log(f"dumped {len(arrays)} arrays ({total / 1e6:.1f} MB) to {out_dir}")
+
+
 def v1_shape_leg(pkg, args, device):
     import torch
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -558,4 +580,9 @@ if __name__ == "__main__":
     ap.add_argument("--force-comm", action="store_true",
                     help="N=1 only: run aleppo_train's data-parallel schedule through a 1-rank RCCL communicator")
     ap.add_argument("--master-port", type=int, default=29517, help="rendezvous port when bench.py spawns the ranks")
-    run(ap.parse_args())
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (metrics, parameters, rollout batch) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    run(args)

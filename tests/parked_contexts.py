@@ -1,13 +1,17 @@
 """Helper process of test_other_contexts_and_operators_never_wait_for_a_parked_stream (tests/test_gpu_at_size.py).
 
-Runs with GPU_MAX_HW_QUEUES=16: the HIP runtime multiplexes streams onto that many hardware queues (default 4), and a
-kernel that lands in the queue of a PARKED stream waits behind its gate whatever the library does (parkprobe: "kernels on 6
-new streams").  With a queue per stream what is left is what the library controls: which runtime calls its entry points
-make while another context's stream is parked."""
+The HIP runtime multiplexes streams onto a limited number of hardware queues per process (GPU_MAX_HW_QUEUES), and a
+kernel that lands in the queue of a PARKED stream waits behind its gate whatever the library does (parkprobe: "kernels
+on 6 new streams").  The test is about what the library controls: which runtime calls its entry points make while
+another context's stream is parked.  So before the check, A's hardware queue is made the busiest one of the process:
+idle filler contexts are created, the ones whose acting forward waits behind A's gate are kept (their stream shares A's
+queue) and the others are closed.  The runtime gives a new stream the queue with the fewest streams, so B's streams and
+the operators' stream, all created afterwards, land in other queues even when the process may only open two."""
 import ctypes
 import os
 import sys
 import threading
+import time
 
 import numpy as np
 
@@ -24,6 +28,36 @@ E, T, A, H = 8, 4, 4, 32
 a = pkg.Engine(E, T, A, H, seed=3)
 a.load_params(hf.fill_params(2710, H, A))
 fbuf, sbuf = a.host_alloc(E * 7056), a.host_alloc(E)
+
+# ---- hardware-queue layout (module docstring): keep the idle filler contexts whose stream shares A's queue
+fillers = []
+for k in range(12):
+    f = pkg.Engine(E, T, A, H, seed=20 + k)
+    f.load_params(hf.fill_params(2720 + k, H, A))
+    fillers.append(f)
+
+
+def release_a():
+    ctypes.memmove(fbuf, hf.hf_bytes(2717, (E, 84, 84)).ctypes.data, E * 7056)
+    ctypes.memset(sbuf, 0, E)
+    a.release_step(np.zeros(E, np.float32), np.zeros(E, np.uint8), np.zeros(E, np.uint8))
+
+
+a.act()
+a.arm_step(fbuf, sbuf, pkg.FRAMES_84)
+probes = [threading.Thread(target=f.act, daemon=True) for f in fillers]  # one acting forward on each filler's stream
+for t in probes:
+    t.start()
+time.sleep(1.0)  # a free queue runs it in well under a millisecond
+behind_a = [t.is_alive() for t in probes]
+release_a()
+for t in probes:
+    t.join(120)
+for f, keep in zip(fillers, behind_a):
+    if not keep:
+        f.close()
+fillers = [f for f, keep in zip(fillers, behind_a) if keep]
+
 a.act()
 a.arm_step(fbuf, sbuf, pkg.FRAMES_84)  # A's stream is parked from here on
 done, err = threading.Event(), []
@@ -78,15 +112,16 @@ th.start()
 finished = done.wait(60)
 stuck = prog[-1:]  # (what B was inside of when the wait ran out)
 # release A whatever happened, so that a regression fails the test instead of hanging the box
-ctypes.memmove(fbuf, hf.hf_bytes(2717, (E, 84, 84)).ctypes.data, E * 7056)
-ctypes.memset(sbuf, 0, E)
-a.release_step(np.zeros(E, np.float32), np.zeros(E, np.uint8), np.zeros(E, np.uint8))
+release_a()
 th.join(120)
-assert finished, f"context B / a stateless operator waited for context A's parked stream in: {stuck}"
+assert finished, (f"context B / a stateless operator waited for context A's parked stream in: {stuck} "
+                  f"({len(fillers)} filler contexts kept in A's hardware queue)")
 assert err and not isinstance(err[0], Exception), err
 a.act()  # A is intact: the armed slot ran after the release
 err[0].close()
 a.host_free(fbuf)
 a.host_free(sbuf)
 a.close()
+for f in fillers:
+    f.close()
 print("parked-contexts ok")

@@ -695,7 +695,7 @@ def test_rollouts_run_concurrently_from_threads_match_rollouts_run_alone(pkg):
 # ------------------------------------------------------------------ the slot-ahead hand-off under several contexts
 def test_other_contexts_and_operators_never_wait_for_a_parked_stream():
     """The cause of round 2's two-thread hang, made deterministic (tests/parked_contexts.py, run in a process of its own
-    because it needs GPU_MAX_HW_QUEUES set before HIP initialises).  Context A has a step ARMED: its stream is parked behind
+    because it lays out the process's hardware queues itself).  Context A has a step ARMED: its stream is parked behind
     the release word, which only A's owner lifts.  hipFree / hipHostFree / hipDeviceSynchronize wait for EVERY stream of the
     device AND block the owner's next enqueue on the parked stream while they wait (tests/tools/parkprobe.hip,
     profiles/r03_parkprobe.log) - so an entry point that calls one of them on behalf of context B while A's owner is between
@@ -703,7 +703,7 @@ def test_other_contexts_and_operators_never_wait_for_a_parked_stream():
     more: creating a second context, a whole rollout and update on it, every read-back (which used to hipMalloc + hipFree
     per call), staging buffers that have to grow and the stateless operators all complete while A stays armed."""
     r = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "parked_contexts.py")],
-                       capture_output=True, text=True, timeout=600, env=dict(os.environ, GPU_MAX_HW_QUEUES="16"))
+                       capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "parked-contexts ok" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
 
 
