@@ -48,6 +48,7 @@ OPT_FC_PIPE, OPT_FUSED_ACT, OPT_UPDATE_GRAPH = 4, 6, 7
 OPT_GATE_TIMEOUT_MS = 9
 OPT_FUSED_FWD = 10
 OPT_FUSED_BWD = 11
+OPT_MINIBATCH_SHUFFLE = 12
 
 EXPORTS = [
     "aleppo_abi_version", "aleppo_create", "aleppo_destroy", "aleppo_last_error", "aleppo_param_count",
@@ -59,6 +60,7 @@ EXPORTS = [
     "aleppo_profile_reset", "aleppo_synchronize", "aleppo_set_option", "aleppo_export_optimizer",
     "aleppo_import_optimizer", "aleppo_replay_rollout", "aleppo_get_option",
     "aleppo_host_alloc", "aleppo_host_free", "aleppo_arm_step", "aleppo_release_step", "aleppo_device_check",
+    "aleppo_read_sample_order",
 ]
 
 
@@ -256,6 +258,7 @@ class Engine:
         self._ctx = C.c_void_p()
         _check(lib().aleppo_create(C.byref(self.cfg), C.byref(self._ctx)))
         self.E, self.T, self.A, self.H = num_envs, horizon, num_actions, hidden_size
+        self._batch_n = num_envs * horizon  # samples in the training arrays (aleppo_set_batch may hold fewer)
         n = C.c_size_t()
         _check(lib().aleppo_param_count(self._ctx, C.byref(n)), self._ctx)
         self.param_count = n.value
@@ -386,6 +389,7 @@ class Engine:
     def finish_rollout(self, noise=None):
         n = None if noise is None else _f32(noise)
         self._c(lib().aleppo_finish_rollout(self._ctx, _ptr(n)))
+        self._batch_n = self.E * self.T
 
     # -- update --
     def train(self, lr, epochs, num_mini_batches):
@@ -399,11 +403,19 @@ class Engine:
         self._c(lib().aleppo_read_train_metric(self._ctx, METRIC_FIELDS[name], _ptr(out), C.c_size_t(out.size)))
         return out
 
+    def sample_order(self, epochs):
+        """aleppo_read_sample_order: int32 [epochs, N], row e = the logical samples of epoch e in minibatch order
+        (identity rows after a contiguous update)."""
+        out = np.zeros((epochs, self._batch_n), np.int32)
+        self._c(lib().aleppo_read_sample_order(self._ctx, _ptr(out), C.c_size_t(out.size)))
+        return out
+
     def set_batch(self, observations, actions, log_probabilities, advantages, returns, masks):
         obs = _u8(observations)
         self._c(lib().aleppo_set_batch(self._ctx, _ptr(obs), _ptr(_i64(actions)), _ptr(_f32(log_probabilities)),
                                        _ptr(_f32(advantages)), _ptr(_f32(returns)), _ptr(_u8(masks)),
                                        C.c_int64(obs.shape[0])))
+        self._batch_n = obs.shape[0]
 
     def forward(self, observations):
         obs = _u8(observations)

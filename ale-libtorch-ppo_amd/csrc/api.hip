@@ -506,7 +506,8 @@ extern "C" void aleppo_destroy(aleppo_ctx *c) {
                  c->W2d,   c->W3d,      c->WfcT,      c->a1,        c->a2,         c->a3,      c->dz1,
                  c->dz2,   c->dz3,      c->h,         c->hpart,     c->dh,        c->logits_b,   c->values_b, c->slab,
                  c->sumsq_part, c->metric_ps, c->metric_red, c->grad_norms, c->adv_stats, c->stage_u8, c->stage_obs,
-                 c->adam_sched, c->rb_tmp[0], c->rb_tmp[1]};
+                 c->adam_sched, c->rb_tmp[0], c->rb_tmp[1], c->order, c->act_p, c->oldlp_p, c->adv_p,
+                 c->ret_p,  c->mask_p,   c->mask_counts_ep, c->shuf_keys};
   for (void *p : dev)
     if (p)
       hipFree(p);
@@ -515,7 +516,7 @@ extern "C" void aleppo_destroy(aleppo_ctx *c) {
   if (c->Pc && c->Pc != c->P)
     hipFree(c->Pc);
   void *host[] = {c->h_go, c->h_actions, c->h_step, c->h_rec, c->h_frames, c->h_noise, c->h_err, c->h_metric_red,
-                  c->h_adam_sched};
+                  c->h_adam_sched, c->h_shuf_keys};
   for (void *p : host)
     if (p)
       hipHostFree(p);
@@ -1156,6 +1157,53 @@ static int ensure_metric_storage(aleppo_ctx *c, int epochs, int M, long B) {
   return ALEPPO_OK;
 }
 
+// ALEPPO_OPT_MINIBATCH_SHUFFLE: order + gathered planes for epochs x N samples, mask counts and round keys per epoch / minibatch
+// (grown together, like the metric storage; never freed before aleppo_destroy)
+static int ensure_shuffle_storage(aleppo_ctx *c, int epochs, long N) {
+  const size_t ns = (size_t)epochs * N;
+  if (ns > c->shuf_cap || epochs > c->shuf_epochs_cap) {
+    for (void *p : {(void *)c->order, (void *)c->act_p, c->oldlp_p, c->adv_p, c->ret_p, (void *)c->mask_p,
+                    (void *)c->mask_counts_ep, (void *)c->shuf_keys})
+      retire(c, p);
+    retire_host(c, c->h_shuf_keys);
+    c->order = nullptr;
+    c->act_p = nullptr;
+    c->oldlp_p = c->adv_p = c->ret_p = nullptr;
+    c->mask_p = nullptr;
+    c->mask_counts_ep = nullptr;
+    c->shuf_keys = c->h_shuf_keys = nullptr;
+    c->shuf_cap = 0;
+    c->shuf_epochs_cap = 0;
+    HIPCHK(c, dalloc(&c->order, ns * 4, c->stream));
+    HIPCHK(c, dalloc(&c->act_p, ns * 4, c->stream));
+    HIPCHK(c, dalloc(&c->oldlp_p, ns * c->A * c->rsz, c->stream));
+    HIPCHK(c, dalloc(&c->adv_p, ns * c->rsz, c->stream));
+    HIPCHK(c, dalloc(&c->ret_p, ns * c->rsz, c->stream));
+    HIPCHK(c, dalloc(&c->mask_p, ns, c->stream));
+    HIPCHK(c, dalloc(&c->mask_counts_ep, ns * 4, c->stream)); // (epochs * M <= epochs * N counts)
+    HIPCHK(c, dalloc(&c->shuf_keys, (size_t)epochs * 16, c->stream));
+    HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_shuf_keys), (size_t)epochs * 16, hipHostMallocDefault));
+    c->shuf_cap = ns;
+    c->shuf_epochs_cap = epochs;
+  }
+  return ALEPPO_OK;
+}
+
+static uint64_t splitmix64(uint64_t x) { // the permutation of aleppo.h (aleppo_read_sample_order)
+  uint64_t z = x + 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+// half width h of the Feistel network over [0, 2^(2h)) for N samples: 2h = ceil(log2 N), at least 2, rounded up to even
+static int feistel_half_width(long N) {
+  int w = 0;
+  while ((1L << w) < N)
+    ++w;
+  w = std::max(w, 2);
+  return (w + 1) / 2;
+}
+
 static bool fuse_tail_env() { // A/B switch: conv1's slab reduce fused into the sum-of-squares pass (default)
   static const bool v = [] {
     const char *e = getenv("ALEPPO_FUSE_TAIL_REDUCE");
@@ -1184,6 +1232,9 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
   int rc = ensure_metric_storage(c, epochs, M, B);
   if (rc)
     return rc;
+  const bool shuffle = c->shuffle;
+  if (shuffle && (rc = ensure_shuffle_storage(c, epochs, N)))
+    return rc;
   ncclComm_t comm = static_cast<ncclComm_t>(c->nccl_comm);
   const bool dp = c->world > 1 || (c->nccl_comm && c->force_comm); // force_comm: 1-rank communicator (tests)
   // side streams, created on first use (see aleppo_create): the weight-gradient stream, and - only with data parallelism -
@@ -1206,6 +1257,18 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
     c->h_adam_sched[2 * i + 1] = (float)std::sqrt(1.0 - std::pow(b2, t));
   }
   HIPCHK(c, hipMemcpyAsync(c->adam_sched, c->h_adam_sched, (size_t)nm * 8, hipMemcpyHostToDevice, s));
+  // ... and, with ALEPPO_OPT_MINIBATCH_SHUFFLE, the round keys of every epoch's permutation (aleppo.h): keyed by the Adam
+  // step the epoch starts at, so a graph replay reads this call's keys and a resumed run replays the same orders
+  const int shuf_h = feistel_half_width(N);
+  if (shuffle) {
+    for (int e = 0; e < epochs; ++e) {
+      const uint64_t step0 = (uint64_t)(c->adam_step + (int64_t)e * M);
+      const uint64_t key = splitmix64(c->cfg.seed ^ splitmix64(((uint64_t)(uint32_t)c->rank << 40) ^ step0));
+      for (int r = 0; r < 4; ++r)
+        c->h_shuf_keys[4 * e + r] = (uint32_t)splitmix64(key + (uint64_t)r);
+    }
+    HIPCHK(c, hipMemcpyAsync(c->shuf_keys, c->h_shuf_keys, (size_t)epochs * 16, hipMemcpyHostToDevice, s));
+  }
 
   float *sW1 = c->slab + c->slab_off[0], *sB1 = c->slab + c->slab_off[1], *sW2 = c->slab + c->slab_off[2],
         *sB2 = c->slab + c->slab_off[3], *sW3 = c->slab + c->slab_off[4], *sB3 = c->slab + c->slab_off[5],
@@ -1245,18 +1308,33 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
   // Everything the update enqueues - mask counts, epochs x minibatches of forward / loss / backward / [all-reduce] /
   // clip / Adam, the metric reduction - as one function: run eagerly, or recorded once into a hipGraph and replayed.
   auto enqueue_update = [&]() -> int {
-  launch_mask_count(s, c->mask_n, c->mask_counts, B, M);
+  // Shuffled: the order of every epoch and the per-sample planes in that order ([epochs][N]); the minibatches then read
+  // them like the contiguous planes, and find their observations through SampleMap::idx.  Mask counts per (epoch, minibatch).
+  if (shuffle)
+    launch_shuffle_gather(s, c->shuf_keys, shuf_h, N, epochs, A, c->order, c->act_n, c->oldlp_n, c->adv_n, c->ret_n,
+                          c->mask_n, c->act_p, c->oldlp_p, c->adv_p, c->ret_p, c->mask_p, c->rt16);
+  const int ncounts = shuffle ? nm : M;
+  float *const counts = shuffle ? c->mask_counts_ep : c->mask_counts;
+  launch_mask_count(s, shuffle ? c->mask_p : c->mask_n, counts, B, ncounts);
   if (dp) // N_m of the masked mean is the GLOBAL count
-    NCCLCHK(c, ncclAllReduce(c->mask_counts, c->mask_counts, M, ncclFloat, ncclSum, comm, s));
+    NCCLCHK(c, ncclAllReduce(counts, counts, ncounts, ncclFloat, ncclSum, comm, s));
   for (int ep = 0; ep < epochs; ++ep)
-    for (int mb = 0; mb < M; ++mb) { // contiguous env-major slices; randperm unused (Q1)
+    for (int mb = 0; mb < M; ++mb) { // contiguous env-major slices unless shuffling (the reference's randperm is unused, Q1)
       const int mi = ep * M + mb;
       const long n0 = (long)mb * B;
-      const SampleMap map = train_map(c, n0);
+      SampleMap map = train_map(c, n0);
+      // the per-sample planes of this minibatch: position n0 + b of the batch, or of epoch ep's gathered planes
+      const size_t p0 = shuffle ? (size_t)ep * N + n0 : (size_t)n0;
+      const int *act = shuffle ? c->act_p : c->act_n;
+      void *oldlp = shuffle ? c->oldlp_p : c->oldlp_n, *adv = shuffle ? c->adv_p : c->adv_n,
+           *ret = shuffle ? c->ret_p : c->ret_n;
+      const uint8_t *mask = shuffle ? c->mask_p : c->mask_n;
+      if (shuffle)
+        map.idx = c->order + (size_t)ep * N;
       const int hparts = net_forward(c, c->obs, map, B, FC_FWD_MAX_PARTS);
       prof_begin(c, ALEPPO_K_HEAD);
-      launch_head_train(s, c->h, Pf(c, P_WH), Pf(c, P_BH), c->act_n + n0, rp(c, c->oldlp_n, (size_t)n0 * A),
-                        rp(c, c->adv_n, (size_t)n0), rp(c, c->ret_n, (size_t)n0), c->mask_n + n0, c->mask_counts + mb, hp,
+      launch_head_train(s, c->h, Pf(c, P_WH), Pf(c, P_BH), act + p0, rp(c, oldlp, p0 * A), rp(c, adv, p0),
+                        rp(c, ret, p0), mask + p0, counts + (shuffle ? mi : mb), hp,
                         c->dh, prec,
                         c->metric_ps + 0 * fs + (size_t)mi * B, c->metric_ps + 1 * fs + (size_t)mi * B,
                         c->metric_ps + 2 * fs + (size_t)mi * B, c->metric_ps + 3 * fs + (size_t)mi * B,
@@ -1389,7 +1467,10 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
                   c->cfg.adam_beta2, c->cfg.adam_eps, c->grad_norms + mi);
       prof_end(c, ALEPPO_K_ADAM);
     }
-  launch_metrics_reduce(s, c->metric_ps, fs, c->mask_n, B, M, epochs, c->metric_red);
+  if (shuffle) // (epoch ep's masks in its order: minibatch mi's are the mi-th B of mask_p)
+    launch_metrics_reduce(s, c->metric_ps, fs, c->mask_p, B, nm, 1, c->metric_red);
+  else
+    launch_metrics_reduce(s, c->metric_ps, fs, c->mask_n, B, M, epochs, c->metric_red);
   if (dp)
     NCCLCHK(c, ncclAllReduce(c->metric_red, c->metric_red, (size_t)nm * 8, ncclFloat, ncclSum, comm, s));
   return ALEPPO_OK;
@@ -1405,6 +1486,7 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
   key.N = N;
   key.metric_ps = c->metric_ps;
   key.metric_red = c->metric_red;
+  key.order = shuffle ? c->order : nullptr;
   const bool want_graph = c->update_graph && !dp && !c->prof_on;
   if (want_graph && c->graph_exec && c->graph_key == key) {
     HIPCHK(c, hipGraphLaunch(c->graph_exec, s));
@@ -1454,6 +1536,7 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
   c->last_epochs = epochs;
   c->last_M = M;
   c->last_B = B;
+  c->last_shuffled = shuffle;
   if (out)
     for (int i = 0; i < nm; ++i) {
       const float *r = c->h_metric_red + (size_t)i * 8;
@@ -1476,6 +1559,23 @@ extern "C" int aleppo_read_train_metric(aleppo_ctx *c, int field, float *dst, si
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "read_train_metric: bad field or count");
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, copy_sync(c, dst, c->metric_ps + (size_t)field * c->metric_cap, n * 4, hipMemcpyDeviceToHost));
+  return ALEPPO_OK;
+}
+
+extern "C" int aleppo_read_sample_order(aleppo_ctx *c, int32_t *dst, size_t count) {
+  CHECK_CTX(c);
+  const size_t N = (size_t)c->last_M * c->last_B, n = (size_t)c->last_epochs * N;
+  if (n == 0)
+    return set_err(c, ALEPPO_ERR_RUNTIME, "read_sample_order: no update has run yet");
+  if (!dst || count != n)
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "read_sample_order: count must be epochs * N of the last aleppo_train");
+  if (!c->last_shuffled) {
+    for (size_t i = 0; i < n; ++i)
+      dst[i] = (int32_t)(i % N);
+    return ALEPPO_OK;
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, copy_sync(c, dst, c->order, n * 4, hipMemcpyDeviceToHost));
   return ALEPPO_OK;
 }
 
@@ -1723,6 +1823,8 @@ extern "C" int aleppo_set_option(aleppo_ctx *c, int option, int value) {
     c->serial_update = value != 0;
   else if (option == ALEPPO_OPT_FORCE_COMM)
     c->force_comm = value != 0;
+  else if (option == ALEPPO_OPT_MINIBATCH_SHUFFLE)
+    c->shuffle = value != 0;
   else if (option == ALEPPO_OPT_UPDATE_GRAPH)
     c->update_graph = value != 0;
   else if (option == ALEPPO_OPT_GATE_TIMEOUT_MS)
@@ -1745,6 +1847,7 @@ extern "C" int aleppo_get_option(aleppo_ctx *c, int option, int64_t *value) {
   case ALEPPO_OPT_FUSED_FWD: *value = c->tune.fused_fwd; break;
   case ALEPPO_OPT_FUSED_BWD: *value = c->tune.fused_bwd; break;
   case ALEPPO_OPT_UPDATE_GRAPH: *value = c->graph_replays; break;
+  case ALEPPO_OPT_MINIBATCH_SHUFFLE: *value = c->shuffle; break;
   case ALEPPO_OPT_GATE_TIMEOUT_MS: *value = (int64_t)(c->gate_timeout_ticks / 100000ull); break;
   default: return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "unknown option");
   }

@@ -39,11 +39,20 @@ void params_to_internal(const ParamLayout &L, const float *ref, float *internal)
 void params_to_reference(const ParamLayout &L, const float *internal, float *ref);
 
 // sample n of a batch lives in obs slot  (n / TP) * s1 + (n % TP) * s0 + base   (units: u32 pixels)
+// idx != nullptr (ALEPPO_OPT_MINIBATCH_SHUFFLE): logical sample n is first replaced by idx[n].  The kernels that read
+// observations come in two instantiations, contiguous (IDX = false: idx is never read) and indexed, chosen by the launcher.
 struct SampleMap {
   int TP;
   long s1, s0, base;
   int n0; // first sample of this launch (minibatch offset)
+  const int32_t *idx = nullptr; // [n0 + ns] order of the launch's samples, or nullptr: contiguous
 };
+// u32-pixel offset of the stack of batch sample nn (n0 already added); IDX: nn goes through the order table first
+template <bool IDX> __device__ __forceinline__ long sample_off(const SampleMap &m, long nn) {
+  if constexpr (IDX)
+    nn = m.idx[nn];
+  return (nn / m.TP) * m.s1 + (nn % m.TP) * m.s0 + m.base;
+}
 
 struct ProfClass {
   std::vector<hipEvent_t> start, stop;
@@ -158,6 +167,17 @@ struct Ctx {
   float *metric_red = nullptr, *h_metric_red = nullptr;
   float *grad_norms = nullptr; // [mi]
   float *adam_sched = nullptr, *h_adam_sched = nullptr; // [mi][2] step scalars of one aleppo_train call (device / pinned)
+  // ---- ALEPPO_OPT_MINIBATCH_SHUFFLE: per-epoch sample order and the per-sample planes gathered into it ([epochs][N])
+  bool shuffle = false;
+  size_t shuf_cap = 0;        // samples (epochs * N) the buffers below hold
+  int shuf_epochs_cap = 0;    // epochs the key buffers hold
+  int32_t *order = nullptr;   // [epochs][N]
+  int *act_p = nullptr;
+  void *oldlp_p = nullptr, *adv_p = nullptr, *ret_p = nullptr; // RT [epochs][N][A], [epochs][N], [epochs][N]
+  uint8_t *mask_p = nullptr;
+  float *mask_counts_ep = nullptr; // [epochs * M] global unmasked count per (epoch, minibatch)
+  uint32_t *shuf_keys = nullptr, *h_shuf_keys = nullptr; // [epochs][4] Feistel round keys of one call (device / pinned)
+  bool last_shuffled = false;
   // ---- captured update (ALEPPO_OPT_UPDATE_GRAPH): the epochs x minibatches loop as one hipGraph, re-captured when
   // the shape (or a baked pointer) changes; the first call of a shape runs eagerly (one-time kernel attribute set-up)
   bool update_graph = false;
@@ -167,9 +187,10 @@ struct Ctx {
     int epochs = 0, M = 0, two = 0;
     long N = 0;
     const void *metric_ps = nullptr, *metric_red = nullptr;
+    const void *order = nullptr; // shuffled updates: the order / gathered-plane storage (nullptr: contiguous)
     bool operator==(const GraphKey &o) const {
       return epochs == o.epochs && M == o.M && two == o.two && N == o.N && metric_ps == o.metric_ps &&
-             metric_red == o.metric_red;
+             metric_red == o.metric_red && order == o.order;
     }
   } graph_key, warm_key;
   long graph_replays = 0;
@@ -224,6 +245,12 @@ void launch_adv_norm(hipStream_t s, void *adv_n, const uint8_t *mask_n, float *s
 void launch_plane_to_float(hipStream_t s, const void *src, float *dst, long n, bool rt16);
 void launch_plane_from_float(hipStream_t s, const float *src, void *dst, long n, bool rt16);
 void launch_mask_count(hipStream_t s, const uint8_t *mask_n, float *counts, long B, int M);
+// ALEPPO_OPT_MINIBATCH_SHUFFLE: order[e][i] = the keyed bijection of aleppo.h (round keys rk[e][4], domain 2^(2h)) and the
+// per-sample planes gathered into that order: act / oldlp / adv / ret / mask_p[e][i] = plane[order[e][i]]
+void launch_shuffle_gather(hipStream_t s, const uint32_t *rk, int h, long N, int epochs, int A, int32_t *order,
+                           const int *act_n, const void *oldlp_n, const void *adv_n, const void *ret_n,
+                           const uint8_t *mask_n, int *act_p, void *oldlp_p, void *adv_p, void *ret_p, uint8_t *mask_p,
+                           bool rt16);
 void launch_head_train(hipStream_t s, const float *h, const float *Wh, const float *bh, const int *act,
                        const void *oldlp, const void *adv, const void *ret, const uint8_t *mask,
                        const float *mask_count, Hyper hp, void *dh, int prec, float *ps_total, float *ps_clipped,

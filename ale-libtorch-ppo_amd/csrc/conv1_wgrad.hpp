@@ -46,6 +46,8 @@ constexpr size_t SMEM = SMEM_LOOP > SMEM_RED ? SMEM_LOOP : SMEM_RED;
 static_assert(X_ELEMS % 8 == 0 && BUF_ELEMS % 8 == 0, "16-byte aligned tiles");
 } // namespace c1w
 
+// IDX: the stacks are located through P.map.idx (SampleMap; ALEPPO_OPT_MINIBATCH_SHUFFLE)
+template <bool IDX = false>
 __global__ __launch_bounds__(c1w::NTHREADS) void conv1_wgrad_shift_kernel(WgradParams P) {
   using namespace c1w;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -78,7 +80,10 @@ __global__ __launch_bounds__(c1w::NTHREADS) void conv1_wgrad_shift_kernel(WgradP
     // conv kernels - cold or warm - it measured 3-8 us SLOWER per kernel (update 7.57-7.70 ms) and stays off there.
     auto gload = [&](Regs &R, long g) {
       g = min(g, ngroups - 1);
-      const uint32_t n = (uint32_t)(g >> 1) + (uint32_t)P.map.n0, tp = (uint32_t)P.map.TP;
+      uint32_t n = (uint32_t)(g >> 1) + (uint32_t)P.map.n0;
+      if constexpr (IDX)
+        n = (uint32_t)P.map.idx[n];
+      const uint32_t tp = (uint32_t)P.map.TP;
       const uint32_t q = n / tp, r = n - q * tp;
       const long off = (long)q * P.map.s1 + (long)r * P.map.s0 + P.map.base;
       const u32x4 *px = reinterpret_cast<const u32x4 *>(static_cast<const uint8_t *>(P.x) + off * 4 + (g & 1) * (long)GSTRIDE);

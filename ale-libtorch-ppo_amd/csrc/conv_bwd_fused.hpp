@@ -138,8 +138,8 @@ template <int NVM> struct FFWaitVm<NVM, 7> {
 };
 
 // ABL: timing-only ablations (wrong results): 1 no conv2 dgrad, 2 no conv2 wgrad, 4 no conv1 wgrad, 8 no staging stores, 16 no
-// widening
-template <int ABL>
+// widening.  IDX: the stacks are located through P.map.idx (WgIdx, conv_fwd_fused.hpp; ALEPPO_OPT_MINIBATCH_SHUFFLE)
+template <int ABL, bool IDX = false>
 __global__ __launch_bounds__(cb::NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void conv_bwd_fused_kernel(ConvBwdParams P) {
   using namespace cb;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -204,9 +204,16 @@ __global__ __launch_bounds__(cb::NT) __attribute__((amdgpu_waves_per_eu(1, 1))) 
     for (int i = 0; i < 7; ++i)
       asm volatile("global_load_dwordx4 %0, %1, off" : "=a"(RA[3 + i]) : "v"(pa + min(tid + NT * i, AV - 1)) : "memory");
   };
-  auto prefetch_x = [&](long m) {
-    const long nn = min(m, P.ns - 1) + P.map.n0;
-    const long off = (nn / P.map.TP) * P.map.s1 + (nn % P.map.TP) * P.map.s0 + P.map.base;
+  WgIdx<false> wi; // IDX: the indices of samples 64 c .. 64 c + 63 of this workgroup
+  int k = 0;  // IDX: this workgroup's sample counter (n = blockIdx.x + k gs)
+  auto prefetch_x = [&](long m, int km) { // km = m's sample counter
+    long nn;
+    if constexpr (IDX) {
+      nn = wi.at(km);
+    } else {
+      nn = min(m, P.ns - 1) + P.map.n0;
+    }
+    const long off = sample_off<false>(P.map, nn);
     const u32x4 *src = reinterpret_cast<const u32x4 *>(P.obs + off);
 #pragma unroll
     for (int i = 0; i < 7; ++i)
@@ -230,9 +237,11 @@ __global__ __launch_bounds__(cb::NT) __attribute__((amdgpu_waves_per_eu(1, 1))) 
   // ---- lane constants of the wgrad phases
   const int lrow = 4 * lg + (li >> 2), lcol = 4 * (li & 3); // row / first column a lane supplies to a transposed read
 
+  if constexpr (IDX)
+    wi.fetch(P.map, P.ns, 0, lane); // (before the first prefetch: nothing else is in flight)
   __syncthreads(); // dY tile zeroed
   prefetch_a(n);
-  prefetch_x(n);
+  prefetch_x(n, 0);
   auto pk = [](uint32_t lo, uint32_t hi) { return pack_u8_pair_bf16(lo, hi); };
 
   for (; n < P.ns; n += gs) {
@@ -414,7 +423,11 @@ __global__ __launch_bounds__(cb::NT) __attribute__((amdgpu_waves_per_eu(1, 1))) 
         }
       }
     }
-    prefetch_x(n + gs);
+    if constexpr (IDX)
+      if (((k + 1) & 63) == 0) // refill (drains the next sample's dz2 / a1 loads: once per 64 samples)
+        wi.fetch(P.map, P.ns, (k + 1) >> 6, lane);
+    prefetch_x(n + gs, k + 1);
+    ++k;
     __syncthreads();
     // =========================================================== P4: dW1 += sample n (this wave's 4 of the 16 k-steps)
     if constexpr (!(ABL & 4)) {

@@ -42,6 +42,32 @@ template <int N, class F> __device__ __forceinline__ void static_for(F &&f) {
   static_for_impl(f, std::make_integer_sequence<int, N>{});
 }
 
+// Sample indices of one persistent workgroup (the indexed instantiations of the fused kernels; SampleMap::idx).  Lane j of
+// every wave holds the stack index of the workgroup's sample 64 c + j (k-th sample = blockIdx.x + k gridDim.x, clamped to
+// the last one like the contiguous addresses); `at(k)` is a lane read - no memory operation where the pipelines count
+// their waits.  `fetch` waits for its load on the spot (the inline-assembly move below makes hipcc wait right there: the
+// value is never a pending load when the loop reads it), so it belongs where nothing else is in flight (kernel start) or
+// where draining costs only a refill every 64 samples.
+// AGPR: the lane vector lives in an accumulation register (the fused forward kernel has no architectural VGPR to spare
+// across its loop, the fused backward kernel no AGPR).
+template <bool AGPR> struct WgIdx {
+  int r;
+  __device__ __forceinline__ void fetch(const SampleMap &map, long ns, int c, int lane) {
+    const long k = (long)c * 64 + lane;
+    const int v = map.idx[map.n0 + min((long)blockIdx.x + k * (long)gridDim.x, ns - 1)];
+    if constexpr (AGPR)
+      asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(r) : "v"(v));
+    else
+      asm volatile("v_mov_b32 %0, %1" : "=v"(r) : "v"(v));
+  }
+  __device__ __forceinline__ long at(int k) const {
+    int v = r;
+    if constexpr (AGPR)
+      asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(r));
+    return __builtin_amdgcn_readlane(v, k & 63);
+  }
+};
+
 // Two 16-channel atoms (32 output channels) of layer L for one wave, in registers for the whole kernel.  Row fr of atom a is
 // output channel 32 og + (fr >> 2) * 8 + a * 4 + (fr & 3): lane (fr, fg) then leaves the two MFMAs with 8 CONSECUTIVE
 // channels 32 og + 8 fg + {0..7} - one 16-byte store (conv_patch_kernel's mapping).
@@ -171,7 +197,8 @@ constexpr size_t FWD_FUSED_SMEM = 160 * 1024;
 constexpr int FF_NT = 256; // 4 waves = one per SIMD: a wave may then use the whole 512-entry register file
 
 // ABL: timing-only ablations (wrong results): 1 no widening, 2 / 4 / 8 no conv1 / conv2 / conv3 phase, 16 no global stores
-template <int ABL>
+// IDX: the stacks are located through P.map.idx (WgIdx; ALEPPO_OPT_MINIBATCH_SHUFFLE)
+template <int ABL, bool IDX = false>
 __global__ __launch_bounds__(FF_NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void fwd_fused_kernel(FwdFusedParams P) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   typedef __attribute__((address_space(3))) uint8_t *lds_ptr;
@@ -197,15 +224,24 @@ __global__ __launch_bounds__(FF_NT) __attribute__((amdgpu_waves_per_eu(1, 1))) v
   long n = blockIdx.x;
   if (n >= P.ns)
     return;
-  auto load_obs = [&](long m) { // unconditional: sample and vector index clamped
-    const long nn = min(m, P.ns - 1) + P.map.n0;
-    const long off = (nn / P.map.TP) * P.map.s1 + (nn % P.map.TP) * P.map.s0 + P.map.base;
+  WgIdx<true> wi; // IDX: the indices of samples 64 c .. 64 c + 63 of this workgroup
+  int k = 0;  // IDX: this workgroup's sample counter (n = blockIdx.x + k gs)
+  auto load_obs = [&](long m, int km) { // unconditional: sample and vector index clamped; km = m's sample counter
+    long nn;
+    if constexpr (IDX) {
+      nn = wi.at(km);
+    } else {
+      nn = min(m, P.ns - 1) + P.map.n0;
+    }
+    const long off = sample_off<false>(P.map, nn);
     const u32x4 *src = reinterpret_cast<const u32x4 *>(P.obs + off);
 #pragma unroll
     for (int i = 0; i < NR; ++i)
       asm volatile("global_load_dwordx4 %0, %1, off" : "=a"(R[i]) : "v"(src + min(tid + FF_NT * i, NXV - 1)) : "memory");
   };
-  load_obs(n); // (first: its round trip to HBM runs under the weight set-up below)
+  if constexpr (IDX)
+    wi.fetch(P.map, P.ns, 0, lane); // (nothing else is in flight yet)
+  load_obs(n, 0); // (first: its round trip to HBM runs under the weight set-up below)
   { // ---- the three layers' weights: one coalesced copy per workgroup -> padded LDS image -> this wave's two atoms
     auto img_off = [](int v, int vpr, int pitch) { return (v / vpr) * pitch + (v % vpr) * 16; };
     W1.load_bias(P.b1, wave, lane);
@@ -261,7 +297,10 @@ __global__ __launch_bounds__(FF_NT) __attribute__((amdgpu_waves_per_eu(1, 1))) v
       }
     }
     __syncthreads(); // (also: every wave is done with conv3 of the previous sample - s2 may be rewritten two barriers on)
-    load_obs(n + gs);
+    if constexpr (IDX)
+      if (((k + 1) & 63) == 0) // refill: only the previous sample's stores are in flight (drained once per 64 samples)
+        wi.fetch(P.map, P.ns, (k + 1) >> 6, lane);
+    load_obs(n + gs, k + 1);
     if constexpr (!(ABL & 2)) {
       bf16 *g1 = P.a1 + n * (long)(400 * 32) + fg * 8;
       fused_phase<LConv1Full, true>(sx_addr, W1, 1.0f / 255.0f, wave, lane, [&](int q, u32x4 v) {
@@ -290,6 +329,7 @@ __global__ __launch_bounds__(FF_NT) __attribute__((amdgpu_waves_per_eu(1, 1))) v
                  : "+a"(R[0]), "+a"(R[1]), "+a"(R[2]), "+a"(R[3]), "+a"(R[4]), "+a"(R[5]), "+a"(R[6])
                  : "n"(NSTORES)
                  : "memory");
+    ++k;
   }
 }
 

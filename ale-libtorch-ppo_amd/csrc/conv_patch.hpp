@@ -127,7 +127,9 @@ __device__ __forceinline__ u32x2 pack4_bf16(float a, float b, float c, float d) 
 }
 __device__ __forceinline__ float bf16_bits_to_f32(uint32_t hi16) { return __uint_as_float(hi16 << 16); }
 
-template <class L, int NW> __global__ __launch_bounds__(64 * NW) void conv_patch_kernel(PatchParams P) {
+// IDX: conv1's stacks are located through P.map.idx (SampleMap; ALEPPO_OPT_MINIBATCH_SHUFFLE)
+template <class L, int NW, bool IDX = false>
+__global__ __launch_bounds__(64 * NW) void conv_patch_kernel(PatchParams P) {
   using InT = typename L::InT;
   constexpr bool U8 = sizeof(InT) == 1;
   constexpr int K = 32 * L::KS;
@@ -193,7 +195,7 @@ template <class L, int NW> __global__ __launch_bounds__(64 * NW) void conv_patch
         const int v = min(tid + NT * i, SRC_VECS - 1);
         if constexpr (U8) { // SB == 1: one half of a packed stack per group, located through the slot map
           const long n = n0 / L::GPS + P.map.n0;
-          const long off = (n / P.map.TP) * P.map.s1 + (n % P.map.TP) * P.map.s0 + P.map.base; // u32 pixels
+          const long off = sample_off<IDX>(P.map, n); // u32 pixels
           R[i] = reinterpret_cast<const u32x4 *>(static_cast<const uint8_t *>(P.in) + off * 4 +
                                                  (n0 % L::GPS) * (long)L::GSTRIDE)[v];
         } else {
@@ -210,7 +212,7 @@ template <class L, int NW> __global__ __launch_bounds__(64 * NW) void conv_patch
         if (v < SRC_VECS && grp < ngroups) {
           if constexpr (U8) {
             const long n = n0 / L::GPS + P.map.n0;
-            const long off = (n / P.map.TP) * P.map.s1 + (n % P.map.TP) * P.map.s0 + P.map.base; // u32 pixels
+            const long off = sample_off<IDX>(P.map, n); // u32 pixels
             R[i] = reinterpret_cast<const u32x4 *>(static_cast<const uint8_t *>(P.in) + off * 4 +
                                                    (n0 % L::GPS) * (long)L::GSTRIDE)[v];
           } else {

@@ -50,23 +50,27 @@ static bf16 *fwd_dummy() {
 }
 
 // NW waves per workgroup, WPC persistent workgroups per CU
-template <class L, int NW, int WPC> static void launch_patch(hipStream_t s, const PatchParams &P) {
+// IDX: the instantiation that locates conv1's stacks through P.map.idx
+template <class L, int NW, int WPC, bool IDX = false> static void launch_patch(hipStream_t s, const PatchParams &P) {
   static bool once = false;
   constexpr size_t sm = conv_patch_smem<L>();
   static_assert(sm * WPC <= 160 * 1024, "LDS budget per CU");
   if (!once) {
-    allow_smem(conv_patch_kernel<L, NW>, sm);
+    allow_smem(conv_patch_kernel<L, NW, IDX>, sm);
     once = true;
   }
   const long ngroups = (P.ns * L::GPS + L::SB - 1) / L::SB;
   const int grid = (int)std::min<long>(ngroups, (long)num_cus() * WPC);
-  hipLaunchKernelGGL((conv_patch_kernel<L, NW>), dim3(grid), dim3(64 * NW), sm, s, P);
+  hipLaunchKernelGGL((conv_patch_kernel<L, NW, IDX>), dim3(grid), dim3(64 * NW), sm, s, P);
 }
 
 void patch_conv1_fwd(hipStream_t s, const uint32_t *obs, SampleMap map, const void *W1, const float *b1, void *a1,
                      long ns) {
   PatchParams P{obs, static_cast<const bf16 *>(W1), b1, nullptr, static_cast<bf16 *>(a1), ns, map, 1.0f / 255.0f, fwd_dummy()};
-  launch_patch<LConv1Fwd, 8, 2>(s, P);
+  if (map.idx)
+    launch_patch<LConv1Fwd, 8, 2, true>(s, P);
+  else
+    launch_patch<LConv1Fwd, 8, 2>(s, P);
 }
 void patch_conv2_fwd(hipStream_t s, const void *a1, const void *W2, const float *b2, void *a2, long ns) {
   PatchParams P{a1, static_cast<const bf16 *>(W2), b2, nullptr, static_cast<bf16 *>(a2), ns, SampleMap{1, 0, 0, 0, 0},
@@ -84,13 +88,14 @@ void patch_conv3_fwd(hipStream_t s, const void *a2, const void *W3, const float 
   else
     launch_patch<LConv3Fwd1W4, 4, 2>(s, P);
 }
-template <int ABL> static void launch_fwd_fused(hipStream_t s, const FwdFusedParams &P) {
+template <int ABL, bool IDX = false> static void launch_fwd_fused(hipStream_t s, const FwdFusedParams &P) {
   static bool once = false;
   if (!once) {
-    allow_smem(fwd_fused_kernel<ABL>, FWD_FUSED_SMEM);
+    allow_smem(fwd_fused_kernel<ABL, IDX>, FWD_FUSED_SMEM);
     once = true;
   }
-  hipLaunchKernelGGL(fwd_fused_kernel<ABL>, dim3((unsigned)std::min<long>(P.ns, num_cus())), dim3(FF_NT), FWD_FUSED_SMEM, s, P);
+  hipLaunchKernelGGL((fwd_fused_kernel<ABL, IDX>), dim3((unsigned)std::min<long>(P.ns, num_cus())), dim3(FF_NT),
+                     FWD_FUSED_SMEM, s, P);
 }
 void patch_fwd_fused(hipStream_t s, const uint32_t *obs, SampleMap map, const void *W1, const float *b1, const void *W2,
                      const float *b2, const void *W3, const float *b3, void *a1, void *a2, void *a3, long ns) {
@@ -98,6 +103,8 @@ void patch_fwd_fused(hipStream_t s, const uint32_t *obs, SampleMap map, const vo
                    b1,  b2,  b3, static_cast<bf16 *>(a1), static_cast<bf16 *>(a2), static_cast<bf16 *>(a3), ns};
   // ALEPPO_FF_ABLATE: timing-only builds of the kernel with one part left out (wrong results)
   static const int abl = ablation_switch("ALEPPO_FF_ABLATE");
+  if (map.idx) // (the ablations are contiguous-only)
+    return launch_fwd_fused<0, true>(s, P);
   switch (abl) {
   case 1: return launch_fwd_fused<1>(s, P);
   case 2: return launch_fwd_fused<2>(s, P);
@@ -108,13 +115,13 @@ void patch_fwd_fused(hipStream_t s, const uint32_t *obs, SampleMap map, const vo
   default: return launch_fwd_fused<0>(s, P);
   }
 }
-template <int ABL> static void launch_conv_bwd(hipStream_t s, const ConvBwdParams &P, int grid) {
+template <int ABL, bool IDX = false> static void launch_conv_bwd(hipStream_t s, const ConvBwdParams &P, int grid) {
   static bool once = false;
   if (!once) {
-    allow_smem(conv_bwd_fused_kernel<ABL>, cb::SMEM);
+    allow_smem(conv_bwd_fused_kernel<ABL, IDX>, cb::SMEM);
     once = true;
   }
-  hipLaunchKernelGGL(conv_bwd_fused_kernel<ABL>, dim3(grid), dim3(cb::NT), cb::SMEM, s, P);
+  hipLaunchKernelGGL((conv_bwd_fused_kernel<ABL, IDX>), dim3(grid), dim3(cb::NT), cb::SMEM, s, P);
 }
 int patch_conv_bwd_fused(hipStream_t s, const void *dz2, const void *a1, const uint32_t *obs, SampleMap map, const void *W2d,
                          float *sw2, float *sb2, float *sw1, float *sb1, long ns) {
@@ -123,6 +130,10 @@ int patch_conv_bwd_fused(hipStream_t s, const void *dz2, const void *a1, const u
   const int grid = (int)std::min<long>(ns, std::min(num_cus(), std::min(MAXS_C1, MAXS_C2)));
   // ALEPPO_CB_ABLATE: timing-only builds of the kernel with one part left out (wrong results)
   static const int abl = ablation_switch("ALEPPO_CB_ABLATE");
+  if (map.idx) { // (the ablations are contiguous-only)
+    launch_conv_bwd<0, true>(s, P, grid);
+    return grid;
+  }
   switch (abl) {
   case 1: launch_conv_bwd<1>(s, P, grid); break;
   case 2: launch_conv_bwd<2>(s, P, grid); break;
@@ -217,11 +228,15 @@ int patch_conv1_wgrad(hipStream_t s, const void *dz1, const uint32_t *obs, Sampl
   WgradParams P{obs, static_cast<const bf16 *>(dz1), sw, sb, ns, map, 1.0f / 255.0f};
   static bool once = false;
   if (!once) {
-    allow_smem(conv1_wgrad_shift_kernel, c1w::SMEM);
+    allow_smem(conv1_wgrad_shift_kernel<false>, c1w::SMEM);
+    allow_smem(conv1_wgrad_shift_kernel<true>, c1w::SMEM);
     once = true;
   }
   const int grid = (int)std::min<long>(2 * ns, std::min(num_cus(), MAXS_C1));
-  hipLaunchKernelGGL(conv1_wgrad_shift_kernel, dim3(grid), dim3(c1w::NTHREADS), c1w::SMEM, s, P);
+  if (map.idx)
+    hipLaunchKernelGGL(conv1_wgrad_shift_kernel<true>, dim3(grid), dim3(c1w::NTHREADS), c1w::SMEM, s, P);
+  else
+    hipLaunchKernelGGL(conv1_wgrad_shift_kernel<false>, dim3(grid), dim3(c1w::NTHREADS), c1w::SMEM, s, P);
   return grid;
 }
 int patch_conv2_wgrad(hipStream_t s, const void *dz2, const void *a1, float *sw, float *sb, long ns) {

@@ -104,13 +104,15 @@ template <class T> struct DenseLoader {
 // One kh segment (KW*C elements) is contiguous in memory.  Sample n lives at
 //   x + (n / TP) * s1 + (n % TP) * s0 + base      (rollout buffer slots are [E][T+1])
 // InT = uint8_t reads the packed 4-frame stack (conv1) and widens to T.
-template <class T, class InT, int PIX, int OW, int STRIDE, int IW, int C, int KW> struct ConvGatherLoader {
+// IDX: sample n is first replaced by idx[n] (SampleMap::idx; ALEPPO_OPT_MINIBATCH_SHUFFLE)
+template <class T, class InT, int PIX, int OW, int STRIDE, int IW, int C, int KW, bool IDX = false> struct ConvGatherLoader {
   static constexpr int SEG = KW * C, PITCH = IW * C;
   struct P {
     const InT *x;
     int TP;
     long s1, s0, base;
     int n0;
+    const int32_t *idx; // IDX only
   };
   struct Row {
     long off;
@@ -121,7 +123,10 @@ template <class T, class InT, int PIX, int OW, int STRIDE, int IW, int C, int KW
     if (m >= M)
       return Row{0, false};
     const int nl = m / PIX, pix = m - nl * PIX, oy = pix / OW, ox = pix - oy * OW;
-    const int n = nl + p.n0, q = n / p.TP, r = n - q * p.TP;
+    int n = nl + p.n0;
+    if constexpr (IDX)
+      n = p.idx[n];
+    const int q = n / p.TP, r = n - q * p.TP;
     return Row{(long)q * p.s1 + (long)r * p.s0 + p.base + (long)((oy * STRIDE) * IW + ox * STRIDE) * C, true};
   }
   static __device__ __forceinline__ u32x4 load(const P &p, const Row &r, int k, int K) {

@@ -20,15 +20,18 @@ static inline dim3 grid2(long M, int BM, long N, int BN, int Z = 1) {
 }
 
 // ------------------------------------------------------------------ forward
-template <class T>
+template <class T, bool IDX = false>
 static void conv1_fwd_t(hipStream_t s, const uint32_t *obs, SampleMap map, const void *W1, const float *b1, void *a1,
                         long ns) {
+  if constexpr (!IDX)
+    if (map.idx)
+      return conv1_fwd_t<T, true>(s, obs, map, W1, b1, a1, ns);
   // A: packed u8 stack [84][84][4] per sample, 8x8 s4 window -> k = (kh, kw*4+c), 32 contiguous bytes per kh
-  using AL = ConvGatherLoader<T, uint8_t, 400, 20, 4, 84, 4, 8>;
+  using AL = ConvGatherLoader<T, uint8_t, 400, 20, 4, 84, 4, 8, IDX>;
   using BL = DenseLoader<T>;
   using EP = EpiBiasAct<T, true>;
   const long M = ns * 400;
-  typename AL::P ap{reinterpret_cast<const uint8_t *>(obs), map.TP, map.s1 * 4, map.s0 * 4, map.base * 4, map.n0};
+  typename AL::P ap{reinterpret_cast<const uint8_t *>(obs), map.TP, map.s1 * 4, map.s0 * 4, map.base * 4, map.n0, map.idx};
   typename BL::P bp{static_cast<const T *>(W1), 256, 0};
   typename EP::P ep{static_cast<T *>(a1), b1, 32, 1.0f / 255.0f}; // x/255 folded into the epilogue (train.cc:258-259)
   hipLaunchKernelGGL((gemm_nt_kernel<T, AL, BL, EP, 128, 32, 4, 1>), grid2(M, 128, 32, 32), dim3(256), 0, s, ap, bp,
@@ -406,18 +409,21 @@ template <class T> static int conv2_wgrad_t(hipStream_t s, const void *dz2, cons
                      sb, 64, 512, (int)K, kc, 1.0f, 0);
   return S;
 }
-template <class T>
+template <class T, bool IDX = false>
 static int conv1_wgrad_t(hipStream_t s, const void *dz1, const uint32_t *obs, SampleMap map, float *sw, float *sb,
                          long ns) {
+  if constexpr (!IDX)
+    if (map.idx)
+      return conv1_wgrad_t<T, true>(s, dz1, obs, map, sw, sb, ns);
   using AL = DenseLoader<T>;
-  using BL = ConvGatherLoader<T, uint8_t, 400, 20, 4, 84, 4, 8>;
+  using BL = ConvGatherLoader<T, uint8_t, 400, 20, 4, 84, 4, 8, IDX>;
   constexpr int KP = Atom<T>::KT;
   const long K = ns * 400;
   const dim3 g = grid2(32, 32, 256, 128);
   const int S = pick_slices(K, KP, g.x * g.y, MAXS_C1);
   const int kc = chunk_for(K, S, KP);
   typename AL::P ap{static_cast<const T *>(dz1), 32, 0};
-  typename BL::P bp{reinterpret_cast<const uint8_t *>(obs), map.TP, map.s1 * 4, map.s0 * 4, map.base * 4, map.n0};
+  typename BL::P bp{reinterpret_cast<const uint8_t *>(obs), map.TP, map.s1 * 4, map.s0 * 4, map.base * 4, map.n0, map.idx};
   hipLaunchKernelGGL((gemm_tn_kernel<T, AL, BL, 32, 128, 1, 4, true>), dim3(g.x, g.y, S), dim3(256), 0, s, ap, bp, sw,
                      sb, 32, 256, (int)K, kc, 1.0f / 255.0f, 0);
   return S;

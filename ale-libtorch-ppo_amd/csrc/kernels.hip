@@ -551,6 +551,80 @@ void launch_mask_count(hipStream_t s, const uint8_t *mask_n, float *counts, long
 }
 
 // ================================================================================================
+// Per-epoch minibatch shuffling (ALEPPO_OPT_MINIBATCH_SHUFFLE; the permutation is specified in aleppo.h).  One thread per
+// position i of epoch e = blockIdx.y: a four-round Feistel network on [0, 2^(2h)) walked until it lands in [0, N).  The
+// small per-sample planes are gathered into the new order (coalesced writes; oldlp's A elements per sample go through
+// LDS-held indices so that consecutive threads write consecutive elements).  The observations are NOT moved: the
+// update's kernels read them through SampleMap::idx = order[e].
+// ================================================================================================
+__device__ __forceinline__ uint32_t fmix32(uint32_t h) {
+  h ^= h >> 16;
+  h *= 0x85EBCA6Bu;
+  h ^= h >> 13;
+  h *= 0xC2B2AE35u;
+  h ^= h >> 16;
+  return h;
+}
+__device__ __forceinline__ uint32_t feistel4(uint32_t x, const uint32_t k[4], int h) {
+  const uint32_t mask = (1u << h) - 1u;
+  uint32_t L = x >> h, R = x & mask;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const uint32_t t = R;
+    R = L ^ (fmix32(R ^ k[r]) & mask);
+    L = t;
+  }
+  return (L << h) | R;
+}
+template <class RT>
+__global__ __launch_bounds__(256) void shuffle_gather_kernel(const uint32_t *__restrict__ rk, int h, long N, int A,
+                                                             int32_t *order, const int *__restrict__ act_n,
+                                                             const RT *__restrict__ oldlp_n, const RT *__restrict__ adv_n,
+                                                             const RT *__restrict__ ret_n,
+                                                             const uint8_t *__restrict__ mask_n, int *act_p, RT *oldlp_p,
+                                                             RT *adv_p, RT *ret_p, uint8_t *mask_p) {
+  __shared__ int sj[256];
+  const int e = blockIdx.y;
+  const long i0 = (long)blockIdx.x * 256, i = i0 + threadIdx.x;
+  const uint32_t k[4] = {rk[4 * e], rk[4 * e + 1], rk[4 * e + 2], rk[4 * e + 3]};
+  const size_t row = (size_t)e * N;
+  if (i < N) {
+    uint32_t y = feistel4((uint32_t)i, k, h);
+    while (y >= (uint32_t)N) // cycle-walking: the cycle through i returns to [0, N)
+      y = feistel4(y, k, h);
+    const long j = (long)y;
+    sj[threadIdx.x] = (int)j;
+    order[row + i] = (int32_t)j;
+    act_p[row + i] = act_n[j];
+    adv_p[row + i] = adv_n[j];
+    ret_p[row + i] = ret_n[j];
+    mask_p[row + i] = mask_n[j];
+  }
+  __syncthreads();
+  const long cnt = min(256L, N - i0);
+  for (long t = threadIdx.x; t < cnt * A; t += 256) {
+    const long s = t / A, a = t - s * A;
+    oldlp_p[(row + i0 + s) * A + a] = oldlp_n[(long)sj[s] * A + a];
+  }
+}
+void launch_shuffle_gather(hipStream_t s, const uint32_t *rk, int h, long N, int epochs, int A, int32_t *order,
+                           const int *act_n, const void *oldlp_n, const void *adv_n, const void *ret_n,
+                           const uint8_t *mask_n, int *act_p, void *oldlp_p, void *adv_p, void *ret_p, uint8_t *mask_p,
+                           bool rt16) {
+  const dim3 g((unsigned)((N + 255) / 256), (unsigned)epochs);
+  if (rt16)
+    hipLaunchKernelGGL(shuffle_gather_kernel<f16>, g, dim3(256), 0, s, rk, h, N, A, order, act_n,
+                       static_cast<const f16 *>(oldlp_n), static_cast<const f16 *>(adv_n),
+                       static_cast<const f16 *>(ret_n), mask_n, act_p, static_cast<f16 *>(oldlp_p),
+                       static_cast<f16 *>(adv_p), static_cast<f16 *>(ret_p), mask_p);
+  else
+    hipLaunchKernelGGL(shuffle_gather_kernel<float>, g, dim3(256), 0, s, rk, h, N, A, order, act_n,
+                       static_cast<const float *>(oldlp_n), static_cast<const float *>(adv_n),
+                       static_cast<const float *>(ret_n), mask_n, act_p, static_cast<float *>(oldlp_p),
+                       static_cast<float *>(adv_p), static_cast<float *>(ret_p), mask_p);
+}
+
+// ================================================================================================
 // PPO head, training.  Fuses: action/value linear layers (train.cc:245-253,262-263), normalize_logits
 // (losses.cc:45-47), losses::compute forward (losses.cc:4-26) with its closed-form backward (SURVEY
 // app. B: autograd's gradient of the masked-mean loss), the head dgrad (dh) and the head wgrad

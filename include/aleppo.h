@@ -224,14 +224,35 @@ int aleppo_replay_rollout(aleppo_ctx *ctx, const uint8_t *frames, int frame_kind
 int aleppo_finish_rollout(aleppo_ctx *ctx, const float *noise);
 
 /* ------------------------------------------------------------------ update (ai::ppo::train::train, train.h:133-157)
- * epochs x num_mini_batches contiguous env-major slices; per minibatch forward, loss, backward,
+ * epochs x num_mini_batches contiguous env-major slices (ALEPPO_OPT_MINIBATCH_SHUFFLE = 1: a fresh permutation per epoch,
+ * see aleppo_read_sample_order); per minibatch forward, loss, backward,
  * [RCCL all-reduce when world_size>1], clip_grad_norm_, Adam.  lr is this rollout's annealed rate
  * (train.cc:424-428).  out_metrics: [epochs*num_mini_batches], may be NULL.
  * ALEPPO_ERR_RUNTIME if E*T % num_mini_batches != 0 (train.h:140-143). */
 int aleppo_train(aleppo_ctx *ctx, double lr, int epochs, int num_mini_batches,
                  aleppo_minibatch_metrics *out_metrics);
-/* Per-sample metric tensors of the last aleppo_train, float [epochs,M,B]. */
+/* Per-sample metric tensors of the last aleppo_train, float [epochs,M,B], in the order of aleppo_read_sample_order:
+ * element [e][m][b] belongs to logical sample order[e][m*B + b]. */
 int aleppo_read_train_metric(aleppo_ctx *ctx, int metric_field, float *dst, size_t count);
+/* Sample order of the last aleppo_train, int32 [epochs][N] (count = epochs * N, N = the batch's sample count): row e,
+ * position m*B + b is the logical sample (n = e_env*T + t of the rollout, or row n of aleppo_set_batch) that sat at
+ * position b of minibatch m in epoch e.  Identity rows after a contiguous update; ALEPPO_ERR_RUNTIME before any update.
+ *
+ * With ALEPPO_OPT_MINIBATCH_SHUFFLE = 1 row e is the keyed bijection below, which any host can recompute (stateless,
+ * each position on its own; u32 / u64 arithmetic wraps):
+ *   splitmix64(x): z = x + 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *                  z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31)
+ *   fmix32(h):     h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16; return h
+ *   w = ceil(log2 N), at least 2, rounded up to an even number; h = w / 2; mask = 2^h - 1
+ *   step0 = the Adam step count when epoch e starts (the context's step at the call, + e * num_mini_batches; it is what
+ *           aleppo_export_optimizer / aleppo_import_optimizer carry, so a resumed run replays the same orders)
+ *   key = splitmix64(config.seed ^ splitmix64(((uint64)config.rank << 40) ^ step0))
+ *   k_r = (uint32) splitmix64(key + r), r = 0..3
+ *   P(x): L = x >> h, R = x & mask; for r = 0..3: (L, R) <- (R, L ^ (fmix32(R ^ k_r) & mask)); return (L << h) | R
+ *   order[e][i]: y = P(i); while (y >= N) y = P(y)      (cycle-walking on [0, 2^w))
+ * Each rank permutes its own N local samples (rank is in the key); a global minibatch is the union of the ranks'
+ * shuffled local minibatches. */
+int aleppo_read_sample_order(aleppo_ctx *ctx, int32_t *dst, size_t count);
 
 /* Same update on a caller-supplied batch (what ai::ppo::train::train takes: train.h:34-57, 133-137):
  * observations uint8 [N,4,84,84], actions int64 [N], old log-probs float [N,A], advantages, returns
@@ -331,9 +352,14 @@ typedef enum {
                                       keeps dz1 on the CU (bf16): 0 never (three launches on two streams: A/B, parity
                                       tests), 1 at minibatches of >= 2048 samples (default), 2 always; environment:
                                       ALEPPO_BWD_FUSED */
-  ALEPPO_OPT_UPDATE_GRAPH = 7      /* 1: capture the epochs x minibatches loop of aleppo_train in a hipGraph and replay it
+  ALEPPO_OPT_UPDATE_GRAPH = 7,     /* 1: capture the epochs x minibatches loop of aleppo_train in a hipGraph and replay it
                                       (capture_train_cuda_graph, src/ai/ppo/train.h:163-195); lr and the Adam bias
                                       corrections are device scalars, so a replay follows the annealed rate */
+  ALEPPO_OPT_MINIBATCH_SHUFFLE = 12 /* 0 (default): minibatch m of every epoch is the contiguous slice [m*B, (m+1)*B) of the
+                                      batch, like the reference (which draws randperm and never uses it, train.h:146).
+                                      1: every epoch of every aleppo_train uses a fresh permutation of the N local samples
+                                      (the keyed bijection documented at aleppo_read_sample_order), on every schedule -
+                                      eager or ALEPPO_OPT_UPDATE_GRAPH, fp32 or bf16, one GPU or data parallel */
 } aleppo_option;
 int aleppo_set_option(aleppo_ctx *ctx, int option, int value);
 /* Current value of an option; for ALEPPO_OPT_UPDATE_GRAPH the number of graph launches so far (0 = every update ran

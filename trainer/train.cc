@@ -69,6 +69,7 @@ struct Config {
   size_t num_rollouts = 7000, num_workers = 16, worker_batch_size = 32, frame_skip = 4;
   float max_return = -1.0f;
   bool record_observation = false, record_video = false, cuda_graph = false, deterministic = false;
+  bool shuffle_minibatches = false; // extension: a fresh sample permutation per epoch (ALEPPO_OPT_MINIBATCH_SHUFFLE)
   // extensions
   std::string precision = "fp32", rollout_precision = "fp32";
   bool device_preprocess = false; // emulators hand over raw frame pairs; gray LUT + resize + max run on the device (N2)
@@ -145,6 +146,7 @@ static Config load_config(const std::string &path) { // keys / defaults of src/b
   c.record_observation = as_bool(kv, "record_observation", false);
   c.record_video = as_bool(kv, "record_video", false);
   c.cuda_graph = as_bool(kv, "cuda_graph", false);
+  c.shuffle_minibatches = as_bool(kv, "shuffle_minibatches", false);
   c.deterministic = as_bool(kv, "deterministic", false);
   c.precision = as<std::string>(kv, "precision", "fp32");
   c.rollout_precision = as<std::string>(kv, "rollout_precision", "fp32");
@@ -786,8 +788,16 @@ int main(int argc, char **argv) {
     EventWriter logger(rank == 0 ? log_path : log_path + ".rank" + std::to_string(rank)); // rank 0's file is THE log
     if (cfg.cuda_graph) // the reference's `cuda_graph: true`: replay the update loop as a captured graph
       check(ctx, aleppo_set_option(ctx, ALEPPO_OPT_UPDATE_GRAPH, 1));
+    if (cfg.shuffle_minibatches) // extension: minibatches of a fresh per-epoch permutation instead of contiguous slices
+      check(ctx, aleppo_set_option(ctx, ALEPPO_OPT_MINIBATCH_SHUFFLE, 1));
     if (prof.on())
       check(ctx, aleppo_profile_enable(ctx, 1));
+    std::vector<std::pair<std::string, bool>> hparam_flags{{"record_observation", cfg.record_observation},
+                                                           {"record_video", cfg.record_video},
+                                                           {"cuda_graph", cfg.cuda_graph},
+                                                           {"deterministic", cfg.deterministic}};
+    if (cfg.shuffle_minibatches) // (only when set: the records of existing configs stay byte-identical)
+      hparam_flags.emplace_back("shuffle_minibatches", true);
     logger.add_hparams( // get_parameters (train.cc:76-105), same keys
         {{"total_environments", (double)cfg.total_environments}, {"hidden_size", (double)cfg.hidden_size},
          {"action_size", (double)cfg.action_size}, {"horizon", (double)cfg.horizon}, {"max_steps", (double)cfg.max_steps},
@@ -799,9 +809,7 @@ int main(int argc, char **argv) {
          {"num_rollouts", (double)cfg.num_rollouts}, {"num_workers", (double)cfg.num_workers},
          {"worker_batch_size", (double)cfg.worker_batch_size}, {"frame_skip", (double)cfg.frame_skip},
          {"max_return", cfg.max_return}},
-        {{"record_observation", cfg.record_observation}, {"record_video", cfg.record_video},
-         {"cuda_graph", cfg.cuda_graph}, {"deterministic", cfg.deterministic}},
-        group, (double)start_time * 1e-9);
+        hparam_flags, group, (double)start_time * 1e-9);
 
     // ---- Rollout host half (src/ai/rollout.cc)
     std::vector<SyntheticAtari> envs;
