@@ -420,6 +420,62 @@ void oracle_net_backward(const float *params, int H, int A, int N, const float *
   free(part);
 }
 
+/* ------------------------------------------------------------------ bf16 emulation (rounding points: oracle.h) */
+/* round-to-nearest-even to bf16, kept as fp32 - the device's (__bf16) cast; NaN -> the canonical quiet NaN */
+static inline float bf16r(float x) {
+  uint32_t u;
+  memcpy(&u, &x, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u)
+    u = 0x7fc00000u;
+  else
+    u = (u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u;
+  memcpy(&x, &u, 4);
+  return x;
+}
+void oracle_round_bf16(const float *in, float *out, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    out[i] = bf16r(in[i]);
+}
+/* the device's compute copy of the parameters: conv1-3 and fc weights bf16, biases and both heads fp32 */
+static float *bf16_compute_copy(const float *params, const size_t *po) {
+  float *pb = (float *)malloc(sizeof(float) * po[12]);
+  memcpy(pb, params, sizeof(float) * po[12]);
+  for (int k = 0; k <= 6; k += 2)
+    for (size_t i = po[k]; i < po[k + 1]; ++i)
+      pb[i] = bf16r(pb[i]);
+  return pb;
+}
+
+#define ACC double
+#define EMU(name) emu_##name##_d
+#include "oracle_bf16.inc"
+#undef ACC
+#undef EMU
+#define ACC float
+#define EMU(name) emu_##name##_f
+#include "oracle_bf16.inc"
+#undef ACC
+#undef EMU
+
+void oracle_net_forward_ex(const float *params, int H, int A, const uint8_t *obs, int N, float *logits, float *values,
+                           float *acts, int mode) {
+  if (mode == ORACLE_BF16)
+    emu_net_forward_d(params, H, A, obs, N, logits, values, acts);
+  else if (mode == ORACLE_BF16_F32SUM)
+    emu_net_forward_f(params, H, A, obs, N, logits, values, acts);
+  else
+    oracle_net_forward(params, H, A, obs, N, logits, values, acts);
+}
+void oracle_net_backward_ex(const float *params, int H, int A, int N, const float *acts, const float *dlogits,
+                            const float *dvalues, float *grads, int mode) {
+  if (mode == ORACLE_BF16)
+    emu_net_backward_d(params, H, A, N, acts, dlogits, dvalues, grads);
+  else if (mode == ORACLE_BF16_F32SUM)
+    emu_net_backward_f(params, H, A, N, acts, dlogits, dvalues, grads);
+  else
+    oracle_net_backward(params, H, A, N, acts, dlogits, dvalues, grads);
+}
+
 /* ------------------------------------------------------------------ PPO loss: src/ai/ppo/losses.cc:4-43 */
 float oracle_ppo_loss(const float *logits, const float *old_logp, const int64_t *actions, const float *adv,
                       const float *values, const float *returns, const uint8_t *masks, int B, int A, float clip,
@@ -506,11 +562,11 @@ void oracle_adam_step(float *p, const float *g, float *m, float *v, size_t n, do
 }
 
 /* ------------------------------------------------------------------ train loop: src/ai/ppo/train.h:114-157 */
-int oracle_train(float *params, float *adam_m, float *adam_v, int64_t *adam_step, int H, int A, const uint8_t *obs,
+int oracle_train_ex(float *params, float *adam_m, float *adam_v, int64_t *adam_step, int H, int A, const uint8_t *obs,
                  const int64_t *actions, const float *old_logp, const float *adv, const float *returns,
                  const uint8_t *masks, int N, int epochs, int M, double lr, float clip, float c_v, float c_e,
                  float max_norm, float *loss, float *grad_norm, float *total_losses, float *ratio, float *entropies,
-                 float *value_losses, float *clipped, float *last_grads) {
+                 float *value_losses, float *clipped, float *last_grads, int mode) {
   if (N % M != 0)
     return -1; /* train.h:140-143 */
   const int B = N / M;
@@ -524,13 +580,13 @@ int oracle_train(float *params, float *adam_m, float *adam_v, int64_t *adam_step
   for (int ep = 0; ep < epochs; ++ep)
     for (int k = 0; k < M; ++k) { /* contiguous slices, randperm unused (Q1) */
       const size_t s = (size_t)k * B, mi = (size_t)ep * M + k;
-      oracle_net_forward(params, H, A, obs + s * X0, B, logits, values, acts);
+      oracle_net_forward_ex(params, H, A, obs + s * X0, B, logits, values, acts, mode);
       loss[mi] = oracle_ppo_loss(
           logits, old_logp + s * A, actions + s, adv + s, values, returns + s, masks + s, B, A, clip, c_v, c_e, 0.0f,
           clipped ? clipped + mi * B : NULL, value_losses ? value_losses + mi * B : NULL,
           entropies ? entropies + mi * B : NULL, total_losses ? total_losses + mi * B : NULL,
           ratio ? ratio + mi * B : NULL, dlogits, dvalues);
-      oracle_net_backward(params, H, A, B, acts, dlogits, dvalues, grads);
+      oracle_net_backward_ex(params, H, A, B, acts, dlogits, dvalues, grads, mode);
       grad_norm[mi] = oracle_clip_grad_norm(grads, H, A, max_norm);
       *adam_step += 1;
       oracle_adam_step(params, grads, adam_m, adam_v, np, lr, 0.9, 0.999, 1e-5, *adam_step);
@@ -544,6 +600,16 @@ int oracle_train(float *params, float *adam_m, float *adam_v, int64_t *adam_step
   free(dvalues);
   free(grads);
   return 0;
+}
+
+int oracle_train(float *params, float *adam_m, float *adam_v, int64_t *adam_step, int H, int A, const uint8_t *obs,
+                 const int64_t *actions, const float *old_logp, const float *adv, const float *returns,
+                 const uint8_t *masks, int N, int epochs, int M, double lr, float clip, float c_v, float c_e,
+                 float max_norm, float *loss, float *grad_norm, float *total_losses, float *ratio, float *entropies,
+                 float *value_losses, float *clipped, float *last_grads) {
+  return oracle_train_ex(params, adam_m, adam_v, adam_step, H, A, obs, actions, old_logp, adv, returns, masks, N, epochs,
+                         M, lr, clip, c_v, c_e, max_norm, loss, grad_norm, total_losses, ratio, entropies, value_losses,
+                         clipped, last_grads, ORACLE_FP32);
 }
 
 /* ------------------------------------------------------------------ advantage normalisation

@@ -79,6 +79,73 @@ int oracle_train(float *params, float *adam_m, float *adam_v, int64_t *adam_step
                  const uint8_t *masks, int N, int epochs, int M, double lr, float clip, float c_v, float c_e,
                  float max_norm, float *loss, float *grad_norm, float *total_losses, float *ratio, float *entropies,
                  float *value_losses, float *clipped, float *last_grads);
+/* ---------------------------------------------------------------- bf16 emulation
+ * mode ORACLE_FP32 (0): the functions above, bit for bit.  ORACLE_BF16 (1): the exact model of the bf16 update /
+ * acting path - operands rounded to bf16 (round-to-nearest-even, the device's (__bf16) casts) where the device STORES
+ * bf16 and nowhere else, every sum before a rounding point taken in double, results kept as fp32.  ORACLE_BF16_F32SUM
+ * (2): the same rounding points with sequential fp32 sums - a second summation order, used only to measure how far
+ * summation order alone moves the results (the floor under the GPU bounds, tests/test_oracle_bf16.py).
+ *
+ * Rounding points, checked against the kernels of every route (paths below ale-libtorch-ppo_amd/csrc/):
+ *
+ *  quantity              | device storage / arithmetic                                  | emulation
+ *  ----------------------+--------------------------------------------------------------+---------------------------
+ *  conv1-3, fc weights   | bf16 compute copy of the fp32 master: cast_params_kernel      | W_b = bf16(W)
+ *                        | kernels.hip:1270-1273, adam_kernel kernels.hip:1206 / 1232;  |
+ *                        | dgrad layouts W3d / W2d kernels.hip:1284 / 1289, WfcT        |
+ *                        | kernels.hip:1301 - all (T) casts of the same fp32 value      |
+ *  biases, action/value  | fp32: load_bias conv_patch.hpp:474, EpiBiasAct gemm.hpp:196, | no rounding
+ *  heads                 | fwd_fused W.br conv_fwd_fused.hpp:167; head_train_kernel     |
+ *                        | kernels.hip:713-724 and infer_head_kernel kernels.hip:183-252 |
+ *                        | read fp32 Wh / bh                                            |
+ *  observations          | u8, widened exactly (gemm.hpp:55-75); 1/255 is conv1's fp32  | x = byte value;
+ *                        | epilogue scale (conv_fwd_fused.hpp:306, conv_patch_launch.hip:| a1 = bf16(relu(S/255 + b1))
+ *                        | 69, conv_patch.hpp:656, gemm_launch.hip:36) and the scale of  | dW1 = (1/255) sum dz1_b x
+ *                        | conv1's weight-gradient slabs (conv1_wgrad.hpp:239,          |
+ *                        | conv_bwd_fused.hpp:539, gemm_launch.hip:428)                 |
+ *  a1, a2, a3            | bf16 after scale, bias, ReLU: fused conv_fwd_fused.hpp:167;  | bf16(relu(S*scale + b))
+ *                        | three launches conv_patch.hpp:357-360; acting                |
+ *                        | conv_patch.hpp:504-505; generic gemm.hpp:196-199             |
+ *  h (fc output)         | fp32 split-K slabs summed in head_train_kernel               | none (fp32)
+ *                        | kernels.hip:666-673 / infer_head_kernel kernels.hip:219-230  |
+ *  logits, value, loss,  | fp32 (kernels.hip:710-790)                                   | none; the loss and its
+ *  planes, dlogits/dvalue|                                                              | gradient are oracle_ppo_loss
+ *  dh                    | bf16: head_train_kernel kernels.hip:822 `dr[i] = (T)d[i]`    | dh_b = bf16(Wh^T dz)
+ *  dz3                   | bf16 gated by the stored bf16 a3 > 0: pipelined fc dgrad     | bf16((a3 > 0) Wfc_b^T dh_b)
+ *                        | gemm_pipe.hpp:302-310; small-tile / generic EpiDgrad         |
+ *                        | gemm.hpp:250-252                                             |
+ *  dz2                   | bf16 gated by a2 > 0: conv3_dgrad_tile_kernel                | bf16((a2 > 0) W3_b^T dz3_b)
+ *                        | conv3_tile.hpp:131-143; patch dgrad conv_patch.hpp:372-379;  |
+ *                        | generic gemm.hpp:250-252                                     |
+ *  dz1                   | bf16 gated by a1 > 0: fused tail (LDS only)                  | bf16((a1 > 0) W2_b^T dz2_b)
+ *                        | conv_bwd_fused.hpp:313-321; three launches                   |
+ *                        | conv_patch.hpp:372-379; generic gemm.hpp:250-252             |
+ *  conv / fc weight and  | fp32 accumulation of the bf16 operands into fp32 slabs; the  | double sums of the rounded
+ *  bias gradients        | bias gradient is the column sum of the SAME bf16 dz operand  | dz / dh (bias included)
+ *                        | on every route: gemm_tn_kernel gemm.hpp:479 / 636, patch     |
+ *                        | wgrad conv_patch.hpp:893 / 953, conv1 wgrad                  |
+ *                        | conv1_wgrad.hpp:191, fused tail conv_bwd_fused.hpp:483       |
+ *  head weight / bias    | fp32 from the fp32 dz and fp32 h: kernels.hip:817 / 834      | none
+ *  gradients             |                                                              |
+ *  clip, Adam, masters   | fp32                                                         | unchanged (mode-free)
+ *
+ * Every route - fused / three-launch forward, fused / three-launch backward tail, pipelined / small-tile fc, patch /
+ * generic convs, shuffled / contiguous minibatches - rounds at the same points, so one model covers all of them: no
+ * per-route switch is needed (the sweep in tests/test_gpu_bf16_emulated.py checks each against this model).
+ * Activations saved for the backward pass (acts) hold x0 as raw byte values in the emulated modes. */
+#define ORACLE_FP32 0
+#define ORACLE_BF16 1
+#define ORACLE_BF16_F32SUM 2
+void oracle_round_bf16(const float *in, float *out, size_t n);
+void oracle_net_forward_ex(const float *params, int H, int A, const uint8_t *obs, int N, float *logits, float *values,
+                           float *acts, int mode);
+void oracle_net_backward_ex(const float *params, int H, int A, int N, const float *acts, const float *dlogits,
+                            const float *dvalues, float *grads, int mode);
+int oracle_train_ex(float *params, float *adam_m, float *adam_v, int64_t *adam_step, int H, int A, const uint8_t *obs,
+                    const int64_t *actions, const float *old_logp, const float *adv, const float *returns,
+                    const uint8_t *masks, int N, int epochs, int M, double lr, float clip, float c_v, float c_e,
+                    float max_norm, float *loss, float *grad_norm, float *total_losses, float *ratio, float *entropies,
+                    float *value_losses, float *clipped, float *last_grads, int mode);
 /* advantage normalisation over unmasked samples - an extension with NO reference counterpart:
  * PARITY UNPINNED, see oracle.c.  returns the unmasked count. */
 long oracle_adv_norm(float *adv, const uint8_t *masks, long n);

@@ -17,8 +17,8 @@ def lib():
     global _LIB
     if _LIB is None:
         path = os.path.join(ROOT, "oracle", "liboracle.so")
-        src = os.path.join(ROOT, "oracle", "oracle.c")
-        if not os.path.exists(path) or os.path.getmtime(path) < os.path.getmtime(src):
+        srcs = [os.path.join(ROOT, "oracle", f) for f in ("oracle.c", "oracle.h", "oracle_bf16.inc")]
+        if not os.path.exists(path) or os.path.getmtime(path) < max(os.path.getmtime(s) for s in srcs):
             subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle")])
         _LIB = C.CDLL(path)
         _LIB.oracle_param_count.restype = C.c_size_t
@@ -30,6 +30,26 @@ def lib():
 
 def _p(a, t):
     return None if a is None else a.ctypes.data_as(C.POINTER(t))
+
+
+# precision modes of the *_ex entry points (oracle.h): fp32, the exact bf16 model (double sums before every rounding
+# point), the same rounding points with sequential fp32 sums (only to measure the effect of a summation order)
+FP32, BF16, BF16_F32SUM = 0, 1, 2
+
+
+def _mode(emulate_bf16, sums):
+    if not emulate_bf16:
+        return FP32
+    assert sums in ("double", "float32"), sums
+    return BF16 if sums == "double" else BF16_F32SUM
+
+
+def round_bf16(x):
+    """round-to-nearest-even to bf16, returned as float32 (the oracle's rounding helper)"""
+    x = cf(x)
+    out = np.empty_like(x)
+    lib().oracle_round_bf16(_p(x, C.c_float), _p(out, C.c_float), C.c_size_t(x.size))
+    return out
 
 
 def c8(a):
@@ -133,22 +153,24 @@ def sample(probs, q):
     return a
 
 
-def net_forward(params, H, A, obs, want_acts=False):
+def net_forward(params, H, A, obs, want_acts=False, emulate_bf16=False, sums="double"):
+    """emulate_bf16: the bf16 model of oracle.h (sums: "double" = exact, "float32" = sequential fp32 sums)"""
     params, obs = cf(params), c8(obs)
     N = obs.shape[0]
     logits = np.zeros((N, A), np.float32)
     values = np.zeros(N, np.float32)
     acts = np.zeros((N, lib().oracle_acts_per_sample(H)), np.float32) if want_acts else None
-    lib().oracle_net_forward(_p(params, C.c_float), H, A, _p(obs, C.c_uint8), N, _p(logits, C.c_float),
-                             _p(values, C.c_float), _p(acts, C.c_float))
+    lib().oracle_net_forward_ex(_p(params, C.c_float), H, A, _p(obs, C.c_uint8), N, _p(logits, C.c_float),
+                                _p(values, C.c_float), _p(acts, C.c_float), _mode(emulate_bf16, sums))
     return (logits, values, acts) if want_acts else (logits, values)
 
 
-def net_backward(params, H, A, acts, dlogits, dvalues):
+def net_backward(params, H, A, acts, dlogits, dvalues, emulate_bf16=False, sums="double"):
     params, acts, dlogits, dvalues = cf(params), cf(acts), cf(dlogits), cf(dvalues)
     g = np.zeros(param_count(H, A), np.float32)
-    lib().oracle_net_backward(_p(params, C.c_float), H, A, acts.shape[0], _p(acts, C.c_float),
-                              _p(dlogits, C.c_float), _p(dvalues, C.c_float), _p(g, C.c_float))
+    lib().oracle_net_backward_ex(_p(params, C.c_float), H, A, acts.shape[0], _p(acts, C.c_float),
+                                 _p(dlogits, C.c_float), _p(dvalues, C.c_float), _p(g, C.c_float),
+                                 _mode(emulate_bf16, sums))
     return g
 
 
@@ -194,8 +216,9 @@ def adam_step(p, g, m, v, lr, step, beta1=0.9, beta2=0.999, eps=1e-5):
 
 
 def train(params, H, A, obs, actions, old_logp, adv, returns, masks, epochs, M, lr=2.5e-4, clip=0.1, c_v=0.5,
-          c_e=0.01, max_norm=0.5, adam=None):
-    """returns dict(params, loss[e,M], grad_norm[e,M], per-sample [e,M,B] arrays, last_grads, adam)"""
+          c_e=0.01, max_norm=0.5, adam=None, emulate_bf16=False, sums="double"):
+    """returns dict(params, loss[e,M], grad_norm[e,M], per-sample [e,M,B] arrays, last_grads, adam).
+    emulate_bf16: the network in the bf16 model of oracle.h (sums: "double" = exact, "float32" = fp32 sums)."""
     params = cf(params).copy()
     obs = c8(obs)
     N = obs.shape[0]
@@ -211,13 +234,14 @@ def train(params, H, A, obs, actions, old_logp, adv, returns, masks, epochs, M, 
     loss = np.zeros((epochs, M), np.float32)
     gn = np.zeros((epochs, M), np.float32)
     lg = np.zeros_like(params)
-    rc = lib().oracle_train(_p(params, C.c_float), _p(m, C.c_float), _p(v, C.c_float), C.byref(step), H, A,
+    rc = lib().oracle_train_ex(_p(params, C.c_float), _p(m, C.c_float), _p(v, C.c_float), C.byref(step), H, A,
                             _p(obs, C.c_uint8), _p(actions, C.c_int64), _p(old_logp, C.c_float), _p(adv, C.c_float),
                             _p(returns, C.c_float), _p(masks, C.c_uint8), N, epochs, M, C.c_double(lr),
                             C.c_float(clip), C.c_float(c_v), C.c_float(c_e), C.c_float(max_norm),
                             _p(loss, C.c_float), _p(gn, C.c_float), _p(out["total_losses"], C.c_float),
                             _p(out["ratio"], C.c_float), _p(out["entropies"], C.c_float),
-                            _p(out["value_losses"], C.c_float), _p(out["clipped"], C.c_float), _p(lg, C.c_float))
+                            _p(out["value_losses"], C.c_float), _p(out["clipped"], C.c_float), _p(lg, C.c_float),
+                            _mode(emulate_bf16, sums))
     if rc:
         raise RuntimeError("Batch size must be divisible by num_mini_batches")
     out.update(params=params, loss=loss, grad_norm=gn, last_grads=lg, adam=dict(m=m, v=v, step=step.value))

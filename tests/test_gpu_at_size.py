@@ -19,6 +19,7 @@ import time
 import numpy as np
 import pytest
 
+import bf16_check as bc
 import hashfill as hf
 import oracle_lib as orc
 from __graft_entry__ import load_package
@@ -186,7 +187,7 @@ def test_bf16_update_at_benched_size_vs_oracle(pkg, A):
     for step, epochs, resync in ((1, 1, False), (3, 2, False), (4, 1, True)):
         if resync:
             eng.load_state_dict(dict(params=wparams, exp_avg=adam["m"], exp_avg_sq=adam["v"], step=adam["step"]))
-        before = wparams
+        before, adam_before = wparams, adam
         m = eng.train(lr, epochs, 1)
         w = orc.train(wparams, H, A, obs, actions, old_lp, adv, ret, masks, epochs, 1, lr=lr, adam=adam)
         adam, wparams = w["adam"], w["params"]
@@ -196,11 +197,12 @@ def test_bf16_update_at_benched_size_vs_oracle(pkg, A):
         check(f"step{step}_loss", np.max(np.abs(m["loss"] - w["loss"]) - 1e-2 * np.abs(w["loss"])), 3e-2)
         check(f"step{step}_grad_norm_rel", np.max(np.abs(m["grad_norm"] / w["grad_norm"] - 1)), 5e-2)
         np.testing.assert_array_equal(m["mask_count"], np.full_like(m["mask_count"], masks.sum()))
+        planes = {}
         # per-sample metric planes (Metrics::set, train.h:93-108): |error| <= 5e-2 + 5 % of the value on every sample
         # (value losses reach ~4 here: a 3e-2 error of v moves 0.5 (v - R)^2 by |v - R| * 3e-2), 1e-2 on the mean
         for ours, ref in (("total_losses", "total_losses"), ("ratio", "ratio"), ("entropies", "entropies"),
                           ("value_losses", "value_losses"), ("clipped_losses", "clipped")):
-            got = eng.read_train_metric(ours, epochs, 1, N)
+            got = planes[ours] = eng.read_train_metric(ours, epochs, 1, N)
             err = np.abs(got - w[ref])
             check(f"step{step}_{ours}_excess", np.max(err - 5e-2 * np.abs(w[ref])), 5e-2)
             check(f"step{step}_{ours}_mean_excess", err.mean() - 2e-2 * np.abs(w[ref]).mean(), 1e-2)
@@ -211,10 +213,14 @@ def test_bf16_update_at_benched_size_vs_oracle(pkg, A):
         # measured on MI355X: 0.4-1.7 % per tensor on identical parameters, 1.3-2.3 % over all tensors on separate
         # trajectories
         if same:
-            # (the action head after three updates: a small-norm sum of policy-gradient terms that nearly cancel, measured
-            # 4.3 / 6.4 % for its weight / bias on identical parameters - bound 1e-1 there, 3e-2 everywhere else)
+            # (the action head at step 4: 4.3 / 6.4 % from the fp32 oracle for its weight / bias at A = 4 on identical
+            # parameters.  The emulated oracle shows that gap is bf16 quantisation, not a kernel error: the emulation
+            # itself is 4.3 / 6.4 % (A = 4) and 2.6 / 2.3 % (A = 6) from the fp32 oracle there
+            # (step4_emu_vs_fp32_grad_action.*, printed in the report) while the engine is within 2.1e-4 of the
+            # emulation (step4_emu_grad_action.*, bound bf16_check.BOUNDS["grad"]).  So 1e-1 stays on the fp32
+            # comparison of the action head after step 1 only as that quantisation envelope; 3e-2 elsewhere)
             for k, nm in enumerate(names):
-                bound = 1e-1 if step > 1 and nm.startswith("action") else 3e-2
+                bound = 1e-1 if step > 1 and nm.startswith("action") else 3e-2  # quantisation envelope (see above)
                 check(f"step{step}_grad_{nm}_rel", _rel(g[offs[k]:offs[k + 1]] / c0, wg[offs[k]:offs[k + 1]] / cw), bound)
             check(f"step{step}_grad_all_rel", _rel(g / c0, wg / cw), 2e-2)
         else:  # separate trajectories: only the whole gradient, loosely (measured 1.3-2.3 %)
@@ -222,6 +228,17 @@ def test_bf16_update_at_benched_size_vs_oracle(pkg, A):
         # parameters: Adam's first steps move every weight by ~lr whatever the gradient's size, so a bf16 sign flip of
         # a near-zero gradient entry costs up to 2 lr per step: bound 2.5 lr * steps on the max, lr / 5 * steps on the mean
         p = eng.export_params()
+        if same:  # the same step against the bf16-emulating oracle, on the same parameters and Adam state
+            we = bc.emulated_train(before, H, A, obs, actions, old_lp, adv, ret, masks, epochs, 1, lr=lr,
+                                   adam=adam_before)
+            c = bc.Checker()
+            c.train(H, A, m, planes, g, we, params0=before, params=p)
+            report.update({f"step{step}_emu_{k}": v for k, v in c.report.items()})
+            bad.extend((f"step{step}_emu_{k}", v, b) for k, v, b in c.failures)
+            ce = min(1.0, 0.5 / (float(we["grad_norm"][-1, -1]) + 1e-6))
+            for k in (8, 9):  # how far bf16 quantisation alone moves the action head (report only)
+                report[f"step{step}_emu_vs_fp32_grad_{names[k]}"] = _rel(we["last_grads"][offs[k]:offs[k + 1]] / ce,
+                                                                         wg[offs[k]:offs[k + 1]] / cw)
         d = np.abs(p - wparams)
         drift = 1 if resync else step  # optimizer steps since the two sides last had identical parameters
         check(f"step{step}_param_maxabs_over_lr", d.max() / lr, 2.5 * drift)
@@ -842,6 +859,17 @@ def test_fp16_rollout_buffer_mixed_precision_vs_oracle(pkg):
     cw = min(1.0, 0.5 / (float(w["grad_norm"][-1, -1]) + 1e-6))
     c0 = min(1.0, 0.5 / (float(m["grad_norm"][-1, -1]) + 1e-6))
     assert _rel(g / c0, wg / cw) < 3e-2
+    # and against the bf16-emulating oracle on the same half planes (forward of the acting path, the update)
+    c = bc.Checker()
+    c.forward(b["logits"].reshape(E * T, A), b["values"].ravel(),
+              bc.emulated_forward(params, H, A, obs_em.reshape(E * T, 4, 84, 84)), "act_")
+    we = bc.emulated_train(params, H, A, obs_em.reshape(E * T, 4, 84, 84), b["actions"].ravel(),
+                           b["log_probs"].reshape(E * T, A), b["advantages"].ravel(), b["returns"].ravel(),
+                           b["masks"].ravel(), 1, 1)
+    planes = {ours: eng.read_train_metric(ours, 1, 1, E * T) for ours, _ in bc.PLANES}
+    c.train(H, A, m, planes, g, we, params0=params, params=eng.export_params())
+    print(c.summary("fp16-rollout bf16 vs emulated oracle"))
+    assert not c.failures, c.failures
     dev.free()
     eng.close()
 

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import bf16_check as bc
 import hashfill as hf
 import oracle_lib as orc
 from conftest import GAE_KATS, gae_kat_expected
@@ -196,6 +197,10 @@ def test_forward_bf16_close(pkg, golden):
     logits, values = eng.forward(hf.hf_bytes(301, (8, 4, 84, 84)))
     np.testing.assert_allclose(logits, golden[f"g3_H{H}_A{A}_logits"], atol=3e-2)
     np.testing.assert_allclose(values, golden[f"g3_H{H}_A{A}_values"], atol=3e-2)
+    # and the bf16-emulating oracle at the tight bounds of bf16_check.py
+    c = bc.Checker()
+    c.forward(logits, values, bc.emulated_forward(hf.fill_params(310, H, A), H, A, hf.hf_bytes(301, (8, 4, 84, 84))))
+    assert not c.failures, c.failures
     eng.close()
 
 
@@ -275,6 +280,13 @@ def test_train_vs_oracle(pkg, prec, H, A, N, M):
         np.testing.assert_allclose(eng.export_params(), w["params"], atol=1e-4)
         g, wg = eng.export_grads(), w["last_grads"]
         np.testing.assert_allclose(g, wg, atol=1e-5 + 2e-3 * np.abs(wg).max())
+    else:  # bf16: every minibatch's loss / norm / planes and the whole update against the bf16-emulating oracle
+        we = bc.emulated_train(params, H, A, obs, actions, old_lp, adv, ret, masks, 2, M)
+        c = bc.Checker()
+        planes = {ours: eng.read_train_metric(ours, 2, M, N // M) for ours, _ in bc.PLANES}
+        c.train(H, A, m, planes, None, we, params0=params, params=eng.export_params())
+        print(c.summary(f"train bf16 H={H} A={A} vs emulated oracle"))
+        assert not c.failures, c.failures
     eng.close()
 
 
@@ -302,6 +314,18 @@ def test_bf16_patch_kernels_match_generic_kernels(pkg, N):
         m = eng.train(2.5e-4, 1, M)
         res[generic] = (logits, values, m, eng.export_grads(), eng.export_params())
         eng.close()
+    # each route on its own against the bf16-emulating oracle (two kernels that share a mistake agree with each other):
+    # forward, both minibatches' loss / norm, the update; the exported gradients belong to the second minibatch, i.e. to
+    # parameters that already differ by one step's rounding, where a 100-sample minibatch's clip states can flip - the
+    # gradients themselves are compared on identical parameters in test_gpu_bf16_emulated.py
+    we = bc.emulated_train(params, H, A, obs, actions, old_lp, adv, ret, masks, 1, M)
+    ef = bc.emulated_forward(params, H, A, obs[:77])
+    for generic, (lg, vl, mm, gg, pp) in res.items():
+        c = bc.Checker()
+        c.forward(lg, vl, ef)
+        c.train(H, A, mm, {}, None, we, params0=params, params=pp)
+        print(c.summary(f"generic={generic} N={N} vs emulated oracle"))
+        assert not c.failures, (generic, c.failures)
     (l1, v1, m1, g1, p1), (l0, v0, m0, g0, p0) = res[1], res[0]
     np.testing.assert_allclose(l0, l1, atol=2e-3)
     np.testing.assert_allclose(v0, v1, atol=2e-3)
@@ -410,9 +434,22 @@ def test_bf16_conv1_weight_gradient_ragged_sizes(pkg, N, M):
         eng.load_params(params)
         eng.set_batch(obs, actions, old_lp, adv, ret, masks)
         m = eng.train(2.5e-4, 1, M)
-        res[generic] = (eng.export_grads(), m["grad_norm"])
+        res[generic] = (eng.export_grads(), m)
         eng.close()
-    (g1, n1), (g0, n0) = res[1], res[0]
+    # each route against the bf16-emulating oracle, per tensor and per channel, where the exported gradients belong to
+    # the first step (M = 1: identical parameters); with M = 2 the first minibatch's gradient norm
+    we = bc.emulated_train(params, H, A, obs, actions, old_lp, adv, ret, masks, 1, M)
+    for generic, (g, m) in res.items():
+        c = bc.Checker()
+        if M == 1:
+            c.train(H, A, m, {}, g, we)
+        else:  # the first minibatch's loss and norm (the engine's metrics, both sides on identical parameters)
+            first = {k: m[k][:, :1] for k in ("loss", "grad_norm")}
+            c.train(H, A, first, {}, None, dict(loss=we["loss"][:, :1], grad_norm=we["grad_norm"][:, :1],
+                                                floor_run={k: we["floor_run"][k][:, :1] for k in ("loss", "grad_norm")}))
+        assert not c.failures, (generic, c.failures)
+    (g1, m1), (g0, m0) = res[1], res[0]
+    n1, n0 = m1["grad_norm"], m0["grad_norm"]
     np.testing.assert_allclose(n0, n1, rtol=5e-3)
     for k, name in ((0, "conv1.w"), (1, "conv1.b")):
         a, b = g0[offs[k]:offs[k + 1]], g1[offs[k]:offs[k + 1]]
@@ -445,6 +482,13 @@ def test_bf16_pipelined_fc_gemms_match_small_tile_kernels(pkg, N, M, H):
         m = eng.train(2.5e-4, 2, M)
         res[pipe] = (m, eng.export_grads(), eng.export_params())
         eng.close()
+    # each route against the bf16-emulating oracle: every minibatch's loss and norm, the update of 2 * M steps
+    we = bc.emulated_train(params, H, A, obs, actions, old_lp, adv, ret, masks, 2, M)
+    for pipe, (mm, gg, pp) in res.items():
+        c = bc.Checker()
+        c.train(H, A, mm, {}, None, we, params0=params, params=pp)
+        print(c.summary(f"fc pipe={pipe} N={N} H={H} vs emulated oracle"))
+        assert not c.failures, (pipe, c.failures)
     (m0, g0, p0), (m1, g1, p1) = res[0], res[1]
     np.testing.assert_allclose(m1["loss"], m0["loss"], rtol=2e-3, atol=2e-3)
     np.testing.assert_allclose(m1["grad_norm"], m0["grad_norm"], rtol=5e-3)
@@ -638,6 +682,10 @@ def test_bf16_acting_path_close_to_oracle(pkg):
     wl, wv = orc.net_forward(params, H, A, np.stack(obs_all, 1).reshape(E * T, 4, 84, 84))
     np.testing.assert_allclose(logits.reshape(E * T, A), wl, atol=3e-2)
     np.testing.assert_allclose(values.ravel(), wv, atol=3e-2)
+    c = bc.Checker()  # and the bf16-emulating oracle at the tight bounds of bf16_check.py
+    c.forward(logits.reshape(E * T, A), values.ravel(),
+              bc.emulated_forward(params, H, A, np.stack(obs_all, 1).reshape(E * T, 4, 84, 84)))
+    assert not c.failures, c.failures
     want = orc.sample(orc.softmax(logits.reshape(E * T, A)), np.stack(noises, 1).reshape(E * T, A))
     np.testing.assert_array_equal(np.stack(acts, 1).ravel(), want)
     eng.close()
@@ -673,6 +721,12 @@ def test_rccl_path_at_benched_size_with_one_rank_communicator(pkg):
         np.testing.assert_array_equal(out[0][0][k], out[1][0][k])
     np.testing.assert_array_equal(out[0][1], out[1][1])
     np.testing.assert_array_equal(out[0][2], out[1][2])
+    # the three-launch tail at B = 4096 against the bf16-emulating oracle: every minibatch's loss / norm, the update
+    we = bc.emulated_train(params, H, A, obs, actions, old_lp, adv, ret, masks, 2, M)
+    c = bc.Checker()
+    c.train(H, A, out[1][0], {}, None, we, params0=params, params=out[1][1])
+    print(c.summary("data-parallel schedule B=4096 vs emulated oracle"))
+    assert not c.failures, c.failures
 
 
 @pytest.mark.parametrize("prec", ["bf16"])  # one precision: the 1-rank communicator init alone takes ~60 s
