@@ -36,7 +36,10 @@ UNIQUE_ID_BYTES = 128
 
 FIELDS = dict(observations=0, actions=1, rewards=2, masks=3, logits=4, values=5, advantages=6, returns=7,
               log_probs=8, terminals=9, truncations=10, current_obs=11, next_values=12)
-METRIC_FIELDS = dict(total_losses=0, clipped_losses=1, value_losses=2, entropies=3, ratio=4)
+METRIC_FIELDS = dict(total_losses=0, clipped_losses=1, value_losses=2, entropies=3, ratio=4, approx_kl=5,
+                     clip_fraction=6)
+# the [epochs, M] masked means of approx_kl / clip_fraction (aleppo_read_train_metric; Engine.train_diagnostics)
+METRIC_MEAN_FIELDS = dict(approx_kl=7, clip_fraction=8)
 KERNEL_CLASSES = dict(ingest=0, gae=1, head=2, adam=3, conv1_fwd=4, conv2_fwd=5, conv3_fwd=6, fc_fwd=7, fc_dgrad=8,
                       fc_wgrad=9, conv3_dgrad=10, conv3_wgrad=11, conv2_dgrad=12, conv2_wgrad=13, conv1_wgrad=14,
                       reduce=15, infer_head=16, act_fused=17, conv_fwd=18, conv_bwd=19)
@@ -49,6 +52,7 @@ OPT_GATE_TIMEOUT_MS = 9
 OPT_FUSED_FWD = 10
 OPT_FUSED_BWD = 11
 OPT_MINIBATCH_SHUFFLE = 12
+OPT_VALUE_CLIP = 13
 
 EXPORTS = [
     "aleppo_abi_version", "aleppo_create", "aleppo_destroy", "aleppo_last_error", "aleppo_param_count",
@@ -60,7 +64,7 @@ EXPORTS = [
     "aleppo_profile_reset", "aleppo_synchronize", "aleppo_set_option", "aleppo_export_optimizer",
     "aleppo_import_optimizer", "aleppo_replay_rollout", "aleppo_get_option",
     "aleppo_host_alloc", "aleppo_host_free", "aleppo_arm_step", "aleppo_release_step", "aleppo_device_check",
-    "aleppo_read_sample_order",
+    "aleppo_read_sample_order", "aleppo_set_batch_values",
 ]
 
 
@@ -403,6 +407,16 @@ class Engine:
         self._c(lib().aleppo_read_train_metric(self._ctx, METRIC_FIELDS[name], _ptr(out), C.c_size_t(out.size)))
         return out
 
+    def train_diagnostics(self, epochs, M):
+        """{"approx_kl", "clip_fraction"}: float32 [epochs, M] masked means of the last train (aleppo.h: the k3
+        approx-KL estimator and the strict clip fraction, over the global unmasked count)"""
+        out = {}
+        for name, field in METRIC_MEAN_FIELDS.items():
+            a = np.zeros((epochs, M), np.float32)
+            self._c(lib().aleppo_read_train_metric(self._ctx, field, _ptr(a), C.c_size_t(a.size)))
+            out[name] = a
+        return out
+
     def sample_order(self, epochs):
         """aleppo_read_sample_order: int32 [epochs, N], row e = the logical samples of epoch e in minibatch order
         (identity rows after a contiguous update)."""
@@ -410,12 +424,20 @@ class Engine:
         self._c(lib().aleppo_read_sample_order(self._ctx, _ptr(out), C.c_size_t(out.size)))
         return out
 
-    def set_batch(self, observations, actions, log_probabilities, advantages, returns, masks):
+    def set_batch(self, observations, actions, log_probabilities, advantages, returns, masks, values=None):
+        """values: the values the batch was collected with (aleppo_set_batch_values), for OPT_VALUE_CLIP"""
         obs = _u8(observations)
         self._c(lib().aleppo_set_batch(self._ctx, _ptr(obs), _ptr(_i64(actions)), _ptr(_f32(log_probabilities)),
                                        _ptr(_f32(advantages)), _ptr(_f32(returns)), _ptr(_u8(masks)),
                                        C.c_int64(obs.shape[0])))
         self._batch_n = obs.shape[0]
+        if values is not None:
+            self.set_batch_values(values)
+
+    def set_batch_values(self, values, n=None):
+        """aleppo_set_batch_values: float [n] old values of the batch of the last set_batch (n defaults to its size)"""
+        v = _f32(values).ravel()
+        self._c(lib().aleppo_set_batch_values(self._ctx, _ptr(v), C.c_int64(v.size if n is None else n)))
 
     def forward(self, observations):
         obs = _u8(observations)

@@ -507,7 +507,7 @@ extern "C" void aleppo_destroy(aleppo_ctx *c) {
                  c->dz2,   c->dz3,      c->h,         c->hpart,     c->dh,        c->logits_b,   c->values_b, c->slab,
                  c->sumsq_part, c->metric_ps, c->metric_red, c->grad_norms, c->adv_stats, c->stage_u8, c->stage_obs,
                  c->adam_sched, c->rb_tmp[0], c->rb_tmp[1], c->order, c->act_p, c->oldlp_p, c->adv_p,
-                 c->ret_p,  c->mask_p,   c->mask_counts_ep, c->shuf_keys};
+                 c->ret_p,  c->mask_p,   c->mask_counts_ep, c->shuf_keys, c->val_n, c->val_p};
   for (void *p : dev)
     if (p)
       hipFree(p);
@@ -1124,6 +1124,8 @@ extern "C" int aleppo_finish_rollout(aleppo_ctx *c, const float *noise) {
   c->pre_acted = -1;
   c->need_carry = true;
   c->batch_n = c->N;
+  c->caller_batch = false;
+  c->val_src = Ctx::VAL_ROLLOUT; // (values_tm; any values supplied for a caller batch are forgotten)
   if (*c->h_err)
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT,
                    "Episode starts, terminals, and truncations must be mutually exclusive."); // gae.cc:49-53
@@ -1136,7 +1138,7 @@ static int ensure_metric_storage(aleppo_ctx *c, int epochs, int M, long B) {
   if (need > c->metric_cap) {
     retire(c, c->metric_ps); // (never hipFree before aleppo_destroy: see dalloc)
     c->metric_ps = nullptr;
-    HIPCHK(c, dalloc(&c->metric_ps, need * 5 * 4, c->stream));
+    HIPCHK(c, dalloc(&c->metric_ps, need * 7 * 4, c->stream)); // aleppo_metric_field 0-6
     c->metric_cap = need;
   }
   const size_t nm = (size_t)epochs * M;
@@ -1162,13 +1164,13 @@ static int ensure_metric_storage(aleppo_ctx *c, int epochs, int M, long B) {
 static int ensure_shuffle_storage(aleppo_ctx *c, int epochs, long N) {
   const size_t ns = (size_t)epochs * N;
   if (ns > c->shuf_cap || epochs > c->shuf_epochs_cap) {
-    for (void *p : {(void *)c->order, (void *)c->act_p, c->oldlp_p, c->adv_p, c->ret_p, (void *)c->mask_p,
+    for (void *p : {(void *)c->order, (void *)c->act_p, c->oldlp_p, c->adv_p, c->ret_p, c->val_p, (void *)c->mask_p,
                     (void *)c->mask_counts_ep, (void *)c->shuf_keys})
       retire(c, p);
     retire_host(c, c->h_shuf_keys);
     c->order = nullptr;
     c->act_p = nullptr;
-    c->oldlp_p = c->adv_p = c->ret_p = nullptr;
+    c->oldlp_p = c->adv_p = c->ret_p = c->val_p = nullptr;
     c->mask_p = nullptr;
     c->mask_counts_ep = nullptr;
     c->shuf_keys = c->h_shuf_keys = nullptr;
@@ -1179,6 +1181,7 @@ static int ensure_shuffle_storage(aleppo_ctx *c, int epochs, long N) {
     HIPCHK(c, dalloc(&c->oldlp_p, ns * c->A * c->rsz, c->stream));
     HIPCHK(c, dalloc(&c->adv_p, ns * c->rsz, c->stream));
     HIPCHK(c, dalloc(&c->ret_p, ns * c->rsz, c->stream));
+    HIPCHK(c, dalloc(&c->val_p, ns * c->rsz, c->stream));
     HIPCHK(c, dalloc(&c->mask_p, ns, c->stream));
     HIPCHK(c, dalloc(&c->mask_counts_ep, ns * 4, c->stream)); // (epochs * M <= epochs * N counts)
     HIPCHK(c, dalloc(&c->shuf_keys, (size_t)epochs * 16, c->stream));
@@ -1186,6 +1189,13 @@ static int ensure_shuffle_storage(aleppo_ctx *c, int epochs, long N) {
     c->shuf_cap = ns;
     c->shuf_epochs_cap = epochs;
   }
+  return ALEPPO_OK;
+}
+
+// ALEPPO_OPT_VALUE_CLIP: the env-major old-values plane, RT [E*T] (allocated on first use, never moved: graphs bake it)
+static int ensure_val_storage(aleppo_ctx *c) {
+  if (!c->val_n)
+    HIPCHK(c, dalloc(&c->val_n, (size_t)c->N * c->rsz, c->stream));
   return ALEPPO_OK;
 }
 
@@ -1229,12 +1239,20 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "num_mini_batches > 4096");
   if (c->world > 1 && !c->nccl_comm)
     return set_err(c, ALEPPO_ERR_RUNTIME, "world_size > 1 but aleppo_comm_init was not called");
+  const bool vclip = c->value_clip;
+  if (vclip && c->val_src == Ctx::VAL_NONE)
+    return set_err(c, ALEPPO_ERR_RUNTIME,
+                   "ALEPPO_OPT_VALUE_CLIP needs the batch's old values: call aleppo_set_batch_values after aleppo_set_batch");
   int rc = ensure_metric_storage(c, epochs, M, B);
   if (rc)
     return rc;
   const bool shuffle = c->shuffle;
   if (shuffle && (rc = ensure_shuffle_storage(c, epochs, N)))
     return rc;
+  if (vclip && (rc = ensure_val_storage(c)))
+    return rc;
+  // a rollout batch's old values are slots 0..T-1 of values_tm ([T+1][E], time-major): transposed inside the update
+  const bool val_transpose = vclip && c->val_src == Ctx::VAL_ROLLOUT;
   ncclComm_t comm = static_cast<ncclComm_t>(c->nccl_comm);
   const bool dp = c->world > 1 || (c->nccl_comm && c->force_comm); // force_comm: 1-rank communicator (tests)
   // side streams, created on first use (see aleppo_create): the weight-gradient stream, and - only with data parallelism -
@@ -1308,11 +1326,14 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
   // Everything the update enqueues - mask counts, epochs x minibatches of forward / loss / backward / [all-reduce] /
   // clip / Adam, the metric reduction - as one function: run eagerly, or recorded once into a hipGraph and replayed.
   auto enqueue_update = [&]() -> int {
+  if (val_transpose) // (ALEPPO_OPT_VALUE_CLIP on a rollout batch) values_tm [T][E] -> val_n [E][T]
+    launch_transpose_tm_pitched(s, c->values_tm, (size_t)c->E * c->rsz, c->val_n, c->E, c->T, 1, (int)c->rsz);
   // Shuffled: the order of every epoch and the per-sample planes in that order ([epochs][N]); the minibatches then read
   // them like the contiguous planes, and find their observations through SampleMap::idx.  Mask counts per (epoch, minibatch).
   if (shuffle)
     launch_shuffle_gather(s, c->shuf_keys, shuf_h, N, epochs, A, c->order, c->act_n, c->oldlp_n, c->adv_n, c->ret_n,
-                          c->mask_n, c->act_p, c->oldlp_p, c->adv_p, c->ret_p, c->mask_p, c->rt16);
+                          vclip ? c->val_n : nullptr, c->mask_n, c->act_p, c->oldlp_p, c->adv_p, c->ret_p, c->val_p,
+                          c->mask_p, c->rt16);
   const int ncounts = shuffle ? nm : M;
   float *const counts = shuffle ? c->mask_counts_ep : c->mask_counts;
   launch_mask_count(s, shuffle ? c->mask_p : c->mask_n, counts, B, ncounts);
@@ -1327,18 +1348,19 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
       const size_t p0 = shuffle ? (size_t)ep * N + n0 : (size_t)n0;
       const int *act = shuffle ? c->act_p : c->act_n;
       void *oldlp = shuffle ? c->oldlp_p : c->oldlp_n, *adv = shuffle ? c->adv_p : c->adv_n,
-           *ret = shuffle ? c->ret_p : c->ret_n;
+           *ret = shuffle ? c->ret_p : c->ret_n, *vold = vclip ? (shuffle ? c->val_p : c->val_n) : nullptr;
       const uint8_t *mask = shuffle ? c->mask_p : c->mask_n;
       if (shuffle)
         map.idx = c->order + (size_t)ep * N;
       const int hparts = net_forward(c, c->obs, map, B, FC_FWD_MAX_PARTS);
       prof_begin(c, ALEPPO_K_HEAD);
       launch_head_train(s, c->h, Pf(c, P_WH), Pf(c, P_BH), act + p0, rp(c, oldlp, p0 * A), rp(c, adv, p0),
-                        rp(c, ret, p0), mask + p0, counts + (shuffle ? mi : mb), hp,
+                        rp(c, ret, p0), vold ? rp(c, vold, p0) : nullptr, mask + p0, counts + (shuffle ? mi : mb), hp,
                         c->dh, prec,
                         c->metric_ps + 0 * fs + (size_t)mi * B, c->metric_ps + 1 * fs + (size_t)mi * B,
                         c->metric_ps + 2 * fs + (size_t)mi * B, c->metric_ps + 3 * fs + (size_t)mi * B,
-                        c->metric_ps + 4 * fs + (size_t)mi * B, sWh, sBh, nblk_head, B, H, A, nullptr, nullptr, hparts,
+                        c->metric_ps + 4 * fs + (size_t)mi * B, c->metric_ps + 5 * fs + (size_t)mi * B,
+                        c->metric_ps + 6 * fs + (size_t)mi * B, sWh, sBh, nblk_head, B, H, A, nullptr, nullptr, hparts,
                         c->rt16);
       prof_end(c, ALEPPO_K_HEAD);
       HIPCHK(c, fork(c->ev_head)); // dh is ready
@@ -1487,6 +1509,7 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
   key.metric_ps = c->metric_ps;
   key.metric_red = c->metric_red;
   key.order = shuffle ? c->order : nullptr;
+  key.vclip = vclip ? 1 + c->val_src : 0;
   const bool want_graph = c->update_graph && !dp && !c->prof_on;
   if (want_graph && c->graph_exec && c->graph_key == key) {
     HIPCHK(c, hipGraphLaunch(c->graph_exec, s));
@@ -1554,8 +1577,20 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
 
 extern "C" int aleppo_read_train_metric(aleppo_ctx *c, int field, float *dst, size_t count) {
   CHECK_CTX(c);
+  if (field == ALEPPO_M_MEAN_APPROX_KL || field == ALEPPO_M_MEAN_CLIP_FRACTION) {
+    // masked means [epochs, M] from the reduced records aleppo_train brought back (slots 6 / 7 over the count, slot 5)
+    const size_t nm = (size_t)c->last_epochs * c->last_M;
+    if (!dst || count != nm || nm == 0)
+      return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "read_train_metric: count must be epochs * M of the last aleppo_train");
+    const int slot = field == ALEPPO_M_MEAN_APPROX_KL ? 6 : 7;
+    for (size_t i = 0; i < nm; ++i) {
+      const float *r = c->h_metric_red + i * 8;
+      dst[i] = r[slot] / r[5];
+    }
+    return ALEPPO_OK;
+  }
   const size_t n = (size_t)c->last_epochs * c->last_M * c->last_B;
-  if (!dst || field < 0 || field > 4 || count != n || n == 0)
+  if (!dst || field < 0 || field > ALEPPO_M_CLIP_FRACTION || count != n || n == 0)
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "read_train_metric: bad field or count");
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, copy_sync(c, dst, c->metric_ps + (size_t)field * c->metric_cap, n * 4, hipMemcpyDeviceToHost));
@@ -1636,6 +1671,33 @@ extern "C" int aleppo_set_batch(aleppo_ctx *c, const uint8_t *observations, cons
   HIPCHK(c, copy_sync(c, c->mask_n, masks, (size_t)n, hipMemcpyHostToDevice));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->batch_n = n;
+  c->caller_batch = true;
+  c->val_src = Ctx::VAL_NONE; // (values supplied for an earlier batch are forgotten)
+  return ALEPPO_OK;
+}
+
+extern "C" int aleppo_set_batch_values(aleppo_ctx *c, const float *values, int64_t n) {
+  CHECK_CTX(c);
+  if (!values)
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "null argument");
+  if (!c->caller_batch)
+    return set_err(c, ALEPPO_ERR_RUNTIME, "set_batch_values: no caller batch (call aleppo_set_batch first)");
+  if (n != c->batch_n)
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "set_batch_values: n must be the n of the last aleppo_set_batch");
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  int rc = ensure_val_storage(c);
+  if (rc)
+    return rc;
+  if (!c->rt16) {
+    HIPCHK(c, copy_sync(c, c->val_n, values, (size_t)n * 4, hipMemcpyHostToDevice));
+  } else { // half plane: upload as float into the (idle) metric scratch area, round on the device (as aleppo_set_batch)
+    if ((rc = ensure_metric_storage(c, 1, 1, (long)n)))
+      return rc;
+    HIPCHK(c, copy_sync(c, c->metric_ps, values, (size_t)n * 4, hipMemcpyHostToDevice));
+    launch_plane_from_float(c->stream, c->metric_ps, c->val_n, (long)n, true);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  c->val_src = Ctx::VAL_CALLER;
   return ALEPPO_OK;
 }
 
@@ -1825,7 +1887,11 @@ extern "C" int aleppo_set_option(aleppo_ctx *c, int option, int value) {
     c->force_comm = value != 0;
   else if (option == ALEPPO_OPT_MINIBATCH_SHUFFLE)
     c->shuffle = value != 0;
-  else if (option == ALEPPO_OPT_UPDATE_GRAPH)
+  else if (option == ALEPPO_OPT_VALUE_CLIP) {
+    if (value != 0 && value != 1)
+      return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "ALEPPO_OPT_VALUE_CLIP: 0 (off) or 1 (clip at config.clip_param)");
+    c->value_clip = value != 0;
+  } else if (option == ALEPPO_OPT_UPDATE_GRAPH)
     c->update_graph = value != 0;
   else if (option == ALEPPO_OPT_GATE_TIMEOUT_MS)
     c->gate_timeout_ticks = (unsigned long long)std::max(1, value) * 100000ull; // 100 MHz wall clock
@@ -1848,6 +1914,7 @@ extern "C" int aleppo_get_option(aleppo_ctx *c, int option, int64_t *value) {
   case ALEPPO_OPT_FUSED_BWD: *value = c->tune.fused_bwd; break;
   case ALEPPO_OPT_UPDATE_GRAPH: *value = c->graph_replays; break;
   case ALEPPO_OPT_MINIBATCH_SHUFFLE: *value = c->shuffle; break;
+  case ALEPPO_OPT_VALUE_CLIP: *value = c->value_clip; break;
   case ALEPPO_OPT_GATE_TIMEOUT_MS: *value = (int64_t)(c->gate_timeout_ticks / 100000ull); break;
   default: return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "unknown option");
   }
@@ -2142,16 +2209,16 @@ extern "C" int aleppo_ppo_loss(int dev, const float *logits, const float *old_lp
   OPCHK(ma.up(masks, (size_t)B));
   OPCHK(cnt.up(nullptr, 16));
   OPCHK(dh_out.up(nullptr, (size_t)B * H * 4));
-  OPCHK(ps.up(nullptr, (size_t)5 * B * 4));
+  OPCHK(ps.up(nullptr, (size_t)7 * B * 4)); // aleppo_metric_field 0-6 (5-6 are not returned)
   OPCHK(sw.up(nullptr, (size_t)nblk * (A + 1) * H * 4));
   OPCHK(sb.up(nullptr, (size_t)nblk * (A + 1) * 4));
   OPCHK(red.up(nullptr, 8 * 4));
   launch_mask_count(op.st, ma.as<uint8_t>(), cnt.as<float>(), B, 1); // losses.cc:19 masks.sum()
   float *p = ps.as<float>();
   launch_head_train(op.st, dh_in.as<float>(), dW.as<float>(), db.as<float>(), ac.as<int>(), ol.as<float>(),
-                    ad.as<float>(), re.as<float>(), ma.as<uint8_t>(), cnt.as<float>(), Hyper{clip, c_v, c_e, 0.f},
-                    dh_out.p, ALEPPO_FP32, p, p + B, p + 2 * B, p + 3 * B, p + 4 * B, sw.as<float>(), sb.as<float>(),
-                    nblk, B, H, (int)A, nullptr, nullptr, 1);
+                    ad.as<float>(), re.as<float>(), nullptr, ma.as<uint8_t>(), cnt.as<float>(),
+                    Hyper{clip, c_v, c_e, 0.f}, dh_out.p, ALEPPO_FP32, p, p + B, p + 2 * B, p + 3 * B, p + 4 * B,
+                    p + 5 * B, p + 6 * B, sw.as<float>(), sb.as<float>(), nblk, B, H, (int)A, nullptr, nullptr, 1);
   launch_metrics_reduce(op.st, p, (size_t)B, ma.as<uint8_t>(), B, 1, 1, red.as<float>());
   OPCHK(op.sync());
   float r8[8];

@@ -160,7 +160,7 @@ struct Ctx {
   size_t slab_off[11] = {0}; // W1 b1 W2 b2 W3 b3 Wfc bfc Wh bh
   float *adv_stats = nullptr;
   float *sumsq_part = nullptr; // [1024]
-  // ---- per-sample train metrics [mi][B] x 5, and reduced [mi][8] ----
+  // ---- per-sample train metrics [mi][B] x 7 (aleppo_metric_field 0-6), and reduced [mi][8] (metrics_reduce_kernel) ----
   float *metric_ps = nullptr;
   size_t metric_cap = 0; // floats per field
   size_t metric_red_cap = 0;
@@ -174,10 +174,17 @@ struct Ctx {
   int32_t *order = nullptr;   // [epochs][N]
   int *act_p = nullptr;
   void *oldlp_p = nullptr, *adv_p = nullptr, *ret_p = nullptr; // RT [epochs][N][A], [epochs][N], [epochs][N]
+  void *val_p = nullptr;      // RT [epochs][N]: the old values in that order (ALEPPO_OPT_VALUE_CLIP)
   uint8_t *mask_p = nullptr;
   float *mask_counts_ep = nullptr; // [epochs * M] global unmasked count per (epoch, minibatch)
   uint32_t *shuf_keys = nullptr, *h_shuf_keys = nullptr; // [epochs][4] Feistel round keys of one call (device / pinned)
   bool last_shuffled = false;
+  // ---- ALEPPO_OPT_VALUE_CLIP: the values the batch was collected with, env-major RT [N] (allocated on first use)
+  bool value_clip = false;
+  void *val_n = nullptr;
+  enum ValSrc { VAL_NONE = 0, VAL_ROLLOUT = 1, VAL_CALLER = 2 };
+  int val_src = VAL_NONE; // VAL_ROLLOUT: val_n is filled from values_tm inside the update; VAL_CALLER: aleppo_set_batch_values
+  bool caller_batch = false; // the batch came from aleppo_set_batch
   // ---- captured update (ALEPPO_OPT_UPDATE_GRAPH): the epochs x minibatches loop as one hipGraph, re-captured when
   // the shape (or a baked pointer) changes; the first call of a shape runs eagerly (one-time kernel attribute set-up)
   bool update_graph = false;
@@ -188,9 +195,10 @@ struct Ctx {
     long N = 0;
     const void *metric_ps = nullptr, *metric_red = nullptr;
     const void *order = nullptr; // shuffled updates: the order / gathered-plane storage (nullptr: contiguous)
+    int vclip = 0;               // ALEPPO_OPT_VALUE_CLIP: 0 off, else 1 + the ValSrc the old values come from
     bool operator==(const GraphKey &o) const {
       return epochs == o.epochs && M == o.M && two == o.two && N == o.N && metric_ps == o.metric_ps &&
-             metric_red == o.metric_red && order == o.order;
+             metric_red == o.metric_red && order == o.order && vclip == o.vclip;
     }
   } graph_key, warm_key;
   long graph_replays = 0;
@@ -247,16 +255,19 @@ void launch_plane_from_float(hipStream_t s, const float *src, void *dst, long n,
 void launch_mask_count(hipStream_t s, const uint8_t *mask_n, float *counts, long B, int M);
 // ALEPPO_OPT_MINIBATCH_SHUFFLE: order[e][i] = the keyed bijection of aleppo.h (round keys rk[e][4], domain 2^(2h)) and the
 // per-sample planes gathered into that order: act / oldlp / adv / ret / mask_p[e][i] = plane[order[e][i]]
+// (val_n != nullptr, ALEPPO_OPT_VALUE_CLIP: also val_p[e][i] = val_n[order[e][i]])
 void launch_shuffle_gather(hipStream_t s, const uint32_t *rk, int h, long N, int epochs, int A, int32_t *order,
                            const int *act_n, const void *oldlp_n, const void *adv_n, const void *ret_n,
-                           const uint8_t *mask_n, int *act_p, void *oldlp_p, void *adv_p, void *ret_p, uint8_t *mask_p,
-                           bool rt16);
+                           const void *val_n, const uint8_t *mask_n, int *act_p, void *oldlp_p, void *adv_p,
+                           void *ret_p, void *val_p, uint8_t *mask_p, bool rt16);
+// vold: the values the samples were collected with (ALEPPO_OPT_VALUE_CLIP), or nullptr for the reference's value loss;
+// ps_kl / ps_cf: the per-sample approx-KL and clip-fraction planes (always written)
 void launch_head_train(hipStream_t s, const float *h, const float *Wh, const float *bh, const int *act,
-                       const void *oldlp, const void *adv, const void *ret, const uint8_t *mask,
+                       const void *oldlp, const void *adv, const void *ret, const void *vold, const uint8_t *mask,
                        const float *mask_count, Hyper hp, void *dh, int prec, float *ps_total, float *ps_clipped,
-                       float *ps_value, float *ps_entropy, float *ps_ratio, float *slab_w, float *slab_b, int nblk,
-                       long B, int H, int A, float *logits_out, float *values_out, int hparts = 1,
-                       bool rt16 = false); // oldlp / adv / ret are f16 planes
+                       float *ps_value, float *ps_entropy, float *ps_ratio, float *ps_kl, float *ps_cf, float *slab_w,
+                       float *slab_b, int nblk, long B, int H, int A, float *logits_out, float *values_out,
+                       int hparts = 1, bool rt16 = false); // oldlp / adv / ret / vold are f16 planes
 struct ReduceSeg {
   const float *slab;
   int S;

@@ -580,9 +580,9 @@ template <class RT>
 __global__ __launch_bounds__(256) void shuffle_gather_kernel(const uint32_t *__restrict__ rk, int h, long N, int A,
                                                              int32_t *order, const int *__restrict__ act_n,
                                                              const RT *__restrict__ oldlp_n, const RT *__restrict__ adv_n,
-                                                             const RT *__restrict__ ret_n,
+                                                             const RT *__restrict__ ret_n, const RT *__restrict__ val_n,
                                                              const uint8_t *__restrict__ mask_n, int *act_p, RT *oldlp_p,
-                                                             RT *adv_p, RT *ret_p, uint8_t *mask_p) {
+                                                             RT *adv_p, RT *ret_p, RT *val_p, uint8_t *mask_p) {
   __shared__ int sj[256];
   const int e = blockIdx.y;
   const long i0 = (long)blockIdx.x * 256, i = i0 + threadIdx.x;
@@ -598,6 +598,8 @@ __global__ __launch_bounds__(256) void shuffle_gather_kernel(const uint32_t *__r
     act_p[row + i] = act_n[j];
     adv_p[row + i] = adv_n[j];
     ret_p[row + i] = ret_n[j];
+    if (val_n) // ALEPPO_OPT_VALUE_CLIP: the old values travel with their samples
+      val_p[row + i] = val_n[j];
     mask_p[row + i] = mask_n[j];
   }
   __syncthreads();
@@ -609,19 +611,21 @@ __global__ __launch_bounds__(256) void shuffle_gather_kernel(const uint32_t *__r
 }
 void launch_shuffle_gather(hipStream_t s, const uint32_t *rk, int h, long N, int epochs, int A, int32_t *order,
                            const int *act_n, const void *oldlp_n, const void *adv_n, const void *ret_n,
-                           const uint8_t *mask_n, int *act_p, void *oldlp_p, void *adv_p, void *ret_p, uint8_t *mask_p,
-                           bool rt16) {
+                           const void *val_n, const uint8_t *mask_n, int *act_p, void *oldlp_p, void *adv_p,
+                           void *ret_p, void *val_p, uint8_t *mask_p, bool rt16) {
   const dim3 g((unsigned)((N + 255) / 256), (unsigned)epochs);
   if (rt16)
     hipLaunchKernelGGL(shuffle_gather_kernel<f16>, g, dim3(256), 0, s, rk, h, N, A, order, act_n,
                        static_cast<const f16 *>(oldlp_n), static_cast<const f16 *>(adv_n),
-                       static_cast<const f16 *>(ret_n), mask_n, act_p, static_cast<f16 *>(oldlp_p),
-                       static_cast<f16 *>(adv_p), static_cast<f16 *>(ret_p), mask_p);
+                       static_cast<const f16 *>(ret_n), static_cast<const f16 *>(val_n), mask_n, act_p,
+                       static_cast<f16 *>(oldlp_p), static_cast<f16 *>(adv_p), static_cast<f16 *>(ret_p),
+                       static_cast<f16 *>(val_p), mask_p);
   else
     hipLaunchKernelGGL(shuffle_gather_kernel<float>, g, dim3(256), 0, s, rk, h, N, A, order, act_n,
                        static_cast<const float *>(oldlp_n), static_cast<const float *>(adv_n),
-                       static_cast<const float *>(ret_n), mask_n, act_p, static_cast<float *>(oldlp_p),
-                       static_cast<float *>(adv_p), static_cast<float *>(ret_p), mask_p);
+                       static_cast<const float *>(ret_n), static_cast<const float *>(val_n), mask_n, act_p,
+                       static_cast<float *>(oldlp_p), static_cast<float *>(adv_p), static_cast<float *>(ret_p),
+                       static_cast<float *>(val_p), mask_p);
 }
 
 // ================================================================================================
@@ -634,13 +638,16 @@ void launch_shuffle_gather(hipStream_t s, const uint32_t *rk, int h, long N, int
 // ================================================================================================
 // Wide action sets (AMAX = 18: 19 x 8 wgrad accumulators per lane) run 4 waves per workgroup: one wave per SIMD may
 // use the whole 512-entry register file; with 8 waves the 256-register cap spilled the accumulators (150 us vs 22).
-template <class T, int AMAX, class RT>
+// VCLIP (ALEPPO_OPT_VALUE_CLIP): the value term is the clipped one of aleppo.h against vold, the values the samples were
+// collected with; without it vold is never read.  ps_kl / ps_cf (approx-KL and clip fraction) are written either way.
+template <class T, int AMAX, class RT, bool VCLIP>
 __global__ __launch_bounds__(AMAX > 10 ? 256 : 512) void head_train_kernel(
     const float *__restrict__ h, const float *__restrict__ Wh, const float *__restrict__ bh,
     const int *__restrict__ act, const RT *__restrict__ oldlp, const RT *__restrict__ adv,
-    const RT *__restrict__ ret, const uint8_t *__restrict__ mask, const float *__restrict__ mask_count, Hyper hp,
-    T *dh, float *ps_total, float *ps_clipped, float *ps_value, float *ps_entropy, float *ps_ratio, float *slab_w,
-    float *slab_b, long B, int H, int A, float *logits_out, float *values_out, int hparts) {
+    const RT *__restrict__ ret, const RT *__restrict__ vold, const uint8_t *__restrict__ mask,
+    const float *__restrict__ mask_count, Hyper hp, T *dh, float *ps_total, float *ps_clipped, float *ps_value,
+    float *ps_entropy, float *ps_ratio, float *ps_kl, float *ps_cf, float *slab_w, float *slab_b, long B, int H, int A,
+    float *logits_out, float *values_out, int hparts) {
   constexpr int A1 = AMAX + 1, HPL = 8; // H <= 512: 8 hidden units per lane
   constexpr int NWV = AMAX > 10 ? 4 : 8; // waves per workgroup
   extern __shared__ float smem[];
@@ -653,7 +660,7 @@ __global__ __launch_bounds__(AMAX > 10 ? 256 : 512) void head_train_kernel(
   // Everything a row needs (h, action, advantage, return, mask and ALL A old log-probs, so that nothing is a
   // dependent load) is fetched ONE ROW AHEAD: a row's memory round trips hide behind the previous row's math.
   // The first row's loads are issued before the weight staging below.
-  float hnext[HPL], olp_n[AMAX], adv_n = 0.f, ret_n = 0.f;
+  float hnext[HPL], olp_n[AMAX], adv_n = 0.f, ret_n = 0.f, vold_n = 0.f;
   int act_n = 0;
   bool mask_n = false;
   auto fetch = [&](long r) {
@@ -680,6 +687,8 @@ __global__ __launch_bounds__(AMAX > 10 ? 256 : 512) void head_train_kernel(
     act_n = ok ? act[r] : 0;
     adv_n = ok ? (float)adv[r] : 0.f;
     ret_n = ok ? (float)ret[r] : 0.f;
+    if constexpr (VCLIP)
+      vold_n = ok ? (float)vold[r] : 0.f;
     mask_n = ok ? mask[r] != 0 : false;
   };
   fetch(row0 + wave);
@@ -704,7 +713,7 @@ __global__ __launch_bounds__(AMAX > 10 ? 256 : 512) void head_train_kernel(
     for (int a = 0; a < AMAX; ++a)
       olp_c[a] = olp_n[a];
     const int ai = act_n;
-    const float advi = adv_n, reti = ret_n;
+    const float advi = adv_n, reti = ret_n, voldi = vold_n;
     const bool maski = mask_n;
     fetch(row + NWV); // next row of this wave
     float z[A1];
@@ -762,12 +771,24 @@ __global__ __launch_bounds__(AMAX > 10 ? 256 : 512) void head_train_kernel(
       }
     }
     ent = -ent;
-    const float rho = expf(lpa - olpa);                                  // losses.cc:33
+    const float logr = lpa - olpa;
+    const float rho = expf(logr);                                        // losses.cc:33
     const float crho = fminf(fmaxf(rho, 1.0f - hp.clip), 1.0f + hp.clip); // losses.cc:34-35
     const float un = rho * advi, cl = crho * advi;
     const float obj = fminf(un, cl);                                     // losses.cc:38
     const float dv = value - reti;
-    const float lv = 0.5f * (dv * dv);                                   // losses.cc:15
+    float lv, dvg; // value loss and its derivative in v (before the mask and c_v)
+    if constexpr (VCLIP) { // aleppo.h ALEPPO_OPT_VALUE_CLIP: a select, so that inside the range vc IS value
+      const float d = value - voldi;
+      const float vc = fabsf(d) <= hp.clip ? value : voldi + copysignf(hp.clip, d);
+      const float dc = vc - reti;
+      const float lu = dv * dv, lc = dc * dc;
+      lv = 0.5f * fmaxf(lu, lc);
+      dvg = lu >= lc ? dv : 0.f; // ties: the unclipped branch; the clipped one is flat in v
+    } else {
+      lv = 0.5f * (dv * dv);                                             // losses.cc:15
+      dvg = dv;
+    }
     const float Ltot = -obj + hp.c_v * lv - hp.c_e * ent;                // losses.cc:17-18
     const float m = maski ? inv_nm : 0.f;                                // losses.cc:19 masked mean
     const bool active = advi >= 0.f ? (rho <= 1.0f + hp.clip) : (rho >= 1.0f - hp.clip);
@@ -780,7 +801,7 @@ __global__ __launch_bounds__(AMAX > 10 ? 256 : 512) void head_train_kernel(
         dz[a] = m * (gs * ((a == ai ? 1.0f : 0.0f) - p[a < AMAX ? a : 0]) +
                      hp.c_e * p[a < AMAX ? a : 0] * (lp[a < AMAX ? a : 0] + ent));
       if (a == A)
-        dz[a] = m * hp.c_v * dv;
+        dz[a] = m * hp.c_v * dvg;
     }
     if (lane == 0) {
       ps_total[row] = Ltot;
@@ -788,6 +809,8 @@ __global__ __launch_bounds__(AMAX > 10 ? 256 : 512) void head_train_kernel(
       ps_value[row] = lv;
       ps_entropy[row] = ent;
       ps_ratio[row] = rho;
+      ps_kl[row] = (rho - 1.0f) - logr;                                  // approx-KL (k3 estimator)
+      ps_cf[row] = fabsf(rho - 1.0f) > hp.clip ? 1.0f : 0.0f;           // clip fraction (strict)
       if (logits_out) {
 #pragma unroll
         for (int a = 0; a < AMAX; ++a)
@@ -869,21 +892,21 @@ __global__ __launch_bounds__(AMAX > 10 ? 256 : 512) void head_train_kernel(
   }
 }
 
-template <class T, class RT>
+template <class T, class RT, bool VCLIP>
 static void head_train_t(hipStream_t s, const float *h, const float *Wh, const float *bh, const int *act,
-                         const RT *oldlp, const RT *adv, const RT *ret, const uint8_t *mask,
+                         const RT *oldlp, const RT *adv, const RT *ret, const RT *vold, const uint8_t *mask,
                          const float *mask_count, Hyper hp, void *dh, float *ps_total, float *ps_clipped,
-                         float *ps_value, float *ps_entropy, float *ps_ratio, float *slab_w, float *slab_b, int nblk,
-                         long B, int H, int A, float *lo, float *vo, int hparts) {
+                         float *ps_value, float *ps_entropy, float *ps_ratio, float *ps_kl, float *ps_cf, float *slab_w,
+                         float *slab_b, int nblk, long B, int H, int A, float *lo, float *vo, int hparts) {
 #define LAUNCH_HEAD(AM)                                                                                                \
   do {                                                                                                                 \
     const size_t sm = ((size_t)((AM + 1) + ((AM + 1) > 8 ? (AM + 1) : 8)) * H + 8 * (AM + 1)) * sizeof(float);        \
     if (sm > 48 * 1024)                                                                                                \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&head_train_kernel<T, AM, RT>),                         \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&head_train_kernel<T, AM, RT, VCLIP>),                  \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);                                  \
-    hipLaunchKernelGGL((head_train_kernel<T, AM, RT>), dim3(nblk), dim3(AM > 10 ? 256 : 512), sm, s, h, Wh, bh, act, oldlp, adv, ret,  \
-                       mask, mask_count, hp, static_cast<T *>(dh), ps_total, ps_clipped, ps_value, ps_entropy,         \
-                       ps_ratio, slab_w, slab_b, B, H, A, lo, vo, hparts);                                                   \
+    hipLaunchKernelGGL((head_train_kernel<T, AM, RT, VCLIP>), dim3(nblk), dim3(AM > 10 ? 256 : 512), sm, s, h, Wh, bh, \
+                       act, oldlp, adv, ret, vold, mask, mask_count, hp, static_cast<T *>(dh), ps_total, ps_clipped,   \
+                       ps_value, ps_entropy, ps_ratio, ps_kl, ps_cf, slab_w, slab_b, B, H, A, lo, vo, hparts);         \
   } while (0)
   if (A <= 4)
     LAUNCH_HEAD(4);
@@ -896,25 +919,34 @@ static void head_train_t(hipStream_t s, const float *h, const float *Wh, const f
 #undef LAUNCH_HEAD
 }
 void launch_head_train(hipStream_t s, const float *h, const float *Wh, const float *bh, const int *act,
-                       const void *oldlp, const void *adv, const void *ret, const uint8_t *mask,
+                       const void *oldlp, const void *adv, const void *ret, const void *vold, const uint8_t *mask,
                        const float *mask_count, Hyper hp, void *dh, int prec, float *ps_total, float *ps_clipped,
-                       float *ps_value, float *ps_entropy, float *ps_ratio, float *slab_w, float *slab_b, int nblk,
-                       long B, int H, int A, float *logits_out, float *values_out, int hparts, bool rt16) {
+                       float *ps_value, float *ps_entropy, float *ps_ratio, float *ps_kl, float *ps_cf, float *slab_w,
+                       float *slab_b, int nblk, long B, int H, int A, float *logits_out, float *values_out, int hparts,
+                       bool rt16) {
 #define HEAD_ARGS(RT)                                                                                                  \
-  s, h, Wh, bh, act, static_cast<const RT *>(oldlp), static_cast<const RT *>(adv), static_cast<const RT *>(ret), mask, \
-      mask_count, hp, dh, ps_total, ps_clipped, ps_value, ps_entropy, ps_ratio, slab_w, slab_b, nblk, B, H, A,         \
-      logits_out, values_out, hparts
+  s, h, Wh, bh, act, static_cast<const RT *>(oldlp), static_cast<const RT *>(adv), static_cast<const RT *>(ret),       \
+      static_cast<const RT *>(vold), mask, mask_count, hp, dh, ps_total, ps_clipped, ps_value, ps_entropy, ps_ratio,   \
+      ps_kl, ps_cf, slab_w, slab_b, nblk, B, H, A, logits_out, values_out, hparts
+#define HEAD_T(T, RT)                                                                                                  \
+  do {                                                                                                                 \
+    if (vold)                                                                                                          \
+      head_train_t<T, RT, true>(HEAD_ARGS(RT));                                                                        \
+    else                                                                                                               \
+      head_train_t<T, RT, false>(HEAD_ARGS(RT));                                                                       \
+  } while (0)
   if (prec == ALEPPO_BF16) {
     if (rt16)
-      head_train_t<bf16, f16>(HEAD_ARGS(f16));
+      HEAD_T(bf16, f16);
     else
-      head_train_t<bf16, float>(HEAD_ARGS(float));
+      HEAD_T(bf16, float);
   } else {
     if (rt16)
-      head_train_t<float, f16>(HEAD_ARGS(f16));
+      HEAD_T(float, f16);
     else
-      head_train_t<float, float>(HEAD_ARGS(float));
+      HEAD_T(float, float);
   }
+#undef HEAD_T
 #undef HEAD_ARGS
 }
 
@@ -1317,18 +1349,20 @@ void launch_pack_dgrad(hipStream_t s, const float *P, const ParamLayout &L, void
   }
 }
 
-// masked sums of the per-sample metric arrays (log_data's masked means, train.cc:163-210): block per (epoch, mb)
+// masked sums of the per-sample metric arrays (log_data's masked means, train.cc:163-210): block per (epoch, mb).
+// Record [mi][8]: the sums of fields 0-4 (total, clipped, value, entropy, ratio), the count, then the sums of fields 5-6
+// (approx-KL, clip fraction)
 __global__ __launch_bounds__(256) void metrics_reduce_kernel(const float *ps, size_t field_stride, const uint8_t *mask_n,
                                                               long B, int M, float *out) {
   __shared__ float s4[4];
   const int mi = blockIdx.x, mb = mi % M;
   const uint8_t *m = mask_n + (size_t)mb * B;
-  float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, cnt = 0.f;
+  float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, cnt = 0.f;
   for (long i = threadIdx.x; i < B; i += 256)
     if (m[i]) {
       cnt += 1.f;
 #pragma unroll
-      for (int f = 0; f < 5; ++f)
+      for (int f = 0; f < 7; ++f)
         acc[f] += ps[f * field_stride + (size_t)mi * B + i];
     }
 #pragma unroll
@@ -1340,6 +1374,12 @@ __global__ __launch_bounds__(256) void metrics_reduce_kernel(const float *ps, si
   cnt = block_sum_256(cnt, s4);
   if (threadIdx.x == 0)
     out[mi * 8 + 5] = cnt;
+#pragma unroll
+  for (int f = 5; f < 7; ++f) {
+    const float v = block_sum_256(acc[f], s4);
+    if (threadIdx.x == 0)
+      out[mi * 8 + 1 + f] = v;
+  }
 }
 void launch_metrics_reduce(hipStream_t s, const float *ps, size_t field_stride, const uint8_t *mask_n, long B, int M,
                            int epochs, float *out) {

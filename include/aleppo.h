@@ -114,13 +114,23 @@ typedef enum {
   ALEPPO_F_NEXT_VALUES = 12  /* float  [E]: bootstrap values of the last finish_rollout */
 } aleppo_field;
 
-/* Per-sample training metrics (ai::ppo::train::Metrics, src/ai/ppo/train.h:64-109), [epochs,M,B] */
+/* Per-sample training metrics (ai::ppo::train::Metrics, src/ai/ppo/train.h:64-109), [epochs,M,B], read with
+ * aleppo_read_train_metric; fields 5-8 are extensions (the reference has none).  With logr = logp(a) - old_logp(a) and
+ * rho = exp(logr) per sample, computed on every update whatever ALEPPO_OPT_VALUE_CLIP is:
+ *   approx_kl     = (rho - 1) - logr                  (the "k3" estimator CleanRL logs as approx_kl)
+ *   clip_fraction = |rho - 1| > clip_param ? 1 : 0     (strict)
+ * The two MEAN fields are the masked means of those planes per minibatch, float [epochs,M] (count = epochs * M), with the
+ * denominator of aleppo_minibatch_metrics: the global unmasked count (under data parallelism they are global means). */
 typedef enum {
   ALEPPO_M_TOTAL_LOSSES = 0,
   ALEPPO_M_CLIPPED_LOSSES = 1,
   ALEPPO_M_VALUE_LOSSES = 2,
   ALEPPO_M_ENTROPIES = 3,
-  ALEPPO_M_RATIO = 4
+  ALEPPO_M_RATIO = 4,
+  ALEPPO_M_APPROX_KL = 5,          /* [epochs,M,B] per sample, unmasked, in aleppo_read_sample_order order */
+  ALEPPO_M_CLIP_FRACTION = 6,      /* [epochs,M,B] per sample (0 / 1), same conventions */
+  ALEPPO_M_MEAN_APPROX_KL = 7,     /* [epochs,M] masked means */
+  ALEPPO_M_MEAN_CLIP_FRACTION = 8  /* [epochs,M] masked means */
 } aleppo_metric_field;
 
 /* ------------------------------------------------------------------ lifetime */
@@ -232,7 +242,8 @@ int aleppo_finish_rollout(aleppo_ctx *ctx, const float *noise);
 int aleppo_train(aleppo_ctx *ctx, double lr, int epochs, int num_mini_batches,
                  aleppo_minibatch_metrics *out_metrics);
 /* Per-sample metric tensors of the last aleppo_train, float [epochs,M,B], in the order of aleppo_read_sample_order:
- * element [e][m][b] belongs to logical sample order[e][m*B + b]. */
+ * element [e][m][b] belongs to logical sample order[e][m*B + b].  ALEPPO_M_MEAN_* fields: float [epochs,M], count =
+ * epochs * M. */
 int aleppo_read_train_metric(aleppo_ctx *ctx, int metric_field, float *dst, size_t count);
 /* Sample order of the last aleppo_train, int32 [epochs][N] (count = epochs * N, N = the batch's sample count): row e,
  * position m*B + b is the logical sample (n = e_env*T + t of the rollout, or row n of aleppo_set_batch) that sat at
@@ -260,6 +271,11 @@ int aleppo_read_sample_order(aleppo_ctx *ctx, int32_t *dst, size_t count);
 int aleppo_set_batch(aleppo_ctx *ctx, const uint8_t *observations, const int64_t *actions,
                      const float *log_probabilities, const float *advantages, const float *returns,
                      const uint8_t *masks, int64_t n);
+/* The values v_old the caller batch was collected with, float [n], for ALEPPO_OPT_VALUE_CLIP: called after
+ * aleppo_set_batch with the same n (ALEPPO_ERR_INVALID_ARGUMENT otherwise; ALEPPO_ERR_RUNTIME without a caller batch).
+ * Stored like the other planes of that call (rounded to the rollout plane type).  The next aleppo_set_batch or
+ * aleppo_finish_rollout forgets them. */
+int aleppo_set_batch_values(aleppo_ctx *ctx, const float *values, int64_t n);
 
 int aleppo_read_batch(aleppo_ctx *ctx, int field, void *dst, size_t bytes);
 /* Network forward only (NetworkImpl::forward, train.cc:255-265) on host observations uint8
@@ -355,11 +371,26 @@ typedef enum {
   ALEPPO_OPT_UPDATE_GRAPH = 7,     /* 1: capture the epochs x minibatches loop of aleppo_train in a hipGraph and replay it
                                       (capture_train_cuda_graph, src/ai/ppo/train.h:163-195); lr and the Adam bias
                                       corrections are device scalars, so a replay follows the annealed rate */
-  ALEPPO_OPT_MINIBATCH_SHUFFLE = 12 /* 0 (default): minibatch m of every epoch is the contiguous slice [m*B, (m+1)*B) of the
+  ALEPPO_OPT_MINIBATCH_SHUFFLE = 12, /* 0 (default): minibatch m of every epoch is the contiguous slice [m*B, (m+1)*B) of the
                                       batch, like the reference (which draws randperm and never uses it, train.h:146).
                                       1: every epoch of every aleppo_train uses a fresh permutation of the N local samples
                                       (the keyed bijection documented at aleppo_read_sample_order), on every schedule -
                                       eager or ALEPPO_OPT_UPDATE_GRAPH, fp32 or bf16, one GPU or data parallel */
+  ALEPPO_OPT_VALUE_CLIP = 13       /* value-function clipping (CleanRL clip_vloss, baselines ppo2).  0 (default): the
+                                      reference's value loss 0.5 (v - R)^2.  1: clipped at c = config.clip_param; any other
+                                      value is ALEPPO_ERR_INVALID_ARGUMENT.  Per sample, v = the value head's output, R = the
+                                      return, v_old = the value stored when the sample was collected:
+                                        d   = v - v_old
+                                        v_c = |d| <= c ? v : v_old + copysign(c, d)   (a select: inside the range v_c IS v)
+                                        l_u = (v - R)^2,  l_c = (v_c - R)^2
+                                        value loss = 0.5 max(l_u, l_c)   (ALEPPO_M_VALUE_LOSSES and the value_loss mean)
+                                        dL/dv = l_u >= l_c ? v - R : 0   (ties: the unclipped branch)
+                                      and only that term of the total loss changes (same coefficients, masked mean and
+                                      global count).  v_old of a rollout batch (aleppo_finish_rollout) is the values plane
+                                      as stored - with ALEPPO_ROLLOUT_FP16 the fp16-rounded values, what aleppo_read_batch
+                                      (ALEPPO_F_VALUES) returns; of a caller batch, what aleppo_set_batch_values stored:
+                                      aleppo_train on a caller batch without them is ALEPPO_ERR_RUNTIME.  The same on every
+                                      schedule, like ALEPPO_OPT_MINIBATCH_SHUFFLE */
 } aleppo_option;
 int aleppo_set_option(aleppo_ctx *ctx, int option, int value);
 /* Current value of an option; for ALEPPO_OPT_UPDATE_GRAPH the number of graph launches so far (0 = every update ran

@@ -28,7 +28,10 @@
 // device_preprocess: false (true: the emulators hand over RAW 210x160 frame pairs and the device does gray LUT + resize +
 // max), advantage_norm: false, action_size (honoured here; the reference hard-codes 4, Q4), seed,
 // slot_ahead: true (the next slot's ingest + acting kernels are enqueued BEFORE the emulator threads run, behind a stream
-// wait that aleppo_release_step lifts when they are done: aleppo_arm_step in include/aleppo.h; false: aleppo_step).
+// wait that aleppo_release_step lifts when they are done: aleppo_arm_step in include/aleppo.h; false: aleppo_step),
+// shuffle_minibatches: false, clip_value_loss: false (ALEPPO_OPT_VALUE_CLIP: CleanRL's clip_vloss), target_kl (absent or
+// <= 0: off; else the update runs one epoch per aleppo_train call and stops after the epoch whose LAST minibatch's
+// approx-KL exceeds it, CleanRL's rule; exact, because E one-epoch calls equal one call of E epochs).
 // Data parallelism (no reference counterpart): start one process per GPU with RANK / WORLD_SIZE / LOCAL_RANK
 // in the environment (torchrun / mpirun style).  Rank r owns the contiguous environment block
 // [r * E / W, (r + 1) * E / W) and GPU LOCAL_RANK; rank 0 creates the RCCL id, hands it to the others through the file
@@ -70,6 +73,8 @@ struct Config {
   float max_return = -1.0f;
   bool record_observation = false, record_video = false, cuda_graph = false, deterministic = false;
   bool shuffle_minibatches = false; // extension: a fresh sample permutation per epoch (ALEPPO_OPT_MINIBATCH_SHUFFLE)
+  bool clip_value_loss = false;     // extension: value-function clipping (ALEPPO_OPT_VALUE_CLIP)
+  double target_kl = 0.0;           // extension: early stop of the update's epochs on approx-KL (<= 0: off)
   // extensions
   std::string precision = "fp32", rollout_precision = "fp32";
   bool device_preprocess = false; // emulators hand over raw frame pairs; gray LUT + resize + max run on the device (N2)
@@ -147,6 +152,8 @@ static Config load_config(const std::string &path) { // keys / defaults of src/b
   c.record_video = as_bool(kv, "record_video", false);
   c.cuda_graph = as_bool(kv, "cuda_graph", false);
   c.shuffle_minibatches = as_bool(kv, "shuffle_minibatches", false);
+  c.clip_value_loss = as_bool(kv, "clip_value_loss", false);
+  c.target_kl = as<double>(kv, "target_kl", 0.0);
   c.deterministic = as_bool(kv, "deterministic", false);
   c.precision = as<std::string>(kv, "precision", "fp32");
   c.rollout_precision = as<std::string>(kv, "rollout_precision", "fp32");
@@ -790,6 +797,8 @@ int main(int argc, char **argv) {
       check(ctx, aleppo_set_option(ctx, ALEPPO_OPT_UPDATE_GRAPH, 1));
     if (cfg.shuffle_minibatches) // extension: minibatches of a fresh per-epoch permutation instead of contiguous slices
       check(ctx, aleppo_set_option(ctx, ALEPPO_OPT_MINIBATCH_SHUFFLE, 1));
+    if (cfg.clip_value_loss) // extension: the clipped value loss of ppo2 / CleanRL (clip range = clip_param)
+      check(ctx, aleppo_set_option(ctx, ALEPPO_OPT_VALUE_CLIP, 1));
     if (prof.on())
       check(ctx, aleppo_profile_enable(ctx, 1));
     std::vector<std::pair<std::string, bool>> hparam_flags{{"record_observation", cfg.record_observation},
@@ -798,6 +807,8 @@ int main(int argc, char **argv) {
                                                            {"deterministic", cfg.deterministic}};
     if (cfg.shuffle_minibatches) // (only when set: the records of existing configs stay byte-identical)
       hparam_flags.emplace_back("shuffle_minibatches", true);
+    if (cfg.clip_value_loss)
+      hparam_flags.emplace_back("clip_value_loss", true);
     logger.add_hparams( // get_parameters (train.cc:76-105), same keys
         {{"total_environments", (double)cfg.total_environments}, {"hidden_size", (double)cfg.hidden_size},
          {"action_size", (double)cfg.action_size}, {"horizon", (double)cfg.horizon}, {"max_steps", (double)cfg.max_steps},
@@ -917,15 +928,40 @@ int main(int argc, char **argv) {
 
     rollout(); // the warm rollout before the loop (train.cc:391-396): collected, never trained on
     const auto t_begin = std::chrono::steady_clock::now();
-    std::vector<aleppo_minibatch_metrics> m((size_t)cfg.num_epochs * (size_t)cfg.num_mini_batches);
+    const size_t nmb = (size_t)cfg.num_mini_batches, N = E * T;
+    // metrics of every epoch that ran: per minibatch, and the per-sample planes of log_data's histograms ([epochs][N])
+    std::vector<aleppo_minibatch_metrics> m((size_t)cfg.num_epochs * nmb);
+    std::vector<float> kl((size_t)cfg.num_epochs * nmb), cf((size_t)cfg.num_epochs * nmb);
+    const std::pair<int, const char *> sample_fields[5] = {{ALEPPO_M_TOTAL_LOSSES, "losses"},
+                                                           {ALEPPO_M_CLIPPED_LOSSES, "clipped_losses"},
+                                                           {ALEPPO_M_VALUE_LOSSES, "value_losses"},
+                                                           {ALEPPO_M_ENTROPIES, "entropies"},
+                                                           {ALEPPO_M_RATIO, "ratios"}};
+    std::vector<std::vector<float>> planes(5, std::vector<float>((size_t)cfg.num_epochs * N));
     for (size_t r = 0; r < cfg.num_rollouts; ++r) {
       std::cout << "Rollout " << r + 1 << " of " << cfg.num_rollouts << std::endl;
       const double lr = cfg.learning_rate * (1.0 - r / static_cast<double>(cfg.num_rollouts)); // train.cc:424-428
       const Log log = rollout();
-      {
-        Profile::Span sp(&prof, "aleppo_train");
-        check(ctx, aleppo_train(ctx, lr, (int)cfg.num_epochs, (int)cfg.num_mini_batches, m.data()));
+      // one call of num_epochs epochs, or - with target_kl - one call per epoch until an epoch's last minibatch is over
+      // the target (the Adam schedule and the shuffle keys follow the Adam step, so the calls add up to the same update)
+      size_t epochs_run = 0;
+      const size_t per_call = cfg.target_kl > 0 ? 1 : (size_t)cfg.num_epochs;
+      while (epochs_run < (size_t)cfg.num_epochs) {
+        const size_t e0 = epochs_run;
+        {
+          Profile::Span sp(&prof, "aleppo_train");
+          check(ctx, aleppo_train(ctx, lr, (int)per_call, (int)nmb, m.data() + e0 * nmb));
+        }
+        Profile::Span sp_read(&prof, "read_train_metrics");
+        check(ctx, aleppo_read_train_metric(ctx, ALEPPO_M_MEAN_APPROX_KL, kl.data() + e0 * nmb, per_call * nmb));
+        check(ctx, aleppo_read_train_metric(ctx, ALEPPO_M_MEAN_CLIP_FRACTION, cf.data() + e0 * nmb, per_call * nmb));
+        for (size_t k = 0; k < 5; ++k)
+          check(ctx, aleppo_read_train_metric(ctx, sample_fields[k].first, planes[k].data() + e0 * N, per_call * N));
+        epochs_run += per_call;
+        if (cfg.target_kl > 0 && kl[epochs_run * nmb - 1] > cfg.target_kl)
+          break;
       }
+      const size_t nrun = epochs_run * nmb; // minibatches that ran
       Profile::Span sp_log(&prof, "log_data");
       // log_data (train.cc:163-210): x axis = non-reset env steps
       const int64_t step = (int64_t)total_steps;
@@ -944,9 +980,15 @@ int main(int argc, char **argv) {
       }
       auto avg = [&](float aleppo_minibatch_metrics::*f) {
         double s = 0;
-        for (auto &x : m)
-          s += x.*f;
-        return (float)(s / (double)m.size());
+        for (size_t i = 0; i < nrun; ++i)
+          s += m[i].*f;
+        return (float)(s / (double)nrun);
+      };
+      auto avgv = [&](const std::vector<float> &x) { // (computed like mean_ratio)
+        double s = 0;
+        for (size_t i = 0; i < nrun; ++i)
+          s += x[i];
+        return (float)(s / (double)nrun);
       };
       logger.add_scalar("mean_clipped_gradient", step, avg(&aleppo_minibatch_metrics::grad_norm));
       logger.add_scalar("mean_loss", step, avg(&aleppo_minibatch_metrics::loss));
@@ -954,18 +996,21 @@ int main(int argc, char **argv) {
       logger.add_scalar("mean_value_loss", step, avg(&aleppo_minibatch_metrics::value_loss));
       logger.add_scalar("mean_entropy", step, avg(&aleppo_minibatch_metrics::entropy));
       logger.add_scalar("mean_ratio", step, avg(&aleppo_minibatch_metrics::ratio));
+      logger.add_scalar("mean_approx_kl", step, avgv(kl));
+      logger.add_scalar("mean_clip_fraction", step, avgv(cf));
+      if (cfg.target_kl > 0)
+        logger.add_scalar("update_epochs", step, (float)epochs_run);
       logger.add_scalar("learning_rate", step, (float)lr);
       {
         std::vector<float> gn;
-        for (auto &x : m)
-          gn.push_back(x.grad_norm);
+        for (size_t i = 0; i < nrun; ++i)
+          gn.push_back(m[i].grad_norm);
         if (gn.size() > 1)
           logger.add_histogram("clipped_gradients", step, gn);
       }
       { // the per-sample histograms of log_data (train.cc:190-207): mask-selected values of the [epochs, M, B] planes
-        const size_t N = E * T, per = (size_t)cfg.num_epochs * N;
         std::vector<uint8_t> masks(N);
-        std::vector<float> plane(per), adv(N), ret(N), sel;
+        std::vector<float> adv(N), ret(N), sel;
         check(ctx, aleppo_read_batch(ctx, ALEPPO_F_MASKS, masks.data(), N));
         auto gather = [&](const std::vector<float> &x, size_t reps) { // gather(t, masks): unmasked entries, every epoch
           sel.clear();
@@ -975,15 +1020,8 @@ int main(int argc, char **argv) {
                 sel.push_back(x[r * N + i]);
           return sel;
         };
-        const std::pair<int, const char *> fields[5] = {{ALEPPO_M_TOTAL_LOSSES, "losses"},
-                                                        {ALEPPO_M_CLIPPED_LOSSES, "clipped_losses"},
-                                                        {ALEPPO_M_VALUE_LOSSES, "value_losses"},
-                                                        {ALEPPO_M_ENTROPIES, "entropies"},
-                                                        {ALEPPO_M_RATIO, "ratios"}};
-        for (auto &fd : fields) {
-          check(ctx, aleppo_read_train_metric(ctx, fd.first, plane.data(), per));
-          logger.add_histogram(fd.second, step, gather(plane, (size_t)cfg.num_epochs));
-        }
+        for (size_t k = 0; k < 5; ++k) // (every epoch that ran)
+          logger.add_histogram(sample_fields[k].second, step, gather(planes[k], epochs_run));
         check(ctx, aleppo_read_batch(ctx, ALEPPO_F_ADVANTAGES, adv.data(), N * 4));
         check(ctx, aleppo_read_batch(ctx, ALEPPO_F_RETURNS, ret.data(), N * 4));
         logger.add_histogram("advantages", step, gather(adv, 1));
