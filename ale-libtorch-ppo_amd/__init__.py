@@ -40,6 +40,8 @@ METRIC_FIELDS = dict(total_losses=0, clipped_losses=1, value_losses=2, entropies
                      clip_fraction=6)
 # the [epochs, M] masked means of approx_kl / clip_fraction (aleppo_read_train_metric; Engine.train_diagnostics)
 METRIC_MEAN_FIELDS = dict(approx_kl=7, clip_fraction=8)
+# the [epochs, M] statistics of OPT_ADV_NORM_MINIBATCH (aleppo_read_train_metric; Engine.advantage_stats)
+METRIC_ADV_FIELDS = dict(mean=9, std=10)
 KERNEL_CLASSES = dict(ingest=0, gae=1, head=2, adam=3, conv1_fwd=4, conv2_fwd=5, conv3_fwd=6, fc_fwd=7, fc_dgrad=8,
                       fc_wgrad=9, conv3_dgrad=10, conv3_wgrad=11, conv2_dgrad=12, conv2_wgrad=13, conv1_wgrad=14,
                       reduce=15, infer_head=16, act_fused=17, conv_fwd=18, conv_bwd=19)
@@ -53,6 +55,7 @@ OPT_FUSED_FWD = 10
 OPT_FUSED_BWD = 11
 OPT_MINIBATCH_SHUFFLE = 12
 OPT_VALUE_CLIP = 13
+OPT_ADV_NORM_MINIBATCH = 14
 
 EXPORTS = [
     "aleppo_abi_version", "aleppo_create", "aleppo_destroy", "aleppo_last_error", "aleppo_param_count",
@@ -416,6 +419,16 @@ class Engine:
             self._c(lib().aleppo_read_train_metric(self._ctx, field, _ptr(a), C.c_size_t(a.size)))
             out[name] = a
         return out
+
+    def advantage_stats(self, epochs, M):
+        """(mean, std): float32 [epochs, M] statistics OPT_ADV_NORM_MINIBATCH normalised each minibatch's advantages with
+        in the last train (aleppo.h: mean_f and (float)std of the unmasked advantages)"""
+        out = []
+        for field in (METRIC_ADV_FIELDS["mean"], METRIC_ADV_FIELDS["std"]):
+            a = np.zeros((epochs, M), np.float32)
+            self._c(lib().aleppo_read_train_metric(self._ctx, field, _ptr(a), C.c_size_t(a.size)))
+            out.append(a)
+        return tuple(out)
 
     def sample_order(self, epochs):
         """aleppo_read_sample_order: int32 [epochs, N], row e = the logical samples of epoch e in minibatch order

@@ -507,7 +507,8 @@ extern "C" void aleppo_destroy(aleppo_ctx *c) {
                  c->dz2,   c->dz3,      c->h,         c->hpart,     c->dh,        c->logits_b,   c->values_b, c->slab,
                  c->sumsq_part, c->metric_ps, c->metric_red, c->grad_norms, c->adv_stats, c->stage_u8, c->stage_obs,
                  c->adam_sched, c->rb_tmp[0], c->rb_tmp[1], c->order, c->act_p, c->oldlp_p, c->adv_p,
-                 c->ret_p,  c->mask_p,   c->mask_counts_ep, c->shuf_keys, c->val_n, c->val_p};
+                 c->ret_p,  c->mask_p,   c->mask_counts_ep, c->shuf_keys, c->val_n, c->val_p, c->advn_part,
+                 c->advn_stats};
   for (void *p : dev)
     if (p)
       hipFree(p);
@@ -516,7 +517,7 @@ extern "C" void aleppo_destroy(aleppo_ctx *c) {
   if (c->Pc && c->Pc != c->P)
     hipFree(c->Pc);
   void *host[] = {c->h_go, c->h_actions, c->h_step, c->h_rec, c->h_frames, c->h_noise, c->h_err, c->h_metric_red,
-                  c->h_adam_sched, c->h_shuf_keys};
+                  c->h_adam_sched, c->h_shuf_keys, c->h_advn_stats};
   for (void *p : host)
     if (p)
       hipHostFree(p);
@@ -1146,14 +1147,23 @@ static int ensure_metric_storage(aleppo_ctx *c, int epochs, int M, long B) {
     retire(c, c->metric_red);
     retire(c, c->grad_norms);
     retire(c, c->adam_sched);
+    retire(c, c->advn_part);
+    retire(c, c->advn_stats);
     retire_host(c, c->h_metric_red);
     retire_host(c, c->h_adam_sched);
+    retire_host(c, c->h_advn_stats);
     c->metric_red = c->grad_norms = c->h_metric_red = c->adam_sched = c->h_adam_sched = nullptr;
+    c->advn_part = nullptr;
+    c->advn_stats = c->h_advn_stats = nullptr;
+    c->last_advn = false; // (its statistics went with the old buffer)
     HIPCHK(c, dalloc(&c->metric_red, nm * 8 * 4, c->stream));
     HIPCHK(c, dalloc(&c->grad_norms, nm * 4, c->stream));
     HIPCHK(c, dalloc(&c->adam_sched, nm * 2 * 4, c->stream));
+    HIPCHK(c, dalloc(&c->advn_part, nm * 4 * 8, c->stream));  // ALEPPO_OPT_ADV_NORM_MINIBATCH (n, S, Q, 0) per minibatch
+    HIPCHK(c, dalloc(&c->advn_stats, nm * 4 * 4, c->stream)); // ... and (mean_f, inv_f, std, 0)
     HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_metric_red), nm * 9 * 4, hipHostMallocDefault));
     HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_adam_sched), nm * 2 * 4, hipHostMallocDefault));
+    HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_advn_stats), nm * 4 * 4, hipHostMallocDefault));
     c->metric_red_cap = nm;
   }
   return ALEPPO_OK;
@@ -1247,6 +1257,7 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
   if (rc)
     return rc;
   const bool shuffle = c->shuffle;
+  const bool advn = c->adv_norm_mb; // ALEPPO_OPT_ADV_NORM_MINIBATCH (statistics in advn_stats, grown with the metrics)
   if (shuffle && (rc = ensure_shuffle_storage(c, epochs, N)))
     return rc;
   if (vclip && (rc = ensure_val_storage(c)))
@@ -1339,6 +1350,17 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
   launch_mask_count(s, shuffle ? c->mask_p : c->mask_n, counts, B, ncounts);
   if (dp) // N_m of the masked mean is the GLOBAL count
     NCCLCHK(c, ncclAllReduce(counts, counts, ncounts, ncclFloat, ncclSum, comm, s));
+  // ALEPPO_OPT_ADV_NORM_MINIBATCH: the statistics of the same (epoch, minibatch) sample sets as the counts - over the
+  // global minibatch with data parallelism (double sums all-reduced, then finalised)
+  if (advn) {
+    const void *adv_src = shuffle ? c->adv_p : c->adv_n;
+    const uint8_t *mask_src = shuffle ? c->mask_p : c->mask_n;
+    launch_advn_stats(s, adv_src, mask_src, B, ncounts, dp ? c->advn_part : nullptr, c->advn_stats, c->rt16);
+    if (dp) {
+      NCCLCHK(c, ncclAllReduce(c->advn_part, c->advn_part, (size_t)ncounts * 4, ncclDouble, ncclSum, comm, s));
+      launch_advn_finalise(s, c->advn_part, c->advn_stats, ncounts);
+    }
+  }
   for (int ep = 0; ep < epochs; ++ep)
     for (int mb = 0; mb < M; ++mb) { // contiguous env-major slices unless shuffling (the reference's randperm is unused, Q1)
       const int mi = ep * M + mb;
@@ -1361,7 +1383,7 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
                         c->metric_ps + 2 * fs + (size_t)mi * B, c->metric_ps + 3 * fs + (size_t)mi * B,
                         c->metric_ps + 4 * fs + (size_t)mi * B, c->metric_ps + 5 * fs + (size_t)mi * B,
                         c->metric_ps + 6 * fs + (size_t)mi * B, sWh, sBh, nblk_head, B, H, A, nullptr, nullptr, hparts,
-                        c->rt16);
+                        c->rt16, advn ? c->advn_stats + (size_t)(shuffle ? mi : mb) * 4 : nullptr);
       prof_end(c, ALEPPO_K_HEAD);
       HIPCHK(c, fork(c->ev_head)); // dh is ready
       prof_begin(c, ALEPPO_K_FC_DGRAD);
@@ -1510,6 +1532,7 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
   key.metric_red = c->metric_red;
   key.order = shuffle ? c->order : nullptr;
   key.vclip = vclip ? 1 + c->val_src : 0;
+  key.advn = advn ? c->advn_stats : nullptr;
   const bool want_graph = c->update_graph && !dp && !c->prof_on;
   if (want_graph && c->graph_exec && c->graph_key == key) {
     HIPCHK(c, hipGraphLaunch(c->graph_exec, s));
@@ -1554,12 +1577,15 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(c->h_metric_red, c->metric_red, (size_t)nm * 8 * 4, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipMemcpyAsync(c->h_metric_red + (size_t)nm * 8, c->grad_norms, (size_t)nm * 4, hipMemcpyDeviceToHost, s));
+  if (advn) // (contiguous: M records, the same slices every epoch)
+    HIPCHK(c, hipMemcpyAsync(c->h_advn_stats, c->advn_stats, (size_t)(shuffle ? nm : M) * 16, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   CHECK_ASYNC(c);
   c->last_epochs = epochs;
   c->last_M = M;
   c->last_B = B;
   c->last_shuffled = shuffle;
+  c->last_advn = advn;
   if (out)
     for (int i = 0; i < nm; ++i) {
       const float *r = c->h_metric_red + (size_t)i * 8;
@@ -1587,6 +1613,19 @@ extern "C" int aleppo_read_train_metric(aleppo_ctx *c, int field, float *dst, si
       const float *r = c->h_metric_red + i * 8;
       dst[i] = r[slot] / r[5];
     }
+    return ALEPPO_OK;
+  }
+  if (field == ALEPPO_M_ADV_MEAN || field == ALEPPO_M_ADV_STD) {
+    // the ALEPPO_OPT_ADV_NORM_MINIBATCH statistics [epochs, M] of the last aleppo_train (brought back by it)
+    const size_t nm = (size_t)c->last_epochs * c->last_M;
+    if (!c->last_advn || nm == 0)
+      return set_err(c, ALEPPO_ERR_RUNTIME,
+                     "read_train_metric: the last aleppo_train ran without ALEPPO_OPT_ADV_NORM_MINIBATCH");
+    if (!dst || count != nm)
+      return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "read_train_metric: count must be epochs * M of the last aleppo_train");
+    const int slot = field == ALEPPO_M_ADV_MEAN ? 0 : 2;
+    for (size_t i = 0; i < nm; ++i)
+      dst[i] = c->h_advn_stats[(c->last_shuffled ? i : i % (size_t)c->last_M) * 4 + slot];
     return ALEPPO_OK;
   }
   const size_t n = (size_t)c->last_epochs * c->last_M * c->last_B;
@@ -1891,6 +1930,11 @@ extern "C" int aleppo_set_option(aleppo_ctx *c, int option, int value) {
     if (value != 0 && value != 1)
       return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "ALEPPO_OPT_VALUE_CLIP: 0 (off) or 1 (clip at config.clip_param)");
     c->value_clip = value != 0;
+  } else if (option == ALEPPO_OPT_ADV_NORM_MINIBATCH) {
+    if (value != 0 && value != 1)
+      return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT,
+                     "ALEPPO_OPT_ADV_NORM_MINIBATCH: 0 (off) or 1 (normalise each minibatch's advantages)");
+    c->adv_norm_mb = value != 0;
   } else if (option == ALEPPO_OPT_UPDATE_GRAPH)
     c->update_graph = value != 0;
   else if (option == ALEPPO_OPT_GATE_TIMEOUT_MS)
@@ -1915,6 +1959,7 @@ extern "C" int aleppo_get_option(aleppo_ctx *c, int option, int64_t *value) {
   case ALEPPO_OPT_UPDATE_GRAPH: *value = c->graph_replays; break;
   case ALEPPO_OPT_MINIBATCH_SHUFFLE: *value = c->shuffle; break;
   case ALEPPO_OPT_VALUE_CLIP: *value = c->value_clip; break;
+  case ALEPPO_OPT_ADV_NORM_MINIBATCH: *value = c->adv_norm_mb; break;
   case ALEPPO_OPT_GATE_TIMEOUT_MS: *value = (int64_t)(c->gate_timeout_ticks / 100000ull); break;
   default: return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "unknown option");
   }

@@ -185,6 +185,11 @@ struct Ctx {
   enum ValSrc { VAL_NONE = 0, VAL_ROLLOUT = 1, VAL_CALLER = 2 };
   int val_src = VAL_NONE; // VAL_ROLLOUT: val_n is filled from values_tm inside the update; VAL_CALLER: aleppo_set_batch_values
   bool caller_batch = false; // the batch came from aleppo_set_batch
+  // ---- ALEPPO_OPT_ADV_NORM_MINIBATCH: per-minibatch advantage statistics (grown with the metric storage, [metric_red_cap])
+  bool adv_norm_mb = false;
+  double *advn_part = nullptr;                    // [mi][4] (n, S, Q, 0) partial sums (data parallel: all-reduced)
+  float *advn_stats = nullptr, *h_advn_stats = nullptr; // [mi][4] (mean_f, inv_f, std, 0) (device / pinned)
+  bool last_advn = false;                         // the last aleppo_train ran with the option (h_advn_stats holds it)
   // ---- captured update (ALEPPO_OPT_UPDATE_GRAPH): the epochs x minibatches loop as one hipGraph, re-captured when
   // the shape (or a baked pointer) changes; the first call of a shape runs eagerly (one-time kernel attribute set-up)
   bool update_graph = false;
@@ -196,9 +201,10 @@ struct Ctx {
     const void *metric_ps = nullptr, *metric_red = nullptr;
     const void *order = nullptr; // shuffled updates: the order / gathered-plane storage (nullptr: contiguous)
     int vclip = 0;               // ALEPPO_OPT_VALUE_CLIP: 0 off, else 1 + the ValSrc the old values come from
+    const void *advn = nullptr;  // ALEPPO_OPT_ADV_NORM_MINIBATCH: the statistics storage (nullptr: off)
     bool operator==(const GraphKey &o) const {
       return epochs == o.epochs && M == o.M && two == o.two && N == o.N && metric_ps == o.metric_ps &&
-             metric_red == o.metric_red && order == o.order && vclip == o.vclip;
+             metric_red == o.metric_red && order == o.order && vclip == o.vclip && advn == o.advn;
     }
   } graph_key, warm_key;
   long graph_replays = 0;
@@ -253,6 +259,11 @@ void launch_adv_norm(hipStream_t s, void *adv_n, const uint8_t *mask_n, float *s
 void launch_plane_to_float(hipStream_t s, const void *src, float *dst, long n, bool rt16);
 void launch_plane_from_float(hipStream_t s, const float *src, void *dst, long n, bool rt16);
 void launch_mask_count(hipStream_t s, const uint8_t *mask_n, float *counts, long B, int M);
+// ALEPPO_OPT_ADV_NORM_MINIBATCH: block per minibatch i < nmb over adv / mask + i*B.  part == nullptr: stats[i][4] =
+// (mean_f, inv_f, std, 0) of aleppo.h; else part[i][4] = (n, S, Q, 0) in double, for an all-reduce and launch_advn_finalise
+void launch_advn_stats(hipStream_t s, const void *adv, const uint8_t *mask, long B, int nmb, double *part, float *stats,
+                       bool rt16);
+void launch_advn_finalise(hipStream_t s, const double *part, float *stats, int nmb);
 // ALEPPO_OPT_MINIBATCH_SHUFFLE: order[e][i] = the keyed bijection of aleppo.h (round keys rk[e][4], domain 2^(2h)) and the
 // per-sample planes gathered into that order: act / oldlp / adv / ret / mask_p[e][i] = plane[order[e][i]]
 // (val_n != nullptr, ALEPPO_OPT_VALUE_CLIP: also val_p[e][i] = val_n[order[e][i]])
@@ -261,13 +272,15 @@ void launch_shuffle_gather(hipStream_t s, const uint32_t *rk, int h, long N, int
                            const void *val_n, const uint8_t *mask_n, int *act_p, void *oldlp_p, void *adv_p,
                            void *ret_p, void *val_p, uint8_t *mask_p, bool rt16);
 // vold: the values the samples were collected with (ALEPPO_OPT_VALUE_CLIP), or nullptr for the reference's value loss;
-// ps_kl / ps_cf: the per-sample approx-KL and clip-fraction planes (always written)
+// ps_kl / ps_cf: the per-sample approx-KL and clip-fraction planes (always written);
+// advs: this minibatch's (mean_f, inv_f) of ALEPPO_OPT_ADV_NORM_MINIBATCH, or nullptr for the advantages as stored
 void launch_head_train(hipStream_t s, const float *h, const float *Wh, const float *bh, const int *act,
                        const void *oldlp, const void *adv, const void *ret, const void *vold, const uint8_t *mask,
                        const float *mask_count, Hyper hp, void *dh, int prec, float *ps_total, float *ps_clipped,
                        float *ps_value, float *ps_entropy, float *ps_ratio, float *ps_kl, float *ps_cf, float *slab_w,
                        float *slab_b, int nblk, long B, int H, int A, float *logits_out, float *values_out,
-                       int hparts = 1, bool rt16 = false); // oldlp / adv / ret / vold are f16 planes
+                       int hparts = 1, bool rt16 = false, // oldlp / adv / ret / vold are f16 planes
+                       const float *advs = nullptr);
 struct ReduceSeg {
   const float *slab;
   int S;

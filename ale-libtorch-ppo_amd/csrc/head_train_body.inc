@@ -1,0 +1,253 @@
+// head_train_body.inc - the body of the PPO head training kernel (kernels.hip), included by its two __global__ entry
+// points: head_train_kernel (ADVN = false) and head_train_advn_kernel (ADVN = true, ALEPPO_OPT_ADV_NORM_MINIBATCH).  The
+// text is shared this way, not through a __device__ function, because inlining a function changed the register
+// allocation of the default kernels (AMAX = 18: 336 instead of 402 VGPRs); included into the kernel, the ADVN = false
+// instantiations compile to the same code as before the option existed.
+// In scope: the template parameters T, AMAX, RT, VCLIP, the kernel arguments, `constexpr bool ADVN` and `advs`.
+  constexpr int A1 = AMAX + 1, HPL = 8; // H <= 512: 8 hidden units per lane
+  constexpr int NWV = AMAX > 10 ? 4 : 8; // waves per workgroup
+  extern __shared__ float smem[];
+  float *sW = smem;                    // [(A+1)][H]
+  float *sAcc = smem + (size_t)A1 * H; // [(A+1)][H] cross-wave wgrad accumulator
+  float *sB = sAcc + (size_t)(A1 > NWV ? A1 : NWV) * H; // [NWV][A1]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long rows_per_blk = (B + gridDim.x - 1) / gridDim.x;
+  const long row0 = (long)blockIdx.x * rows_per_blk, row1 = min(B, row0 + rows_per_blk);
+  // Everything a row needs (h, action, advantage, return, mask and ALL A old log-probs, so that nothing is a
+  // dependent load) is fetched ONE ROW AHEAD: a row's memory round trips hide behind the previous row's math.
+  // The first row's loads are issued before the weight staging below.
+  float hnext[HPL], olp_n[AMAX], adv_n = 0.f, ret_n = 0.f, vold_n = 0.f;
+  int act_n = 0;
+  bool mask_n = false;
+  auto fetch = [&](long r) {
+    const bool ok = r < row1;
+    // lane l owns hidden units 4l .. 4l+3 and H/2 + 4l .. H/2 + 4l+3 (H % 8 == 0): 16-byte loads instead of scalar
+    // ones, and consecutive lanes touch consecutive 16-byte pieces (coalesced; conflict-free LDS reads of the weights)
+#pragma unroll
+    for (int i = 0; i < HPL; ++i)
+      hnext[i] = 0.f;
+    if (ok && lane * 8 < H) { // h arrives as `hparts` split-K partial slabs [hparts][B][H] (slab 0 carries the bias)
+      for (int p = 0; p < hparts; ++p) {
+        const float *src = h + ((size_t)p * B + r) * H + lane * 4;
+        const f32x4 v0 = *reinterpret_cast<const f32x4 *>(src), v1 = *reinterpret_cast<const f32x4 *>(src + H / 2);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          hnext[i] += v0[i];
+          hnext[4 + i] += v1[i];
+        }
+      }
+    }
+#pragma unroll
+    for (int a = 0; a < AMAX; ++a)
+      olp_n[a] = (ok && a < A) ? (float)oldlp[(size_t)r * A + a] : 0.f;
+    act_n = ok ? act[r] : 0;
+    adv_n = ok ? (float)adv[r] : 0.f;
+    ret_n = ok ? (float)ret[r] : 0.f;
+    if constexpr (VCLIP)
+      vold_n = ok ? (float)vold[r] : 0.f;
+    mask_n = ok ? mask[r] != 0 : false;
+  };
+  fetch(row0 + wave);
+  for (int i = tid; i < (A + 1) * H; i += 64 * NWV)
+    sW[i] = Wh[i];
+  __syncthreads();
+  const float inv_nm = 1.0f / mask_count[0];
+  float adv_mean = 0.f, adv_inv = 1.f;
+  if constexpr (ADVN) {
+    adv_mean = advs[0];
+    adv_inv = advs[1];
+  }
+  float gW[A1][HPL], gb[A1];
+#pragma unroll
+  for (int a = 0; a < A1; ++a) {
+    gb[a] = 0.f;
+#pragma unroll
+    for (int i = 0; i < HPL; ++i)
+      gW[a][i] = 0.f;
+  }
+  for (long row = row0 + wave; row < row1; row += NWV) {
+    float hv[HPL], olp_c[AMAX];
+#pragma unroll
+    for (int i = 0; i < HPL; ++i)
+      hv[i] = hnext[i];
+#pragma unroll
+    for (int a = 0; a < AMAX; ++a)
+      olp_c[a] = olp_n[a];
+    const int ai = act_n;
+    const float advi = ADVN ? (adv_n - adv_mean) * adv_inv : adv_n, reti = ret_n, voldi = vold_n;
+    const bool maski = mask_n;
+    fetch(row + NWV); // next row of this wave
+    float z[A1];
+#pragma unroll
+    for (int a = 0; a < A1; ++a) {
+      float s = 0.f;
+      if (a <= A) {
+        if (lane * 8 < H) {
+          const f32x4 w0 = *reinterpret_cast<const f32x4 *>(sW + a * H + lane * 4);
+          const f32x4 w1 = *reinterpret_cast<const f32x4 *>(sW + a * H + H / 2 + lane * 4);
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            s += hv[i] * w0[i];
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            s += hv[4 + i] * w1[i];
+        }
+        s = wave_sum(s) + bh[a];
+      }
+      z[a] = s;
+    }
+    // every lane now holds logits z[0..A-1] and the value z[A]
+    const float value = [&] {
+      float v = 0.f;
+#pragma unroll
+      for (int a = 0; a < A1; ++a)
+        if (a == A)
+          v = z[a];
+      return v;
+    }();
+    float mx = -3.0e38f;
+#pragma unroll
+    for (int a = 0; a < AMAX; ++a)
+      if (a < A)
+        mx = fmaxf(mx, z[a]);
+    float se = 0.f;
+#pragma unroll
+    for (int a = 0; a < AMAX; ++a)
+      if (a < A)
+        se += expf(z[a] - mx);
+    const float lse = mx + logf(se);
+    float lp[AMAX], p[AMAX], ent = 0.f, lpa = 0.f, olpa = 0.f;
+#pragma unroll
+    for (int a = 0; a < AMAX; ++a) {
+      lp[a] = 0.f;
+      p[a] = 0.f;
+      if (a < A) {
+        lp[a] = z[a] - lse;            // losses.cc:45-47
+        p[a] = expf(lp[a]);
+        ent += p[a] * lp[a];           // losses.cc:41-43
+        if (a == ai) {
+          lpa = lp[a];
+          olpa = olp_c[a];
+        }
+      }
+    }
+    ent = -ent;
+    const float logr = lpa - olpa;
+    const float rho = expf(logr);                                        // losses.cc:33
+    const float crho = fminf(fmaxf(rho, 1.0f - hp.clip), 1.0f + hp.clip); // losses.cc:34-35
+    const float un = rho * advi, cl = crho * advi;
+    const float obj = fminf(un, cl);                                     // losses.cc:38
+    const float dv = value - reti;
+    float lv, dvg; // value loss and its derivative in v (before the mask and c_v)
+    if constexpr (VCLIP) { // aleppo.h ALEPPO_OPT_VALUE_CLIP: a select, so that inside the range vc IS value
+      const float d = value - voldi;
+      const float vc = fabsf(d) <= hp.clip ? value : voldi + copysignf(hp.clip, d);
+      const float dc = vc - reti;
+      const float lu = dv * dv, lc = dc * dc;
+      lv = 0.5f * fmaxf(lu, lc);
+      dvg = lu >= lc ? dv : 0.f; // ties: the unclipped branch; the clipped one is flat in v
+    } else {
+      lv = 0.5f * (dv * dv);                                             // losses.cc:15
+      dvg = dv;
+    }
+    const float Ltot = -obj + hp.c_v * lv - hp.c_e * ent;                // losses.cc:17-18
+    const float m = maski ? inv_nm : 0.f;                                // losses.cc:19 masked mean
+    const bool active = advi >= 0.f ? (rho <= 1.0f + hp.clip) : (rho >= 1.0f - hp.clip);
+    const float gs = active ? -rho * advi : 0.f;
+    float dz[A1];
+#pragma unroll
+    for (int a = 0; a < A1; ++a) {
+      dz[a] = 0.f;
+      if (a < A && a < AMAX)
+        dz[a] = m * (gs * ((a == ai ? 1.0f : 0.0f) - p[a < AMAX ? a : 0]) +
+                     hp.c_e * p[a < AMAX ? a : 0] * (lp[a < AMAX ? a : 0] + ent));
+      if (a == A)
+        dz[a] = m * hp.c_v * dvg;
+    }
+    if (lane == 0) {
+      ps_total[row] = Ltot;
+      ps_clipped[row] = obj;
+      ps_value[row] = lv;
+      ps_entropy[row] = ent;
+      ps_ratio[row] = rho;
+      ps_kl[row] = (rho - 1.0f) - logr;                                  // approx-KL (k3 estimator)
+      ps_cf[row] = fabsf(rho - 1.0f) > hp.clip ? 1.0f : 0.0f;           // clip fraction (strict)
+      if (logits_out) {
+#pragma unroll
+        for (int a = 0; a < AMAX; ++a)
+          if (a < A)
+            logits_out[(size_t)row * A + a] = z[a];
+        values_out[row] = value;
+      }
+    }
+    // head dgrad: dh = sum_a dz[a] * W[a][:]   and wgrad partial: gW[a][:] += dz[a] * h
+    if (lane * 8 < H) {
+      float d[HPL];
+#pragma unroll
+      for (int i = 0; i < HPL; ++i)
+        d[i] = 0.f;
+#pragma unroll
+      for (int a = 0; a < A1; ++a)
+        if (a <= A) {
+          const f32x4 w0 = *reinterpret_cast<const f32x4 *>(sW + a * H + lane * 4);
+          const f32x4 w1 = *reinterpret_cast<const f32x4 *>(sW + a * H + H / 2 + lane * 4);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            d[i] += dz[a] * w0[i];
+            d[4 + i] += dz[a] * w1[i];
+          }
+#pragma unroll
+          for (int i = 0; i < HPL; ++i)
+            gW[a][i] += dz[a] * hv[i];
+        }
+      T dr[HPL];
+#pragma unroll
+      for (int i = 0; i < HPL; ++i)
+        dr[i] = (T)d[i];
+      T *dst = dh + (size_t)row * H + lane * 4;
+      if constexpr (sizeof(T) == 2) {
+        *reinterpret_cast<u32x2 *>(dst) = reinterpret_cast<const u32x2 *>(dr)[0];
+        *reinterpret_cast<u32x2 *>(dst + H / 2) = reinterpret_cast<const u32x2 *>(dr)[1];
+      } else {
+        *reinterpret_cast<u32x4 *>(dst) = reinterpret_cast<const u32x4 *>(dr)[0];
+        *reinterpret_cast<u32x4 *>(dst + H / 2) = reinterpret_cast<const u32x4 *>(dr)[1];
+      }
+    }
+#pragma unroll
+    for (int a = 0; a < A1; ++a)
+      gb[a] += dz[a];
+  }
+  // deterministic cross-wave reduction, one head row at a time: every wave writes its partial of row a, then
+  // thread j adds the NWV partials of column j in fixed order and stores the workgroup's slab entry
+  float *sPart = sAcc; // [NWV][H] (reuses the accumulator region: (A+1)*H >= ... is not needed, H*NWV floats)
+  float *ow = slab_w + (size_t)blockIdx.x * (A + 1) * H;
+#pragma unroll
+  for (int a = 0; a < A1; ++a) {
+    if (a <= A) {
+      __syncthreads();
+#pragma unroll
+      for (int i = 0; i < HPL; ++i) {
+        const int j = (i < 4 ? 0 : H / 2) + lane * 4 + (i & 3);
+        if (lane * 8 < H)
+          sPart[wave * H + j] = gW[a][i];
+      }
+      if (lane == 0)
+        sB[wave * A1 + a] = gb[a];
+      __syncthreads();
+      for (int j = tid; j < H; j += 64 * NWV) {
+        float sum = 0.f;
+#pragma unroll
+        for (int w = 0; w < NWV; ++w)
+          sum += sPart[w * H + j];
+        ow[a * H + j] = sum;
+      }
+    }
+  }
+  __syncthreads();
+  if (tid <= A) {
+    float sb = 0.f;
+#pragma unroll
+    for (int w = 0; w < NWV; ++w)
+      sb += sB[w * A1 + tid];
+    slab_b[(size_t)blockIdx.x * (A + 1) + tid] = sb;
+  }

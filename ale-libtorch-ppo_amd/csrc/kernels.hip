@@ -550,6 +550,83 @@ void launch_mask_count(hipStream_t s, const uint8_t *mask_n, float *counts, long
   hipLaunchKernelGGL(mask_count_kernel, dim3(M), dim3(256), 0, s, mask_n, counts, B);
 }
 
+// ALEPPO_OPT_ADV_NORM_MINIBATCH: (n, S, Q) = count, sum and sum of squares of the unmasked advantages of one minibatch, in
+// double (aleppo.h), block per minibatch.  Fixed order: thread t sums samples t, t + 256, ... in turn, then the block
+// reduces with the same shuffle tree every time.  a*a of a widened float is exact in double, so a contracted fma is too.
+__device__ __forceinline__ double block_sum_256d(double v, double *s4) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+    v += __shfl_xor(v, o, 64);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0)
+    s4[wave] = v;
+  __syncthreads();
+  return (s4[0] + s4[1]) + (s4[2] + s4[3]);
+}
+// (mean_f, inv_f, std, 0) of aleppo.h from the (all-reduced) sums; n = 0: (0, 1, 0, 0)
+__device__ __forceinline__ void advn_finalise(double n, double S, double Q, float *out) {
+  if (!(n > 0.0)) {
+    out[0] = 0.f;
+    out[1] = 1.f;
+    out[2] = 0.f;
+    out[3] = 0.f;
+    return;
+  }
+  const double mean = S / n;
+  const double var = fmax(0.0, (Q - S * S / n) / fmax(n - 1.0, 1.0));
+  const double sd = sqrt(var);
+  out[0] = (float)mean;
+  out[1] = (float)(1.0 / (sd + 1e-8));
+  out[2] = (float)sd;
+  out[3] = 0.f;
+}
+template <class RT>
+__global__ __launch_bounds__(256) void advn_stats_kernel(const RT *__restrict__ adv, const uint8_t *__restrict__ mask,
+                                                         long B, double *part, float *stats) {
+  __shared__ double s4[4];
+  const RT *a = adv + (size_t)blockIdx.x * B;
+  const uint8_t *m = mask + (size_t)blockIdx.x * B;
+  double n = 0.0, S = 0.0, Q = 0.0;
+  for (long i = threadIdx.x; i < B; i += 256)
+    if (m[i]) {
+      const double x = (double)(float)a[i];
+      n += 1.0;
+      S += x;
+      Q += x * x;
+    }
+  n = block_sum_256d(n, s4);
+  S = block_sum_256d(S, s4);
+  Q = block_sum_256d(Q, s4);
+  if (threadIdx.x == 0) {
+    if (part) { // data parallel: the partial sums, all-reduced and then finalised by advn_finalise_kernel
+      part[(size_t)blockIdx.x * 4 + 0] = n;
+      part[(size_t)blockIdx.x * 4 + 1] = S;
+      part[(size_t)blockIdx.x * 4 + 2] = Q;
+      part[(size_t)blockIdx.x * 4 + 3] = 0.0;
+    } else {
+      advn_finalise(n, S, Q, stats + (size_t)blockIdx.x * 4);
+    }
+  }
+}
+__global__ __launch_bounds__(256) void advn_finalise_kernel(const double *part, float *stats, int nmb) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < nmb)
+    advn_finalise(part[(size_t)i * 4], part[(size_t)i * 4 + 1], part[(size_t)i * 4 + 2], stats + (size_t)i * 4);
+}
+void launch_advn_stats(hipStream_t s, const void *adv, const uint8_t *mask, long B, int nmb, double *part, float *stats,
+                       bool rt16) {
+  if (rt16)
+    hipLaunchKernelGGL(advn_stats_kernel<f16>, dim3(nmb), dim3(256), 0, s, static_cast<const f16 *>(adv), mask, B, part,
+                       stats);
+  else
+    hipLaunchKernelGGL(advn_stats_kernel<float>, dim3(nmb), dim3(256), 0, s, static_cast<const float *>(adv), mask, B,
+                       part, stats);
+}
+void launch_advn_finalise(hipStream_t s, const double *part, float *stats, int nmb) {
+  hipLaunchKernelGGL(advn_finalise_kernel, dim3((unsigned)((nmb + 255) / 256)), dim3(256), 0, s, part, stats, nmb);
+}
+
 // ================================================================================================
 // Per-epoch minibatch shuffling (ALEPPO_OPT_MINIBATCH_SHUFFLE; the permutation is specified in aleppo.h).  One thread per
 // position i of epoch e = blockIdx.y: a four-round Feistel network on [0, 2^(2h)) walked until it lands in [0, N).  The
@@ -640,273 +717,53 @@ void launch_shuffle_gather(hipStream_t s, const uint32_t *rk, int h, long N, int
 // use the whole 512-entry register file; with 8 waves the 256-register cap spilled the accumulators (150 us vs 22).
 // VCLIP (ALEPPO_OPT_VALUE_CLIP): the value term is the clipped one of aleppo.h against vold, the values the samples were
 // collected with; without it vold is never read.  ps_kl / ps_cf (approx-KL and clip fraction) are written either way.
+// ADVN (ALEPPO_OPT_ADV_NORM_MINIBATCH): every row's advantage a becomes (a - advs[0]) * advs[1] in fp32, this minibatch's
+// (mean_f, inv_f) from advn_stats_kernel; without it advs is never read.  The body is shared by two entry points:
+// head_train_kernel (ADVN off, the default path's instantiations) and head_train_advn_kernel (ADVN on).
+#define HEAD_PARAMS                                                                                                    \
+  const float *__restrict__ h, const float *__restrict__ Wh, const float *__restrict__ bh, const int *__restrict__ act, \
+      const RT *__restrict__ oldlp, const RT *__restrict__ adv, const RT *__restrict__ ret,                            \
+      const RT *__restrict__ vold, const uint8_t *__restrict__ mask, const float *__restrict__ mask_count, Hyper hp,   \
+      T *dh, float *ps_total, float *ps_clipped, float *ps_value, float *ps_entropy, float *ps_ratio, float *ps_kl,    \
+      float *ps_cf, float *slab_w, float *slab_b, long B, int H, int A, float *logits_out, float *values_out, int hparts
 template <class T, int AMAX, class RT, bool VCLIP>
-__global__ __launch_bounds__(AMAX > 10 ? 256 : 512) void head_train_kernel(
-    const float *__restrict__ h, const float *__restrict__ Wh, const float *__restrict__ bh,
-    const int *__restrict__ act, const RT *__restrict__ oldlp, const RT *__restrict__ adv,
-    const RT *__restrict__ ret, const RT *__restrict__ vold, const uint8_t *__restrict__ mask,
-    const float *__restrict__ mask_count, Hyper hp, T *dh, float *ps_total, float *ps_clipped, float *ps_value,
-    float *ps_entropy, float *ps_ratio, float *ps_kl, float *ps_cf, float *slab_w, float *slab_b, long B, int H, int A,
-    float *logits_out, float *values_out, int hparts) {
-  constexpr int A1 = AMAX + 1, HPL = 8; // H <= 512: 8 hidden units per lane
-  constexpr int NWV = AMAX > 10 ? 4 : 8; // waves per workgroup
-  extern __shared__ float smem[];
-  float *sW = smem;                    // [(A+1)][H]
-  float *sAcc = smem + (size_t)A1 * H; // [(A+1)][H] cross-wave wgrad accumulator
-  float *sB = sAcc + (size_t)(A1 > NWV ? A1 : NWV) * H; // [NWV][A1]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long rows_per_blk = (B + gridDim.x - 1) / gridDim.x;
-  const long row0 = (long)blockIdx.x * rows_per_blk, row1 = min(B, row0 + rows_per_blk);
-  // Everything a row needs (h, action, advantage, return, mask and ALL A old log-probs, so that nothing is a
-  // dependent load) is fetched ONE ROW AHEAD: a row's memory round trips hide behind the previous row's math.
-  // The first row's loads are issued before the weight staging below.
-  float hnext[HPL], olp_n[AMAX], adv_n = 0.f, ret_n = 0.f, vold_n = 0.f;
-  int act_n = 0;
-  bool mask_n = false;
-  auto fetch = [&](long r) {
-    const bool ok = r < row1;
-    // lane l owns hidden units 4l .. 4l+3 and H/2 + 4l .. H/2 + 4l+3 (H % 8 == 0): 16-byte loads instead of scalar
-    // ones, and consecutive lanes touch consecutive 16-byte pieces (coalesced; conflict-free LDS reads of the weights)
-#pragma unroll
-    for (int i = 0; i < HPL; ++i)
-      hnext[i] = 0.f;
-    if (ok && lane * 8 < H) { // h arrives as `hparts` split-K partial slabs [hparts][B][H] (slab 0 carries the bias)
-      for (int p = 0; p < hparts; ++p) {
-        const float *src = h + ((size_t)p * B + r) * H + lane * 4;
-        const f32x4 v0 = *reinterpret_cast<const f32x4 *>(src), v1 = *reinterpret_cast<const f32x4 *>(src + H / 2);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          hnext[i] += v0[i];
-          hnext[4 + i] += v1[i];
-        }
-      }
-    }
-#pragma unroll
-    for (int a = 0; a < AMAX; ++a)
-      olp_n[a] = (ok && a < A) ? (float)oldlp[(size_t)r * A + a] : 0.f;
-    act_n = ok ? act[r] : 0;
-    adv_n = ok ? (float)adv[r] : 0.f;
-    ret_n = ok ? (float)ret[r] : 0.f;
-    if constexpr (VCLIP)
-      vold_n = ok ? (float)vold[r] : 0.f;
-    mask_n = ok ? mask[r] != 0 : false;
-  };
-  fetch(row0 + wave);
-  for (int i = tid; i < (A + 1) * H; i += 64 * NWV)
-    sW[i] = Wh[i];
-  __syncthreads();
-  const float inv_nm = 1.0f / mask_count[0];
-  float gW[A1][HPL], gb[A1];
-#pragma unroll
-  for (int a = 0; a < A1; ++a) {
-    gb[a] = 0.f;
-#pragma unroll
-    for (int i = 0; i < HPL; ++i)
-      gW[a][i] = 0.f;
-  }
-  for (long row = row0 + wave; row < row1; row += NWV) {
-    float hv[HPL], olp_c[AMAX];
-#pragma unroll
-    for (int i = 0; i < HPL; ++i)
-      hv[i] = hnext[i];
-#pragma unroll
-    for (int a = 0; a < AMAX; ++a)
-      olp_c[a] = olp_n[a];
-    const int ai = act_n;
-    const float advi = adv_n, reti = ret_n, voldi = vold_n;
-    const bool maski = mask_n;
-    fetch(row + NWV); // next row of this wave
-    float z[A1];
-#pragma unroll
-    for (int a = 0; a < A1; ++a) {
-      float s = 0.f;
-      if (a <= A) {
-        if (lane * 8 < H) {
-          const f32x4 w0 = *reinterpret_cast<const f32x4 *>(sW + a * H + lane * 4);
-          const f32x4 w1 = *reinterpret_cast<const f32x4 *>(sW + a * H + H / 2 + lane * 4);
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-            s += hv[i] * w0[i];
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-            s += hv[4 + i] * w1[i];
-        }
-        s = wave_sum(s) + bh[a];
-      }
-      z[a] = s;
-    }
-    // every lane now holds logits z[0..A-1] and the value z[A]
-    const float value = [&] {
-      float v = 0.f;
-#pragma unroll
-      for (int a = 0; a < A1; ++a)
-        if (a == A)
-          v = z[a];
-      return v;
-    }();
-    float mx = -3.0e38f;
-#pragma unroll
-    for (int a = 0; a < AMAX; ++a)
-      if (a < A)
-        mx = fmaxf(mx, z[a]);
-    float se = 0.f;
-#pragma unroll
-    for (int a = 0; a < AMAX; ++a)
-      if (a < A)
-        se += expf(z[a] - mx);
-    const float lse = mx + logf(se);
-    float lp[AMAX], p[AMAX], ent = 0.f, lpa = 0.f, olpa = 0.f;
-#pragma unroll
-    for (int a = 0; a < AMAX; ++a) {
-      lp[a] = 0.f;
-      p[a] = 0.f;
-      if (a < A) {
-        lp[a] = z[a] - lse;            // losses.cc:45-47
-        p[a] = expf(lp[a]);
-        ent += p[a] * lp[a];           // losses.cc:41-43
-        if (a == ai) {
-          lpa = lp[a];
-          olpa = olp_c[a];
-        }
-      }
-    }
-    ent = -ent;
-    const float logr = lpa - olpa;
-    const float rho = expf(logr);                                        // losses.cc:33
-    const float crho = fminf(fmaxf(rho, 1.0f - hp.clip), 1.0f + hp.clip); // losses.cc:34-35
-    const float un = rho * advi, cl = crho * advi;
-    const float obj = fminf(un, cl);                                     // losses.cc:38
-    const float dv = value - reti;
-    float lv, dvg; // value loss and its derivative in v (before the mask and c_v)
-    if constexpr (VCLIP) { // aleppo.h ALEPPO_OPT_VALUE_CLIP: a select, so that inside the range vc IS value
-      const float d = value - voldi;
-      const float vc = fabsf(d) <= hp.clip ? value : voldi + copysignf(hp.clip, d);
-      const float dc = vc - reti;
-      const float lu = dv * dv, lc = dc * dc;
-      lv = 0.5f * fmaxf(lu, lc);
-      dvg = lu >= lc ? dv : 0.f; // ties: the unclipped branch; the clipped one is flat in v
-    } else {
-      lv = 0.5f * (dv * dv);                                             // losses.cc:15
-      dvg = dv;
-    }
-    const float Ltot = -obj + hp.c_v * lv - hp.c_e * ent;                // losses.cc:17-18
-    const float m = maski ? inv_nm : 0.f;                                // losses.cc:19 masked mean
-    const bool active = advi >= 0.f ? (rho <= 1.0f + hp.clip) : (rho >= 1.0f - hp.clip);
-    const float gs = active ? -rho * advi : 0.f;
-    float dz[A1];
-#pragma unroll
-    for (int a = 0; a < A1; ++a) {
-      dz[a] = 0.f;
-      if (a < A && a < AMAX)
-        dz[a] = m * (gs * ((a == ai ? 1.0f : 0.0f) - p[a < AMAX ? a : 0]) +
-                     hp.c_e * p[a < AMAX ? a : 0] * (lp[a < AMAX ? a : 0] + ent));
-      if (a == A)
-        dz[a] = m * hp.c_v * dvg;
-    }
-    if (lane == 0) {
-      ps_total[row] = Ltot;
-      ps_clipped[row] = obj;
-      ps_value[row] = lv;
-      ps_entropy[row] = ent;
-      ps_ratio[row] = rho;
-      ps_kl[row] = (rho - 1.0f) - logr;                                  // approx-KL (k3 estimator)
-      ps_cf[row] = fabsf(rho - 1.0f) > hp.clip ? 1.0f : 0.0f;           // clip fraction (strict)
-      if (logits_out) {
-#pragma unroll
-        for (int a = 0; a < AMAX; ++a)
-          if (a < A)
-            logits_out[(size_t)row * A + a] = z[a];
-        values_out[row] = value;
-      }
-    }
-    // head dgrad: dh = sum_a dz[a] * W[a][:]   and wgrad partial: gW[a][:] += dz[a] * h
-    if (lane * 8 < H) {
-      float d[HPL];
-#pragma unroll
-      for (int i = 0; i < HPL; ++i)
-        d[i] = 0.f;
-#pragma unroll
-      for (int a = 0; a < A1; ++a)
-        if (a <= A) {
-          const f32x4 w0 = *reinterpret_cast<const f32x4 *>(sW + a * H + lane * 4);
-          const f32x4 w1 = *reinterpret_cast<const f32x4 *>(sW + a * H + H / 2 + lane * 4);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            d[i] += dz[a] * w0[i];
-            d[4 + i] += dz[a] * w1[i];
-          }
-#pragma unroll
-          for (int i = 0; i < HPL; ++i)
-            gW[a][i] += dz[a] * hv[i];
-        }
-      T dr[HPL];
-#pragma unroll
-      for (int i = 0; i < HPL; ++i)
-        dr[i] = (T)d[i];
-      T *dst = dh + (size_t)row * H + lane * 4;
-      if constexpr (sizeof(T) == 2) {
-        *reinterpret_cast<u32x2 *>(dst) = reinterpret_cast<const u32x2 *>(dr)[0];
-        *reinterpret_cast<u32x2 *>(dst + H / 2) = reinterpret_cast<const u32x2 *>(dr)[1];
-      } else {
-        *reinterpret_cast<u32x4 *>(dst) = reinterpret_cast<const u32x4 *>(dr)[0];
-        *reinterpret_cast<u32x4 *>(dst + H / 2) = reinterpret_cast<const u32x4 *>(dr)[1];
-      }
-    }
-#pragma unroll
-    for (int a = 0; a < A1; ++a)
-      gb[a] += dz[a];
-  }
-  // deterministic cross-wave reduction, one head row at a time: every wave writes its partial of row a, then
-  // thread j adds the NWV partials of column j in fixed order and stores the workgroup's slab entry
-  float *sPart = sAcc; // [NWV][H] (reuses the accumulator region: (A+1)*H >= ... is not needed, H*NWV floats)
-  float *ow = slab_w + (size_t)blockIdx.x * (A + 1) * H;
-#pragma unroll
-  for (int a = 0; a < A1; ++a) {
-    if (a <= A) {
-      __syncthreads();
-#pragma unroll
-      for (int i = 0; i < HPL; ++i) {
-        const int j = (i < 4 ? 0 : H / 2) + lane * 4 + (i & 3);
-        if (lane * 8 < H)
-          sPart[wave * H + j] = gW[a][i];
-      }
-      if (lane == 0)
-        sB[wave * A1 + a] = gb[a];
-      __syncthreads();
-      for (int j = tid; j < H; j += 64 * NWV) {
-        float sum = 0.f;
-#pragma unroll
-        for (int w = 0; w < NWV; ++w)
-          sum += sPart[w * H + j];
-        ow[a * H + j] = sum;
-      }
-    }
-  }
-  __syncthreads();
-  if (tid <= A) {
-    float sb = 0.f;
-#pragma unroll
-    for (int w = 0; w < NWV; ++w)
-      sb += sB[w * A1 + tid];
-    slab_b[(size_t)blockIdx.x * (A + 1) + tid] = sb;
-  }
+__global__ __launch_bounds__(AMAX > 10 ? 256 : 512) void head_train_kernel(HEAD_PARAMS) {
+  constexpr bool ADVN = false;
+  const float *advs = nullptr;
+#include "head_train_body.inc"
 }
+// advs: float [4] of this minibatch (mean_f, inv_f, std, 0)
+template <class T, int AMAX, class RT, bool VCLIP>
+__global__ __launch_bounds__(AMAX > 10 ? 256 : 512) void head_train_advn_kernel(HEAD_PARAMS,
+                                                                                 const float *__restrict__ advs) {
+  constexpr bool ADVN = true;
+#include "head_train_body.inc"
+}
+#undef HEAD_PARAMS
 
 template <class T, class RT, bool VCLIP>
 static void head_train_t(hipStream_t s, const float *h, const float *Wh, const float *bh, const int *act,
                          const RT *oldlp, const RT *adv, const RT *ret, const RT *vold, const uint8_t *mask,
                          const float *mask_count, Hyper hp, void *dh, float *ps_total, float *ps_clipped,
                          float *ps_value, float *ps_entropy, float *ps_ratio, float *ps_kl, float *ps_cf, float *slab_w,
-                         float *slab_b, int nblk, long B, int H, int A, float *lo, float *vo, int hparts) {
+                         float *slab_b, int nblk, long B, int H, int A, float *lo, float *vo, int hparts,
+                         const float *advs) {
+#define HEAD_LAUNCH_ARGS                                                                                               \
+  h, Wh, bh, act, oldlp, adv, ret, vold, mask, mask_count, hp, static_cast<T *>(dh), ps_total, ps_clipped, ps_value,    \
+      ps_entropy, ps_ratio, ps_kl, ps_cf, slab_w, slab_b, B, H, A, lo, vo, hparts
 #define LAUNCH_HEAD(AM)                                                                                                \
   do {                                                                                                                 \
     const size_t sm = ((size_t)((AM + 1) + ((AM + 1) > 8 ? (AM + 1) : 8)) * H + 8 * (AM + 1)) * sizeof(float);        \
+    const void *fn = advs ? reinterpret_cast<const void *>(&head_train_advn_kernel<T, AM, RT, VCLIP>)                  \
+                          : reinterpret_cast<const void *>(&head_train_kernel<T, AM, RT, VCLIP>);                      \
     if (sm > 48 * 1024)                                                                                                \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&head_train_kernel<T, AM, RT, VCLIP>),                  \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);                                  \
-    hipLaunchKernelGGL((head_train_kernel<T, AM, RT, VCLIP>), dim3(nblk), dim3(AM > 10 ? 256 : 512), sm, s, h, Wh, bh, \
-                       act, oldlp, adv, ret, vold, mask, mask_count, hp, static_cast<T *>(dh), ps_total, ps_clipped,   \
-                       ps_value, ps_entropy, ps_ratio, ps_kl, ps_cf, slab_w, slab_b, B, H, A, lo, vo, hparts);         \
+      (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);                              \
+    if (advs)                                                                                                          \
+      hipLaunchKernelGGL((head_train_advn_kernel<T, AM, RT, VCLIP>), dim3(nblk), dim3(AM > 10 ? 256 : 512), sm, s,     \
+                         HEAD_LAUNCH_ARGS, advs);                                                                      \
+    else                                                                                                               \
+      hipLaunchKernelGGL((head_train_kernel<T, AM, RT, VCLIP>), dim3(nblk), dim3(AM > 10 ? 256 : 512), sm, s,          \
+                         HEAD_LAUNCH_ARGS);                                                                            \
   } while (0)
   if (A <= 4)
     LAUNCH_HEAD(4);
@@ -917,17 +774,18 @@ static void head_train_t(hipStream_t s, const float *h, const float *Wh, const f
   else
     LAUNCH_HEAD(18);
 #undef LAUNCH_HEAD
+#undef HEAD_LAUNCH_ARGS
 }
 void launch_head_train(hipStream_t s, const float *h, const float *Wh, const float *bh, const int *act,
                        const void *oldlp, const void *adv, const void *ret, const void *vold, const uint8_t *mask,
                        const float *mask_count, Hyper hp, void *dh, int prec, float *ps_total, float *ps_clipped,
                        float *ps_value, float *ps_entropy, float *ps_ratio, float *ps_kl, float *ps_cf, float *slab_w,
                        float *slab_b, int nblk, long B, int H, int A, float *logits_out, float *values_out, int hparts,
-                       bool rt16) {
+                       bool rt16, const float *advs) {
 #define HEAD_ARGS(RT)                                                                                                  \
   s, h, Wh, bh, act, static_cast<const RT *>(oldlp), static_cast<const RT *>(adv), static_cast<const RT *>(ret),       \
       static_cast<const RT *>(vold), mask, mask_count, hp, dh, ps_total, ps_clipped, ps_value, ps_entropy, ps_ratio,   \
-      ps_kl, ps_cf, slab_w, slab_b, nblk, B, H, A, logits_out, values_out, hparts
+      ps_kl, ps_cf, slab_w, slab_b, nblk, B, H, A, logits_out, values_out, hparts, advs
 #define HEAD_T(T, RT)                                                                                                  \
   do {                                                                                                                 \
     if (vold)                                                                                                          \

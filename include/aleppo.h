@@ -115,12 +115,15 @@ typedef enum {
 } aleppo_field;
 
 /* Per-sample training metrics (ai::ppo::train::Metrics, src/ai/ppo/train.h:64-109), [epochs,M,B], read with
- * aleppo_read_train_metric; fields 5-8 are extensions (the reference has none).  With logr = logp(a) - old_logp(a) and
+ * aleppo_read_train_metric; fields 5-10 are extensions (the reference has none).  With logr = logp(a) - old_logp(a) and
  * rho = exp(logr) per sample, computed on every update whatever ALEPPO_OPT_VALUE_CLIP is:
  *   approx_kl     = (rho - 1) - logr                  (the "k3" estimator CleanRL logs as approx_kl)
  *   clip_fraction = |rho - 1| > clip_param ? 1 : 0     (strict)
  * The two MEAN fields are the masked means of those planes per minibatch, float [epochs,M] (count = epochs * M), with the
- * denominator of aleppo_minibatch_metrics: the global unmasked count (under data parallelism they are global means). */
+ * denominator of aleppo_minibatch_metrics: the global unmasked count (under data parallelism they are global means).
+ * Fields 9-10 are the statistics ALEPPO_OPT_ADV_NORM_MINIBATCH normalised each minibatch's advantages with in the last
+ * aleppo_train, float [epochs,M] (count = epochs * M; with contiguous minibatches every epoch's row is the same): mean_f
+ * and (float)std as defined there.  Reading them after an update that ran with the option off is ALEPPO_ERR_RUNTIME. */
 typedef enum {
   ALEPPO_M_TOTAL_LOSSES = 0,
   ALEPPO_M_CLIPPED_LOSSES = 1,
@@ -130,7 +133,9 @@ typedef enum {
   ALEPPO_M_APPROX_KL = 5,          /* [epochs,M,B] per sample, unmasked, in aleppo_read_sample_order order */
   ALEPPO_M_CLIP_FRACTION = 6,      /* [epochs,M,B] per sample (0 / 1), same conventions */
   ALEPPO_M_MEAN_APPROX_KL = 7,     /* [epochs,M] masked means */
-  ALEPPO_M_MEAN_CLIP_FRACTION = 8  /* [epochs,M] masked means */
+  ALEPPO_M_MEAN_CLIP_FRACTION = 8, /* [epochs,M] masked means */
+  ALEPPO_M_ADV_MEAN = 9,           /* [epochs,M] mean_f of ALEPPO_OPT_ADV_NORM_MINIBATCH */
+  ALEPPO_M_ADV_STD = 10            /* [epochs,M] (float)std of ALEPPO_OPT_ADV_NORM_MINIBATCH */
 } aleppo_metric_field;
 
 /* ------------------------------------------------------------------ lifetime */
@@ -242,7 +247,7 @@ int aleppo_finish_rollout(aleppo_ctx *ctx, const float *noise);
 int aleppo_train(aleppo_ctx *ctx, double lr, int epochs, int num_mini_batches,
                  aleppo_minibatch_metrics *out_metrics);
 /* Per-sample metric tensors of the last aleppo_train, float [epochs,M,B], in the order of aleppo_read_sample_order:
- * element [e][m][b] belongs to logical sample order[e][m*B + b].  ALEPPO_M_MEAN_* fields: float [epochs,M], count =
+ * element [e][m][b] belongs to logical sample order[e][m*B + b].  Fields 7-10: float [epochs,M], count =
  * epochs * M. */
 int aleppo_read_train_metric(aleppo_ctx *ctx, int metric_field, float *dst, size_t count);
 /* Sample order of the last aleppo_train, int32 [epochs][N] (count = epochs * N, N = the batch's sample count): row e,
@@ -376,7 +381,7 @@ typedef enum {
                                       1: every epoch of every aleppo_train uses a fresh permutation of the N local samples
                                       (the keyed bijection documented at aleppo_read_sample_order), on every schedule -
                                       eager or ALEPPO_OPT_UPDATE_GRAPH, fp32 or bf16, one GPU or data parallel */
-  ALEPPO_OPT_VALUE_CLIP = 13       /* value-function clipping (CleanRL clip_vloss, baselines ppo2).  0 (default): the
+  ALEPPO_OPT_VALUE_CLIP = 13,      /* value-function clipping (CleanRL clip_vloss, baselines ppo2).  0 (default): the
                                       reference's value loss 0.5 (v - R)^2.  1: clipped at c = config.clip_param; any other
                                       value is ALEPPO_ERR_INVALID_ARGUMENT.  Per sample, v = the value head's output, R = the
                                       return, v_old = the value stored when the sample was collected:
@@ -391,6 +396,30 @@ typedef enum {
                                       (ALEPPO_F_VALUES) returns; of a caller batch, what aleppo_set_batch_values stored:
                                       aleppo_train on a caller batch without them is ALEPPO_ERR_RUNTIME.  The same on every
                                       schedule, like ALEPPO_OPT_MINIBATCH_SHUFFLE */
+  ALEPPO_OPT_ADV_NORM_MINIBATCH = 14 /* per-minibatch advantage normalisation (CleanRL norm_adv, SB3 normalize_advantage).
+                                      0 (default): the advantages as stored.  1: normalised per minibatch; any other value
+                                      is ALEPPO_ERR_INVALID_ARGUMENT.  Read at each aleppo_train.  For every (epoch e,
+                                      minibatch m) of the call:
+                                        sample set: the minibatch's unmasked samples (mask = !episode_start, the loss's
+                                          mask) in the call's order, contiguous or shuffled; with data parallelism the
+                                          global minibatch, the union over ranks (like the masked-mean count)
+                                        sums, in double: n = count, S = sum a, Q = sum a^2, a = the advantage as stored
+                                          widened to fp32 and then to double; each rank sums in a fixed order and the
+                                          ranks' (n, S, Q) are all-reduced in double
+                                        mean = S / n,  var = max(0, (Q - S*S/n) / max(n - 1, 1))  (unbiased, like
+                                          torch.std),  std = sqrt(var),  mean_f = (float)mean,
+                                          inv_f = (float)(1 / (std + 1e-8))  (computed in double)
+                                        n = 0: mean_f = 0, inv_f = 1 (and std = 0); such a minibatch contributes nothing
+                                        every sample of the minibatch, masked or not, uses a^ = (a - mean_f) * inv_f in fp32
+                                          in place of a wherever the loss uses the advantage: the surrogate, the clip
+                                          activity test and the gradient.  a^ is never stored (with ALEPPO_ROLLOUT_FP16
+                                          planes it is not rounded to half)
+                                      It composes with config.advantage_norm = 1 (the whole-batch normalisation of
+                                      aleppo_finish_rollout runs first, this one on top of it in the update) and works with
+                                      ALEPPO_OPT_MINIBATCH_SHUFFLE, ALEPPO_OPT_VALUE_CLIP, ALEPPO_OPT_UPDATE_GRAPH, fp32 and
+                                      bf16, rollout and aleppo_set_batch batches, one GPU or data parallel.  The statistics
+                                      depend only on a minibatch's sample set, so one call of E epochs equals E one-epoch
+                                      calls bit for bit.  Read back: ALEPPO_M_ADV_MEAN / ALEPPO_M_ADV_STD */
 } aleppo_option;
 int aleppo_set_option(aleppo_ctx *ctx, int option, int value);
 /* Current value of an option; for ALEPPO_OPT_UPDATE_GRAPH the number of graph launches so far (0 = every update ran

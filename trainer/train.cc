@@ -31,7 +31,8 @@
 // wait that aleppo_release_step lifts when they are done: aleppo_arm_step in include/aleppo.h; false: aleppo_step),
 // shuffle_minibatches: false, clip_value_loss: false (ALEPPO_OPT_VALUE_CLIP: CleanRL's clip_vloss), target_kl (absent or
 // <= 0: off; else the update runs one epoch per aleppo_train call and stops after the epoch whose LAST minibatch's
-// approx-KL exceeds it, CleanRL's rule; exact, because E one-epoch calls equal one call of E epochs).
+// approx-KL exceeds it, CleanRL's rule; exact, because E one-epoch calls equal one call of E epochs),
+// minibatch_advantage_norm: false (ALEPPO_OPT_ADV_NORM_MINIBATCH: CleanRL's norm_adv; logs mean_advantage_std).
 // Data parallelism (no reference counterpart): start one process per GPU with RANK / WORLD_SIZE / LOCAL_RANK
 // in the environment (torchrun / mpirun style).  Rank r owns the contiguous environment block
 // [r * E / W, (r + 1) * E / W) and GPU LOCAL_RANK; rank 0 creates the RCCL id, hands it to the others through the file
@@ -74,6 +75,7 @@ struct Config {
   bool record_observation = false, record_video = false, cuda_graph = false, deterministic = false;
   bool shuffle_minibatches = false; // extension: a fresh sample permutation per epoch (ALEPPO_OPT_MINIBATCH_SHUFFLE)
   bool clip_value_loss = false;     // extension: value-function clipping (ALEPPO_OPT_VALUE_CLIP)
+  bool minibatch_advantage_norm = false; // extension: per-minibatch advantage normalisation (ALEPPO_OPT_ADV_NORM_MINIBATCH)
   double target_kl = 0.0;           // extension: early stop of the update's epochs on approx-KL (<= 0: off)
   // extensions
   std::string precision = "fp32", rollout_precision = "fp32";
@@ -153,6 +155,7 @@ static Config load_config(const std::string &path) { // keys / defaults of src/b
   c.cuda_graph = as_bool(kv, "cuda_graph", false);
   c.shuffle_minibatches = as_bool(kv, "shuffle_minibatches", false);
   c.clip_value_loss = as_bool(kv, "clip_value_loss", false);
+  c.minibatch_advantage_norm = as_bool(kv, "minibatch_advantage_norm", false);
   c.target_kl = as<double>(kv, "target_kl", 0.0);
   c.deterministic = as_bool(kv, "deterministic", false);
   c.precision = as<std::string>(kv, "precision", "fp32");
@@ -799,6 +802,8 @@ int main(int argc, char **argv) {
       check(ctx, aleppo_set_option(ctx, ALEPPO_OPT_MINIBATCH_SHUFFLE, 1));
     if (cfg.clip_value_loss) // extension: the clipped value loss of ppo2 / CleanRL (clip range = clip_param)
       check(ctx, aleppo_set_option(ctx, ALEPPO_OPT_VALUE_CLIP, 1));
+    if (cfg.minibatch_advantage_norm) // extension: each minibatch's advantages normalised before the loss (norm_adv)
+      check(ctx, aleppo_set_option(ctx, ALEPPO_OPT_ADV_NORM_MINIBATCH, 1));
     if (prof.on())
       check(ctx, aleppo_profile_enable(ctx, 1));
     std::vector<std::pair<std::string, bool>> hparam_flags{{"record_observation", cfg.record_observation},
@@ -809,6 +814,8 @@ int main(int argc, char **argv) {
       hparam_flags.emplace_back("shuffle_minibatches", true);
     if (cfg.clip_value_loss)
       hparam_flags.emplace_back("clip_value_loss", true);
+    if (cfg.minibatch_advantage_norm)
+      hparam_flags.emplace_back("minibatch_advantage_norm", true);
     logger.add_hparams( // get_parameters (train.cc:76-105), same keys
         {{"total_environments", (double)cfg.total_environments}, {"hidden_size", (double)cfg.hidden_size},
          {"action_size", (double)cfg.action_size}, {"horizon", (double)cfg.horizon}, {"max_steps", (double)cfg.max_steps},
@@ -932,6 +939,7 @@ int main(int argc, char **argv) {
     // metrics of every epoch that ran: per minibatch, and the per-sample planes of log_data's histograms ([epochs][N])
     std::vector<aleppo_minibatch_metrics> m((size_t)cfg.num_epochs * nmb);
     std::vector<float> kl((size_t)cfg.num_epochs * nmb), cf((size_t)cfg.num_epochs * nmb);
+    std::vector<float> adv_std(cfg.minibatch_advantage_norm ? (size_t)cfg.num_epochs * nmb : 0);
     const std::pair<int, const char *> sample_fields[5] = {{ALEPPO_M_TOTAL_LOSSES, "losses"},
                                                            {ALEPPO_M_CLIPPED_LOSSES, "clipped_losses"},
                                                            {ALEPPO_M_VALUE_LOSSES, "value_losses"},
@@ -955,6 +963,8 @@ int main(int argc, char **argv) {
         Profile::Span sp_read(&prof, "read_train_metrics");
         check(ctx, aleppo_read_train_metric(ctx, ALEPPO_M_MEAN_APPROX_KL, kl.data() + e0 * nmb, per_call * nmb));
         check(ctx, aleppo_read_train_metric(ctx, ALEPPO_M_MEAN_CLIP_FRACTION, cf.data() + e0 * nmb, per_call * nmb));
+        if (cfg.minibatch_advantage_norm)
+          check(ctx, aleppo_read_train_metric(ctx, ALEPPO_M_ADV_STD, adv_std.data() + e0 * nmb, per_call * nmb));
         for (size_t k = 0; k < 5; ++k)
           check(ctx, aleppo_read_train_metric(ctx, sample_fields[k].first, planes[k].data() + e0 * N, per_call * N));
         epochs_run += per_call;
@@ -998,6 +1008,8 @@ int main(int argc, char **argv) {
       logger.add_scalar("mean_ratio", step, avg(&aleppo_minibatch_metrics::ratio));
       logger.add_scalar("mean_approx_kl", step, avgv(kl));
       logger.add_scalar("mean_clip_fraction", step, avgv(cf));
+      if (cfg.minibatch_advantage_norm) // (the std each minibatch's advantages were divided by, before the 1e-8)
+        logger.add_scalar("mean_advantage_std", step, avgv(adv_std));
       if (cfg.target_kl > 0)
         logger.add_scalar("update_epochs", step, (float)epochs_run);
       logger.add_scalar("learning_rate", step, (float)lr);
