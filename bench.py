@@ -9,7 +9,10 @@ Synthetic inputs are resident in HBM before the timed region.  value = env-steps
 counting (like the reference, rollout.cc:225) only non-episode-start slots.
 
 Contract: python bench.py --gpus N --steps K --warmup W ; for N>1 launched by torch.distributed.run
-(one rank per GPU, RCCL).  Prints ONE JSON line on rank 0.
+(one rank per GPU, RCCL).  Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps, writes
+--dump-outputs and prints that line.  Everything else it can report takes runs of its own and is measured only with
+--full (null otherwise): the per-kernel roofline passes, the fused-backward on / off leg, the frames-in-host-memory legs,
+the CPU baseline, the v1.yaml-shape leg and the ratios to the reference's published figure.
 """
 import argparse
 import json
@@ -231,7 +234,7 @@ def run(args):
     # one rollout (acting shapes) and one update (training shapes) are profiled separately
     roofline = None
     phase = {}
-    if True:  # EVERY rank runs the profiled passes (finish_rollout / train hold collectives); rank 0 reports
+    if args.full:  # EVERY rank runs the profiled passes (finish_rollout / train hold collectives); rank 0 reports
         def rollout_only():
             rew, te, tr, st = plans[-1]
             ra, ta, ua, sa = rew.ctypes.data, te.ctypes.data, tr.ctypes.data, st.ctypes.data
@@ -334,7 +337,8 @@ def run(args):
     # ALEPPO_OPT_FUSED_BWD = 0: three launches on two streams; csrc/conv_bwd_fused.hpp): the same update both ways,
     # alternating, same process
     fused_bwd = None
-    if rank == 0 and world == 1 and args.dtype == "bf16" and hasattr(pkg, "OPT_FUSED_BWD") and not args.no_host_legs:
+    if args.full and rank == 0 and world == 1 and args.dtype == "bf16" and hasattr(pkg, "OPT_FUSED_BWD") and \
+            not args.no_host_legs:
         t_on, t_off = [], []
         for rep in range(4):
             for on, acc in ((2, t_on), (0, t_off)):
@@ -353,7 +357,7 @@ def run(args):
     # ---- the SAME workload with the frames where a host emulator leaves them (rollout.cc:325-326): page-locked host
     # memory the ingest kernel reads in place over PCIe (ALEPPO_HOST_MAPPED).  Reported beside `value`, never as it.
     host_legs = None
-    if rank == 0 and world == 1 and not args.no_host_legs:
+    if args.full and rank == 0 and world == 1 and not args.no_host_legs:
         host_legs = {}
         hsteps = max(2, min(args.steps, 5))
         # (+ the metric's own wording, "84x84x4 uint8 batches": finished 84x84 frames resident in HBM, no preprocessing)
@@ -399,7 +403,7 @@ def run(args):
 
     # ---- CPU baseline beside it (rank 0, N=1 only): the reference's own compiled CPU-libtorch path
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(E, T, A, epochs, M)
 
     last_loss, last_norm = float(metrics["loss"][-1, -1]), float(metrics["grad_norm"][-1, -1])
@@ -409,7 +413,7 @@ def run(args):
     # ---- secondary leg: the reference's configs/v1.yaml shape (4096 envs x T=5, 1 epoch, 16 minibatches of 1280) -
     # the configuration its published ~26 k env-steps/s was quoted on.  N=1 only, reported beside `value`.
     v1 = None
-    if rank == 0 and world == 1 and not args.no_v1:
+    if args.full and rank == 0 and world == 1 and not args.no_v1:
         try:
             v1 = v1_shape_leg(pkg, args, local_rank)
         except Exception as e:  # noqa: BLE001
@@ -430,7 +434,7 @@ def run(args):
                        "dp_schedule_forced": bool(args.force_comm and world == 1)},
             "roofline": roofline, "cpu_baseline": cpu,
             "frames_84_hbm": (host_legs or {}).pop("frames_84_hbm", None), "host_frames": host_legs,
-            "vs_reference_published_v1_26289": round(value / 26289.0, 2), "v1_shape": v1,
+            "vs_reference_published_v1_26289": round(value / 26289.0, 2) if args.full else None, "v1_shape": v1,
             "fused_bwd_option": fused_bwd,
             "last_loss": last_loss, "last_grad_norm": last_norm,
         }
@@ -568,6 +572,9 @@ if __name__ == "__main__":
     ap.add_argument("--epochs", type=int, default=4)
     ap.add_argument("--minibatches", type=int, default=4)
     ap.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also take the roofline passes, the fused-backward, host-frames and "
+                         "v1.yaml-shape legs and the CPU baseline (each --no-* below leaves one out)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--python-slot-loop", action="store_true",
                     help="drive the per-slot act/step loop from Python instead of aleppo_replay_rollout")

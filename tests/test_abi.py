@@ -118,14 +118,14 @@ def test_option_and_location_constants_match_the_header(pkg):
 
 @pytest.mark.gpu
 def test_bench_line_keeps_the_contract():
-    """`python bench.py` (short: 2 steps, no CPU baseline / host legs / v1 leg) prints ONE JSON line with the keys the driver
-    reads, the dominant kernel's roofline block (achieved / peak = frac, algorithmic bytes, the kernel-source stamp) and - on a
-    1-GPU bf16 run with the legs on - the fused-backward option leg."""
+    """`python bench.py --full` (short: 2 steps, no CPU baseline / host legs / v1 leg) prints ONE JSON line with the keys the
+    driver reads, the dominant kernel's roofline block (achieved / peak = frac, algorithmic bytes, the kernel-source stamp) and
+    - on a 1-GPU bf16 run with the legs on - the fused-backward option leg."""
     import json
     import subprocess
     import sys
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                        "--no-host-legs", "--no-v1"], capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1",
+                        "--no-cpu-baseline", "--no-host-legs", "--no-v1"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -140,3 +140,28 @@ def test_bench_line_keeps_the_contract():
         assert k in rf, k
     assert rf["bound"] in ("hbm", "mfma") and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-3
     assert rf["kernel"] in rf["update_kernels"] and rf["update_kernels"][rf["kernel"]]["ms"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_measures_only_the_headline(tmp_path):
+    """`python bench.py` without --full stops after the timed steps: the line carries the headline keys and the last timed
+    step's loss, --dump-outputs still writes what that step computed, and everything --full measures in runs of its own
+    (roofline passes, fused-backward / host-frames / v1-shape legs, CPU baseline, reference ratio) is null."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--dump-outputs",
+                        str(tmp_path)], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "env-steps/s" and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["higher_is_better"] is True and d["dtype"] == "bf16"
+    for k in ("roofline", "cpu_baseline", "frames_84_hbm", "host_frames", "vs_reference_published_v1_26289", "v1_shape",
+              "fused_bwd_option"):
+        assert d[k] is None, k
+    assert "frame leg" not in r.stderr and "cpu baseline" not in r.stderr
+    assert (tmp_path / "params.npy").exists()
+    assert float(np.load(tmp_path / "train_loss.npy")[-1, -1]) == d["last_loss"]

@@ -23,9 +23,9 @@ python3 tests/tools/pmc_traffic.py $OUT/pmc_fetch $OUT/pmc_write $OUT/kt > $OUT/
 python3 tests/tools/pmc_summary.py $OUT/pmc_sq > $OUT/pmc_sq.json || exit 1
 cp $OUT/pmc_traffic.json profiles/${TAG}_pmc_traffic.json   # (on the box: lets the bench runs below quote it)
 echo "[profiles] bench (un-profiled)"; date
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_final.log 2> $OUT/bench_final.err || exit 1
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_final.log 2> $OUT/bench_final.err || exit 1
 echo "[profiles] bench under rocprofv3 --kernel-trace --stats"; date
-rocprofv3 --kernel-trace --stats -d $OUT/prof_bench -o bench -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-v1 --no-host-legs > $OUT/bench_prof.log 2> $OUT/bench_prof.err || exit 1
+rocprofv3 --kernel-trace --stats -d $OUT/prof_bench -o bench -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-v1 --no-host-legs > $OUT/bench_prof.log 2> $OUT/bench_prof.err || exit 1
 # keep the merge-back small: the raw rocpd database is summarised here, only the summary travels
 python3 tests/tools/rocpd_stats.py $OUT/prof_bench/bench_results.db $OUT/bench_kernel_stats > $OUT/bench_kernel_stats.txt || exit 1
 rm -rf $OUT/prof_bench $OUT/kt $OUT/pmc_fetch $OUT/pmc_write $OUT/pmc_sq

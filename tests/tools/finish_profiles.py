@@ -40,7 +40,7 @@ json.dump(sq, open(os.path.join(P, f"{tag}_pmc_sq_update_kernels.json"), "w"), i
 
 rows = list(csv.DictReader(open(os.path.join(P, f"{tag}_bench_kernel_stats.csv"))))
 r = json.loads(lines(os.path.join(G, "bench_prof.log"), lambda l: l.startswith("{"))[-1])["roofline"]
-md = [f"# rocprofv3 --kernel-trace --stats -d gpurun_out/{tag}/prof_bench -o bench -- python3 bench.py --steps 10 --warmup 3 "
+md = [f"# rocprofv3 --kernel-trace --stats -d {tag}/prof_bench -o bench -- python3 bench.py --full --steps 10 --warmup 3 "
       "--no-cpu-baseline --no-v1 --no-host-legs (MI355X)", "",
       "Summary exported from the rocpd database with `tests/tools/rocpd_stats.py`. The update runs 16 times: 15 updates on "
       "the timed", "region's two-stream schedule (weight-gradient kernels + slab reduce co-scheduled on a second stream) and, "

@@ -14,7 +14,7 @@ out = os.path.join(ROOT, "profiles", "r01_bench_kernel_stats_final")
 rocpd_stats.main(os.path.join(G, "prof_final", "bench_results.db"), out)
 rows = list(csv.DictReader(open(out + ".csv")))
 r = json.loads([l for l in open(os.path.join(G, "b_prof.log")) if l.startswith("{")][-1])["roofline"]
-md = ["# rocprofv3 --kernel-trace --stats -d gpurun_out/prof_final -o bench -- python3 bench.py --no-cpu-baseline --no-v1 "
+md = ["# rocprofv3 --kernel-trace --stats -d prof_final -o bench -- python3 bench.py --full --no-cpu-baseline --no-v1 "
       "(MI355X, round 1 final build)", "",
       "Summary exported from the rocpd database with `tests/tools/rocpd_stats.py`. The update runs 16 times: 15 updates on "
       "the timed", "region's two-stream schedule (wgrad kernels + slab reduce co-scheduled on a second stream) and, last, "

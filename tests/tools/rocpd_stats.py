@@ -1,6 +1,7 @@
-"""Kernel statistics from a rocprofv3 rocpd database (`rocprofv3 --kernel-trace --stats -d DIR -o NAME -- python3 bench.py ...`
-writes DIR/NAME_results.db on this image).  Prints / writes the per-kernel summary (calls, total, average, share) and,
-for the update kernels, the average over the launches of the LAST update separately: bench.py's final profiling pass
+"""Kernel statistics from a rocprofv3 rocpd database (`rocprofv3 --kernel-trace --stats -d DIR -o NAME --
+python3 bench.py --full ...` writes DIR/NAME_results.db).  Prints / writes the per-kernel summary (calls, total,
+average, share) and, for the update kernels, the average over the launches of the LAST update separately: bench.py's
+final profiling pass
 runs that update with every kernel alone on the main stream (ALEPPO_OPT_SERIAL_UPDATE), all earlier updates use the
 timed region's two-stream schedule.
 
