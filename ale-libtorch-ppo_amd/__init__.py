@@ -17,6 +17,7 @@ Sub-namespaces mirror the reference's C++ namespaces for this path:
 """
 import ctypes as C
 import os
+import struct
 from types import SimpleNamespace
 
 import numpy as np
@@ -37,9 +38,10 @@ UNIQUE_ID_BYTES = 128
 FIELDS = dict(observations=0, actions=1, rewards=2, masks=3, logits=4, values=5, advantages=6, returns=7,
               log_probs=8, terminals=9, truncations=10, current_obs=11, next_values=12)
 METRIC_FIELDS = dict(total_losses=0, clipped_losses=1, value_losses=2, entropies=3, ratio=4, approx_kl=5,
-                     clip_fraction=6)
-# the [epochs, M] masked means of approx_kl / clip_fraction (aleppo_read_train_metric; Engine.train_diagnostics)
-METRIC_MEAN_FIELDS = dict(approx_kl=7, clip_fraction=8)
+                     clip_fraction=6, kl=11)  # (kl: OPT_KL_PENALTY's exact KL per sample)
+# the [epochs, M] masked means of approx_kl / clip_fraction (aleppo_read_train_metric; Engine.train_diagnostics) and of
+# OPT_KL_PENALTY's exact KL (Engine.kl_divergence)
+METRIC_MEAN_FIELDS = dict(approx_kl=7, clip_fraction=8, kl=12)
 # the [epochs, M] statistics of OPT_ADV_NORM_MINIBATCH (aleppo_read_train_metric; Engine.advantage_stats)
 METRIC_ADV_FIELDS = dict(mean=9, std=10)
 KERNEL_CLASSES = dict(ingest=0, gae=1, head=2, adam=3, conv1_fwd=4, conv2_fwd=5, conv3_fwd=6, fc_fwd=7, fc_dgrad=8,
@@ -56,6 +58,8 @@ OPT_FUSED_BWD = 11
 OPT_MINIBATCH_SHUFFLE = 12
 OPT_VALUE_CLIP = 13
 OPT_ADV_NORM_MINIBATCH = 14
+OPT_KL_PENALTY = 15
+OPT_KL_COEF = 16  # (the value is beta's binary32 bit pattern: Engine.set_kl_coef / Engine.kl_coef)
 
 EXPORTS = [
     "aleppo_abi_version", "aleppo_create", "aleppo_destroy", "aleppo_last_error", "aleppo_param_count",
@@ -414,7 +418,8 @@ class Engine:
         """{"approx_kl", "clip_fraction"}: float32 [epochs, M] masked means of the last train (aleppo.h: the k3
         approx-KL estimator and the strict clip fraction, over the global unmasked count)"""
         out = {}
-        for name, field in METRIC_MEAN_FIELDS.items():
+        for name in ("approx_kl", "clip_fraction"):
+            field = METRIC_MEAN_FIELDS[name]
             a = np.zeros((epochs, M), np.float32)
             self._c(lib().aleppo_read_train_metric(self._ctx, field, _ptr(a), C.c_size_t(a.size)))
             out[name] = a
@@ -429,6 +434,21 @@ class Engine:
             self._c(lib().aleppo_read_train_metric(self._ctx, field, _ptr(a), C.c_size_t(a.size)))
             out.append(a)
         return tuple(out)
+
+    def kl_divergence(self, epochs, M):
+        """float32 [epochs, M] masked means of the exact KL(pi_old || pi) OPT_KL_PENALTY computed in the last train
+        (global means under data parallelism); the per-sample plane is read_train_metric("kl", ...)"""
+        a = np.zeros((epochs, M), np.float32)
+        self._c(lib().aleppo_read_train_metric(self._ctx, METRIC_MEAN_FIELDS["kl"], _ptr(a), C.c_size_t(a.size)))
+        return a
+
+    def set_kl_coef(self, beta):
+        """OPT_KL_COEF: beta of OPT_KL_PENALTY (a finite non-negative float, rounded to float32), passed as its bits"""
+        self.set_option(OPT_KL_COEF, struct.unpack("<i", struct.pack("<f", beta))[0])
+
+    def kl_coef(self):
+        """the float32 beta of OPT_KL_COEF"""
+        return struct.unpack("<f", struct.pack("<I", self.get_option(OPT_KL_COEF) & 0xFFFFFFFF))[0]
 
     def sample_order(self, epochs):
         """aleppo_read_sample_order: int32 [epochs, N], row e = the logical samples of epoch e in minibatch order

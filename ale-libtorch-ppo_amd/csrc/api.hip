@@ -508,7 +508,7 @@ extern "C" void aleppo_destroy(aleppo_ctx *c) {
                  c->sumsq_part, c->metric_ps, c->metric_red, c->grad_norms, c->adv_stats, c->stage_u8, c->stage_obs,
                  c->adam_sched, c->rb_tmp[0], c->rb_tmp[1], c->order, c->act_p, c->oldlp_p, c->adv_p,
                  c->ret_p,  c->mask_p,   c->mask_counts_ep, c->shuf_keys, c->val_n, c->val_p, c->advn_part,
-                 c->advn_stats};
+                 c->advn_stats, c->kl_ps, c->kl_beta};
   for (void *p : dev)
     if (p)
       hipFree(p);
@@ -517,7 +517,7 @@ extern "C" void aleppo_destroy(aleppo_ctx *c) {
   if (c->Pc && c->Pc != c->P)
     hipFree(c->Pc);
   void *host[] = {c->h_go, c->h_actions, c->h_step, c->h_rec, c->h_frames, c->h_noise, c->h_err, c->h_metric_red,
-                  c->h_adam_sched, c->h_shuf_keys, c->h_advn_stats};
+                  c->h_adam_sched, c->h_shuf_keys, c->h_advn_stats, c->h_kl_beta};
   for (void *p : host)
     if (p)
       hipHostFree(p);
@@ -596,7 +596,7 @@ extern "C" int aleppo_export_grads(aleppo_ctx *c, float *flat, size_t count) {
   if (rc || c->last_epochs * c->last_M == 0)
     return rc;
   const size_t nm = (size_t)c->last_epochs * c->last_M;
-  const float norm = c->h_metric_red[nm * 8 + nm - 1];
+  const float norm = c->h_metric_red[nm * METRIC_REC + nm - 1];
   float coef = c->cfg.max_gradient_norm / (norm + 1e-6f);
   coef = std::fmin(coef, 1.0f);
   for (size_t i = 0; i < count; ++i)
@@ -1156,12 +1156,14 @@ static int ensure_metric_storage(aleppo_ctx *c, int epochs, int M, long B) {
     c->advn_part = nullptr;
     c->advn_stats = c->h_advn_stats = nullptr;
     c->last_advn = false; // (its statistics went with the old buffer)
-    HIPCHK(c, dalloc(&c->metric_red, nm * 8 * 4, c->stream));
+    c->last_kl = false;   // (and so did the KL means)
+    HIPCHK(c, dalloc(&c->metric_red, nm * METRIC_REC * 4, c->stream));
     HIPCHK(c, dalloc(&c->grad_norms, nm * 4, c->stream));
     HIPCHK(c, dalloc(&c->adam_sched, nm * 2 * 4, c->stream));
     HIPCHK(c, dalloc(&c->advn_part, nm * 4 * 8, c->stream));  // ALEPPO_OPT_ADV_NORM_MINIBATCH (n, S, Q, 0) per minibatch
     HIPCHK(c, dalloc(&c->advn_stats, nm * 4 * 4, c->stream)); // ... and (mean_f, inv_f, std, 0)
-    HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_metric_red), nm * 9 * 4, hipHostMallocDefault));
+    HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_metric_red), nm * (METRIC_REC + 1) * 4,
+                            hipHostMallocDefault)); // records, then the grad norms
     HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_adam_sched), nm * 2 * 4, hipHostMallocDefault));
     HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_advn_stats), nm * 4 * 4, hipHostMallocDefault));
     c->metric_red_cap = nm;
@@ -1198,6 +1200,24 @@ static int ensure_shuffle_storage(aleppo_ctx *c, int epochs, long N) {
     HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_shuf_keys), (size_t)epochs * 16, hipHostMallocDefault));
     c->shuf_cap = ns;
     c->shuf_epochs_cap = epochs;
+  }
+  return ALEPPO_OK;
+}
+
+// ALEPPO_OPT_KL_PENALTY: beta's device word (allocated once, never moved: graphs bake it) and the per-sample exact-KL
+// plane, as large as one field of metric_ps (regrown with it; the graph key holds its address)
+static int ensure_kl_storage(aleppo_ctx *c) {
+  if (!c->kl_beta) {
+    HIPCHK(c, dalloc(&c->kl_beta, 16, c->stream));
+    HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_kl_beta), 16, hipHostMallocDefault));
+  }
+  if (c->kl_cap < c->metric_cap) {
+    retire(c, c->kl_ps);
+    c->kl_ps = nullptr;
+    c->kl_cap = 0;
+    c->last_kl = false;
+    HIPCHK(c, dalloc(&c->kl_ps, c->metric_cap * 4, c->stream));
+    c->kl_cap = c->metric_cap;
   }
   return ALEPPO_OK;
 }
@@ -1258,6 +1278,9 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
     return rc;
   const bool shuffle = c->shuffle;
   const bool advn = c->adv_norm_mb; // ALEPPO_OPT_ADV_NORM_MINIBATCH (statistics in advn_stats, grown with the metrics)
+  const bool klpen = c->kl_pen;     // ALEPPO_OPT_KL_PENALTY (the exact-KL plane kl_ps, beta in kl_beta)
+  if (klpen && (rc = ensure_kl_storage(c)))
+    return rc;
   if (shuffle && (rc = ensure_shuffle_storage(c, epochs, N)))
     return rc;
   if (vclip && (rc = ensure_val_storage(c)))
@@ -1286,6 +1309,11 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
     c->h_adam_sched[2 * i + 1] = (float)std::sqrt(1.0 - std::pow(b2, t));
   }
   HIPCHK(c, hipMemcpyAsync(c->adam_sched, c->h_adam_sched, (size_t)nm * 8, hipMemcpyHostToDevice, s));
+  // ... and, with ALEPPO_OPT_KL_PENALTY, beta: the head kernel reads it from device memory for the same reason
+  if (klpen) {
+    std::memcpy(c->h_kl_beta, &c->kl_coef_bits, 4);
+    HIPCHK(c, hipMemcpyAsync(c->kl_beta, c->h_kl_beta, 4, hipMemcpyHostToDevice, s));
+  }
   // ... and, with ALEPPO_OPT_MINIBATCH_SHUFFLE, the round keys of every epoch's permutation (aleppo.h): keyed by the Adam
   // step the epoch starts at, so a graph replay reads this call's keys and a resumed run replays the same orders
   const int shuf_h = feistel_half_width(N);
@@ -1383,7 +1411,8 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
                         c->metric_ps + 2 * fs + (size_t)mi * B, c->metric_ps + 3 * fs + (size_t)mi * B,
                         c->metric_ps + 4 * fs + (size_t)mi * B, c->metric_ps + 5 * fs + (size_t)mi * B,
                         c->metric_ps + 6 * fs + (size_t)mi * B, sWh, sBh, nblk_head, B, H, A, nullptr, nullptr, hparts,
-                        c->rt16, advn ? c->advn_stats + (size_t)(shuffle ? mi : mb) * 4 : nullptr);
+                        c->rt16, advn ? c->advn_stats + (size_t)(shuffle ? mi : mb) * 4 : nullptr,
+                        klpen ? c->kl_beta : nullptr, klpen ? c->kl_ps + (size_t)mi * B : nullptr);
       prof_end(c, ALEPPO_K_HEAD);
       HIPCHK(c, fork(c->ev_head)); // dh is ready
       prof_begin(c, ALEPPO_K_FC_DGRAD);
@@ -1512,11 +1541,11 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
       prof_end(c, ALEPPO_K_ADAM);
     }
   if (shuffle) // (epoch ep's masks in its order: minibatch mi's are the mi-th B of mask_p)
-    launch_metrics_reduce(s, c->metric_ps, fs, c->mask_p, B, nm, 1, c->metric_red);
+    launch_metrics_reduce(s, c->metric_ps, fs, c->mask_p, B, nm, 1, c->metric_red, klpen ? c->kl_ps : nullptr);
   else
-    launch_metrics_reduce(s, c->metric_ps, fs, c->mask_n, B, M, epochs, c->metric_red);
+    launch_metrics_reduce(s, c->metric_ps, fs, c->mask_n, B, M, epochs, c->metric_red, klpen ? c->kl_ps : nullptr);
   if (dp)
-    NCCLCHK(c, ncclAllReduce(c->metric_red, c->metric_red, (size_t)nm * 8, ncclFloat, ncclSum, comm, s));
+    NCCLCHK(c, ncclAllReduce(c->metric_red, c->metric_red, (size_t)nm * METRIC_REC, ncclFloat, ncclSum, comm, s));
   return ALEPPO_OK;
   }; // enqueue_update
 
@@ -1533,6 +1562,8 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
   key.order = shuffle ? c->order : nullptr;
   key.vclip = vclip ? 1 + c->val_src : 0;
   key.advn = advn ? c->advn_stats : nullptr;
+  key.klpen = klpen ? 1 : 0;
+  key.kl_ps = klpen ? c->kl_ps : nullptr;
   const bool want_graph = c->update_graph && !dp && !c->prof_on;
   if (want_graph && c->graph_exec && c->graph_key == key) {
     HIPCHK(c, hipGraphLaunch(c->graph_exec, s));
@@ -1575,8 +1606,9 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
   }
   c->adam_step += nm;
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(c->h_metric_red, c->metric_red, (size_t)nm * 8 * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(c->h_metric_red + (size_t)nm * 8, c->grad_norms, (size_t)nm * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(c->h_metric_red, c->metric_red, (size_t)nm * METRIC_REC * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(c->h_metric_red + (size_t)nm * METRIC_REC, c->grad_norms, (size_t)nm * 4,
+                           hipMemcpyDeviceToHost, s));
   if (advn) // (contiguous: M records, the same slices every epoch)
     HIPCHK(c, hipMemcpyAsync(c->h_advn_stats, c->advn_stats, (size_t)(shuffle ? nm : M) * 16, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
@@ -1586,9 +1618,10 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
   c->last_B = B;
   c->last_shuffled = shuffle;
   c->last_advn = advn;
+  c->last_kl = klpen;
   if (out)
     for (int i = 0; i < nm; ++i) {
-      const float *r = c->h_metric_red + (size_t)i * 8;
+      const float *r = c->h_metric_red + (size_t)i * METRIC_REC;
       const float cnt = r[5];
       out[i].loss = r[0] / cnt;
       out[i].clipped_loss = r[1] / cnt;
@@ -1596,7 +1629,7 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
       out[i].entropy = r[3] / cnt;
       out[i].ratio = r[4] / cnt;
       out[i].mask_count = cnt;
-      out[i].grad_norm = c->h_metric_red[(size_t)nm * 8 + i];
+      out[i].grad_norm = c->h_metric_red[(size_t)nm * METRIC_REC + i];
     }
   return ALEPPO_OK;
 }
@@ -1610,9 +1643,30 @@ extern "C" int aleppo_read_train_metric(aleppo_ctx *c, int field, float *dst, si
       return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "read_train_metric: count must be epochs * M of the last aleppo_train");
     const int slot = field == ALEPPO_M_MEAN_APPROX_KL ? 6 : 7;
     for (size_t i = 0; i < nm; ++i) {
-      const float *r = c->h_metric_red + i * 8;
+      const float *r = c->h_metric_red + i * METRIC_REC;
       dst[i] = r[slot] / r[5];
     }
+    return ALEPPO_OK;
+  }
+  if (field == ALEPPO_M_KL || field == ALEPPO_M_MEAN_KL) {
+    // ALEPPO_OPT_KL_PENALTY's exact KL: the per-sample plane, or the masked means (slot 8 over the count, slot 5)
+    const size_t nm = (size_t)c->last_epochs * c->last_M, n = nm * c->last_B;
+    if (!c->last_kl || nm == 0)
+      return set_err(c, ALEPPO_ERR_RUNTIME, "read_train_metric: the last aleppo_train ran without ALEPPO_OPT_KL_PENALTY");
+    if (field == ALEPPO_M_MEAN_KL) {
+      if (!dst || count != nm)
+        return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT,
+                       "read_train_metric: count must be epochs * M of the last aleppo_train");
+      for (size_t i = 0; i < nm; ++i) {
+        const float *r = c->h_metric_red + i * METRIC_REC;
+        dst[i] = r[8] / r[5];
+      }
+      return ALEPPO_OK;
+    }
+    if (!dst || count != n)
+      return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "read_train_metric: bad field or count");
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, copy_sync(c, dst, c->kl_ps, n * 4, hipMemcpyDeviceToHost));
     return ALEPPO_OK;
   }
   if (field == ALEPPO_M_ADV_MEAN || field == ALEPPO_M_ADV_STD) {
@@ -1905,9 +1959,12 @@ extern "C" int aleppo_comm_init(aleppo_ctx *c, const uint8_t id[ALEPPO_UNIQUE_ID
 extern "C" int aleppo_set_option(aleppo_ctx *c, int option, int value) {
   CHECK_CTX(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  // a captured update holds the kernels the switches selected when it was recorded: any change re-arms the capture
-  c->graph_key = Ctx::GraphKey();
-  c->warm_key = Ctx::GraphKey();
+  // a captured update holds the kernels the switches selected when it was recorded: any change re-arms the capture -
+  // except beta (ALEPPO_OPT_KL_COEF), a device value uploaded at each aleppo_train, which a replay reads as it is
+  if (option != ALEPPO_OPT_KL_COEF) {
+    c->graph_key = Ctx::GraphKey();
+    c->warm_key = Ctx::GraphKey();
+  }
   if (option == ALEPPO_OPT_GENERIC_CONV)
     c->tune.patch_conv = value == 0;
   else if (option == ALEPPO_OPT_FC_PIPE)
@@ -1935,6 +1992,18 @@ extern "C" int aleppo_set_option(aleppo_ctx *c, int option, int value) {
       return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT,
                      "ALEPPO_OPT_ADV_NORM_MINIBATCH: 0 (off) or 1 (normalise each minibatch's advantages)");
     c->adv_norm_mb = value != 0;
+  } else if (option == ALEPPO_OPT_KL_PENALTY) {
+    if (value != 0 && value != 1)
+      return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT,
+                     "ALEPPO_OPT_KL_PENALTY: 0 (off) or 1 (exact KL, beta KL added to the loss)");
+    c->kl_pen = value != 0;
+  } else if (option == ALEPPO_OPT_KL_COEF) {
+    // the bit pattern of a finite non-negative float: [0, 0x7F800000) (-0.0 and every negative float or NaN have the
+    // sign bit set and are negative as an int; +Inf is 0x7F800000 and the positive NaNs lie above it)
+    if (value < 0 || value >= 0x7F800000)
+      return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT,
+                     "ALEPPO_OPT_KL_COEF: the binary32 bits of a finite non-negative float (not -0.0, Inf or NaN)");
+    c->kl_coef_bits = (uint32_t)value;
   } else if (option == ALEPPO_OPT_UPDATE_GRAPH)
     c->update_graph = value != 0;
   else if (option == ALEPPO_OPT_GATE_TIMEOUT_MS)
@@ -1960,6 +2029,8 @@ extern "C" int aleppo_get_option(aleppo_ctx *c, int option, int64_t *value) {
   case ALEPPO_OPT_MINIBATCH_SHUFFLE: *value = c->shuffle; break;
   case ALEPPO_OPT_VALUE_CLIP: *value = c->value_clip; break;
   case ALEPPO_OPT_ADV_NORM_MINIBATCH: *value = c->adv_norm_mb; break;
+  case ALEPPO_OPT_KL_PENALTY: *value = c->kl_pen; break;
+  case ALEPPO_OPT_KL_COEF: *value = (int64_t)c->kl_coef_bits; break;
   case ALEPPO_OPT_GATE_TIMEOUT_MS: *value = (int64_t)(c->gate_timeout_ticks / 100000ull); break;
   default: return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "unknown option");
   }

@@ -19,6 +19,9 @@ constexpr int MAX_ACTIONS = 18;
 constexpr int FC_SPLITS = 7; // split-K slices of the acting-size fc forward (3136 = 7 * 448)
 // split-K slice caps of the wgrad slabs (gemm_launch.hip) and of the head kernel's partial slabs
 constexpr int MAXS_C1 = 256, MAXS_C2 = 256, MAXS_C3 = 256, MAXS_FC = 8, MAXS_HEAD = 256;
+// floats per reduced per-minibatch metric record (metrics_reduce_kernel): the sums of fields 0-4, the unmasked count,
+// the sums of approx-KL and clip fraction, and the sum of the exact KL of ALEPPO_OPT_KL_PENALTY (0 with the option off)
+constexpr int METRIC_REC = 9;
 
 // ---- internal flat parameter layout (fp32 master, Adam moments, gradient share it) ----
 // order chosen so that what backward finishes FIRST is at the FRONT: bucket 0 = heads + fc can be
@@ -160,7 +163,7 @@ struct Ctx {
   size_t slab_off[11] = {0}; // W1 b1 W2 b2 W3 b3 Wfc bfc Wh bh
   float *adv_stats = nullptr;
   float *sumsq_part = nullptr; // [1024]
-  // ---- per-sample train metrics [mi][B] x 7 (aleppo_metric_field 0-6), and reduced [mi][8] (metrics_reduce_kernel) ----
+  // ---- per-sample train metrics [mi][B] x 7 (aleppo_metric_field 0-6), and reduced [mi][METRIC_REC] (metrics_reduce_kernel)
   float *metric_ps = nullptr;
   size_t metric_cap = 0; // floats per field
   size_t metric_red_cap = 0;
@@ -190,6 +193,13 @@ struct Ctx {
   double *advn_part = nullptr;                    // [mi][4] (n, S, Q, 0) partial sums (data parallel: all-reduced)
   float *advn_stats = nullptr, *h_advn_stats = nullptr; // [mi][4] (mean_f, inv_f, std, 0) (device / pinned)
   bool last_advn = false;                         // the last aleppo_train ran with the option (h_advn_stats holds it)
+  // ---- ALEPPO_OPT_KL_PENALTY / ALEPPO_OPT_KL_COEF: the exact-KL plane and beta (allocated on first use)
+  bool kl_pen = false;
+  uint32_t kl_coef_bits = 0;                     // beta as an IEEE-754 binary32 bit pattern (finite, non-negative)
+  float *kl_ps = nullptr;                        // [mi][B] per-sample exact KL, kl_cap floats (grown with metric_ps)
+  size_t kl_cap = 0;
+  float *kl_beta = nullptr, *h_kl_beta = nullptr; // [1] beta, uploaded at each aleppo_train (device / pinned)
+  bool last_kl = false;                          // the last aleppo_train ran with the option (kl_ps / slot 8 hold it)
   // ---- captured update (ALEPPO_OPT_UPDATE_GRAPH): the epochs x minibatches loop as one hipGraph, re-captured when
   // the shape (or a baked pointer) changes; the first call of a shape runs eagerly (one-time kernel attribute set-up)
   bool update_graph = false;
@@ -202,9 +212,12 @@ struct Ctx {
     const void *order = nullptr; // shuffled updates: the order / gathered-plane storage (nullptr: contiguous)
     int vclip = 0;               // ALEPPO_OPT_VALUE_CLIP: 0 off, else 1 + the ValSrc the old values come from
     const void *advn = nullptr;  // ALEPPO_OPT_ADV_NORM_MINIBATCH: the statistics storage (nullptr: off)
+    int klpen = 0;               // ALEPPO_OPT_KL_PENALTY (beta is a device value and not part of the key)
+    const void *kl_ps = nullptr; // ... its per-sample plane (nullptr: off)
     bool operator==(const GraphKey &o) const {
       return epochs == o.epochs && M == o.M && two == o.two && N == o.N && metric_ps == o.metric_ps &&
-             metric_red == o.metric_red && order == o.order && vclip == o.vclip && advn == o.advn;
+             metric_red == o.metric_red && order == o.order && vclip == o.vclip && advn == o.advn &&
+             klpen == o.klpen && kl_ps == o.kl_ps;
     }
   } graph_key, warm_key;
   long graph_replays = 0;
@@ -273,14 +286,15 @@ void launch_shuffle_gather(hipStream_t s, const uint32_t *rk, int h, long N, int
                            void *ret_p, void *val_p, uint8_t *mask_p, bool rt16);
 // vold: the values the samples were collected with (ALEPPO_OPT_VALUE_CLIP), or nullptr for the reference's value loss;
 // ps_kl / ps_cf: the per-sample approx-KL and clip-fraction planes (always written);
-// advs: this minibatch's (mean_f, inv_f) of ALEPPO_OPT_ADV_NORM_MINIBATCH, or nullptr for the advantages as stored
+// advs: this minibatch's (mean_f, inv_f) of ALEPPO_OPT_ADV_NORM_MINIBATCH, or nullptr for the advantages as stored;
+// klb: ALEPPO_OPT_KL_PENALTY's beta (device float [1]) and ps_kle its per-sample exact-KL plane, or nullptr (off)
 void launch_head_train(hipStream_t s, const float *h, const float *Wh, const float *bh, const int *act,
                        const void *oldlp, const void *adv, const void *ret, const void *vold, const uint8_t *mask,
                        const float *mask_count, Hyper hp, void *dh, int prec, float *ps_total, float *ps_clipped,
                        float *ps_value, float *ps_entropy, float *ps_ratio, float *ps_kl, float *ps_cf, float *slab_w,
                        float *slab_b, int nblk, long B, int H, int A, float *logits_out, float *values_out,
                        int hparts = 1, bool rt16 = false, // oldlp / adv / ret / vold are f16 planes
-                       const float *advs = nullptr);
+                       const float *advs = nullptr, const float *klb = nullptr, float *ps_kle = nullptr);
 struct ReduceSeg {
   const float *slab;
   int S;
@@ -302,8 +316,9 @@ void launch_adam(hipStream_t s, float *P, const float *G_in, float *G_out_scaled
 void launch_pack_dgrad(hipStream_t s, const float *P, const ParamLayout &L, void *W2d, void *W3d, void *WfcT,
                        int prec);
 void launch_cast_params(hipStream_t s, const float *P, void *Pc, long n);
+// out: [epochs * M][METRIC_REC] records; kle: the exact-KL plane of ALEPPO_OPT_KL_PENALTY (slot 8), or nullptr
 void launch_metrics_reduce(hipStream_t s, const float *ps, size_t field_stride, const uint8_t *mask_n, long B, int M,
-                           int epochs, float *out);
+                           int epochs, float *out, const float *kle = nullptr);
 void launch_obs_unpack(hipStream_t s, const uint32_t *obs, uint8_t *out, long nsamp, SampleMap map);
 void launch_obs_pack(hipStream_t s, const uint8_t *in, uint32_t *obs, long nsamp, SampleMap map);
 void launch_transpose_tm_pitched(hipStream_t s, const void *src_tm, size_t pitch, void *dst_em, int E, int T, int inner,

@@ -718,8 +718,14 @@ void launch_shuffle_gather(hipStream_t s, const uint32_t *rk, int h, long N, int
 // VCLIP (ALEPPO_OPT_VALUE_CLIP): the value term is the clipped one of aleppo.h against vold, the values the samples were
 // collected with; without it vold is never read.  ps_kl / ps_cf (approx-KL and clip fraction) are written either way.
 // ADVN (ALEPPO_OPT_ADV_NORM_MINIBATCH): every row's advantage a becomes (a - advs[0]) * advs[1] in fp32, this minibatch's
-// (mean_f, inv_f) from advn_stats_kernel; without it advs is never read.  The body is shared by two entry points:
-// head_train_kernel (ADVN off, the default path's instantiations) and head_train_advn_kernel (ADVN on).
+// (mean_f, inv_f) from advn_stats_kernel; without it advs is never read.
+// KLPEN (ALEPPO_OPT_KL_PENALTY): the exact KL(pi_old || pi) of every row goes to ps_kle, and with beta = klb[0] != 0 the
+// loss gains beta KL and its gradient beta (p S - q) (include/aleppo.h).  The body is shared by three entry points:
+// head_train_kernel (ADVN and KLPEN off, the default path's instantiations), head_train_advn_kernel (ADVN on) and
+// head_train_kl_kernel (KLPEN on, with advantage normalisation a run-time switch: advs may be null).
+// Waves per workgroup: 8, or 4 where one wave per SIMD needs more than 256 registers - the wide action sets, and with
+// the KL penalty (its S / KL pass and the q_a of the gradient) from AMAX = 10 on (8 waves spilled ~40 registers there).
+constexpr int head_waves(int amax, bool klpen) { return amax > 10 || (klpen && amax > 6) ? 4 : 8; }
 #define HEAD_PARAMS                                                                                                    \
   const float *__restrict__ h, const float *__restrict__ Wh, const float *__restrict__ bh, const int *__restrict__ act, \
       const RT *__restrict__ oldlp, const RT *__restrict__ adv, const RT *__restrict__ ret,                            \
@@ -728,16 +734,30 @@ void launch_shuffle_gather(hipStream_t s, const uint32_t *rk, int h, long N, int
       float *ps_cf, float *slab_w, float *slab_b, long B, int H, int A, float *logits_out, float *values_out, int hparts
 template <class T, int AMAX, class RT, bool VCLIP>
 __global__ __launch_bounds__(AMAX > 10 ? 256 : 512) void head_train_kernel(HEAD_PARAMS) {
-  constexpr bool ADVN = false;
-  const float *advs = nullptr;
+  constexpr bool ADVN = false, KLPEN = false;
+  const float *advs = nullptr, *klb = nullptr;
+  float *ps_kle = nullptr;
 #include "head_train_body.inc"
 }
 // advs: float [4] of this minibatch (mean_f, inv_f, std, 0)
 template <class T, int AMAX, class RT, bool VCLIP>
 __global__ __launch_bounds__(AMAX > 10 ? 256 : 512) void head_train_advn_kernel(HEAD_PARAMS,
                                                                                  const float *__restrict__ advs) {
-  constexpr bool ADVN = true;
+  constexpr bool ADVN = true, KLPEN = false;
+  const float *klb = nullptr;
+  float *ps_kle = nullptr;
 #include "head_train_body.inc"
+}
+// advs: as above, or nullptr (no minibatch normalisation); klb: float [1], beta; ps_kle: float [B], the exact KL per row
+template <class T, int AMAX, class RT, bool VCLIP>
+__global__ __launch_bounds__(64 * head_waves(AMAX, true)) void head_train_kl_kernel(HEAD_PARAMS,
+                                                                               const float *__restrict__ advs,
+                                                                               const float *__restrict__ klb,
+                                                                               float *ps_kle) {
+  constexpr bool ADVN = true, KLPEN = true;
+#define HEAD_TRAIN_PASSES
+#include "head_train_body.inc"
+#undef HEAD_TRAIN_PASSES
 }
 #undef HEAD_PARAMS
 
@@ -747,18 +767,22 @@ static void head_train_t(hipStream_t s, const float *h, const float *Wh, const f
                          const float *mask_count, Hyper hp, void *dh, float *ps_total, float *ps_clipped,
                          float *ps_value, float *ps_entropy, float *ps_ratio, float *ps_kl, float *ps_cf, float *slab_w,
                          float *slab_b, int nblk, long B, int H, int A, float *lo, float *vo, int hparts,
-                         const float *advs) {
+                         const float *advs, const float *klb, float *ps_kle) {
 #define HEAD_LAUNCH_ARGS                                                                                               \
   h, Wh, bh, act, oldlp, adv, ret, vold, mask, mask_count, hp, static_cast<T *>(dh), ps_total, ps_clipped, ps_value,    \
       ps_entropy, ps_ratio, ps_kl, ps_cf, slab_w, slab_b, B, H, A, lo, vo, hparts
 #define LAUNCH_HEAD(AM)                                                                                                \
   do {                                                                                                                 \
     const size_t sm = ((size_t)((AM + 1) + ((AM + 1) > 8 ? (AM + 1) : 8)) * H + 8 * (AM + 1)) * sizeof(float);        \
-    const void *fn = advs ? reinterpret_cast<const void *>(&head_train_advn_kernel<T, AM, RT, VCLIP>)                  \
-                          : reinterpret_cast<const void *>(&head_train_kernel<T, AM, RT, VCLIP>);                      \
+    const void *fn = klb    ? reinterpret_cast<const void *>(&head_train_kl_kernel<T, AM, RT, VCLIP>)                  \
+                     : advs ? reinterpret_cast<const void *>(&head_train_advn_kernel<T, AM, RT, VCLIP>)                \
+                            : reinterpret_cast<const void *>(&head_train_kernel<T, AM, RT, VCLIP>);                    \
     if (sm > 48 * 1024)                                                                                                \
       (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);                              \
-    if (advs)                                                                                                          \
+    if (klb)                                                                                                           \
+      hipLaunchKernelGGL((head_train_kl_kernel<T, AM, RT, VCLIP>), dim3(nblk), dim3(64 * head_waves(AM, true)), sm, s, \
+                         HEAD_LAUNCH_ARGS, advs, klb, ps_kle);                                                         \
+    else if (advs)                                                                                                     \
       hipLaunchKernelGGL((head_train_advn_kernel<T, AM, RT, VCLIP>), dim3(nblk), dim3(AM > 10 ? 256 : 512), sm, s,     \
                          HEAD_LAUNCH_ARGS, advs);                                                                      \
     else                                                                                                               \
@@ -781,11 +805,11 @@ void launch_head_train(hipStream_t s, const float *h, const float *Wh, const flo
                        const float *mask_count, Hyper hp, void *dh, int prec, float *ps_total, float *ps_clipped,
                        float *ps_value, float *ps_entropy, float *ps_ratio, float *ps_kl, float *ps_cf, float *slab_w,
                        float *slab_b, int nblk, long B, int H, int A, float *logits_out, float *values_out, int hparts,
-                       bool rt16, const float *advs) {
+                       bool rt16, const float *advs, const float *klb, float *ps_kle) {
 #define HEAD_ARGS(RT)                                                                                                  \
   s, h, Wh, bh, act, static_cast<const RT *>(oldlp), static_cast<const RT *>(adv), static_cast<const RT *>(ret),       \
       static_cast<const RT *>(vold), mask, mask_count, hp, dh, ps_total, ps_clipped, ps_value, ps_entropy, ps_ratio,   \
-      ps_kl, ps_cf, slab_w, slab_b, nblk, B, H, A, logits_out, values_out, hparts, advs
+      ps_kl, ps_cf, slab_w, slab_b, nblk, B, H, A, logits_out, values_out, hparts, advs, klb, ps_kle
 #define HEAD_T(T, RT)                                                                                                  \
   do {                                                                                                                 \
     if (vold)                                                                                                          \
@@ -1210,38 +1234,46 @@ void launch_pack_dgrad(hipStream_t s, const float *P, const ParamLayout &L, void
 // masked sums of the per-sample metric arrays (log_data's masked means, train.cc:163-210): block per (epoch, mb).
 // Record [mi][8]: the sums of fields 0-4 (total, clipped, value, entropy, ratio), the count, then the sums of fields 5-6
 // (approx-KL, clip fraction)
+// kle: the exact-KL plane of ALEPPO_OPT_KL_PENALTY ([mi][B], like one field of ps), summed into slot 8; nullptr: 0 there
 __global__ __launch_bounds__(256) void metrics_reduce_kernel(const float *ps, size_t field_stride, const uint8_t *mask_n,
-                                                              long B, int M, float *out) {
+                                                              long B, int M, const float *kle, float *out) {
   __shared__ float s4[4];
   const int mi = blockIdx.x, mb = mi % M;
   const uint8_t *m = mask_n + (size_t)mb * B;
-  float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, cnt = 0.f;
+  float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, cnt = 0.f, kacc = 0.f;
   for (long i = threadIdx.x; i < B; i += 256)
     if (m[i]) {
       cnt += 1.f;
 #pragma unroll
       for (int f = 0; f < 7; ++f)
         acc[f] += ps[f * field_stride + (size_t)mi * B + i];
+      if (kle)
+        kacc += kle[(size_t)mi * B + i];
     }
 #pragma unroll
   for (int f = 0; f < 5; ++f) {
     const float v = block_sum_256(acc[f], s4);
     if (threadIdx.x == 0)
-      out[mi * 8 + f] = v;
+      out[mi * METRIC_REC + f] = v;
   }
   cnt = block_sum_256(cnt, s4);
   if (threadIdx.x == 0)
-    out[mi * 8 + 5] = cnt;
+    out[mi * METRIC_REC + 5] = cnt;
 #pragma unroll
   for (int f = 5; f < 7; ++f) {
     const float v = block_sum_256(acc[f], s4);
     if (threadIdx.x == 0)
-      out[mi * 8 + 1 + f] = v;
+      out[mi * METRIC_REC + 1 + f] = v;
   }
+  if (kle) // (uniform: the whole workgroup takes the branch)
+    kacc = block_sum_256(kacc, s4);
+  if (threadIdx.x == 0)
+    out[mi * METRIC_REC + 8] = kacc;
 }
 void launch_metrics_reduce(hipStream_t s, const float *ps, size_t field_stride, const uint8_t *mask_n, long B, int M,
-                           int epochs, float *out) {
-  hipLaunchKernelGGL(metrics_reduce_kernel, dim3(epochs * M), dim3(256), 0, s, ps, field_stride, mask_n, B, M, out);
+                           int epochs, float *out, const float *kle) {
+  hipLaunchKernelGGL(metrics_reduce_kernel, dim3(epochs * M), dim3(256), 0, s, ps, field_stride, mask_n, B, M, kle,
+                     out);
 }
 
 // ================================================================================================

@@ -115,7 +115,7 @@ typedef enum {
 } aleppo_field;
 
 /* Per-sample training metrics (ai::ppo::train::Metrics, src/ai/ppo/train.h:64-109), [epochs,M,B], read with
- * aleppo_read_train_metric; fields 5-10 are extensions (the reference has none).  With logr = logp(a) - old_logp(a) and
+ * aleppo_read_train_metric; fields 5-12 are extensions (the reference has none).  With logr = logp(a) - old_logp(a) and
  * rho = exp(logr) per sample, computed on every update whatever ALEPPO_OPT_VALUE_CLIP is:
  *   approx_kl     = (rho - 1) - logr                  (the "k3" estimator CleanRL logs as approx_kl)
  *   clip_fraction = |rho - 1| > clip_param ? 1 : 0     (strict)
@@ -123,7 +123,10 @@ typedef enum {
  * denominator of aleppo_minibatch_metrics: the global unmasked count (under data parallelism they are global means).
  * Fields 9-10 are the statistics ALEPPO_OPT_ADV_NORM_MINIBATCH normalised each minibatch's advantages with in the last
  * aleppo_train, float [epochs,M] (count = epochs * M; with contiguous minibatches every epoch's row is the same): mean_f
- * and (float)std as defined there.  Reading them after an update that ran with the option off is ALEPPO_ERR_RUNTIME. */
+ * and (float)std as defined there.  Reading them after an update that ran with the option off is ALEPPO_ERR_RUNTIME.
+ * Fields 11-12 are the exact KL(pi_old || pi) of ALEPPO_OPT_KL_PENALTY: per sample [epochs,M,B] (unmasked, like field 5)
+ * and its masked means [epochs,M] (like field 7: global means under data parallelism).  Reading them after an update
+ * that ran with the option off is ALEPPO_ERR_RUNTIME, as for fields 9-10. */
 typedef enum {
   ALEPPO_M_TOTAL_LOSSES = 0,
   ALEPPO_M_CLIPPED_LOSSES = 1,
@@ -135,7 +138,9 @@ typedef enum {
   ALEPPO_M_MEAN_APPROX_KL = 7,     /* [epochs,M] masked means */
   ALEPPO_M_MEAN_CLIP_FRACTION = 8, /* [epochs,M] masked means */
   ALEPPO_M_ADV_MEAN = 9,           /* [epochs,M] mean_f of ALEPPO_OPT_ADV_NORM_MINIBATCH */
-  ALEPPO_M_ADV_STD = 10            /* [epochs,M] (float)std of ALEPPO_OPT_ADV_NORM_MINIBATCH */
+  ALEPPO_M_ADV_STD = 10,           /* [epochs,M] (float)std of ALEPPO_OPT_ADV_NORM_MINIBATCH */
+  ALEPPO_M_KL = 11,                /* [epochs,M,B] per-sample exact KL of ALEPPO_OPT_KL_PENALTY, unmasked */
+  ALEPPO_M_MEAN_KL = 12            /* [epochs,M] masked means of ALEPPO_M_KL */
 } aleppo_metric_field;
 
 /* ------------------------------------------------------------------ lifetime */
@@ -247,7 +252,7 @@ int aleppo_finish_rollout(aleppo_ctx *ctx, const float *noise);
 int aleppo_train(aleppo_ctx *ctx, double lr, int epochs, int num_mini_batches,
                  aleppo_minibatch_metrics *out_metrics);
 /* Per-sample metric tensors of the last aleppo_train, float [epochs,M,B], in the order of aleppo_read_sample_order:
- * element [e][m][b] belongs to logical sample order[e][m*B + b].  Fields 7-10: float [epochs,M], count =
+ * element [e][m][b] belongs to logical sample order[e][m*B + b].  Fields 7-10 and 12: float [epochs,M], count =
  * epochs * M. */
 int aleppo_read_train_metric(aleppo_ctx *ctx, int metric_field, float *dst, size_t count);
 /* Sample order of the last aleppo_train, int32 [epochs][N] (count = epochs * N, N = the batch's sample count): row e,
@@ -396,7 +401,7 @@ typedef enum {
                                       (ALEPPO_F_VALUES) returns; of a caller batch, what aleppo_set_batch_values stored:
                                       aleppo_train on a caller batch without them is ALEPPO_ERR_RUNTIME.  The same on every
                                       schedule, like ALEPPO_OPT_MINIBATCH_SHUFFLE */
-  ALEPPO_OPT_ADV_NORM_MINIBATCH = 14 /* per-minibatch advantage normalisation (CleanRL norm_adv, SB3 normalize_advantage).
+  ALEPPO_OPT_ADV_NORM_MINIBATCH = 14, /* per-minibatch advantage normalisation (CleanRL norm_adv, SB3 normalize_advantage).
                                       0 (default): the advantages as stored.  1: normalised per minibatch; any other value
                                       is ALEPPO_ERR_INVALID_ARGUMENT.  Read at each aleppo_train.  For every (epoch e,
                                       minibatch m) of the call:
@@ -420,6 +425,35 @@ typedef enum {
                                       bf16, rollout and aleppo_set_batch batches, one GPU or data parallel.  The statistics
                                       depend only on a minibatch's sample set, so one call of E epochs equals E one-epoch
                                       calls bit for bit.  Read back: ALEPPO_M_ADV_MEAN / ALEPPO_M_ADV_STD */
+  ALEPPO_OPT_KL_PENALTY = 15,      /* the adaptive-KL-penalty objective of the PPO paper (section 4; RLlib's kl_coeff), on
+                                      top of the clipped one.  0 (default): nothing changes.  1: the exact KL is computed
+                                      for every sample and beta KL is added to the loss, beta = ALEPPO_OPT_KL_COEF; any
+                                      other value is ALEPPO_ERR_INVALID_ARGUMENT.  Read at each aleppo_train.  Per sample,
+                                      masked or not, with olp = the stored old log-probs widened to fp32 (with
+                                      ALEPPO_ROLLOUT_FP16 planes: the fp16 values as stored) and lp = the log-softmax of
+                                      the logits the loss computes, p = exp(lp):
+                                        q_a = exp(olp_a),  S = sum_a q_a,  KL = sum_a q_a (olp_a - lp_a)
+                                        total loss += beta KL   (ALEPPO_M_TOTAL_LOSSES, aleppo_minibatch_metrics.loss)
+                                        dL/dz_j += (mask / mask_count) beta (p_j S - q_j)   (z: the logits; the value
+                                          output's gradient is untouched)
+                                      S stands where 1 would with exact old probabilities: with fp16 planes sum q is not
+                                      exactly 1, and the gradient is the exact derivative of the loss reported.  With
+                                      beta = 0 the per-sample KL is still computed and read back, and every other number
+                                      (parameters, Adam state, every other plane and metric) is bit-identical to option 0.
+                                      A very large config.clip_param makes the clipped surrogate the plain ratio times the
+                                      advantage, which turns the update into pure PPO-penalty.  Works with
+                                      ALEPPO_OPT_MINIBATCH_SHUFFLE, ALEPPO_OPT_VALUE_CLIP, ALEPPO_OPT_ADV_NORM_MINIBATCH,
+                                      config.advantage_norm, ALEPPO_OPT_UPDATE_GRAPH, fp32 and bf16, fp32 and fp16 rollout
+                                      planes, rollout and aleppo_set_batch batches, one GPU or data parallel; one call of
+                                      E epochs equals E one-epoch calls bit for bit.  Read back: ALEPPO_M_KL /
+                                      ALEPPO_M_MEAN_KL.  Adapting beta between updates (the paper's rule) is the caller's
+                                      part: the trainer's kl_target does it */
+  ALEPPO_OPT_KL_COEF = 16          /* beta of ALEPPO_OPT_KL_PENALTY as the IEEE-754 binary32 BIT PATTERN in `value`
+                                      (default 0 = +0.0f).  Valid: exactly the finite non-negative floats, value in
+                                      [0, 0x7F800000); -0.0, negative values, Inf and NaN are ALEPPO_ERR_INVALID_ARGUMENT.
+                                      aleppo_get_option returns the bits.  A device value, uploaded at each aleppo_train:
+                                      a captured update (ALEPPO_OPT_UPDATE_GRAPH) follows a beta changed between calls,
+                                      and unlike the other options setting it does not re-arm the capture */
 } aleppo_option;
 int aleppo_set_option(aleppo_ctx *ctx, int option, int value);
 /* Current value of an option; for ALEPPO_OPT_UPDATE_GRAPH the number of graph launches so far (0 = every update ran

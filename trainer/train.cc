@@ -32,7 +32,13 @@
 // shuffle_minibatches: false, clip_value_loss: false (ALEPPO_OPT_VALUE_CLIP: CleanRL's clip_vloss), target_kl (absent or
 // <= 0: off; else the update runs one epoch per aleppo_train call and stops after the epoch whose LAST minibatch's
 // approx-KL exceeds it, CleanRL's rule; exact, because E one-epoch calls equal one call of E epochs),
-// minibatch_advantage_norm: false (ALEPPO_OPT_ADV_NORM_MINIBATCH: CleanRL's norm_adv; logs mean_advantage_std).
+// minibatch_advantage_norm: false (ALEPPO_OPT_ADV_NORM_MINIBATCH: CleanRL's norm_adv; logs mean_advantage_std),
+// kl_coef (absent or 0: off; > 0: ALEPPO_OPT_KL_PENALTY with this initial beta, the PPO paper's KL penalty on top of
+// clipping) and kl_target (absent or 0: beta stays put; > 0, which needs kl_coef > 0: after each rollout's update, with
+// d = the mean exact KL over the minibatches of the last epoch that ran, beta /= 2 if d < kl_target / 1.5 and beta *= 2
+// if d > 1.5 kl_target, the paper's section 4 rule; halving stops at KL_BETA_MIN, so that beta can always grow again;
+// every rank computes the same beta, since the means are global).  Negative values are refused.  With kl_coef > 0 the
+// trainer logs kl_coef (the beta of the rollout's update) and mean_kl (d).
 // Data parallelism (no reference counterpart): start one process per GPU with RANK / WORLD_SIZE / LOCAL_RANK
 // in the environment (torchrun / mpirun style).  Rank r owns the contiguous environment block
 // [r * E / W, (r + 1) * E / W) and GPU LOCAL_RANK; rank 0 creates the RCCL id, hands it to the others through the file
@@ -77,6 +83,8 @@ struct Config {
   bool clip_value_loss = false;     // extension: value-function clipping (ALEPPO_OPT_VALUE_CLIP)
   bool minibatch_advantage_norm = false; // extension: per-minibatch advantage normalisation (ALEPPO_OPT_ADV_NORM_MINIBATCH)
   double target_kl = 0.0;           // extension: early stop of the update's epochs on approx-KL (<= 0: off)
+  double kl_coef = 0.0, kl_target = 0.0; // extension: adaptive KL penalty (ALEPPO_OPT_KL_PENALTY; <= 0: off / fixed beta)
+  bool kl_coef_set = false, kl_target_set = false; // (the keys were given: hparams entries)
   // extensions
   std::string precision = "fp32", rollout_precision = "fp32";
   bool device_preprocess = false; // emulators hand over raw frame pairs; gray LUT + resize + max run on the device (N2)
@@ -126,6 +134,9 @@ static bool as_bool(const std::map<std::string, std::string> &kv, const char *k,
     return dflt;
   return it->second == "true" || it->second == "True" || it->second == "1" || it->second == "yes";
 }
+// kl_target's rule never halves beta below this (nor raises a smaller initial kl_coef to it): repeated halving would
+// otherwise reach 0 through the subnormals, and 0 doubled stays 0
+constexpr float KL_BETA_MIN = 1e-6f;
 static Config load_config(const std::string &path) { // keys / defaults of src/bin/train.cc:108-136
   const auto kv = parse_yaml(path);
   Config c;
@@ -157,6 +168,14 @@ static Config load_config(const std::string &path) { // keys / defaults of src/b
   c.clip_value_loss = as_bool(kv, "clip_value_loss", false);
   c.minibatch_advantage_norm = as_bool(kv, "minibatch_advantage_norm", false);
   c.target_kl = as<double>(kv, "target_kl", 0.0);
+  c.kl_coef = as<double>(kv, "kl_coef", 0.0);
+  c.kl_target = as<double>(kv, "kl_target", 0.0);
+  c.kl_coef_set = kv.count("kl_coef") != 0;
+  c.kl_target_set = kv.count("kl_target") != 0;
+  if (!(c.kl_coef >= 0 && c.kl_coef < 3.0e38) || !(c.kl_target >= 0 && c.kl_target < 3.0e38)) // (beta is a float)
+    throw std::runtime_error("kl_coef / kl_target must be finite and non-negative");
+  if (c.kl_target > 0 && !(c.kl_coef > 0)) // (it would adapt a penalty that is off)
+    throw std::runtime_error("kl_target needs kl_coef > 0");
   c.deterministic = as_bool(kv, "deterministic", false);
   c.precision = as<std::string>(kv, "precision", "fp32");
   c.rollout_precision = as<std::string>(kv, "rollout_precision", "fp32");
@@ -804,6 +823,10 @@ int main(int argc, char **argv) {
       check(ctx, aleppo_set_option(ctx, ALEPPO_OPT_VALUE_CLIP, 1));
     if (cfg.minibatch_advantage_norm) // extension: each minibatch's advantages normalised before the loss (norm_adv)
       check(ctx, aleppo_set_option(ctx, ALEPPO_OPT_ADV_NORM_MINIBATCH, 1));
+    const bool kl_pen = cfg.kl_coef > 0; // extension: the KL penalty; beta is set before every update (adapted below)
+    float kl_beta = kl_pen ? (float)cfg.kl_coef : 0.0f;
+    if (kl_pen)
+      check(ctx, aleppo_set_option(ctx, ALEPPO_OPT_KL_PENALTY, 1));
     if (prof.on())
       check(ctx, aleppo_profile_enable(ctx, 1));
     std::vector<std::pair<std::string, bool>> hparam_flags{{"record_observation", cfg.record_observation},
@@ -816,18 +839,22 @@ int main(int argc, char **argv) {
       hparam_flags.emplace_back("clip_value_loss", true);
     if (cfg.minibatch_advantage_norm)
       hparam_flags.emplace_back("minibatch_advantage_norm", true);
-    logger.add_hparams( // get_parameters (train.cc:76-105), same keys
-        {{"total_environments", (double)cfg.total_environments}, {"hidden_size", (double)cfg.hidden_size},
-         {"action_size", (double)cfg.action_size}, {"horizon", (double)cfg.horizon}, {"max_steps", (double)cfg.max_steps},
-         {"frame_stack", (double)cfg.frame_stack}, {"learning_rate", cfg.learning_rate}, {"clip_param", cfg.clip_param},
-         {"value_loss_coef", cfg.value_loss_coef}, {"entropy_coef", cfg.entropy_coef},
-         {"num_epochs", (double)cfg.num_epochs}, {"mini_batch_size", (double)cfg.mini_batch_size},
-         {"num_mini_batches", (double)cfg.num_mini_batches}, {"gae_discount", cfg.gae_discount},
-         {"gae_lambda", cfg.gae_lambda}, {"max_gradient_norm", cfg.max_gradient_norm},
-         {"num_rollouts", (double)cfg.num_rollouts}, {"num_workers", (double)cfg.num_workers},
-         {"worker_batch_size", (double)cfg.worker_batch_size}, {"frame_skip", (double)cfg.frame_skip},
-         {"max_return", cfg.max_return}},
-        hparam_flags, group, (double)start_time * 1e-9);
+    std::vector<std::pair<std::string, double>> hparam_numbers{ // get_parameters (train.cc:76-105), same keys
+        {"total_environments", (double)cfg.total_environments}, {"hidden_size", (double)cfg.hidden_size},
+        {"action_size", (double)cfg.action_size}, {"horizon", (double)cfg.horizon}, {"max_steps", (double)cfg.max_steps},
+        {"frame_stack", (double)cfg.frame_stack}, {"learning_rate", cfg.learning_rate}, {"clip_param", cfg.clip_param},
+        {"value_loss_coef", cfg.value_loss_coef}, {"entropy_coef", cfg.entropy_coef},
+        {"num_epochs", (double)cfg.num_epochs}, {"mini_batch_size", (double)cfg.mini_batch_size},
+        {"num_mini_batches", (double)cfg.num_mini_batches}, {"gae_discount", cfg.gae_discount},
+        {"gae_lambda", cfg.gae_lambda}, {"max_gradient_norm", cfg.max_gradient_norm},
+        {"num_rollouts", (double)cfg.num_rollouts}, {"num_workers", (double)cfg.num_workers},
+        {"worker_batch_size", (double)cfg.worker_batch_size}, {"frame_skip", (double)cfg.frame_skip},
+        {"max_return", cfg.max_return}};
+    if (cfg.kl_coef_set) // (only when set, like the flags above)
+      hparam_numbers.emplace_back("kl_coef", cfg.kl_coef);
+    if (cfg.kl_target_set)
+      hparam_numbers.emplace_back("kl_target", cfg.kl_target);
+    logger.add_hparams(hparam_numbers, hparam_flags, group, (double)start_time * 1e-9);
 
     // ---- Rollout host half (src/ai/rollout.cc)
     std::vector<SyntheticAtari> envs;
@@ -940,6 +967,7 @@ int main(int argc, char **argv) {
     std::vector<aleppo_minibatch_metrics> m((size_t)cfg.num_epochs * nmb);
     std::vector<float> kl((size_t)cfg.num_epochs * nmb), cf((size_t)cfg.num_epochs * nmb);
     std::vector<float> adv_std(cfg.minibatch_advantage_norm ? (size_t)cfg.num_epochs * nmb : 0);
+    std::vector<float> mean_kl(kl_pen ? (size_t)cfg.num_epochs * nmb : 0);
     const std::pair<int, const char *> sample_fields[5] = {{ALEPPO_M_TOTAL_LOSSES, "losses"},
                                                            {ALEPPO_M_CLIPPED_LOSSES, "clipped_losses"},
                                                            {ALEPPO_M_VALUE_LOSSES, "value_losses"},
@@ -954,6 +982,11 @@ int main(int argc, char **argv) {
       // the target (the Adam schedule and the shuffle keys follow the Adam step, so the calls add up to the same update)
       size_t epochs_run = 0;
       const size_t per_call = cfg.target_kl > 0 ? 1 : (size_t)cfg.num_epochs;
+      if (kl_pen) { // beta of this rollout's update, as its binary32 bit pattern
+        int32_t bits;
+        std::memcpy(&bits, &kl_beta, 4);
+        check(ctx, aleppo_set_option(ctx, ALEPPO_OPT_KL_COEF, bits));
+      }
       while (epochs_run < (size_t)cfg.num_epochs) {
         const size_t e0 = epochs_run;
         {
@@ -965,6 +998,8 @@ int main(int argc, char **argv) {
         check(ctx, aleppo_read_train_metric(ctx, ALEPPO_M_MEAN_CLIP_FRACTION, cf.data() + e0 * nmb, per_call * nmb));
         if (cfg.minibatch_advantage_norm)
           check(ctx, aleppo_read_train_metric(ctx, ALEPPO_M_ADV_STD, adv_std.data() + e0 * nmb, per_call * nmb));
+        if (kl_pen)
+          check(ctx, aleppo_read_train_metric(ctx, ALEPPO_M_MEAN_KL, mean_kl.data() + e0 * nmb, per_call * nmb));
         for (size_t k = 0; k < 5; ++k)
           check(ctx, aleppo_read_train_metric(ctx, sample_fields[k].first, planes[k].data() + e0 * N, per_call * N));
         epochs_run += per_call;
@@ -1012,6 +1047,20 @@ int main(int argc, char **argv) {
         logger.add_scalar("mean_advantage_std", step, avgv(adv_std));
       if (cfg.target_kl > 0)
         logger.add_scalar("update_epochs", step, (float)epochs_run);
+      if (kl_pen) { // the adaptive KL coefficient (PPO paper section 4) from the last epoch's mean exact KL
+        double d = 0;
+        for (size_t i = nrun - nmb; i < nrun; ++i)
+          d += mean_kl[i];
+        d /= (double)nmb;
+        logger.add_scalar("kl_coef", step, kl_beta);
+        logger.add_scalar("mean_kl", step, (float)d);
+        if (cfg.kl_target > 0) {
+          if (d < cfg.kl_target / 1.5)
+            kl_beta = std::max(0.5f * kl_beta, std::min(kl_beta, KL_BETA_MIN));
+          else if (d > 1.5 * cfg.kl_target && std::isfinite(2.0f * kl_beta))
+            kl_beta *= 2.0f;
+        }
+      }
       logger.add_scalar("learning_rate", step, (float)lr);
       {
         std::vector<float> gn;
