@@ -69,11 +69,13 @@ def _flags(seed, T, E, p_term=0.08, p_trunc=0.04):
     return te, tr, st
 
 
-def _rollout_vs_oracle(b, frames84, st, rew, te, tr, obs0, params, H, A, tol, noise=None):
+def _rollout_vs_oracle(b, frames84, st, rew, te, tr, obs0, params, H, A, tol, noise=None, checker=None):
     """One rollout's read-back planes `b` (read_batch dict) against the ORACLE on the same trace (rollout.cc:198-278 +
     buffer.cc:58-77): observation stacks byte-exact (update_observations), logits / values within `tol` of the oracle's
     fp32 forward, sampled actions bit-exact on ITS logits (when the noise is known), flag / reward planes exact, GAE planes
-    bit-exact from ITS values.  Returns the stack after the last slot (= the next rollout's first observation)."""
+    bit-exact from ITS values.  checker (a bf16_check.Checker, bf16 acting): logits, values and next_values against the
+    bf16-emulating forward under the checker's bounds instead of `tol` (its failures are left to the caller).
+    Returns the stack after the last slot (= the next rollout's first observation)."""
     T, E = st.shape
     obs, stacks = obs0.copy(), []
     for t in range(T):
@@ -82,12 +84,18 @@ def _rollout_vs_oracle(b, frames84, st, rew, te, tr, obs0, params, H, A, tol, no
     obs_em = np.stack(stacks, 1)
     np.testing.assert_array_equal(b["observations"], obs_em)
     np.testing.assert_array_equal(b["masks"], 1 - st.T)
-    wl, wv = orc.net_forward(params, H, A, obs_em.reshape(E * T, 4, 84, 84))
-    rtol = 1e-2 if tol > 1e-3 else 0  # bf16 operands: the documented bound is 1 % relative + 3e-2 absolute
-    np.testing.assert_allclose(b["logits"].reshape(E * T, A), wl, atol=tol, rtol=rtol)
-    np.testing.assert_allclose(b["values"].ravel(), wv, atol=tol, rtol=rtol)
-    _, nv = orc.net_forward(params, H, A, obs)
-    np.testing.assert_allclose(b["next_values"], nv, atol=tol, rtol=rtol)
+    if checker is not None:  # every slot's stack and the stack after the last slot in ONE emulated forward
+        n = E * T
+        wl, wv, (fl, fv) = bc.emulated_forward(params, H, A, np.concatenate([obs_em.reshape(n, 4, 84, 84), obs]))
+        checker.forward(b["logits"].reshape(n, A), np.concatenate([b["values"].ravel(), b["next_values"]]),
+                        (wl[:n], wv, (fl[:n], fv)), "rollout_")
+    else:
+        wl, wv = orc.net_forward(params, H, A, obs_em.reshape(E * T, 4, 84, 84))
+        rtol = 1e-2 if tol > 1e-3 else 0  # bf16 operands: the documented bound is 1 % relative + 3e-2 absolute
+        np.testing.assert_allclose(b["logits"].reshape(E * T, A), wl, atol=tol, rtol=rtol)
+        np.testing.assert_allclose(b["values"].ravel(), wv, atol=tol, rtol=rtol)
+        _, nv = orc.net_forward(params, H, A, obs)
+        np.testing.assert_allclose(b["next_values"], nv, atol=tol, rtol=rtol)
     if noise is not None:
         want = orc.sample(orc.softmax(b["logits"].reshape(E * T, A)), noise.transpose(1, 0, 2).reshape(E * T, A))
         np.testing.assert_array_equal(b["actions"].ravel(), want)
