@@ -36,7 +36,11 @@ ABI_VERSION = 2
 UNIQUE_ID_BYTES = 128
 
 FIELDS = dict(observations=0, actions=1, rewards=2, masks=3, logits=4, values=5, advantages=6, returns=7,
-              log_probs=8, terminals=9, truncations=10, current_obs=11, next_values=12)
+              log_probs=8, terminals=9, truncations=10, current_obs=11, next_values=12, batch_stats=13)
+# ALEPPO_F_BATCH_STATS: the indices of its ALEPPO_BATCH_STATS_COUNT doubles (aleppo_batch_stat; Engine.batch_stats)
+BATCH_STATS_COUNT = 10
+BATCH_STATS = dict(count=0, explained_variance=1, value_mean=2, value_std=3, return_mean=4, return_std=5,
+                   advantage_mean=6, advantage_std=7, residual_mean=8, residual_std=9)
 METRIC_FIELDS = dict(total_losses=0, clipped_losses=1, value_losses=2, entropies=3, ratio=4, approx_kl=5,
                      clip_fraction=6, kl=11)  # (kl: OPT_KL_PENALTY's exact KL per sample)
 # the [epochs, M] masked means of approx_kl / clip_fraction (aleppo_read_train_metric; Engine.train_diagnostics) and of
@@ -487,11 +491,18 @@ class Engine:
                       values=((E, T), np.float32), advantages=((E, T), np.float32), returns=((E, T), np.float32),
                       log_probs=((E, T, A), np.float32), terminals=((E, T), np.uint8),
                       truncations=((E, T), np.uint8), current_obs=((E, 4, 84, 84), np.uint8),
-                      next_values=((E,), np.float32))
+                      next_values=((E,), np.float32), batch_stats=((BATCH_STATS_COUNT,), np.float64))
         shp, dt = shapes[name]
         out = np.zeros(shp, dt)
         self._c(lib().aleppo_read_batch(self._ctx, FIELDS[name], _ptr(out), C.c_size_t(out.nbytes)))
         return out
+
+    def batch_stats(self):
+        """ALEPPO_F_BATCH_STATS: dict of ten floats (count, explained_variance, value / return / advantage / residual mean
+        and std) over the unmasked samples of the batch the context holds, reduced on the device when called; a
+        collective with a communicator (aleppo.h)"""
+        a = self.read_batch("batch_stats")
+        return {name: float(a[i]) for name, i in BATCH_STATS.items()}
 
     # -- multi GPU --
     @staticmethod

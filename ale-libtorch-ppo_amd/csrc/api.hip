@@ -1927,6 +1927,36 @@ extern "C" int aleppo_read_batch(aleppo_ctx *c, int field, void *dst, size_t byt
     return plane(c->oldlp_n, N * A, false, A);
   case ALEPPO_F_NEXT_VALUES:
     return plane(rp(c, c->values_tm, (size_t)T * E), (size_t)E, false, 1);
+  case ALEPPO_F_BATCH_STATS: { // computed here, when it is read (aleppo.h): nothing is enqueued anywhere else for it
+    need = ALEPPO_BATCH_STATS_COUNT * sizeof(double);
+    if (bytes != need)
+      return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "read_batch: wrong byte count");
+    const long n = c->batch_n;
+    if (n <= 0)
+      return set_err(c, ALEPPO_ERR_RUNTIME, "no batch: call aleppo_finish_rollout or aleppo_set_batch first");
+    if (c->val_src == Ctx::VAL_NONE)
+      return set_err(c, ALEPPO_ERR_RUNTIME,
+                     "ALEPPO_F_BATCH_STATS needs the batch's values: call aleppo_set_batch_values after aleppo_set_batch");
+    if (c->world > 1 && !c->nccl_comm)
+      return set_err(c, ALEPPO_ERR_RUNTIME, "world_size > 1 but aleppo_comm_init was not called");
+    const bool dp = c->world > 1 || (c->nccl_comm && c->force_comm);
+    // scratch: [0, 16) the results, [16, 32) the sums (all-reduced in place), then the partials of stage 1
+    const int nblk = bstat_blocks(n);
+    if (int rc = scratch(1, (32 + (size_t)nblk * BSTAT_SUMS) * sizeof(double), &tmp))
+      return rc;
+    double *result = static_cast<double *>(tmp), *sums = result + 16, *part = result + 32;
+    // a rollout batch's values are slots 0..T-1 of values_tm ([T+1][E], time-major), indexed in place: val_n stays what
+    // the last update or aleppo_set_batch_values made it
+    const bool tm = c->val_src == Ctx::VAL_ROLLOUT;
+    launch_bstat_partial(s, tm ? c->values_tm : c->val_n, c->ret_n, c->adv_n, c->mask_n, n, tm ? E : 0, tm ? T : 0, part,
+                         c->rt16);
+    launch_bstat_reduce(s, part, nblk, dp ? sums : nullptr, dp ? nullptr : result);
+    if (dp) {
+      NCCLCHK(c, ncclAllReduce(sums, sums, BSTAT_SUMS, ncclDouble, ncclSum, static_cast<ncclComm_t>(c->nccl_comm), s));
+      launch_bstat_finalise(s, sums, result);
+    }
+    return fin(result);
+  }
   default:
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "read_batch: unknown field");
   }

@@ -277,6 +277,16 @@ void launch_mask_count(hipStream_t s, const uint8_t *mask_n, float *counts, long
 void launch_advn_stats(hipStream_t s, const void *adv, const uint8_t *mask, long B, int nmb, double *part, float *stats,
                        bool rt16);
 void launch_advn_finalise(hipStream_t s, const double *part, float *stats, int nmb);
+// ALEPPO_F_BATCH_STATS: stage 1, block b < bstat_blocks(n) over samples [b * BSTAT_CHUNK, ...) writes part[b][BSTAT_SUMS] =
+// (n, S_v, Q_v, S_R, Q_R, S_a, Q_a, S_d, Q_d) in double; val is time-major [T+1][E] when E > 0, sample-major when E == 0.
+// Stage 2 adds the partials in index order into sums[BSTAT_SUMS] (when not null) and / or finalises them into
+// result[ALEPPO_BATCH_STATS_COUNT]; launch_bstat_finalise does the latter from all-reduced sums.
+constexpr int BSTAT_CHUNK = 4096, BSTAT_SUMS = 9;
+int bstat_blocks(long n);
+void launch_bstat_partial(hipStream_t s, const void *val, const void *ret, const void *adv, const uint8_t *mask, long n,
+                          int E, int T, double *part, bool rt16);
+void launch_bstat_reduce(hipStream_t s, const double *part, int nblk, double *sums, double *result);
+void launch_bstat_finalise(hipStream_t s, const double *sums, double *result);
 // ALEPPO_OPT_MINIBATCH_SHUFFLE: order[e][i] = the keyed bijection of aleppo.h (round keys rk[e][4], domain 2^(2h)) and the
 // per-sample planes gathered into that order: act / oldlp / adv / ret / mask_p[e][i] = plane[order[e][i]]
 // (val_n != nullptr, ALEPPO_OPT_VALUE_CLIP: also val_p[e][i] = val_n[order[e][i]])

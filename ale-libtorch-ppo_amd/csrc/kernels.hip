@@ -628,6 +628,105 @@ void launch_advn_finalise(hipStream_t s, const double *part, float *stats, int n
 }
 
 // ================================================================================================
+// ALEPPO_F_BATCH_STATS (aleppo.h): count, sum and sum of squares of the stored values v, returns R, advantages a and of
+// d = R - v over the unmasked samples of the batch, in double, in two stages whose order depends on the sample count only.
+// Stage 1: workgroup b sums the samples [b * BSTAT_CHUNK, (b + 1) * BSTAT_CHUNK): thread t takes t, t + 256, ... in turn,
+// then the block folds with the shuffle tree of block_sum_256d.  x * x of a widened float is exact in double (a
+// contracted fma is too); d is one rounded double subtraction of two widened floats.  The values of a rollout batch are
+// time-major ([T+1][E], sample n = e*T + t sits at t*E + e: E > 0); those of a caller batch are sample-major (E == 0).
+template <class RT>
+__global__ __launch_bounds__(256) void bstat_partial_kernel(const RT *__restrict__ val, const RT *__restrict__ ret,
+                                                            const RT *__restrict__ adv, const uint8_t *__restrict__ mask,
+                                                            long n, int E, int T, double *__restrict__ part) {
+  __shared__ double s4[4];
+  const long i0 = (long)blockIdx.x * BSTAT_CHUNK;
+  const long i1 = i0 + BSTAT_CHUNK < n ? i0 + BSTAT_CHUNK : n;
+  double acc[BSTAT_SUMS];
+#pragma unroll
+  for (int k = 0; k < BSTAT_SUMS; ++k)
+    acc[k] = 0.0;
+  for (long i = i0 + threadIdx.x; i < i1; i += 256)
+    if (mask[i]) {
+      const unsigned u = (unsigned)i; // (n <= E*T fits 32 bits: 32-bit division)
+      const long iv = E > 0 ? (long)(u % (unsigned)T) * E + u / (unsigned)T : i;
+      const double v = (double)(float)val[iv], r = (double)(float)ret[i], a = (double)(float)adv[i];
+      const double d = r - v;
+      acc[0] += 1.0;
+      acc[1] += v;
+      acc[2] += v * v;
+      acc[3] += r;
+      acc[4] += r * r;
+      acc[5] += a;
+      acc[6] += a * a;
+      acc[7] += d;
+      acc[8] += d * d;
+    }
+#pragma unroll
+  for (int k = 0; k < BSTAT_SUMS; ++k)
+    acc[k] = block_sum_256d(acc[k], s4);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < BSTAT_SUMS; ++k)
+      part[(size_t)blockIdx.x * BSTAT_SUMS + k] = acc[k];
+  }
+}
+// The ten results of aleppo.h from the nine (all-reduced) sums: population variance max(0, Q / n - mean^2), without
+// contraction so that every instance of this function rounds alike; n == 0: zeros and a NaN explained variance.
+__device__ __forceinline__ void bstat_finalise(const double *sums, double *out) {
+#pragma clang fp contract(off)
+  const double n = sums[0];
+  double var[4];
+  out[ALEPPO_BS_COUNT] = n;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const double S = sums[1 + 2 * k], Q = sums[2 + 2 * k];
+    const double mean = n > 0.0 ? S / n : 0.0;
+    var[k] = n > 0.0 ? fmax(0.0, Q / n - mean * mean) : 0.0;
+    out[2 + 2 * k] = mean;
+    out[3 + 2 * k] = sqrt(var[k]);
+  }
+  out[ALEPPO_BS_EXPLAINED_VARIANCE] = (n > 0.0 && var[1] > 0.0) ? 1.0 - var[3] / var[1] : __builtin_nan("");
+}
+// Stage 2, one workgroup: thread k < 9 adds sum k of the nblk partials in index order; then either the sums (for the
+// all-reduce, finalised by bstat_finalise_kernel) or the results.
+__global__ __launch_bounds__(64) void bstat_reduce_kernel(const double *__restrict__ part, int nblk, double *sums_out,
+                                                          double *result) {
+  __shared__ double sums[BSTAT_SUMS];
+  if (threadIdx.x < BSTAT_SUMS) {
+    double acc = 0.0;
+    for (int b = 0; b < nblk; ++b)
+      acc += part[(size_t)b * BSTAT_SUMS + threadIdx.x];
+    sums[threadIdx.x] = acc;
+    if (sums_out)
+      sums_out[threadIdx.x] = acc;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && result)
+    bstat_finalise(sums, result);
+}
+__global__ __launch_bounds__(64) void bstat_finalise_kernel(const double *sums, double *result) {
+  if (threadIdx.x == 0 && blockIdx.x == 0)
+    bstat_finalise(sums, result);
+}
+int bstat_blocks(long n) { return (int)((n + BSTAT_CHUNK - 1) / BSTAT_CHUNK); }
+void launch_bstat_partial(hipStream_t s, const void *val, const void *ret, const void *adv, const uint8_t *mask, long n,
+                          int E, int T, double *part, bool rt16) {
+  const dim3 grid((unsigned)bstat_blocks(n));
+  if (rt16)
+    hipLaunchKernelGGL(bstat_partial_kernel<f16>, grid, dim3(256), 0, s, static_cast<const f16 *>(val),
+                       static_cast<const f16 *>(ret), static_cast<const f16 *>(adv), mask, n, E, T, part);
+  else
+    hipLaunchKernelGGL(bstat_partial_kernel<float>, grid, dim3(256), 0, s, static_cast<const float *>(val),
+                       static_cast<const float *>(ret), static_cast<const float *>(adv), mask, n, E, T, part);
+}
+void launch_bstat_reduce(hipStream_t s, const double *part, int nblk, double *sums, double *result) {
+  hipLaunchKernelGGL(bstat_reduce_kernel, dim3(1), dim3(64), 0, s, part, nblk, sums, result);
+}
+void launch_bstat_finalise(hipStream_t s, const double *sums, double *result) {
+  hipLaunchKernelGGL(bstat_finalise_kernel, dim3(1), dim3(64), 0, s, sums, result);
+}
+
+// ================================================================================================
 // Per-epoch minibatch shuffling (ALEPPO_OPT_MINIBATCH_SHUFFLE; the permutation is specified in aleppo.h).  One thread per
 // position i of epoch e = blockIdx.y: a four-round Feistel network on [0, 2^(2h)) walked until it lands in [0, N).  The
 // small per-sample planes are gathered into the new order (coalesced writes; oldlp's A elements per sample go through

@@ -111,8 +111,53 @@ typedef enum {
   ALEPPO_F_TERMINALS = 9,    /* uint8  [E,T] */
   ALEPPO_F_TRUNCATIONS = 10, /* uint8  [E,T] */
   ALEPPO_F_CURRENT_OBS = 11, /* uint8  [E,4,84,84]: Rollout::observations_ right now */
-  ALEPPO_F_NEXT_VALUES = 12  /* float  [E]: bootstrap values of the last finish_rollout */
+  ALEPPO_F_NEXT_VALUES = 12, /* float  [E]: bootstrap values of the last finish_rollout */
+  ALEPPO_F_BATCH_STATS = 13  /* double [ALEPPO_BATCH_STATS_COUNT]: explained variance and batch statistics, see below */
 } aleppo_field;
+
+/* ALEPPO_F_BATCH_STATS: the critic diagnostics CleanRL / Stable-Baselines3 log on every update (the reference has none),
+ * reduced on the device where the planes are.  aleppo_read_batch(ctx, ALEPPO_F_BATCH_STATS, dst, ALEPPO_BATCH_STATS_COUNT
+ * * sizeof(double)) writes the ten doubles indexed by aleppo_batch_stat.
+ * Sample set: the unmasked samples (mask = !episode_start, the loss's mask) of the batch the context holds: the rollout
+ *   batch after aleppo_finish_rollout (E*T samples), or the caller batch of aleppo_set_batch (its n samples: this field
+ *   uses the batch's own sample count, what aleppo_train uses, while the other fields read E*T elements whatever the
+ *   batch).  With a communicator (world_size > 1, or ALEPPO_OPT_FORCE_COMM) it is the union over the ranks, and the call
+ *   is then a COLLECTIVE like aleppo_train: every rank makes it at the same point.
+ * Planes: v, R, a are the values, returns and advantages AS STORED, widened to float and then to double: with
+ *   ALEPPO_ROLLOUT_FP16 the rounded values aleppo_read_batch returns.  v is what ALEPPO_OPT_VALUE_CLIP calls v_old: the
+ *   values plane of a rollout batch, or what aleppo_set_batch_values stored for a caller batch (a caller batch without
+ *   them: ALEPPO_ERR_RUNTIME, as for value clipping).  a is the advantage plane as it stands: with config.advantage_norm
+ *   = 1 the normalised one.  d = (double)R - (double)v.
+ * Arithmetic: n and the sum S and sum of squares Q of v, R, a and d, in double (nine numbers per rank; under data
+ *   parallelism all-reduced as ncclDouble / ncclSum).  Then on the device, in double: mean = S / n, var = max(0, Q / n -
+ *   mean^2), std = sqrt(var), explained_variance = 1 - var(d) / var(R).  This is the POPULATION variance (numpy.var's
+ *   default, what CleanRL's and SB3's explained_variance use), not the unbiased one of ALEPPO_OPT_ADV_NORM_MINIBATCH.
+ *   explained_variance is NaN when n == 0 or var(R) == 0 (as CleanRL / SB3 return NaN); with n == 0 every mean and std
+ *   is 0.  var(R) == 0 is decided on the variance as computed above: exact for R == 0 everywhere, or whenever the sums are
+ *   exact; a constant R whose sum of squares rounds can leave a variance of a few ulp of mean^2 instead.
+ * Deterministic: each rank sums in a fixed order that depends on the batch's sample count only (chunks of 4096 samples,
+ *   256 strided accumulators per chunk folded by a fixed tree, chunks added in index order), not on the device or on
+ *   timing: two reads of one batch are bit-identical.  The read refers to the batch in logical order, so it is
+ *   bit-identical before and after aleppo_train whatever options that update ran with.
+ * It is computed WHEN IT IS READ, on the context's stream, followed by that stream's synchronise like the other fields:
+ *   aleppo_finish_rollout, aleppo_set_batch and aleppo_train enqueue nothing for it, and a context that never reads the
+ *   field runs exactly the commands it ran before the field existed.
+ * Errors: a wrong byte count is ALEPPO_ERR_INVALID_ARGUMENT like the other fields; ALEPPO_ERR_RUNTIME while a step is
+ *   armed (every field), when the context holds no batch yet (neither aleppo_finish_rollout nor aleppo_set_batch has
+ *   succeeded), when a caller batch has no values, and when world_size > 1 but aleppo_comm_init was not called. */
+#define ALEPPO_BATCH_STATS_COUNT 10
+typedef enum {
+  ALEPPO_BS_COUNT = 0,              /* n: the number of unmasked samples */
+  ALEPPO_BS_EXPLAINED_VARIANCE = 1, /* 1 - var(d) / var(R) */
+  ALEPPO_BS_VALUE_MEAN = 2,
+  ALEPPO_BS_VALUE_STD = 3,
+  ALEPPO_BS_RETURN_MEAN = 4,
+  ALEPPO_BS_RETURN_STD = 5,
+  ALEPPO_BS_ADVANTAGE_MEAN = 6,
+  ALEPPO_BS_ADVANTAGE_STD = 7,
+  ALEPPO_BS_RESIDUAL_MEAN = 8,      /* of d = R - v */
+  ALEPPO_BS_RESIDUAL_STD = 9
+} aleppo_batch_stat;
 
 /* Per-sample training metrics (ai::ppo::train::Metrics, src/ai/ppo/train.h:64-109), [epochs,M,B], read with
  * aleppo_read_train_metric; fields 5-12 are extensions (the reference has none).  With logr = logp(a) - old_logp(a) and

@@ -38,7 +38,10 @@
 // d = the mean exact KL over the minibatches of the last epoch that ran, beta /= 2 if d < kl_target / 1.5 and beta *= 2
 // if d > 1.5 kl_target, the paper's section 4 rule; halving stops at KL_BETA_MIN, so that beta can always grow again;
 // every rank computes the same beta, since the means are global).  Negative values are refused.  With kl_coef > 0 the
-// trainer logs kl_coef (the beta of the rollout's update) and mean_kl (d).
+// trainer logs kl_coef (the beta of the rollout's update) and mean_kl (d).  log_batch_stats: false (true: after every
+// rollout that is trained on, ALEPPO_F_BATCH_STATS is read - a collective under data parallelism, so every rank reads -
+// and explained_variance, mean_value / std_value, mean_return / std_return, mean_advantage / std_advantage are logged;
+// a NaN explained variance is logged as NaN).
 // Data parallelism (no reference counterpart): start one process per GPU with RANK / WORLD_SIZE / LOCAL_RANK
 // in the environment (torchrun / mpirun style).  Rank r owns the contiguous environment block
 // [r * E / W, (r + 1) * E / W) and GPU LOCAL_RANK; rank 0 creates the RCCL id, hands it to the others through the file
@@ -85,6 +88,7 @@ struct Config {
   double target_kl = 0.0;           // extension: early stop of the update's epochs on approx-KL (<= 0: off)
   double kl_coef = 0.0, kl_target = 0.0; // extension: adaptive KL penalty (ALEPPO_OPT_KL_PENALTY; <= 0: off / fixed beta)
   bool kl_coef_set = false, kl_target_set = false; // (the keys were given: hparams entries)
+  bool log_batch_stats = false; // extension: explained variance and value / return / advantage statistics (ALEPPO_F_BATCH_STATS)
   // extensions
   std::string precision = "fp32", rollout_precision = "fp32";
   bool device_preprocess = false; // emulators hand over raw frame pairs; gray LUT + resize + max run on the device (N2)
@@ -170,6 +174,7 @@ static Config load_config(const std::string &path) { // keys / defaults of src/b
   c.target_kl = as<double>(kv, "target_kl", 0.0);
   c.kl_coef = as<double>(kv, "kl_coef", 0.0);
   c.kl_target = as<double>(kv, "kl_target", 0.0);
+  c.log_batch_stats = as_bool(kv, "log_batch_stats", false);
   c.kl_coef_set = kv.count("kl_coef") != 0;
   c.kl_target_set = kv.count("kl_target") != 0;
   if (!(c.kl_coef >= 0 && c.kl_coef < 3.0e38) || !(c.kl_target >= 0 && c.kl_target < 3.0e38)) // (beta is a float)
@@ -839,6 +844,8 @@ int main(int argc, char **argv) {
       hparam_flags.emplace_back("clip_value_loss", true);
     if (cfg.minibatch_advantage_norm)
       hparam_flags.emplace_back("minibatch_advantage_norm", true);
+    if (cfg.log_batch_stats)
+      hparam_flags.emplace_back("log_batch_stats", true);
     std::vector<std::pair<std::string, double>> hparam_numbers{ // get_parameters (train.cc:76-105), same keys
         {"total_environments", (double)cfg.total_environments}, {"hidden_size", (double)cfg.hidden_size},
         {"action_size", (double)cfg.action_size}, {"horizon", (double)cfg.horizon}, {"max_steps", (double)cfg.max_steps},
@@ -978,6 +985,11 @@ int main(int argc, char **argv) {
       std::cout << "Rollout " << r + 1 << " of " << cfg.num_rollouts << std::endl;
       const double lr = cfg.learning_rate * (1.0 - r / static_cast<double>(cfg.num_rollouts)); // train.cc:424-428
       const Log log = rollout();
+      double bstats[ALEPPO_BATCH_STATS_COUNT] = {};
+      if (cfg.log_batch_stats) { // of the rollout batch as the update below will see it; every rank calls (collective)
+        Profile::Span sp(&prof, "read_batch_stats");
+        check(ctx, aleppo_read_batch(ctx, ALEPPO_F_BATCH_STATS, bstats, sizeof(bstats)));
+      }
       // one call of num_epochs epochs, or - with target_kl - one call per epoch until an epoch's last minibatch is over
       // the target (the Adam schedule and the shuffle keys follow the Adam step, so the calls add up to the same update)
       size_t epochs_run = 0;
@@ -1060,6 +1072,15 @@ int main(int argc, char **argv) {
           else if (d > 1.5 * cfg.kl_target && std::isfinite(2.0f * kl_beta))
             kl_beta *= 2.0f;
         }
+      }
+      if (cfg.log_batch_stats) { // (global statistics under data parallelism; a NaN explained variance is logged as NaN)
+        logger.add_scalar("explained_variance", step, (float)bstats[ALEPPO_BS_EXPLAINED_VARIANCE]);
+        logger.add_scalar("mean_value", step, (float)bstats[ALEPPO_BS_VALUE_MEAN]);
+        logger.add_scalar("std_value", step, (float)bstats[ALEPPO_BS_VALUE_STD]);
+        logger.add_scalar("mean_return", step, (float)bstats[ALEPPO_BS_RETURN_MEAN]);
+        logger.add_scalar("std_return", step, (float)bstats[ALEPPO_BS_RETURN_STD]);
+        logger.add_scalar("mean_advantage", step, (float)bstats[ALEPPO_BS_ADVANTAGE_MEAN]);
+        logger.add_scalar("std_advantage", step, (float)bstats[ALEPPO_BS_ADVANTAGE_STD]);
       }
       logger.add_scalar("learning_rate", step, (float)lr);
       {
