@@ -64,6 +64,21 @@ OPT_VALUE_CLIP = 13
 OPT_ADV_NORM_MINIBATCH = 14
 OPT_KL_PENALTY = 15
 OPT_KL_COEF = 16  # (the value is beta's binary32 bit pattern: Engine.set_kl_coef / Engine.kl_coef)
+# the per-update hyper-parameters, each as its binary32 bit pattern (Engine.set_hyper / Engine.hyper)
+OPT_CLIP_PARAM, OPT_VALUE_CLIP_RANGE, OPT_VALUE_LOSS_COEF, OPT_ENTROPY_COEF, OPT_MAX_GRAD_NORM = 17, 18, 19, 20, 21
+HYPER_OPTIONS = dict(clip_param=OPT_CLIP_PARAM, value_clip_range=OPT_VALUE_CLIP_RANGE,
+                     value_loss_coef=OPT_VALUE_LOSS_COEF, entropy_coef=OPT_ENTROPY_COEF,
+                     max_grad_norm=OPT_MAX_GRAD_NORM)
+
+
+def float_bits(x):
+    """the IEEE-754 binary32 bit pattern of x (rounded to float32) as the signed int aleppo_set_option takes"""
+    return struct.unpack("<i", struct.pack("<f", x))[0]
+
+
+def bits_float(v):
+    """the float32 whose binary32 bit pattern is the low 32 bits of v (what aleppo_get_option returned)"""
+    return struct.unpack("<f", struct.pack("<I", v & 0xFFFFFFFF))[0]
 
 EXPORTS = [
     "aleppo_abi_version", "aleppo_create", "aleppo_destroy", "aleppo_last_error", "aleppo_param_count",
@@ -453,6 +468,23 @@ class Engine:
     def kl_coef(self):
         """the float32 beta of OPT_KL_COEF"""
         return struct.unpack("<f", struct.pack("<I", self.get_option(OPT_KL_COEF) & 0xFFFFFFFF))[0]
+
+    def set_hyper(self, clip_param=None, value_clip_range=None, value_loss_coef=None, entropy_coef=None,
+                  max_grad_norm=None):
+        """OPT_CLIP_PARAM / OPT_VALUE_CLIP_RANGE / OPT_VALUE_LOSS_COEF / OPT_ENTROPY_COEF / OPT_MAX_GRAD_NORM: the
+        hyper-parameters of the next train() calls (None: leave as it is).  Each is rounded to float32 and passed as its
+        bits; clip_param, value_clip_range and max_grad_norm must be finite and > 0, the coefficients finite and >= 0.
+        Under data parallelism every rank sets the same values."""
+        given = dict(clip_param=clip_param, value_clip_range=value_clip_range, value_loss_coef=value_loss_coef,
+                     entropy_coef=entropy_coef, max_grad_norm=max_grad_norm)
+        for name, x in given.items():
+            if x is not None:
+                self.set_option(HYPER_OPTIONS[name], float_bits(x))
+
+    def hyper(self):
+        """the five current float32 values: {clip_param, value_clip_range, value_loss_coef, entropy_coef,
+        max_grad_norm} (the config's until set; value_clip_range follows clip_param until set itself)"""
+        return {name: bits_float(self.get_option(opt)) for name, opt in HYPER_OPTIONS.items()}
 
     def sample_order(self, epochs):
         """aleppo_read_sample_order: int32 [epochs, N], row e = the logical samples of epoch e in minibatch order

@@ -356,6 +356,8 @@ extern "C" int aleppo_create(const aleppo_config *cfg, aleppo_ctx **out) {
 
   aleppo_ctx *c = new aleppo_ctx();
   c->cfg = *cfg;
+  c->hyper = Hyper{cfg->clip_param, cfg->value_loss_coef, cfg->entropy_coef, cfg->max_gradient_norm};
+  c->value_clip_range = cfg->clip_param;
   c->tune = tuning_from_env();
   set_tuning(&c->tune);
   if (c->cfg.adam_beta1 == 0.f)
@@ -508,7 +510,7 @@ extern "C" void aleppo_destroy(aleppo_ctx *c) {
                  c->sumsq_part, c->metric_ps, c->metric_red, c->grad_norms, c->adv_stats, c->stage_u8, c->stage_obs,
                  c->adam_sched, c->rb_tmp[0], c->rb_tmp[1], c->order, c->act_p, c->oldlp_p, c->adv_p,
                  c->ret_p,  c->mask_p,   c->mask_counts_ep, c->shuf_keys, c->val_n, c->val_p, c->advn_part,
-                 c->advn_stats, c->kl_ps, c->kl_beta};
+                 c->advn_stats, c->kl_ps, c->kl_beta, c->hyper_blk};
   for (void *p : dev)
     if (p)
       hipFree(p);
@@ -517,7 +519,7 @@ extern "C" void aleppo_destroy(aleppo_ctx *c) {
   if (c->Pc && c->Pc != c->P)
     hipFree(c->Pc);
   void *host[] = {c->h_go, c->h_actions, c->h_step, c->h_rec, c->h_frames, c->h_noise, c->h_err, c->h_metric_red,
-                  c->h_adam_sched, c->h_shuf_keys, c->h_advn_stats, c->h_kl_beta};
+                  c->h_adam_sched, c->h_shuf_keys, c->h_advn_stats, c->h_kl_beta, c->h_hyper_blk};
   for (void *p : host)
     if (p)
       hipHostFree(p);
@@ -597,7 +599,7 @@ extern "C" int aleppo_export_grads(aleppo_ctx *c, float *flat, size_t count) {
     return rc;
   const size_t nm = (size_t)c->last_epochs * c->last_M;
   const float norm = c->h_metric_red[nm * METRIC_REC + nm - 1];
-  float coef = c->cfg.max_gradient_norm / (norm + 1e-6f);
+  float coef = c->last_max_norm / (norm + 1e-6f); // (the limit that update ran with)
   coef = std::fmin(coef, 1.0f);
   for (size_t i = 0; i < count; ++i)
     flat[i] *= coef;
@@ -1222,6 +1224,15 @@ static int ensure_kl_storage(aleppo_ctx *c) {
   return ALEPPO_OK;
 }
 
+// ALEPPO_OPT_CLIP_PARAM and its kin: the device block of the hyper-parameters (allocated once, never moved: graphs bake it)
+static int ensure_hyper_storage(aleppo_ctx *c) {
+  if (!c->hyper_blk) {
+    HIPCHK(c, dalloc(&c->hyper_blk, HYPER_BLOCK * 4, c->stream));
+    HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_hyper_blk), HYPER_BLOCK * 4, hipHostMallocDefault));
+  }
+  return ALEPPO_OK;
+}
+
 // ALEPPO_OPT_VALUE_CLIP: the env-major old-values plane, RT [E*T] (allocated on first use, never moved: graphs bake it)
 static int ensure_val_storage(aleppo_ctx *c) {
   if (!c->val_n)
@@ -1298,7 +1309,13 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
   const int H = c->H, A = c->A, prec = c->prec;
   const ParamLayout &L = c->L;
   hipStream_t s = c->stream;
-  const Hyper hp{c->cfg.clip_param, c->cfg.value_loss_coef, c->cfg.entropy_coef, c->cfg.max_gradient_norm};
+  // The hyper-parameters of this call: kernel arguments - or, once one of ALEPPO_OPT_CLIP_PARAM and its kin was set, the
+  // device block hpd, which the *_dev_kernel entry points of the head and of Adam read (a captured update follows it)
+  const Hyper hp = c->hyper;
+  const bool hyper_dev = c->hyper_dev;
+  if (hyper_dev && (rc = ensure_hyper_storage(c)))
+    return rc;
+  const float *const hpd = hyper_dev ? c->hyper_blk : nullptr;
 
   // Adam's per-step scalars for the whole call, uploaded once: step size lr / (1 - beta1^t) and sqrt(1 - beta2^t) are
   // DEVICE values the Adam kernel reads (kernel arguments would be baked into a captured graph)
@@ -1309,6 +1326,16 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
     c->h_adam_sched[2 * i + 1] = (float)std::sqrt(1.0 - std::pow(b2, t));
   }
   HIPCHK(c, hipMemcpyAsync(c->adam_sched, c->h_adam_sched, (size_t)nm * 8, hipMemcpyHostToDevice, s));
+  if (hyper_dev) { // ... and the hyper-parameter block, for the same reason
+    float *b = c->h_hyper_blk;
+    std::memset(b, 0, HYPER_BLOCK * 4);
+    b[HYPER_CLIP] = hp.clip;
+    b[HYPER_VCLIP] = c->vclip_range_set ? c->value_clip_range : hp.clip;
+    b[HYPER_CV] = hp.c_v;
+    b[HYPER_CE] = hp.c_e;
+    b[HYPER_MAX_NORM] = hp.max_norm;
+    HIPCHK(c, hipMemcpyAsync(c->hyper_blk, c->h_hyper_blk, HYPER_BLOCK * 4, hipMemcpyHostToDevice, s));
+  }
   // ... and, with ALEPPO_OPT_KL_PENALTY, beta: the head kernel reads it from device memory for the same reason
   if (klpen) {
     std::memcpy(c->h_kl_beta, &c->kl_coef_bits, 4);
@@ -1404,15 +1431,23 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
         map.idx = c->order + (size_t)ep * N;
       const int hparts = net_forward(c, c->obs, map, B, FC_FWD_MAX_PARTS);
       prof_begin(c, ALEPPO_K_HEAD);
-      launch_head_train(s, c->h, Pf(c, P_WH), Pf(c, P_BH), act + p0, rp(c, oldlp, p0 * A), rp(c, adv, p0),
-                        rp(c, ret, p0), vold ? rp(c, vold, p0) : nullptr, mask + p0, counts + (shuffle ? mi : mb), hp,
-                        c->dh, prec,
-                        c->metric_ps + 0 * fs + (size_t)mi * B, c->metric_ps + 1 * fs + (size_t)mi * B,
-                        c->metric_ps + 2 * fs + (size_t)mi * B, c->metric_ps + 3 * fs + (size_t)mi * B,
-                        c->metric_ps + 4 * fs + (size_t)mi * B, c->metric_ps + 5 * fs + (size_t)mi * B,
-                        c->metric_ps + 6 * fs + (size_t)mi * B, sWh, sBh, nblk_head, B, H, A, nullptr, nullptr, hparts,
-                        c->rt16, advn ? c->advn_stats + (size_t)(shuffle ? mi : mb) * 4 : nullptr,
-                        klpen ? c->kl_beta : nullptr, klpen ? c->kl_ps + (size_t)mi * B : nullptr);
+      float *const mps = c->metric_ps + (size_t)mi * B; // this minibatch's slice of every per-sample metric plane
+      const float *mcount = counts + (shuffle ? mi : mb);
+      const float *advs = advn ? c->advn_stats + (size_t)(shuffle ? mi : mb) * 4 : nullptr;
+      const float *klb = klpen ? c->kl_beta : nullptr;
+      float *ps_kle = klpen ? c->kl_ps + (size_t)mi * B : nullptr;
+      if (hpd)
+        launch_head_train_dev(s, c->h, Pf(c, P_WH), Pf(c, P_BH), act + p0, rp(c, oldlp, p0 * A), rp(c, adv, p0),
+                              rp(c, ret, p0), vold ? rp(c, vold, p0) : nullptr, mask + p0, mcount, hpd, c->dh, prec,
+                              mps + 0 * fs, mps + 1 * fs, mps + 2 * fs, mps + 3 * fs, mps + 4 * fs, mps + 5 * fs,
+                              mps + 6 * fs, sWh, sBh, nblk_head, B, H, A, nullptr, nullptr, hparts, c->rt16, advs, klb,
+                              ps_kle);
+      else
+        launch_head_train(s, c->h, Pf(c, P_WH), Pf(c, P_BH), act + p0, rp(c, oldlp, p0 * A), rp(c, adv, p0),
+                          rp(c, ret, p0), vold ? rp(c, vold, p0) : nullptr, mask + p0, mcount, hp, c->dh, prec,
+                          mps + 0 * fs, mps + 1 * fs, mps + 2 * fs, mps + 3 * fs, mps + 4 * fs, mps + 5 * fs,
+                          mps + 6 * fs, sWh, sBh, nblk_head, B, H, A, nullptr, nullptr, hparts, c->rt16, advs, klb,
+                          ps_kle);
       prof_end(c, ALEPPO_K_HEAD);
       HIPCHK(c, fork(c->ev_head)); // dh is ready
       prof_begin(c, ALEPPO_K_FC_DGRAD);
@@ -1537,7 +1572,7 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
       // (the Adam kernel also writes the bf16 compute copy and the dgrad-side transposed layouts W2d / W3d / WfcT)
       launch_adam(s, c->P, c->G, nullptr, c->M1, c->M2, c->prec == ALEPPO_BF16 ? c->Pc : nullptr, c->WfcT, c->W3d, c->W2d,
                   L, prec, c->sumsq_part, nblk_norm, hp.max_norm, c->adam_sched + 2 * mi, c->cfg.adam_beta1,
-                  c->cfg.adam_beta2, c->cfg.adam_eps, c->grad_norms + mi);
+                  c->cfg.adam_beta2, c->cfg.adam_eps, c->grad_norms + mi, hpd);
       prof_end(c, ALEPPO_K_ADAM);
     }
   if (shuffle) // (epoch ep's masks in its order: minibatch mi's are the mi-th B of mask_p)
@@ -1564,6 +1599,7 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
   key.advn = advn ? c->advn_stats : nullptr;
   key.klpen = klpen ? 1 : 0;
   key.kl_ps = klpen ? c->kl_ps : nullptr;
+  key.hyper_dev = hyper_dev ? 1 : 0;
   const bool want_graph = c->update_graph && !dp && !c->prof_on;
   if (want_graph && c->graph_exec && c->graph_key == key) {
     HIPCHK(c, hipGraphLaunch(c->graph_exec, s));
@@ -1619,6 +1655,7 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
   c->last_shuffled = shuffle;
   c->last_advn = advn;
   c->last_kl = klpen;
+  c->last_max_norm = hp.max_norm;
   if (out)
     for (int i = 0; i < nm; ++i) {
       const float *r = c->h_metric_red + (size_t)i * METRIC_REC;
@@ -1986,12 +2023,22 @@ extern "C" int aleppo_comm_init(aleppo_ctx *c, const uint8_t id[ALEPPO_UNIQUE_ID
 }
 
 // ------------------------------------------------------------------ profiling
+static uint32_t float_bits(float f) {
+  uint32_t u;
+  std::memcpy(&u, &f, 4);
+  return u;
+}
 extern "C" int aleppo_set_option(aleppo_ctx *c, int option, int value) {
   CHECK_CTX(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   // a captured update holds the kernels the switches selected when it was recorded: any change re-arms the capture -
-  // except beta (ALEPPO_OPT_KL_COEF), a device value uploaded at each aleppo_train, which a replay reads as it is
-  if (option != ALEPPO_OPT_KL_COEF) {
+  // except beta (ALEPPO_OPT_KL_COEF) and the five hyper-parameter options, device values uploaded at each aleppo_train,
+  // which a replay reads as they are.  (The FIRST of those five to be set moves the context to the device-block entry
+  // points: that is a different graph key, hyper_dev, so the next update runs eagerly and the one after is captured anew.)
+  const bool hyper_opt = option == ALEPPO_OPT_CLIP_PARAM || option == ALEPPO_OPT_VALUE_CLIP_RANGE ||
+                         option == ALEPPO_OPT_VALUE_LOSS_COEF || option == ALEPPO_OPT_ENTROPY_COEF ||
+                         option == ALEPPO_OPT_MAX_GRAD_NORM;
+  if (option != ALEPPO_OPT_KL_COEF && !hyper_opt) {
     c->graph_key = Ctx::GraphKey();
     c->warm_key = Ctx::GraphKey();
   }
@@ -2034,6 +2081,30 @@ extern "C" int aleppo_set_option(aleppo_ctx *c, int option, int value) {
       return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT,
                      "ALEPPO_OPT_KL_COEF: the binary32 bits of a finite non-negative float (not -0.0, Inf or NaN)");
     c->kl_coef_bits = (uint32_t)value;
+  } else if (hyper_opt) {
+    // the bits of a finite float, > 0 or (the two coefficients) >= 0: as an int, [1 or 0, 0x7F800000) - see above
+    const bool zero_ok = option == ALEPPO_OPT_VALUE_LOSS_COEF || option == ALEPPO_OPT_ENTROPY_COEF;
+    if (value < (zero_ok ? 0 : 1) || value >= 0x7F800000)
+      return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT,
+                     zero_ok ? "ALEPPO_OPT_VALUE_LOSS_COEF / ALEPPO_OPT_ENTROPY_COEF: the binary32 bits of a finite "
+                               "non-negative float (not -0.0, Inf or NaN)"
+                             : "ALEPPO_OPT_CLIP_PARAM / ALEPPO_OPT_VALUE_CLIP_RANGE / ALEPPO_OPT_MAX_GRAD_NORM: the "
+                               "binary32 bits of a finite float > 0 (not zero, Inf or NaN)");
+    float f;
+    const uint32_t bits = (uint32_t)value;
+    std::memcpy(&f, &bits, 4);
+    if (option == ALEPPO_OPT_CLIP_PARAM)
+      c->hyper.clip = f;
+    else if (option == ALEPPO_OPT_VALUE_CLIP_RANGE) {
+      c->value_clip_range = f;
+      c->vclip_range_set = true;
+    } else if (option == ALEPPO_OPT_VALUE_LOSS_COEF)
+      c->hyper.c_v = f;
+    else if (option == ALEPPO_OPT_ENTROPY_COEF)
+      c->hyper.c_e = f;
+    else
+      c->hyper.max_norm = f;
+    c->hyper_dev = true; // from now on the update's head and Adam kernels read all of them from the device block
   } else if (option == ALEPPO_OPT_UPDATE_GRAPH)
     c->update_graph = value != 0;
   else if (option == ALEPPO_OPT_GATE_TIMEOUT_MS)
@@ -2061,6 +2132,13 @@ extern "C" int aleppo_get_option(aleppo_ctx *c, int option, int64_t *value) {
   case ALEPPO_OPT_ADV_NORM_MINIBATCH: *value = c->adv_norm_mb; break;
   case ALEPPO_OPT_KL_PENALTY: *value = c->kl_pen; break;
   case ALEPPO_OPT_KL_COEF: *value = (int64_t)c->kl_coef_bits; break;
+  case ALEPPO_OPT_CLIP_PARAM: *value = (int64_t)float_bits(c->hyper.clip); break;
+  case ALEPPO_OPT_VALUE_CLIP_RANGE:
+    *value = (int64_t)float_bits(c->vclip_range_set ? c->value_clip_range : c->hyper.clip);
+    break;
+  case ALEPPO_OPT_VALUE_LOSS_COEF: *value = (int64_t)float_bits(c->hyper.c_v); break;
+  case ALEPPO_OPT_ENTROPY_COEF: *value = (int64_t)float_bits(c->hyper.c_e); break;
+  case ALEPPO_OPT_MAX_GRAD_NORM: *value = (int64_t)float_bits(c->hyper.max_norm); break;
   case ALEPPO_OPT_GATE_TIMEOUT_MS: *value = (int64_t)(c->gate_timeout_ticks / 100000ull); break;
   default: return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "unknown option");
   }

@@ -59,6 +59,7 @@
     sW[i] = Wh[i];
   __syncthreads();
   const float inv_nm = 1.0f / mask_count[0];
+  HEAD_HYPER_LOAD
   float kl_beta = 0.f;
   if constexpr (KLPEN)
     kl_beta = klb[0]; // ALEPPO_OPT_KL_COEF: a device value, so that a graph replay follows a beta changed between calls
@@ -173,14 +174,14 @@
       }
       const float logr = lpa - olpa;
       const float rho = expf(logr);                                        // losses.cc:33
-      const float crho = fminf(fmaxf(rho, 1.0f - hp.clip), 1.0f + hp.clip); // losses.cc:34-35
+      const float crho = fminf(fmaxf(rho, 1.0f - hp_clip), 1.0f + hp_clip); // losses.cc:34-35
       const float un = rho * advi, cl = crho * advi;
       const float obj = fminf(un, cl);                                     // losses.cc:38
       const float dv = value - reti;
       float lv, dvg; // value loss and its derivative in v (before the mask and c_v)
       if constexpr (VCLIP) { // aleppo.h ALEPPO_OPT_VALUE_CLIP: a select, so that inside the range vc IS value
         const float d = value - voldi;
-        const float vc = fabsf(d) <= hp.clip ? value : voldi + copysignf(hp.clip, d);
+        const float vc = fabsf(d) <= hp_vclip ? value : voldi + copysignf(hp_vclip, d);
         const float dc = vc - reti;
         const float lu = dv * dv, lc = dc * dc;
         lv = 0.5f * fmaxf(lu, lc);
@@ -189,13 +190,13 @@
         lv = 0.5f * (dv * dv);                                             // losses.cc:15
         dvg = dv;
       }
-      float Ltot = -obj + hp.c_v * lv - hp.c_e * ent;                      // losses.cc:17-18
+      float Ltot = -obj + hp_cv * lv - hp_ce * ent;                      // losses.cc:17-18
       if constexpr (KLPEN) {
         if (kl_beta != 0.f) // (a branch, not + 0 * KL: beta = 0 leaves every number of the option-off kernel as it was)
           Ltot += kl_beta * kl;
       }
       const float m = maski ? inv_nm : 0.f;                                // losses.cc:19 masked mean
-      const bool active = advi >= 0.f ? (rho <= 1.0f + hp.clip) : (rho >= 1.0f - hp.clip);
+      const bool active = advi >= 0.f ? (rho <= 1.0f + hp_clip) : (rho >= 1.0f - hp_clip);
       const float gs = active ? -rho * advi : 0.f;
       float dz[A1];
 #pragma unroll
@@ -203,9 +204,9 @@
         dz[a] = 0.f;
         if (a < A && a < AMAX)
           dz[a] = m * (gs * ((a == ai ? 1.0f : 0.0f) - p[a < AMAX ? a : 0]) +
-                       hp.c_e * p[a < AMAX ? a : 0] * (lp[a < AMAX ? a : 0] + ent));
+                       hp_ce * p[a < AMAX ? a : 0] * (lp[a < AMAX ? a : 0] + ent));
         if (a == A)
-          dz[a] = m * hp.c_v * dvg;
+          dz[a] = m * hp_cv * dvg;
       }
       if constexpr (KLPEN) {
         if (kl_beta != 0.f) { // d(beta KL)/dz_j = beta (p_j S - q_j): S, not 1, the exact derivative when sum q != 1
@@ -223,7 +224,7 @@
         ps_entropy[row] = ent;
         ps_ratio[row] = rho;
         ps_kl[row] = (rho - 1.0f) - logr;                                  // approx-KL (k3 estimator)
-        ps_cf[row] = fabsf(rho - 1.0f) > hp.clip ? 1.0f : 0.0f;           // clip fraction (strict)
+        ps_cf[row] = fabsf(rho - 1.0f) > hp_clip ? 1.0f : 0.0f;           // clip fraction (strict)
         if constexpr (KLPEN)
           ps_kle[row] = kl;                                                // exact KL (ALEPPO_M_KL)
         if (logits_out) {

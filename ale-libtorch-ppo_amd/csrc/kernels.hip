@@ -5,20 +5,11 @@
 // conversions used only at the C-ABI boundary.  Each kernel cites the reference code it replaces.
 #include "common.hpp"
 #include "gemm.hpp" // bf16 / vector typedefs
+#include "head_train.hpp" // f16, wave_sum, and what the head kernel's entry points share
 #include <cstdlib>
 
 namespace aleppo {
 
-// Rollout-plane storage type RT: float (the reference's Buffer, buffer.cc:12-38) or IEEE half (BASELINE configs[4],
-// "fp16 rollout buffer").  Arithmetic is always fp32: planes are widened on load and rounded (RNE) on store.
-typedef _Float16 f16;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-    v += __shfl_xor(v, o, 64);
-  return v;
-}
 // deterministic block reduction (256 threads): wave shuffles, then wave 0 sums the 4 partials in order
 __device__ __forceinline__ float block_sum_256(float v, float *s4) {
   v = wave_sum(v);
@@ -824,112 +815,16 @@ void launch_shuffle_gather(hipStream_t s, const uint32_t *rk, int h, long N, int
 // head_train_kl_kernel (KLPEN on, with advantage normalisation a run-time switch: advs may be null).
 // Waves per workgroup: 8, or 4 where one wave per SIMD needs more than 256 registers - the wide action sets, and with
 // the KL penalty (its S / KL pass and the q_a of the gradient) from AMAX = 10 on (8 waves spilled ~40 registers there).
-constexpr int head_waves(int amax, bool klpen) { return amax > 10 || (klpen && amax > 6) ? 4 : 8; }
-#define HEAD_PARAMS                                                                                                    \
-  const float *__restrict__ h, const float *__restrict__ Wh, const float *__restrict__ bh, const int *__restrict__ act, \
-      const RT *__restrict__ oldlp, const RT *__restrict__ adv, const RT *__restrict__ ret,                            \
-      const RT *__restrict__ vold, const uint8_t *__restrict__ mask, const float *__restrict__ mask_count, Hyper hp,   \
-      T *dh, float *ps_total, float *ps_clipped, float *ps_value, float *ps_entropy, float *ps_ratio, float *ps_kl,    \
-      float *ps_cf, float *slab_w, float *slab_b, long B, int H, int A, float *logits_out, float *values_out, int hparts
-template <class T, int AMAX, class RT, bool VCLIP>
-__global__ __launch_bounds__(AMAX > 10 ? 256 : 512) void head_train_kernel(HEAD_PARAMS) {
-  constexpr bool ADVN = false, KLPEN = false;
-  const float *advs = nullptr, *klb = nullptr;
-  float *ps_kle = nullptr;
-#include "head_train_body.inc"
-}
-// advs: float [4] of this minibatch (mean_f, inv_f, std, 0)
-template <class T, int AMAX, class RT, bool VCLIP>
-__global__ __launch_bounds__(AMAX > 10 ? 256 : 512) void head_train_advn_kernel(HEAD_PARAMS,
-                                                                                 const float *__restrict__ advs) {
-  constexpr bool ADVN = true, KLPEN = false;
-  const float *klb = nullptr;
-  float *ps_kle = nullptr;
-#include "head_train_body.inc"
-}
-// advs: as above, or nullptr (no minibatch normalisation); klb: float [1], beta; ps_kle: float [B], the exact KL per row
-template <class T, int AMAX, class RT, bool VCLIP>
-__global__ __launch_bounds__(64 * head_waves(AMAX, true)) void head_train_kl_kernel(HEAD_PARAMS,
-                                                                               const float *__restrict__ advs,
-                                                                               const float *__restrict__ klb,
-                                                                               float *ps_kle) {
-  constexpr bool ADVN = true, KLPEN = true;
-#define HEAD_TRAIN_PASSES
-#include "head_train_body.inc"
-#undef HEAD_TRAIN_PASSES
-}
-#undef HEAD_PARAMS
-
-template <class T, class RT, bool VCLIP>
-static void head_train_t(hipStream_t s, const float *h, const float *Wh, const float *bh, const int *act,
-                         const RT *oldlp, const RT *adv, const RT *ret, const RT *vold, const uint8_t *mask,
-                         const float *mask_count, Hyper hp, void *dh, float *ps_total, float *ps_clipped,
-                         float *ps_value, float *ps_entropy, float *ps_ratio, float *ps_kl, float *ps_cf, float *slab_w,
-                         float *slab_b, int nblk, long B, int H, int A, float *lo, float *vo, int hparts,
-                         const float *advs, const float *klb, float *ps_kle) {
-#define HEAD_LAUNCH_ARGS                                                                                               \
-  h, Wh, bh, act, oldlp, adv, ret, vold, mask, mask_count, hp, static_cast<T *>(dh), ps_total, ps_clipped, ps_value,    \
-      ps_entropy, ps_ratio, ps_kl, ps_cf, slab_w, slab_b, B, H, A, lo, vo, hparts
-#define LAUNCH_HEAD(AM)                                                                                                \
-  do {                                                                                                                 \
-    const size_t sm = ((size_t)((AM + 1) + ((AM + 1) > 8 ? (AM + 1) : 8)) * H + 8 * (AM + 1)) * sizeof(float);        \
-    const void *fn = klb    ? reinterpret_cast<const void *>(&head_train_kl_kernel<T, AM, RT, VCLIP>)                  \
-                     : advs ? reinterpret_cast<const void *>(&head_train_advn_kernel<T, AM, RT, VCLIP>)                \
-                            : reinterpret_cast<const void *>(&head_train_kernel<T, AM, RT, VCLIP>);                    \
-    if (sm > 48 * 1024)                                                                                                \
-      (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);                              \
-    if (klb)                                                                                                           \
-      hipLaunchKernelGGL((head_train_kl_kernel<T, AM, RT, VCLIP>), dim3(nblk), dim3(64 * head_waves(AM, true)), sm, s, \
-                         HEAD_LAUNCH_ARGS, advs, klb, ps_kle);                                                         \
-    else if (advs)                                                                                                     \
-      hipLaunchKernelGGL((head_train_advn_kernel<T, AM, RT, VCLIP>), dim3(nblk), dim3(AM > 10 ? 256 : 512), sm, s,     \
-                         HEAD_LAUNCH_ARGS, advs);                                                                      \
-    else                                                                                                               \
-      hipLaunchKernelGGL((head_train_kernel<T, AM, RT, VCLIP>), dim3(nblk), dim3(AM > 10 ? 256 : 512), sm, s,          \
-                         HEAD_LAUNCH_ARGS);                                                                            \
-  } while (0)
-  if (A <= 4)
-    LAUNCH_HEAD(4);
-  else if (A <= 6)
-    LAUNCH_HEAD(6);
-  else if (A <= 10)
-    LAUNCH_HEAD(10);
-  else
-    LAUNCH_HEAD(18);
-#undef LAUNCH_HEAD
-#undef HEAD_LAUNCH_ARGS
-}
-void launch_head_train(hipStream_t s, const float *h, const float *Wh, const float *bh, const int *act,
-                       const void *oldlp, const void *adv, const void *ret, const void *vold, const uint8_t *mask,
-                       const float *mask_count, Hyper hp, void *dh, int prec, float *ps_total, float *ps_clipped,
-                       float *ps_value, float *ps_entropy, float *ps_ratio, float *ps_kl, float *ps_cf, float *slab_w,
-                       float *slab_b, int nblk, long B, int H, int A, float *logits_out, float *values_out, int hparts,
-                       bool rt16, const float *advs, const float *klb, float *ps_kle) {
-#define HEAD_ARGS(RT)                                                                                                  \
-  s, h, Wh, bh, act, static_cast<const RT *>(oldlp), static_cast<const RT *>(adv), static_cast<const RT *>(ret),       \
-      static_cast<const RT *>(vold), mask, mask_count, hp, dh, ps_total, ps_clipped, ps_value, ps_entropy, ps_ratio,   \
-      ps_kl, ps_cf, slab_w, slab_b, nblk, B, H, A, logits_out, values_out, hparts, advs, klb, ps_kle
-#define HEAD_T(T, RT)                                                                                                  \
-  do {                                                                                                                 \
-    if (vold)                                                                                                          \
-      head_train_t<T, RT, true>(HEAD_ARGS(RT));                                                                        \
-    else                                                                                                               \
-      head_train_t<T, RT, false>(HEAD_ARGS(RT));                                                                       \
-  } while (0)
-  if (prec == ALEPPO_BF16) {
-    if (rt16)
-      HEAD_T(bf16, f16);
-    else
-      HEAD_T(bf16, float);
-  } else {
-    if (rt16)
-      HEAD_T(float, f16);
-    else
-      HEAD_T(float, float);
-  }
-#undef HEAD_T
-#undef HEAD_ARGS
-}
+// The entry points and their launcher are the text of head_train_entry.inc, instantiated twice: here with the hyper-
+// parameters as a kernel argument (the default route), and in head_hyper.hip with the device block of
+// ALEPPO_OPT_CLIP_PARAM and its kin (head_train_dev_kernel / head_train_advn_dev_kernel / head_train_kl_dev_kernel).
+#define HEAD_KERNEL head_train_kernel
+#define HEAD_ADVN_KERNEL head_train_advn_kernel
+#define HEAD_KL_KERNEL head_train_kl_kernel
+#define HEAD_LAUNCH launch_head_train
+#define HEAD_HP_T Hyper
+#define HEAD_HYPER_LOAD const float hp_clip = hp.clip, hp_vclip = hp.clip, hp_cv = hp.c_v, hp_ce = hp.c_e;
+#include "head_train_entry.inc"
 
 // ================================================================================================
 // Split-K slab reduction -> flat gradient (fixed summation order => run-to-run deterministic).
@@ -1138,116 +1033,23 @@ __global__ __launch_bounds__(256) void adam_kernel(float *P, const float *__rest
                                                     long4_ranges fr, const float *__restrict__ partials, int nblk,
                                                     float max_norm, const float *__restrict__ sched, float beta1,
                                                     float beta2, float eps, float *grad_norm_out) {
-  __shared__ float s4[4];
-  __shared__ float tile[64][65];
-  float s = 0.f;
-  for (int i = threadIdx.x; i < nblk; i += 256)
-    s += partials[i];
-  s = block_sum_256(s, s4);
-  const float norm = sqrtf(s);
-  float coef = max_norm / (norm + 1e-6f); // train.cc:39
-  coef = fminf(coef, 1.0f);               // train.cc:40-41
-  if (blockIdx.x == 0 && threadIdx.x == 0 && grad_norm_out)
-    *grad_norm_out = norm;                // pre-clip norm is what the reference reports (Q9)
-  // lr / (1 - beta1^t) and sqrt(1 - beta2^t) of THIS optimizer step: device scalars (a captured hipGraph of the update
-  // follows the annealed rate and the step count; the reference's captured graph bakes both, train.h:163-195)
-  const AdamScalars a{coef, sched[0], sched[1], beta1, beta2, 1.0f - beta1, 1.0f - beta2, eps};
-  const int ntile = tl.first[3];
-  if ((int)blockIdx.x < ntile) { // a 64-row tile of Wfc / W3 / W2
-    const int t = blockIdx.x;
-    long src;      // flat index of tile element (0, 0)
-    int rs, rows, cols;
-    T *dst;        // transposed element (c, r) at dst[c * ds + r]
-    int ds;
-    if (t < tl.first[1]) {          // Wfc[o][j] -> WfcT[j][o]: tile (o-block, j-block of 64; 3136 = 49 * 64)
-      const int ob = t / 49, jb = t - ob * 49;
-      rs = FC_IN;
-      rows = min(64, tl.H - ob * 64);
-      cols = 64;
-      src = tl.off[0] + (long)ob * 64 * FC_IN + jb * 64;
-      dst = WfcT + (long)jb * 64 * tl.H + ob * 64;
-      ds = tl.H;
-    } else if (t < tl.first[2]) {   // W3[oc][tap][c] -> W3d[c][tap][oc]: one tile per tap
-      const int tap = t - tl.first[1];
-      rs = 576;
-      rows = 64;
-      cols = 64;
-      src = tl.off[1] + tap * 64;
-      dst = W3d + tap * 64;
-      ds = 576;
-    } else {                        // W2[oc][(kh,kw)][c] -> W2d[class][c][(ab)][oc]: one 64 x 32 tile per (kh, kw)
-      const int k = t - tl.first[2], kh = k >> 2, kw = k & 3;
-      const int cls = (kh & 1) * 2 + (kw & 1), ab = (kh >> 1) * 2 + (kw >> 1);
-      rs = 512;
-      rows = 64;
-      cols = 32;
-      src = tl.off[2] + k * 32;
-      dst = W2d + cls * (32 * 256) + ab * 64;
-      ds = 256;
-    }
-    const int c = threadIdx.x & 63, r4 = threadIdx.x >> 6;
-    if (c < cols) {
-      // all 64 loads of a thread's 16 elements are issued before the first store (P / M1 / M2 are read and written through
-      // the same pointers, so the compiler may not hoist them itself; a dependent load-compute-store chain per element made
-      // this kernel latency-bound: 23 vs 13 us)
-      float g[16], m1[16], m2[16], p0[16];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) {
-        const int r = r4 + 4 * k;
-        const long i = src + (long)(r < rows ? r : 0) * rs + c;
-        g[k] = G[i];
-        m1[k] = M1[i];
-        m2[k] = M2[i];
-        p0[k] = P[i];
-      }
-#pragma unroll
-      for (int k = 0; k < 16; ++k) {
-        const int r = r4 + 4 * k;
-        if (r < rows) {
-          const long i = src + (long)r * rs + c;
-          const float gg = g[k] * a.coef;
-          const float m = m1[k] * a.beta1 + a.omb1 * gg;
-          const float v = m2[k] * a.beta2 + a.omb2 * (gg * gg);
-          const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-          const float p = p0[k] - a.step_size * (m / denom);
-          M1[i] = m;
-          M2[i] = v;
-          P[i] = p;
-          if (Gs)
-            Gs[i] = gg;
-          if (Pc)
-            Pc[i] = (T)p;
-          tile[r][c] = p;
-        }
-      }
-    }
-    __syncthreads();
-    const int r = threadIdx.x & 63, c4 = threadIdx.x >> 6;
-    if (r < rows)
-      for (int cc = c4; cc < cols; cc += 4)
-        dst[(long)cc * ds + r] = (T)tile[r][cc];
-    return;
-  }
-  // everything else, flat: index k of the compacted space of the (at most four) ranges between the tiled tensors
-  const long stride = (long)(gridDim.x - ntile) * 256;
-  for (long k = (long)((int)blockIdx.x - ntile) * 256 + threadIdx.x; k < n_flat; k += stride) {
-    long i = k;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      if (i < fr.len[q]) {
-        i += fr.begin[q];
-        break;
-      }
-      i -= fr.len[q];
-    }
-    const float p = adam_element(i, P, G, Gs, M1, M2, a);
-    if (Pc)
-      Pc[i] = (T)p;
-  }
+#include "adam_body.inc"
+}
+// hpd: the device block of the hyper-parameter options (common.hpp HYPER_*), read once per workgroup
+template <class T>
+__global__ __launch_bounds__(256) void adam_dev_kernel(float *P, const float *__restrict__ G, float *Gs, float *M1,
+                                                        float *M2, T *Pc, T *WfcT, T *W3d, T *W2d, AdamTiles tl,
+                                                        long n_flat, long4_ranges fr,
+                                                        const float *__restrict__ partials, int nblk,
+                                                        const float *__restrict__ hpd, const float *__restrict__ sched,
+                                                        float beta1, float beta2, float eps, float *grad_norm_out) {
+  const float max_norm = hpd[HYPER_MAX_NORM];
+#include "adam_body.inc"
 }
 void launch_adam(hipStream_t s, float *P, const float *G_in, float *G_out_scaled, float *M1, float *M2, void *Pc,
                  void *WfcT, void *W3d, void *W2d, const ParamLayout &L, int prec, const float *partials, int nblk,
-                 float max_norm, const float *sched, float beta1, float beta2, float eps, float *grad_norm_out) {
+                 float max_norm, const float *sched, float beta1, float beta2, float eps, float *grad_norm_out,
+                 const float *hpd) {
   AdamTiles tl;
   tl.off[0] = (long)L.off[P_WFC];
   tl.off[1] = (long)L.off[P_W3];
@@ -1268,6 +1070,19 @@ void launch_adam(hipStream_t s, float *P, const float *G_in, float *G_out_scaled
     n_flat += fr.len[q];
   }
   const int nb = tl.first[3] + (int)std::min<long>((n_flat + 255) / 256, 1024);
+  if (hpd) {
+    if (prec == ALEPPO_BF16)
+      hipLaunchKernelGGL(adam_dev_kernel<bf16>, dim3(nb), dim3(256), 0, s, P, G_in, G_out_scaled, M1, M2,
+                         static_cast<bf16 *>(Pc), static_cast<bf16 *>(WfcT), static_cast<bf16 *>(W3d),
+                         static_cast<bf16 *>(W2d), tl, n_flat, fr, partials, nblk, hpd, sched, beta1, beta2, eps,
+                         grad_norm_out);
+    else
+      hipLaunchKernelGGL(adam_dev_kernel<float>, dim3(nb), dim3(256), 0, s, P, G_in, G_out_scaled, M1, M2,
+                         static_cast<float *>(nullptr), static_cast<float *>(WfcT), static_cast<float *>(W3d),
+                         static_cast<float *>(W2d), tl, n_flat, fr, partials, nblk, hpd, sched, beta1, beta2, eps,
+                         grad_norm_out);
+    return;
+  }
   if (prec == ALEPPO_BF16)
     hipLaunchKernelGGL(adam_kernel<bf16>, dim3(nb), dim3(256), 0, s, P, G_in, G_out_scaled, M1, M2,
                        static_cast<bf16 *>(Pc), static_cast<bf16 *>(WfcT), static_cast<bf16 *>(W3d),

@@ -493,12 +493,43 @@ typedef enum {
                                       E epochs equals E one-epoch calls bit for bit.  Read back: ALEPPO_M_KL /
                                       ALEPPO_M_MEAN_KL.  Adapting beta between updates (the paper's rule) is the caller's
                                       part: the trainer's kl_target does it */
-  ALEPPO_OPT_KL_COEF = 16          /* beta of ALEPPO_OPT_KL_PENALTY as the IEEE-754 binary32 BIT PATTERN in `value`
+  ALEPPO_OPT_KL_COEF = 16,         /* beta of ALEPPO_OPT_KL_PENALTY as the IEEE-754 binary32 BIT PATTERN in `value`
                                       (default 0 = +0.0f).  Valid: exactly the finite non-negative floats, value in
                                       [0, 0x7F800000); -0.0, negative values, Inf and NaN are ALEPPO_ERR_INVALID_ARGUMENT.
                                       aleppo_get_option returns the bits.  A device value, uploaded at each aleppo_train:
                                       a captured update (ALEPPO_OPT_UPDATE_GRAPH) follows a beta changed between calls,
                                       and unlike the other options setting it does not re-arm the capture */
+  /* 17-21: the clip range, the loss coefficients and the gradient-norm limit PER UPDATE (baselines ppo2's annealed
+     cliprange, SB3's clip_range / clip_range_vf schedules, RLlib's entropy_coeff_schedule).  Each carries the IEEE-754
+     binary32 BIT PATTERN of its float in `value`, like ALEPPO_OPT_KL_COEF, and replaces one aleppo_config value from the
+     next aleppo_train on.  An invalid pattern (-0.0, a negative value, Inf, NaN, and zero where > 0 is required) is
+     ALEPPO_ERR_INVALID_ARGUMENT and leaves the old value in place.  Until an option is set aleppo_get_option returns the
+     bits of the config value it stands for; there is no "unset", and setting the config's own value is allowed.
+     The values are read at each aleppo_train and hold for the whole call (no schedule inside a call).  They are device
+     values uploaded at the start of the call, next to Adam's step scalars: a captured update (ALEPPO_OPT_UPDATE_GRAPH)
+     follows values changed between calls, and setting one does not re-arm the capture.  A context on which none of the
+     five was ever set launches the kernels it always launched, with the numbers as kernel arguments, and uploads nothing;
+     from the first set on (of any of them, for all of them) it uses entry points of the head and Adam kernels that read
+     the numbers from device memory - the one switch of route a captured update is recorded anew for.  The arithmetic is
+     the same text: a context created with values X and one created with other values and set to X give bit-identical
+     parameters, Adam state, metrics, per-sample planes and gradients.  They work on every schedule the other options
+     work on: eager or captured, fp32 or bf16, fp32 or fp16 rollout planes, rollout and aleppo_set_batch batches, with
+     ALEPPO_OPT_MINIBATCH_SHUFFLE, ALEPPO_OPT_VALUE_CLIP, ALEPPO_OPT_ADV_NORM_MINIBATCH and ALEPPO_OPT_KL_PENALTY in any
+     combination, one GPU or data parallel.  With data parallelism EVERY RANK MUST SET THE SAME VALUES before the same
+     update (they are not exchanged: ranks that clip or weigh differently apply different steps and drift apart). */
+  ALEPPO_OPT_CLIP_PARAM = 17,      /* replaces config.clip_param: the range of the clipped surrogate, of the clip-fraction
+                                      metric (ALEPPO_M_CLIP_FRACTION), and of ALEPPO_OPT_VALUE_CLIP's c unless
+                                      ALEPPO_OPT_VALUE_CLIP_RANGE was set.  Valid: finite and > 0 */
+  ALEPPO_OPT_VALUE_CLIP_RANGE = 18, /* the c of ALEPPO_OPT_VALUE_CLIP only (SB3's clip_range_vf); nothing else reads it.
+                                      Until it is set it IS the current clip parameter, and follows ALEPPO_OPT_CLIP_PARAM
+                                      (aleppo_get_option returns those bits); once set it stays what it was set to.
+                                      Valid: finite and > 0 */
+  ALEPPO_OPT_VALUE_LOSS_COEF = 19, /* replaces config.value_loss_coef.  Valid: finite and >= 0 (+0.0: no value gradient) */
+  ALEPPO_OPT_ENTROPY_COEF = 20,    /* replaces config.entropy_coef.  Valid: finite and >= 0 */
+  ALEPPO_OPT_MAX_GRAD_NORM = 21    /* replaces config.max_gradient_norm, the limit of the global-norm clip in front of
+                                      Adam.  The reported grad_norm is the norm before clipping and does not depend on
+                                      it; aleppo_export_grads scales by the limit the last aleppo_train ran with.
+                                      Valid: finite and > 0 */
 } aleppo_option;
 int aleppo_set_option(aleppo_ctx *ctx, int option, int value);
 /* Current value of an option; for ALEPPO_OPT_UPDATE_GRAPH the number of graph launches so far (0 = every update ran

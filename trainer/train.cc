@@ -41,7 +41,14 @@
 // trainer logs kl_coef (the beta of the rollout's update) and mean_kl (d).  log_batch_stats: false (true: after every
 // rollout that is trained on, ALEPPO_F_BATCH_STATS is read - a collective under data parallelism, so every rank reads -
 // and explained_variance, mean_value / std_value, mean_return / std_return, mean_advantage / std_advantage are logged;
-// a NaN explained variance is logged as NaN).
+// a NaN explained variance is logged as NaN).  clip_param_final, value_loss_coef_final, entropy_coef_final,
+// max_gradient_norm_final (absent: the value stays what the config says and no option is set; given: rollout i of
+// num_rollouts updates with v0 + (v_final - v0) * i / num_rollouts, computed in double and rounded to float once - the
+// shape of the learning-rate anneal, which never reaches its end value either - set through ALEPPO_OPT_CLIP_PARAM /
+// _VALUE_LOSS_COEF / _ENTROPY_COEF / _MAX_GRAD_NORM before the update, logged under the key's own name (clip_param, ...)
+// and recorded in the hparams; every rank computes the same values) and value_clip_range (a constant:
+// ALEPPO_OPT_VALUE_CLIP_RANGE, SB3's clip_range_vf; needs clip_value_loss).  Values the options would refuse are
+// refused when the config is loaded.
 // Data parallelism (no reference counterpart): start one process per GPU with RANK / WORLD_SIZE / LOCAL_RANK
 // in the environment (torchrun / mpirun style).  Rank r owns the contiguous environment block
 // [r * E / W, (r + 1) * E / W) and GPU LOCAL_RANK; rank 0 creates the RCCL id, hands it to the others through the file
@@ -88,6 +95,13 @@ struct Config {
   double target_kl = 0.0;           // extension: early stop of the update's epochs on approx-KL (<= 0: off)
   double kl_coef = 0.0, kl_target = 0.0; // extension: adaptive KL penalty (ALEPPO_OPT_KL_PENALTY; <= 0: off / fixed beta)
   bool kl_coef_set = false, kl_target_set = false; // (the keys were given: hparams entries)
+  // extension: per-update hyper-parameters (ALEPPO_OPT_CLIP_PARAM and its kin).  *_final: the end of a linear schedule
+  // from the value above; *_set: the key was given (absent keys set no option)
+  double clip_param_final = 0, value_loss_coef_final = 0, entropy_coef_final = 0, max_gradient_norm_final = 0;
+  bool clip_param_final_set = false, value_loss_coef_final_set = false, entropy_coef_final_set = false,
+       max_gradient_norm_final_set = false;
+  double value_clip_range = 0; // constant c of the clipped value loss (ALEPPO_OPT_VALUE_CLIP_RANGE)
+  bool value_clip_range_set = false;
   bool log_batch_stats = false; // extension: explained variance and value / return / advantage statistics (ALEPPO_F_BATCH_STATS)
   // extensions
   std::string precision = "fp32", rollout_precision = "fp32";
@@ -181,6 +195,30 @@ static Config load_config(const std::string &path) { // keys / defaults of src/b
     throw std::runtime_error("kl_coef / kl_target must be finite and non-negative");
   if (c.kl_target > 0 && !(c.kl_coef > 0)) // (it would adapt a penalty that is off)
     throw std::runtime_error("kl_target needs kl_coef > 0");
+  // the per-update hyper-parameters: what the options would refuse is refused here (they are floats: < 3e38 is finite)
+  auto sched_key = [&](const char *key, double &v, bool &set, double v0, bool zero_ok) {
+    set = kv.count(key) != 0;
+    if (!set)
+      return;
+    v = as<double>(kv, key, 0.0);
+    const bool ok = (zero_ok ? v >= 0 : v > 0) && v < 3.0e38 && (zero_ok ? v0 >= 0 : v0 > 0) && v0 < 3.0e38;
+    if (!ok) // (the schedule's start is the config's own value: it has to be settable too)
+      throw std::runtime_error(std::string(key) + (zero_ok ? " and the value it starts from must be finite and non-negative"
+                                                           : " and the value it starts from must be finite and positive"));
+  };
+  sched_key("clip_param_final", c.clip_param_final, c.clip_param_final_set, c.clip_param, false);
+  sched_key("value_loss_coef_final", c.value_loss_coef_final, c.value_loss_coef_final_set, c.value_loss_coef, true);
+  sched_key("entropy_coef_final", c.entropy_coef_final, c.entropy_coef_final_set, c.entropy_coef, true);
+  sched_key("max_gradient_norm_final", c.max_gradient_norm_final, c.max_gradient_norm_final_set, c.max_gradient_norm,
+            false);
+  c.value_clip_range_set = kv.count("value_clip_range") != 0;
+  if (c.value_clip_range_set) {
+    c.value_clip_range = as<double>(kv, "value_clip_range", 0.0);
+    if (!(c.value_clip_range > 0 && c.value_clip_range < 3.0e38))
+      throw std::runtime_error("value_clip_range must be finite and positive");
+    if (!c.clip_value_loss) // (nothing else reads it)
+      throw std::runtime_error("value_clip_range needs clip_value_loss: true");
+  }
   c.deterministic = as_bool(kv, "deterministic", false);
   c.precision = as<std::string>(kv, "precision", "fp32");
   c.rollout_precision = as<std::string>(kv, "rollout_precision", "fp32");
@@ -832,6 +870,30 @@ int main(int argc, char **argv) {
     float kl_beta = kl_pen ? (float)cfg.kl_coef : 0.0f;
     if (kl_pen)
       check(ctx, aleppo_set_option(ctx, ALEPPO_OPT_KL_PENALTY, 1));
+    auto set_float_option = [&](int option, float v) { // (the options take the binary32 bit pattern)
+      int32_t bits;
+      std::memcpy(&bits, &v, 4);
+      check(ctx, aleppo_set_option(ctx, option, bits));
+    };
+    if (cfg.value_clip_range_set) // extension: a value-clip range of its own (constant)
+      set_float_option(ALEPPO_OPT_VALUE_CLIP_RANGE, (float)cfg.value_clip_range);
+    // extension: linear schedules of the clip range, the loss coefficients and the norm limit, one value per rollout
+    struct HyperSchedule {
+      const char *name; // the scalar's tag: the config key it schedules
+      int option;
+      double v0, v1;
+    };
+    std::vector<HyperSchedule> hyper_schedules;
+    if (cfg.clip_param_final_set)
+      hyper_schedules.push_back({"clip_param", ALEPPO_OPT_CLIP_PARAM, cfg.clip_param, cfg.clip_param_final});
+    if (cfg.value_loss_coef_final_set)
+      hyper_schedules.push_back({"value_loss_coef", ALEPPO_OPT_VALUE_LOSS_COEF, cfg.value_loss_coef,
+                                 cfg.value_loss_coef_final});
+    if (cfg.entropy_coef_final_set)
+      hyper_schedules.push_back({"entropy_coef", ALEPPO_OPT_ENTROPY_COEF, cfg.entropy_coef, cfg.entropy_coef_final});
+    if (cfg.max_gradient_norm_final_set)
+      hyper_schedules.push_back({"max_gradient_norm", ALEPPO_OPT_MAX_GRAD_NORM, cfg.max_gradient_norm,
+                                 cfg.max_gradient_norm_final});
     if (prof.on())
       check(ctx, aleppo_profile_enable(ctx, 1));
     std::vector<std::pair<std::string, bool>> hparam_flags{{"record_observation", cfg.record_observation},
@@ -861,6 +923,16 @@ int main(int argc, char **argv) {
       hparam_numbers.emplace_back("kl_coef", cfg.kl_coef);
     if (cfg.kl_target_set)
       hparam_numbers.emplace_back("kl_target", cfg.kl_target);
+    if (cfg.clip_param_final_set)
+      hparam_numbers.emplace_back("clip_param_final", cfg.clip_param_final);
+    if (cfg.value_loss_coef_final_set)
+      hparam_numbers.emplace_back("value_loss_coef_final", cfg.value_loss_coef_final);
+    if (cfg.entropy_coef_final_set)
+      hparam_numbers.emplace_back("entropy_coef_final", cfg.entropy_coef_final);
+    if (cfg.max_gradient_norm_final_set)
+      hparam_numbers.emplace_back("max_gradient_norm_final", cfg.max_gradient_norm_final);
+    if (cfg.value_clip_range_set)
+      hparam_numbers.emplace_back("value_clip_range", cfg.value_clip_range);
     logger.add_hparams(hparam_numbers, hparam_flags, group, (double)start_time * 1e-9);
 
     // ---- Rollout host half (src/ai/rollout.cc)
@@ -994,6 +1066,13 @@ int main(int argc, char **argv) {
       // the target (the Adam schedule and the shuffle keys follow the Adam step, so the calls add up to the same update)
       size_t epochs_run = 0;
       const size_t per_call = cfg.target_kl > 0 ? 1 : (size_t)cfg.num_epochs;
+      // this rollout's scheduled hyper-parameters (a function of r alone: the same on every rank)
+      std::vector<float> hyper_now(hyper_schedules.size());
+      for (size_t k = 0; k < hyper_schedules.size(); ++k) {
+        const HyperSchedule &h = hyper_schedules[k];
+        hyper_now[k] = (float)(h.v0 + (h.v1 - h.v0) * (r / static_cast<double>(cfg.num_rollouts)));
+        set_float_option(h.option, hyper_now[k]);
+      }
       if (kl_pen) { // beta of this rollout's update, as its binary32 bit pattern
         int32_t bits;
         std::memcpy(&bits, &kl_beta, 4);
@@ -1082,6 +1161,8 @@ int main(int argc, char **argv) {
         logger.add_scalar("mean_advantage", step, (float)bstats[ALEPPO_BS_ADVANTAGE_MEAN]);
         logger.add_scalar("std_advantage", step, (float)bstats[ALEPPO_BS_ADVANTAGE_STD]);
       }
+      for (size_t k = 0; k < hyper_schedules.size(); ++k) // (the values this rollout's update ran with)
+        logger.add_scalar(hyper_schedules[k].name, step, hyper_now[k]);
       logger.add_scalar("learning_rate", step, (float)lr);
       {
         std::vector<float> gn;
