@@ -48,6 +48,10 @@ METRIC_FIELDS = dict(total_losses=0, clipped_losses=1, value_losses=2, entropies
 METRIC_MEAN_FIELDS = dict(approx_kl=7, clip_fraction=8, kl=12)
 # the [epochs, M] statistics of OPT_ADV_NORM_MINIBATCH (aleppo_read_train_metric; Engine.advantage_stats)
 METRIC_ADV_FIELDS = dict(mean=9, std=10)
+# aleppo_eval_rule / aleppo_eval_field: the evaluation lanes (Engine.eval_open / eval_push_frames / eval_act / eval_read)
+EVAL_GREEDY, EVAL_SAMPLE, EVAL_EPSILON_GREEDY = 0, 1, 2
+EVAL_RULES = dict(greedy=EVAL_GREEDY, sample=EVAL_SAMPLE, epsilon=EVAL_EPSILON_GREEDY)
+EVAL_FIELDS = dict(observations=0, logits=1, values=2, actions=3)
 KERNEL_CLASSES = dict(ingest=0, gae=1, head=2, adam=3, conv1_fwd=4, conv2_fwd=5, conv3_fwd=6, fc_fwd=7, fc_dgrad=8,
                       fc_wgrad=9, conv3_dgrad=10, conv3_wgrad=11, conv2_dgrad=12, conv2_wgrad=13, conv1_wgrad=14,
                       reduce=15, infer_head=16, act_fused=17, conv_fwd=18, conv_bwd=19)
@@ -91,6 +95,7 @@ EXPORTS = [
     "aleppo_import_optimizer", "aleppo_replay_rollout", "aleppo_get_option",
     "aleppo_host_alloc", "aleppo_host_free", "aleppo_arm_step", "aleppo_release_step", "aleppo_device_check",
     "aleppo_read_sample_order", "aleppo_set_batch_values",
+    "aleppo_eval_open", "aleppo_eval_push_frames", "aleppo_eval_act", "aleppo_eval_read",
 ]
 
 
@@ -535,6 +540,42 @@ class Engine:
         collective with a communicator (aleppo.h)"""
         a = self.read_batch("batch_stats")
         return {name: float(a[i]) for name, i in BATCH_STATS.items()}
+
+    # -- evaluation lanes --
+    def eval_open(self, lanes):
+        """aleppo_eval_open: `lanes` frame stacks of their own (1..4096) with their own scratch and action buffer; again
+        with the same count: zero stacks, the built-in noise stream from its start"""
+        self._c(lib().aleppo_eval_open(self._ctx, C.c_int32(int(lanes))))
+        self.eval_lanes = int(lanes)
+
+    def eval_push_frames(self, frames, episode_start, kind=FRAMES_84, device_ptr=None):
+        """aleppo_eval_push_frames: push_frames for the evaluation lanes"""
+        st = _u8(episode_start)
+        if device_ptr is not None:
+            self._c(lib().aleppo_eval_push_frames(self._ctx, C.c_void_p(device_ptr), kind, DEVICE, _ptr(st)))
+        else:
+            self._c(lib().aleppo_eval_push_frames(self._ctx, _ptr(_u8(frames)), kind, HOST, _ptr(st)))
+
+    def eval_act(self, rule="greedy", temperature=1.0, epsilon=0.0, noise=None):
+        """aleppo_eval_act: int64 [L] actions (a view of the lanes' pinned buffer, valid until the next eval_act) under
+        rule "greedy", "sample" (temperature; noise: Exp(1) draws [L, A]) or "epsilon" (epsilon; noise: uniforms (u, w)
+        [L, 2]); noise None: the built-in generator"""
+        r = EVAL_RULES[rule] if isinstance(rule, str) else int(rule)
+        param = temperature if r == EVAL_SAMPLE else epsilon if r == EVAL_EPSILON_GREEDY else 0.0
+        n = None if noise is None else _f32(noise)
+        p = C.POINTER(C.c_int64)()
+        self._c(lib().aleppo_eval_act(self._ctx, C.c_int(r), C.c_float(param), _ptr(n), C.byref(p)))
+        return np.ctypeslib.as_array(p, shape=(self.eval_lanes,))
+
+    def eval_read(self, name):
+        """aleppo_eval_read: "observations" uint8 [L,4,84,84] (the stacks now), or "logits" float32 [L,A] / "values"
+        float32 [L] / "actions" int64 [L] of the last eval_act"""
+        L = getattr(self, "eval_lanes", 1)
+        shp, dt = dict(observations=((L, 4, 84, 84), np.uint8), logits=((L, self.A), np.float32),
+                       values=((L,), np.float32), actions=((L,), np.int64))[name]
+        out = np.zeros(shp, dt)
+        self._c(lib().aleppo_eval_read(self._ctx, EVAL_FIELDS[name], _ptr(out), C.c_size_t(out.nbytes)))
+        return out
 
     # -- multi GPU --
     @staticmethod

@@ -249,6 +249,23 @@ struct Ctx {
   size_t stage_u8_cap = 0;
   uint32_t *stage_obs = nullptr; // packed stacks of aleppo_forward's samples (never the rollout slots)
   size_t stage_obs_cap = 0;
+  // ---- evaluation lanes (aleppo_eval_open): L frame stacks of their own, their own acting scratch, upload staging and
+  // action hand-off; nothing below is allocated, and nothing is enqueued for it, on a context that never opens them
+  int ev_L = 0;                    // 0: not opened
+  uint32_t *ev_obs = nullptr;      // [L][7056] packed stacks, updated in place by ingest_kernel
+  void *ev_a1 = nullptr, *ev_a2 = nullptr, *ev_a3 = nullptr; // conv activations at L samples (a1 / a2: unfused convs only)
+  float *ev_hpart = nullptr;       // [FC_SPLITS][L][H]
+  float *ev_logits = nullptr, *ev_values = nullptr; // [L][A], [L] of the last aleppo_eval_act (always fp32)
+  int *ev_actions = nullptr;       // [L]
+  uint8_t *ev_d_frames = nullptr, *ev_h_frames = nullptr; // frame staging (device / pinned), L raw pairs
+  uint8_t *ev_d_start = nullptr, *ev_h_start = nullptr;   // [L] episode-start flags
+  float *ev_d_noise = nullptr, *ev_h_noise = nullptr;     // [L][max(A, 2)]
+  int64_t *ev_h_actions = nullptr; // [L] + the ticket word, mapped pinned (aleppo_eval_act's *actions_pinned)
+  unsigned int *ev_d_done = nullptr; // arrival counter of eval_head_kernel's ticket publish
+  long long ev_ticket = 0;
+  uint64_t ev_counter = 0;         // evaluation counter n of the built-in generator
+  bool ev_acted = false;           // ev_logits / ev_values / ev_actions hold an aleppo_eval_act
+  hipEvent_t ev_staged = nullptr;  // the last upload out of the pinned staging buffers has run
   bool prof_on = false;
   bool serial_update = false; // ALEPPO_OPT_SERIAL_UPDATE: every update kernel on the main stream
   bool dbg_no_publish = false;
@@ -277,6 +294,12 @@ void launch_infer_head(hipStream_t s, const float *hpart, int nsplit, const floa
                        const float *bh, const float *noise, uint64_t seed, uint64_t counter, void *logits_t,
                        void *values_t, int *actions_t, int64_t *pinned, unsigned int *done_ctr, long long ticket, int E,
                        int H, int A, const float *probs_in = nullptr, bool rt16 = false);
+// head of the evaluation lanes: rule = aleppo_eval_rule, param = 1 / tau (SAMPLE) or epsilon (EPSILON_GREEDY); key = the
+// Philox key of the evaluation stream, counter = the evaluation counter; fp32 outputs; pinned / done_ctr never null
+void launch_eval_head(hipStream_t s, const float *hpart, const float *bfc, const float *Wh, const float *bh,
+                      const float *noise, uint64_t key, uint64_t counter, int rule, float param, float *logits,
+                      float *values, int *actions, int64_t *pinned, unsigned int *done_ctr, long long ticket, int L, int H,
+                      int A);
 void launch_gae(hipStream_t s, uint8_t *step_rec, size_t rec_bytes, const void *values_tm, const void *logits_tm,
                 const int *actions_tm, void *adv_n, void *ret_n, void *oldlp_n, int *act_n, uint8_t *mask_n, int *err,
                 int E, int T, int A, float gamma, float lambda, bool clamp = true, bool rt16 = false);

@@ -315,6 +315,158 @@ void launch_infer_head(hipStream_t s, const float *hpart, int nsplit, const floa
 }
 
 // ================================================================================================
+// Head of the evaluation lanes (aleppo_eval_act; the reference has no evaluation loop - SB3's predict(deterministic) /
+// EvalCallback, the epsilon-greedy evaluation of the DQN / PPO papers).  The forward half is infer_head_kernel's text:
+// the same split-K sum, the same head dot products in the same order, the same softmax and arg-max, so that at
+// rule = SAMPLE with 1 / tau = 1 (an exact multiplication) a lane computes what an environment of aleppo_act computes,
+// bit for bit.  One wave per lane; the rule is workgroup-uniform.  Outputs are always fp32 (they are not rollout planes).
+//   GREEDY          r_k = z_k                                      -> first maximum
+//   SAMPLE          r_k = p_k / q_k, p = softmax(z * inv_tau)      -> first maximum (multinomial via Exp(1) noise)
+//   EPSILON_GREEDY  u < epsilon ? min((int)(w * A), A - 1) : the greedy action
+// Built-in noise (noise == nullptr): Philox4x32-10 under the key the host derived from config.seed and the evaluation
+// domain constant, counter words { n lo, n hi, lane, block } with n the evaluation counter (include/aleppo.h).
+// The hand-off to the host is infer_head_kernel's (system-scope action stores, drained, one ticket by the last workgroup)
+// on the lanes' OWN pinned buffer and arrival counter.
+// ================================================================================================
+template <int NSPLIT>
+__global__ __launch_bounds__(256) void eval_head_kernel(const float *__restrict__ hpart, const float *__restrict__ bfc,
+                                                         const float *__restrict__ Wh, const float *__restrict__ bh,
+                                                         const float *__restrict__ noise, uint64_t key, uint64_t counter,
+                                                         int rule, float param, float *logits_o, float *values_o,
+                                                         int *actions_o, int64_t *pinned, unsigned int *done_ctr,
+                                                         long long ticket, int E, int H, int A) {
+  extern __shared__ float sWh[]; // [(A+1)][H] head weights
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int e = blockIdx.x * 4 + wave;
+  float hv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  {
+    f32x4 part[NSPLIT][2];
+    const bool own = e < E && lane * 8 < H;
+#pragma unroll
+    for (int z = 0; z < NSPLIT; ++z) { // issue every split-K partial load first (independent)
+      const float *src = hpart + ((size_t)z * E + (own ? e : 0)) * H + (own ? lane * 4 : 0);
+      part[z][0] = *reinterpret_cast<const f32x4 *>(src);
+      part[z][1] = *reinterpret_cast<const f32x4 *>(src + H / 2);
+    }
+    {
+      const float *b = bfc + (own ? lane * 4 : 0);
+      const f32x4 b0 = *reinterpret_cast<const f32x4 *>(b), b1 = *reinterpret_cast<const f32x4 *>(b + H / 2);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        hv[i] = b0[i];
+        hv[4 + i] = b1[i];
+      }
+    }
+    for (int k = threadIdx.x; k < (A + 1) * H / 4; k += 256)
+      reinterpret_cast<f32x4 *>(sWh)[k] = reinterpret_cast<const f32x4 *>(Wh)[k];
+#pragma unroll
+    for (int z = 0; z < NSPLIT; ++z)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        hv[i] += part[z][0][i];
+        hv[4 + i] += part[z][1][i];
+      }
+  }
+  __syncthreads();
+  if (e < E) {
+    float zmine = 0.f; // lane a keeps logit a (a < A) / the value (a == A)
+    for (int a = 0; a <= A; ++a) {
+      float s = 0.f;
+      if (lane * 8 < H) {
+        const f32x4 w0 = *reinterpret_cast<const f32x4 *>(sWh + a * H + lane * 4);
+        const f32x4 w1 = *reinterpret_cast<const f32x4 *>(sWh + a * H + H / 2 + lane * 4);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          s += hv[i] * w0[i];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          s += hv[4 + i] * w1[i];
+      }
+      s = wave_sum(s) + bh[a];
+      if (lane == a)
+        zmine = s;
+    }
+    const bool isact = lane < A;
+    const bool sample = rule == ALEPPO_EVAL_SAMPLE; // workgroup-uniform
+    float r = isact ? zmine : -INFINITY;            // GREEDY / EPSILON_GREEDY: the logit itself
+    float u0 = 1.f, u1 = 0.f;                       // EPSILON_GREEDY's (u, w)
+    if (sample) {
+      float mx = isact ? zmine : -3.0e38f;
+#pragma unroll
+      for (int o = 16; o > 0; o >>= 1)
+        mx = fmaxf(mx, __shfl_xor(mx, o, 64)); // A <= 18 < 32
+      const float ex = isact ? expf((zmine - mx) * param) : 0.f; // param = 1 / tau
+      float sum = ex;
+#pragma unroll
+      for (int o = 16; o > 0; o >>= 1)
+        sum += __shfl_xor(sum, o, 64);
+      float q = 1.f;
+      if (isact) {
+        if (noise) {
+          q = noise[(size_t)e * A + lane];
+        } else { // block (n, lane, action / 4): four actions share a block
+          uint32_t c[4] = {(uint32_t)counter, (uint32_t)(counter >> 32), (uint32_t)e, (uint32_t)(lane >> 2)};
+          philox4x32_10(c, (uint32_t)key, (uint32_t)(key >> 32));
+          const uint32_t w = (lane & 3) == 0 ? c[0] : (lane & 3) == 1 ? c[1] : (lane & 3) == 2 ? c[2] : c[3];
+          q = -logf(((float)(w >> 8) + 0.5f) * (1.0f / 16777216.0f)); // u in (0,1)
+        }
+      }
+      const float pk = ex / sum;
+      r = isact ? pk / q : -1.f;
+    } else if (rule == ALEPPO_EVAL_EPSILON_GREEDY) { // (every lane holds the lane's two uniforms: no broadcast needed)
+      if (noise) {
+        u0 = noise[(size_t)e * 2];
+        u1 = noise[(size_t)e * 2 + 1];
+      } else { // block (n, lane, 0): words 0 and 1
+        uint32_t c[4] = {(uint32_t)counter, (uint32_t)(counter >> 32), (uint32_t)e, 0u};
+        philox4x32_10(c, (uint32_t)key, (uint32_t)(key >> 32));
+        u0 = ((float)(c[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+        u1 = ((float)(c[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+      }
+    }
+    int best = lane;
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) { // arg-max, ties -> lowest index (first maximum wins)
+      const float ro = __shfl_xor(r, o, 64);
+      const int bo = __shfl_xor(best, o, 64);
+      if (ro > r || (ro == r && bo < best)) {
+        r = ro;
+        best = bo;
+      }
+    }
+    if (rule == ALEPPO_EVAL_EPSILON_GREEDY && u0 < param) // param = epsilon
+      best = min((int)(u1 * (float)A), A - 1);
+    if (isact)
+      logits_o[(size_t)e * A + lane] = zmine;
+    if (lane == A)
+      values_o[e] = zmine;
+    if (lane == 0) {
+      actions_o[e] = best;
+      __hip_atomic_store(pinned + e, (int64_t)best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+  // publish: infer_head_kernel's hand-off (every storing wave drains, the workgroup meets, the last arriver writes the
+  // ticket at system scope; all atomics relaxed on purpose - see there)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned int prev = __hip_atomic_fetch_add(done_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (prev == gridDim.x - 1) {
+      __hip_atomic_store(done_ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(reinterpret_cast<long long *>(pinned + E), ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
+void launch_eval_head(hipStream_t s, const float *hpart, const float *bfc, const float *Wh, const float *bh,
+                      const float *noise, uint64_t key, uint64_t counter, int rule, float param, float *logits,
+                      float *values, int *actions, int64_t *pinned, unsigned int *done_ctr, long long ticket, int L, int H,
+                      int A) {
+  const size_t sm = (size_t)(A + 1) * H * sizeof(float);
+  hipLaunchKernelGGL((eval_head_kernel<FC_SPLITS>), dim3((L + 3) / 4), dim3(256), sm, s, hpart, bfc, Wh, bh, noise, key,
+                     counter, rule, param, logits, values, actions, pinned, done_ctr, ticket, L, H, A);
+}
+
+// ================================================================================================
 // Reward clamp + GAE + returns + masks + old log-probs in ONE pass: Buffer::get (buffer.cc:58-77),
 // ai::gae::gae (gae.cc:49-79) and prepare_batch's normalize_logits (train.cc:272-283).
 // Rollout scalars are time-major [T][E] so each wave reads 64 consecutive environments per slot

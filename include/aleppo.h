@@ -337,6 +337,67 @@ int aleppo_read_batch(aleppo_ctx *ctx, int field, void *dst, size_t bytes);
  * [n,4,84,84] -> logits float [n,A], values float [n].  n <= max(E, max_minibatch). */
 int aleppo_forward(aleppo_ctx *ctx, const uint8_t *observations, int64_t n, float *logits, float *values);
 
+/* ------------------------------------------------------------------ evaluation lanes (the reference has no evaluation
+ * loop: SB3's predict(deterministic=True) / EvalCallback, the epsilon-greedy scores of the DQN / PPO papers)
+ * L frame stacks of their own, next to the rollout, on which the network acts under one of three rules - so that a
+ * trained (or half-trained) agent can be scored on OTHER emulator instances without touching the batch being collected.
+ * Per evaluation step the caller does  eval_act -> (step its L evaluation emulators) -> eval_push_frames; returns and
+ * episode lengths are the caller's bookkeeping, as they are for training.
+ * Isolation: the four calls change nothing the rollout or the update can observe - not the rollout's stacks and planes,
+ * t, the acting generator's counter, the pre-computed acting scratch of aleppo_step, aleppo_act's pinned buffer and
+ * ticket, Adam state, metrics or a captured update.  A training run with evaluation calls inserted at any point where no
+ * step is armed (between an aleppo_step and the aleppo_act that follows it included) is bit-identical to the run without
+ * them.  While a step is armed all four fail with ALEPPO_ERR_RUNTIME like every other stateful entry point; before
+ * aleppo_eval_open the other three are ALEPPO_ERR_RUNTIME.  The lanes are local to a rank: nothing is exchanged under
+ * data parallelism and no call is a collective. */
+typedef enum { ALEPPO_EVAL_GREEDY = 0, ALEPPO_EVAL_SAMPLE = 1, ALEPPO_EVAL_EPSILON_GREEDY = 2 } aleppo_eval_rule;
+typedef enum {
+  ALEPPO_EF_OBSERVATIONS = 0, /* uint8 [L,4,84,84] the lanes' stacks right now */
+  ALEPPO_EF_LOGITS = 1,       /* float [L,A] of the last aleppo_eval_act (always fp32, whatever rollout_precision is) */
+  ALEPPO_EF_VALUES = 2,       /* float [L] */
+  ALEPPO_EF_ACTIONS = 3       /* int64 [L] */
+} aleppo_eval_field;
+/* Allocates, in this call and never later, everything the lanes need: the packed stacks (zeroed), the pinned action
+ * buffer, upload staging for frames / start flags / noise, and the lanes' OWN acting scratch (the conv3 output and the
+ * split-K fc partials; the conv1 / conv2 outputs too where the context's acting convolutions are separate launches: fp32,
+ * or ALEPPO_OPT_GENERIC_CONV set BEFORE this call - a bf16 context that switches to the generic convolutions afterwards
+ * gets ALEPPO_ERR_RUNTIME from aleppo_eval_act).  1 <= num_lanes <= 4096 (ALEPPO_ERR_INVALID_ARGUMENT otherwise).
+ * Called again with the same num_lanes it zeroes the stacks, restarts the evaluation counter at 0 and forgets the last
+ * aleppo_eval_act; with another num_lanes it is ALEPPO_ERR_RUNTIME.  Nothing is freed before aleppo_destroy. */
+int aleppo_eval_open(aleppo_ctx *ctx, int32_t num_lanes);
+/* aleppo_push_frames for the L lanes: same arguments and meaning (both frame kinds, all three locations, the gray LUT of
+ * aleppo_set_gray_lut), through the same ingest kernel, in place on the evaluation stacks.  A lane whose episode_start
+ * flag is set gets its new frame in all four positions. */
+int aleppo_eval_push_frames(aleppo_ctx *ctx, const uint8_t *frames, int frame_kind, int location,
+                            const uint8_t *episode_start);
+/* Eval forward on the lanes' stacks with the parameters as they stand (after the last aleppo_train / aleppo_load_params):
+ * aleppo_act's acting kernels, then the evaluation head.  With z the fp32 logits:
+ *   ALEPPO_EVAL_GREEDY          the lowest index of the maximum of z.  param must be 0 and noise NULL; nothing is drawn.
+ *   ALEPPO_EVAL_SAMPLE          param = the temperature tau, finite and > 0 (and 1 / tau finite in fp32).  With inv = 1 / tau
+ *                               computed once in fp32: e_k = expf((z_k - max z) * inv), p_k = e_k / sum e, action =
+ *                               argmax_k p_k / q_k, first maximum wins.  noise: float [L,A] of Exp(1) draws q, or NULL.
+ *                               At tau = 1 the multiplication is exact and the rule is aleppo_act's, instruction for
+ *                               instruction.
+ *   ALEPPO_EVAL_EPSILON_GREEDY  param = epsilon in [0, 1].  noise: float [L,2] of uniforms (u, w) in [0, 1), or NULL.  A
+ *                               lane explores iff u < epsilon; its action is then min((int)(w * A), A - 1), w * A rounded
+ *                               once in fp32; otherwise the greedy action.
+ * Anything else (an unknown rule, a NaN / Inf / out-of-range param, noise given to GREEDY) is
+ * ALEPPO_ERR_INVALID_ARGUMENT, and such a call changes nothing.
+ * Built-in generator (noise == NULL): Philox4x32-10, the block function of aleppo_act's generator, under the key
+ *   K = config.seed ^ 0x4556414C4C414E45 ("EVALLANE"; key words K lo, K hi) - another stream than aleppo_act's, whose key
+ *   is config.seed.  n = the evaluation counter: 0 at aleppo_eval_open, + 1 per successful aleppo_eval_act whatever the
+ *   rule (GREEDY included).  Counter words { n lo, n hi, lane, block }, output words c[0..3]:
+ *     SAMPLE          block = k / 4, q_k = -logf(U(c[k % 4]))
+ *     EPSILON_GREEDY  block = 0, u = U(c[0]), w = U(c[1])
+ *   with U(x) = ((x >> 8) + 0.5) / 2^24 in fp32, as aleppo_act draws its uniforms.
+ * *actions_pinned (may be NULL): int64 [L] in page-locked host memory owned by ctx - a buffer of its own, not aleppo_act's -
+ * valid when the call returns and until the next aleppo_eval_act. */
+int aleppo_eval_act(aleppo_ctx *ctx, int rule, float param, const float *noise, const int64_t **actions_pinned);
+/* Read an aleppo_eval_field; synchronises the context's stream like aleppo_read_batch.  A wrong byte count is
+ * ALEPPO_ERR_INVALID_ARGUMENT; fields 1-3 before the first aleppo_eval_act (since aleppo_eval_open) are
+ * ALEPPO_ERR_RUNTIME. */
+int aleppo_eval_read(aleppo_ctx *ctx, int field, void *dst, size_t bytes);
+
 /* ------------------------------------------------------------------ multi-GPU (no reference counterpart)
  * One process per GPU.  Rank 0 creates the id, the launcher broadcasts its bytes, every rank calls
  * aleppo_comm_init.  Gradients (+ mask counts) are all-reduced with RCCL inside aleppo_train. */

@@ -48,7 +48,15 @@
 // _VALUE_LOSS_COEF / _ENTROPY_COEF / _MAX_GRAD_NORM before the update, logged under the key's own name (clip_param, ...)
 // and recorded in the hparams; every rank computes the same values) and value_clip_range (a constant:
 // ALEPPO_OPT_VALUE_CLIP_RANGE, SB3's clip_range_vf; needs clip_value_loss).  Values the options would refuse are
-// refused when the config is loaded.
+// refused when the config is loaded.  eval_interval (absent or 0: off; n: after the update of every n-th rollout, before the
+// next rollout, the agent plays eval_episodes - default 10 - full episodes, life loss to life loss like the training
+// episodes, on eval_environments - default 8 - SyntheticAtari instances of its own, seeded past every training
+// environment of every rank, through the evaluation lanes: aleppo_eval_open / aleppo_eval_push_frames / aleppo_eval_act,
+// stepped by the same worker pool) with eval_rule: greedy|sample|epsilon (default greedy), eval_temperature (default 1)
+// and eval_epsilon (default 0.05); logs eval/episode_return_mean, eval/episode_return_max, eval/episode_length_mean and
+// eval/episodes on the training scalars' step axis.  Each evaluation starts from freshly reset emulators and stacks, and
+// the lanes change nothing the rollout or the update can observe: the training run is bit-identical to the run without
+// the keys.  Under data parallelism every rank evaluates its own lanes and rank 0's are logged.
 // Data parallelism (no reference counterpart): start one process per GPU with RANK / WORLD_SIZE / LOCAL_RANK
 // in the environment (torchrun / mpirun style).  Rank r owns the contiguous environment block
 // [r * E / W, (r + 1) * E / W) and GPU LOCAL_RANK; rank 0 creates the RCCL id, hands it to the others through the file
@@ -78,6 +86,17 @@
 #include <thread>
 #include <vector>
 
+// The evaluation lanes are declared weak: a build linked against a library without them (the host-only stand-in of the
+// ThreadSanitizer build) still links, and a config that asks for evaluation is then refused at start-up.
+extern "C" {
+int aleppo_eval_open(aleppo_ctx *ctx, int32_t num_lanes) __attribute__((weak));
+int aleppo_eval_push_frames(aleppo_ctx *ctx, const uint8_t *frames, int frame_kind, int location,
+                            const uint8_t *episode_start) __attribute__((weak));
+int aleppo_eval_act(aleppo_ctx *ctx, int rule, float param, const float *noise, const int64_t **actions_pinned)
+    __attribute__((weak));
+int aleppo_eval_read(aleppo_ctx *ctx, int field, void *dst, size_t bytes) __attribute__((weak));
+}
+
 // ------------------------------------------------------------------ config
 struct Config {
   size_t total_environments = 512, hidden_size = 512, action_size = 4, horizon = 128, max_steps = 108000,
@@ -102,6 +121,10 @@ struct Config {
        max_gradient_norm_final_set = false;
   double value_clip_range = 0; // constant c of the clipped value loss (ALEPPO_OPT_VALUE_CLIP_RANGE)
   bool value_clip_range_set = false;
+  // extension: periodic evaluation episodes through the evaluation lanes (aleppo_eval_*)
+  size_t eval_interval = 0, eval_environments = 8, eval_episodes = 10;
+  std::string eval_rule = "greedy";
+  double eval_temperature = 1.0, eval_epsilon = 0.05;
   bool log_batch_stats = false; // extension: explained variance and value / return / advantage statistics (ALEPPO_F_BATCH_STATS)
   // extensions
   std::string precision = "fp32", rollout_precision = "fp32";
@@ -218,6 +241,31 @@ static Config load_config(const std::string &path) { // keys / defaults of src/b
       throw std::runtime_error("value_clip_range must be finite and positive");
     if (!c.clip_value_loss) // (nothing else reads it)
       throw std::runtime_error("value_clip_range needs clip_value_loss: true");
+  }
+  { // evaluation: what aleppo_eval_open / aleppo_eval_act would refuse is refused here
+    const long interval = as<long>(kv, "eval_interval", 0), envs = as<long>(kv, "eval_environments", 8),
+               episodes = as<long>(kv, "eval_episodes", 10);
+    if (interval < 0)
+      throw std::runtime_error("eval_interval must be non-negative");
+    for (const char *k : {"eval_environments", "eval_episodes", "eval_rule", "eval_temperature", "eval_epsilon"})
+      if (kv.count(k) && interval == 0)
+        throw std::runtime_error(std::string(k) + " needs eval_interval > 0");
+    if (envs < 1 || envs > 4096)
+      throw std::runtime_error("eval_environments must be in [1, 4096]");
+    if (episodes < 1)
+      throw std::runtime_error("eval_episodes must be positive");
+    c.eval_interval = (size_t)interval;
+    c.eval_environments = (size_t)envs;
+    c.eval_episodes = (size_t)episodes;
+    c.eval_rule = as<std::string>(kv, "eval_rule", "greedy");
+    if (c.eval_rule != "greedy" && c.eval_rule != "sample" && c.eval_rule != "epsilon")
+      throw std::runtime_error("eval_rule must be greedy, sample or epsilon");
+    c.eval_temperature = as<double>(kv, "eval_temperature", 1.0);
+    if (!(c.eval_temperature > 0 && c.eval_temperature < 3.0e38) || !std::isfinite(1.0f / (float)c.eval_temperature))
+      throw std::runtime_error("eval_temperature must be finite and positive");
+    c.eval_epsilon = as<double>(kv, "eval_epsilon", 0.05);
+    if (!(c.eval_epsilon >= 0 && c.eval_epsilon <= 1))
+      throw std::runtime_error("eval_epsilon must be in [0, 1]");
   }
   c.deterministic = as_bool(kv, "deterministic", false);
   c.precision = as<std::string>(kv, "precision", "fp32");
@@ -763,6 +811,9 @@ int main(int argc, char **argv) {
       std::cout << "initial parameters written: " << p.size() << std::endl;
       return 0;
     }
+    if (cfg.eval_interval > 0 && !(aleppo_eval_open && aleppo_eval_push_frames && aleppo_eval_act && aleppo_eval_read))
+      throw std::runtime_error("eval_interval is set but this build's library has no evaluation lanes "
+                               "(aleppo_eval_open is missing)");
     aleppo_config ac{};
     ac.abi_version = ALEPPO_ABI_VERSION;
     ac.device_ordinal = local_rank;
@@ -896,6 +947,7 @@ int main(int argc, char **argv) {
                                  cfg.max_gradient_norm_final});
     if (prof.on())
       check(ctx, aleppo_profile_enable(ctx, 1));
+    std::vector<std::pair<std::string, double>> hparam_numbers_eval;
     std::vector<std::pair<std::string, bool>> hparam_flags{{"record_observation", cfg.record_observation},
                                                            {"record_video", cfg.record_video},
                                                            {"cuda_graph", cfg.cuda_graph},
@@ -908,6 +960,14 @@ int main(int argc, char **argv) {
       hparam_flags.emplace_back("minibatch_advantage_norm", true);
     if (cfg.log_batch_stats)
       hparam_flags.emplace_back("log_batch_stats", true);
+    if (cfg.eval_interval > 0) { // (only when set, like the others)
+      hparam_numbers_eval = {{"eval_interval", (double)cfg.eval_interval},
+                             {"eval_environments", (double)cfg.eval_environments},
+                             {"eval_episodes", (double)cfg.eval_episodes},
+                             {"eval_rule", cfg.eval_rule == "greedy" ? 0.0 : cfg.eval_rule == "sample" ? 1.0 : 2.0},
+                             {"eval_temperature", cfg.eval_temperature},
+                             {"eval_epsilon", cfg.eval_epsilon}};
+    }
     std::vector<std::pair<std::string, double>> hparam_numbers{ // get_parameters (train.cc:76-105), same keys
         {"total_environments", (double)cfg.total_environments}, {"hidden_size", (double)cfg.hidden_size},
         {"action_size", (double)cfg.action_size}, {"horizon", (double)cfg.horizon}, {"max_steps", (double)cfg.max_steps},
@@ -933,6 +993,7 @@ int main(int argc, char **argv) {
       hparam_numbers.emplace_back("max_gradient_norm_final", cfg.max_gradient_norm_final);
     if (cfg.value_clip_range_set)
       hparam_numbers.emplace_back("value_clip_range", cfg.value_clip_range);
+    hparam_numbers.insert(hparam_numbers.end(), hparam_numbers_eval.begin(), hparam_numbers_eval.end());
     logger.add_hparams(hparam_numbers, hparam_flags, group, (double)start_time * 1e-9);
 
     // ---- Rollout host half (src/ai/rollout.cc)
@@ -960,7 +1021,13 @@ int main(int argc, char **argv) {
     const int64_t *actions = nullptr;
     size_t total_steps = 0, episodes = 0;
     std::cout << "Creating " << cfg.num_workers << " worker threads." << std::endl;
+    std::atomic<bool> eval_mode{false}; // the pool steps the evaluation emulators instead (set around run_all only)
+    std::function<void(size_t)> eval_step;
     WorkerPool pool(cfg.num_workers, [&](size_t i) { // Rollout::step (rollout.cc:299-328)
+      if (eval_mode.load()) {
+        eval_step(i);
+        return;
+      }
       if (start_cpu[i]) {
         envs[i].reset(&frames[i * fbytes]);
         results[i] = StepOut{};
@@ -1037,6 +1104,85 @@ int main(int argc, char **argv) {
         check(ctx, aleppo_finish_rollout(ctx, nullptr));
       }
       return log;
+    };
+
+    // ---- evaluation (eval_interval): full episodes on emulators of its own through the evaluation lanes.  Nothing here
+    // touches the training emulators, their flags or the rollout: the lanes have their own stacks, scratch and noise stream.
+    const size_t L = cfg.eval_interval > 0 ? cfg.eval_environments : 0;
+    std::vector<SyntheticAtari> eval_envs;
+    uint8_t *eval_frames = nullptr;
+    std::vector<uint8_t> eval_start(L, 1);
+    std::vector<StepOut> eval_results(L);
+    const int64_t *eval_actions = nullptr;
+    if (L > 0) {
+      check(ctx, aleppo_eval_open(ctx, (int32_t)L));
+      check(ctx, aleppo_host_alloc(ctx, L * fbytes, reinterpret_cast<void **>(&eval_frames)));
+    }
+    eval_step = [&](size_t i) {
+      if (eval_start[i]) {
+        eval_envs[i].reset(&eval_frames[i * fbytes]);
+        eval_results[i] = StepOut{};
+      } else {
+        const int64_t a = eval_actions[i];
+        if (a < 0 || (size_t)a >= A)
+          throw std::out_of_range("Action index out of range for evaluation environment " + std::to_string(i));
+        eval_results[i] = eval_envs[i].step((int)a, &eval_frames[i * fbytes]);
+      }
+    };
+    struct EvalLog {
+      float return_mean = 0, return_max = 0, length_mean = 0;
+      size_t episodes = 0;
+    };
+    auto evaluate = [&](size_t round) {
+      // fresh emulators per evaluation, seeded past every rank's training environments (env0 + i < total_environments)
+      eval_envs.clear();
+      for (size_t i = 0; i < L; ++i)
+        eval_envs.emplace_back(cfg.total_environments + (round * (size_t)world + (size_t)rank) * L + i, cfg.max_steps,
+                               cfg.max_return, A, cfg.device_preprocess);
+      std::fill(eval_start.begin(), eval_start.end(), 1);
+      std::vector<float> ret(L, 0.f), returns;
+      std::vector<size_t> len(L, 0), lengths;
+      const int rule = cfg.eval_rule == "greedy" ? ALEPPO_EVAL_GREEDY
+                                                 : cfg.eval_rule == "sample" ? ALEPPO_EVAL_SAMPLE : ALEPPO_EVAL_EPSILON_GREEDY;
+      const float param = rule == ALEPPO_EVAL_SAMPLE ? (float)cfg.eval_temperature
+                                                     : rule == ALEPPO_EVAL_EPSILON_GREEDY ? (float)cfg.eval_epsilon : 0.f;
+      const int fkind = cfg.device_preprocess ? ALEPPO_FRAMES_RAW_PAIR : ALEPPO_FRAMES_84;
+      while (returns.size() < cfg.eval_episodes) {
+        check(ctx, aleppo_eval_act(ctx, rule, param, nullptr, &eval_actions));
+        const std::vector<uint8_t> start_at_entry = eval_start;
+        eval_mode.store(true);
+        pool.run_all(L);
+        eval_mode.store(false);
+        check(ctx, aleppo_eval_push_frames(ctx, eval_frames, fkind, ALEPPO_HOST_MAPPED, start_at_entry.data()));
+        for (size_t i = 0; i < L; ++i) {
+          if (!start_at_entry[i]) {
+            ret[i] += eval_results[i].reward;
+            len[i]++;
+          }
+          if (eval_results[i].terminated || eval_results[i].truncated) {
+            if (returns.size() < cfg.eval_episodes) { // (the first eval_episodes to finish, in lane order within a step)
+              returns.push_back(ret[i]);
+              lengths.push_back(len[i]);
+            }
+            ret[i] = 0;
+            len[i] = 0;
+            eval_start[i] = 1;
+          } else {
+            eval_start[i] = 0;
+          }
+        }
+      }
+      // the ingest of the last push reads eval_frames in place: it must have run before the next evaluation's workers
+      // (or the training loop's host_free) touch the buffer
+      // (aleppo_eval_read synchronises the context's stream)
+      std::vector<float> last_values(L);
+      check(ctx, aleppo_eval_read(ctx, ALEPPO_EF_VALUES, last_values.data(), L * sizeof(float)));
+      EvalLog e;
+      e.return_mean = meanf(returns);
+      e.return_max = *std::max_element(returns.begin(), returns.end());
+      e.length_mean = meanf(lengths);
+      e.episodes = returns.size();
+      return e;
     };
 
     rollout(); // the warm rollout before the loop (train.cc:391-396): collected, never trained on
@@ -1164,6 +1310,14 @@ int main(int argc, char **argv) {
       for (size_t k = 0; k < hyper_schedules.size(); ++k) // (the values this rollout's update ran with)
         logger.add_scalar(hyper_schedules[k].name, step, hyper_now[k]);
       logger.add_scalar("learning_rate", step, (float)lr);
+      if (cfg.eval_interval > 0 && (r + 1) % cfg.eval_interval == 0) { // between this update and the next rollout
+        Profile::Span sp(&prof, "evaluate");
+        const EvalLog e = evaluate(r / cfg.eval_interval);
+        logger.add_scalar("eval/episode_return_mean", step, e.return_mean);
+        logger.add_scalar("eval/episode_return_max", step, e.return_max);
+        logger.add_scalar("eval/episode_length_mean", step, e.length_mean);
+        logger.add_scalar("eval/episodes", step, (float)e.episodes);
+      }
       {
         std::vector<float> gn;
         for (size_t i = 0; i < nrun; ++i)
@@ -1214,6 +1368,8 @@ int main(int argc, char **argv) {
     }
     check(ctx, aleppo_host_free(ctx, frames));
     check(ctx, aleppo_host_free(ctx, start_mapped));
+    if (eval_frames)
+      check(ctx, aleppo_host_free(ctx, eval_frames));
     aleppo_destroy(ctx);
     std::cout << "Success" << std::endl;
     return 0;
