@@ -36,7 +36,11 @@ ABI_VERSION = 2
 UNIQUE_ID_BYTES = 128
 
 FIELDS = dict(observations=0, actions=1, rewards=2, masks=3, logits=4, values=5, advantages=6, returns=7,
-              log_probs=8, terminals=9, truncations=10, current_obs=11, next_values=12, batch_stats=13)
+              log_probs=8, terminals=9, truncations=10, current_obs=11, next_values=12, batch_stats=13,
+              reward_scale=14)
+# ALEPPO_F_REWARD_SCALE: the indices of its ALEPPO_REWARD_SCALE_COUNT doubles (aleppo_reward_scale_stat; Engine.reward_scale)
+REWARD_SCALE_COUNT = 6
+REWARD_SCALE = dict(count=0, mean=1, var=2, scale=3, batch_count=4, clipped=5)
 # ALEPPO_F_BATCH_STATS: the indices of its ALEPPO_BATCH_STATS_COUNT doubles (aleppo_batch_stat; Engine.batch_stats)
 BATCH_STATS_COUNT = 10
 BATCH_STATS = dict(count=0, explained_variance=1, value_mean=2, value_std=3, return_mean=4, return_std=5,
@@ -70,6 +74,8 @@ OPT_KL_PENALTY = 15
 OPT_KL_COEF = 16  # (the value is beta's binary32 bit pattern: Engine.set_kl_coef / Engine.kl_coef)
 # the per-update hyper-parameters, each as its binary32 bit pattern (Engine.set_hyper / Engine.hyper)
 OPT_CLIP_PARAM, OPT_VALUE_CLIP_RANGE, OPT_VALUE_LOSS_COEF, OPT_ENTROPY_COEF, OPT_MAX_GRAD_NORM = 17, 18, 19, 20, 21
+# return-based reward scaling in place of the clamp (Engine.set_reward_scaling); the clip as its binary32 bit pattern
+OPT_REWARD_SCALE, OPT_REWARD_SCALE_CLIP = 23, 24  # (22 is unassigned)
 HYPER_OPTIONS = dict(clip_param=OPT_CLIP_PARAM, value_clip_range=OPT_VALUE_CLIP_RANGE,
                      value_loss_coef=OPT_VALUE_LOSS_COEF, entropy_coef=OPT_ENTROPY_COEF,
                      max_grad_norm=OPT_MAX_GRAD_NORM)
@@ -96,6 +102,7 @@ EXPORTS = [
     "aleppo_host_alloc", "aleppo_host_free", "aleppo_arm_step", "aleppo_release_step", "aleppo_device_check",
     "aleppo_read_sample_order", "aleppo_set_batch_values",
     "aleppo_eval_open", "aleppo_eval_push_frames", "aleppo_eval_act", "aleppo_eval_read",
+    "aleppo_export_reward_scale", "aleppo_import_reward_scale", "aleppo_reward_scale",
 ]
 
 
@@ -259,7 +266,31 @@ def _sample(probs, q, device=0):
     return a
 
 
+def _reward_scale(rewards, terminals, truncations, episode_starts, gamma, clip, stats, returns, device=0):
+    """aleppo_reward_scale: OPT_REWARD_SCALE's five steps on one rollout, env-major [E,T], through the kernels
+    finish_rollout launches.  stats = (count, mean, var), returns = the running returns float64 [E], both BEFORE the
+    rollout.  Returns (scaled rewards float32 [E,T], stats after float64 [3], returns after float64 [E], scale float32,
+    clipped int); the arguments are not modified."""
+    r = _f32(rewards).copy()
+    if r.ndim != 2 or np.ndim(terminals) != 2 or np.ndim(truncations) != 2 or np.ndim(episode_starts) != 2:
+        raise AleppoInvalidArgument("All input tensors must be 2D except returns which must be 1D.")
+    E, T = r.shape
+    te, tr, st = _u8(terminals), _u8(truncations), _u8(episode_starts)
+    g = np.array(returns, dtype=np.float64).ravel()
+    if te.shape != (E, T) or tr.shape != (E, T) or st.shape != (E, T) or g.shape != (E,):
+        raise AleppoInvalidArgument("Input tensors must have compatible dimensions.")
+    s3 = np.array(stats, dtype=np.float64).ravel()
+    if s3.shape != (3,):
+        raise AleppoInvalidArgument("stats must be (count, mean, var)")
+    scale, clipped = C.c_float(), C.c_int64()
+    _check(lib().aleppo_reward_scale(C.c_int(device), _ptr(r), _ptr(te), _ptr(tr), _ptr(st), C.c_int64(E), C.c_int64(T),
+                                     C.c_float(gamma), C.c_float(clip), _ptr(s3), _ptr(g), C.byref(scale),
+                                     C.byref(clipped)))
+    return r, s3, g, np.float32(scale.value), int(clipped.value)
+
+
 gae = SimpleNamespace(gae=_gae)
+rewards = SimpleNamespace(scale=_reward_scale)
 vision = SimpleNamespace(resize_frame_stacked_grayscale_images=_resize_frame_stacked_grayscale_images,
                          rgb_to_grayscale_frame_stacked_images=_rgb_to_grayscale_frame_stacked_images,
                          preprocess=_preprocess)
@@ -336,13 +367,45 @@ class Engine:
         v = np.zeros(self.param_count, np.float32)
         step = C.c_int64()
         self._c(lib().aleppo_export_optimizer(self._ctx, _ptr(m), _ptr(v), C.byref(step), C.c_size_t(m.size)))
-        return dict(params=self.export_params(), exp_avg=m, exp_avg_sq=v, step=np.int64(step.value))
+        sd = dict(params=self.export_params(), exp_avg=m, exp_avg_sq=v, step=np.int64(step.value))
+        if self.get_option(OPT_REWARD_SCALE):  # (only while the option is on: the keys other callers see stay the same)
+            sd["reward_scale"] = self.reward_scale_state()
+        return sd
 
     def load_state_dict(self, sd):
         self.load_params(sd["params"])  # resets Adam, then restore it
         m, v = _f32(sd["exp_avg"]).ravel(), _f32(sd["exp_avg_sq"]).ravel()
         self._c(lib().aleppo_import_optimizer(self._ctx, _ptr(m), _ptr(v), C.c_int64(int(sd["step"])),
                                               C.c_size_t(m.size)))
+        if "reward_scale" in sd:
+            self.load_reward_scale_state(sd["reward_scale"])
+
+    # -- return-based reward scaling (OPT_REWARD_SCALE) --
+    def set_reward_scaling(self, on, clip=10.0):
+        """OPT_REWARD_SCALE / OPT_REWARD_SCALE_CLIP: from the next finish_rollout on, divide the rewards by the running
+        standard deviation of the discounted return and clip them at +-clip (finite, > 0; rounded to float32) instead of
+        clamping them to [-1, 1].  Under data parallelism every rank sets the same values."""
+        self.set_option(OPT_REWARD_SCALE_CLIP, float_bits(clip))
+        self.set_option(OPT_REWARD_SCALE, int(bool(on)))
+
+    def reward_scale(self):
+        """ALEPPO_F_REWARD_SCALE: {count, mean, var, scale, batch_count, clipped} (aleppo.h)"""
+        a = self.read_batch("reward_scale")
+        return {name: float(a[i]) for name, i in REWARD_SCALE.items()}
+
+    def reward_scale_state(self):
+        """aleppo_export_reward_scale: {"stats": float64 [3] (count, mean, var), "returns": float64 [E]}"""
+        stats, g = np.zeros(3, np.float64), np.zeros(self.E, np.float64)
+        self._c(lib().aleppo_export_reward_scale(self._ctx, _ptr(stats), _ptr(g), C.c_size_t(g.size)))
+        return dict(stats=stats, returns=g)
+
+    def load_reward_scale_state(self, state):
+        """aleppo_import_reward_scale: what reward_scale_state returned"""
+        stats = np.ascontiguousarray(state["stats"], dtype=np.float64).ravel()
+        g = np.ascontiguousarray(state["returns"], dtype=np.float64).ravel()
+        if stats.size != 3:
+            raise AleppoInvalidArgument("reward scale stats must be (count, mean, var)")
+        self._c(lib().aleppo_import_reward_scale(self._ctx, _ptr(stats), _ptr(g), C.c_size_t(g.size)))
 
     # -- rollout --
     def act(self, noise=None):
@@ -528,7 +591,8 @@ class Engine:
                       values=((E, T), np.float32), advantages=((E, T), np.float32), returns=((E, T), np.float32),
                       log_probs=((E, T, A), np.float32), terminals=((E, T), np.uint8),
                       truncations=((E, T), np.uint8), current_obs=((E, 4, 84, 84), np.uint8),
-                      next_values=((E,), np.float32), batch_stats=((BATCH_STATS_COUNT,), np.float64))
+                      next_values=((E,), np.float32), batch_stats=((BATCH_STATS_COUNT,), np.float64),
+                      reward_scale=((REWARD_SCALE_COUNT,), np.float64))
         shp, dt = shapes[name]
         out = np.zeros(shp, dt)
         self._c(lib().aleppo_read_batch(self._ctx, FIELDS[name], _ptr(out), C.c_size_t(out.nbytes)))

@@ -510,7 +510,7 @@ extern "C" void aleppo_destroy(aleppo_ctx *c) {
                  c->sumsq_part, c->metric_ps, c->metric_red, c->grad_norms, c->adv_stats, c->stage_u8, c->stage_obs,
                  c->adam_sched, c->rb_tmp[0], c->rb_tmp[1], c->order, c->act_p, c->oldlp_p, c->adv_p,
                  c->ret_p,  c->mask_p,   c->mask_counts_ep, c->shuf_keys, c->val_n, c->val_p, c->advn_part,
-                 c->advn_stats, c->kl_ps, c->kl_beta, c->hyper_blk, c->ev_obs, c->ev_a1, c->ev_a2, c->ev_a3, c->ev_hpart,
+                 c->advn_stats, c->kl_ps, c->kl_beta, c->hyper_blk, c->rs_blk, c->ev_obs, c->ev_a1, c->ev_a2, c->ev_a3, c->ev_hpart,
                  c->ev_logits, c->ev_values, c->ev_actions, c->ev_d_frames, c->ev_d_start, c->ev_d_noise, c->ev_d_done};
   for (void *p : dev)
     if (p)
@@ -1094,6 +1094,28 @@ extern "C" int aleppo_set_gray_lut(aleppo_ctx *c, const uint8_t *lut256) {
   return ALEPPO_OK;
 }
 
+// ALEPPO_OPT_REWARD_SCALE: one device allocation, made on first use and kept where it is until aleppo_destroy - the
+// state block, the two running-return arrays (state / scan output), the scan's partials and the all-reduce's sums.
+static const double RS_INITIAL[RS_BLOCK] = {1e-4, 0.0, 1.0, 1.0, 0.0, 0.0, 0.0, 0.0}; // gym's RunningMeanStd; s = 1
+static int ensure_rs_storage(aleppo_ctx *c) {
+  if (c->rs_blk)
+    return ALEPPO_OK;
+  const size_t E = (size_t)c->E, doubles = RS_BLOCK + 2 * E + (size_t)rs_blocks(c->E) * 4 + 4;
+  double *blk = nullptr;
+  HIPCHK(c, dalloc(&blk, doubles * sizeof(double), c->stream)); // (zeroed: G = 0)
+  HIPCHK(c, copy_sync(c, blk, RS_INITIAL, sizeof(RS_INITIAL), hipMemcpyHostToDevice));
+  c->rs_blk = blk;
+  c->rs_g[0] = blk + RS_BLOCK;
+  c->rs_g[1] = c->rs_g[0] + E;
+  c->rs_part = c->rs_g[1] + E;
+  c->rs_cur = 0;
+  return ALEPPO_OK;
+}
+static bool rs_state_valid(const double stats[3]) {
+  return std::isfinite(stats[0]) && std::isfinite(stats[1]) && std::isfinite(stats[2]) && stats[0] > 0.0 &&
+         stats[2] >= 0.0;
+}
+
 extern "C" int aleppo_finish_rollout(aleppo_ctx *c, const float *noise) {
   CHECK_CTX(c);
   c->act_queued_slot = -1;
@@ -1102,6 +1124,14 @@ extern "C" int aleppo_finish_rollout(aleppo_ctx *c, const float *noise) {
   if (int rcg = check_gate(c))
     return rcg;
   const int E = c->E, T = c->T, A = c->A;
+  const bool rs_on = c->reward_scale;
+  const bool rs_dp = rs_on && (c->world > 1 || (c->nccl_comm && c->force_comm));
+  if (rs_on) {
+    if (c->world > 1 && !c->nccl_comm)
+      return set_err(c, ALEPPO_ERR_RUNTIME, "world_size > 1 but aleppo_comm_init was not called");
+    if (int rcs = ensure_rs_storage(c))
+      return rcs;
+  }
   // extra selector call on the post-rollout observation: its values bootstrap slot T-1, its sample is
   // discarded but advances the RNG stream like the reference (rollout.cc:268-270)
   int rc = do_act(c, noise, T, rp(c, c->logits_tm, (size_t)T * E * A), rp(c, c->values_tm, (size_t)T * E),
@@ -1110,10 +1140,26 @@ extern "C" int aleppo_finish_rollout(aleppo_ctx *c, const float *noise) {
     return rc;
   HIPCHK(c, hipMemcpyAsync(c->step_rec, c->h_rec, c->step_rec_bytes * T, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(c->d_err, 0, 4, c->stream));
-  prof_begin(c, ALEPPO_K_GAE);
-  launch_gae(c->stream, c->step_rec, c->step_rec_bytes, c->values_tm, c->logits_tm, c->actions_tm, c->adv_n, c->ret_n,
-             c->oldlp_n, c->act_n, c->mask_n, c->d_err, E, T, A, c->cfg.gamma, c->cfg.lambda, true, c->rt16);
-  prof_end(c, ALEPPO_K_GAE);
+  if (rs_on) { // ALEPPO_OPT_REWARD_SCALE: scan -> moments -> [all-reduce] -> merge and scale -> GAE on the scaled rewards
+    double *const sums = c->rs_part + (size_t)rs_blocks(E) * 4;
+    prof_begin(c, ALEPPO_K_GAE);
+    launch_rs_scan(c->stream, c->step_rec, c->step_rec_bytes, c->rs_g[c->rs_cur], c->rs_g[c->rs_cur ^ 1], c->rs_part,
+                   c->d_err, E, T, c->cfg.gamma);
+    launch_rs_reduce(c->stream, c->rs_part, rs_blocks(E), rs_dp ? sums : nullptr, c->rs_blk, c->d_err);
+    if (rs_dp) {
+      NCCLCHK(c, ncclAllReduce(sums, sums, 3, ncclDouble, ncclSum, static_cast<ncclComm_t>(c->nccl_comm), c->stream));
+      launch_rs_finalise(c->stream, sums, c->rs_blk, c->d_err);
+    }
+    launch_gae_scaled(c->stream, c->step_rec, c->step_rec_bytes, c->values_tm, c->logits_tm, c->actions_tm, c->adv_n,
+                      c->ret_n, c->oldlp_n, c->act_n, c->mask_n, c->d_err, E, T, A, c->cfg.gamma, c->cfg.lambda, c->rs_blk,
+                      c->reward_scale_clip, c->rt16);
+    prof_end(c, ALEPPO_K_GAE);
+  } else {
+    prof_begin(c, ALEPPO_K_GAE);
+    launch_gae(c->stream, c->step_rec, c->step_rec_bytes, c->values_tm, c->logits_tm, c->actions_tm, c->adv_n, c->ret_n,
+               c->oldlp_n, c->act_n, c->mask_n, c->d_err, E, T, A, c->cfg.gamma, c->cfg.lambda, true, c->rt16);
+    prof_end(c, ALEPPO_K_GAE);
+  }
   if (c->cfg.advantage_norm) {
     launch_adv_norm(c->stream, c->adv_n, c->mask_n, c->adv_stats, c->N, 0, c->rt16);
     if ((c->world > 1 || c->force_comm) && c->nccl_comm)
@@ -1131,6 +1177,8 @@ extern "C" int aleppo_finish_rollout(aleppo_ctx *c, const float *noise) {
   c->batch_n = c->N;
   c->caller_batch = false;
   c->val_src = Ctx::VAL_ROLLOUT; // (values_tm; any values supplied for a caller batch are forgotten)
+  if (rs_on && !*c->h_err)
+    c->rs_cur ^= 1; // the scan's output is the running return now (a refused rollout leaves the state as it was)
   if (*c->h_err)
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT,
                    "Episode starts, terminals, and truncations must be mutually exclusive."); // gae.cc:49-53
@@ -1996,9 +2044,60 @@ extern "C" int aleppo_read_batch(aleppo_ctx *c, int field, void *dst, size_t byt
     }
     return fin(result);
   }
+  case ALEPPO_F_REWARD_SCALE: {
+    need = ALEPPO_REWARD_SCALE_COUNT * sizeof(double);
+    if (bytes != need)
+      return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "read_batch: wrong byte count");
+    if (int rc = ensure_rs_storage(c))
+      return rc;
+    double blk[RS_BLOCK];
+    HIPCHK(c, copy_sync(c, blk, c->rs_blk, sizeof(blk), hipMemcpyDeviceToHost));
+    unsigned long long clipped;
+    std::memcpy(&clipped, &blk[RS_CLIPPED], 8);
+    double *o = static_cast<double *>(dst);
+    for (int k = 0; k < 5; ++k)
+      o[k] = blk[k];
+    o[5] = (double)clipped;
+    return ALEPPO_OK;
+  }
   default:
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "read_batch: unknown field");
   }
+}
+
+// ALEPPO_OPT_REWARD_SCALE's part of a checkpoint: the running statistics and the per-environment running returns
+extern "C" int aleppo_export_reward_scale(aleppo_ctx *c, double stats[3], double *returns, size_t num_envs) {
+  CHECK_CTX(c);
+  if (!stats || !returns)
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "export_reward_scale: null argument");
+  if (num_envs != (size_t)c->E)
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "export_reward_scale: num_envs is not the context's");
+  if (int rc = ensure_rs_storage(c))
+    return rc;
+  HIPCHK(c, hipMemcpyAsync(stats, c->rs_blk, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, copy_sync(c, returns, c->rs_g[c->rs_cur], num_envs * sizeof(double), hipMemcpyDeviceToHost));
+  return ALEPPO_OK;
+}
+extern "C" int aleppo_import_reward_scale(aleppo_ctx *c, const double stats[3], const double *returns,
+                                          size_t num_envs) {
+  CHECK_CTX(c);
+  if (!stats || !returns)
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "import_reward_scale: null argument");
+  if (num_envs != (size_t)c->E)
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "import_reward_scale: num_envs is not the context's");
+  if (!rs_state_valid(stats))
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT,
+                   "import_reward_scale: count must be finite and > 0, mean finite, var finite and >= 0");
+  for (size_t e = 0; e < num_envs; ++e)
+    if (!std::isfinite(returns[e]))
+      return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "import_reward_scale: a running return is not finite");
+  if (int rc = ensure_rs_storage(c))
+    return rc;
+  // (the scale, the batch count and the clip counter describe the last scaled rollout: they are not part of the state)
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->rs_blk, stats, 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, copy_sync(c, c->rs_g[c->rs_cur], returns, num_envs * sizeof(double), hipMemcpyHostToDevice));
+  return ALEPPO_OK;
 }
 
 // ------------------------------------------------------------------ evaluation lanes (include/aleppo.h)
@@ -2277,7 +2376,9 @@ extern "C" int aleppo_set_option(aleppo_ctx *c, int option, int value) {
   const bool hyper_opt = option == ALEPPO_OPT_CLIP_PARAM || option == ALEPPO_OPT_VALUE_CLIP_RANGE ||
                          option == ALEPPO_OPT_VALUE_LOSS_COEF || option == ALEPPO_OPT_ENTROPY_COEF ||
                          option == ALEPPO_OPT_MAX_GRAD_NORM;
-  if (option != ALEPPO_OPT_KL_COEF && !hyper_opt) {
+  // (the two reward-scaling options are read by aleppo_finish_rollout alone: the update does not see them)
+  const bool rollout_opt = option == ALEPPO_OPT_REWARD_SCALE || option == ALEPPO_OPT_REWARD_SCALE_CLIP;
+  if (option != ALEPPO_OPT_KL_COEF && !hyper_opt && !rollout_opt) {
     c->graph_key = Ctx::GraphKey();
     c->warm_key = Ctx::GraphKey();
   }
@@ -2313,6 +2414,17 @@ extern "C" int aleppo_set_option(aleppo_ctx *c, int option, int value) {
       return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT,
                      "ALEPPO_OPT_KL_PENALTY: 0 (off) or 1 (exact KL, beta KL added to the loss)");
     c->kl_pen = value != 0;
+  } else if (option == ALEPPO_OPT_REWARD_SCALE) {
+    if (value != 0 && value != 1)
+      return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT,
+                     "ALEPPO_OPT_REWARD_SCALE: 0 (clamp to [-1, 1]) or 1 (divide by the running return's std, clip)");
+    c->reward_scale = value != 0;
+  } else if (option == ALEPPO_OPT_REWARD_SCALE_CLIP) {
+    if (value < 1 || value >= 0x7F800000) // the bits of a finite float > 0: see ALEPPO_OPT_KL_COEF below
+      return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT,
+                     "ALEPPO_OPT_REWARD_SCALE_CLIP: the binary32 bits of a finite float > 0 (not zero, Inf or NaN)");
+    const uint32_t bits = (uint32_t)value;
+    std::memcpy(&c->reward_scale_clip, &bits, 4);
   } else if (option == ALEPPO_OPT_KL_COEF) {
     // the bit pattern of a finite non-negative float: [0, 0x7F800000) (-0.0 and every negative float or NaN have the
     // sign bit set and are negative as an int; +Inf is 0x7F800000 and the positive NaNs lie above it)
@@ -2379,6 +2491,8 @@ extern "C" int aleppo_get_option(aleppo_ctx *c, int option, int64_t *value) {
   case ALEPPO_OPT_ENTROPY_COEF: *value = (int64_t)float_bits(c->hyper.c_e); break;
   case ALEPPO_OPT_MAX_GRAD_NORM: *value = (int64_t)float_bits(c->hyper.max_norm); break;
   case ALEPPO_OPT_GATE_TIMEOUT_MS: *value = (int64_t)(c->gate_timeout_ticks / 100000ull); break;
+  case ALEPPO_OPT_REWARD_SCALE: *value = c->reward_scale; break;
+  case ALEPPO_OPT_REWARD_SCALE_CLIP: *value = (int64_t)float_bits(c->reward_scale_clip); break;
   default: return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "unknown option");
   }
   return ALEPPO_OK;
@@ -2536,6 +2650,87 @@ extern "C" int aleppo_gae(int dev, float *advantages, const float *rewards, cons
     return set_err(nullptr, ALEPPO_ERR_INVALID_ARGUMENT,
                    "Episode starts, terminals, and truncations must be mutually exclusive."); // gae.cc:49-53
   OPCHK(op.down(advantages, a.p, n * 4));
+  return ALEPPO_OK;
+}
+
+// ALEPPO_OPT_REWARD_SCALE through the production kernels: the host arrays are laid out as the rollout's step records, then
+// rs_scan_kernel, rs_reduce_kernel and gae_scaled_kernel run as aleppo_finish_rollout runs them (the GAE on a zero value
+// plane, its advantages discarded: what is wanted of it is step 5, the scaled rewards in place and the clip count).
+extern "C" int aleppo_reward_scale(int dev, float *rewards, const uint8_t *terminals, const uint8_t *truncations,
+                                   const uint8_t *episode_starts, int64_t E, int64_t T, float gamma, float clip,
+                                   double stats[3], double *returns, float *scale_out, int64_t *clipped_out) {
+  if (!rewards || !terminals || !truncations || !episode_starts || !stats || !returns)
+    return set_err(nullptr, ALEPPO_ERR_INVALID_ARGUMENT, "All input tensors must be 2D except returns which must be 1D.");
+  if (E <= 0 || T <= 0 || E > INT32_MAX || T > INT32_MAX)
+    return set_err(nullptr, ALEPPO_ERR_INVALID_ARGUMENT, "Input tensors must have compatible dimensions.");
+  if (!(clip > 0.f) || !std::isfinite(clip) || !std::isfinite(gamma))
+    return set_err(nullptr, ALEPPO_ERR_INVALID_ARGUMENT, "reward_scale: clip must be finite and > 0, gamma finite");
+  if (!rs_state_valid(stats))
+    return set_err(nullptr, ALEPPO_ERR_INVALID_ARGUMENT,
+                   "reward_scale: count must be finite and > 0, mean finite, var finite and >= 0");
+  for (int64_t e = 0; e < E; ++e)
+    if (!std::isfinite(returns[e]))
+      return set_err(nullptr, ALEPPO_ERR_INVALID_ARGUMENT, "reward_scale: a running return is not finite");
+  int rc = select_device(dev);
+  if (rc)
+    return rc;
+  OpScope op(dev);
+  OPCHK(op.err);
+  const size_t n = (size_t)E * T, rb = ((size_t)7 * E + 15) / 16 * 16;
+  std::vector<uint8_t> rec(rb * T, 0);
+  for (int64_t t = 0; t < T; ++t) {
+    uint8_t *r = rec.data() + (size_t)t * rb;
+    for (int64_t e = 0; e < E; ++e) {
+      reinterpret_cast<float *>(r)[e] = rewards[e * T + t];
+      r[4 * E + e] = terminals[e * T + t];
+      r[5 * E + e] = truncations[e * T + t];
+      r[6 * E + e] = episode_starts[e * T + t];
+    }
+  }
+  double blk[RS_BLOCK];
+  std::memcpy(blk, RS_INITIAL, sizeof(blk));
+  blk[RS_COUNT] = stats[0];
+  blk[RS_MEAN] = stats[1];
+  blk[RS_VAR] = stats[2];
+  const int nblk = rs_blocks((int)E);
+  DevBuf drec, dblk, gin, gout, part, dv, a, r, m, er;
+  OPCHK(drec.up(rec.data(), rec.size()));
+  OPCHK(dblk.up(blk, sizeof(blk)));
+  OPCHK(gin.up(returns, (size_t)E * 8));
+  OPCHK(gout.up(nullptr, (size_t)E * 8));
+  OPCHK(part.up(nullptr, (size_t)nblk * 4 * 8));
+  OPCHK(dv.up(nullptr, (size_t)(T + 1) * E * 4));
+  OPCHK(a.up(nullptr, n * 4));
+  OPCHK(r.up(nullptr, n * 4));
+  OPCHK(m.up(nullptr, n));
+  OPCHK(er.up(nullptr, 16));
+  launch_rs_scan(op.st, drec.as<uint8_t>(), rb, gin.as<double>(), gout.as<double>(), part.as<double>(), er.as<int>(),
+                 (int)E, (int)T, gamma);
+  launch_rs_reduce(op.st, part.as<double>(), nblk, nullptr, dblk.as<double>(), er.as<int>());
+  launch_gae_scaled(op.st, drec.as<uint8_t>(), rb, dv.as<float>(), nullptr, nullptr, a.as<float>(), r.as<float>(),
+                    nullptr, nullptr, m.as<uint8_t>(), er.as<int>(), (int)E, (int)T, 0, gamma, 0.f, dblk.as<double>(),
+                    clip, false);
+  int err = 0;
+  OPCHK(op.down(&err, er.p, 4));
+  if (err)
+    return set_err(nullptr, ALEPPO_ERR_INVALID_ARGUMENT,
+                   "Episode starts, terminals, and truncations must be mutually exclusive."); // gae.cc:49-53
+  OPCHK(op.down(rec.data(), drec.p, rec.size()));
+  OPCHK(op.down(blk, dblk.p, sizeof(blk)));
+  OPCHK(op.down(returns, gout.p, (size_t)E * 8));
+  for (int64_t t = 0; t < T; ++t)
+    for (int64_t e = 0; e < E; ++e)
+      rewards[e * T + t] = reinterpret_cast<const float *>(rec.data() + (size_t)t * rb)[e];
+  stats[0] = blk[RS_COUNT];
+  stats[1] = blk[RS_MEAN];
+  stats[2] = blk[RS_VAR];
+  if (scale_out)
+    *scale_out = (float)blk[RS_SCALE];
+  if (clipped_out) {
+    unsigned long long cl;
+    std::memcpy(&cl, &blk[RS_CLIPPED], 8);
+    *clipped_out = (int64_t)cl;
+  }
   return ALEPPO_OK;
 }
 

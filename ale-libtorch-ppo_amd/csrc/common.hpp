@@ -212,6 +212,13 @@ struct Ctx {
   float last_max_norm = 0.f;                     // hyper.max_norm of the last aleppo_train (aleppo_export_grads)
   bool hyper_dev = false;                        // one of the five was set: the *_dev_kernel entry points from now on
   float *hyper_blk = nullptr, *h_hyper_blk = nullptr; // [HYPER_BLOCK], uploaded at each aleppo_train (device / pinned)
+  // ---- ALEPPO_OPT_REWARD_SCALE / _CLIP: device storage allocated on first use (ensure_rs_storage), never moved
+  bool reward_scale = false;
+  float reward_scale_clip = 10.0f;
+  double *rs_blk = nullptr;   // [RS_BLOCK] the state block
+  double *rs_g[2] = {nullptr, nullptr}; // [E] running returns: rs_g[rs_cur] is the state, the other the scan's output
+  int rs_cur = 0;             // (flipped once a rollout is accepted: a refused one leaves the state as it was)
+  double *rs_part = nullptr;  // [rs_blocks(E)][4] partials, then [4] the sums for the all-reduce
   // ---- captured update (ALEPPO_OPT_UPDATE_GRAPH): the epochs x minibatches loop as one hipGraph, re-captured when
   // the shape (or a baked pointer) changes; the first call of a shape runs eagerly (one-time kernel attribute set-up)
   bool update_graph = false;
@@ -303,6 +310,23 @@ void launch_eval_head(hipStream_t s, const float *hpart, const float *bfc, const
 void launch_gae(hipStream_t s, uint8_t *step_rec, size_t rec_bytes, const void *values_tm, const void *logits_tm,
                 const int *actions_tm, void *adv_n, void *ret_n, void *oldlp_n, int *act_n, uint8_t *mask_n, int *err,
                 int E, int T, int A, float gamma, float lambda, bool clamp = true, bool rt16 = false);
+
+// ALEPPO_OPT_REWARD_SCALE.  The state block is double [RS_BLOCK] in device memory: the running (count, mean, var), the
+// scale s (a float, widened), the sample count of the last scaled rollout, and the clip counter as a 64-bit integer.
+enum { RS_COUNT = 0, RS_MEAN = 1, RS_VAR = 2, RS_SCALE = 3, RS_BATCH_COUNT = 4, RS_CLIPPED = 5, RS_BLOCK = 8 };
+// stage 1: the forward scan over the step records; g_in / g_out: the running returns [E] before / after, part:
+// [rs_blocks(E)][4] = (n, S, Q, 0) per workgroup, err: set when flags overlap (like gae_kernel).  Stage 2 adds the partials
+// in index order and merges them into the block rs (sums_out == nullptr), or writes the three sums for an all-reduce
+// that launch_rs_finalise merges afterwards.
+int rs_blocks(int E);
+void launch_rs_scan(hipStream_t s, const uint8_t *step_rec, size_t rec_bytes, const double *g_in, double *g_out,
+                    double *part, int *err, int E, int T, float gamma);
+void launch_rs_reduce(hipStream_t s, const double *part, int nblk, double *sums_out, double *rs, const int *err);
+void launch_rs_finalise(hipStream_t s, const double *sums, double *rs, const int *err);
+// launch_gae with step 5 of ALEPPO_OPT_REWARD_SCALE in place of the clamp: s from rs[RS_SCALE], the clip as an argument
+void launch_gae_scaled(hipStream_t s, uint8_t *step_rec, size_t rec_bytes, const void *values_tm, const void *logits_tm,
+                       const int *actions_tm, void *adv_n, void *ret_n, void *oldlp_n, int *act_n, uint8_t *mask_n,
+                       int *err, int E, int T, int A, float gamma, float lambda, double *rs, float clip, bool rt16);
 
 void launch_adv_norm(hipStream_t s, void *adv_n, const uint8_t *mask_n, float *stats, long n, int phase, bool rt16);
 void launch_plane_to_float(hipStream_t s, const void *src, float *dst, long n, bool rt16);

@@ -501,10 +501,14 @@ struct GaeChunk {
   float r[CH], v[CH];
   uint8_t te[CH], tr[CH], st[CH];
 };
-template <class RT>
-__global__ __launch_bounds__(64) void gae_kernel(uint8_t *rec, size_t rb, const RT *__restrict__ values_tm, RT *adv_n,
-                                                  RT *ret_n, uint8_t *mask_n, int *err, int E, int T, float gamma,
-                                                  float lambda, int clamp) {
+// The scan is ONE text with two entry points: gae_kernel (SCALED = false: the reference's clamp, or none) and
+// gae_scaled_kernel (SCALED = true, ALEPPO_OPT_REWARD_SCALE: step 5 of aleppo.h in place of the clamp - every reward
+// becomes min(max(r * s, -c), c) in fp32, s from the reward-scale state block, and the rewards the clip changed are
+// counted).  Everything SCALED adds is behind `if constexpr`, so gae_kernel's instruction stream is what it was.
+template <class RT, bool SCALED>
+__device__ __forceinline__ void gae_scan(uint8_t *rec, size_t rb, const RT *__restrict__ values_tm, RT *adv_n, RT *ret_n,
+                                         uint8_t *mask_n, int *err, int E, int T, float gamma, float lambda, int clamp,
+                                         float rs_s, float rs_c, unsigned long long *rs_clipped) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= E)
     return;
@@ -512,12 +516,21 @@ __global__ __launch_bounds__(64) void gae_kernel(uint8_t *rec, size_t rb, const 
   const float gl = gamma * lambda;
   float last = 0.f, nv = (float)values_tm[(size_t)T * E + e];
   int bad = 0;
+  [[maybe_unused]] unsigned int nclip = 0;
   auto step = [&](int t, float r, float v, bool bte, bool btr, bool bst) {
-    // buffer.cc:67 clamp_, in place (Buffer::get).  clamp == 0: ai::gae::gae alone (the stateless aleppo_gae
-    // operator) - rewards are used as given and left untouched.
-    const float rc = clamp ? fminf(fmaxf(r, -1.0f), 1.0f) : r;
-    if (clamp)
+    float rc;
+    if constexpr (SCALED) {
+      const float p = r * rs_s;
+      rc = fminf(fmaxf(p, -rs_c), rs_c);
+      nclip += fabsf(p) > rs_c ? 1u : 0u;
       reinterpret_cast<float *>(rec + (size_t)t * rb)[e] = rc;
+    } else {
+      // buffer.cc:67 clamp_, in place (Buffer::get).  clamp == 0: ai::gae::gae alone (the stateless aleppo_gae
+      // operator) - rewards are used as given and left untouched.
+      rc = clamp ? fminf(fmaxf(r, -1.0f), 1.0f) : r;
+      if (clamp)
+        reinterpret_cast<float *>(rec + (size_t)t * rb)[e] = rc;
+    }
     bad |= ((int)bte + (int)btr + (int)bst > 1) ? 1 : 0; // gae.cc:49-53
     const float a = gae_step(rc, v, nv, last, gamma, gl, bst, bte, btr);
     const size_t n = (size_t)e * T + t;
@@ -572,6 +585,24 @@ __global__ __launch_bounds__(64) void gae_kernel(uint8_t *rec, size_t rb, const 
   }
   if (bad)
     *err = 1;
+  if constexpr (SCALED) {
+    if (nclip) // an integer vector atomic: the total does not depend on the order of arrival
+      atomicAdd(rs_clipped, (unsigned long long)nclip);
+  }
+}
+template <class RT>
+__global__ __launch_bounds__(64) void gae_kernel(uint8_t *rec, size_t rb, const RT *__restrict__ values_tm, RT *adv_n,
+                                                  RT *ret_n, uint8_t *mask_n, int *err, int E, int T, float gamma,
+                                                  float lambda, int clamp) {
+  gae_scan<RT, false>(rec, rb, values_tm, adv_n, ret_n, mask_n, err, E, T, gamma, lambda, clamp, 0.f, 0.f, nullptr);
+}
+// rs: the reward-scale state block (RS_SCALE: the float s, widened; RS_CLIPPED: the counter, zeroed by the second stage)
+template <class RT>
+__global__ __launch_bounds__(64) void gae_scaled_kernel(uint8_t *rec, size_t rb, const RT *__restrict__ values_tm,
+                                                         RT *adv_n, RT *ret_n, uint8_t *mask_n, int *err, int E, int T,
+                                                         float gamma, float lambda, double *rs, float clip) {
+  gae_scan<RT, true>(rec, rb, values_tm, adv_n, ret_n, mask_n, err, E, T, gamma, lambda, 1, (float)rs[RS_SCALE], clip,
+                     reinterpret_cast<unsigned long long *>(rs + RS_CLIPPED));
 }
 // the embarrassingly parallel part of prepare_batch (train.cc:272-283): old log-probs + actions, one thread
 // per (t, e) slot, written env-major
@@ -598,23 +629,39 @@ __global__ void oldlp_kernel(const RT *__restrict__ logits_tm, const int *__rest
 template <class RT>
 static void launch_gae_t(hipStream_t s, uint8_t *step_rec, size_t rec_bytes, const void *values_tm, const void *logits_tm,
                          const int *actions_tm, void *adv_n, void *ret_n, void *oldlp_n, int *act_n, uint8_t *mask_n,
-                         int *err, int E, int T, int A, float gamma, float lambda, bool clamp) {
+                         int *err, int E, int T, int A, float gamma, float lambda, bool clamp, double *rs,
+                         float rs_clip) {
   if (logits_tm) // (the stateless aleppo_gae operator has no logits / actions)
     hipLaunchKernelGGL(oldlp_kernel<RT>, dim3((unsigned)(((long)E * T + 255) / 256)), dim3(256), 0, s,
                        static_cast<const RT *>(logits_tm), actions_tm, static_cast<RT *>(oldlp_n), act_n, E, T, A);
-  hipLaunchKernelGGL(gae_kernel<RT>, dim3((E + 63) / 64), dim3(64), 0, s, step_rec, rec_bytes,
-                     static_cast<const RT *>(values_tm), static_cast<RT *>(adv_n), static_cast<RT *>(ret_n), mask_n, err,
-                     E, T, gamma, lambda, clamp ? 1 : 0);
+  if (rs)
+    hipLaunchKernelGGL(gae_scaled_kernel<RT>, dim3((E + 63) / 64), dim3(64), 0, s, step_rec, rec_bytes,
+                       static_cast<const RT *>(values_tm), static_cast<RT *>(adv_n), static_cast<RT *>(ret_n), mask_n,
+                       err, E, T, gamma, lambda, rs, rs_clip);
+  else
+    hipLaunchKernelGGL(gae_kernel<RT>, dim3((E + 63) / 64), dim3(64), 0, s, step_rec, rec_bytes,
+                       static_cast<const RT *>(values_tm), static_cast<RT *>(adv_n), static_cast<RT *>(ret_n), mask_n,
+                       err, E, T, gamma, lambda, clamp ? 1 : 0);
 }
 void launch_gae(hipStream_t s, uint8_t *step_rec, size_t rec_bytes, const void *values_tm, const void *logits_tm,
                 const int *actions_tm, void *adv_n, void *ret_n, void *oldlp_n, int *act_n, uint8_t *mask_n, int *err,
                 int E, int T, int A, float gamma, float lambda, bool clamp, bool rt16) {
   if (rt16)
     launch_gae_t<f16>(s, step_rec, rec_bytes, values_tm, logits_tm, actions_tm, adv_n, ret_n, oldlp_n, act_n, mask_n, err,
-                      E, T, A, gamma, lambda, clamp);
+                      E, T, A, gamma, lambda, clamp, nullptr, 0.f);
   else
     launch_gae_t<float>(s, step_rec, rec_bytes, values_tm, logits_tm, actions_tm, adv_n, ret_n, oldlp_n, act_n, mask_n,
-                        err, E, T, A, gamma, lambda, clamp);
+                        err, E, T, A, gamma, lambda, clamp, nullptr, 0.f);
+}
+void launch_gae_scaled(hipStream_t s, uint8_t *step_rec, size_t rec_bytes, const void *values_tm, const void *logits_tm,
+                       const int *actions_tm, void *adv_n, void *ret_n, void *oldlp_n, int *act_n, uint8_t *mask_n,
+                       int *err, int E, int T, int A, float gamma, float lambda, double *rs, float clip, bool rt16) {
+  if (rt16)
+    launch_gae_t<f16>(s, step_rec, rec_bytes, values_tm, logits_tm, actions_tm, adv_n, ret_n, oldlp_n, act_n, mask_n, err,
+                      E, T, A, gamma, lambda, true, rs, clip);
+  else
+    launch_gae_t<float>(s, step_rec, rec_bytes, values_tm, logits_tm, actions_tm, adv_n, ret_n, oldlp_n, act_n, mask_n,
+                        err, E, T, A, gamma, lambda, true, rs, clip);
 }
 
 // optional advantage normalisation over unmasked samples (NOT in the reference, Q2; off by default).
@@ -867,6 +914,162 @@ void launch_bstat_reduce(hipStream_t s, const double *part, int nblk, double *su
 }
 void launch_bstat_finalise(hipStream_t s, const double *sums, double *result) {
   hipLaunchKernelGGL(bstat_finalise_kernel, dim3(1), dim3(64), 0, s, sums, result);
+}
+
+// ================================================================================================
+// ALEPPO_OPT_REWARD_SCALE (aleppo.h): the running discounted return per environment, the count, sum and sum of squares of
+// its samples over one rollout, and the merge into the running mean / variance that gives the scale s - all in double.
+// Stage 1, rs_scan_kernel: one thread = one environment, scanning t = 0 .. T-1 over the time-major step records (a wave
+// reads 64 consecutive environments per slot), with gae_kernel's loading discipline: the rewards and flags of 16 slots
+// are loaded together, the next 16 are already in flight, and a chunk is processed branch-free (selects, no per-step
+// branches: see the comment above GaeChunk for what the naive form costs).  G * gamma + r keeps its two roundings
+// (contraction off), so the samples are the bits a host restatement in double gets.  The wave then folds (n, S, Q) with
+// xor butterflies (the wave stage of block_sum_256d) and writes one partial per workgroup.  The order of every addition
+// is a function of (E, T) only.
+// ================================================================================================
+struct RsChunk {
+  static constexpr int CH = 16;
+  float r[CH];
+  uint8_t te[CH], tr[CH], st[CH];
+};
+__device__ __forceinline__ void rs_step(double &G, double &n, double &S, double &Q, int &bad, double g, float r, bool te,
+                                        bool tr, bool st) {
+#pragma clang fp contract(off)
+  bad |= ((int)te + (int)tr + (int)st > 1) ? 1 : 0; // gae.cc:49-53, as gae_kernel checks it
+  const double x = G * g + (double)r;
+  const bool live = !st; // an episode-start slot carries the stale reward: no sample, G untouched
+  G = live ? x : G;
+  n += live ? 1.0 : 0.0;
+  S += live ? x : 0.0;
+  Q += live ? x * x : 0.0;
+  G = (live && (te || tr)) ? 0.0 : G;
+}
+__global__ __launch_bounds__(64) void rs_scan_kernel(const uint8_t *__restrict__ rec, size_t rb,
+                                                     const double *__restrict__ g_in, double *__restrict__ g_out,
+                                                     double *__restrict__ part, int *err, int E, int T, float gamma) {
+  constexpr int CH = RsChunk::CH;
+  const int e = blockIdx.x * 64 + threadIdx.x;
+  double G = 0.0, n = 0.0, S = 0.0, Q = 0.0;
+  if (e < E) {
+    const double g = (double)gamma;
+    int bad = 0;
+    G = g_in[e];
+    auto load = [&](RsChunk &c, int t0) { // slots t0 .. t0+CH-1, all valid
+#pragma unroll
+      for (int k = 0; k < CH; ++k) {
+        const uint8_t *row = rec + (size_t)(t0 + k) * rb;
+        const uint8_t *fl = row + 4 * (size_t)E;
+        c.r[k] = reinterpret_cast<const float *>(row)[e];
+        c.te[k] = fl[e];
+        c.tr[k] = fl[E + e];
+        c.st[k] = fl[2 * E + e];
+      }
+    };
+    auto process = [&](const RsChunk &c) {
+#pragma unroll
+      for (int k = 0; k < CH; ++k)
+        rs_step(G, n, S, Q, bad, g, c.r[k], c.te[k] != 0, c.tr[k] != 0, c.st[k] != 0);
+    };
+    int t0 = 0;
+    for (const int rem = T % CH; t0 < rem; ++t0) { // the ragged start of the horizon, one slot at a time
+      const uint8_t *row = rec + (size_t)t0 * rb;
+      const uint8_t *fl = row + 4 * (size_t)E;
+      rs_step(G, n, S, Q, bad, g, reinterpret_cast<const float *>(row)[e], fl[e] != 0, fl[E + e] != 0,
+              fl[2 * E + e] != 0);
+    }
+    if (t0 < T) { // T - t0 is a multiple of CH (uniform control flow: T is a kernel argument)
+      RsChunk ca, cb;
+      load(ca, t0);
+      while (true) {
+        const bool more_b = t0 + CH < T;
+        if (more_b)
+          load(cb, t0 + CH);
+        process(ca);
+        if (!more_b)
+          break;
+        const bool more_a = t0 + 2 * CH < T;
+        if (more_a)
+          load(ca, t0 + 2 * CH);
+        process(cb);
+        if (!more_a)
+          break;
+        t0 += 2 * CH;
+      }
+    }
+    g_out[e] = G;
+    if (bad)
+      *err = 1;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { // lanes past E hold zeros
+    n += __shfl_xor(n, o, 64);
+    S += __shfl_xor(S, o, 64);
+    Q += __shfl_xor(Q, o, 64);
+  }
+  if (threadIdx.x == 0) {
+    double *p = part + (size_t)blockIdx.x * 4;
+    p[0] = n;
+    p[1] = S;
+    p[2] = Q;
+    p[3] = 0.0;
+  }
+}
+// gym's / SB3's RunningMeanStd.update_from_moments on the state block, then the scale; without contraction so that the
+// direct and the all-reduced path round alike (a 1-rank communicator gives the single-GPU bits).  n == 0: the statistics
+// stay.  A rollout whose flags overlap (*err set by the scan; aleppo_finish_rollout refuses it) changes nothing.
+__device__ __forceinline__ void rs_merge(double *rs, double n, double S, double Q, const int *err) {
+#pragma clang fp contract(off)
+  if (*err)
+    return;
+  double count = rs[RS_COUNT], mean = rs[RS_MEAN], var = rs[RS_VAR];
+  if (n > 0.0) {
+    const double mean_b = S / n;
+    const double var_b = fmax(0.0, Q / n - mean_b * mean_b);
+    const double d = mean_b - mean, tot = count + n;
+    mean = mean + d * n / tot;
+    var = (var * count + var_b * n + d * d * count * n / tot) / tot;
+    count = tot;
+  }
+  const float s = (float)(1.0 / sqrt(var + 1e-8));
+  rs[RS_COUNT] = count;
+  rs[RS_MEAN] = mean;
+  rs[RS_VAR] = var;
+  rs[RS_SCALE] = (double)s;
+  rs[RS_BATCH_COUNT] = n;
+  reinterpret_cast<unsigned long long *>(rs)[RS_CLIPPED] = 0ull; // gae_scaled_kernel counts from here
+}
+// Stage 2, one workgroup: thread k < 3 adds sum k of the partials in index order; then either the merge, or (sums_out:
+// data parallel) the three sums for the all-reduce, merged by rs_finalise_kernel afterwards.
+__global__ __launch_bounds__(64) void rs_reduce_kernel(const double *__restrict__ part, int nblk, double *sums_out,
+                                                       double *rs, const int *err) {
+  __shared__ double sums[3];
+  if (threadIdx.x < 3) {
+    double acc = 0.0;
+    for (int b = 0; b < nblk; ++b)
+      acc += part[(size_t)b * 4 + threadIdx.x];
+    sums[threadIdx.x] = acc;
+    if (sums_out)
+      sums_out[threadIdx.x] = acc;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && !sums_out)
+    rs_merge(rs, sums[0], sums[1], sums[2], err);
+}
+__global__ __launch_bounds__(64) void rs_finalise_kernel(const double *sums, double *rs, const int *err) {
+  if (threadIdx.x == 0 && blockIdx.x == 0)
+    rs_merge(rs, sums[0], sums[1], sums[2], err);
+}
+int rs_blocks(int E) { return (E + 63) / 64; }
+void launch_rs_scan(hipStream_t s, const uint8_t *step_rec, size_t rec_bytes, const double *g_in, double *g_out,
+                    double *part, int *err, int E, int T, float gamma) {
+  hipLaunchKernelGGL(rs_scan_kernel, dim3(rs_blocks(E)), dim3(64), 0, s, step_rec, rec_bytes, g_in, g_out, part, err, E,
+                     T, gamma);
+}
+void launch_rs_reduce(hipStream_t s, const double *part, int nblk, double *sums_out, double *rs, const int *err) {
+  hipLaunchKernelGGL(rs_reduce_kernel, dim3(1), dim3(64), 0, s, part, nblk, sums_out, rs, err);
+}
+void launch_rs_finalise(hipStream_t s, const double *sums, double *rs, const int *err) {
+  hipLaunchKernelGGL(rs_finalise_kernel, dim3(1), dim3(64), 0, s, sums, rs, err);
 }
 
 // ================================================================================================

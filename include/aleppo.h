@@ -101,7 +101,7 @@ typedef struct {
 typedef enum {
   ALEPPO_F_OBSERVATIONS = 0, /* uint8  [E,T,4,84,84] */
   ALEPPO_F_ACTIONS = 1,      /* int64  [E,T] */
-  ALEPPO_F_REWARDS = 2,      /* float  [E,T] (clamped after finish_rollout) */
+  ALEPPO_F_REWARDS = 2,      /* float  [E,T] (clamped after finish_rollout; scaled and clipped with ALEPPO_OPT_REWARD_SCALE) */
   ALEPPO_F_MASKS = 3,        /* uint8  [E,T] = !episode_starts */
   ALEPPO_F_LOGITS = 4,       /* float  [E,T,A] */
   ALEPPO_F_VALUES = 5,       /* float  [E,T] */
@@ -112,8 +112,24 @@ typedef enum {
   ALEPPO_F_TRUNCATIONS = 10, /* uint8  [E,T] */
   ALEPPO_F_CURRENT_OBS = 11, /* uint8  [E,4,84,84]: Rollout::observations_ right now */
   ALEPPO_F_NEXT_VALUES = 12, /* float  [E]: bootstrap values of the last finish_rollout */
-  ALEPPO_F_BATCH_STATS = 13  /* double [ALEPPO_BATCH_STATS_COUNT]: explained variance and batch statistics, see below */
+  ALEPPO_F_BATCH_STATS = 13, /* double [ALEPPO_BATCH_STATS_COUNT]: explained variance and batch statistics, see below */
+  ALEPPO_F_REWARD_SCALE = 14 /* double [ALEPPO_REWARD_SCALE_COUNT]: the state of ALEPPO_OPT_REWARD_SCALE, see below */
 } aleppo_field;
+
+/* ALEPPO_F_REWARD_SCALE: the running statistics of ALEPPO_OPT_REWARD_SCALE and what the last scaled rollout did, six
+ * doubles indexed by aleppo_reward_scale_stat.  Readable at any time after aleppo_create (whether the option is on or
+ * not, with or without a batch): before any scaled rollout it is the initial state (1e-4, 0, 1, 1, 0, 0).  Errors as for
+ * the other fields: a wrong byte count is ALEPPO_ERR_INVALID_ARGUMENT, a read while a step is armed ALEPPO_ERR_RUNTIME.
+ * Never a collective: the all-reduce happens inside aleppo_finish_rollout. */
+#define ALEPPO_REWARD_SCALE_COUNT 6
+typedef enum {
+  ALEPPO_RS_COUNT = 0,       /* count of the running statistics (1e-4 + every sample merged so far) */
+  ALEPPO_RS_MEAN = 1,        /* running mean of the discounted return */
+  ALEPPO_RS_VAR = 2,         /* running (population) variance of the discounted return */
+  ALEPPO_RS_SCALE = 3,       /* the float s the last scaled rollout's rewards were multiplied with, widened; 1 before any */
+  ALEPPO_RS_BATCH_COUNT = 4, /* n of the last scaled rollout (global under data parallelism) */
+  ALEPPO_RS_CLIPPED = 5      /* how many of THIS RANK's E*T rewards the clip changed (|r * s| > c) in that rollout */
+} aleppo_reward_scale_stat;
 
 /* ALEPPO_F_BATCH_STATS: the critic diagnostics CleanRL / Stable-Baselines3 log on every update (the reference has none),
  * reduced on the device where the planes are.  aleppo_read_batch(ctx, ALEPPO_F_BATCH_STATS, dst, ALEPPO_BATCH_STATS_COUNT
@@ -213,6 +229,15 @@ int aleppo_export_grads(aleppo_ctx *ctx, float *flat, size_t count);
 int aleppo_export_optimizer(aleppo_ctx *ctx, float *exp_avg, float *exp_avg_sq, int64_t *step, size_t count);
 int aleppo_import_optimizer(aleppo_ctx *ctx, const float *exp_avg, const float *exp_avg_sq, int64_t step,
                             size_t count);
+/* The state of ALEPPO_OPT_REWARD_SCALE: stats = (count, mean, var) of the running statistics, returns = the running
+ * discounted return G[e] of this rank's environments, double [num_envs].  With the two pairs above this is the whole
+ * learner state again: a fresh context that imports all three continues bit for bit.  The scale, batch count and clip
+ * counter of ALEPPO_F_REWARD_SCALE describe the last scaled rollout and are not part of it (an import leaves them).
+ * ALEPPO_ERR_INVALID_ARGUMENT: num_envs != config.num_envs, a null pointer, and for the import a non-finite entry,
+ * count <= 0 or var < 0 (nothing is changed then).  Both work whether the option is on or not, synchronise the
+ * context's own stream only, and are ALEPPO_ERR_RUNTIME while a step is armed. */
+int aleppo_export_reward_scale(aleppo_ctx *ctx, double stats[3], double *returns, size_t num_envs);
+int aleppo_import_reward_scale(aleppo_ctx *ctx, const double stats[3], const double *returns, size_t num_envs);
 
 /* ------------------------------------------------------------------ rollout (Rollout::rollout, rollout.cc:198-278)
  * Per slot t = 0..T-1 the caller does  act -> (step its emulators) -> push_frames -> record_step,
@@ -413,6 +438,15 @@ int aleppo_comm_init(aleppo_ctx *ctx, const uint8_t id[ALEPPO_UNIQUE_ID_BYTES]);
 int aleppo_gae(int device_ordinal, float *advantages, const float *rewards, const float *values,
                const float *next_values, const uint8_t *terminals, const uint8_t *truncations,
                const uint8_t *episode_starts, int64_t num_envs, int64_t num_steps, float gamma, float lambda);
+/* ALEPPO_OPT_REWARD_SCALE on host tensors (no reference counterpart): steps 1-5 of the option on one rollout, through
+ * the kernels aleppo_finish_rollout launches (rs_scan_kernel, rs_reduce_kernel, gae_scaled_kernel).  rewards: float [E,T]
+ * env-major, raw in, scaled and clipped out; the flags uint8 [E,T]; stats_inout = (count, mean, var) and returns_inout =
+ * G, double [E], before / after; *scale_out = s and *clipped_out = the clip count (either may be NULL).  Validation as
+ * aleppo_gae (null tensors, E or T <= 0, overlapping flags: ALEPPO_ERR_INVALID_ARGUMENT), plus clip finite and > 0 and a
+ * state aleppo_import_reward_scale would accept.  Nothing is written back when the call fails. */
+int aleppo_reward_scale(int device_ordinal, float *rewards, const uint8_t *terminals, const uint8_t *truncations,
+                        const uint8_t *episode_starts, int64_t num_envs, int64_t num_steps, float gamma, float clip,
+                        double stats_inout[3], double *returns_inout, float *scale_out, int64_t *clipped_out);
 /* ai::vision::resize_frame_stacked_grayscale_images (vision.cc:22-32): float [n,210,160] -> [n,84,84] */
 int aleppo_vision_resize_area(int device_ordinal, const float *images, float *out, int64_t n);
 /* ai::vision::rgb_to_grayscale_frame_stacked_images (vision.cc:71-84): float [n,3,84,84] -> [n,84,84] */
@@ -438,7 +472,7 @@ int aleppo_sample(int device_ordinal, const float *probs, const float *q, int64_
  * with HIP events on the stream the kernels run on; *launches gets the number of timed launches. */
 typedef enum {
   ALEPPO_K_INGEST = 0,      /* preprocess + frame stack + rollout-slot write */
-  ALEPPO_K_GAE = 1,         /* reward clamp + GAE + returns + old log-probs */
+  ALEPPO_K_GAE = 1,         /* reward clamp (or ALEPPO_OPT_REWARD_SCALE's scan and merge) + GAE + returns + old log-probs */
   ALEPPO_K_HEAD = 2,        /* heads + PPO loss forward/backward */
   ALEPPO_K_ADAM = 3,        /* sum of squares + clip + Adam + dgrad weight repack */
   ALEPPO_K_CONV1_FWD = 4,
@@ -587,10 +621,54 @@ typedef enum {
                                       Valid: finite and > 0 */
   ALEPPO_OPT_VALUE_LOSS_COEF = 19, /* replaces config.value_loss_coef.  Valid: finite and >= 0 (+0.0: no value gradient) */
   ALEPPO_OPT_ENTROPY_COEF = 20,    /* replaces config.entropy_coef.  Valid: finite and >= 0 */
-  ALEPPO_OPT_MAX_GRAD_NORM = 21    /* replaces config.max_gradient_norm, the limit of the global-norm clip in front of
+  ALEPPO_OPT_MAX_GRAD_NORM = 21,   /* replaces config.max_gradient_norm, the limit of the global-norm clip in front of
                                       Adam.  The reported grad_norm is the norm before clipping and does not depend on
                                       it; aleppo_export_grads scales by the limit the last aleppo_train ran with.
                                       Valid: finite and > 0 */
+  /* 22 stays unassigned: tests/test_hyper_schedule.py holds it as its example of an option that does not exist */
+  ALEPPO_OPT_REWARD_SCALE = 23,    /* return-based reward scaling (gym's NormalizeReward, SB3's VecNormalize(norm_reward),
+                                      the "reward scaling" of Engstrom et al. 2020) in place of the reward clamp.
+                                      0 (default): the reference's clamp to [-1, 1] (buffer.cc:67).  1: scaling; any other
+                                      value is ALEPPO_ERR_INVALID_ARGUMENT.  Read at each aleppo_finish_rollout, which then,
+                                      before GAE, on the records as the caller recorded them (raw fp32 rewards r[t][e] and
+                                      the three flags; whichever of aleppo_record_step / aleppo_step, aleppo_arm_step /
+                                      aleppo_release_step and aleppo_replay_rollout filled them):
+                                        1 running return.  G[e], a double per environment of this rank, 0 at aleppo_create,
+                                          carried from rollout to rollout.  For t = 0 .. T-1, in a slot that is NOT an
+                                          episode-start slot: G[e] = G[e] * (double)gamma + (double)r[t][e] (two roundings),
+                                          and this G[e] is one sample x; then G[e] = 0 if the slot is terminal or truncated.
+                                          An episode-start slot (whose reward is the stale one, rollout.cc:214) gives no
+                                          sample and leaves G[e] alone.
+                                        2 batch moments, in double: n, S = sum x, Q = sum x^2 over the rollout's samples.
+                                          The order is fixed and a function of (E, T) only: each environment in slot
+                                          order, 64 consecutive environments folded by a fixed tree, the groups of 64 added
+                                          in index order - two runs give the same bits.  With a communicator (world_size > 1
+                                          or ALEPPO_OPT_FORCE_COMM) the ranks' (n, S, Q) are all-reduced as ncclDouble /
+                                          ncclSum, and the call is a COLLECTIVE (as it is with advantage_norm = 1).
+                                          mean_b = S / n, var_b = max(0, Q / n - mean_b^2).
+                                        3 running statistics (count, mean, var), gym's / SB3's RunningMeanStd in double,
+                                          (1e-4, 0, 1) at aleppo_create.  If n > 0: d = mean_b - mean, tot = count + n,
+                                          mean += d * n / tot, var = (var * count + var_b * n + d * d * count * n / tot) /
+                                          tot, count = tot (left to right, no fused multiply-add; the same code with and
+                                          without the all-reduce, so a 1-rank communicator gives the single-GPU bits).
+                                        4 s = (float)(1 / sqrt(var + 1e-8)), computed in double and rounded once.
+                                        5 every reward of the rollout, start slots included, becomes
+                                          min(max(r * s, -c), c) in fp32, in place, c = ALEPPO_OPT_REWARD_SCALE_CLIP.  These
+                                          are the rewards GAE uses and ALEPPO_F_REWARDS returns; the clamp does not run.
+                                      Unlike gym, which updates the statistics after every step and scales that step's
+                                      reward with the statistics so far, all T slots of a rollout are scaled with the
+                                      statistics AFTER the whole rollout was merged; the running state after the rollout
+                                      is gym's (the merge is associative up to rounding).  The mean is never subtracted.
+                                      With the option off the state is kept and not updated.  aleppo_set_batch batches and
+                                      the evaluation lanes are untouched; ALEPPO_ROLLOUT_FP16 changes nothing here (the
+                                      records hold fp32 rewards).  A rollout aleppo_finish_rollout refuses for overlapping
+                                      flags leaves the state as it was.  With data parallelism every rank must set the same
+                                      two options (they are not exchanged, as for 17-21).  Read back: ALEPPO_F_REWARD_SCALE;
+                                      checkpoint: aleppo_export_reward_scale / aleppo_import_reward_scale */
+  ALEPPO_OPT_REWARD_SCALE_CLIP = 24 /* the clip c of ALEPPO_OPT_REWARD_SCALE as the IEEE-754 binary32 BIT PATTERN, like
+                                      ALEPPO_OPT_KL_COEF (default: the bits of 10.0f).  Valid: finite and > 0; anything else
+                                      is ALEPPO_ERR_INVALID_ARGUMENT and leaves the old value in place.  Read at each
+                                      aleppo_finish_rollout */
 } aleppo_option;
 int aleppo_set_option(aleppo_ctx *ctx, int option, int value);
 /* Current value of an option; for ALEPPO_OPT_UPDATE_GRAPH the number of graph launches so far (0 = every update ran

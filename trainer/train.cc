@@ -57,6 +57,11 @@
 // eval/episodes on the training scalars' step axis.  Each evaluation starts from freshly reset emulators and stacks, and
 // the lanes change nothing the rollout or the update can observe: the training run is bit-identical to the run without
 // the keys.  Under data parallelism every rank evaluates its own lanes and rank 0's are logged.
+// reward_scaling: false (true: ALEPPO_OPT_REWARD_SCALE - every rollout's rewards are divided by the running standard
+// deviation of the per-environment discounted return and clipped at +-reward_scale_clip, default 10, instead of being
+// clamped to +-1, so 1 and 4 points per brick stay 1 : 4; logs reward_scale, return_rms_std and rewards_clipped per
+// rollout).  A reward_scale_clip that is not finite and positive, or given without reward_scaling, is refused when the
+// config is loaded; a build whose library lacks the entry points refuses reward_scaling: true at start-up.
 // Data parallelism (no reference counterpart): start one process per GPU with RANK / WORLD_SIZE / LOCAL_RANK
 // in the environment (torchrun / mpirun style).  Rank r owns the contiguous environment block
 // [r * E / W, (r + 1) * E / W) and GPU LOCAL_RANK; rank 0 creates the RCCL id, hands it to the others through the file
@@ -95,6 +100,10 @@ int aleppo_eval_push_frames(aleppo_ctx *ctx, const uint8_t *frames, int frame_ki
 int aleppo_eval_act(aleppo_ctx *ctx, int rule, float param, const float *noise, const int64_t **actions_pinned)
     __attribute__((weak));
 int aleppo_eval_read(aleppo_ctx *ctx, int field, void *dst, size_t bytes) __attribute__((weak));
+// ... and so is the reward-scaling state (reward_scaling: true is refused without it)
+int aleppo_export_reward_scale(aleppo_ctx *ctx, double stats[3], double *returns, size_t num_envs) __attribute__((weak));
+int aleppo_import_reward_scale(aleppo_ctx *ctx, const double stats[3], const double *returns, size_t num_envs)
+    __attribute__((weak));
 }
 
 // ------------------------------------------------------------------ config
@@ -125,6 +134,9 @@ struct Config {
   size_t eval_interval = 0, eval_environments = 8, eval_episodes = 10;
   std::string eval_rule = "greedy";
   double eval_temperature = 1.0, eval_epsilon = 0.05;
+  // extension: return-based reward scaling in place of the reward clamp (ALEPPO_OPT_REWARD_SCALE / _CLIP)
+  bool reward_scaling = false;
+  double reward_scale_clip = 10.0;
   bool log_batch_stats = false; // extension: explained variance and value / return / advantage statistics (ALEPPO_F_BATCH_STATS)
   // extensions
   std::string precision = "fp32", rollout_precision = "fp32";
@@ -241,6 +253,14 @@ static Config load_config(const std::string &path) { // keys / defaults of src/b
       throw std::runtime_error("value_clip_range must be finite and positive");
     if (!c.clip_value_loss) // (nothing else reads it)
       throw std::runtime_error("value_clip_range needs clip_value_loss: true");
+  }
+  c.reward_scaling = as_bool(kv, "reward_scaling", false);
+  if (kv.count("reward_scale_clip")) { // what the option would refuse is refused here (a float: < 3e38 is finite)
+    c.reward_scale_clip = as<double>(kv, "reward_scale_clip", 10.0);
+    if (!(c.reward_scale_clip > 0 && c.reward_scale_clip < 3.0e38))
+      throw std::runtime_error("reward_scale_clip must be finite and positive");
+    if (!c.reward_scaling) // (nothing else reads it)
+      throw std::runtime_error("reward_scale_clip needs reward_scaling: true");
   }
   { // evaluation: what aleppo_eval_open / aleppo_eval_act would refuse is refused here
     const long interval = as<long>(kv, "eval_interval", 0), envs = as<long>(kv, "eval_environments", 8),
@@ -814,6 +834,9 @@ int main(int argc, char **argv) {
     if (cfg.eval_interval > 0 && !(aleppo_eval_open && aleppo_eval_push_frames && aleppo_eval_act && aleppo_eval_read))
       throw std::runtime_error("eval_interval is set but this build's library has no evaluation lanes "
                                "(aleppo_eval_open is missing)");
+    if (cfg.reward_scaling && !(aleppo_export_reward_scale && aleppo_import_reward_scale))
+      throw std::runtime_error("reward_scaling is set but this build's library has no reward scaling "
+                               "(aleppo_export_reward_scale is missing)");
     aleppo_config ac{};
     ac.abi_version = ALEPPO_ABI_VERSION;
     ac.device_ordinal = local_rank;
@@ -928,6 +951,10 @@ int main(int argc, char **argv) {
     };
     if (cfg.value_clip_range_set) // extension: a value-clip range of its own (constant)
       set_float_option(ALEPPO_OPT_VALUE_CLIP_RANGE, (float)cfg.value_clip_range);
+    if (cfg.reward_scaling) { // extension: rewards divided by the running return's std and clipped, not clamped to +-1
+      set_float_option(ALEPPO_OPT_REWARD_SCALE_CLIP, (float)cfg.reward_scale_clip);
+      check(ctx, aleppo_set_option(ctx, ALEPPO_OPT_REWARD_SCALE, 1));
+    }
     // extension: linear schedules of the clip range, the loss coefficients and the norm limit, one value per rollout
     struct HyperSchedule {
       const char *name; // the scalar's tag: the config key it schedules
@@ -960,6 +987,8 @@ int main(int argc, char **argv) {
       hparam_flags.emplace_back("minibatch_advantage_norm", true);
     if (cfg.log_batch_stats)
       hparam_flags.emplace_back("log_batch_stats", true);
+    if (cfg.reward_scaling)
+      hparam_flags.emplace_back("reward_scaling", true);
     if (cfg.eval_interval > 0) { // (only when set, like the others)
       hparam_numbers_eval = {{"eval_interval", (double)cfg.eval_interval},
                              {"eval_environments", (double)cfg.eval_environments},
@@ -1203,6 +1232,12 @@ int main(int argc, char **argv) {
       std::cout << "Rollout " << r + 1 << " of " << cfg.num_rollouts << std::endl;
       const double lr = cfg.learning_rate * (1.0 - r / static_cast<double>(cfg.num_rollouts)); // train.cc:424-428
       const Log log = rollout();
+      double rstats[ALEPPO_REWARD_SCALE_COUNT] = {}, rrms[3] = {0.0, 0.0, 1.0};
+      if (cfg.reward_scaling) { // what this rollout's finish_rollout did (the state is global under data parallelism)
+        std::vector<double> running(E);
+        check(ctx, aleppo_read_batch(ctx, ALEPPO_F_REWARD_SCALE, rstats, sizeof(rstats)));
+        check(ctx, aleppo_export_reward_scale(ctx, rrms, running.data(), running.size()));
+      }
       double bstats[ALEPPO_BATCH_STATS_COUNT] = {};
       if (cfg.log_batch_stats) { // of the rollout batch as the update below will see it; every rank calls (collective)
         Profile::Span sp(&prof, "read_batch_stats");
@@ -1297,6 +1332,11 @@ int main(int argc, char **argv) {
           else if (d > 1.5 * cfg.kl_target && std::isfinite(2.0f * kl_beta))
             kl_beta *= 2.0f;
         }
+      }
+      if (cfg.reward_scaling) { // (rewards_clipped: rank 0's environments)
+        logger.add_scalar("reward_scale", step, (float)rstats[ALEPPO_RS_SCALE]);
+        logger.add_scalar("return_rms_std", step, (float)std::sqrt(rrms[2]));
+        logger.add_scalar("rewards_clipped", step, (float)rstats[ALEPPO_RS_CLIPPED]);
       }
       if (cfg.log_batch_stats) { // (global statistics under data parallelism; a NaN explained variance is logged as NaN)
         logger.add_scalar("explained_variance", step, (float)bstats[ALEPPO_BS_EXPLAINED_VARIANCE]);
