@@ -1,0 +1,129 @@
+// api_internal.hpp - what the C ABI's translation units share (api_core.hip, api_rollout.hip, api_train.hip,
+// api_batch.hip, api_eval.hip, api_ops.hip): the entry-point guard macros and the host-side helpers.  Host code only; the
+// helpers are defined in api_core.hip unless noted.
+#pragma once
+#include "common.hpp"
+#include <algorithm>
+#include <cmath>
+#include <atomic>
+#include <chrono>
+#include <thread>
+#include <mutex>
+#include <cstring>
+#include <rccl/rccl.h>
+
+// ------------------------------------------------------------------ helpers
+// every stateful entry point: the caller's thread may have another device current, and the kernel-selection switches
+// are this context's
+#define CHECK_CTX_ANY(c)                                                                                               \
+  do {                                                                                                                 \
+    if (!(c))                                                                                                          \
+      return set_err(nullptr, ALEPPO_ERR_INVALID_ARGUMENT, "null context");                                            \
+    if (hipSetDevice((c)->cfg.device_ordinal) != hipSuccess)                                                           \
+      return set_err(const_cast<aleppo_ctx *>(c), ALEPPO_ERR_HIP, "hipSetDevice failed");                              \
+    set_tuning(&(c)->tune);                                                                                            \
+    if ((c)->failed)                                                                                                   \
+      return set_err(const_cast<aleppo_ctx *>(c), ALEPPO_ERR_RUNTIME, (c)->fail_msg);                                  \
+  } while (0)
+// Between aleppo_arm_step and aleppo_release_step the stream is parked on the release word: anything that enqueues behind
+// it and then waits (or rewrites what the parked kernels read) would dead-lock, so every entry point but the release
+// refuses.
+#define CHECK_CTX(c)                                                                                                   \
+  do {                                                                                                                 \
+    CHECK_CTX_ANY(c);                                                                                                  \
+    if ((c)->armed)                                                                                                    \
+      return set_err(const_cast<aleppo_ctx *>(c), ALEPPO_ERR_RUNTIME,                                                  \
+                     "a step is armed: call aleppo_release_step first");                                               \
+  } while (0)
+#define CHECK_ASYNC(c)                                                                                                 \
+  do {                                                                                                                 \
+    if ((c)->async_err != hipSuccess) {                                                                                \
+      const hipError_t e_ = (c)->async_err;                                                                            \
+      (c)->async_err = hipSuccess;                                                                                     \
+      return set_err((c), ALEPPO_ERR_HIP, std::string("asynchronous HIP failure: ") + hipGetErrorString(e_));          \
+    }                                                                                                                  \
+  } while (0)
+#define NCCLCHK(c, x)                                                                                                  \
+  do {                                                                                                                 \
+    ncclResult_t r_ = (x);                                                                                             \
+    if (r_ != ncclSuccess)                                                                                             \
+      return set_err((c), ALEPPO_ERR_HIP, std::string(#x) + ": " + ncclGetErrorString(r_));                            \
+  } while (0)
+
+namespace aleppo {
+
+// A failure after which the rollout / learner state is undefined: the context refuses every later call (sticky), any
+// gate still on the stream is released so that the stream drains, and nothing is freed or reused before aleppo_destroy
+// (kernels that are still queued may read the caller's frame buffers until then).
+int fail_ctx(Ctx *c, int code, const std::string &msg);
+
+inline size_t tsz(const Ctx *c) { return c->prec == ALEPPO_BF16 ? 2 : 4; }
+// A context only ever touches its OWN streams after aleppo_create: no null-stream operation, no hipFree, no
+// hipDeviceSynchronize.  Those calls wait for (hipFree / hipHostFree / hipDeviceSynchronize) or are ordered against
+// (null stream) other streams of the device - and another context's stream may be parked behind its release word,
+// which only ITS owner thread lifts (the cause of the two-context hang of round 2).
+template <class T> hipError_t dalloc(T **p, size_t bytes, hipStream_t st) {
+  hipError_t e = hipMalloc(reinterpret_cast<void **>(p), bytes ? bytes : 16);
+  if (e == hipSuccess)
+    e = hipMemsetAsync(*p, 0, bytes ? bytes : 16, st);
+  // the fill is asynchronous: wait for it, or a kernel on another stream of the context could use the buffer first and
+  // have its results wiped afterwards (round 2: a late fill of the ticket counter / the metric planes)
+  if (e == hipSuccess)
+    e = hipStreamSynchronize(st);
+  return e;
+}
+// host <-> device copy on the context's main stream, complete when the call returns
+hipError_t copy_sync(Ctx *c, void *dst, const void *src, size_t bytes, hipMemcpyKind kind);
+// device / pinned-host memory a context has outgrown: kept until aleppo_destroy (see above)
+void retire(Ctx *c, void *dev);
+void retire_host(Ctx *c, void *host);
+
+// a failure inside a helper that cannot return a status is kept in the context and reported by CHECK_ASYNC at the end of
+// the entry point (never dropped)
+inline void note(Ctx *c, hipError_t e) {
+  if (e != hipSuccess && c->async_err == hipSuccess)
+    c->async_err = e;
+}
+void prof_begin(Ctx *c, int cls, hipStream_t st = nullptr);
+void prof_end(Ctx *c, int cls, hipStream_t st = nullptr); // same stream as the matching prof_begin
+
+inline SampleMap train_map(const Ctx *c, long n0) {
+  // sample n = e*T + t lives in slot (e, t) of obs [E][T+1][7056]
+  return SampleMap{c->T, (long)(c->T + 1) * FRAME_PIX, (long)FRAME_PIX, 0, (int)n0};
+}
+inline SampleMap slot_map(const Ctx *c, int t) {
+  return SampleMap{1, (long)(c->T + 1) * FRAME_PIX, 0, (long)t * FRAME_PIX, 0};
+}
+
+inline const float *Pf(const Ctx *c, ParamId id) { return c->P + c->L.off[id]; }
+// element i of a rollout plane stored as RT (float or half)
+inline void *rp(const Ctx *c, void *plane, size_t i) { return static_cast<char *>(plane) + i * c->rsz; }
+inline const void *Pcw(const Ctx *c, ParamId id) {
+  return static_cast<const char *>(c->Pc) + c->L.off[id] * tsz(c);
+}
+
+// conv stack forward for ns samples addressed by map -> c->h
+// returns the number of split-K partial slabs of h (1 unless max_parts allows the pipelined fc kernel to split)
+int net_forward(Ctx *c, const uint32_t *obs, SampleMap map, long ns, int max_parts = 1);
+
+void refresh_compute_copies(Ctx *c);
+
+inline uint32_t float_bits(float f) {
+  uint32_t u;
+  std::memcpy(&u, &f, 4);
+  return u;
+}
+
+// the device the stateless operators and aleppo_create run on (process-default kernel switches)
+int select_device(int ordinal);
+
+// storage that more than one subsystem grows or reads.  api_train.hip: the per-sample metric planes (also the float
+// staging of aleppo_set_batch's half planes) and ALEPPO_OPT_VALUE_CLIP's old-values plane; api_rollout.hip:
+// ALEPPO_OPT_REWARD_SCALE's state
+int ensure_metric_storage(aleppo_ctx *c, int epochs, int M, long B);
+int ensure_val_storage(aleppo_ctx *c);
+extern const double RS_INITIAL[RS_BLOCK];
+int ensure_rs_storage(aleppo_ctx *c);
+bool rs_state_valid(const double stats[3]);
+
+} // namespace aleppo

@@ -94,9 +94,8 @@ struct Ctx {
   ParamLayout L;
   std::string err;
   hipStream_t stream = nullptr, comm_stream = nullptr, wg_stream = nullptr;
-  hipEvent_t ev_bucket0 = nullptr, ev_comm0 = nullptr, ev_comm1 = nullptr, ev_tmp = nullptr;
+  hipEvent_t ev_bucket0 = nullptr, ev_comm0 = nullptr, ev_tmp = nullptr;
   hipEvent_t ev_head = nullptr, ev_dz3 = nullptr, ev_dz2 = nullptr, ev_wg = nullptr; // dgrad chain -> wgrad side stream
-  hipEvent_t ev_adam = nullptr, ev_pack = nullptr; // adam done -> dgrad weight repack on the side stream -> done
   void *nccl_comm = nullptr;
 
   // ---- rollout storage (time-major scalars, env-major packed observation slots) ----
@@ -150,7 +149,7 @@ struct Ctx {
   uint8_t *mask_n = nullptr;
   float *mask_counts = nullptr; // [M_max] global unmasked count per minibatch
   // ---- network state ----
-  float *P = nullptr, *G = nullptr, *Gs = nullptr, *M1 = nullptr, *M2 = nullptr; // fp32, internal layout (Gs: unused)
+  float *P = nullptr, *G = nullptr, *M1 = nullptr, *M2 = nullptr; // fp32, internal layout
   void *Pc = nullptr;   // compute copy of P in T (same layout); == P for fp32
   void *W2d = nullptr, *W3d = nullptr, *WfcT = nullptr; // dgrad-transposed copies in T
   int64_t adam_step = 0;
@@ -358,20 +357,28 @@ void launch_shuffle_gather(hipStream_t s, const uint32_t *rk, int h, long N, int
 // ps_kl / ps_cf: the per-sample approx-KL and clip-fraction planes (always written);
 // advs: this minibatch's (mean_f, inv_f) of ALEPPO_OPT_ADV_NORM_MINIBATCH, or nullptr for the advantages as stored;
 // klb: ALEPPO_OPT_KL_PENALTY's beta (device float [1]) and ps_kle its per-sample exact-KL plane, or nullptr (off)
-void launch_head_train(hipStream_t s, const float *h, const float *Wh, const float *bh, const int *act,
-                       const void *oldlp, const void *adv, const void *ret, const void *vold, const uint8_t *mask,
-                       const float *mask_count, Hyper hp, void *dh, int prec, float *ps_total, float *ps_clipped,
-                       float *ps_value, float *ps_entropy, float *ps_ratio, float *ps_kl, float *ps_cf, float *slab_w,
-                       float *slab_b, int nblk, long B, int H, int A, float *logits_out, float *values_out,
-                       int hparts = 1, bool rt16 = false, // oldlp / adv / ret / vold are f16 planes
-                       const float *advs = nullptr, const float *klb = nullptr, float *ps_kle = nullptr);
+struct HeadTrainArgs {
+  const float *h, *Wh, *bh;
+  const int *act;
+  const void *oldlp, *adv, *ret, *vold; // planes of RT (float, or f16 with rt16)
+  const uint8_t *mask;
+  const float *mask_count;
+  void *dh;
+  int prec;
+  float *ps_total, *ps_clipped, *ps_value, *ps_entropy, *ps_ratio, *ps_kl, *ps_cf;
+  float *slab_w, *slab_b;
+  int nblk;
+  long B;
+  int H, A;
+  float *logits_out = nullptr, *values_out = nullptr;
+  int hparts = 1;
+  bool rt16 = false; // oldlp / adv / ret / vold are f16 planes
+  const float *advs = nullptr, *klb = nullptr;
+  float *ps_kle = nullptr;
+};
+void launch_head_train(hipStream_t s, const HeadTrainArgs &a, Hyper hp);
 // the same with hp = the device block of the hyper-parameter options (slots HYPER_CLIP .. HYPER_CE; head_hyper.hip)
-void launch_head_train_dev(hipStream_t s, const float *h, const float *Wh, const float *bh, const int *act,
-                           const void *oldlp, const void *adv, const void *ret, const void *vold, const uint8_t *mask,
-                           const float *mask_count, const float *hp, void *dh, int prec, float *ps_total,
-                           float *ps_clipped, float *ps_value, float *ps_entropy, float *ps_ratio, float *ps_kl,
-                           float *ps_cf, float *slab_w, float *slab_b, int nblk, long B, int H, int A, float *logits_out,
-                           float *values_out, int hparts, bool rt16, const float *advs, const float *klb, float *ps_kle);
+void launch_head_train_dev(hipStream_t s, const HeadTrainArgs &a, const float *hp);
 struct ReduceSeg {
   const float *slab;
   int S;

@@ -1,7 +1,7 @@
 // head_train_entry.inc - the PPO head training kernel's three __global__ entry points and their launcher, as text that is
 // instantiated once per way of passing the hyper-parameters (the includer defines, and owns, the macros):
 //   HEAD_KERNEL / HEAD_ADVN_KERNEL / HEAD_KL_KERNEL  the entry points' names
-//   HEAD_LAUNCH                                       the launcher's name (declared in common.hpp)
+//   HEAD_LAUNCH                                       the launcher's name (declared in common.hpp; HeadTrainArgs)
 //   HEAD_HP_T                                         the type of the argument `hp`: Hyper by value, or the device block
 //   HEAD_HYPER_LOAD                                   defines hp_clip / hp_vclip / hp_cv / hp_ce from `hp`
 // kernels.hip: the default route, whose instantiations are the ones that existed before the device block did;
@@ -35,73 +35,60 @@ __global__ __launch_bounds__(64 * head_waves(AMAX, true)) void HEAD_KL_KERNEL(HE
 }
 
 template <class T, class RT, bool VCLIP>
-static void head_train_t(hipStream_t s, const float *h, const float *Wh, const float *bh, const int *act,
-                         const RT *oldlp, const RT *adv, const RT *ret, const RT *vold, const uint8_t *mask,
-                         const float *mask_count, HEAD_HP_T hp, void *dh, float *ps_total, float *ps_clipped,
-                         float *ps_value, float *ps_entropy, float *ps_ratio, float *ps_kl, float *ps_cf, float *slab_w,
-                         float *slab_b, int nblk, long B, int H, int A, float *lo, float *vo, int hparts,
-                         const float *advs, const float *klb, float *ps_kle) {
+static void head_train_t(hipStream_t s, const HeadTrainArgs &a, HEAD_HP_T hp) {
+  const int H = a.H;
 #define HEAD_LAUNCH_ARGS                                                                                               \
-  h, Wh, bh, act, oldlp, adv, ret, vold, mask, mask_count, hp, static_cast<T *>(dh), ps_total, ps_clipped, ps_value,   \
-      ps_entropy, ps_ratio, ps_kl, ps_cf, slab_w, slab_b, B, H, A, lo, vo, hparts
+  a.h, a.Wh, a.bh, a.act, static_cast<const RT *>(a.oldlp), static_cast<const RT *>(a.adv),                            \
+      static_cast<const RT *>(a.ret), static_cast<const RT *>(a.vold), a.mask, a.mask_count, hp,                       \
+      static_cast<T *>(a.dh), a.ps_total, a.ps_clipped, a.ps_value, a.ps_entropy, a.ps_ratio, a.ps_kl, a.ps_cf,        \
+      a.slab_w, a.slab_b, a.B, a.H, a.A, a.logits_out, a.values_out, a.hparts
 #define LAUNCH_HEAD(AM)                                                                                                \
   do {                                                                                                                 \
     const size_t sm = ((size_t)((AM + 1) + ((AM + 1) > 8 ? (AM + 1) : 8)) * H + 8 * (AM + 1)) * sizeof(float);         \
-    const void *fn = klb    ? reinterpret_cast<const void *>(&HEAD_KL_KERNEL<T, AM, RT, VCLIP>)                        \
-                     : advs ? reinterpret_cast<const void *>(&HEAD_ADVN_KERNEL<T, AM, RT, VCLIP>)                      \
-                            : reinterpret_cast<const void *>(&HEAD_KERNEL<T, AM, RT, VCLIP>);                          \
+    const void *fn = a.klb    ? reinterpret_cast<const void *>(&HEAD_KL_KERNEL<T, AM, RT, VCLIP>)                      \
+                     : a.advs ? reinterpret_cast<const void *>(&HEAD_ADVN_KERNEL<T, AM, RT, VCLIP>)                    \
+                              : reinterpret_cast<const void *>(&HEAD_KERNEL<T, AM, RT, VCLIP>);                        \
     if (sm > 48 * 1024)                                                                                                \
       (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);                              \
-    if (klb)                                                                                                           \
-      hipLaunchKernelGGL((HEAD_KL_KERNEL<T, AM, RT, VCLIP>), dim3(nblk), dim3(64 * head_waves(AM, true)), sm, s,       \
-                         HEAD_LAUNCH_ARGS, advs, klb, ps_kle);                                                         \
-    else if (advs)                                                                                                     \
-      hipLaunchKernelGGL((HEAD_ADVN_KERNEL<T, AM, RT, VCLIP>), dim3(nblk), dim3(AM > 10 ? 256 : 512), sm, s,           \
-                         HEAD_LAUNCH_ARGS, advs);                                                                      \
+    if (a.klb)                                                                                                         \
+      hipLaunchKernelGGL((HEAD_KL_KERNEL<T, AM, RT, VCLIP>), dim3(a.nblk), dim3(64 * head_waves(AM, true)), sm, s,     \
+                         HEAD_LAUNCH_ARGS, a.advs, a.klb, a.ps_kle);                                                   \
+    else if (a.advs)                                                                                                   \
+      hipLaunchKernelGGL((HEAD_ADVN_KERNEL<T, AM, RT, VCLIP>), dim3(a.nblk), dim3(AM > 10 ? 256 : 512), sm, s,         \
+                         HEAD_LAUNCH_ARGS, a.advs);                                                                    \
     else                                                                                                               \
-      hipLaunchKernelGGL((HEAD_KERNEL<T, AM, RT, VCLIP>), dim3(nblk), dim3(AM > 10 ? 256 : 512), sm, s,                \
+      hipLaunchKernelGGL((HEAD_KERNEL<T, AM, RT, VCLIP>), dim3(a.nblk), dim3(AM > 10 ? 256 : 512), sm, s,              \
                          HEAD_LAUNCH_ARGS);                                                                            \
   } while (0)
-  if (A <= 4)
+  if (a.A <= 4)
     LAUNCH_HEAD(4);
-  else if (A <= 6)
+  else if (a.A <= 6)
     LAUNCH_HEAD(6);
-  else if (A <= 10)
+  else if (a.A <= 10)
     LAUNCH_HEAD(10);
   else
     LAUNCH_HEAD(18);
 #undef LAUNCH_HEAD
 #undef HEAD_LAUNCH_ARGS
 }
-void HEAD_LAUNCH(hipStream_t s, const float *h, const float *Wh, const float *bh, const int *act,
-                       const void *oldlp, const void *adv, const void *ret, const void *vold, const uint8_t *mask,
-                       const float *mask_count, HEAD_HP_T hp, void *dh, int prec, float *ps_total, float *ps_clipped,
-                       float *ps_value, float *ps_entropy, float *ps_ratio, float *ps_kl, float *ps_cf, float *slab_w,
-                       float *slab_b, int nblk, long B, int H, int A, float *logits_out, float *values_out, int hparts,
-                       bool rt16, const float *advs, const float *klb, float *ps_kle) {
-#define HEAD_ARGS(RT)                                                                                                  \
-  s, h, Wh, bh, act, static_cast<const RT *>(oldlp), static_cast<const RT *>(adv), static_cast<const RT *>(ret),       \
-      static_cast<const RT *>(vold), mask, mask_count, hp, dh, ps_total, ps_clipped, ps_value, ps_entropy, ps_ratio,   \
-      ps_kl, ps_cf, slab_w, slab_b, nblk, B, H, A, logits_out, values_out, hparts, advs, klb, ps_kle
+void HEAD_LAUNCH(hipStream_t s, const HeadTrainArgs &a, HEAD_HP_T hp) {
 #define HEAD_T(T, RT)                                                                                                  \
   do {                                                                                                                 \
-    if (vold)                                                                                                          \
-      head_train_t<T, RT, true>(HEAD_ARGS(RT));                                                                        \
+    if (a.vold)                                                                                                        \
+      head_train_t<T, RT, true>(s, a, hp);                                                                             \
     else                                                                                                               \
-      head_train_t<T, RT, false>(HEAD_ARGS(RT));                                                                       \
+      head_train_t<T, RT, false>(s, a, hp);                                                                            \
   } while (0)
-  if (prec == ALEPPO_BF16) {
-    if (rt16)
+  if (a.prec == ALEPPO_BF16) {
+    if (a.rt16)
       HEAD_T(bf16, f16);
     else
       HEAD_T(bf16, float);
   } else {
-    if (rt16)
+    if (a.rt16)
       HEAD_T(float, f16);
     else
       HEAD_T(float, float);
   }
 #undef HEAD_T
-#undef HEAD_ARGS
 }
-

@@ -430,7 +430,7 @@ def test_a_schedule_under_the_captured_update(pkg, prec):
     """Three updates with three settings of all four numbers, replayed from ONE captured graph, equal the same three
     updates run eagerly bit for bit, and the launch counter advances by three.  That the graph is not captured anew
     between them is not observable through the ABI: it is the option setter's re-arm list in aleppo_set_option
-    (api.hip) that leaves graph_key alone for the five options, as for ALEPPO_OPT_KL_COEF; a re-armed capture would
+    (api_core.hip) that leaves graph_key alone for the five options, as for ALEPPO_OPT_KL_COEF; a re-armed capture would
     run the next update eagerly and the counter would not advance on it."""
     E, T, A, H, epochs, M = 16, 16, 6, 256, 2, 2
     p = pkg.BF16 if prec == "bf16" else pkg.FP32
