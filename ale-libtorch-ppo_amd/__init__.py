@@ -52,6 +52,10 @@ METRIC_FIELDS = dict(total_losses=0, clipped_losses=1, value_losses=2, entropies
 METRIC_MEAN_FIELDS = dict(approx_kl=7, clip_fraction=8, kl=12)
 # the [epochs, M] statistics of OPT_ADV_NORM_MINIBATCH (aleppo_read_train_metric; Engine.advantage_stats)
 METRIC_ADV_FIELDS = dict(mean=9, std=10)
+# aleppo_state_digest: the indices of its ALEPPO_DIGEST_COUNT words (aleppo_digest_section; Engine.state_digest)
+DIGEST_COUNT = 4
+DIGEST_SECTIONS = dict(params=0, optimizer=1, rollout=2, reward_scale=3)
+ROLLOUT_STATE_WORDS = 4
 # aleppo_eval_rule / aleppo_eval_field: the evaluation lanes (Engine.eval_open / eval_push_frames / eval_act / eval_read)
 EVAL_GREEDY, EVAL_SAMPLE, EVAL_EPSILON_GREEDY = 0, 1, 2
 EVAL_RULES = dict(greedy=EVAL_GREEDY, sample=EVAL_SAMPLE, epsilon=EVAL_EPSILON_GREEDY)
@@ -103,6 +107,7 @@ EXPORTS = [
     "aleppo_read_sample_order", "aleppo_set_batch_values",
     "aleppo_eval_open", "aleppo_eval_push_frames", "aleppo_eval_act", "aleppo_eval_read",
     "aleppo_export_reward_scale", "aleppo_import_reward_scale", "aleppo_reward_scale",
+    "aleppo_export_rollout_state", "aleppo_import_rollout_state", "aleppo_state_digest",
 ]
 
 
@@ -379,6 +384,43 @@ class Engine:
                                               C.c_size_t(m.size)))
         if "reward_scale" in sd:
             self.load_reward_scale_state(sd["reward_scale"])
+
+    def rollout_state(self):
+        """aleppo_export_rollout_state, between rollouts only: {"observations": uint8 [E,4,84,84] the next act acts on,
+        "counter": the acting generator's counter}"""
+        obs = np.zeros((self.E, 4, 84, 84), np.uint8)
+        words = np.zeros(ROLLOUT_STATE_WORDS, np.uint64)
+        self._c(lib().aleppo_export_rollout_state(self._ctx, _ptr(obs), _ptr(words), C.c_size_t(self.E)))
+        return dict(observations=obs, counter=int(words[0]))
+
+    def load_rollout_state(self, state):
+        """aleppo_import_rollout_state: what rollout_state returned"""
+        obs = _u8(state["observations"])
+        if obs.shape != (self.E, 4, 84, 84):
+            raise AleppoInvalidArgument("rollout state observations must be uint8 [E,4,84,84]")
+        words = np.zeros(ROLLOUT_STATE_WORDS, np.uint64)
+        words[0] = int(state["counter"])
+        self._c(lib().aleppo_import_rollout_state(self._ctx, _ptr(obs), _ptr(words), C.c_size_t(self.E)))
+
+    def run_state(self):
+        """the whole run state between rollouts: state_dict() plus "rollout" (rollout_state) and, whether the option is on
+        or not, "reward_scale"; a fresh Engine that loads it continues the run bit for bit"""
+        sd = self.state_dict()
+        sd["reward_scale"] = self.reward_scale_state()
+        sd["rollout"] = self.rollout_state()
+        return sd
+
+    def load_run_state(self, sd):
+        """what run_state returned"""
+        self.load_state_dict(sd)
+        self.load_rollout_state(sd["rollout"])
+
+    def state_digest(self):
+        """aleppo_state_digest: {"params", "optimizer", "rollout", "reward_scale"} -> int, the 64-bit words of aleppo.h,
+        computed on the device; between rollouts only"""
+        out = np.zeros(DIGEST_COUNT, np.uint64)
+        self._c(lib().aleppo_state_digest(self._ctx, _ptr(out)))
+        return {name: int(out[i]) for name, i in DIGEST_SECTIONS.items()}
 
     # -- return-based reward scaling (OPT_REWARD_SCALE) --
     def set_reward_scaling(self, on, clip=10.0):

@@ -5,7 +5,7 @@
 using namespace aleppo;
 
 // NCHW uint8 observations of the caller -> c->stage_u8 (device), grown on demand and kept
-static int stage_observations(aleppo_ctx *c, const uint8_t *observations, int64_t n) {
+int aleppo::stage_observations(aleppo_ctx *c, const uint8_t *observations, int64_t n) {
   const size_t bytes = (size_t)n * 4 * FRAME_PIX;
   if (bytes > c->stage_u8_cap) {
     retire(c, c->stage_u8);

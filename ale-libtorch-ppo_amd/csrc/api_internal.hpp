@@ -1,5 +1,5 @@
 // api_internal.hpp - what the C ABI's translation units share (api_core.hip, api_rollout.hip, api_train.hip,
-// api_batch.hip, api_eval.hip, api_ops.hip): the entry-point guard macros and the host-side helpers.  Host code only; the
+// api_batch.hip, api_eval.hip, api_state.hip, api_ops.hip): the entry-point guard macros and the host-side helpers.  Host code only; the
 // helpers are defined in api_core.hip unless noted.
 #pragma once
 #include "common.hpp"
@@ -121,6 +121,8 @@ int select_device(int ordinal);
 // staging of aleppo_set_batch's half planes) and ALEPPO_OPT_VALUE_CLIP's old-values plane; api_rollout.hip:
 // ALEPPO_OPT_REWARD_SCALE's state
 int ensure_metric_storage(aleppo_ctx *c, int epochs, int M, long B);
+// api_batch.hip: NCHW uint8 observations of the caller -> c->stage_u8 (device), grown on demand and kept
+int stage_observations(aleppo_ctx *c, const uint8_t *observations, int64_t n);
 int ensure_val_storage(aleppo_ctx *c);
 extern const double RS_INITIAL[RS_BLOCK];
 int ensure_rs_storage(aleppo_ctx *c);

@@ -255,6 +255,7 @@ struct Ctx {
   size_t stage_u8_cap = 0;
   uint32_t *stage_obs = nullptr; // packed stacks of aleppo_forward's samples (never the rollout slots)
   size_t stage_obs_cap = 0;
+  unsigned long long *dg_out = nullptr; // aleppo_state_digest's four words (allocated on first use)
   // ---- evaluation lanes (aleppo_eval_open): L frame stacks of their own, their own acting scratch, upload staging and
   // action hand-off; nothing below is allocated, and nothing is enqueued for it, on a context that never opens them
   int ev_L = 0;                    // 0: not opened
@@ -408,6 +409,12 @@ void launch_obs_unpack(hipStream_t s, const uint32_t *obs, uint8_t *out, long ns
 void launch_obs_pack(hipStream_t s, const uint8_t *in, uint32_t *obs, long nsamp, SampleMap map);
 void launch_transpose_tm_pitched(hipStream_t s, const void *src_tm, size_t pitch, void *dst_em, int E, int T, int inner,
                                  int elem);
+// aleppo_state_digest: zeroes out[ALEPPO_DIGEST_COUNT] and adds the four sections of aleppo.h into it - the learner from the
+// internal layout (step: the Adam step), the rollout from the packed stacks of `slot` of obs [E][slots][7056] (counter: the
+// acting generator's), the reward-scale state from its block and running returns.  Reads only.
+void launch_state_digest(hipStream_t s, const float *P, const float *M1, const float *M2, const ParamLayout &L,
+                         int64_t step, const uint32_t *obs, int slots, int slot, int E, uint64_t counter,
+                         const double *rs_blk, const double *rs_g, unsigned long long *out);
 void launch_heads_fwd(hipStream_t s, const float *h, const float *Wh, const float *bh, float *logits, float *values,
                       long n, int H, int A);
 void launch_logsoftmax_rows(hipStream_t s, const float *in, float *out, long rows, int A);

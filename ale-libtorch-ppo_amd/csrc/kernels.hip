@@ -6,6 +6,7 @@
 #include "common.hpp"
 #include "gemm.hpp" // bf16 / vector typedefs
 #include "head_train.hpp" // f16, wave_sum, and what the head kernel's entry points share
+#include <algorithm>
 #include <cstdlib>
 
 namespace aleppo {
@@ -1680,5 +1681,157 @@ __global__ void rgb_to_gray_kernel(const float *in, float *out) {
 }
 void launch_rgb_to_gray(hipStream_t s, const float *in, float *out, long n) {
   hipLaunchKernelGGL(rgb_to_gray_kernel, dim3((FRAME_PIX + 255) / 256, (unsigned)n), dim3(256), 0, s, in, out);
+}
+
+// ================================================================================================
+// aleppo_state_digest (the definition is in aleppo.h): D(tag, w) = sum_i splitmix64(splitmix64(tag) ^ (i << 32 | w_i))
+// over the EXPORTED representation, computed from the private layouts in place.  One bandwidth-bound pass: every thread
+// takes 16-byte loads in a grid-stride loop, maps each word to its index in the exported order, and keeps a 64-bit sum;
+// a workgroup folds its sums (wave shuffles, then LDS) and adds them to the section's word with ONE 64-bit integer
+// atomic.  Integer addition mod 2^64 commutes, so the grid and the order of arrival do not show in the result.
+// Everything is only read; the four words of `out` are the only stores.
+// ================================================================================================
+__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
+  unsigned long long z = x + 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+__device__ __forceinline__ unsigned long long digest_term(unsigned long long tagkey, uint32_t i, uint32_t w) {
+  return splitmix64(tagkey ^ (((unsigned long long)i << 32) | w));
+}
+// sum of v over the 256 threads of the workgroup, valid in thread 0 (s4: 4 words of LDS; may be reused after a barrier)
+__device__ __forceinline__ unsigned long long digest_block_sum(unsigned long long v, unsigned long long *s4) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+    v += __shfl_down(v, o, 64);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0)
+    s4[wave] = v;
+  __syncthreads();
+  return s4[0] + s4[1] + s4[2] + s4[3];
+}
+// internal parameter layout -> libtorch parameters() index (the inverse of params_to_internal, api_core.hip): tensor k
+// holds `size` elements from internal offset `off`; element j = (oc, kk, c) of a [oc][KK][C] weight is exported at
+// base + (oc * C + c) * KK + kk (C = KK = 1: a plain copy); the stacked heads split at `split` (action rows | value row)
+struct DigestSeg {
+  uint32_t off, size, base, C, KK, split, base2;
+};
+struct DigestLayout {
+  DigestSeg seg[P_COUNT];
+  uint32_t groups; // 16-byte groups of the padded flat vector
+};
+__global__ __launch_bounds__(256) void digest_learner_kernel(const u32x4 *__restrict__ P, const u32x4 *__restrict__ M1,
+                                                              const u32x4 *__restrict__ M2, DigestLayout L,
+                                                              unsigned long long step, unsigned long long *out) {
+  __shared__ unsigned long long s4[4];
+  const unsigned long long k1 = splitmix64(1), k2 = splitmix64(2), k3 = splitmix64(3);
+  unsigned long long ap = 0, am = 0;
+  for (uint32_t g = blockIdx.x * 256u + threadIdx.x; g < L.groups; g += gridDim.x * 256u) {
+    const uint32_t i0 = g * 4u;
+    DigestSeg sg = L.seg[0]; // (selects on constant indices: the argument stays in scalar registers)
+#pragma unroll
+    for (int q = 1; q < P_COUNT; ++q) // (tensors start 64-float aligned: a group never straddles two)
+      if (i0 >= L.seg[q].off)
+        sg = L.seg[q];
+    const uint32_t j0 = i0 - sg.off;
+    if (j0 >= sg.size) // alignment pad: not part of the exported state
+      continue;
+    const u32x4 p = P[g], m = M1[g], v = M2[g];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const uint32_t j = j0 + e;
+      if (j < sg.size) {
+        uint32_t ref;
+        if (j >= sg.split)
+          ref = sg.base2 + (j - sg.split);
+        else {
+          const uint32_t c = j % sg.C, r = j / sg.C, kk = r % sg.KK, oc = r / sg.KK;
+          ref = sg.base + (oc * sg.C + c) * sg.KK + kk;
+        }
+        ap += digest_term(k1, ref, p[e]);
+        am += digest_term(k2, ref, m[e]) + digest_term(k3, ref, v[e]);
+      }
+    }
+  }
+  ap = digest_block_sum(ap, s4);
+  am = digest_block_sum(am, s4);
+  if (threadIdx.x == 0) {
+    if (blockIdx.x == 0)
+      am += splitmix64(splitmix64(4) ^ step);
+    atomicAdd(out + ALEPPO_DG_PARAMS, ap);
+    atomicAdd(out + ALEPPO_DG_OPTIMIZER, am);
+  }
+}
+// the stacks of slot `slot`: the packed word of a pixel IS s[e * 7056 + p] of the definition
+__global__ __launch_bounds__(256) void digest_rollout_kernel(const uint32_t *__restrict__ obs, int slots, int slot, int E,
+                                                              unsigned long long counter, unsigned long long *out) {
+  __shared__ unsigned long long s4[4];
+  constexpr uint32_t GPE = FRAME_PIX / 4; // 16-byte groups per environment
+  const unsigned long long k5 = splitmix64(5);
+  const uint32_t groups = (uint32_t)E * GPE;
+  unsigned long long a = 0;
+  for (uint32_t g = blockIdx.x * 256u + threadIdx.x; g < groups; g += gridDim.x * 256u) {
+    const uint32_t e = g / GPE, q = g - e * GPE;
+    const u32x4 w = *reinterpret_cast<const u32x4 *>(obs + ((size_t)e * slots + slot) * FRAME_PIX + q * 4u);
+    const uint32_t i = e * (uint32_t)FRAME_PIX + q * 4u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      a += digest_term(k5, i + k, w[k]);
+  }
+  a = digest_block_sum(a, s4);
+  if (threadIdx.x == 0) {
+    if (blockIdx.x == 0)
+      a += splitmix64(splitmix64(6) ^ counter);
+    atomicAdd(out + ALEPPO_DG_ROLLOUT, a);
+  }
+}
+// (count, mean, var) of the state block and the E running returns, each double as its low then its high word
+__global__ __launch_bounds__(256) void digest_rs_kernel(const double *__restrict__ blk, const double *__restrict__ g, int E,
+                                                         unsigned long long *out) {
+  __shared__ unsigned long long s4[4];
+  const unsigned long long k7 = splitmix64(7);
+  unsigned long long a = 0;
+  for (int d = threadIdx.x; d < 3 + E; d += 256) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(d < 3 ? blk[d] : g[d - 3]);
+    a += digest_term(k7, 2u * d, (uint32_t)b) + digest_term(k7, 2u * d + 1u, (uint32_t)(b >> 32));
+  }
+  a = digest_block_sum(a, s4);
+  if (threadIdx.x == 0)
+    atomicAdd(out + ALEPPO_DG_REWARD_SCALE, a);
+}
+void launch_state_digest(hipStream_t s, const float *P, const float *M1, const float *M2, const ParamLayout &L,
+                         int64_t step, const uint32_t *obs, int slots, int slot, int E, uint64_t counter,
+                         const double *rs_blk, const double *rs_g, unsigned long long *out) {
+  DigestLayout dl{};
+  const uint32_t H = (uint32_t)L.H, A = (uint32_t)L.A;
+  // reference offsets: c1w c1b c2w c2b c3w c3b fcw fcb aw ab vw vb
+  const uint32_t r_b1 = 32 * 256, r_w2 = r_b1 + 32, r_b2 = r_w2 + 64 * 512, r_w3 = r_b2 + 64, r_b3 = r_w3 + 64 * 576,
+                 r_fc = r_b3 + 64, r_bfc = r_fc + H * FC_IN, r_aw = r_bfc + H, r_ab = r_aw + A * H, r_vw = r_ab + A,
+                 r_vb = r_vw + H;
+  auto seg = [&](ParamId id, uint32_t base, uint32_t C, uint32_t KK, uint32_t split = ~0u, uint32_t base2 = 0) {
+    dl.seg[id] = DigestSeg{(uint32_t)L.off[id], (uint32_t)L.size[id], base, C, KK, split, base2};
+  };
+  seg(P_WH, r_aw, 1, 1, A * H, r_vw);
+  seg(P_BH, r_ab, 1, 1, A, r_vb);
+  seg(P_WFC, r_fc, 64, 49);
+  seg(P_BFC, r_bfc, 1, 1);
+  seg(P_W3, r_w3, 64, 9);
+  seg(P_B3, r_b3, 1, 1);
+  seg(P_W2, r_w2, 32, 16);
+  seg(P_B2, r_b2, 1, 1);
+  seg(P_W1, 0, 4, 64);
+  seg(P_B1, r_b1, 1, 1);
+  dl.groups = (uint32_t)(L.total() / 4);
+  // one 16-byte group per thread up to 2048 workgroups (8 per CU), a grid-stride loop beyond
+  auto grid = [](uint32_t groups) { return dim3(std::min<uint32_t>((groups + 255u) / 256u, 2048u)); };
+  hipMemsetAsync(out, 0, ALEPPO_DIGEST_COUNT * sizeof(unsigned long long), s);
+  hipLaunchKernelGGL(digest_learner_kernel, grid(dl.groups), dim3(256), 0, s, reinterpret_cast<const u32x4 *>(P),
+                     reinterpret_cast<const u32x4 *>(M1), reinterpret_cast<const u32x4 *>(M2), dl,
+                     (unsigned long long)step, out);
+  hipLaunchKernelGGL(digest_rollout_kernel, grid((uint32_t)E * (FRAME_PIX / 4)), dim3(256), 0, s, obs, slots, slot, E,
+                     (unsigned long long)counter, out);
+  hipLaunchKernelGGL(digest_rs_kernel, dim3(1), dim3(256), 0, s, rs_blk, rs_g, E, out);
 }
 } // namespace aleppo

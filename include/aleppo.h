@@ -238,6 +238,57 @@ int aleppo_import_optimizer(aleppo_ctx *ctx, const float *exp_avg, const float *
  * context's own stream only, and are ALEPPO_ERR_RUNTIME while a step is armed. */
 int aleppo_export_reward_scale(aleppo_ctx *ctx, double stats[3], double *returns, size_t num_envs);
 int aleppo_import_reward_scale(aleppo_ctx *ctx, const double stats[3], const double *returns, size_t num_envs);
+/* The rollout side of a checkpoint - what the three pairs above do not carry across a process boundary: the current
+ * frame stacks and the counter of the acting generator.  With it a fresh context continues the RUN bit for bit, not only
+ * the learner: the rollout that follows an import is the one the exporting context would have run - actions, logits,
+ * values and every plane.
+ * observations: uint8 [num_envs,4,84,84] in reference layout, the observation the next aleppo_act will act on (the bytes
+ *   of ALEPPO_F_CURRENT_OBS).  words[0]: the counter of aleppo_act's built-in generator (every aleppo_act and the
+ *   bootstrap forward of aleppo_finish_rollout advance it by one); words[1..3] are reserved: the export writes 0, the
+ *   import refuses anything else.
+ * Both calls are valid BETWEEN ROLLOUTS only: the next slot to fill is 0, which holds after aleppo_create and after
+ *   aleppo_finish_rollout, with or without the aleppo_train that follows; at any other time ALEPPO_ERR_RUNTIME, as while a
+ *   step is armed.  A null pointer, num_envs != config.num_envs and a non-zero reserved word are
+ *   ALEPPO_ERR_INVALID_ARGUMENT.  A call that fails changes nothing.
+ * The import puts the stacks where a finished rollout leaves its last observation (the next aleppo_act carries them into
+ *   the first slot, as it does after aleppo_finish_rollout), drops the acting scratch aleppo_step pre-computed and sets the
+ *   counter.  The batch (a rollout that was finished but not trained on yet included), the metrics, the options and the
+ *   evaluation lanes are not part of the state and are left alone.
+ * Both synchronise the context's own stream only and are never a collective; staging is grown on demand and kept until
+ *   aleppo_destroy like the other boundary buffers. */
+#define ALEPPO_ROLLOUT_STATE_WORDS 4
+int aleppo_export_rollout_state(aleppo_ctx *ctx, uint8_t *observations, uint64_t words[ALEPPO_ROLLOUT_STATE_WORDS],
+                                size_t num_envs);
+int aleppo_import_rollout_state(aleppo_ctx *ctx, const uint8_t *observations,
+                                const uint64_t words[ALEPPO_ROLLOUT_STATE_WORDS], size_t num_envs);
+/* A digest of the whole run state, computed on the device where the state is: four 64-bit words, one per section, that
+ * any host can recompute from the exported state.  Two contexts whose words agree hold the same run state (up to a
+ * 64-bit hash collision): a resumed run proves that it continues the run that was saved, and two data-parallel ranks -
+ * which must hold the same parameters and Adam state, and drift apart when they are given different options - can be
+ * compared from their logs, without moving 20 MB to the host per check.
+ * With splitmix64 as specified at aleppo_read_sample_order, u64 arithmetic that wraps, and w a sequence of 32-bit words:
+ *   D(tag, w[0..n)) = sum_i splitmix64( splitmix64(tag) ^ (((uint64)i << 32) | w_i) )
+ *   ALEPPO_DG_PARAMS        D(1, the bits of the flat fp32 parameters of aleppo_export_params, in that order)
+ *   ALEPPO_DG_OPTIMIZER     D(2, bits of exp_avg) + D(3, bits of exp_avg_sq) + splitmix64(splitmix64(4) ^ (uint64)step)
+ *                           (aleppo_export_optimizer)
+ *   ALEPPO_DG_ROLLOUT       D(5, s) + splitmix64(splitmix64(6) ^ words[0]) of aleppo_export_rollout_state, with
+ *                           s[e * 7056 + p] = obs[e,0,p] | obs[e,1,p] << 8 | obs[e,2,p] << 16 | obs[e,3,p] << 24
+ *   ALEPPO_DG_REWARD_SCALE  D(7, w), w = the doubles (count, mean, var, G[0 .. num_envs)) of aleppo_export_reward_scale,
+ *                           each as its low and then its high 32-bit word; before ALEPPO_OPT_REWARD_SCALE was ever used
+ *                           that is the initial state (1e-4, 0, 1) and G = 0
+ * The sums commute, so the words do not depend on how the device walks its private layouts.  Computed WHEN CALLED, on the
+ * context's stream (one pass that only reads the state), followed by that stream's synchronise; never a collective; a
+ * context that never calls it enqueues nothing for it.  ALEPPO_ERR_RUNTIME while a step is armed and, because the rollout
+ * section is defined between rollouts only (see above), while a rollout is in progress; a null pointer is
+ * ALEPPO_ERR_INVALID_ARGUMENT. */
+#define ALEPPO_DIGEST_COUNT 4
+typedef enum {
+  ALEPPO_DG_PARAMS = 0,
+  ALEPPO_DG_OPTIMIZER = 1,
+  ALEPPO_DG_ROLLOUT = 2,
+  ALEPPO_DG_REWARD_SCALE = 3
+} aleppo_digest_section;
+int aleppo_state_digest(aleppo_ctx *ctx, uint64_t out[ALEPPO_DIGEST_COUNT]);
 
 /* ------------------------------------------------------------------ rollout (Rollout::rollout, rollout.cc:198-278)
  * Per slot t = 0..T-1 the caller does  act -> (step its emulators) -> push_frames -> record_step,

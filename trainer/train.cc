@@ -62,6 +62,15 @@
 // clamped to +-1, so 1 and 4 points per brick stay 1 : 4; logs reward_scale, return_rms_std and rewards_clipped per
 // rollout).  A reward_scale_clip that is not finite and positive, or given without reward_scaling, is refused when the
 // config is loaded; a build whose library lacks the entry points refuses reward_scaling: true at start-up.
+// checkpoint_path: <file> (absent: the run is unchanged), checkpoint_interval: n (needs checkpoint_path; n > 0: the whole run
+// state - parameters, Adam state, reward-scale state, the rollout's frame stacks and sampling counter, and this trainer's
+// own bookkeeping down to every emulator's fields - is written after the update of every n-th rollout and after the last
+// one, to <file>.tmp and then renamed; the four words of aleppo_state_digest are stored in the file and logged as hex) and
+// resume: <file> (the run continues at the rollout the file was written before, bit for bit: the warm rollout is not
+// repeated, and after the import the digest is computed again and compared with the file's, a mismatch being fatal).
+// Under data parallelism every rank writes and reads <file>.rank<r>.  A resume file that is missing, truncated, of another
+// format version or written for another shape (environments, horizon, actions, hidden size, precision, world size, rank)
+// is refused before anything is created; a library without the entry points refuses the three keys at start-up.
 // Data parallelism (no reference counterpart): start one process per GPU with RANK / WORLD_SIZE / LOCAL_RANK
 // in the environment (torchrun / mpirun style).  Rank r owns the contiguous environment block
 // [r * E / W, (r + 1) * E / W) and GPU LOCAL_RANK; rank 0 creates the RCCL id, hands it to the others through the file
@@ -104,6 +113,16 @@ int aleppo_eval_read(aleppo_ctx *ctx, int field, void *dst, size_t bytes) __attr
 int aleppo_export_reward_scale(aleppo_ctx *ctx, double stats[3], double *returns, size_t num_envs) __attribute__((weak));
 int aleppo_import_reward_scale(aleppo_ctx *ctx, const double stats[3], const double *returns, size_t num_envs)
     __attribute__((weak));
+// ... and what a checkpoint needs (checkpoint_path / checkpoint_interval / resume are refused without it)
+int aleppo_export_optimizer(aleppo_ctx *ctx, float *exp_avg, float *exp_avg_sq, int64_t *step, size_t count)
+    __attribute__((weak));
+int aleppo_import_optimizer(aleppo_ctx *ctx, const float *exp_avg, const float *exp_avg_sq, int64_t step, size_t count)
+    __attribute__((weak));
+int aleppo_export_rollout_state(aleppo_ctx *ctx, uint8_t *observations, uint64_t words[4], size_t num_envs)
+    __attribute__((weak));
+int aleppo_import_rollout_state(aleppo_ctx *ctx, const uint8_t *observations, const uint64_t words[4], size_t num_envs)
+    __attribute__((weak));
+int aleppo_state_digest(aleppo_ctx *ctx, uint64_t out[4]) __attribute__((weak));
 }
 
 // ------------------------------------------------------------------ config
@@ -137,6 +156,9 @@ struct Config {
   // extension: return-based reward scaling in place of the reward clamp (ALEPPO_OPT_REWARD_SCALE / _CLIP)
   bool reward_scaling = false;
   double reward_scale_clip = 10.0;
+  // extension: checkpoint and resume (aleppo_export_rollout_state / aleppo_state_digest and the learner's export pairs)
+  std::string checkpoint_path, resume;
+  long checkpoint_interval = 0; // 0: only after the last rollout
   bool log_batch_stats = false; // extension: explained variance and value / return / advantage statistics (ALEPPO_F_BATCH_STATS)
   // extensions
   std::string precision = "fp32", rollout_precision = "fp32";
@@ -287,6 +309,15 @@ static Config load_config(const std::string &path) { // keys / defaults of src/b
     if (!(c.eval_epsilon >= 0 && c.eval_epsilon <= 1))
       throw std::runtime_error("eval_epsilon must be in [0, 1]");
   }
+  c.checkpoint_path = as<std::string>(kv, "checkpoint_path", "");
+  c.resume = as<std::string>(kv, "resume", "");
+  if (kv.count("checkpoint_interval")) {
+    c.checkpoint_interval = as<long>(kv, "checkpoint_interval", 0);
+    if (c.checkpoint_interval <= 0)
+      throw std::runtime_error("checkpoint_interval must be positive");
+    if (c.checkpoint_path.empty()) // (there would be nowhere to write to)
+      throw std::runtime_error("checkpoint_interval needs checkpoint_path");
+  }
   c.deterministic = as_bool(kv, "deterministic", false);
   c.precision = as<std::string>(kv, "precision", "fp32");
   c.rollout_precision = as<std::string>(kv, "rollout_precision", "fp32");
@@ -364,6 +395,28 @@ public:
     render(frame);
     (void)actions_;
     return o;
+  }
+
+  // every field that changes after construction, for a checkpoint (the constructor's arguments come from the config)
+  static constexpr size_t state_bytes = 8 + 9 * 4 + 8 + 4;
+  void save(std::string &out) const {
+    const int32_t ints[9] = {lives_, paddle_, ball_x_, ball_y_, prev_x_, prev_y_, dx_, dy_, bricks_};
+    const uint64_t steps = steps_;
+    out.append(reinterpret_cast<const char *>(&rng_), 8);
+    out.append(reinterpret_cast<const char *>(ints), sizeof(ints));
+    out.append(reinterpret_cast<const char *>(&steps), 8);
+    out.append(reinterpret_cast<const char *>(&episode_return_), 4);
+  }
+  void load(const uint8_t *in) { // state_bytes bytes that save() wrote
+    int32_t ints[9];
+    uint64_t steps;
+    std::memcpy(&rng_, in, 8);
+    std::memcpy(ints, in + 8, sizeof(ints));
+    std::memcpy(&steps, in + 8 + sizeof(ints), 8);
+    std::memcpy(&episode_return_, in + 16 + sizeof(ints), 4);
+    lives_ = ints[0], paddle_ = ints[1], ball_x_ = ints[2], ball_y_ = ints[3], prev_x_ = ints[4], prev_y_ = ints[5];
+    dx_ = ints[6], dy_ = ints[7], bricks_ = ints[8];
+    steps_ = (size_t)steps;
   }
 
 private:
@@ -783,6 +836,121 @@ template <class T> static float meanf(const std::vector<T> &v) {
   return v.empty() ? 0.f : (float)(std::accumulate(v.begin(), v.end(), 0.0) / (double)v.size());
 }
 
+// ------------------------------------------------------------------ checkpoint file (INTEGRATION.md has the format)
+// little-endian: magic, version, the shape header, sections of (u32 id, u64 byte length, bytes), the end mark
+constexpr char CKPT_MAGIC[8] = {'A', 'L', 'E', 'P', 'P', 'O', 'C', 'K'};
+constexpr char CKPT_END[8] = {'A', 'L', 'E', 'P', 'P', 'O', 'E', 'N'};
+constexpr uint32_t CKPT_VERSION = 1;
+enum CkptSection : uint32_t { CK_PARAMS = 1, CK_OPTIMIZER = 2, CK_REWARD_SCALE = 3, CK_ROLLOUT = 4, CK_TRAINER = 5, CK_DIGEST = 6 };
+static const char *const DIGEST_NAMES[ALEPPO_DIGEST_COUNT] = {"params", "optimizer", "rollout", "reward_scale"};
+struct CkptShape {
+  uint32_t E, T, A, H, precision, world, rank, reserved;
+  uint64_t param_count;
+};
+struct Checkpoint {
+  CkptShape shape{};
+  std::map<uint32_t, std::string> sections;
+};
+template <class T> static void put(std::string &out, const T &v) { out.append(reinterpret_cast<const char *>(&v), sizeof(T)); }
+template <class T> static void put_vec(std::string &out, const std::vector<T> &v) {
+  out.append(reinterpret_cast<const char *>(v.data()), v.size() * sizeof(T));
+}
+static void write_checkpoint_file(const std::string &path, const Checkpoint &ck) {
+  std::string out(CKPT_MAGIC, 8);
+  put(out, CKPT_VERSION);
+  put(out, ck.shape);
+  for (const auto &sec : ck.sections) {
+    put(out, sec.first);
+    put(out, (uint64_t)sec.second.size());
+    out += sec.second;
+  }
+  out.append(CKPT_END, 8);
+  const std::string tmp = path + ".tmp";
+  {
+    std::ofstream f(tmp, std::ios::binary | std::ios::trunc);
+    f.write(out.data(), (std::streamsize)out.size());
+    f.flush();
+    if (!f)
+      throw std::runtime_error("cannot write checkpoint " + tmp);
+  }
+  std::filesystem::rename(tmp, path); // atomic: a reader sees a whole checkpoint under the final name, or the old one
+}
+// reads and checks the framing: every failure names the file and what is wrong with it
+static Checkpoint read_checkpoint_file(const std::string &path) {
+  std::ifstream f(path, std::ios::binary);
+  if (!f)
+    throw std::runtime_error("resume: cannot open checkpoint " + path);
+  const std::string in((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+  size_t pos = 0;
+  auto need = [&](size_t n) {
+    if (in.size() - pos < n)
+      throw std::runtime_error("resume: checkpoint " + path + " is truncated");
+  };
+  auto get = [&](void *dst, size_t n) {
+    need(n);
+    std::memcpy(dst, in.data() + pos, n);
+    pos += n;
+  };
+  char magic[8];
+  get(magic, 8);
+  if (std::memcmp(magic, CKPT_MAGIC, 8) != 0)
+    throw std::runtime_error("resume: " + path + " is not a checkpoint (wrong magic)");
+  uint32_t version = 0;
+  get(&version, 4);
+  if (version != CKPT_VERSION)
+    throw std::runtime_error("resume: checkpoint " + path + " has format version " + std::to_string(version) +
+                             ", this build reads version " + std::to_string(CKPT_VERSION));
+  Checkpoint ck;
+  get(&ck.shape, sizeof(ck.shape));
+  for (;;) {
+    need(8);
+    if (std::memcmp(in.data() + pos, CKPT_END, 8) == 0 && in.size() - pos == 8)
+      break;
+    uint32_t id = 0;
+    uint64_t len = 0;
+    get(&id, 4);
+    get(&len, 8);
+    if (len > in.size() - pos)
+      throw std::runtime_error("resume: checkpoint " + path + " is truncated");
+    ck.sections[id] = in.substr(pos, (size_t)len);
+    pos += (size_t)len;
+  }
+  for (uint32_t id : {CK_PARAMS, CK_OPTIMIZER, CK_REWARD_SCALE, CK_ROLLOUT, CK_TRAINER, CK_DIGEST})
+    if (!ck.sections.count(id))
+      throw std::runtime_error("resume: checkpoint " + path + " lacks section " + std::to_string(id));
+  return ck;
+}
+// the shape the file was written for against this run's; the section sizes that follow from it
+static void check_checkpoint_shape(const std::string &path, const Checkpoint &ck, const CkptShape &want) {
+  const struct {
+    const char *name;
+    uint64_t file, run;
+  } f[] = {{"total_environments / WORLD_SIZE", ck.shape.E, want.E}, {"horizon", ck.shape.T, want.T},
+           {"action_size", ck.shape.A, want.A},                     {"hidden_size", ck.shape.H, want.H},
+           {"precision", ck.shape.precision, want.precision},       {"WORLD_SIZE", ck.shape.world, want.world},
+           {"RANK", ck.shape.rank, want.rank},                      {"parameter count", ck.shape.param_count, want.param_count}};
+  for (const auto &x : f)
+    if (x.file != x.run)
+      throw std::runtime_error("resume: checkpoint " + path + " was written for " + x.name + " = " +
+                               std::to_string(x.file) + ", this run has " + std::to_string(x.run));
+  const size_t n = (size_t)want.param_count, E = want.E;
+  const size_t trainer_bytes = 4 * 8 + 4 + 4 * E + 3 * 4 * E + 2 * 8 * E + E * SyntheticAtari::state_bytes;
+  const std::pair<uint32_t, size_t> sizes[] = {{CK_PARAMS, n * 4},
+                                               {CK_OPTIMIZER, 2 * n * 4 + 8},
+                                               {CK_REWARD_SCALE, (3 + E) * 8},
+                                               {CK_ROLLOUT, 4 * 8 + E * 4 * 84 * 84},
+                                               {CK_TRAINER, trainer_bytes},
+                                               {CK_DIGEST, ALEPPO_DIGEST_COUNT * 8}};
+  for (const auto &sz : sizes)
+    if (ck.sections.at(sz.first).size() != sz.second)
+      throw std::runtime_error("resume: checkpoint " + path + " is corrupt (section " + std::to_string(sz.first) + " has " +
+                               std::to_string(ck.sections.at(sz.first).size()) + " bytes, expected " +
+                               std::to_string(sz.second) + ")");
+}
+static size_t reference_param_count(size_t H, size_t A) { // libtorch parameters() element count of the network
+  return 32 * 256 + 32 + 64 * 512 + 64 + 64 * 576 + 64 + H * 3136 + H + A * H + A + H + 1;
+}
+
 int main(int argc, char **argv) {
   if (argc < 6) {
     std::fprintf(stderr, "usage: %s <rom> <tensorboard log path> <video dir> <group> <config.yaml> [profile]\n", argv[0]);
@@ -824,6 +992,24 @@ int main(int argc, char **argv) {
     if (cfg.record_video)
       std::cerr << "note: record_video ignored (no ffmpeg / ALE in this build)\n";
 
+    // checkpoint / resume: refused here, before anything is created, when the library or the file cannot serve it
+    const bool ckpt_keys = !cfg.checkpoint_path.empty() || !cfg.resume.empty();
+    if (ckpt_keys && !(aleppo_export_rollout_state && aleppo_import_rollout_state && aleppo_state_digest &&
+                       aleppo_export_optimizer && aleppo_import_optimizer && aleppo_export_reward_scale &&
+                       aleppo_import_reward_scale))
+      throw std::runtime_error("checkpoint_path / checkpoint_interval / resume are set but this build's library cannot "
+                               "checkpoint a run (aleppo_export_rollout_state is missing)");
+    const std::string rank_suffix = world > 1 ? ".rank" + std::to_string(rank) : "";
+    const std::string ckpt_file = cfg.checkpoint_path.empty() ? "" : cfg.checkpoint_path + rank_suffix;
+    const std::string resume_file = cfg.resume.empty() ? "" : cfg.resume + rank_suffix;
+    CkptShape ckpt_shape{(uint32_t)E, (uint32_t)T, (uint32_t)A, (uint32_t)cfg.hidden_size,
+                         (uint32_t)(cfg.precision == "bf16" ? ALEPPO_BF16 : ALEPPO_FP32), (uint32_t)world, (uint32_t)rank, 0,
+                         (uint64_t)reference_param_count(cfg.hidden_size, A)};
+    Checkpoint resumed;
+    if (!resume_file.empty()) {
+      resumed = read_checkpoint_file(resume_file);
+      check_checkpoint_shape(resume_file, resumed, ckpt_shape);
+    }
     if (const char *dump = std::getenv("ALEPPO_TRAINER_DUMP_INIT")) { // test hook: the initial parameters, no GPU needed
       const std::vector<float> p = init_params(cfg.hidden_size, A, cfg.deterministic ? 42 : (uint64_t)start_time);
       std::ofstream f(dump, std::ios::binary);
@@ -1214,7 +1400,126 @@ int main(int argc, char **argv) {
       return e;
     };
 
-    rollout(); // the warm rollout before the loop (train.cc:391-396): collected, never trained on
+    // ---- checkpoint / resume: the whole run state between two rollouts
+    const size_t n_params = (size_t)ckpt_shape.param_count;
+    auto save_checkpoint = [&](size_t next_rollout) {
+      Profile::Span sp(&prof, "checkpoint");
+      Checkpoint ck;
+      ck.shape = ckpt_shape;
+      std::vector<float> p(n_params), m1(n_params), m2(n_params);
+      int64_t adam_step = 0;
+      check(ctx, aleppo_export_params(ctx, p.data(), n_params));
+      check(ctx, aleppo_export_optimizer(ctx, m1.data(), m2.data(), &adam_step, n_params));
+      std::string &so = ck.sections[CK_OPTIMIZER];
+      put_vec(ck.sections[CK_PARAMS], p);
+      put_vec(so, m1);
+      put_vec(so, m2);
+      put(so, adam_step);
+      std::vector<double> rs(3 + E);
+      check(ctx, aleppo_export_reward_scale(ctx, rs.data(), rs.data() + 3, E));
+      put_vec(ck.sections[CK_REWARD_SCALE], rs);
+      std::vector<uint8_t> obs(E * 4 * 84 * 84);
+      uint64_t words[ALEPPO_ROLLOUT_STATE_WORDS];
+      check(ctx, aleppo_export_rollout_state(ctx, obs.data(), words, E));
+      std::string &sr = ck.sections[CK_ROLLOUT];
+      put(sr, words);
+      put_vec(sr, obs);
+      std::string &st = ck.sections[CK_TRAINER];
+      put(st, (uint64_t)next_rollout);
+      put(st, (uint64_t)total_steps);
+      put(st, (uint64_t)episodes);
+      put(st, (uint64_t)next_rollout); // the schedule position: the rollout index the annealed values are functions of
+      put(st, kl_beta);
+      put_vec(st, start_cpu);
+      put_vec(st, term);
+      put_vec(st, trunc);
+      put_vec(st, game_over);
+      put_vec(st, rewards);
+      put_vec(st, ep_ret);
+      put_vec(st, game_ret);
+      put_vec(st, std::vector<uint64_t>(ep_len.begin(), ep_len.end()));
+      put_vec(st, std::vector<uint64_t>(game_len.begin(), game_len.end()));
+      for (const SyntheticAtari &e : envs)
+        e.save(st);
+      uint64_t dg[ALEPPO_DIGEST_COUNT];
+      check(ctx, aleppo_state_digest(ctx, dg));
+      put(ck.sections[CK_DIGEST], dg);
+      write_checkpoint_file(ckpt_file, ck);
+      char line[256];
+      std::snprintf(line, sizeof line, "checkpoint rollout %zu digest params=%016llx optimizer=%016llx rollout=%016llx "
+                    "reward_scale=%016llx", next_rollout, (unsigned long long)dg[0], (unsigned long long)dg[1],
+                    (unsigned long long)dg[2], (unsigned long long)dg[3]);
+      std::cout << line << " -> " << ckpt_file << std::endl;
+    };
+    size_t first_rollout = 0;
+    if (!resume_file.empty()) { // import everything, then prove it: the device's digest against the file's
+      const auto sec = [&](uint32_t id) { return reinterpret_cast<const uint8_t *>(resumed.sections.at(id).data()); };
+      auto take = [](const uint8_t *&p, void *dst, size_t n) {
+        std::memcpy(dst, p, n);
+        p += n;
+      };
+      std::vector<float> p(n_params), m1(n_params), m2(n_params);
+      int64_t adam_step = 0;
+      std::memcpy(p.data(), sec(CK_PARAMS), n_params * 4);
+      const uint8_t *q = sec(CK_OPTIMIZER);
+      take(q, m1.data(), n_params * 4);
+      take(q, m2.data(), n_params * 4);
+      take(q, &adam_step, 8);
+      check(ctx, aleppo_load_params(ctx, p.data(), n_params)); // (resets the Adam state, restored next)
+      check(ctx, aleppo_import_optimizer(ctx, m1.data(), m2.data(), adam_step, n_params));
+      std::vector<double> rs(3 + E);
+      std::memcpy(rs.data(), sec(CK_REWARD_SCALE), rs.size() * 8);
+      check(ctx, aleppo_import_reward_scale(ctx, rs.data(), rs.data() + 3, E));
+      uint64_t words[ALEPPO_ROLLOUT_STATE_WORDS];
+      q = sec(CK_ROLLOUT);
+      take(q, words, sizeof(words));
+      check(ctx, aleppo_import_rollout_state(ctx, q, words, E));
+      q = sec(CK_TRAINER);
+      uint64_t u[4];
+      take(q, u, sizeof(u));
+      if (u[0] > cfg.num_rollouts || u[3] != u[0])
+        throw std::runtime_error("resume: checkpoint " + resume_file + " continues at rollout " + std::to_string(u[0]) +
+                                 ", this run has " + std::to_string(cfg.num_rollouts));
+      first_rollout = (size_t)u[0];
+      total_steps = (size_t)u[1];
+      episodes = (size_t)u[2];
+      take(q, &kl_beta, 4);
+      take(q, start_cpu.data(), E);
+      take(q, term.data(), E);
+      take(q, trunc.data(), E);
+      take(q, game_over.data(), E);
+      take(q, rewards.data(), E * 4);
+      take(q, ep_ret.data(), E * 4);
+      take(q, game_ret.data(), E * 4);
+      std::vector<uint64_t> l64(E);
+      take(q, l64.data(), E * 8);
+      std::copy(l64.begin(), l64.end(), ep_len.begin());
+      take(q, l64.data(), E * 8);
+      std::copy(l64.begin(), l64.end(), game_len.begin());
+      for (SyntheticAtari &e : envs) {
+        e.load(q);
+        q += SyntheticAtari::state_bytes;
+      }
+      uint64_t want[ALEPPO_DIGEST_COUNT], got[ALEPPO_DIGEST_COUNT];
+      std::memcpy(want, sec(CK_DIGEST), sizeof(want));
+      check(ctx, aleppo_state_digest(ctx, got));
+      for (int k = 0; k < ALEPPO_DIGEST_COUNT; ++k)
+        if (want[k] != got[k]) {
+          char b[160];
+          std::snprintf(b, sizeof b, ": the %s digest after the import is %016llx, the file recorded %016llx",
+                        DIGEST_NAMES[k], (unsigned long long)got[k], (unsigned long long)want[k]);
+          throw std::runtime_error("resume: checkpoint " + resume_file + b);
+        }
+      std::cout << "resumed from " << resume_file << " at rollout " << first_rollout << " of " << cfg.num_rollouts
+                << ", state digest verified" << std::endl;
+    } else {
+      rollout(); // the warm rollout before the loop (train.cc:391-396): collected, never trained on
+    }
+    // test hook: stop (cleanly) right after the checkpoint that continues at this rollout index, as an interruption would
+    const long stop_after = std::getenv("ALEPPO_TRAINER_STOP_AFTER_CHECKPOINT")
+                                ? std::atol(std::getenv("ALEPPO_TRAINER_STOP_AFTER_CHECKPOINT"))
+                                : -1;
+    size_t rollouts_done = first_rollout;
     const auto t_begin = std::chrono::steady_clock::now();
     const size_t nmb = (size_t)cfg.num_mini_batches, N = E * T;
     // metrics of every epoch that ran: per minibatch, and the per-sample planes of log_data's histograms ([epochs][N])
@@ -1228,7 +1533,7 @@ int main(int argc, char **argv) {
                                                            {ALEPPO_M_ENTROPIES, "entropies"},
                                                            {ALEPPO_M_RATIO, "ratios"}};
     std::vector<std::vector<float>> planes(5, std::vector<float>((size_t)cfg.num_epochs * N));
-    for (size_t r = 0; r < cfg.num_rollouts; ++r) {
+    for (size_t r = first_rollout; r < cfg.num_rollouts; ++r) {
       std::cout << "Rollout " << r + 1 << " of " << cfg.num_rollouts << std::endl;
       const double lr = cfg.learning_rate * (1.0 - r / static_cast<double>(cfg.num_rollouts)); // train.cc:424-428
       const Log log = rollout();
@@ -1385,6 +1690,15 @@ int main(int argc, char **argv) {
         logger.add_histogram("returns", step, gather(ret, 1));
       }
       logger.flush();
+      rollouts_done = r + 1;
+      if (!ckpt_file.empty() && (r + 1 == cfg.num_rollouts ||
+                                 (cfg.checkpoint_interval > 0 && (r + 1) % (size_t)cfg.checkpoint_interval == 0))) {
+        save_checkpoint(r + 1);
+        if (stop_after == (long)(r + 1)) {
+          std::cout << "stopped after the checkpoint of rollout " << r + 1 << std::endl;
+          break;
+        }
+      }
     }
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
     size_t pending_starts = 0; // environments whose next slot is an episode-start slot
@@ -1393,7 +1707,8 @@ int main(int argc, char **argv) {
     // total_steps counts only non-start slots (rollout.cc:225,266): slots = steps + start slots, and the start slots are
     // the E initial ones plus one per finished episode, minus those still pending
     std::cout << "steps " << total_steps << " episodes " << episodes << " pending_starts " << pending_starts << " slots "
-              << (cfg.num_rollouts + 1) * E * T << " env-steps/s " << (double)(cfg.num_rollouts * E * T) / secs << std::endl;
+              << (rollouts_done + 1) * E * T << " env-steps/s " << (double)((rollouts_done - first_rollout) * E * T) / secs
+              << std::endl;
     if (prof.on()) {
       prof.device_summary(ctx);
       prof.save();
