@@ -396,6 +396,9 @@ extern "C" int aleppo_create(const aleppo_config *cfg, aleppo_ctx **out) {
   CK(dalloc(&c->slab, c->slab_floats * 4, c->stream));
   CK(dalloc(&c->sumsq_part, 1024 * 4, c->stream));
   CK(dalloc(&c->adv_stats, 64, c->stream));
+  // the hyper-parameter block of ALEPPO_OPT_CLIP_PARAM and its kin, filled and uploaded at each aleppo_train
+  CK(dalloc(&c->hyper_blk, HYPER_BLOCK * 4, c->stream));
+  CK(hipHostMalloc(reinterpret_cast<void **>(&c->h_hyper_blk), HYPER_BLOCK * 4, hipHostMallocDefault));
   CK(hipStreamSynchronize(c->stream)); // (own streams only: see dalloc)
 #undef CK
   *out = c;
@@ -603,8 +606,7 @@ extern "C" int aleppo_set_option(aleppo_ctx *c, int option, int value) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   // a captured update holds the kernels the switches selected when it was recorded: any change re-arms the capture -
   // except beta (ALEPPO_OPT_KL_COEF) and the five hyper-parameter options, device values uploaded at each aleppo_train,
-  // which a replay reads as they are.  (The FIRST of those five to be set moves the context to the device-block entry
-  // points: that is a different graph key, hyper_dev, so the next update runs eagerly and the one after is captured anew.)
+  // which a replay reads as they are
   const bool hyper_opt = option == ALEPPO_OPT_CLIP_PARAM || option == ALEPPO_OPT_VALUE_CLIP_RANGE ||
                          option == ALEPPO_OPT_VALUE_LOSS_COEF || option == ALEPPO_OPT_ENTROPY_COEF ||
                          option == ALEPPO_OPT_MAX_GRAD_NORM;
@@ -687,7 +689,6 @@ extern "C" int aleppo_set_option(aleppo_ctx *c, int option, int value) {
       c->hyper.c_e = f;
     else
       c->hyper.max_norm = f;
-    c->hyper_dev = true; // from now on the update's head and Adam kernels read all of them from the device block
   } else if (option == ALEPPO_OPT_UPDATE_GRAPH)
     c->update_graph = value != 0;
   else if (option == ALEPPO_OPT_GATE_TIMEOUT_MS)

@@ -334,7 +334,7 @@ extern "C" int aleppo_ppo_loss(int dev, const float *logits, const float *old_lp
   for (int64_t k = 0; k <= A; ++k)
     Wh[(size_t)k * H + k] = 1.0f;
   const int nblk = (int)std::min<int64_t>(MAXS_HEAD, (B + 15) / 16);
-  DevBuf dh_in, dW, db, ol, ac, ad, re, ma, cnt, dh_out, ps, sw, sb, red;
+  DevBuf dh_in, dW, db, ol, ac, ad, re, ma, cnt, dh_out, ps, sw, sb, red, hyp;
   OPCHK(dh_in.up(h.data(), h.size() * 4));
   OPCHK(dW.up(Wh.data(), Wh.size() * 4));
   OPCHK(db.up(bh.data(), bh.size() * 4));
@@ -349,6 +349,9 @@ extern "C" int aleppo_ppo_loss(int dev, const float *logits, const float *old_lp
   OPCHK(sw.up(nullptr, (size_t)nblk * (A + 1) * H * 4));
   OPCHK(sb.up(nullptr, (size_t)nblk * (A + 1) * 4));
   OPCHK(red.up(nullptr, 8 * 4));
+  float hblk[HYPER_BLOCK] = {}; // the kernel reads its hyper-parameters from a device block (common.hpp HYPER_*)
+  hblk[HYPER_CLIP] = clip, hblk[HYPER_VCLIP] = clip, hblk[HYPER_CV] = c_v, hblk[HYPER_CE] = c_e;
+  OPCHK(hyp.up(hblk, sizeof(hblk)));
   launch_mask_count(op.st, ma.as<uint8_t>(), cnt.as<float>(), B, 1); // losses.cc:19 masks.sum()
   float *p = ps.as<float>();
   HeadTrainArgs ha{}; // (hparts = 1, float planes: the struct's defaults)
@@ -377,7 +380,7 @@ extern "C" int aleppo_ppo_loss(int dev, const float *logits, const float *old_lp
   ha.B = B;
   ha.H = H;
   ha.A = (int)A;
-  launch_head_train(op.st, ha, Hyper{clip, c_v, c_e, 0.f});
+  launch_head_train(op.st, ha, hyp.as<float>());
   launch_metrics_reduce(op.st, p, (size_t)B, ma.as<uint8_t>(), B, 1, 1, red.as<float>());
   OPCHK(op.sync());
   float r8[8];

@@ -93,15 +93,6 @@ static int ensure_kl_storage(aleppo_ctx *c) {
   return ALEPPO_OK;
 }
 
-// ALEPPO_OPT_CLIP_PARAM and its kin: the device block of the hyper-parameters (allocated once, never moved: graphs bake it)
-static int ensure_hyper_storage(aleppo_ctx *c) {
-  if (!c->hyper_blk) {
-    HIPCHK(c, dalloc(&c->hyper_blk, HYPER_BLOCK * 4, c->stream));
-    HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_hyper_blk), HYPER_BLOCK * 4, hipHostMallocDefault));
-  }
-  return ALEPPO_OK;
-}
-
 // ALEPPO_OPT_VALUE_CLIP: the env-major old-values plane, RT [E*T] (allocated on first use, never moved: graphs bake it)
 int aleppo::ensure_val_storage(aleppo_ctx *c) {
   if (!c->val_n)
@@ -169,11 +160,11 @@ struct Planes {
 struct UpdatePlan {
   int epochs, M, nm; // nm = epochs * M optimizer steps
   long N, B;
-  bool shuffle, vclip, val_transpose, advn, klpen, hyper_dev, dp, two, bwd_fused, fuse_tail;
+  bool shuffle, vclip, val_transpose, advn, klpen, dp, two, bwd_fused, fuse_tail;
   hipStream_t s, sw; // main stream; stream of the weight-gradient kernels (== s unless two)
   ncclComm_t comm;
-  // The hyper-parameters of this call: kernel arguments - or, once one of ALEPPO_OPT_CLIP_PARAM and its kin was set, the
-  // device block hpd, which the *_dev_kernel entry points of the head and of Adam read (a captured update follows it)
+  // The hyper-parameters of this call (ALEPPO_OPT_CLIP_PARAM and its kin), and the device block they are uploaded to:
+  // the head and Adam kernels read them there, so a captured update follows them
   Hyper hp;
   const float *hpd;
   int shuf_h, nblk_head, nblk_sq;
@@ -233,10 +224,7 @@ static int plan_update(aleppo_ctx *c, int epochs, int M, UpdatePlan *plan) {
     HIPCHK(c, hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking));
   p.s = c->stream;
   p.hp = c->hyper;
-  p.hyper_dev = c->hyper_dev;
-  if (p.hyper_dev && (rc = ensure_hyper_storage(c)))
-    return rc;
-  p.hpd = p.hyper_dev ? c->hyper_blk : nullptr;
+  p.hpd = c->hyper_blk;
   p.shuf_h = feistel_half_width(N);
 
   p.sW1 = c->slab + c->slab_off[0], p.sB1 = c->slab + c->slab_off[1], p.sW2 = c->slab + c->slab_off[2];
@@ -291,16 +279,15 @@ static int upload_call_scalars(aleppo_ctx *c, const UpdatePlan &p, double lr) {
     c->h_adam_sched[2 * i + 1] = (float)std::sqrt(1.0 - std::pow(b2, t));
   }
   HIPCHK(c, hipMemcpyAsync(c->adam_sched, c->h_adam_sched, (size_t)p.nm * 8, hipMemcpyHostToDevice, s));
-  if (p.hyper_dev) { // ... and the hyper-parameter block, for the same reason
-    float *b = c->h_hyper_blk;
-    std::memset(b, 0, HYPER_BLOCK * 4);
-    b[HYPER_CLIP] = p.hp.clip;
-    b[HYPER_VCLIP] = c->vclip_range_set ? c->value_clip_range : p.hp.clip;
-    b[HYPER_CV] = p.hp.c_v;
-    b[HYPER_CE] = p.hp.c_e;
-    b[HYPER_MAX_NORM] = p.hp.max_norm;
-    HIPCHK(c, hipMemcpyAsync(c->hyper_blk, c->h_hyper_blk, HYPER_BLOCK * 4, hipMemcpyHostToDevice, s));
-  }
+  // ... and the hyper-parameter block, for the same reason
+  float *b = c->h_hyper_blk;
+  std::memset(b, 0, HYPER_BLOCK * 4);
+  b[HYPER_CLIP] = p.hp.clip;
+  b[HYPER_VCLIP] = c->vclip_range_set ? c->value_clip_range : p.hp.clip;
+  b[HYPER_CV] = p.hp.c_v;
+  b[HYPER_CE] = p.hp.c_e;
+  b[HYPER_MAX_NORM] = p.hp.max_norm;
+  HIPCHK(c, hipMemcpyAsync(c->hyper_blk, c->h_hyper_blk, HYPER_BLOCK * 4, hipMemcpyHostToDevice, s));
   // ... and, with ALEPPO_OPT_KL_PENALTY, beta: the head kernel reads it from device memory for the same reason
   if (p.klpen) {
     std::memcpy(c->h_kl_beta, &c->kl_coef_bits, 4);
@@ -393,10 +380,7 @@ static void enqueue_head(aleppo_ctx *c, const UpdatePlan &p, int ep, int mb, int
   ha.advs = p.advn ? c->advn_stats + pl.record(ep, mb) * 4 : nullptr;
   ha.klb = p.klpen ? c->kl_beta : nullptr;
   ha.ps_kle = p.klpen ? c->kl_ps + (size_t)mi * p.B : nullptr;
-  if (p.hpd)
-    launch_head_train_dev(p.s, ha, p.hpd);
-  else
-    launch_head_train(p.s, ha, p.hp);
+  launch_head_train(p.s, ha, p.hpd);
   prof_end(c, ALEPPO_K_HEAD);
 }
 
@@ -557,8 +541,8 @@ static int enqueue_minibatch(aleppo_ctx *c, const UpdatePlan &p, int ep, int mb)
   const int nblk_norm = launch_sumsq(s, c->G, (long)L.off[P_W1], c->sumsq_part, p.nblk_sq, tail);
   // (the Adam kernel also writes the bf16 compute copy and the dgrad-side transposed layouts W2d / W3d / WfcT)
   launch_adam(s, c->P, c->G, nullptr, c->M1, c->M2, c->prec == ALEPPO_BF16 ? c->Pc : nullptr, c->WfcT, c->W3d, c->W2d, L,
-              prec, c->sumsq_part, nblk_norm, p.hp.max_norm, c->adam_sched + 2 * mi, c->cfg.adam_beta1,
-              c->cfg.adam_beta2, c->cfg.adam_eps, c->grad_norms + mi, p.hpd);
+              prec, c->sumsq_part, nblk_norm, p.hpd, c->adam_sched + 2 * mi, c->cfg.adam_beta1, c->cfg.adam_beta2,
+              c->cfg.adam_eps, c->grad_norms + mi);
   prof_end(c, ALEPPO_K_ADAM);
   return ALEPPO_OK;
 }
@@ -605,7 +589,6 @@ static Ctx::GraphKey graph_key(const UpdatePlan &p, const aleppo_ctx *c) {
   key.advn = p.advn ? c->advn_stats : nullptr;
   key.klpen = p.klpen ? 1 : 0;
   key.kl_ps = p.klpen ? c->kl_ps : nullptr;
-  key.hyper_dev = p.hyper_dev ? 1 : 0;
   return key;
 }
 

@@ -65,9 +65,10 @@ struct ProfClass {
 struct Hyper {
   float clip, c_v, c_e, max_norm;
 };
-// The same numbers as a DEVICE block (ALEPPO_OPT_CLIP_PARAM, ALEPPO_OPT_VALUE_CLIP_RANGE, ALEPPO_OPT_VALUE_LOSS_COEF,
-// ALEPPO_OPT_ENTROPY_COEF, ALEPPO_OPT_MAX_GRAD_NORM): float [HYPER_BLOCK], 16-byte aligned.  The head kernels read slots
-// 0-3 as one 16-byte load, the Adam kernel slot 4.
+// The kernels read them, and the value-clip range, from a DEVICE block (ALEPPO_OPT_CLIP_PARAM, ALEPPO_OPT_VALUE_CLIP_RANGE,
+// ALEPPO_OPT_VALUE_LOSS_COEF, ALEPPO_OPT_ENTROPY_COEF, ALEPPO_OPT_MAX_GRAD_NORM): float [HYPER_BLOCK], 16-byte aligned,
+// uploaded in front of every update, so that a captured update follows values changed between calls.  The head kernels
+// read slots 0-3 as one 16-byte load, the Adam kernel slot 4.
 enum { HYPER_CLIP = 0, HYPER_VCLIP = 1, HYPER_CV = 2, HYPER_CE = 3, HYPER_MAX_NORM = 4, HYPER_BLOCK = 8 };
 
 // Kernel-selection switches of ONE context (aleppo_set_option; initial values from the environment, read once in
@@ -204,12 +205,11 @@ struct Ctx {
   float *kl_beta = nullptr, *h_kl_beta = nullptr; // [1] beta, uploaded at each aleppo_train (device / pinned)
   bool last_kl = false;                          // the last aleppo_train ran with the option (kl_ps / slot 8 hold it)
   // ---- ALEPPO_OPT_CLIP_PARAM / _VALUE_CLIP_RANGE / _VALUE_LOSS_COEF / _ENTROPY_COEF / _MAX_GRAD_NORM: the current values
-  // (from the config until set), and - from the first set on - the device block the update's kernels read them from
+  // (from the config until set), and the device block the update's kernels read them from (aleppo_create; never moved)
   Hyper hyper{};                                 // current clip range, coefficients and norm limit
   float value_clip_range = 0.f;                  // ALEPPO_OPT_VALUE_CLIP_RANGE; follows hyper.clip until set itself
   bool vclip_range_set = false;
   float last_max_norm = 0.f;                     // hyper.max_norm of the last aleppo_train (aleppo_export_grads)
-  bool hyper_dev = false;                        // one of the five was set: the *_dev_kernel entry points from now on
   float *hyper_blk = nullptr, *h_hyper_blk = nullptr; // [HYPER_BLOCK], uploaded at each aleppo_train (device / pinned)
   // ---- ALEPPO_OPT_REWARD_SCALE / _CLIP: device storage allocated on first use (ensure_rs_storage), never moved
   bool reward_scale = false;
@@ -232,11 +232,10 @@ struct Ctx {
     const void *advn = nullptr;  // ALEPPO_OPT_ADV_NORM_MINIBATCH: the statistics storage (nullptr: off)
     int klpen = 0;               // ALEPPO_OPT_KL_PENALTY (beta is a device value and not part of the key)
     const void *kl_ps = nullptr; // ... its per-sample plane (nullptr: off)
-    int hyper_dev = 0;           // the hyper-parameters come from the device block (its values are not part of the key)
     bool operator==(const GraphKey &o) const {
       return epochs == o.epochs && M == o.M && two == o.two && N == o.N && metric_ps == o.metric_ps &&
              metric_red == o.metric_red && order == o.order && vclip == o.vclip && advn == o.advn &&
-             klpen == o.klpen && kl_ps == o.kl_ps && hyper_dev == o.hyper_dev;
+             klpen == o.klpen && kl_ps == o.kl_ps;
     }
   } graph_key, warm_key;
   long graph_replays = 0;
@@ -377,9 +376,8 @@ struct HeadTrainArgs {
   const float *advs = nullptr, *klb = nullptr;
   float *ps_kle = nullptr;
 };
-void launch_head_train(hipStream_t s, const HeadTrainArgs &a, Hyper hp);
-// the same with hp = the device block of the hyper-parameter options (slots HYPER_CLIP .. HYPER_CE; head_hyper.hip)
-void launch_head_train_dev(hipStream_t s, const HeadTrainArgs &a, const float *hp);
+// hp: the device block of the hyper-parameter options (slots HYPER_CLIP .. HYPER_CE; head_train.hip)
+void launch_head_train(hipStream_t s, const HeadTrainArgs &a, const float *hp);
 struct ReduceSeg {
   const float *slab;
   int S;
@@ -395,10 +393,9 @@ int launch_sumsq(hipStream_t s, float *G, long n_main, float *partials, int nblk
 // layouts WfcT / W3d / W2d (both precisions) from the updated parameters in the same pass
 void launch_adam(hipStream_t s, float *P, const float *G_in, float *G_out_scaled, float *M1, float *M2, void *Pc,
                  void *WfcT, void *W3d, void *W2d, const ParamLayout &L, int prec, const float *partials, int nblk,
-                 float max_norm,
+                 const float *hpd,   // the device block of the hyper-parameter options: slot HYPER_MAX_NORM is the limit
                  const float *sched, // device: { lr / (1 - beta1^t), sqrt(1 - beta2^t) } of this step
-                 float beta1, float beta2, float eps, float *grad_norm_out,
-                 const float *hpd = nullptr); // the device block: slot HYPER_MAX_NORM replaces max_norm (adam_dev_kernel)
+                 float beta1, float beta2, float eps, float *grad_norm_out);
 void launch_pack_dgrad(hipStream_t s, const float *P, const ParamLayout &L, void *W2d, void *W3d, void *WfcT,
                        int prec);
 void launch_cast_params(hipStream_t s, const float *P, void *Pc, long n);

@@ -1,0 +1,92 @@
+// head_train.hip - the PPO head training kernel's three __global__ entry points and their launcher (the kernel itself is
+// described in kernels.hip, "PPO head, training"; its body is head_train_body.inc).  A translation unit of its own: the
+// 96 instantiations compile next to kernels.hip.
+#include "head_train.hpp"
+
+namespace aleppo {
+
+template <class T, int AMAX, class RT, bool VCLIP>
+__global__ __launch_bounds__(AMAX > 10 ? 256 : 512) void head_train_kernel(HEAD_PARAMS) {
+  constexpr bool ADVN = false, KLPEN = false;
+  const float *advs = nullptr, *klb = nullptr;
+  float *ps_kle = nullptr;
+#include "head_train_body.inc"
+}
+// advs: float [4] of this minibatch (mean_f, inv_f, std, 0)
+template <class T, int AMAX, class RT, bool VCLIP>
+__global__ __launch_bounds__(AMAX > 10 ? 256 : 512) void head_train_advn_kernel(HEAD_PARAMS,
+                                                                                 const float *__restrict__ advs) {
+  constexpr bool ADVN = true, KLPEN = false;
+  const float *klb = nullptr;
+  float *ps_kle = nullptr;
+#include "head_train_body.inc"
+}
+// advs: as above, or nullptr (no minibatch normalisation); klb: float [1], beta; ps_kle: float [B], the exact KL per row
+template <class T, int AMAX, class RT, bool VCLIP>
+__global__ __launch_bounds__(64 * head_waves(AMAX, true)) void head_train_kl_kernel(HEAD_PARAMS,
+                                                                                    const float *__restrict__ advs,
+                                                                                    const float *__restrict__ klb,
+                                                                                    float *ps_kle) {
+  constexpr bool ADVN = true, KLPEN = true;
+#define HEAD_TRAIN_PASSES
+#include "head_train_body.inc"
+#undef HEAD_TRAIN_PASSES
+}
+
+template <class T, int AM, class RT, bool VCLIP>
+static void head_train_launch(hipStream_t s, const HeadTrainArgs &a, const float *hp) {
+  const int H = a.H;
+  const size_t sm = ((size_t)((AM + 1) + ((AM + 1) > 8 ? (AM + 1) : 8)) * H + 8 * (AM + 1)) * sizeof(float);
+  const void *fn = a.klb    ? reinterpret_cast<const void *>(&head_train_kl_kernel<T, AM, RT, VCLIP>)
+                   : a.advs ? reinterpret_cast<const void *>(&head_train_advn_kernel<T, AM, RT, VCLIP>)
+                            : reinterpret_cast<const void *>(&head_train_kernel<T, AM, RT, VCLIP>);
+  if (sm > 48 * 1024)
+    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
+#define HEAD_ARGS                                                                                                      \
+  a.h, a.Wh, a.bh, a.act, static_cast<const RT *>(a.oldlp), static_cast<const RT *>(a.adv),                            \
+      static_cast<const RT *>(a.ret), static_cast<const RT *>(a.vold), a.mask, a.mask_count, hp,                       \
+      static_cast<T *>(a.dh), a.ps_total, a.ps_clipped, a.ps_value, a.ps_entropy, a.ps_ratio, a.ps_kl, a.ps_cf,        \
+      a.slab_w, a.slab_b, a.B, a.H, a.A, a.logits_out, a.values_out, a.hparts
+  if (a.klb)
+    hipLaunchKernelGGL((head_train_kl_kernel<T, AM, RT, VCLIP>), dim3(a.nblk), dim3(64 * head_waves(AM, true)), sm, s,
+                       HEAD_ARGS, a.advs, a.klb, a.ps_kle);
+  else if (a.advs)
+    hipLaunchKernelGGL((head_train_advn_kernel<T, AM, RT, VCLIP>), dim3(a.nblk), dim3(AM > 10 ? 256 : 512), sm, s,
+                       HEAD_ARGS, a.advs);
+  else
+    hipLaunchKernelGGL((head_train_kernel<T, AM, RT, VCLIP>), dim3(a.nblk), dim3(AM > 10 ? 256 : 512), sm, s,
+                       HEAD_ARGS);
+#undef HEAD_ARGS
+}
+template <class T, class RT, bool VCLIP>
+static void head_train_amax(hipStream_t s, const HeadTrainArgs &a, const float *hp) {
+  if (a.A <= 4)
+    head_train_launch<T, 4, RT, VCLIP>(s, a, hp);
+  else if (a.A <= 6)
+    head_train_launch<T, 6, RT, VCLIP>(s, a, hp);
+  else if (a.A <= 10)
+    head_train_launch<T, 10, RT, VCLIP>(s, a, hp);
+  else
+    head_train_launch<T, 18, RT, VCLIP>(s, a, hp);
+}
+template <class T, class RT> static void head_train_vclip(hipStream_t s, const HeadTrainArgs &a, const float *hp) {
+  if (a.vold)
+    head_train_amax<T, RT, true>(s, a, hp);
+  else
+    head_train_amax<T, RT, false>(s, a, hp);
+}
+void launch_head_train(hipStream_t s, const HeadTrainArgs &a, const float *hp) {
+  if (a.prec == ALEPPO_BF16) {
+    if (a.rt16)
+      head_train_vclip<bf16, f16>(s, a, hp);
+    else
+      head_train_vclip<bf16, float>(s, a, hp);
+  } else {
+    if (a.rt16)
+      head_train_vclip<float, f16>(s, a, hp);
+    else
+      head_train_vclip<float, float>(s, a, hp);
+  }
+}
+
+} // namespace aleppo

@@ -1,6 +1,5 @@
-// head_train.hpp - what the translation units that instantiate the PPO head training kernel share (kernels.hip: the
-// hyper-parameters as a kernel argument; head_hyper.hip: the hyper-parameters in a device block).  The entry points
-// themselves are head_train_entry.inc, their body head_train_body.inc.
+// head_train.hpp - what head_train.hip (the PPO head training kernel's entry points; their body is head_train_body.inc)
+// shares with kernels.hip: the rollout-plane type, the wave sum and the kernel's waves per workgroup.
 #pragma once
 #include "common.hpp"
 #include "gemm.hpp" // bf16 / vector typedefs
@@ -20,13 +19,13 @@ __device__ __forceinline__ float wave_sum(float v) {
 
 // Waves per workgroup of the head training kernel (kernels.hip, "PPO head, training")
 constexpr int head_waves(int amax, bool klpen) { return amax > 10 || (klpen && amax > 6) ? 4 : 8; }
-// hp: HEAD_HP_T is Hyper (by value), or `const float *__restrict__`, the device block of common.hpp's HYPER_* slots
+// The parameters the three entry points share.  hp: the device block of common.hpp's HYPER_* slots
 #define HEAD_PARAMS                                                                                                    \
   const float *__restrict__ h, const float *__restrict__ Wh, const float *__restrict__ bh, const int *__restrict__ act, \
       const RT *__restrict__ oldlp, const RT *__restrict__ adv, const RT *__restrict__ ret,                            \
       const RT *__restrict__ vold, const uint8_t *__restrict__ mask, const float *__restrict__ mask_count,             \
-      HEAD_HP_T hp, T *dh, float *ps_total, float *ps_clipped, float *ps_value, float *ps_entropy, float *ps_ratio,    \
-      float *ps_kl, float *ps_cf, float *slab_w, float *slab_b, long B, int H, int A, float *logits_out,               \
-      float *values_out, int hparts
+      const float *__restrict__ hp, T *dh, float *ps_total, float *ps_clipped, float *ps_value, float *ps_entropy,     \
+      float *ps_ratio, float *ps_kl, float *ps_cf, float *slab_w, float *slab_b, long B, int H, int A,                 \
+      float *logits_out, float *values_out, int hparts
 
 } // namespace aleppo

@@ -1,5 +1,5 @@
-// head_train_body.inc - the body of the PPO head training kernel (kernels.hip), included by its three __global__ entry
-// points: head_train_kernel (ADVN = false), head_train_advn_kernel (ADVN = true, ALEPPO_OPT_ADV_NORM_MINIBATCH) and
+// head_train_body.inc - the body of the PPO head training kernel, included by the three __global__ entry points of
+// head_train.hip: head_train_kernel (ADVN = false), head_train_advn_kernel (ADVN = true, ALEPPO_OPT_ADV_NORM_MINIBATCH),
 // head_train_kl_kernel (KLPEN = true, ALEPPO_OPT_KL_PENALTY; there `advs` may be null, which leaves the advantages as
 // stored).  The text is shared this way, not through a __device__ function, because inlining a function changed the
 // register allocation of the default kernels (AMAX = 18: 336 instead of 402 VGPRs); included into the kernel, the
@@ -59,7 +59,9 @@
     sW[i] = Wh[i];
   __syncthreads();
   const float inv_nm = 1.0f / mask_count[0];
-  HEAD_HYPER_LOAD
+  // the clip range, the value-clip range and the two loss coefficients: slots 0-3 of the device block, one 16-byte load
+  const f32x4 hpv = *reinterpret_cast<const f32x4 *>(hp);
+  const float hp_clip = hpv[HYPER_CLIP], hp_vclip = hpv[HYPER_VCLIP], hp_cv = hpv[HYPER_CV], hp_ce = hpv[HYPER_CE];
   float kl_beta = 0.f;
   if constexpr (KLPEN)
     kl_beta = klb[0]; // ALEPPO_OPT_KL_COEF: a device value, so that a graph replay follows a beta changed between calls

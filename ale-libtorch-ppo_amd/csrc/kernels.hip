@@ -1171,16 +1171,9 @@ void launch_shuffle_gather(hipStream_t s, const uint32_t *rk, int h, long N, int
 // head_train_kl_kernel (KLPEN on, with advantage normalisation a run-time switch: advs may be null).
 // Waves per workgroup: 8, or 4 where one wave per SIMD needs more than 256 registers - the wide action sets, and with
 // the KL penalty (its S / KL pass and the q_a of the gradient) from AMAX = 10 on (8 waves spilled ~40 registers there).
-// The entry points and their launcher are the text of head_train_entry.inc, instantiated twice: here with the hyper-
-// parameters as a kernel argument (the default route), and in head_hyper.hip with the device block of
-// ALEPPO_OPT_CLIP_PARAM and its kin (head_train_dev_kernel / head_train_advn_dev_kernel / head_train_kl_dev_kernel).
-#define HEAD_KERNEL head_train_kernel
-#define HEAD_ADVN_KERNEL head_train_advn_kernel
-#define HEAD_KL_KERNEL head_train_kl_kernel
-#define HEAD_LAUNCH launch_head_train
-#define HEAD_HP_T Hyper
-#define HEAD_HYPER_LOAD const float hp_clip = hp.clip, hp_vclip = hp.clip, hp_cv = hp.c_v, hp_ce = hp.c_e;
-#include "head_train_entry.inc"
+// The clip range, the value-clip range and the two loss coefficients are slots 0-3 of the device block of
+// ALEPPO_OPT_CLIP_PARAM and its kin (common.hpp HYPER_*), read once per workgroup: a captured update follows values changed
+// between calls.  The entry points and their launcher, launch_head_train, are head_train.hip.
 
 // ================================================================================================
 // Split-K slab reduction -> flat gradient (fixed summation order => run-to-run deterministic).
@@ -1383,29 +1376,125 @@ struct AdamTiles {
   int first[4];     // first tile index of each tensor (+ total)
   int H;
 };
+// hpd: the device block of the hyper-parameter options (common.hpp HYPER_*): slot HYPER_MAX_NORM is the gradient-norm
+// limit, a device value so that a captured update follows ALEPPO_OPT_MAX_GRAD_NORM
 template <class T>
 __global__ __launch_bounds__(256) void adam_kernel(float *P, const float *__restrict__ G, float *Gs, float *M1, float *M2,
                                                     T *Pc, T *WfcT, T *W3d, T *W2d, AdamTiles tl, long n_flat,
                                                     long4_ranges fr, const float *__restrict__ partials, int nblk,
-                                                    float max_norm, const float *__restrict__ sched, float beta1,
-                                                    float beta2, float eps, float *grad_norm_out) {
-#include "adam_body.inc"
-}
-// hpd: the device block of the hyper-parameter options (common.hpp HYPER_*), read once per workgroup
-template <class T>
-__global__ __launch_bounds__(256) void adam_dev_kernel(float *P, const float *__restrict__ G, float *Gs, float *M1,
-                                                        float *M2, T *Pc, T *WfcT, T *W3d, T *W2d, AdamTiles tl,
-                                                        long n_flat, long4_ranges fr,
-                                                        const float *__restrict__ partials, int nblk,
-                                                        const float *__restrict__ hpd, const float *__restrict__ sched,
-                                                        float beta1, float beta2, float eps, float *grad_norm_out) {
+                                                    const float *__restrict__ hpd, const float *__restrict__ sched,
+                                                    float beta1, float beta2, float eps, float *grad_norm_out) {
   const float max_norm = hpd[HYPER_MAX_NORM];
-#include "adam_body.inc"
+  __shared__ float s4[4];
+  __shared__ float tile[64][65];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < nblk; i += 256)
+    s += partials[i];
+  s = block_sum_256(s, s4);
+  const float norm = sqrtf(s);
+  float coef = max_norm / (norm + 1e-6f); // train.cc:39
+  coef = fminf(coef, 1.0f);               // train.cc:40-41
+  if (blockIdx.x == 0 && threadIdx.x == 0 && grad_norm_out)
+    *grad_norm_out = norm;                // pre-clip norm is what the reference reports (Q9)
+  // lr / (1 - beta1^t) and sqrt(1 - beta2^t) of THIS optimizer step: device scalars (a captured hipGraph of the update
+  // follows the annealed rate and the step count; the reference's captured graph bakes both, train.h:163-195)
+  const AdamScalars a{coef, sched[0], sched[1], beta1, beta2, 1.0f - beta1, 1.0f - beta2, eps};
+  const int ntile = tl.first[3];
+  if ((int)blockIdx.x < ntile) { // a 64-row tile of Wfc / W3 / W2
+    const int t = blockIdx.x;
+    long src;      // flat index of tile element (0, 0)
+    int rs, rows, cols;
+    T *dst;        // transposed element (c, r) at dst[c * ds + r]
+    int ds;
+    if (t < tl.first[1]) {          // Wfc[o][j] -> WfcT[j][o]: tile (o-block, j-block of 64; 3136 = 49 * 64)
+      const int ob = t / 49, jb = t - ob * 49;
+      rs = FC_IN;
+      rows = min(64, tl.H - ob * 64);
+      cols = 64;
+      src = tl.off[0] + (long)ob * 64 * FC_IN + jb * 64;
+      dst = WfcT + (long)jb * 64 * tl.H + ob * 64;
+      ds = tl.H;
+    } else if (t < tl.first[2]) {   // W3[oc][tap][c] -> W3d[c][tap][oc]: one tile per tap
+      const int tap = t - tl.first[1];
+      rs = 576;
+      rows = 64;
+      cols = 64;
+      src = tl.off[1] + tap * 64;
+      dst = W3d + tap * 64;
+      ds = 576;
+    } else {                        // W2[oc][(kh,kw)][c] -> W2d[class][c][(ab)][oc]: one 64 x 32 tile per (kh, kw)
+      const int k = t - tl.first[2], kh = k >> 2, kw = k & 3;
+      const int cls = (kh & 1) * 2 + (kw & 1), ab = (kh >> 1) * 2 + (kw >> 1);
+      rs = 512;
+      rows = 64;
+      cols = 32;
+      src = tl.off[2] + k * 32;
+      dst = W2d + cls * (32 * 256) + ab * 64;
+      ds = 256;
+    }
+    const int c = threadIdx.x & 63, r4 = threadIdx.x >> 6;
+    if (c < cols) {
+      // all 64 loads of a thread's 16 elements are issued before the first store (P / M1 / M2 are read and written through
+      // the same pointers, so the compiler may not hoist them itself; a dependent load-compute-store chain per element made
+      // this kernel latency-bound: 23 vs 13 us)
+      float g[16], m1[16], m2[16], p0[16];
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        const int r = r4 + 4 * k;
+        const long i = src + (long)(r < rows ? r : 0) * rs + c;
+        g[k] = G[i];
+        m1[k] = M1[i];
+        m2[k] = M2[i];
+        p0[k] = P[i];
+      }
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        const int r = r4 + 4 * k;
+        if (r < rows) {
+          const long i = src + (long)r * rs + c;
+          const float gg = g[k] * a.coef;
+          const float m = m1[k] * a.beta1 + a.omb1 * gg;
+          const float v = m2[k] * a.beta2 + a.omb2 * (gg * gg);
+          const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
+          const float p = p0[k] - a.step_size * (m / denom);
+          M1[i] = m;
+          M2[i] = v;
+          P[i] = p;
+          if (Gs)
+            Gs[i] = gg;
+          if (Pc)
+            Pc[i] = (T)p;
+          tile[r][c] = p;
+        }
+      }
+    }
+    __syncthreads();
+    const int r = threadIdx.x & 63, c4 = threadIdx.x >> 6;
+    if (r < rows)
+      for (int cc = c4; cc < cols; cc += 4)
+        dst[(long)cc * ds + r] = (T)tile[r][cc];
+    return;
+  }
+  // everything else, flat: index k of the compacted space of the (at most four) ranges between the tiled tensors
+  const long stride = (long)(gridDim.x - ntile) * 256;
+  for (long k = (long)((int)blockIdx.x - ntile) * 256 + threadIdx.x; k < n_flat; k += stride) {
+    long i = k;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      if (i < fr.len[q]) {
+        i += fr.begin[q];
+        break;
+      }
+      i -= fr.len[q];
+    }
+    const float p = adam_element(i, P, G, Gs, M1, M2, a);
+    if (Pc)
+      Pc[i] = (T)p;
+  }
 }
 void launch_adam(hipStream_t s, float *P, const float *G_in, float *G_out_scaled, float *M1, float *M2, void *Pc,
                  void *WfcT, void *W3d, void *W2d, const ParamLayout &L, int prec, const float *partials, int nblk,
-                 float max_norm, const float *sched, float beta1, float beta2, float eps, float *grad_norm_out,
-                 const float *hpd) {
+                 const float *hpd, const float *sched, float beta1, float beta2, float eps, float *grad_norm_out) {
   AdamTiles tl;
   tl.off[0] = (long)L.off[P_WFC];
   tl.off[1] = (long)L.off[P_W3];
@@ -1426,28 +1515,15 @@ void launch_adam(hipStream_t s, float *P, const float *G_in, float *G_out_scaled
     n_flat += fr.len[q];
   }
   const int nb = tl.first[3] + (int)std::min<long>((n_flat + 255) / 256, 1024);
-  if (hpd) {
-    if (prec == ALEPPO_BF16)
-      hipLaunchKernelGGL(adam_dev_kernel<bf16>, dim3(nb), dim3(256), 0, s, P, G_in, G_out_scaled, M1, M2,
-                         static_cast<bf16 *>(Pc), static_cast<bf16 *>(WfcT), static_cast<bf16 *>(W3d),
-                         static_cast<bf16 *>(W2d), tl, n_flat, fr, partials, nblk, hpd, sched, beta1, beta2, eps,
-                         grad_norm_out);
-    else
-      hipLaunchKernelGGL(adam_dev_kernel<float>, dim3(nb), dim3(256), 0, s, P, G_in, G_out_scaled, M1, M2,
-                         static_cast<float *>(nullptr), static_cast<float *>(WfcT), static_cast<float *>(W3d),
-                         static_cast<float *>(W2d), tl, n_flat, fr, partials, nblk, hpd, sched, beta1, beta2, eps,
-                         grad_norm_out);
-    return;
-  }
   if (prec == ALEPPO_BF16)
     hipLaunchKernelGGL(adam_kernel<bf16>, dim3(nb), dim3(256), 0, s, P, G_in, G_out_scaled, M1, M2,
                        static_cast<bf16 *>(Pc), static_cast<bf16 *>(WfcT), static_cast<bf16 *>(W3d),
-                       static_cast<bf16 *>(W2d), tl, n_flat, fr, partials, nblk, max_norm, sched, beta1, beta2, eps,
+                       static_cast<bf16 *>(W2d), tl, n_flat, fr, partials, nblk, hpd, sched, beta1, beta2, eps,
                        grad_norm_out);
   else
     hipLaunchKernelGGL(adam_kernel<float>, dim3(nb), dim3(256), 0, s, P, G_in, G_out_scaled, M1, M2,
                        static_cast<float *>(nullptr), static_cast<float *>(WfcT), static_cast<float *>(W3d),
-                       static_cast<float *>(W2d), tl, n_flat, fr, partials, nblk, max_norm, sched, beta1, beta2, eps,
+                       static_cast<float *>(W2d), tl, n_flat, fr, partials, nblk, hpd, sched, beta1, beta2, eps,
                        grad_norm_out);
 }
 

@@ -653,12 +653,10 @@ typedef enum {
      bits of the config value it stands for; there is no "unset", and setting the config's own value is allowed.
      The values are read at each aleppo_train and hold for the whole call (no schedule inside a call).  They are device
      values uploaded at the start of the call, next to Adam's step scalars: a captured update (ALEPPO_OPT_UPDATE_GRAPH)
-     follows values changed between calls, and setting one does not re-arm the capture.  A context on which none of the
-     five was ever set launches the kernels it always launched, with the numbers as kernel arguments, and uploads nothing;
-     from the first set on (of any of them, for all of them) it uses entry points of the head and Adam kernels that read
-     the numbers from device memory - the one switch of route a captured update is recorded anew for.  The arithmetic is
-     the same text: a context created with values X and one created with other values and set to X give bit-identical
-     parameters, Adam state, metrics, per-sample planes and gradients.  They work on every schedule the other options
+     follows values changed between calls, and setting one does not re-arm the capture.  Every context works this way,
+     whether one of the five was ever set or not: the head and Adam kernels read the numbers from device memory, and a
+     context created with values X and one created with other values and set to X give bit-identical parameters, Adam
+     state, metrics, per-sample planes and gradients.  They work on every schedule the other options
      work on: eager or captured, fp32 or bf16, fp32 or fp16 rollout planes, rollout and aleppo_set_batch batches, with
      ALEPPO_OPT_MINIBATCH_SHUFFLE, ALEPPO_OPT_VALUE_CLIP, ALEPPO_OPT_ADV_NORM_MINIBATCH and ALEPPO_OPT_KL_PENALTY in any
      combination, one GPU or data parallel.  With data parallelism EVERY RANK MUST SET THE SAME VALUES before the same

@@ -342,7 +342,7 @@ def test_value_clip_range_of_its_own(pkg):
             eng.set_hyper(value_clip_range=rng_v)
             assert eng.hyper()["value_clip_range"] == _f32(rng_v) and eng.hyper()["clip_param"] == _f32(clip)
         else:
-            eng.set_hyper(clip_param=clip)  # (the device-block route on both sides; the range follows the clip)
+            eng.set_hyper(clip_param=clip)  # (the same setter traffic on both sides; the range follows the clip)
             assert eng.hyper()["value_clip_range"] == _f32(clip)
         outs[name] = _read(eng, eng.train(LR, epochs, M), epochs, M)
         eng.close()
@@ -446,7 +446,7 @@ def test_a_schedule_under_the_captured_update(pkg, prec):
         eng.load_params(params)
         eng.set_batch(*batch, values=vold)
         _set_x(eng, X)
-        eng.train(LR, epochs, M)  # eager (warm-up of the device-block route)
+        eng.train(LR, epochs, M)  # eager (warm-up: the first call of a shape is never captured)
         eng.train(LR, epochs, M)  # graph: capture + first launch
         n0 = eng.get_option(pkg.OPT_UPDATE_GRAPH)
         assert n0 == (1 if graph else 0)

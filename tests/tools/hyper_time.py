@@ -1,11 +1,13 @@
-"""developer tool: cost of the device-block route of ALEPPO_OPT_CLIP_PARAM and its kin at the BASELINE configs[1] update
-shape (128 envs x T = 128, 4 epochs x 4 minibatches of 4096, bf16, rollout batch):
-`python tests/tools/hyper_time.py [reps]`.  Two contexts in one process on the same rollout, alternating per call: `off`
-never sets an option (hyper-parameters as kernel arguments, the default launches), `on` has all five set to the config's
-own values (head_train_dev_kernel / adam_dev_kernel and one extra 32-byte upload per call), so both do the same
-arithmetic.  (Two contexts, not one toggled: there is no way back from the device-block route.)  Two phases: the whole
-aleppo_train (host clock; it waits for the device before it returns) with profiling off, then the head and Adam
-kernels' device time (aleppo_profile_read, HIP events) with profiling on.  Prints one JSON line."""
+"""developer tool: what setting ALEPPO_OPT_CLIP_PARAM and its kin costs at the BASELINE configs[1] update shape (128
+envs x T = 128, 4 epochs x 4 minibatches of 4096, bf16, rollout batch): `python tests/tools/hyper_time.py [reps]
+[first]`.  Two contexts in one process on the same rollout, alternating per call: `off` never sets an option, `on` has
+all five set to the config's own values; `first` (`off`, the default, or `on`) names the one that is created, warmed up
+and timed first.  Both read the numbers from the device block that every aleppo_train uploads and launch the same
+kernels, so the two columns should agree within the scatter.  ALEPPO_LIB_PATH lets the same script time another build of
+the library: with one from before the kernel-argument entry points were removed, the `off` column is those entry points
+and the `on` column the device block.  Two phases: the whole aleppo_train (host clock; it waits for the device before it
+returns) with profiling off, then the head and Adam kernels' device time (aleppo_profile_read, HIP events) with
+profiling on.  Prints one JSON line."""
 import json
 import os
 import sys
@@ -24,7 +26,7 @@ E, T, A, H, M, EP = 128, 128, 4, 512, 4, 4
 dev = DeviceBytes(hf.hf_bytes(311, (T, E, 84, 84)))
 te, tr, st = _flags(312, T, E, 0.01, 0.0)
 engs = {}
-for name in ("off", "on"):
+for name in (("on", "off") if sys.argv[2:3] == ["on"] else ("off", "on")):
     eng = pkg.Engine(E, T, A, H, precision=pkg.BF16, max_minibatch=E * T // M)
     eng.load_params(hf.fill_params(310, H, A))
     eng.replay_rollout(dev.addr, pkg.FRAMES_84, E * 7056, hf.hf_range(313, (T, E), -1, 1), te, tr, st)
