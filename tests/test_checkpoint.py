@@ -124,10 +124,11 @@ def _final(stdout):
 
 
 def test_checkpoint_file_round_trip_and_refusals_without_a_gpu(trainer_stub, tmp_path):
-    """the host-only build: an interrupted and resumed run ends where the uninterrupted one does; the file appears under
-    its final name only, whole; truncated / corrupt / other-shape files and a digest that does not match are refused"""
+    """the host-only build: an interrupted and resumed run ends where the uninterrupted one does, down to the checkpoint
+    file it leaves after the last rollout; the file appears under its final name only, whole; truncated / corrupt / other-shape files and a digest that does not match are refused"""
     ck = tmp_path / "run.ckpt"
-    full = _run(trainer_stub, tmp_path, "", env=dict(ALEPPO_TRAINER_DUMP_FINAL=str(tmp_path / "full.bin")))
+    full = _run(trainer_stub, tmp_path, f"checkpoint_path: {tmp_path / 'full.ckpt'}\ncheckpoint_interval: 2\n",
+                env=dict(ALEPPO_TRAINER_DUMP_FINAL=str(tmp_path / "full.bin")))
     assert full.returncode == 0 and "Success" in full.stdout, full.stderr[-2000:]
     (tmp_path / "run.ckpt.tmp").write_bytes(b"a leftover of an interrupted write")
     keys = f"checkpoint_path: {ck}\ncheckpoint_interval: 2\n"
@@ -148,6 +149,9 @@ def test_checkpoint_file_round_trip_and_refusals_without_a_gpu(trainer_stub, tmp
     assert _final(res.stdout) == _final(full.stdout)
     assert (tmp_path / "resumed.bin").read_bytes() == (tmp_path / "full.bin").read_bytes()
     assert "checkpoint rollout 4 digest" in res.stdout  # (after the last rollout too; the file now continues at 4)
+    # ... and is, byte for byte, the file the uninterrupted run left after rollout 4: what the reader restores is what the
+    # writer wrote, for every field
+    assert ck.read_bytes() == (tmp_path / "full.ckpt").read_bytes()
     # a checkpoint that cannot be written is an error, and nothing is left under the final name
     gone = tmp_path / "no_such_dir" / "x.ckpt"
     r = _run(trainer_stub, tmp_path, f"checkpoint_path: {gone}\ncheckpoint_interval: 1\n")

@@ -25,6 +25,7 @@ import bf16_check as bc
 import hashfill as hf
 import oracle_lib as orc
 import value_clip_ref as vr
+import trainer_helpers
 from __graft_entry__ import load_package
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -105,12 +106,7 @@ def test_float_bits_conversions():
 
 @pytest.fixture(scope="module")
 def stub_trainer(tmp_path_factory):
-    """trainer/train.cc linked against the host-only library stand-in (tests/stub/aleppo_stub.cc), built out of tree"""
-    out = tmp_path_factory.mktemp("stub") / "train_stub"
-    cxx = os.environ.get("CXX", "g++")
-    subprocess.check_call([cxx, "-O1", "-std=c++17", "-pthread", os.path.join(ROOT, "trainer", "train.cc"),
-                           os.path.join(ROOT, "tests", "stub", "aleppo_stub.cc"), "-o", str(out)])
-    return str(out)
+    return trainer_helpers.build_stub_trainer(tmp_path_factory)
 
 
 def _debug_cfg(tmp_path, extra, rollouts=4):

@@ -21,6 +21,8 @@ import bf16_check as bc
 import hashfill as hf
 import kl_penalty_ref as kr
 import oracle_lib as orc
+import trainer_helpers
+from trainer_helpers import debug_cfg as _debug_cfg, events as _events
 from __graft_entry__ import load_package
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -109,26 +111,7 @@ def test_gradient_formula_is_torch_autograd(fp16):
 
 @pytest.fixture(scope="module")
 def stub_trainer(tmp_path_factory):
-    """trainer/train.cc linked against the host-only library stand-in (tests/stub/aleppo_stub.cc), built out of tree"""
-    out = tmp_path_factory.mktemp("stub") / "train_stub"
-    cxx = os.environ.get("CXX", "g++")
-    subprocess.check_call([cxx, "-O1", "-std=c++17", "-pthread", os.path.join(ROOT, "trainer", "train.cc"),
-                           os.path.join(ROOT, "tests", "stub", "aleppo_stub.cc"), "-o", str(out)])
-    return str(out)
-
-
-def _debug_cfg(tmp_path, extra, rollouts=2):
-    txt = open(os.path.join(ROOT, "trainer", "configs", "debug.yaml")).read()
-    txt = re.sub(r"(?m)^num_rollouts: .*$", f"num_rollouts: {rollouts}", txt) + extra
-    cfg = tmp_path / "d.yaml"
-    cfg.write_text(txt)
-    return cfg
-
-
-def _events(d):
-    files = [f for f in os.listdir(d) if ".tfevents." in f]
-    assert len(files) == 1, files
-    return open(os.path.join(d, files[0]), "rb").read()
+    return trainer_helpers.build_stub_trainer(tmp_path_factory)
 
 
 def _scalars(blob, tag):
