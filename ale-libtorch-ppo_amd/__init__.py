@@ -60,6 +60,15 @@ ROLLOUT_STATE_WORDS = 4
 EVAL_GREEDY, EVAL_SAMPLE, EVAL_EPSILON_GREEDY = 0, 1, 2
 EVAL_RULES = dict(greedy=EVAL_GREEDY, sample=EVAL_SAMPLE, epsilon=EVAL_EPSILON_GREEDY)
 EVAL_FIELDS = dict(observations=0, logits=1, values=2, actions=3)
+# device-resident environments (Engine.env_open / env_rollout / env_state / env_read / env_episodes)
+ENV_SYNTHETIC = 0
+ENV_FIELDS = dict(frames=0, episode_returns=1, episode_lengths=2, game_returns=3, game_lengths=4, step_ms=5)
+# aleppo_env_state, 88 bytes without padding (include/aleppo.h)
+ENV_STATE_DTYPE = np.dtype([("rng", "<u8"), ("steps", "<u8"), ("ep_len", "<u8"), ("game_len", "<u8"), ("lives", "<i4"),
+                            ("paddle", "<i4"), ("ball_x", "<i4"), ("ball_y", "<i4"), ("prev_x", "<i4"), ("prev_y", "<i4"),
+                            ("dx", "<i4"), ("dy", "<i4"), ("bricks", "<i4"), ("episode_return", "<f4"), ("reward", "<f4"),
+                            ("ep_ret", "<f4"), ("game_ret", "<f4"), ("start", "u1"), ("game_over", "u1"),
+                            ("reserved", "u1", (2,))])
 KERNEL_CLASSES = dict(ingest=0, gae=1, head=2, adam=3, conv1_fwd=4, conv2_fwd=5, conv3_fwd=6, fc_fwd=7, fc_dgrad=8,
                       fc_wgrad=9, conv3_dgrad=10, conv3_wgrad=11, conv2_dgrad=12, conv2_wgrad=13, conv1_wgrad=14,
                       reduce=15, infer_head=16, act_fused=17, conv_fwd=18, conv_bwd=19)
@@ -108,6 +117,7 @@ EXPORTS = [
     "aleppo_eval_open", "aleppo_eval_push_frames", "aleppo_eval_act", "aleppo_eval_read",
     "aleppo_export_reward_scale", "aleppo_import_reward_scale", "aleppo_reward_scale",
     "aleppo_export_rollout_state", "aleppo_import_rollout_state", "aleppo_state_digest",
+    "aleppo_env_open", "aleppo_env_rollout", "aleppo_env_export_state", "aleppo_env_import_state", "aleppo_env_read",
 ]
 
 
@@ -128,6 +138,11 @@ class Config(C.Structure):
                 ("lambda_", C.c_float), ("clip_param", C.c_float), ("value_loss_coef", C.c_float),
                 ("entropy_coef", C.c_float), ("max_gradient_norm", C.c_float), ("adam_beta1", C.c_float),
                 ("adam_beta2", C.c_float), ("adam_eps", C.c_float), ("seed", C.c_uint64)]
+
+
+class EnvConfig(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("frame_kind", C.c_int32), ("seed_base", C.c_uint64), ("max_steps", C.c_uint64),
+                ("max_return", C.c_float), ("reserved", C.c_int32)]
 
 
 class MinibatchMetrics(C.Structure):
@@ -682,6 +697,52 @@ class Engine:
         out = np.zeros(shp, dt)
         self._c(lib().aleppo_eval_read(self._ctx, EVAL_FIELDS[name], _ptr(out), C.c_size_t(out.nbytes)))
         return out
+
+    # -- device-resident environments --
+    def env_open(self, frame_kind=FRAMES_84, seed_base=0, max_steps=108000, max_return=-1.0, kind=ENV_SYNTHETIC,
+                 reserved=0):
+        """aleppo_env_open: E synthetic environments in device memory, environment e seeded seed_base + e, rendering
+        84x84 frames or raw 2 x 210x160 pairs; again with the same arguments: the environments start over"""
+        cfg = EnvConfig(int(kind), int(frame_kind), int(seed_base), int(max_steps), float(max_return), int(reserved))
+        self._c(lib().aleppo_env_open(self._ctx, C.byref(cfg)))
+        self.env_frame_kind = int(frame_kind)
+
+    def env_rollout(self):
+        """aleppo_env_rollout: all T slots - act, environment step and render, ingest - enqueued without a host wait;
+        finish_rollout comes next"""
+        self._c(lib().aleppo_env_rollout(self._ctx))
+
+    def env_state(self):
+        """aleppo_env_export_state: a structured array [E] of ENV_STATE_DTYPE; between rollouts only"""
+        st = np.zeros(self.E, ENV_STATE_DTYPE)
+        self._c(lib().aleppo_env_export_state(self._ctx, _ptr(st), C.c_size_t(self.E)))
+        return st
+
+    def load_env_state(self, state):
+        """aleppo_env_import_state: what env_state returned (values a run cannot reach are refused)"""
+        st = np.ascontiguousarray(state, dtype=ENV_STATE_DTYPE)
+        self._c(lib().aleppo_env_import_state(self._ctx, _ptr(st), C.c_size_t(st.size)))
+
+    def env_read(self, name):
+        """aleppo_env_read: "frames" uint8 [E,84,84] / [E,2,210,160] (the frame buffer now); the last env_rollout's
+        time-major [T,E] log planes "episode_returns" / "game_returns" float32 and "episode_lengths" / "game_lengths"
+        uint32 (0: nothing ended in that slot); "step_ms" float64 [2] (mean ms of the environment kernel, launches
+        timed while profile() was on)"""
+        E, T = self.E, self.T
+        fshape = (E, 2, 210, 160) if getattr(self, "env_frame_kind", FRAMES_84) == FRAMES_RAW_PAIR else (E, 84, 84)
+        shp, dt = dict(frames=(fshape, np.uint8), episode_returns=((T, E), np.float32),
+                       episode_lengths=((T, E), np.uint32), game_returns=((T, E), np.float32),
+                       game_lengths=((T, E), np.uint32), step_ms=((2,), np.float64))[name]
+        out = np.zeros(shp, dt)
+        self._c(lib().aleppo_env_read(self._ctx, ENV_FIELDS[name], _ptr(out), C.c_size_t(out.nbytes)))
+        return out
+
+    def env_episodes(self):
+        """the last env_rollout's episode log, compacted in slot-then-environment order: (returns float32, lengths
+        uint32, game_returns, game_lengths) of the episodes / games that ended in it"""
+        el, gl = self.env_read("episode_lengths").ravel(), self.env_read("game_lengths").ravel()
+        return (self.env_read("episode_returns").ravel()[el > 0], el[el > 0],
+                self.env_read("game_returns").ravel()[gl > 0], gl[gl > 0])
 
     # -- multi GPU --
     @staticmethod

@@ -433,7 +433,7 @@ extern "C" void aleppo_destroy(aleppo_ctx *c) {
                  c->adam_sched, c->rb_tmp[0], c->rb_tmp[1], c->order, c->act_p, c->oldlp_p, c->adv_p,
                  c->ret_p,  c->mask_p,   c->mask_counts_ep, c->shuf_keys, c->val_n, c->val_p, c->advn_part,
                  c->advn_stats, c->kl_ps, c->kl_beta, c->hyper_blk, c->rs_blk, c->ev_obs, c->ev_a1, c->ev_a2, c->ev_a3, c->ev_hpart,
-                 c->ev_logits, c->ev_values, c->ev_actions, c->ev_d_frames, c->ev_d_start, c->ev_d_noise, c->ev_d_done, c->dg_out};
+                 c->ev_logits, c->ev_values, c->ev_actions, c->ev_d_frames, c->ev_d_start, c->ev_d_noise, c->ev_d_done, c->dg_out, c->env_blk};
   for (void *p : dev)
     if (p)
       hipFree(p);
@@ -454,6 +454,10 @@ extern "C" void aleppo_destroy(aleppo_ctx *c) {
       hipEventDestroy(pc.start[i]);
       hipEventDestroy(pc.stop[i]);
     }
+  for (size_t i = 0; i < c->env_prof.start.size(); ++i) {
+    hipEventDestroy(c->env_prof.start[i]);
+    hipEventDestroy(c->env_prof.stop[i]);
+  }
   for (hipEvent_t e : {c->ev_bucket0, c->ev_comm0, c->ev_tmp, c->ev_head, c->ev_dz3, c->ev_dz2, c->ev_wg,
                        c->ev_staged})
     if (e)
@@ -740,6 +744,7 @@ extern "C" int aleppo_profile_reset(aleppo_ctx *c) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (auto &p : c->prof)
     p.used = 0;
+  c->env_prof.used = 0;
   return ALEPPO_OK;
 }
 extern "C" int aleppo_profile_read(aleppo_ctx *c, int cls, double *avg_ms, int64_t *launches) {

@@ -1,5 +1,5 @@
 // api_internal.hpp - what the C ABI's translation units share (api_core.hip, api_rollout.hip, api_train.hip,
-// api_batch.hip, api_eval.hip, api_state.hip, api_ops.hip): the entry-point guard macros and the host-side helpers.  Host code only; the
+// api_batch.hip, api_eval.hip, api_env.hip, api_state.hip, api_ops.hip): the entry-point guard macros and the host-side helpers.  Host code only; the
 // helpers are defined in api_core.hip unless noted.
 #pragma once
 #include "common.hpp"
@@ -124,6 +124,11 @@ int ensure_metric_storage(aleppo_ctx *c, int epochs, int M, long B);
 // api_batch.hip: NCHW uint8 observations of the caller -> c->stage_u8 (device), grown on demand and kept
 int stage_observations(aleppo_ctx *c, const uint8_t *observations, int64_t n);
 int ensure_val_storage(aleppo_ctx *c);
+// api_rollout.hip, for aleppo_env_rollout (api_env.hip): slot `slot`'s acting kernels and head, and the GPU side of a step
+// whose episode-start flags are bytes already in device memory (start_device)
+int act_enqueue(aleppo_ctx *c, const float *noise, int slot);
+int step_enqueue(aleppo_ctx *c, const uint8_t *df, int kind, int location, const StartBits *sb, const uint8_t *start_mapped,
+                 int t, const uint8_t *start_device = nullptr);
 extern const double RS_INITIAL[RS_BLOCK];
 int ensure_rs_storage(aleppo_ctx *c);
 bool rs_state_valid(const double stats[3]);

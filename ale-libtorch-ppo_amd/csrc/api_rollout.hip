@@ -54,7 +54,7 @@ static int do_act(aleppo_ctx *c, const float *noise, int slot, void *logits_dst,
 }
 
 // enqueue slot c->t's acting kernels (whatever aleppo_step has not already run) + the head that publishes the actions
-static int act_enqueue(aleppo_ctx *c, const float *noise, int slot) {
+int aleppo::act_enqueue(aleppo_ctx *c, const float *noise, int slot) {
   if (slot >= c->T)
     return set_err(c, ALEPPO_ERR_RUNTIME, "rollout buffer is full: call aleppo_finish_rollout");
   if (slot == 0 && c->need_carry) { // slot T of the previous rollout is this rollout's first observation
@@ -216,11 +216,12 @@ static int do_record(aleppo_ctx *c, const float *rewards, const uint8_t *termina
 
 // the GPU side of a step: slot t's new frames -> observation slot t + 1 (+ its convolutions and fc where fused).  The
 // episode-start flags come as a kernel-argument bitmask (sb) or, for a step enqueued before the emulator has produced
-// them (aleppo_arm_step), as bytes in mapped host memory (start_mapped: host pointer, start_dev: its device address).
-static int step_enqueue(aleppo_ctx *c, const uint8_t *df, int kind, int location, const StartBits *sb,
-                        const uint8_t *start_mapped, int t) {
+// them (aleppo_arm_step), as bytes in mapped host memory (start_mapped: host pointer, start_dev: its device address), or,
+// for a slot the device-resident environments stepped (aleppo_env_rollout), as bytes in device memory (start_device).
+int aleppo::step_enqueue(aleppo_ctx *c, const uint8_t *df, int kind, int location, const StartBits *sb,
+                         const uint8_t *start_mapped, int t, const uint8_t *start_device) {
   const int E = c->E;
-  uint8_t *start_dev = nullptr;
+  uint8_t *start_dev = const_cast<uint8_t *>(start_device); // (only ever read)
   if (start_mapped)
     HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(&start_dev), const_cast<uint8_t *>(start_mapped), 0));
   // Fused ingest pays for given 84x84 frames (15.7 -> 14.4 ms per 128-slot rollout+update with the frames in mapped host
@@ -248,8 +249,8 @@ static int step_enqueue(aleppo_ctx *c, const uint8_t *df, int kind, int location
     if (start_mapped) // (every thread of the stand-alone kernel reads its flag: from HBM, not across the bus)
       HIPCHK(c, hipMemcpyAsync(c->d_start, start_mapped, E, hipMemcpyHostToDevice, c->stream));
     prof_begin(c, ALEPPO_K_INGEST);
-    launch_ingest(c->stream, kind == ALEPPO_FRAMES_RAW_PAIR, df, c->lut, start_mapped ? c->d_start : nullptr, sb, c->obs, E,
-                  c->T + 1, t, t + 1);
+    launch_ingest(c->stream, kind == ALEPPO_FRAMES_RAW_PAIR, df, c->lut,
+                  start_device ? start_device : start_mapped ? c->d_start : nullptr, sb, c->obs, E, c->T + 1, t, t + 1);
     prof_end(c, ALEPPO_K_INGEST);
     c->pre_acted = -1;
   }
@@ -490,7 +491,8 @@ extern "C" int aleppo_finish_rollout(aleppo_ctx *c, const float *noise) {
                   c->actions_tm + (size_t)T * E, false);
   if (rc)
     return rc;
-  HIPCHK(c, hipMemcpyAsync(c->step_rec, c->h_rec, c->step_rec_bytes * T, hipMemcpyHostToDevice, c->stream));
+  if (!c->rec_on_device) // (aleppo_env_rollout's records are where GAE reads them already)
+    HIPCHK(c, hipMemcpyAsync(c->step_rec, c->h_rec, c->step_rec_bytes * T, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(c->d_err, 0, 4, c->stream));
   if (rs_on) { // ALEPPO_OPT_REWARD_SCALE: scan -> moments -> [all-reduce] -> merge and scale -> GAE on the scaled rewards
     double *const sums = c->rs_part + (size_t)rs_blocks(E) * 4;
@@ -524,6 +526,7 @@ extern "C" int aleppo_finish_rollout(aleppo_ctx *c, const float *noise) {
   if (int rcg = check_gate(c)) // (the last armed slot's gate may have given up while the stream drained)
     return rcg;
   c->t = 0;
+  c->rec_on_device = false;
   c->pre_acted = -1;
   c->need_carry = true;
   c->batch_n = c->N;

@@ -272,6 +272,17 @@ struct Ctx {
   uint64_t ev_counter = 0;         // evaluation counter n of the built-in generator
   bool ev_acted = false;           // ev_logits / ev_values / ev_actions hold an aleppo_eval_act
   hipEvent_t ev_staged = nullptr;  // the last upload out of the pinned staging buffers has run
+  // ---- device-resident environments (aleppo_env_open): ONE allocation - the frame buffer, two state arrays that
+  // alternate slot by slot (env_step_kernel reads one and writes the other) and the four [T][E] episode-log planes; nothing
+  // below is allocated, and nothing is enqueued for it, on a context that never opens them
+  bool env_open = false;
+  aleppo_env_config env_cfg{};
+  uint8_t *env_blk = nullptr;      // the allocation; the frames are at its start (16-byte aligned)
+  aleppo_env_state *env_state[2] = {nullptr, nullptr};
+  int env_cur = 0;                 // env_state[env_cur] is the state between two slots
+  float *env_log = nullptr;        // [4][T][E]: episode returns, episode lengths (u32), game returns, game lengths (u32)
+  bool rec_on_device = false;      // the rollout being collected wrote its step records on the device (aleppo_env_rollout)
+  ProfClass env_prof;              // ALEPPO_ENV_F_STEP_MS: events around the environment kernel while profiling is on
   bool prof_on = false;
   bool serial_update = false; // ALEPPO_OPT_SERIAL_UPDATE: every update kernel on the main stream
   bool dbg_no_publish = false;

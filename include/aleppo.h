@@ -474,6 +474,91 @@ int aleppo_eval_act(aleppo_ctx *ctx, int rule, float param, const float *noise, 
  * ALEPPO_ERR_RUNTIME. */
 int aleppo_eval_read(aleppo_ctx *ctx, int field, void *dst, size_t bytes);
 
+/* ------------------------------------------------------------------ device-resident environments (no reference
+ * counterpart: the reference's emulators are host threads, rollout.cc:280-328)
+ * E environments that live in device memory and are stepped by a kernel, so that a whole rollout of T slots is ONE burst
+ * of enqueued kernels - per slot the acting head, the environment step and render, the ingest and acting convolutions -
+ * with nothing returning to the host in between.  The only kind is ALEPPO_ENV_SYNTHETIC: the trainer's SyntheticAtari
+ * (trainer/emulator.hpp, which IS the specification: reset, step, the xorshift64 generator and both renderers, read
+ * literally), stepped the way the trainer's EnvSet::step and collect() step it: an episode-start slot resets and keeps
+ * the stale reward, any other slot steps with the action the acting head just sampled; terminal / truncated are 0 in a
+ * start slot; `start` is set after a terminal or a truncation and cleared after the reset slot.  Integer arithmetic and
+ * float additions of small integers only: a device rollout is the rollout the host loop aleppo_act -> emulator ->
+ * aleppo_step would have collected, byte for byte - every plane of aleppo_read_batch, the episode log, the environment
+ * state and aleppo_state_digest - so the two can be mixed rollout by rollout and a checkpoint written with one resumes
+ * with the other.
+ * Shared rules: the context's own stream only, no hipFree, no device-wide synchronise; never a collective (under data
+ * parallelism each rank owns its environments); ALEPPO_ERR_RUNTIME while a step is armed; nothing the evaluation lanes
+ * can observe changes, and the evaluation calls change nothing here.  A context that never calls aleppo_env_open
+ * allocates and enqueues nothing for any of this. */
+typedef enum { ALEPPO_ENV_SYNTHETIC = 0 } aleppo_env_kind;
+typedef struct {
+  int32_t kind;       /* ALEPPO_ENV_SYNTHETIC */
+  int32_t frame_kind; /* ALEPPO_FRAMES_84 | ALEPPO_FRAMES_RAW_PAIR: what the environments render and the ingest reads */
+  uint64_t seed_base; /* environment e is SyntheticAtari(seed_base + e, max_steps, max_return, A, raw) */
+  uint64_t max_steps; /* truncation by emulator-frame budget (4 frames per agent step) */
+  float max_return;   /* truncation by emulator episode return, compared in float; <= 0: off */
+  int32_t reserved;   /* 0 */
+} aleppo_env_config; /* 32 bytes */
+/* One environment between two rollouts, 88 bytes, no padding: the twelve fields SyntheticAtari::visit lists (the
+ * trainer's checkpoint order), then the trainer-side bookkeeping of collect() (TrainerState). */
+typedef struct {
+  uint64_t rng;          /* offset 0: xorshift64 state */
+  uint64_t steps;        /*  8: emulator frames of the current game */
+  uint64_t ep_len;       /* 16: agent steps of the current episode / game (trainer side) */
+  uint64_t game_len;     /* 24 */
+  int32_t lives;         /* 32: 0..5 */
+  int32_t paddle;        /* 36: 4..79 */
+  int32_t ball_x, ball_y, prev_x, prev_y; /* 40, 44, 48, 52: 0..83 */
+  int32_t dx, dy;        /* 56, 60: +1 / -1 */
+  int32_t bricks;        /* 64: >= 0 */
+  float episode_return;  /* 68: the emulator's return of the current game (what max_return is compared with) */
+  float reward;          /* 72: the last recorded reward (a start slot records it again) */
+  float ep_ret, game_ret;/* 76, 80: returns of the current episode / game (trainer side) */
+  uint8_t start;         /* 84: the next slot is an episode-start slot */
+  uint8_t game_over;     /* 85: the last step ended the game */
+  uint8_t reserved[2];   /* 86: 0 */
+} aleppo_env_state;
+typedef enum {
+  ALEPPO_ENV_F_FRAMES = 0,          /* uint8 [E,84,84] or [E,2,210,160]: the frame buffer right now */
+  ALEPPO_ENV_F_EPISODE_RETURNS = 1, /* float  [T,E] time-major: the return of the episode that ended in slot (t, e) */
+  ALEPPO_ENV_F_EPISODE_LENGTHS = 2, /* uint32 [T,E]: its length in agent steps; 0 = no episode ended in that slot */
+  ALEPPO_ENV_F_GAME_RETURNS = 3,    /* float  [T,E]: the same for games (an episode that ended with game over) */
+  ALEPPO_ENV_F_GAME_LENGTHS = 4,    /* uint32 [T,E] */
+  ALEPPO_ENV_F_STEP_MS = 5          /* double [2]: mean device time in ms of the environment kernel and the number of
+                                       launches timed, over the aleppo_env_rollout calls made while aleppo_profile_enable
+                                       was on since the last aleppo_profile_reset (HIP events around each launch) */
+} aleppo_env_field;
+/* Allocates - in this call and never later - the environments' state, the frame buffer ([E,84,84] or [E,2,210,160],
+ * 16-byte aligned; the per-environment strides 7056 and 67200 are multiples of 16) and the four episode-log planes, and
+ * puts every environment into the constructor's state with start = 1 and reward 0.  Called again with the same config
+ * it resets the environments to that state; with another config it is ALEPPO_ERR_RUNTIME.  An unknown kind or frame
+ * kind, a non-zero reserved field or a null pointer is ALEPPO_ERR_INVALID_ARGUMENT.  Nothing is freed before
+ * aleppo_destroy. */
+int aleppo_env_open(aleppo_ctx *ctx, const aleppo_env_config *cfg);
+/* One whole rollout: for t in [0, T) aleppo_act's kernels with the built-in generator (the head publishes the actions and
+ * the ticket as always), the environment kernel - it reads slot t's int32 actions where the head wrote them, steps and
+ * renders every environment, and writes slot t's step record (rewards, terminal, truncated and start-at-entry bytes)
+ * straight into the device record - and aleppo_step's kernels on the frame buffer with the record's start bytes.
+ * Returns once the work is enqueued; no host wait in between.  Leaves the context ready for aleppo_finish_rollout, which
+ * uses the device-written records as they are, as do ALEPPO_OPT_REWARD_SCALE, advantage_norm and ALEPPO_ROLLOUT_FP16.
+ * The acting generator's counter advances as T aleppo_act calls advance it, and the ticket and the pinned action buffer
+ * stay consistent: a host-driven rollout may follow a device one and vice versa.
+ * ALEPPO_ERR_RUNTIME before aleppo_env_open, and unless the rollout buffer is empty (the next slot to fill is 0). */
+int aleppo_env_rollout(aleppo_ctx *ctx);
+/* The environments' part of a checkpoint, states [num_envs].  Valid between rollouts only, like
+ * aleppo_export_rollout_state (ALEPPO_ERR_RUNTIME otherwise, and before aleppo_env_open); a null pointer or num_envs !=
+ * config.num_envs is ALEPPO_ERR_INVALID_ARGUMENT.  The import refuses (ALEPPO_ERR_INVALID_ARGUMENT) what a run cannot
+ * reach - lives outside 0..5, paddle outside 4..79, a ball coordinate outside 0..83, dx / dy not +-1, negative bricks,
+ * a flag that is not 0 / 1, a non-zero reserved byte, a non-finite float - and a refused import changes nothing. */
+int aleppo_env_export_state(aleppo_ctx *ctx, aleppo_env_state *states, size_t num_envs);
+int aleppo_env_import_state(aleppo_ctx *ctx, const aleppo_env_state *states, size_t num_envs);
+/* Read an aleppo_env_field; synchronises the context's stream like aleppo_read_batch.  The log planes are those of the
+ * last aleppo_env_rollout (zero before any); compacted in slot-then-environment order they are the trainer's episode log
+ * in the order collect() appends.  A wrong byte count or an unknown field is ALEPPO_ERR_INVALID_ARGUMENT; before
+ * aleppo_env_open ALEPPO_ERR_RUNTIME. */
+int aleppo_env_read(aleppo_ctx *ctx, int field, void *dst, size_t bytes);
+
 /* ------------------------------------------------------------------ multi-GPU (no reference counterpart)
  * One process per GPU.  Rank 0 creates the id, the launcher broadcasts its bytes, every rank calls
  * aleppo_comm_init.  Gradients (+ mask counts) are all-reduced with RCCL inside aleppo_train. */

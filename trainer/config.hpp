@@ -48,6 +48,7 @@ struct Config {
   // extensions
   std::string precision = "fp32", rollout_precision = "fp32";
   bool device_preprocess = false; // emulators hand over raw frame pairs; gray LUT + resize + max run on the device (N2)
+  bool device_environments = false; // the training environments live on the device: aleppo_env_open / aleppo_env_rollout
   bool slot_ahead = true;         // aleppo_arm_step / aleppo_release_step: the stream runs one slot ahead of the emulators
   bool advantage_norm = false;
   uint64_t seed = 42;
@@ -213,6 +214,7 @@ static Config load_config(const std::string &path) { // keys / defaults of src/b
   read_key(kv, "rollout_precision", c.rollout_precision);
   read_key(kv, "device_preprocess", c.device_preprocess);
   read_key(kv, "slot_ahead", c.slot_ahead);
+  read_key(kv, "device_environments", c.device_environments);
   read_key(kv, "advantage_norm", c.advantage_norm);
   read_key(kv, "seed", c.seed);
   return c;
@@ -287,7 +289,8 @@ static HParams hparams_of(const Config &c) {
                                                     {"clip_value_loss", c.clip_value_loss},
                                                     {"minibatch_advantage_norm", c.minibatch_advantage_norm},
                                                     {"log_batch_stats", c.log_batch_stats},
-                                                    {"reward_scaling", c.reward_scaling}};
+                                                    {"reward_scaling", c.reward_scaling},
+                                                    {"device_environments", c.device_environments}};
   for (const auto &f : when_set)
     if (f.second)
       h.flags.emplace_back(f.first, true);

@@ -71,6 +71,14 @@
 // Under data parallelism every rank writes and reads <file>.rank<r>.  A resume file that is missing, truncated, of another
 // format version or written for another shape (environments, horizon, actions, hidden size, precision, world size, rank)
 // is refused before anything is created; a library without the entry points refuses the three keys at start-up.
+// device_environments: false (true: the training environments are the library's device-resident SyntheticAtari instances,
+// seeded like this trainer's own - environment i of the run is seed i - and a rollout is aleppo_env_rollout +
+// aleppo_finish_rollout: nothing comes back to the host between slots, slot_ahead and the worker pool are not used for
+// training, and the episode log and the step / episode counters come from the library's log planes and the exported
+// environment state.  The run is the run with host environments, bit for bit, and so is the checkpoint file: save exports
+// the device state into the fields the host emulators are saved in, resume imports them, and a file written in one mode
+// resumes in the other.  Evaluation keeps its host emulators and lanes.  A library without the entry points refuses the key
+// at start-up).
 // Data parallelism (no reference counterpart): start one process per GPU with RANK / WORLD_SIZE / LOCAL_RANK
 // in the environment (torchrun / mpirun style).  Rank r owns the contiguous environment block
 // [r * E / W, (r + 1) * E / W) and GPU LOCAL_RANK; rank 0 creates the RCCL id, hands it to the others through the file
@@ -108,6 +116,12 @@
 #pragma weak aleppo_export_rollout_state
 #pragma weak aleppo_import_rollout_state
 #pragma weak aleppo_state_digest
+// ... and the device-resident environments (device_environments: true)
+#pragma weak aleppo_env_open
+#pragma weak aleppo_env_rollout
+#pragma weak aleppo_env_export_state
+#pragma weak aleppo_env_import_state
+#pragma weak aleppo_env_read
 
 static void check(aleppo_ctx *ctx, int rc) { // the reference throws at the same places
   if (rc == ALEPPO_OK)
@@ -229,6 +243,10 @@ static void refuse_missing_entry_points(const Config &cfg) {
   if (cfg.reward_scaling && !(aleppo_export_reward_scale && aleppo_import_reward_scale))
     throw std::runtime_error("reward_scaling is set but this build's library has no reward scaling "
                              "(aleppo_export_reward_scale is missing)");
+  if (cfg.device_environments && !(aleppo_env_open && aleppo_env_rollout && aleppo_env_export_state &&
+                                   aleppo_env_import_state && aleppo_env_read))
+    throw std::runtime_error("device_environments is set but this build's library has no device-resident environments "
+                             "(aleppo_env_open is missing)");
 }
 
 // ------------------------------------------------------------------ start-up
@@ -369,6 +387,15 @@ static void create_environments(Run &run) {
     check(run.ctx, aleppo_set_gray_lut(run.ctx, lut));
   }
   check(run.ctx, aleppo_host_alloc(run.ctx, E, reinterpret_cast<void **>(&run.start_mapped)));
+  if (cfg.device_environments) { // the same E emulators on the device; the host instances above only hold checkpoint fields
+    aleppo_env_config ec{};
+    ec.kind = ALEPPO_ENV_SYNTHETIC;
+    ec.frame_kind = frame_kind(cfg);
+    ec.seed_base = run.env0;
+    ec.max_steps = cfg.max_steps;
+    ec.max_return = (float)cfg.max_return;
+    check(run.ctx, aleppo_env_open(run.ctx, &ec));
+  }
   std::cout << "Creating " << cfg.num_workers << " worker threads." << std::endl;
   run.pool.emplace(cfg.num_workers);
   // evaluation (eval_interval): full episodes on emulators of its own through the evaluation lanes.  Nothing there touches
@@ -387,7 +414,90 @@ struct EpisodeLog {
   std::vector<float> episode_returns, game_returns;
   std::vector<size_t> episode_lengths, game_lengths;
 };
+// device_environments: the state of the library's environments <-> the fields a checkpoint keeps them in (TrainerState and
+// its host SyntheticAtari instances, which are never stepped in that mode)
+struct EnvFieldCopy {
+  aleppo_env_state &s;
+  bool to_host;
+  template <class A, class B> void one(A &host, B &dev) {
+    if (to_host)
+      host = (A)dev;
+    else
+      dev = (B)host;
+  }
+  void operator()(uint64_t &rng, int &lives, int &paddle, int &ball_x, int &ball_y, int &prev_x, int &prev_y, int &dx, int &dy,
+                  int &bricks, uint64_t &steps, float &episode_return) {
+    one(rng, s.rng), one(lives, s.lives), one(paddle, s.paddle), one(ball_x, s.ball_x), one(ball_y, s.ball_y);
+    one(prev_x, s.prev_x), one(prev_y, s.prev_y), one(dx, s.dx), one(dy, s.dy), one(bricks, s.bricks), one(steps, s.steps);
+    one(episode_return, s.episode_return);
+  }
+};
+static void copy_env_fields(TrainerState &st, std::vector<aleppo_env_state> &dev, bool to_host) {
+  for (size_t i = 0; i < dev.size(); ++i) {
+    EnvFieldCopy f{dev[i], to_host};
+    st.set.envs[i].visit(f);
+    f.one(st.set.start[i], dev[i].start), f.one(st.game_over[i], dev[i].game_over), f.one(st.rewards[i], dev[i].reward);
+    f.one(st.ep_ret[i], dev[i].ep_ret), f.one(st.game_ret[i], dev[i].game_ret), f.one(st.ep_len[i], dev[i].ep_len);
+    f.one(st.game_len[i], dev[i].game_len);
+  }
+}
+static void pull_device_environments(Run &run) {
+  std::vector<aleppo_env_state> dev(run.E);
+  check(run.ctx, aleppo_env_export_state(run.ctx, dev.data(), dev.size()));
+  copy_env_fields(run.st, dev, true);
+}
+static void push_device_environments(Run &run) {
+  std::vector<aleppo_env_state> dev(run.E); // (zeroed: the reserved bytes)
+  copy_env_fields(run.st, dev, false);
+  check(run.ctx, aleppo_env_import_state(run.ctx, dev.data(), dev.size()));
+}
+// one rollout on the device's environments: the whole slot loop is one burst of enqueued kernels
+static EpisodeLog collect_on_device(Run &run) {
+  aleppo_ctx *ctx = run.ctx;
+  TrainerState &st = run.st;
+  const size_t n = run.E * run.T;
+  {
+    Profile::Span sp(&run.prof, "aleppo_env_rollout");
+    check(ctx, aleppo_env_rollout(ctx));
+  }
+  {
+    Profile::Span sp(&run.prof, "aleppo_finish_rollout");
+    check(ctx, aleppo_finish_rollout(ctx, nullptr));
+  }
+  // the four [T][E] log planes in slot-then-environment order: the order the host loop appends in
+  std::vector<float> ep_ret(n), game_ret(n);
+  std::vector<uint32_t> ep_len(n), game_len(n);
+  check(ctx, aleppo_env_read(ctx, ALEPPO_ENV_F_EPISODE_RETURNS, ep_ret.data(), n * 4));
+  check(ctx, aleppo_env_read(ctx, ALEPPO_ENV_F_EPISODE_LENGTHS, ep_len.data(), n * 4));
+  check(ctx, aleppo_env_read(ctx, ALEPPO_ENV_F_GAME_RETURNS, game_ret.data(), n * 4));
+  check(ctx, aleppo_env_read(ctx, ALEPPO_ENV_F_GAME_LENGTHS, game_len.data(), n * 4));
+  EpisodeLog log;
+  // every non-start slot added one to its environment's episode length: the steps of this rollout are the lengths that
+  // were logged plus what the running lengths grew by
+  uint64_t steps = 0;
+  for (uint64_t l : st.ep_len)
+    steps -= l;
+  for (size_t k = 0; k < n; ++k) {
+    if (ep_len[k]) {
+      st.episodes++;
+      steps += ep_len[k];
+      log.episode_returns.push_back(ep_ret[k]);
+      log.episode_lengths.push_back(ep_len[k]);
+    }
+    if (game_len[k]) {
+      log.game_returns.push_back(game_ret[k]);
+      log.game_lengths.push_back(game_len[k]);
+    }
+  }
+  pull_device_environments(run);
+  for (uint64_t l : st.ep_len)
+    steps += l;
+  st.total_steps += steps;
+  return log;
+}
 static EpisodeLog collect(Run &run) {
+  if (run.cfg.device_environments)
+    return collect_on_device(run);
   aleppo_ctx *ctx = run.ctx;
   TrainerState &st = run.st;
   EnvSet &set = st.set;
@@ -727,6 +837,8 @@ static void resume(Run &run) { // import everything, then prove it: the device's
                              std::to_string(run.st.next_rollout) + ", this run has " +
                              std::to_string(run.cfg.num_rollouts));
   run.first_rollout = (size_t)run.st.next_rollout;
+  if (run.cfg.device_environments) // (whichever mode wrote the file: the fields are the same)
+    push_device_environments(run);
   uint64_t got[ALEPPO_DIGEST_COUNT];
   check(ctx, aleppo_state_digest(ctx, got));
   for (int k = 0; k < ALEPPO_DIGEST_COUNT; ++k)
