@@ -56,6 +56,15 @@ METRIC_ADV_FIELDS = dict(mean=9, std=10)
 DIGEST_COUNT = 4
 DIGEST_SECTIONS = dict(params=0, optimizer=1, rollout=2, reward_scale=3)
 ROLLOUT_STATE_WORDS = 4
+# aleppo_tensor_stats: double [TENSOR_STATS_ROWS][TENSOR_STATS_COLS], the rows in libtorch parameters() order plus the whole
+# model, the columns of aleppo_tensor_stat, the section bits of aleppo_tensor_stats_section (Engine.tensor_stats)
+TENSOR_STATS_ROWS, TENSOR_STATS_COLS = 13, 10
+TENSOR_NAMES = ("conv1.w", "conv1.b", "conv2.w", "conv2.b", "conv3.w", "conv3.b", "fc.w", "fc.b", "action.w", "action.b",
+                "value.w", "value.b", "total")
+TENSOR_STATS = dict(size=0, param_norm=1, param_maxabs=2, param_nonfinite=3, grad_norm=4, grad_maxabs=5, update_norm=6,
+                    update_maxabs=7, update_ratio=8, step_nonfinite=9)
+TS_SEC_PARAMS, TS_SEC_STEP = 1, 2
+TENSOR_STATS_SECTIONS = dict(params=TS_SEC_PARAMS, step=TS_SEC_STEP, all=TS_SEC_PARAMS | TS_SEC_STEP)
 # aleppo_eval_rule / aleppo_eval_field: the evaluation lanes (Engine.eval_open / eval_push_frames / eval_act / eval_read)
 EVAL_GREEDY, EVAL_SAMPLE, EVAL_EPSILON_GREEDY = 0, 1, 2
 EVAL_RULES = dict(greedy=EVAL_GREEDY, sample=EVAL_SAMPLE, epsilon=EVAL_EPSILON_GREEDY)
@@ -117,6 +126,7 @@ EXPORTS = [
     "aleppo_eval_open", "aleppo_eval_push_frames", "aleppo_eval_act", "aleppo_eval_read",
     "aleppo_export_reward_scale", "aleppo_import_reward_scale", "aleppo_reward_scale",
     "aleppo_export_rollout_state", "aleppo_import_rollout_state", "aleppo_state_digest",
+    "aleppo_tensor_stats",
     "aleppo_env_open", "aleppo_env_rollout", "aleppo_env_export_state", "aleppo_env_import_state", "aleppo_env_read",
 ]
 
@@ -436,6 +446,19 @@ class Engine:
         out = np.zeros(DIGEST_COUNT, np.uint64)
         self._c(lib().aleppo_state_digest(self._ctx, _ptr(out)))
         return {name: int(out[i]) for name, i in DIGEST_SECTIONS.items()}
+
+    def tensor_stats(self, sections="all", raw=False):
+        """aleppo_tensor_stats: per-tensor norms, maxima and non-finite counts of the parameters ("params"), of the last
+        minibatch's clipped gradient and of the last optimizer step ("step": needs a train() with no load_params /
+        load_state_dict since), or both ("all"), reduced on the device.  {tensor: {stat: float}} over TENSOR_NAMES and
+        TENSOR_STATS; raw=True: the float64 [13, 10] array.  `sections` may also be the bits themselves.  The columns of a
+        section that was not asked for are 0."""
+        bits = TENSOR_STATS_SECTIONS[sections] if isinstance(sections, str) else int(sections)
+        out = np.zeros((TENSOR_STATS_ROWS, TENSOR_STATS_COLS), np.float64)
+        self._c(lib().aleppo_tensor_stats(self._ctx, C.c_int(bits), _ptr(out), C.c_size_t(out.size)))
+        if raw:
+            return out
+        return {t: {name: float(out[r, i]) for name, i in TENSOR_STATS.items()} for r, t in enumerate(TENSOR_NAMES)}
 
     # -- return-based reward scaling (OPT_REWARD_SCALE) --
     def set_reward_scaling(self, on, clip=10.0):

@@ -433,7 +433,7 @@ extern "C" void aleppo_destroy(aleppo_ctx *c) {
                  c->adam_sched, c->rb_tmp[0], c->rb_tmp[1], c->order, c->act_p, c->oldlp_p, c->adv_p,
                  c->ret_p,  c->mask_p,   c->mask_counts_ep, c->shuf_keys, c->val_n, c->val_p, c->advn_part,
                  c->advn_stats, c->kl_ps, c->kl_beta, c->hyper_blk, c->rs_blk, c->ev_obs, c->ev_a1, c->ev_a2, c->ev_a3, c->ev_hpart,
-                 c->ev_logits, c->ev_values, c->ev_actions, c->ev_d_frames, c->ev_d_start, c->ev_d_noise, c->ev_d_done, c->dg_out, c->env_blk};
+                 c->ev_logits, c->ev_values, c->ev_actions, c->ev_d_frames, c->ev_d_start, c->ev_d_noise, c->ev_d_done, c->dg_out, c->env_blk, c->ts_scratch};
   for (void *p : dev)
     if (p)
       hipFree(p);
@@ -499,6 +499,7 @@ extern "C" int aleppo_load_params(aleppo_ctx *c, const float *flat, size_t count
   HIPCHK(c, hipMemsetAsync(c->G, 0, tmp.size() * 4, c->stream));
   HIPCHK(c, copy_sync(c, c->P, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice)); // (own stream only: see dalloc)
   c->adam_step = 0;
+  c->ts_step_valid = false; // (aleppo_tensor_stats: the last step can no longer be recomputed)
   c->pre_acted = -1;
   refresh_compute_copies(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -525,10 +526,7 @@ extern "C" int aleppo_export_grads(aleppo_ctx *c, float *flat, size_t count) {
   const int rc = export_flat(c, c->G, flat, count);
   if (rc || c->last_epochs * c->last_M == 0)
     return rc;
-  const size_t nm = (size_t)c->last_epochs * c->last_M;
-  const float norm = c->h_metric_red[nm * METRIC_REC + nm - 1];
-  float coef = c->last_max_norm / (norm + 1e-6f); // (the limit that update ran with)
-  coef = std::fmin(coef, 1.0f);
+  const float coef = last_clip_coef(c); // (with the limit that update ran with)
   for (size_t i = 0; i < count; ++i)
     flat[i] *= coef;
   return ALEPPO_OK;
@@ -560,6 +558,7 @@ extern "C" int aleppo_import_optimizer(aleppo_ctx *c, const float *exp_avg, cons
   params_to_internal(c->L, exp_avg_sq, tmp.data());
   HIPCHK(c, copy_sync(c, c->M2, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice));
   c->adam_step = step;
+  c->ts_step_valid = false; // (aleppo_tensor_stats: these moments are not the last step's)
   return ALEPPO_OK;
 }
 

@@ -114,6 +114,17 @@ inline uint32_t float_bits(float f) {
   return u;
 }
 
+// clip_grad_norm_'s factor of the LAST optimizer step, as adam_kernel formed it: one fp32 quotient of the stored pre-clip
+// norm and the limit that update ran with, clamped to 1 (aleppo_export_grads, aleppo_tensor_stats); 1 before any update
+inline float last_clip_coef(const Ctx *c) {
+  const size_t nm = (size_t)c->last_epochs * c->last_M;
+  if (nm == 0)
+    return 1.0f;
+  const float norm = c->h_metric_red[nm * METRIC_REC + nm - 1];
+  const float coef = c->last_max_norm / (norm + 1e-6f);
+  return std::fmin(coef, 1.0f);
+}
+
 // the device the stateless operators and aleppo_create run on (process-default kernel switches)
 int select_device(int ordinal);
 

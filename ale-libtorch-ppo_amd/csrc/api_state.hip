@@ -1,6 +1,7 @@
 // api_state.hip - C ABI (include/aleppo.h), the run state beyond the learner: the rollout side of a checkpoint
 // (aleppo_export_rollout_state / aleppo_import_rollout_state) and the device-side digest of the whole run state
 // (aleppo_state_digest).  All three are valid between rollouts only and synchronise the context's own stream only.
+// Also the other read-only pass over the learner state: aleppo_tensor_stats (valid at any time no step is armed).
 #include "api_internal.hpp"
 
 using namespace aleppo;
@@ -75,5 +76,34 @@ extern "C" int aleppo_state_digest(aleppo_ctx *c, uint64_t out[ALEPPO_DIGEST_COU
   HIPCHK(c, copy_sync(c, host, c->dg_out, sizeof(host), hipMemcpyDeviceToHost));
   for (int k = 0; k < ALEPPO_DIGEST_COUNT; ++k)
     out[k] = host[k];
+  return ALEPPO_OK;
+}
+
+// Per-tensor norms of the parameters, the last minibatch's clipped gradient and the last optimizer step (aleppo.h), read
+// the way the digest is: computed when called, by kernels that only read, on the context's stream.  Nothing here touches
+// what a captured update bakes in, and no other entry point knows about it.
+extern "C" int aleppo_tensor_stats(aleppo_ctx *c, int sections, double *out, size_t count) {
+  CHECK_CTX(c);
+  constexpr size_t COUNT = (size_t)ALEPPO_TENSOR_STATS_ROWS * ALEPPO_TENSOR_STATS_COLS;
+  if (!out)
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "tensor_stats: null argument");
+  if (count != COUNT)
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "tensor_stats: count must be 130");
+  if (sections <= 0 || (sections & ~(ALEPPO_TS_SEC_PARAMS | ALEPPO_TS_SEC_STEP)))
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "tensor_stats: sections must be ALEPPO_TS_SEC_PARAMS and / or _STEP");
+  const bool step = (sections & ALEPPO_TS_SEC_STEP) != 0;
+  if (step && !c->ts_step_valid)
+    return set_err(c, ALEPPO_ERR_RUNTIME,
+                   "tensor_stats: the step section needs an aleppo_train on this context with no aleppo_load_params / "
+                   "aleppo_import_optimizer since");
+  if (!c->ts_scratch)
+    HIPCHK(c, dalloc(&c->ts_scratch, tensor_stats_scratch_bytes(c->L), c->stream));
+  const double *dev = nullptr;
+  launch_tensor_stats(c->stream, c->P, c->G, c->M1, c->M2, c->L, sections, step ? last_clip_coef(c) : 1.0f, c->ts_sched[0],
+                      c->ts_sched[1], c->cfg.adam_eps, c->ts_scratch, &dev);
+  HIPCHK(c, hipGetLastError());
+  double host[COUNT];
+  HIPCHK(c, copy_sync(c, host, dev, sizeof(host), hipMemcpyDeviceToHost));
+  std::memcpy(out, host, sizeof(host));
   return ALEPPO_OK;
 }

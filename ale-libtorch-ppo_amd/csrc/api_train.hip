@@ -660,6 +660,9 @@ static int read_back_metrics(aleppo_ctx *c, const UpdatePlan &p, aleppo_minibatc
   c->last_advn = p.advn;
   c->last_kl = p.klpen;
   c->last_max_norm = p.hp.max_norm;
+  c->ts_sched[0] = c->h_adam_sched[2 * (nm - 1)]; // (aleppo_tensor_stats recomputes the last step from these)
+  c->ts_sched[1] = c->h_adam_sched[2 * (nm - 1) + 1];
+  c->ts_step_valid = true;
   if (out)
     for (int i = 0; i < nm; ++i) {
       const float *r = c->h_metric_red + (size_t)i * METRIC_REC;
@@ -681,8 +684,10 @@ extern "C" int aleppo_train(aleppo_ctx *c, double lr, int epochs, int M, aleppo_
   int rc = plan_update(c, epochs, M, &plan);
   if (rc == ALEPPO_OK)
     rc = upload_call_scalars(c, plan, lr);
-  if (rc == ALEPPO_OK)
+  if (rc == ALEPPO_OK) {
+    c->ts_step_valid = false; // (until this update's last step is known to have run: read_back_metrics)
     rc = run_update(c, plan);
+  }
   if (rc)
     return rc;
   c->adam_step += plan.nm;

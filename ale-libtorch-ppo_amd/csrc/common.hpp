@@ -255,6 +255,11 @@ struct Ctx {
   uint32_t *stage_obs = nullptr; // packed stacks of aleppo_forward's samples (never the rollout slots)
   size_t stage_obs_cap = 0;
   unsigned long long *dg_out = nullptr; // aleppo_state_digest's four words (allocated on first use)
+  // ---- aleppo_tensor_stats: the per-chunk partial records and the 130 doubles (allocated on first use; its size is a
+  // function of (H, A) only), and what the STEP section is recomputed from
+  void *ts_scratch = nullptr;
+  bool ts_step_valid = false;           // an aleppo_train has succeeded and no load_params / import_optimizer since
+  float ts_sched[2] = {0.f, 0.f};       // the two schedule scalars of the last optimizer step that ran
   // ---- evaluation lanes (aleppo_eval_open): L frame stacks of their own, their own acting scratch, upload staging and
   // action hand-off; nothing below is allocated, and nothing is enqueued for it, on a context that never opens them
   int ev_L = 0;                    // 0: not opened
@@ -423,6 +428,16 @@ void launch_transpose_tm_pitched(hipStream_t s, const void *src_tm, size_t pitch
 void launch_state_digest(hipStream_t s, const float *P, const float *M1, const float *M2, const ParamLayout &L,
                          int64_t step, const uint32_t *obs, int slots, int slot, int E, uint64_t counter,
                          const double *rs_blk, const double *rs_g, unsigned long long *out);
+// aleppo_tensor_stats (tensor_stats.hip): one read-only pass over the padded flat vectors in chunks of TS_CHUNK floats per
+// internal tensor (one workgroup and one pair of partial records per chunk), then one small launch that adds the partials
+// per exported tensor in index order and writes double [ALEPPO_TENSOR_STATS_ROWS][ALEPPO_TENSOR_STATS_COLS] behind the
+// records.  sections: aleppo_tensor_stats_section bits; without ALEPPO_TS_SEC_STEP only P is read.  coef: the clip factor
+// of aleppo_export_grads; step_size / bc2_sqrt / eps: adam_element's scalars of the last optimizer step.
+constexpr int TS_CHUNK = 4096;
+size_t tensor_stats_scratch_bytes(const ParamLayout &L);
+void launch_tensor_stats(hipStream_t s, const float *P, const float *G, const float *M1, const float *M2,
+                         const ParamLayout &L, int sections, float coef, float step_size, float bc2_sqrt, float eps,
+                         void *scratch, const double **out_dev);
 void launch_heads_fwd(hipStream_t s, const float *h, const float *Wh, const float *bh, float *logits, float *values,
                       long n, int H, int A);
 void launch_logsoftmax_rows(hipStream_t s, const float *in, float *out, long rows, int A);

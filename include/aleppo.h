@@ -290,6 +290,60 @@ typedef enum {
 } aleppo_digest_section;
 int aleppo_state_digest(aleppo_ctx *ctx, uint64_t out[ALEPPO_DIGEST_COUNT]);
 
+/* Per-tensor parameter, gradient and update norms (what wandb.watch or a few lines of torch give a CleanRL / SB3 user; the
+ * reference has none), reduced on the device where P, the gradient and the Adam moments are: which layer's gradient
+ * vanished or exploded, how large the last step was relative to the weights, which tensor went non-finite first.
+ * out: double [ALEPPO_TENSOR_STATS_ROWS][ALEPPO_TENSOR_STATS_COLS], row-major; count must be 130.  Rows 0-11 are the twelve
+ *   tensors in the libtorch parameters() order of aleppo_export_params (conv1.w, conv1.b, conv2.w, conv2.b, conv3.w,
+ *   conv3.b, fc.w, fc.b, action.w, action.b, value.w, value.b), row 12 is the whole model.  Columns: aleppo_tensor_stat.
+ * Elements, per exported element i (the alignment pads of the private layout are not elements):
+ *   p_i  the fp32 master parameter (bf16 contexts have one too; the bf16 copies are not read)
+ *   g_i  = float32(raw_i * coef): exactly the element aleppo_export_grads returns - the gradient of the last minibatch,
+ *        coef formed as that function forms it from the stored pre-clip norm and the limit the last update ran with
+ *   u_i  = s * (m_i / (sqrtf(v_i) / c + eps)) in fp32: what the last optimizer step subtracted from p_i.  m, v are the
+ *        moments as they stand (the step subtracts this expression of the very m, v it then stores); s = float32(lr /
+ *        (1 - beta1^t)) and c = float32(sqrt(1 - beta2^t)) are the two schedule scalars of the last optimizer step the
+ *        context ran, t the step count aleppo_export_optimizer returns
+ * Arithmetic: every element is widened to double and squared (exact); the sums are in double, in an order that is a
+ *   function of (H, A) only - per tensor of the private layout chunks of 4096 elements, inside a chunk each of 256
+ *   threads adds its 16 elements in index order and the threads are folded by a fixed tree, the chunks are added in index
+ *   order; no atomics, and the grid does not depend on the device.  A norm is sqrt of its sum, max-abs is exact.  A
+ *   non-finite element is counted and left out of every sum and maximum of its column group: p for columns 1-3 (count:
+ *   PARAM_NONFINITE), (g, m, v, u) for columns 4-9 (an element whose g, m, v or u is NaN / Inf counts once in
+ *   STEP_NONFINITE and enters neither GRAD_ nor UPDATE_ columns), so the norms stay informative when one element is
+ *   poisoned.  Row 12: SIZE and the counts are the sums of the rows, a norm is sqrt of the twelve sums of squares added
+ *   in row order, max-abs the maximum, the ratio formed from its own two norms.  Two reads without an update in between
+ *   are bit-identical.
+ * sections: a non-empty set of aleppo_tensor_stats_section bits.  Columns 0-3 belong to ALEPPO_TS_SEC_PARAMS and are valid
+ *   any time after aleppo_create (with that section alone only P is read).  Columns 4-9 belong to ALEPPO_TS_SEC_STEP and
+ *   need an aleppo_train to have succeeded on this context with no aleppo_load_params / aleppo_import_optimizer since
+ *   (those replace the state the step is recomputed from): otherwise ALEPPO_ERR_RUNTIME, and nothing is written.
+ *   UPDATE_RATIO needs PARAM_NORM, so STEP computes it whether or not PARAMS was requested.  The columns of a section
+ *   that was not requested are written as 0; SIZE is always written.
+ * Computed WHEN CALLED, on the context's stream (one pass that only reads, then one small launch), followed by that
+ *   stream's synchronise and one copy of 1040 bytes; the scratch is allocated on first use and kept until aleppo_destroy.
+ *   Never a collective: under data parallelism the parameters and the all-reduced gradient are the same on every rank, so
+ *   one rank reading suffices.  aleppo_train, a captured update (ALEPPO_OPT_UPDATE_GRAPH) and every other entry point
+ *   enqueue nothing for it; reading it neither re-arms a capture nor changes a bit of the run.
+ * Errors: sections 0 or with other bits, a null pointer or a wrong count are ALEPPO_ERR_INVALID_ARGUMENT (nothing is
+ *   written); ALEPPO_ERR_RUNTIME while a step is armed. */
+#define ALEPPO_TENSOR_STATS_ROWS 13   /* the 12 tensors in libtorch parameters() order, then the whole model */
+#define ALEPPO_TENSOR_STATS_COLS 10
+typedef enum { ALEPPO_TS_SEC_PARAMS = 1, ALEPPO_TS_SEC_STEP = 2 } aleppo_tensor_stats_section;
+typedef enum {
+  ALEPPO_TS_SIZE = 0,            /* elements of the tensor (alignment pads are not elements) */
+  ALEPPO_TS_PARAM_NORM = 1,      /* sqrt(sum p^2) */
+  ALEPPO_TS_PARAM_MAXABS = 2,
+  ALEPPO_TS_PARAM_NONFINITE = 3, /* how many p are NaN / Inf */
+  ALEPPO_TS_GRAD_NORM = 4,       /* of g: the elements aleppo_export_grads returns (last minibatch, clipped) */
+  ALEPPO_TS_GRAD_MAXABS = 5,
+  ALEPPO_TS_UPDATE_NORM = 6,     /* of u: what the last optimizer step subtracted from p */
+  ALEPPO_TS_UPDATE_MAXABS = 7,
+  ALEPPO_TS_UPDATE_RATIO = 8,    /* UPDATE_NORM / PARAM_NORM, IEEE double division (0 / 0 = NaN) */
+  ALEPPO_TS_STEP_NONFINITE = 9   /* elements whose g, m, v or u is NaN / Inf */
+} aleppo_tensor_stat;
+int aleppo_tensor_stats(aleppo_ctx *ctx, int sections, double *out, size_t count);
+
 /* ------------------------------------------------------------------ rollout (Rollout::rollout, rollout.cc:198-278)
  * Per slot t = 0..T-1 the caller does  act -> (step its emulators) -> push_frames -> record_step,
  * then finish_rollout.  aleppo_step = push_frames + record_step in one upload. */

@@ -45,6 +45,7 @@ struct Config {
   std::string checkpoint_path, resume;
   long checkpoint_interval = 0; // 0: only after the last rollout
   bool log_batch_stats = false; // extension: explained variance and value / return / advantage statistics (ALEPPO_F_BATCH_STATS)
+  bool log_tensor_stats = false; // extension: per-tensor gradient / parameter norms and update ratios (aleppo_tensor_stats)
   // extensions
   std::string precision = "fp32", rollout_precision = "fp32";
   bool device_preprocess = false; // emulators hand over raw frame pairs; gray LUT + resize + max run on the device (N2)
@@ -137,6 +138,7 @@ static Config load_config(const std::string &path) { // keys / defaults of src/b
   read_key(kv, "kl_coef", c.kl_coef);
   read_key(kv, "kl_target", c.kl_target);
   read_key(kv, "log_batch_stats", c.log_batch_stats);
+  read_key(kv, "log_tensor_stats", c.log_tensor_stats);
   c.kl_coef_set = kv.count("kl_coef") != 0;
   c.kl_target_set = kv.count("kl_target") != 0;
   if (!(c.kl_coef >= 0 && c.kl_coef < 3.0e38) || !(c.kl_target >= 0 && c.kl_target < 3.0e38)) // (beta is a float)
@@ -289,6 +291,7 @@ static HParams hparams_of(const Config &c) {
                                                     {"clip_value_loss", c.clip_value_loss},
                                                     {"minibatch_advantage_norm", c.minibatch_advantage_norm},
                                                     {"log_batch_stats", c.log_batch_stats},
+                                                    {"log_tensor_stats", c.log_tensor_stats},
                                                     {"reward_scaling", c.reward_scaling},
                                                     {"device_environments", c.device_environments}};
   for (const auto &f : when_set)

@@ -41,7 +41,11 @@
 // trainer logs kl_coef (the beta of the rollout's update) and mean_kl (d).  log_batch_stats: false (true: after every
 // rollout that is trained on, ALEPPO_F_BATCH_STATS is read - a collective under data parallelism, so every rank reads -
 // and explained_variance, mean_value / std_value, mean_return / std_return, mean_advantage / std_advantage are logged;
-// a NaN explained variance is logged as NaN).  clip_param_final, value_loss_coef_final, entropy_coef_final,
+// a NaN explained variance is logged as NaN).  log_tensor_stats: false (true: after each rollout's update rank 0 - the call
+// is not a collective, and every rank holds the same parameters and all-reduced gradient - reads both sections of
+// aleppo_tensor_stats and logs tensor_stats/<tensor>/grad_norm, /param_norm and /update_ratio for the twelve tensors
+// (conv1.w ... value.b) and total, and tensor_stats/nonfinite, the two non-finite counts of the whole model added; a
+// library without the entry point refuses the key at start-up).  clip_param_final, value_loss_coef_final, entropy_coef_final,
 // max_gradient_norm_final (absent: the value stays what the config says and no option is set; given: rollout i of
 // num_rollouts updates with v0 + (v_final - v0) * i / num_rollouts, computed in double and rounded to float once - the
 // shape of the learning-rate anneal, which never reaches its end value either - set through ALEPPO_OPT_CLIP_PARAM /
@@ -122,6 +126,8 @@
 #pragma weak aleppo_env_export_state
 #pragma weak aleppo_env_import_state
 #pragma weak aleppo_env_read
+// ... and the per-tensor statistics (log_tensor_stats: true)
+#pragma weak aleppo_tensor_stats
 
 static void check(aleppo_ctx *ctx, int rc) { // the reference throws at the same places
   if (rc == ALEPPO_OK)
@@ -247,6 +253,9 @@ static void refuse_missing_entry_points(const Config &cfg) {
                                    aleppo_env_import_state && aleppo_env_read))
     throw std::runtime_error("device_environments is set but this build's library has no device-resident environments "
                              "(aleppo_env_open is missing)");
+  if (cfg.log_tensor_stats && !aleppo_tensor_stats)
+    throw std::runtime_error("log_tensor_stats is set but this build's library has no per-tensor statistics "
+                             "(aleppo_tensor_stats is missing)");
 }
 
 // ------------------------------------------------------------------ start-up
@@ -591,6 +600,10 @@ static const std::pair<int, const char *> SAMPLE_FIELDS[5] = {{ALEPPO_M_TOTAL_LO
                                                               {ALEPPO_M_VALUE_LOSSES, "value_losses"},
                                                               {ALEPPO_M_ENTROPIES, "entropies"},
                                                               {ALEPPO_M_RATIO, "ratios"}};
+// the rows of aleppo_tensor_stats: libtorch parameters() order, then the whole model
+static const char *const TENSOR_STAT_NAMES[ALEPPO_TENSOR_STATS_ROWS] = {
+    "conv1.w", "conv1.b", "conv2.w", "conv2.b", "conv3.w", "conv3.b", "fc.w", "fc.b", "action.w", "action.b", "value.w",
+    "value.b", "total"};
 // metrics of every epoch that ran: per minibatch, and the per-sample planes of log_data's histograms ([epochs][N])
 struct Update {
   const size_t nmb, N, slots; // minibatches per epoch, samples per epoch, minibatch slots of num_epochs epochs
@@ -602,6 +615,7 @@ struct Update {
   size_t epochs_run = 0;
   float kl_beta = 0;   // the beta this update ran with ...
   double last_kl = 0;  // ... and the mean exact KL over the minibatches of its last epoch
+  double tensor_stats[ALEPPO_TENSOR_STATS_ROWS][ALEPPO_TENSOR_STATS_COLS] = {}; // log_tensor_stats, rank 0: after the update
   explicit Update(const Run &run)
       : nmb((size_t)run.cfg.num_mini_batches), N(run.E * run.T), slots((size_t)run.cfg.num_epochs * nmb), m(slots),
         kl(slots), cf(slots), adv_std(run.cfg.minibatch_advantage_norm ? slots : 0), mean_kl(run.kl_penalty() ? slots : 0),
@@ -655,6 +669,11 @@ static void update(Run &run, size_t r, Update &u) {
       else if (d > 1.5 * cfg.kl_target && std::isfinite(2.0f * beta))
         beta *= 2.0f;
     }
+  }
+  if (cfg.log_tensor_stats && run.rank == 0) { // (not a collective: every rank's answer would be the same)
+    Profile::Span sp(&run.prof, "aleppo_tensor_stats");
+    check(ctx, aleppo_tensor_stats(ctx, ALEPPO_TS_SEC_PARAMS | ALEPPO_TS_SEC_STEP, &u.tensor_stats[0][0],
+                                   (size_t)ALEPPO_TENSOR_STATS_ROWS * ALEPPO_TENSOR_STATS_COLS));
   }
 }
 
@@ -715,6 +734,17 @@ static void log_scalars(Run &run, const EpisodeLog &log, const BatchStatistics &
     logger.add_scalar("std_return", step, (float)s.batch[ALEPPO_BS_RETURN_STD]);
     logger.add_scalar("mean_advantage", step, (float)s.batch[ALEPPO_BS_ADVANTAGE_MEAN]);
     logger.add_scalar("std_advantage", step, (float)s.batch[ALEPPO_BS_ADVANTAGE_STD]);
+  }
+  if (cfg.log_tensor_stats && run.rank == 0) { // (of the last minibatch's gradient and the last optimizer step)
+    for (int k = 0; k < ALEPPO_TENSOR_STATS_ROWS; ++k) {
+      const std::string tag = std::string("tensor_stats/") + TENSOR_STAT_NAMES[k];
+      logger.add_scalar(tag + "/grad_norm", step, (float)u.tensor_stats[k][ALEPPO_TS_GRAD_NORM]);
+      logger.add_scalar(tag + "/param_norm", step, (float)u.tensor_stats[k][ALEPPO_TS_PARAM_NORM]);
+      logger.add_scalar(tag + "/update_ratio", step, (float)u.tensor_stats[k][ALEPPO_TS_UPDATE_RATIO]);
+    }
+    const double *total = u.tensor_stats[ALEPPO_TENSOR_STATS_ROWS - 1];
+    logger.add_scalar("tensor_stats/nonfinite", step,
+                      (float)(total[ALEPPO_TS_PARAM_NONFINITE] + total[ALEPPO_TS_STEP_NONFINITE]));
   }
   for (size_t k = 0; k < run.schedules.size(); ++k) // (the values this rollout's update ran with)
     logger.add_scalar(run.schedules[k].name, step, u.hyper_now[k]);
