@@ -96,25 +96,12 @@ extern "C" int aleppo_eval_push_frames(aleppo_ctx *c, const uint8_t *frames, int
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "unknown frame kind");
   const size_t L = (size_t)c->ev_L;
   const uint8_t *df = nullptr;
-  if (location == ALEPPO_DEVICE) {
-    if (reinterpret_cast<uintptr_t>(frames) % 16)
-      return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "device frames must be 16-byte aligned");
-    df = frames;
-  } else if (location == ALEPPO_HOST_MAPPED) { // the kernel reads the page-locked host buffer in place
-    void *dp = nullptr;
-    if (hipHostGetDevicePointer(&dp, const_cast<uint8_t *>(frames), 0) != hipSuccess || !dp)
-      return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT,
-                     "ALEPPO_HOST_MAPPED frames must lie in mapped page-locked host memory (hipHostMalloc / hipHostRegister)");
-    if (reinterpret_cast<uintptr_t>(dp) % 16)
-      return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "mapped frames must be 16-byte aligned");
-    df = static_cast<const uint8_t *>(dp);
-  } else if (location != ALEPPO_HOST) {
-    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "unknown frame location");
-  }
+  if (int rc = resolve_frames(c, frames, location, &df)) // (before the staging buffers or the stream are touched)
+    return rc;
   HIPCHK(c, hipEventSynchronize(c->ev_staged)); // the staging buffers are reused: the previous upload has run
   std::memcpy(c->ev_h_start, episode_start, L);
   HIPCHK(c, hipMemcpyAsync(c->ev_d_start, c->ev_h_start, L, hipMemcpyHostToDevice, c->stream));
-  if (location == ALEPPO_HOST) {
+  if (!df) { // ALEPPO_HOST
     const size_t bytes = L * (kind == ALEPPO_FRAMES_RAW_PAIR ? 2 * RAW_H * RAW_W : FRAME_PIX);
     std::memcpy(c->ev_h_frames, frames, bytes);
     HIPCHK(c, hipMemcpyAsync(c->ev_d_frames, c->ev_h_frames, bytes, hipMemcpyHostToDevice, c->stream));
@@ -152,17 +139,8 @@ extern "C" int aleppo_eval_act(aleppo_ctx *c, int rule, float param, const float
                    "aleppo_eval_open)");
   int64_t *pinned_dev = nullptr;
   HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(&pinned_dev), c->ev_h_actions, 0));
-  // do_act's forward at L samples on the lanes' stacks, into the lanes' scratch
-  const SampleMap map = eval_map();
-  if (patch) {
-    patch_act_convs(c->stream, c->ev_obs, map, Pcw(c, P_W1), Pf(c, P_B1), Pcw(c, P_W2), Pf(c, P_B2), Pcw(c, P_W3),
-                    Pf(c, P_B3), c->ev_a3, L);
-  } else {
-    conv1_fwd(c->stream, c->prec, c->ev_obs, map, Pcw(c, P_W1), Pf(c, P_B1), c->ev_a1, L);
-    conv2_fwd(c->stream, c->prec, c->ev_a1, Pcw(c, P_W2), Pf(c, P_B2), c->ev_a2, L);
-    conv3_fwd(c->stream, c->prec, c->ev_a2, Pcw(c, P_W3), Pf(c, P_B3), c->ev_a3, L);
-  }
-  fc_fwd_splitk(c->stream, c->prec, c->ev_a3, Pcw(c, P_WFC), c->ev_hpart, L, c->H);
+  // the rollout's acting forward at L samples on the lanes' stacks, into the lanes' scratch
+  act_forward(c, c->ev_obs, eval_map(), c->ev_a1, c->ev_a2, c->ev_a3, c->ev_hpart, L, false);
   const float *dn = nullptr;
   if (noise) { // (the previous call's head has finished - its ticket was waited for - so the staging is free)
     const size_t bytes = (size_t)L * (rule == ALEPPO_EVAL_SAMPLE ? c->A : 2) * 4;

@@ -138,6 +138,12 @@ int ensure_val_storage(aleppo_ctx *c);
 // api_rollout.hip, for aleppo_env_rollout (api_env.hip): slot `slot`'s acting kernels and head, and the GPU side of a step
 // whose episode-start flags are bytes already in device memory (start_device)
 int act_enqueue(aleppo_ctx *c, const float *noise, int slot);
+// api_rollout.hip, also for the evaluation lanes (api_eval.hip): the acting forward up to the head (patch kernels, or
+// conv1 -> conv2 -> conv3; then the split-K fc) at n samples into the given scratch, and where a kernel reads the
+// caller's frames (*dev_frames; null for ALEPPO_HOST, which the caller stages itself)
+void act_forward(aleppo_ctx *c, uint32_t *obs, SampleMap map, void *a1, void *a2, void *a3, float *hpart, int n,
+                 bool profiled);
+int resolve_frames(aleppo_ctx *c, const uint8_t *frames, int location, const uint8_t **dev_frames);
 int step_enqueue(aleppo_ctx *c, const uint8_t *df, int kind, int location, const StartBits *sb, const uint8_t *start_mapped,
                  int t, const uint8_t *start_device = nullptr);
 extern const double RS_INITIAL[RS_BLOCK];

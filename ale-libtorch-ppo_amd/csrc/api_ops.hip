@@ -418,8 +418,8 @@ extern "C" int aleppo_sample(int dev, const float *probs, const float *q, int64_
   OPCHK(p.up(probs, (size_t)E * A * 4));
   OPCHK(qq.up(q, (size_t)E * A * 4));
   OPCHK(a.up(nullptr, (size_t)E * 4));
-  launch_infer_head(op.st, nullptr, FC_SPLITS, nullptr, nullptr, nullptr, qq.as<float>(), 0, 0, nullptr, nullptr,
-                    a.as<int>(), nullptr, nullptr, 0, (int)E, 32, (int)A, p.as<float>());
+  launch_infer_head(op.st, nullptr, nullptr, nullptr, nullptr, qq.as<float>(), 0, 0, nullptr, nullptr, a.as<int>(),
+                    nullptr, nullptr, 0, (int)E, 32, (int)A, p.as<float>());
   std::vector<int> a32((size_t)E);
   OPCHK(op.down(a32.data(), a.p, (size_t)E * 4));
   for (int64_t e = 0; e < E; ++e)

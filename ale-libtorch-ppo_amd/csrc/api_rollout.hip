@@ -5,30 +5,43 @@
 using namespace aleppo;
 
 // ------------------------------------------------------------------ rollout
+// The acting forward at n samples of obs addressed by map, into the caller's scratch: conv stack + split-K fc; the head
+// kernel finishes the fc reduction.  profiled: the rollout's launches are bracketed for --profile, evaluation's are not.
+void aleppo::act_forward(aleppo_ctx *c, uint32_t *obs, SampleMap map, void *a1, void *a2, void *a3, float *hpart, int n,
+                         bool profiled) {
+  const auto begin = [&](int cls) {
+    if (profiled)
+      prof_begin(c, cls);
+  };
+  const auto end = [&](int cls) {
+    if (profiled)
+      prof_end(c, cls);
+  };
+  if (c->prec == ALEPPO_BF16 && use_patch_kernels()) { // one launch: a1/a2 never leave LDS
+    begin(ALEPPO_K_CONV1_FWD);
+    patch_act_convs(c->stream, obs, map, Pcw(c, P_W1), Pf(c, P_B1), Pcw(c, P_W2), Pf(c, P_B2), Pcw(c, P_W3),
+                    Pf(c, P_B3), a3, n);
+    end(ALEPPO_K_CONV1_FWD);
+  } else {
+    begin(ALEPPO_K_CONV1_FWD);
+    conv1_fwd(c->stream, c->prec, obs, map, Pcw(c, P_W1), Pf(c, P_B1), a1, n);
+    end(ALEPPO_K_CONV1_FWD);
+    begin(ALEPPO_K_CONV2_FWD);
+    conv2_fwd(c->stream, c->prec, a1, Pcw(c, P_W2), Pf(c, P_B2), a2, n);
+    end(ALEPPO_K_CONV2_FWD);
+    begin(ALEPPO_K_CONV3_FWD);
+    conv3_fwd(c->stream, c->prec, a2, Pcw(c, P_W3), Pf(c, P_B3), a3, n);
+    end(ALEPPO_K_CONV3_FWD);
+  }
+  begin(ALEPPO_K_FC_FWD);
+  fc_fwd_splitk(c->stream, c->prec, a3, Pcw(c, P_WFC), hpart, n, c->H);
+  end(ALEPPO_K_FC_FWD);
+}
+
 static int do_act(aleppo_ctx *c, const float *noise, int slot, void *logits_dst, void *values_dst, int *actions_dst,
                   bool publish) {
-  if (c->pre_acted != slot) { // conv stack + split-K fc at acting size; the head kernel finishes the fc reduction
-    const SampleMap map = slot_map(c, slot);
-    if (c->prec == ALEPPO_BF16 && use_patch_kernels()) { // one launch: a1/a2 never leave LDS
-      prof_begin(c, ALEPPO_K_CONV1_FWD);
-      patch_act_convs(c->stream, c->obs, map, Pcw(c, P_W1), Pf(c, P_B1), Pcw(c, P_W2), Pf(c, P_B2), Pcw(c, P_W3),
-                      Pf(c, P_B3), c->a3, c->E);
-      prof_end(c, ALEPPO_K_CONV1_FWD);
-    } else {
-    prof_begin(c, ALEPPO_K_CONV1_FWD);
-    conv1_fwd(c->stream, c->prec, c->obs, map, Pcw(c, P_W1), Pf(c, P_B1), c->a1, c->E);
-    prof_end(c, ALEPPO_K_CONV1_FWD);
-    prof_begin(c, ALEPPO_K_CONV2_FWD);
-    conv2_fwd(c->stream, c->prec, c->a1, Pcw(c, P_W2), Pf(c, P_B2), c->a2, c->E);
-    prof_end(c, ALEPPO_K_CONV2_FWD);
-    prof_begin(c, ALEPPO_K_CONV3_FWD);
-    conv3_fwd(c->stream, c->prec, c->a2, Pcw(c, P_W3), Pf(c, P_B3), c->a3, c->E);
-    prof_end(c, ALEPPO_K_CONV3_FWD);
-    }
-    prof_begin(c, ALEPPO_K_FC_FWD);
-    fc_fwd_splitk(c->stream, c->prec, c->a3, Pcw(c, P_WFC), c->hpart, c->E, c->H);
-    prof_end(c, ALEPPO_K_FC_FWD);
-  }
+  if (c->pre_acted != slot)
+    act_forward(c, c->obs, slot_map(c, slot), c->a1, c->a2, c->a3, c->hpart, c->E, true);
   c->pre_acted = -1; // (consumed; a3 / hpart are scratch again)
   const float *dn = nullptr;
   if (noise) { // (two staging halves: with a gated replay the next slot is enqueued before this copy has run)
@@ -45,9 +58,9 @@ static int do_act(aleppo_ctx *c, const float *noise, int slot, void *logits_dst,
     c->ticket++;
   if (c->dbg_no_publish)
     pinned_dev = nullptr;
-  launch_infer_head(c->stream, c->hpart, FC_SPLITS, Pf(c, P_BFC), Pf(c, P_WH), Pf(c, P_BH), dn, c->cfg.seed,
-                    c->rng_counter++, logits_dst, values_dst, actions_dst, pinned_dev, publish ? c->d_done : nullptr,
-                    c->ticket, c->E, c->H, c->A, nullptr, c->rt16);
+  launch_infer_head(c->stream, c->hpart, Pf(c, P_BFC), Pf(c, P_WH), Pf(c, P_BH), dn, c->cfg.seed, c->rng_counter++,
+                    logits_dst, values_dst, actions_dst, pinned_dev, publish ? c->d_done : nullptr, c->ticket, c->E, c->H,
+                    c->A, nullptr, c->rt16);
   prof_end(c, ALEPPO_K_INFER_HEAD);
   HIPCHK(c, hipGetLastError());
   return ALEPPO_OK;
@@ -148,15 +161,16 @@ extern "C" int aleppo_act(aleppo_ctx *c, const float *noise, const int64_t **act
   return ALEPPO_OK;
 }
 
-static int upload_frames(aleppo_ctx *c, const uint8_t *frames, int kind, int location, const uint8_t **dev_frames) {
-  const size_t bytes = (size_t)c->E * (kind == ALEPPO_FRAMES_RAW_PAIR ? 2 * RAW_H * RAW_W : FRAME_PIX);
+// Where a kernel reads the caller's frames.  ALEPPO_DEVICE: where they are; ALEPPO_HOST_MAPPED: the page-locked host buffer
+// in place, through its device address; ALEPPO_HOST: *dev_frames stays null - the caller stages them in its own buffers.
+// Touches nothing but *dev_frames and, on a refusal, the context's error.
+int aleppo::resolve_frames(aleppo_ctx *c, const uint8_t *frames, int location, const uint8_t **dev_frames) {
+  *dev_frames = nullptr;
   if (location == ALEPPO_DEVICE) {
     if (reinterpret_cast<uintptr_t>(frames) % 16)
       return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "device frames must be 16-byte aligned");
     *dev_frames = frames;
-    return ALEPPO_OK;
-  }
-  if (location == ALEPPO_HOST_MAPPED) { // the kernel reads the page-locked host buffer in place
+  } else if (location == ALEPPO_HOST_MAPPED) {
     void *dp = nullptr;
     if (hipHostGetDevicePointer(&dp, const_cast<uint8_t *>(frames), 0) != hipSuccess || !dp)
       return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT,
@@ -164,10 +178,17 @@ static int upload_frames(aleppo_ctx *c, const uint8_t *frames, int kind, int loc
     if (reinterpret_cast<uintptr_t>(dp) % 16)
       return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "mapped frames must be 16-byte aligned");
     *dev_frames = static_cast<const uint8_t *>(dp);
-    return ALEPPO_OK;
-  }
-  if (location != ALEPPO_HOST)
+  } else if (location != ALEPPO_HOST) {
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "unknown frame location");
+  }
+  return ALEPPO_OK;
+}
+
+static int upload_frames(aleppo_ctx *c, const uint8_t *frames, int kind, int location, const uint8_t **dev_frames) {
+  const int rc = resolve_frames(c, frames, location, dev_frames);
+  if (rc || *dev_frames)
+    return rc;
+  const size_t bytes = (size_t)c->E * (kind == ALEPPO_FRAMES_RAW_PAIR ? 2 * RAW_H * RAW_W : FRAME_PIX);
   std::memcpy(c->h_frames, frames, bytes);
   HIPCHK(c, hipMemcpyAsync(c->d_frames, c->h_frames, bytes, hipMemcpyHostToDevice, c->stream));
   *dev_frames = c->d_frames;

@@ -312,10 +312,10 @@ void launch_ingest(hipStream_t s, bool raw, const uint8_t *frames, const uint8_t
                    const StartBits *sbits, uint32_t *obs, int E, int slots, int t_src, int t_dst);
 void launch_copy_slot(hipStream_t s, uint32_t *obs, int E, int slots, int src, int dst);
 void launch_gate(hipStream_t s, unsigned long long *go_dev, unsigned long long seq, unsigned long long timeout_ticks);
-void launch_infer_head(hipStream_t s, const float *hpart, int nsplit, const float *bfc, const float *Wh,
-                       const float *bh, const float *noise, uint64_t seed, uint64_t counter, void *logits_t,
-                       void *values_t, int *actions_t, int64_t *pinned, unsigned int *done_ctr, long long ticket, int E,
-                       int H, int A, const float *probs_in = nullptr, bool rt16 = false);
+void launch_infer_head(hipStream_t s, const float *hpart, const float *bfc, const float *Wh, const float *bh,
+                       const float *noise, uint64_t seed, uint64_t counter, void *logits_t, void *values_t,
+                       int *actions_t, int64_t *pinned, unsigned int *done_ctr, long long ticket, int E, int H, int A,
+                       const float *probs_in = nullptr, bool rt16 = false);
 // head of the evaluation lanes: rule = aleppo_eval_rule, param = 1 / tau (SAMPLE) or epsilon (EPSILON_GREEDY); key = the
 // Philox key of the evaluation stream, counter = the evaluation counter; fp32 outputs; pinned / done_ctr never null
 void launch_eval_head(hipStream_t s, const float *hpart, const float *bfc, const float *Wh, const float *bh,

@@ -6,6 +6,7 @@
 #include "common.hpp"
 #include "gemm.hpp" // bf16 / vector typedefs
 #include "head_train.hpp" // f16, wave_sum, and what the head kernel's entry points share
+#include "act_head.hpp" // what the acting head's two entry points are built from
 #include <algorithm>
 #include <cstdlib>
 
@@ -147,28 +148,10 @@ void launch_gate(hipStream_t s, unsigned long long *go_dev, unsigned long long s
 // first maximum wins.  One wave per environment.  Actions go to the rollout slot AND to pinned host
 // memory (replaces the per-env .item<int64_t>() of rollout.cc:312-313).
 // ================================================================================================
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    c[1] = (uint32_t)p1;
-    c[3] = (uint32_t)p0;
-    c[0] = n0;
-    c[2] = n2;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
-
 // h = sum of the fc split-K slices + fc bias, formed on the fly (all NSPLIT*8 loads of a lane are independent).
-// Lane k < A owns action k (softmax term, noise, p/q); a wave arg-max picks the first maximum.
-// Hand-off to the host: actions go to pinned memory, then ONE ticket word is published after every wave's
-// stores are system-visible (fence + device counter, last wave publishes) - the host polls the ticket instead
-// of synchronising the stream, so PCIe write latency overlaps the host's next enqueue.
-// (Measured and rejected: one self-describing 8-byte word { ticket | action } per environment, no drain / counter /
-// ticket store, the host sweeping all E words - 5.4-5.6 vs 4.9-5.3 ms per 128-slot rollout on the same box: the host
-// then reads the very lines the device is still writing.)
+// Lane k < A owns action k (softmax term, noise, p/q); a wave arg-max picks the first maximum.  The pieces are
+// act_head.hpp's, shared with the evaluation lanes' head below.
+// Hand-off to the host: actions go to pinned memory, then ONE ticket word is published (publish_ticket).
 // probs_in != nullptr (the stateless aleppo_sample operator, train.cc:374-375 alone): the head is skipped and lane k
 // takes p_k from probs_in[e][k]; the division, the arg-max and the stores are the very same instructions.
 template <int NSPLIT, class RT>
@@ -179,130 +162,44 @@ __global__ __launch_bounds__(256) void infer_head_kernel(const float *__restrict
                                                           int *actions_t, int64_t *pinned, unsigned int *done_ctr,
                                                           long long ticket, int E, int H, int A,
                                                           const float *__restrict__ probs_in) {
-  extern __shared__ float sWh[]; // [(A+1)][H] head weights: ONE parallel round trip for the whole workgroup
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int e = blockIdx.x * 4 + wave;
-  // Lane l owns hidden units 4l .. 4l+3 and H/2 + 4l .. (H <= 512, H % 8 == 0): two 16-byte loads per split-K slice
-  // instead of eight scalar ones (the kernel is latency-bound on ~70 vector-memory instructions per wave; now 18),
-  // consecutive lanes on consecutive 16-byte pieces (coalesced, conflict-free LDS reads of the head weights).
   float hv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   const bool heads = probs_in == nullptr; // workgroup-uniform
-  if (heads) {
-    f32x4 part[NSPLIT][2];
-    const bool own = e < E && lane * 8 < H;
-#pragma unroll
-    for (int z = 0; z < NSPLIT; ++z) { // issue every split-K partial load first (independent)
-      const float *src = hpart + ((size_t)z * E + (own ? e : 0)) * H + (own ? lane * 4 : 0);
-      part[z][0] = *reinterpret_cast<const f32x4 *>(src);
-      part[z][1] = *reinterpret_cast<const f32x4 *>(src + H / 2);
-    }
-    {
-      const float *b = bfc + (own ? lane * 4 : 0);
-      const f32x4 b0 = *reinterpret_cast<const f32x4 *>(b), b1 = *reinterpret_cast<const f32x4 *>(b + H / 2);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        hv[i] = b0[i];
-        hv[4 + i] = b1[i];
-      }
-    }
-    for (int k = threadIdx.x; k < (A + 1) * H / 4; k += 256)
-      reinterpret_cast<f32x4 *>(sWh)[k] = reinterpret_cast<const f32x4 *>(Wh)[k];
-#pragma unroll
-    for (int z = 0; z < NSPLIT; ++z)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        hv[i] += part[z][0][i];
-        hv[4 + i] += part[z][1][i];
-      }
-  }
+  if (heads)
+    head_hidden<NSPLIT>(hpart, bfc, Wh, e, E, H, A, lane, hv);
   __syncthreads();
   if (e < E) {
     float zmine = 0.f; // lane a keeps logit a (a < A) / the value (a == A)
-    for (int a = 0; heads && a <= A; ++a) {
-      float s = 0.f;
-      if (lane * 8 < H) {
-        const f32x4 w0 = *reinterpret_cast<const f32x4 *>(sWh + a * H + lane * 4);
-        const f32x4 w1 = *reinterpret_cast<const f32x4 *>(sWh + a * H + H / 2 + lane * 4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          s += hv[i] * w0[i];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          s += hv[4 + i] * w1[i];
-      }
-      s = wave_sum(s) + bh[a];
-      if (lane == a)
-        zmine = s;
-    }
+    for (int a = 0; heads && a <= A; ++a)
+      head_dot(bh, hv, H, a, lane, zmine);
     const bool isact = lane < A;
-    float mx = isact ? zmine : -3.0e38f;
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1)
-      mx = fmaxf(mx, __shfl_xor(mx, o, 64)); // A <= 18 < 32
-    const float ex = isact ? expf(zmine - mx) : 0.f;
-    float sum = ex;
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1)
-      sum += __shfl_xor(sum, o, 64);
-    float q = 1.f;
-    if (isact) {
-      if (noise) {
-        q = noise[(size_t)e * A + lane];
-      } else { // Philox4x32-10 block (counter, env, lane/4): four actions share a block
-        uint32_t c[4] = {(uint32_t)counter, (uint32_t)(counter >> 32), (uint32_t)e, (uint32_t)(lane >> 2)};
-        philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-        const uint32_t w = (lane & 3) == 0 ? c[0] : (lane & 3) == 1 ? c[1] : (lane & 3) == 2 ? c[2] : c[3];
-        q = -logf(((float)(w >> 8) + 0.5f) * (1.0f / 16777216.0f)); // u in (0,1)
-      }
-    }
+    float sum;
+    const float ex = softmax_term(zmine, isact, 1.0f, sum);
+    const float q = exp1_noise(noise, seed, counter, e, A, lane);
     float pk = ex / sum; // softmax (train.cc:374)
     if (!heads)
       pk = isact ? probs_in[(size_t)e * A + lane] : 0.f;
-    float r = isact ? pk / q : -1.f; // p_k / q_k (train.cc:374-375)
-    int best = lane;
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) { // arg-max, ties -> lowest index (first maximum wins)
-      const float ro = __shfl_xor(r, o, 64);
-      const int bo = __shfl_xor(best, o, 64);
-      if (ro > r || (ro == r && bo < best)) {
-        r = ro;
-        best = bo;
-      }
-    }
+    const float r = isact ? pk / q : -1.f; // p_k / q_k (train.cc:374-375)
+    const int best = wave_argmax_first(r, lane);
     if (heads && isact)
       logits_t[(size_t)e * A + lane] = (RT)zmine;
     if (heads && lane == A)
       values_t[e] = (RT)zmine;
     if (lane == 0) {
-      actions_t[e] = best;
-      if (pinned) // system-scope (sc0 sc1, write-through) store straight to the mapped host buffer
-        __hip_atomic_store(pinned + e, (int64_t)best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      if (pinned)
+        store_action(actions_t, pinned, e, best);
+      else // (the stateless operator, the --profile mode that does not publish)
+        actions_t[e] = best;
     }
   }
-  if (done_ctr && pinned) {
-    // Publish.  The host only needs the actions; they were written with system-scope stores, so a full
-    // system-scope release (an L2 write-back of everything this rollout slot dirtied, ~4 us) is not needed:
-    // every storing wave drains its stores (vmcnt(0): acknowledged), the workgroup meets, one thread bumps the
-    // device counter and the last arriver - which therefore runs after every wave's acknowledged stores - writes
-    // the ticket, again at system scope.  All atomics are RELAXED on purpose (an agent / system release would emit
-    // the buffer_wbl2 this path exists to avoid); the order comes from the explicit vmcnt(0) drain, the barrier and
-    // the data dependency of the ticket store on the counter's return value.
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const unsigned int prev = __hip_atomic_fetch_add(done_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (prev == gridDim.x - 1) {
-        __hip_atomic_store(done_ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(reinterpret_cast<long long *>(pinned + E), ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-    }
-  }
+  if (done_ctr && pinned)
+    publish_ticket(pinned, done_ctr, ticket, E);
 }
-void launch_infer_head(hipStream_t s, const float *hpart, int nsplit, const float *bfc, const float *Wh,
-                       const float *bh, const float *noise, uint64_t seed, uint64_t counter, void *logits_t,
-                       void *values_t, int *actions_t, int64_t *pinned, unsigned int *done_ctr, long long ticket, int E,
-                       int H, int A, const float *probs_in, bool rt16) {
-  (void)nsplit; // always FC_SPLITS on the acting path
+void launch_infer_head(hipStream_t s, const float *hpart, const float *bfc, const float *Wh, const float *bh,
+                       const float *noise, uint64_t seed, uint64_t counter, void *logits_t, void *values_t,
+                       int *actions_t, int64_t *pinned, unsigned int *done_ctr, long long ticket, int E, int H, int A,
+                       const float *probs_in, bool rt16) {
   const dim3 g((E + 3) / 4), b(256);
   const size_t sm = (size_t)(A + 1) * H * sizeof(float);
   if (rt16)
@@ -317,17 +214,17 @@ void launch_infer_head(hipStream_t s, const float *hpart, int nsplit, const floa
 
 // ================================================================================================
 // Head of the evaluation lanes (aleppo_eval_act; the reference has no evaluation loop - SB3's predict(deterministic) /
-// EvalCallback, the epsilon-greedy evaluation of the DQN / PPO papers).  The forward half is infer_head_kernel's text:
-// the same split-K sum, the same head dot products in the same order, the same softmax and arg-max, so that at
-// rule = SAMPLE with 1 / tau = 1 (an exact multiplication) a lane computes what an environment of aleppo_act computes,
-// bit for bit.  One wave per lane; the rule is workgroup-uniform.  Outputs are always fp32 (they are not rollout planes).
+// EvalCallback, the epsilon-greedy evaluation of the DQN / PPO papers).  The forward half is infer_head_kernel's, call
+// for call (act_head.hpp): at rule = SAMPLE with 1 / tau = 1 (an exact multiplication) a lane computes what an
+// environment of aleppo_act computes, bit for bit.  One wave per lane; the rule is workgroup-uniform.  Outputs are
+// always fp32 (they are not rollout planes).
 //   GREEDY          r_k = z_k                                      -> first maximum
 //   SAMPLE          r_k = p_k / q_k, p = softmax(z * inv_tau)      -> first maximum (multinomial via Exp(1) noise)
 //   EPSILON_GREEDY  u < epsilon ? min((int)(w * A), A - 1) : the greedy action
 // Built-in noise (noise == nullptr): Philox4x32-10 under the key the host derived from config.seed and the evaluation
-// domain constant, counter words { n lo, n hi, lane, block } with n the evaluation counter (include/aleppo.h).
-// The hand-off to the host is infer_head_kernel's (system-scope action stores, drained, one ticket by the last workgroup)
-// on the lanes' OWN pinned buffer and arrival counter.
+// domain constant, counter words { n lo, n hi, lane, block } with n the evaluation counter; SAMPLE: block = action / 4,
+// EPSILON_GREEDY: block = 0, words 0 and 1 (include/aleppo.h).
+// The hand-off to the host is publish_ticket on the lanes' OWN pinned buffer and arrival counter.
 // ================================================================================================
 template <int NSPLIT>
 __global__ __launch_bounds__(256) void eval_head_kernel(const float *__restrict__ hpart, const float *__restrict__ bfc,
@@ -336,127 +233,46 @@ __global__ __launch_bounds__(256) void eval_head_kernel(const float *__restrict_
                                                          int rule, float param, float *logits_o, float *values_o,
                                                          int *actions_o, int64_t *pinned, unsigned int *done_ctr,
                                                          long long ticket, int E, int H, int A) {
-  extern __shared__ float sWh[]; // [(A+1)][H] head weights
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int e = blockIdx.x * 4 + wave;
   float hv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  {
-    f32x4 part[NSPLIT][2];
-    const bool own = e < E && lane * 8 < H;
-#pragma unroll
-    for (int z = 0; z < NSPLIT; ++z) { // issue every split-K partial load first (independent)
-      const float *src = hpart + ((size_t)z * E + (own ? e : 0)) * H + (own ? lane * 4 : 0);
-      part[z][0] = *reinterpret_cast<const f32x4 *>(src);
-      part[z][1] = *reinterpret_cast<const f32x4 *>(src + H / 2);
-    }
-    {
-      const float *b = bfc + (own ? lane * 4 : 0);
-      const f32x4 b0 = *reinterpret_cast<const f32x4 *>(b), b1 = *reinterpret_cast<const f32x4 *>(b + H / 2);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        hv[i] = b0[i];
-        hv[4 + i] = b1[i];
-      }
-    }
-    for (int k = threadIdx.x; k < (A + 1) * H / 4; k += 256)
-      reinterpret_cast<f32x4 *>(sWh)[k] = reinterpret_cast<const f32x4 *>(Wh)[k];
-#pragma unroll
-    for (int z = 0; z < NSPLIT; ++z)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        hv[i] += part[z][0][i];
-        hv[4 + i] += part[z][1][i];
-      }
-  }
+  head_hidden<NSPLIT>(hpart, bfc, Wh, e, E, H, A, lane, hv);
   __syncthreads();
   if (e < E) {
     float zmine = 0.f; // lane a keeps logit a (a < A) / the value (a == A)
-    for (int a = 0; a <= A; ++a) {
-      float s = 0.f;
-      if (lane * 8 < H) {
-        const f32x4 w0 = *reinterpret_cast<const f32x4 *>(sWh + a * H + lane * 4);
-        const f32x4 w1 = *reinterpret_cast<const f32x4 *>(sWh + a * H + H / 2 + lane * 4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          s += hv[i] * w0[i];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          s += hv[4 + i] * w1[i];
-      }
-      s = wave_sum(s) + bh[a];
-      if (lane == a)
-        zmine = s;
-    }
+    for (int a = 0; a <= A; ++a)
+      head_dot(bh, hv, H, a, lane, zmine);
     const bool isact = lane < A;
-    const bool sample = rule == ALEPPO_EVAL_SAMPLE; // workgroup-uniform
-    float r = isact ? zmine : -INFINITY;            // GREEDY / EPSILON_GREEDY: the logit itself
-    float u0 = 1.f, u1 = 0.f;                       // EPSILON_GREEDY's (u, w)
-    if (sample) {
-      float mx = isact ? zmine : -3.0e38f;
-#pragma unroll
-      for (int o = 16; o > 0; o >>= 1)
-        mx = fmaxf(mx, __shfl_xor(mx, o, 64)); // A <= 18 < 32
-      const float ex = isact ? expf((zmine - mx) * param) : 0.f; // param = 1 / tau
-      float sum = ex;
-#pragma unroll
-      for (int o = 16; o > 0; o >>= 1)
-        sum += __shfl_xor(sum, o, 64);
-      float q = 1.f;
-      if (isact) {
-        if (noise) {
-          q = noise[(size_t)e * A + lane];
-        } else { // block (n, lane, action / 4): four actions share a block
-          uint32_t c[4] = {(uint32_t)counter, (uint32_t)(counter >> 32), (uint32_t)e, (uint32_t)(lane >> 2)};
-          philox4x32_10(c, (uint32_t)key, (uint32_t)(key >> 32));
-          const uint32_t w = (lane & 3) == 0 ? c[0] : (lane & 3) == 1 ? c[1] : (lane & 3) == 2 ? c[2] : c[3];
-          q = -logf(((float)(w >> 8) + 0.5f) * (1.0f / 16777216.0f)); // u in (0,1)
-        }
-      }
+    float r = isact ? zmine : -INFINITY; // GREEDY / EPSILON_GREEDY: the logit itself
+    float u0 = 1.f, u1 = 0.f;            // EPSILON_GREEDY's (u, w)
+    if (rule == ALEPPO_EVAL_SAMPLE) {    // workgroup-uniform
+      float sum;
+      const float ex = softmax_term(zmine, isact, param, sum); // param = 1 / tau
+      const float q = exp1_noise(noise, key, counter, e, A, lane);
       const float pk = ex / sum;
       r = isact ? pk / q : -1.f;
     } else if (rule == ALEPPO_EVAL_EPSILON_GREEDY) { // (every lane holds the lane's two uniforms: no broadcast needed)
       if (noise) {
         u0 = noise[(size_t)e * 2];
         u1 = noise[(size_t)e * 2 + 1];
-      } else { // block (n, lane, 0): words 0 and 1
+      } else {
         uint32_t c[4] = {(uint32_t)counter, (uint32_t)(counter >> 32), (uint32_t)e, 0u};
         philox4x32_10(c, (uint32_t)key, (uint32_t)(key >> 32));
-        u0 = ((float)(c[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-        u1 = ((float)(c[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+        u0 = philox_unit(c[0]);
+        u1 = philox_unit(c[1]);
       }
     }
-    int best = lane;
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) { // arg-max, ties -> lowest index (first maximum wins)
-      const float ro = __shfl_xor(r, o, 64);
-      const int bo = __shfl_xor(best, o, 64);
-      if (ro > r || (ro == r && bo < best)) {
-        r = ro;
-        best = bo;
-      }
-    }
+    int best = wave_argmax_first(r, lane);
     if (rule == ALEPPO_EVAL_EPSILON_GREEDY && u0 < param) // param = epsilon
       best = min((int)(u1 * (float)A), A - 1);
     if (isact)
       logits_o[(size_t)e * A + lane] = zmine;
     if (lane == A)
       values_o[e] = zmine;
-    if (lane == 0) {
-      actions_o[e] = best;
-      __hip_atomic_store(pinned + e, (int64_t)best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    if (lane == 0)
+      store_action(actions_o, pinned, e, best);
   }
-  // publish: infer_head_kernel's hand-off (every storing wave drains, the workgroup meets, the last arriver writes the
-  // ticket at system scope; all atomics relaxed on purpose - see there)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned int prev = __hip_atomic_fetch_add(done_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (prev == gridDim.x - 1) {
-      __hip_atomic_store(done_ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(reinterpret_cast<long long *>(pinned + E), ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
+  publish_ticket(pinned, done_ctr, ticket, E);
 }
 void launch_eval_head(hipStream_t s, const float *hpart, const float *bfc, const float *Wh, const float *bh,
                       const float *noise, uint64_t key, uint64_t counter, int rule, float param, float *logits,

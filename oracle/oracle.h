@@ -96,7 +96,7 @@ int oracle_train(float *params, float *adam_m, float *adam_v, int64_t *adam_step
  *                        | kernels.hip:1301 - all (T) casts of the same fp32 value      |
  *  biases, action/value  | fp32: load_bias conv_patch.hpp:474, EpiBiasAct gemm.hpp:196, | no rounding
  *  heads                 | fwd_fused W.br conv_fwd_fused.hpp:167; head_train_kernel     |
- *                        | kernels.hip:713-724 and infer_head_kernel kernels.hip:183-252 |
+ *                        | kernels.hip:713-724 and act_head.hpp's head_dot              |
  *                        | read fp32 Wh / bh                                            |
  *  observations          | u8, widened exactly (gemm.hpp:55-75); 1/255 is conv1's fp32  | x = byte value;
  *                        | epilogue scale (conv_fwd_fused.hpp:306, conv_patch_launch.hip:| a1 = bf16(relu(S/255 + b1))
@@ -107,7 +107,7 @@ int oracle_train(float *params, float *adam_m, float *adam_v, int64_t *adam_step
  *                        | three launches conv_patch.hpp:357-360; acting                |
  *                        | conv_patch.hpp:504-505; generic gemm.hpp:196-199             |
  *  h (fc output)         | fp32 split-K slabs summed in head_train_kernel               | none (fp32)
- *                        | kernels.hip:666-673 / infer_head_kernel kernels.hip:219-230  |
+ *                        | kernels.hip:666-673 / act_head.hpp's head_hidden             |
  *  logits, value, loss,  | fp32 (kernels.hip:710-790)                                   | none; the loss and its
  *  planes, dlogits/dvalue|                                                              | gradient are oracle_ppo_loss
  *  dh                    | bf16: head_train_kernel kernels.hip:822 `dr[i] = (T)d[i]`    | dh_b = bf16(Wh^T dz)

@@ -50,14 +50,10 @@ def _frames(seed, n, raw):
 
 
 # ------------------------------------------------------------------ 1. same kernels as acting
-@pytest.mark.parametrize("prec", ["fp32", "bf16"])
-@pytest.mark.parametrize("raw", [0, 1], ids=["frames84", "rawpair"])
-@pytest.mark.parametrize("A", [4, 18])
-def test_sample_at_unit_temperature_is_aleppo_act_bit_for_bit(pkg, prec, raw, A):
+def _lanes_equal_acting(pkg, prec, raw, A, E, T, H):
     """L == E lanes fed the frames the rollout is fed: actions, logits and values of SAMPLE at tau = 1 with aleppo_act's
     noise equal aleppo_act's (fp32 planes), every lane, every slot - the rollout side through aleppo_step (fused ingest +
     acting launch on bf16 with 84x84 frames), the lanes through eval_push_frames + eval_act"""
-    E, T, H = 37, 5, 128
     kind = pkg.FRAMES_RAW_PAIR if raw else pkg.FRAMES_84
     eng = pkg.Engine(E, T, A, H, precision=pkg.BF16 if prec == "bf16" else pkg.FP32)
     eng.load_params(hf.fill_params(4100, H, A))
@@ -83,6 +79,22 @@ def test_sample_at_unit_temperature_is_aleppo_act_bit_for_bit(pkg, prec, raw, A)
         np.testing.assert_array_equal(ev[t][1], logits[:, t], err_msg=f"slot {t}: logits")
         np.testing.assert_array_equal(ev[t][2], values[:, t], err_msg=f"slot {t}: values")
     eng.close()
+
+
+@pytest.mark.parametrize("prec", ["fp32", "bf16"])
+@pytest.mark.parametrize("raw", [0, 1], ids=["frames84", "rawpair"])
+@pytest.mark.parametrize("A", [4, 18])
+def test_sample_at_unit_temperature_is_aleppo_act_bit_for_bit(pkg, prec, raw, A):
+    _lanes_equal_acting(pkg, prec, raw, A, E=37, T=5, H=128)
+
+
+@pytest.mark.parametrize("prec", ["fp32", "bf16"])
+@pytest.mark.parametrize("H", [32, 512])
+def test_sample_at_unit_temperature_is_aleppo_act_at_the_head_tile_extremes(pkg, prec, H):
+    """the branches of the shared head pieces that H = 128, E = 37 never reach: H = 32, where only 4 lanes of a wave own
+    hidden units; H = 512, where all 64 do and the LDS tile is at its largest, (18 + 1) * 512 * 4 = 38,912 bytes; and
+    E = 5, a second workgroup with one live wave and three that only meet the barrier of the ticket publish"""
+    _lanes_equal_acting(pkg, prec, 0, 18, E=5, T=2, H=H)
 
 
 # ------------------------------------------------------------------ 2. forward against the oracle for L != E
