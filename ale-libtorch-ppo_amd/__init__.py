@@ -69,6 +69,11 @@ TENSOR_STATS_SECTIONS = dict(params=TS_SEC_PARAMS, step=TS_SEC_STEP, all=TS_SEC_
 EVAL_GREEDY, EVAL_SAMPLE, EVAL_EPSILON_GREEDY = 0, 1, 2
 EVAL_RULES = dict(greedy=EVAL_GREEDY, sample=EVAL_SAMPLE, epsilon=EVAL_EPSILON_GREEDY)
 EVAL_FIELDS = dict(observations=0, logits=1, values=2, actions=3)
+# aleppo_eval_env_field: the device-resident evaluation environments (Engine.eval_env_open / eval_env_run / eval_env_state /
+# eval_env_read / eval_env_episodes)
+EEF_FRAMES, EEF_EPISODE_RETURNS, EEF_EPISODE_LENGTHS, EEF_GAME_RETURNS, EEF_GAME_LENGTHS = 0, 1, 2, 3, 4
+EVAL_ENV_FIELDS = dict(frames=EEF_FRAMES, episode_returns=EEF_EPISODE_RETURNS, episode_lengths=EEF_EPISODE_LENGTHS,
+                       game_returns=EEF_GAME_RETURNS, game_lengths=EEF_GAME_LENGTHS)
 # device-resident environments (Engine.env_open / env_rollout / env_state / env_read / env_episodes)
 ENV_SYNTHETIC = 0
 ENV_FIELDS = dict(frames=0, episode_returns=1, episode_lengths=2, game_returns=3, game_lengths=4, step_ms=5)
@@ -124,10 +129,13 @@ EXPORTS = [
     "aleppo_host_alloc", "aleppo_host_free", "aleppo_arm_step", "aleppo_release_step", "aleppo_device_check",
     "aleppo_read_sample_order", "aleppo_set_batch_values",
     "aleppo_eval_open", "aleppo_eval_push_frames", "aleppo_eval_act", "aleppo_eval_read",
+    "aleppo_eval_set_counter",
     "aleppo_export_reward_scale", "aleppo_import_reward_scale", "aleppo_reward_scale",
     "aleppo_export_rollout_state", "aleppo_import_rollout_state", "aleppo_state_digest",
     "aleppo_tensor_stats",
     "aleppo_env_open", "aleppo_env_rollout", "aleppo_env_export_state", "aleppo_env_import_state", "aleppo_env_read",
+    "aleppo_eval_env_open", "aleppo_eval_env_run", "aleppo_eval_env_export_state", "aleppo_eval_env_import_state",
+    "aleppo_eval_env_read",
 ]
 
 
@@ -711,6 +719,10 @@ class Engine:
         self._c(lib().aleppo_eval_act(self._ctx, C.c_int(r), C.c_float(param), _ptr(n), C.byref(p)))
         return np.ctypeslib.as_array(p, shape=(self.eval_lanes,))
 
+    def eval_set_counter(self, counter):
+        """aleppo_eval_set_counter: the evaluation counter n of the built-in generator (the next eval_act draws block n)"""
+        self._c(lib().aleppo_eval_set_counter(self._ctx, C.c_uint64(int(counter))))
+
     def eval_read(self, name):
         """aleppo_eval_read: "observations" uint8 [L,4,84,84] (the stacks now), or "logits" float32 [L,A] / "values"
         float32 [L] / "actions" int64 [L] of the last eval_act"""
@@ -766,6 +778,54 @@ class Engine:
         el, gl = self.env_read("episode_lengths").ravel(), self.env_read("game_lengths").ravel()
         return (self.env_read("episode_returns").ravel()[el > 0], el[el > 0],
                 self.env_read("game_returns").ravel()[gl > 0], gl[gl > 0])
+
+    # -- device-resident evaluation environments --
+    def eval_env_open(self, frame_kind=FRAMES_84, seed_base=0, max_steps=108000, max_return=-1.0, run_steps=64,
+                      kind=ENV_SYNTHETIC, reserved=0):
+        """aleppo_eval_env_open: one synthetic environment per evaluation lane in device memory, lane l seeded
+        seed_base + l; run_steps: the most steps one eval_env_run may take (the rows of the log planes); again with
+        another seed_base: the environments start over under the new seeds, the stacks and the counter stay"""
+        cfg = EnvConfig(int(kind), int(frame_kind), int(seed_base), int(max_steps), float(max_return), int(reserved))
+        self._c(lib().aleppo_eval_env_open(self._ctx, C.byref(cfg), C.c_int32(int(run_steps))))
+        self.eval_env_frame_kind, self.eval_env_run_steps = int(frame_kind), int(run_steps)
+
+    def eval_env_run(self, rule="greedy", temperature=1.0, epsilon=0.0, steps=1):
+        """aleppo_eval_env_run: `steps` evaluation steps - act, environment step and render, ingest - enqueued without a
+        host wait, under eval_act's rules with the built-in generator"""
+        r = EVAL_RULES[rule] if isinstance(rule, str) else int(rule)
+        param = temperature if r == EVAL_SAMPLE else epsilon if r == EVAL_EPSILON_GREEDY else 0.0
+        self._c(lib().aleppo_eval_env_run(self._ctx, C.c_int(r), C.c_float(param), C.c_int32(int(steps))))
+
+    def eval_env_state(self):
+        """aleppo_eval_env_export_state: a structured array [L] of ENV_STATE_DTYPE"""
+        st = np.zeros(self.eval_lanes, ENV_STATE_DTYPE)
+        self._c(lib().aleppo_eval_env_export_state(self._ctx, _ptr(st), C.c_size_t(st.size)))
+        return st
+
+    def load_eval_env_state(self, state):
+        """aleppo_eval_env_import_state: what eval_env_state returned (values a run cannot reach are refused)"""
+        st = np.ascontiguousarray(state, dtype=ENV_STATE_DTYPE)
+        self._c(lib().aleppo_eval_env_import_state(self._ctx, _ptr(st), C.c_size_t(st.size)))
+
+    def eval_env_read(self, name):
+        """aleppo_eval_env_read: "frames" uint8 [L,84,84] / [L,2,210,160] (the frame buffer now); the last eval_env_run's
+        step-major [S,L] log planes "episode_returns" / "game_returns" float32 and "episode_lengths" / "game_lengths"
+        uint32 (0: nothing ended in that step; rows past the run's steps are zero)"""
+        L, S = getattr(self, "eval_lanes", 1), getattr(self, "eval_env_run_steps", 1)
+        raw = getattr(self, "eval_env_frame_kind", FRAMES_84) == FRAMES_RAW_PAIR
+        shp, dt = dict(frames=((L, 2, 210, 160) if raw else (L, 84, 84), np.uint8), episode_returns=((S, L), np.float32),
+                       episode_lengths=((S, L), np.uint32), game_returns=((S, L), np.float32),
+                       game_lengths=((S, L), np.uint32))[name]
+        out = np.zeros(shp, dt)
+        self._c(lib().aleppo_eval_env_read(self._ctx, EVAL_ENV_FIELDS[name], _ptr(out), C.c_size_t(out.nbytes)))
+        return out
+
+    def eval_env_episodes(self):
+        """the last eval_env_run's episode log, compacted in step-then-lane order: (returns float32, lengths uint32,
+        game_returns, game_lengths) of the episodes / games that ended in it"""
+        el, gl = self.eval_env_read("episode_lengths").ravel(), self.eval_env_read("game_lengths").ravel()
+        return (self.eval_env_read("episode_returns").ravel()[el > 0], el[el > 0],
+                self.eval_env_read("game_returns").ravel()[gl > 0], gl[gl > 0])
 
     # -- multi GPU --
     @staticmethod

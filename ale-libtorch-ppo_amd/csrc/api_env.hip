@@ -23,7 +23,7 @@ static size_t env_frame_bytes(const aleppo_ctx *c) { // per environment
 static size_t env_plane(const aleppo_ctx *c) { return (size_t)c->T * c->E; } // elements of one log plane
 
 // the constructor's state (emulator.hpp: SyntheticAtari's member initialisers) with start = 1 and reward 0
-static void env_initial(const aleppo_env_config &cfg, std::vector<aleppo_env_state> &st) {
+void aleppo::env_initial(const aleppo_env_config &cfg, std::vector<aleppo_env_state> &st) {
   for (size_t e = 0; e < st.size(); ++e) {
     aleppo_env_state s{};
     s.rng = (cfg.seed_base + e) * 0x9E3779B97F4A7C15ull + 12345;
@@ -34,6 +34,28 @@ static void env_initial(const aleppo_env_config &cfg, std::vector<aleppo_env_sta
     s.start = 1;
     st[e] = s;
   }
+}
+// what a run cannot reach (aleppo_env_import_state, aleppo_eval_env_import_state)
+const char *aleppo::env_state_invalid(const aleppo_env_state &s) {
+  auto pix = [](int v) { return v >= 0 && v <= 83; };
+  if (s.lives < 0 || s.lives > 5)
+    return "lives must be in 0..5";
+  if (s.paddle < 4 || s.paddle > 79)
+    return "paddle must be in 4..79";
+  if (!pix(s.ball_x) || !pix(s.ball_y) || !pix(s.prev_x) || !pix(s.prev_y))
+    return "ball coordinates must be in 0..83";
+  if ((s.dx != 1 && s.dx != -1) || (s.dy != 1 && s.dy != -1))
+    return "dx and dy must be +1 or -1";
+  if (s.bricks < 0)
+    return "bricks must not be negative";
+  if (s.start > 1 || s.game_over > 1)
+    return "flags must be 0 or 1";
+  if (s.reserved[0] || s.reserved[1])
+    return "reserved bytes must be 0";
+  if (!std::isfinite(s.episode_return) || !std::isfinite(s.reward) || !std::isfinite(s.ep_ret) ||
+      !std::isfinite(s.game_ret))
+    return "a float is not finite";
+  return nullptr;
 }
 static int env_upload(aleppo_ctx *c, const aleppo_env_state *st) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -156,31 +178,10 @@ extern "C" int aleppo_env_import_state(aleppo_ctx *c, const aleppo_env_state *st
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "env_import_state: num_envs is not the context's");
   if (int rc = env_between_rollouts(c, "env_import_state"))
     return rc;
-  for (size_t e = 0; e < num_envs; ++e) { // what a run cannot reach is refused before anything changes
-    const aleppo_env_state &s = states[e];
-    const char *bad = nullptr;
-    auto pix = [](int v) { return v >= 0 && v <= 83; };
-    if (s.lives < 0 || s.lives > 5)
-      bad = "lives must be in 0..5";
-    else if (s.paddle < 4 || s.paddle > 79)
-      bad = "paddle must be in 4..79";
-    else if (!pix(s.ball_x) || !pix(s.ball_y) || !pix(s.prev_x) || !pix(s.prev_y))
-      bad = "ball coordinates must be in 0..83";
-    else if ((s.dx != 1 && s.dx != -1) || (s.dy != 1 && s.dy != -1))
-      bad = "dx and dy must be +1 or -1";
-    else if (s.bricks < 0)
-      bad = "bricks must not be negative";
-    else if (s.start > 1 || s.game_over > 1)
-      bad = "flags must be 0 or 1";
-    else if (s.reserved[0] || s.reserved[1])
-      bad = "reserved bytes must be 0";
-    else if (!std::isfinite(s.episode_return) || !std::isfinite(s.reward) || !std::isfinite(s.ep_ret) ||
-             !std::isfinite(s.game_ret))
-      bad = "a float is not finite";
-    if (bad)
+  for (size_t e = 0; e < num_envs; ++e) // what a run cannot reach is refused before anything changes
+    if (const char *bad = env_state_invalid(states[e]))
       return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT,
                      "env_import_state: environment " + std::to_string(e) + ": " + bad);
-  }
   return env_upload(c, states);
 }
 

@@ -114,40 +114,37 @@ extern "C" int aleppo_eval_push_frames(aleppo_ctx *c, const uint8_t *frames, int
   return ALEPPO_OK;
 }
 
-extern "C" int aleppo_eval_act(aleppo_ctx *c, int rule, float param, const float *noise, const int64_t **actions_pinned) {
-  CHECK_EVAL(c);
-  float kparam = 0.f;
+// the one check of an evaluation rule and its parameter (aleppo_eval_act, aleppo_eval_env_run)
+int aleppo::eval_check_rule(aleppo_ctx *c, int rule, float param, bool has_noise, float *kparam) {
+  *kparam = 0.f;
   if (rule == ALEPPO_EVAL_GREEDY) {
-    if (param != 0.f || noise) // (a NaN param compares unequal too)
+    if (param != 0.f || has_noise) // (a NaN param compares unequal too)
       return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "eval_act: the greedy rule takes param = 0 and no noise");
   } else if (rule == ALEPPO_EVAL_SAMPLE) {
     if (!(param > 0.f) || !std::isfinite(param) || !std::isfinite(1.0f / param))
       return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "eval_act: the temperature must be finite and > 0");
-    kparam = 1.0f / param; // once, in fp32
+    *kparam = 1.0f / param; // once, in fp32
   } else if (rule == ALEPPO_EVAL_EPSILON_GREEDY) {
     if (!(param >= 0.f && param <= 1.f))
       return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "eval_act: epsilon must be in [0, 1]");
-    kparam = param;
+    *kparam = param;
   } else {
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "eval_act: unknown rule");
   }
-  const int L = c->ev_L;
   const bool patch = c->prec == ALEPPO_BF16 && use_patch_kernels();
   if (!patch && !c->ev_a1)
     return set_err(c, ALEPPO_ERR_RUNTIME,
                    "eval_act: the lanes were opened without conv1 / conv2 scratch (set ALEPPO_OPT_GENERIC_CONV before "
                    "aleppo_eval_open)");
+  return ALEPPO_OK;
+}
+// the acting half of one evaluation step: nothing here waits for the device
+int aleppo::eval_act_enqueue(aleppo_ctx *c, int rule, float kparam, const float *dn) {
+  const int L = c->ev_L;
   int64_t *pinned_dev = nullptr;
   HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(&pinned_dev), c->ev_h_actions, 0));
   // the rollout's acting forward at L samples on the lanes' stacks, into the lanes' scratch
   act_forward(c, c->ev_obs, eval_map(), c->ev_a1, c->ev_a2, c->ev_a3, c->ev_hpart, L, false);
-  const float *dn = nullptr;
-  if (noise) { // (the previous call's head has finished - its ticket was waited for - so the staging is free)
-    const size_t bytes = (size_t)L * (rule == ALEPPO_EVAL_SAMPLE ? c->A : 2) * 4;
-    std::memcpy(c->ev_h_noise, noise, bytes);
-    HIPCHK(c, hipMemcpyAsync(c->ev_d_noise, c->ev_h_noise, bytes, hipMemcpyHostToDevice, c->stream));
-    dn = c->ev_d_noise;
-  }
   launch_eval_head(c->stream, c->ev_hpart, Pf(c, P_BFC), Pf(c, P_WH), Pf(c, P_BH), dn, c->cfg.seed ^ EVAL_KEY_DOMAIN,
                    c->ev_counter, rule, kparam, c->ev_logits, c->ev_values, c->ev_actions, pinned_dev, c->ev_d_done,
                    c->ev_ticket + 1, L, c->H, c->A);
@@ -155,6 +152,24 @@ extern "C" int aleppo_eval_act(aleppo_ctx *c, int rule, float param, const float
   c->ev_ticket++;
   c->ev_counter++;
   c->ev_acted = true;
+  return ALEPPO_OK;
+}
+
+extern "C" int aleppo_eval_act(aleppo_ctx *c, int rule, float param, const float *noise, const int64_t **actions_pinned) {
+  CHECK_EVAL(c);
+  float kparam = 0.f;
+  if (int rc = eval_check_rule(c, rule, param, noise != nullptr, &kparam))
+    return rc;
+  const int L = c->ev_L;
+  const float *dn = nullptr;
+  if (noise) { // (the previous call's head has finished - its ticket was waited for - so the staging is free)
+    const size_t bytes = (size_t)L * (rule == ALEPPO_EVAL_SAMPLE ? c->A : 2) * 4;
+    std::memcpy(c->ev_h_noise, noise, bytes);
+    HIPCHK(c, hipMemcpyAsync(c->ev_d_noise, c->ev_h_noise, bytes, hipMemcpyHostToDevice, c->stream));
+    dn = c->ev_d_noise;
+  }
+  if (int rc = eval_act_enqueue(c, rule, kparam, dn))
+    return rc;
   // wait for the ticket the head publishes after the actions (bounded spin, then a real synchronise)
   volatile long long *tk = reinterpret_cast<volatile long long *>(c->ev_h_actions + L);
   const auto t0 = std::chrono::steady_clock::now();
@@ -171,6 +186,12 @@ extern "C" int aleppo_eval_act(aleppo_ctx *c, int rule, float param, const float
   if (actions_pinned)
     *actions_pinned = c->ev_h_actions;
   CHECK_ASYNC(c);
+  return ALEPPO_OK;
+}
+
+extern "C" int aleppo_eval_set_counter(aleppo_ctx *c, uint64_t counter) {
+  CHECK_EVAL(c);
+  c->ev_counter = counter; // (host state only: every head launch takes the counter as an argument)
   return ALEPPO_OK;
 }
 

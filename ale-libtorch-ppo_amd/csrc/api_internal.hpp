@@ -1,5 +1,5 @@
 // api_internal.hpp - what the C ABI's translation units share (api_core.hip, api_rollout.hip, api_train.hip,
-// api_batch.hip, api_eval.hip, api_env.hip, api_state.hip, api_ops.hip): the entry-point guard macros and the host-side helpers.  Host code only; the
+// api_batch.hip, api_eval.hip, api_eval_env.hip, api_env.hip, api_state.hip, api_ops.hip): the entry-point guard macros and the host-side helpers.  Host code only; the
 // helpers are defined in api_core.hip unless noted.
 #pragma once
 #include "common.hpp"
@@ -146,6 +146,15 @@ void act_forward(aleppo_ctx *c, uint32_t *obs, SampleMap map, void *a1, void *a2
 int resolve_frames(aleppo_ctx *c, const uint8_t *frames, int location, const uint8_t **dev_frames);
 int step_enqueue(aleppo_ctx *c, const uint8_t *df, int kind, int location, const StartBits *sb, const uint8_t *start_mapped,
                  int t, const uint8_t *start_device = nullptr);
+// api_eval.hip, also for the device-resident evaluation (api_eval_env.hip): THE check of aleppo_eval_act's rule / param /
+// noise (*kparam: what the head kernel takes), and one evaluation step's acting half - act_forward on the lanes' stacks,
+// the evaluation head with device noise dn (or the built-in generator), then ev_ticket++ / ev_counter++
+int eval_check_rule(aleppo_ctx *c, int rule, float param, bool has_noise, float *kparam);
+int eval_act_enqueue(aleppo_ctx *c, int rule, float kparam, const float *dn);
+// api_env.hip, also for api_eval_env.hip: the constructor's state of environment seed_base + e with start = 1 and reward 0,
+// and what aleppo_env_import_state refuses in one environment's state (null: nothing)
+void env_initial(const aleppo_env_config &cfg, std::vector<aleppo_env_state> &st);
+const char *env_state_invalid(const aleppo_env_state &s);
 extern const double RS_INITIAL[RS_BLOCK];
 int ensure_rs_storage(aleppo_ctx *c);
 bool rs_state_valid(const double stats[3]);

@@ -288,6 +288,17 @@ struct Ctx {
   float *env_log = nullptr;        // [4][T][E]: episode returns, episode lengths (u32), game returns, game lengths (u32)
   bool rec_on_device = false;      // the rollout being collected wrote its step records on the device (aleppo_env_rollout)
   ProfClass env_prof;              // ALEPPO_ENV_F_STEP_MS: events around the environment kernel while profiling is on
+  // ---- device-resident evaluation environments (aleppo_eval_env_open), one per evaluation lane: ONE allocation - the
+  // frame buffer, two alternating state arrays, the four [S][L] log planes and the L start-at-entry bytes the ingest reads;
+  // members of their own (nothing of env_* above); nothing is allocated or enqueued on a context that never opens them
+  bool ee_open = false;
+  aleppo_env_config ee_cfg{};
+  int ee_S = 0;                    // max_run_steps: the rows of a log plane
+  uint8_t *ee_blk = nullptr;       // the allocation; the frames are at its start (16-byte aligned)
+  aleppo_env_state *ee_state[2] = {nullptr, nullptr};
+  int ee_cur = 0;                  // ee_state[ee_cur] is the state between two steps
+  float *ee_log = nullptr;         // [4][S][L]: episode returns, episode lengths (u32), game returns, game lengths (u32)
+  uint8_t *ee_start = nullptr;     // [L] start-at-entry bytes of the last step
   bool prof_on = false;
   bool serial_update = false; // ALEPPO_OPT_SERIAL_UPDATE: every update kernel on the main stream
   bool dbg_no_publish = false;

@@ -165,41 +165,12 @@ ENV_HD uint32_t env_pixel_raw(const EnvRawRects &r, int x, int y) {
 }
 
 #ifdef __HIPCC__
-// ================================================================================================
-// One agent step of every environment and its frame.  Grid (E, parts): environment e is blockIdx.x, and its frame is
-// shared out over `parts` workgroups (ENV_RAW_PARTS for a raw pair, whose 67 KB of stores would otherwise run on one CU per
-// environment; 1 for an 84x84 frame).  The game logic is a few dozen uniform integer operations: every lane of every part
-// computes it redundantly from the state of the previous slot (in) - no LDS broadcast, no barrier - and lane 0 of part 0
-// writes the new state to the OTHER state array (out: the two alternate, so no lane can read what has already been
-// written), the slot's step record entries and the episode-log entries.  Then all lanes render: each byte of the frame is
-// computed from (paddle, ball, previous ball, bricks) and written exactly once, 16 at a time; a raw row of 160 bytes is
-// ten such stores, so a store never crosses a row.
-// rec: the device step record of this slot { float r[E]; u8 term[E]; u8 trunc[E]; u8 start[E] }; log_*: row t of the
-// four [T][E] planes; actions: the int32 actions the acting head wrote for this slot.
-// ================================================================================================
 typedef __attribute__((ext_vector_type(4))) unsigned int env_u32x4;
 constexpr int ENV_RAW_PARTS = 4;
-template <bool RAW>
-__global__ __launch_bounds__(256) void env_step_kernel(const aleppo_env_state *__restrict__ in, aleppo_env_state *__restrict__ out,
-                                                        const int *__restrict__ actions, uint8_t *__restrict__ frames,
-                                                        uint8_t *__restrict__ rec, float *__restrict__ log_ep_ret,
-                                                        uint32_t *__restrict__ log_ep_len, float *__restrict__ log_game_ret,
-                                                        uint32_t *__restrict__ log_game_len, int E, uint64_t max_steps,
-                                                        float max_return) {
-  const int e = blockIdx.x, tid = threadIdx.x;
-  aleppo_env_state s = in[e];
-  const EnvSlotOut o = env_slot(s, actions[e], max_steps, max_return);
-  if (tid == 0 && blockIdx.y == 0) {
-    out[e] = s;
-    reinterpret_cast<float *>(rec)[e] = o.reward;
-    rec[4 * (size_t)E + e] = o.term;
-    rec[5 * (size_t)E + e] = o.trunc;
-    rec[6 * (size_t)E + e] = o.start;
-    log_ep_ret[e] = o.ep_ret;
-    log_ep_len[e] = o.ep_len;
-    log_game_ret[e] = o.game_ret;
-    log_game_len[e] = o.game_len;
-  }
+// the frame of environment e from its state s, shared out over gridDim.y workgroups: all 256 lanes of each store
+// 16 bytes at a time (env_step_kernel below, and eval_env_step_kernel of env_eval.hpp)
+template <bool RAW> __device__ __forceinline__ void env_render(uint8_t *__restrict__ frames, int e, const aleppo_env_state &s) {
+  const int tid = threadIdx.x;
   if (RAW) {
     constexpr int ROW16 = 160 / 16, FRAME16 = 210 * ROW16; // 16-byte stores per row / per frame
     env_u32x4 *dst = reinterpret_cast<env_u32x4 *>(frames + (size_t)e * (2 * 210 * 160));
@@ -238,6 +209,41 @@ __global__ __launch_bounds__(256) void env_step_kernel(const aleppo_env_state *_
       dst[c] = v;
     }
   }
+}
+// ================================================================================================
+// One agent step of every environment and its frame.  Grid (E, parts): environment e is blockIdx.x, and its frame is
+// shared out over `parts` workgroups (ENV_RAW_PARTS for a raw pair, whose 67 KB of stores would otherwise run on one CU per
+// environment; 1 for an 84x84 frame).  The game logic is a few dozen uniform integer operations: every lane of every part
+// computes it redundantly from the state of the previous slot (in) - no LDS broadcast, no barrier - and lane 0 of part 0
+// writes the new state to the OTHER state array (out: the two alternate, so no lane can read what has already been
+// written), the slot's step record entries and the episode-log entries.  Then all lanes render: each byte of the frame is
+// computed from (paddle, ball, previous ball, bricks) and written exactly once, 16 at a time; a raw row of 160 bytes is
+// ten such stores, so a store never crosses a row.
+// rec: the device step record of this slot { float r[E]; u8 term[E]; u8 trunc[E]; u8 start[E] }; log_*: row t of the
+// four [T][E] planes; actions: the int32 actions the acting head wrote for this slot.
+// ================================================================================================
+template <bool RAW>
+__global__ __launch_bounds__(256) void env_step_kernel(const aleppo_env_state *__restrict__ in, aleppo_env_state *__restrict__ out,
+                                                        const int *__restrict__ actions, uint8_t *__restrict__ frames,
+                                                        uint8_t *__restrict__ rec, float *__restrict__ log_ep_ret,
+                                                        uint32_t *__restrict__ log_ep_len, float *__restrict__ log_game_ret,
+                                                        uint32_t *__restrict__ log_game_len, int E, uint64_t max_steps,
+                                                        float max_return) {
+  const int e = blockIdx.x, tid = threadIdx.x;
+  aleppo_env_state s = in[e];
+  const EnvSlotOut o = env_slot(s, actions[e], max_steps, max_return);
+  if (tid == 0 && blockIdx.y == 0) {
+    out[e] = s;
+    reinterpret_cast<float *>(rec)[e] = o.reward;
+    rec[4 * (size_t)E + e] = o.term;
+    rec[5 * (size_t)E + e] = o.trunc;
+    rec[6 * (size_t)E + e] = o.start;
+    log_ep_ret[e] = o.ep_ret;
+    log_ep_len[e] = o.ep_len;
+    log_game_ret[e] = o.game_ret;
+    log_game_len[e] = o.game_len;
+  }
+  env_render<RAW>(frames, e, s);
 }
 #endif
 

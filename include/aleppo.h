@@ -527,6 +527,11 @@ int aleppo_eval_act(aleppo_ctx *ctx, int rule, float param, const float *noise, 
  * ALEPPO_ERR_INVALID_ARGUMENT; fields 1-3 before the first aleppo_eval_act (since aleppo_eval_open) are
  * ALEPPO_ERR_RUNTIME. */
 int aleppo_eval_read(aleppo_ctx *ctx, int field, void *dst, size_t bytes);
+/* Sets the evaluation counter n of the built-in generator (what aleppo_eval_open sets to 0 and every aleppo_eval_act
+ * advances by one) and nothing else: the next act draws block n.  For a caller that evaluates in chunks
+ * (aleppo_eval_env_run) and wants its NEXT evaluation to draw what a step-by-step caller, which stops at the step its last
+ * episode ends in, would draw.  ALEPPO_ERR_RUNTIME before aleppo_eval_open and while a step is armed. */
+int aleppo_eval_set_counter(aleppo_ctx *ctx, uint64_t counter);
 
 /* ------------------------------------------------------------------ device-resident environments (no reference
  * counterpart: the reference's emulators are host threads, rollout.cc:280-328)
@@ -612,6 +617,62 @@ int aleppo_env_import_state(aleppo_ctx *ctx, const aleppo_env_state *states, siz
  * in the order collect() appends.  A wrong byte count or an unknown field is ALEPPO_ERR_INVALID_ARGUMENT; before
  * aleppo_env_open ALEPPO_ERR_RUNTIME. */
 int aleppo_env_read(aleppo_ctx *ctx, int field, void *dst, size_t bytes);
+
+/* ------------------------------------------------------------------ device-resident evaluation environments (no
+ * reference counterpart)
+ * L device-resident SyntheticAtari instances, one per evaluation lane, behind the lanes of aleppo_eval_open: one call
+ * enqueues `steps` whole evaluation steps - per step the lanes' acting forward, the evaluation head, the environment
+ * step and render, and the ingest - with nothing returning to the host in between.  The run is byte for byte the run the
+ * host loop aleppo_eval_act -> emulator -> aleppo_eval_push_frames would have produced (the environments are stepped as
+ * aleppo_env_rollout steps its own: a start lane resets and ignores its action), so the two can be mixed step by step.
+ * Isolation: the five calls change nothing the rollout or the update can observe - not the rollout's stacks and planes,
+ * t, the acting generator's counter, the pre-computed acting scratch of aleppo_step, aleppo_act's pinned buffer and
+ * ticket, Adam state, metrics or a captured update.  A training run with these calls inserted at any point where no
+ * step is armed (between an aleppo_step and the aleppo_act that follows it included) is bit-identical to the run without
+ * them.  While a step is armed all five fail with ALEPPO_ERR_RUNTIME like every other stateful entry point; before
+ * aleppo_eval_env_open the other four are ALEPPO_ERR_RUNTIME.  The environments are local to a rank: nothing is
+ * exchanged under data parallelism and no call is a collective.  Nothing the device-resident TRAINING environments can
+ * observe changes - not their state, frames, log or aleppo_state_digest - and their calls change nothing here.  The
+ * context's own stream only, no hipFree, no device-wide synchronise.  A context that never calls aleppo_eval_env_open
+ * allocates and enqueues nothing for any of this. */
+typedef enum {
+  ALEPPO_EEF_FRAMES = 0,          /* uint8 [L,84,84] or [L,2,210,160]: the frame buffer right now */
+  ALEPPO_EEF_EPISODE_RETURNS = 1, /* float  [S,L] step-major: return of the episode that ended in (step, lane) of the LAST run */
+  ALEPPO_EEF_EPISODE_LENGTHS = 2, /* uint32 [S,L]: its length in agent steps; 0 = none ended there */
+  ALEPPO_EEF_GAME_RETURNS = 3,    /* float  [S,L]: the same for games (an episode that ended with game over) */
+  ALEPPO_EEF_GAME_LENGTHS = 4     /* uint32 [S,L] */
+} aleppo_eval_env_field;
+/* Needs aleppo_eval_open first (ALEPPO_ERR_RUNTIME otherwise); L is that call's lane count.  Lane l becomes
+ * SyntheticAtari(cfg->seed_base + l, max_steps, max_return, A, raw) in the constructor's state with start = 1 and reward
+ * 0.  Allocates - in this call and never later, in one block kept until aleppo_destroy - the frame buffer, two alternating
+ * state arrays and the four [S,L] log planes (zeroed), S = max_run_steps in [1, 1024].  Called again with the same kind,
+ * frame kind, max_steps, max_return and S and ANY seed_base it re-seeds every lane to the constructor's state of the new
+ * seed and zeroes the log, and touches neither the lanes' stacks nor the evaluation counter nor the ticket (every lane
+ * then starts with a start step, which overwrites all four stack positions); with another kind, frame kind, budget or S
+ * it is ALEPPO_ERR_RUNTIME.  A null config, an unknown kind or frame kind, a non-zero reserved field or S out of range is
+ * ALEPPO_ERR_INVALID_ARGUMENT. */
+int aleppo_eval_env_open(aleppo_ctx *ctx, const aleppo_env_config *cfg, int32_t max_run_steps);
+/* `steps` evaluation steps, 1 <= steps <= S, with the built-in generator (there is no noise argument); rule and param
+ * are aleppo_eval_act's and are checked by the same code.  For s in [0, steps), on the context's stream and with no host
+ * wait: aleppo_eval_act's kernels (the head publishes the actions and the ticket to the lanes' pinned buffer as always;
+ * the evaluation counter and the ticket advance by one), the environment kernel - it reads the int32 actions the head
+ * just wrote, steps and renders every lane's environment and writes the start-at-entry bytes and row s of the log - and
+ * aleppo_eval_push_frames' ingest on the frame buffer with those start bytes and the gray LUT of aleppo_set_gray_lut.
+ * Returns once everything is enqueued.  Afterwards the lanes are where `steps` host-driven steps would have left them -
+ * stacks, the ALEPPO_EF_* fields of the last step, evaluation counter, ticket and pinned buffer - so an aleppo_eval_act or
+ * aleppo_eval_push_frames may follow and a host-driven step may precede.  Log rows [0, steps) hold this run's records,
+ * rows [steps, S) are zero.  A launch that fails after part of the run is on the stream fails the context, as in
+ * aleppo_env_rollout; a refused call changes nothing. */
+int aleppo_eval_env_run(aleppo_ctx *ctx, int rule, float param, int32_t steps);
+/* As aleppo_env_export_state / aleppo_env_import_state with num_lanes == L and the same refusals (one validator; a
+ * refused import changes nothing), but valid whenever no step is armed: there is no "between rollouts" condition.  Both
+ * synchronise the context's stream. */
+int aleppo_eval_env_export_state(aleppo_ctx *ctx, aleppo_env_state *states, size_t num_lanes);
+int aleppo_eval_env_import_state(aleppo_ctx *ctx, const aleppo_env_state *states, size_t num_lanes);
+/* Read an aleppo_eval_env_field; synchronises the context's stream like aleppo_eval_read.  Compacted in
+ * step-then-lane order the log planes are the episodes in the order the host loop would have met them.  A wrong byte
+ * count or an unknown field is ALEPPO_ERR_INVALID_ARGUMENT; before aleppo_eval_env_open ALEPPO_ERR_RUNTIME. */
+int aleppo_eval_env_read(aleppo_ctx *ctx, int field, void *dst, size_t bytes);
 
 /* ------------------------------------------------------------------ multi-GPU (no reference counterpart)
  * One process per GPU.  Rank 0 creates the id, the launcher broadcasts its bytes, every rank calls

@@ -38,6 +38,9 @@ struct Config {
   size_t eval_interval = 0, eval_environments = 8, eval_episodes = 10;
   std::string eval_rule = "greedy";
   double eval_temperature = 1.0, eval_epsilon = 0.05;
+  // extension: the evaluation's environments live on the device too (aleppo_eval_env_open / aleppo_eval_env_run)
+  bool device_evaluation = false;
+  size_t device_evaluation_steps = 32; // the S of the open and the chunk of every run
   // extension: return-based reward scaling in place of the reward clamp (ALEPPO_OPT_REWARD_SCALE / _CLIP)
   bool reward_scaling = false;
   double reward_scale_clip = 10.0;
@@ -201,6 +204,17 @@ static Config load_config(const std::string &path) { // keys / defaults of src/b
     read_key(kv, "eval_epsilon", c.eval_epsilon);
     if (!(c.eval_epsilon >= 0 && c.eval_epsilon <= 1))
       throw std::runtime_error("eval_epsilon must be in [0, 1]");
+    read_key(kv, "device_evaluation", c.device_evaluation);
+    if (c.device_evaluation && interval == 0)
+      throw std::runtime_error("device_evaluation needs eval_interval > 0");
+    if (kv.count("device_evaluation_steps")) {
+      const long steps = as<long>(kv, "device_evaluation_steps", 32);
+      if (!c.device_evaluation) // (nothing else reads it)
+        throw std::runtime_error("device_evaluation_steps needs device_evaluation: true");
+      if (steps < 1 || steps > 1024)
+        throw std::runtime_error("device_evaluation_steps must be in [1, 1024]");
+      c.device_evaluation_steps = (size_t)steps;
+    }
   }
   read_key(kv, "checkpoint_path", c.checkpoint_path);
   read_key(kv, "resume", c.resume);
@@ -285,6 +299,8 @@ static HParams hparams_of(const Config &c) {
                                        {"eval_rule", (double)eval_rule(c)},
                                        {"eval_temperature", c.eval_temperature},
                                        {"eval_epsilon", c.eval_epsilon}});
+  if (c.device_evaluation)
+    h.numbers.emplace_back("device_evaluation_steps", (double)c.device_evaluation_steps);
   h.flags = {{"record_observation", c.record_observation}, {"record_video", c.record_video},
              {"cuda_graph", c.cuda_graph}, {"deterministic", c.deterministic}};
   const std::pair<const char *, bool> when_set[] = {{"shuffle_minibatches", c.shuffle_minibatches},
@@ -293,7 +309,8 @@ static HParams hparams_of(const Config &c) {
                                                     {"log_batch_stats", c.log_batch_stats},
                                                     {"log_tensor_stats", c.log_tensor_stats},
                                                     {"reward_scaling", c.reward_scaling},
-                                                    {"device_environments", c.device_environments}};
+                                                    {"device_environments", c.device_environments},
+                                                    {"device_evaluation", c.device_evaluation}};
   for (const auto &f : when_set)
     if (f.second)
       h.flags.emplace_back(f.first, true);

@@ -81,8 +81,16 @@
 // training, and the episode log and the step / episode counters come from the library's log planes and the exported
 // environment state.  The run is the run with host environments, bit for bit, and so is the checkpoint file: save exports
 // the device state into the fields the host emulators are saved in, resume imports them, and a file written in one mode
-// resumes in the other.  Evaluation keeps its host emulators and lanes.  A library without the entry points refuses the key
-// at start-up).
+// resumes in the other.  Evaluation keeps its host emulators and lanes unless device_evaluation is set.  A library without
+// the entry points refuses the key at start-up).
+// device_evaluation: false (true, needs eval_interval: each evaluation's environments are the library's device-resident
+// ones behind the lanes - aleppo_eval_env_open with the seed base the host path uses, then aleppo_eval_env_run in chunks of
+// device_evaluation_steps, default 32, in [1, 1024], until eval_episodes are in hand, taken from the log planes in
+// step-then-lane order: the first eval_episodes to finish, as the host path takes them.  No host emulators, no worker-pool
+// pass and no mapped frame buffer exist for evaluation then.  The device runs up to device_evaluation_steps - 1 steps past
+// the step the host path stops at, on environments that are thrown away; the evaluation counter is set back to where the
+// host path would have left it - aleppo_eval_set_counter - so that every later evaluation draws what it draws there and
+// the eval/* scalars are the host path's bit for bit.  A library without the entry points refuses the key at start-up).
 // Data parallelism (no reference counterpart): start one process per GPU with RANK / WORLD_SIZE / LOCAL_RANK
 // in the environment (torchrun / mpirun style).  Rank r owns the contiguous environment block
 // [r * E / W, (r + 1) * E / W) and GPU LOCAL_RANK; rank 0 creates the RCCL id, hands it to the others through the file
@@ -128,6 +136,13 @@
 #pragma weak aleppo_env_read
 // ... and the per-tensor statistics (log_tensor_stats: true)
 #pragma weak aleppo_tensor_stats
+// ... and the device-resident evaluation environments (device_evaluation: true)
+#pragma weak aleppo_eval_env_open
+#pragma weak aleppo_eval_env_run
+#pragma weak aleppo_eval_env_export_state
+#pragma weak aleppo_eval_env_import_state
+#pragma weak aleppo_eval_env_read
+#pragma weak aleppo_eval_set_counter
 
 static void check(aleppo_ctx *ctx, int rc) { // the reference throws at the same places
   if (rc == ALEPPO_OK)
@@ -170,7 +185,8 @@ struct Run {
   uint8_t *start_mapped = nullptr; // episode-start flags at slot entry, where the armed ingest kernel reads them
   bool slot_ahead = false;
   std::vector<HyperSchedule> schedules;
-  EnvSet eval_set; // the evaluation lanes' environments (empty without eval_interval)
+  EnvSet eval_set; // the evaluation lanes' environments (empty without eval_interval, and with device_evaluation)
+  uint64_t eval_counter = 0; // device_evaluation: the evaluation counter where the host path would have left it
   size_t first_rollout = 0, rollouts_done = 0;
   std::optional<WorkerPool> pool; // (last: its threads are joined before anything they touch goes away)
 
@@ -253,6 +269,10 @@ static void refuse_missing_entry_points(const Config &cfg) {
                                    aleppo_env_import_state && aleppo_env_read))
     throw std::runtime_error("device_environments is set but this build's library has no device-resident environments "
                              "(aleppo_env_open is missing)");
+  if (cfg.device_evaluation && !(aleppo_eval_env_open && aleppo_eval_env_run && aleppo_eval_env_export_state &&
+                                 aleppo_eval_env_import_state && aleppo_eval_env_read && aleppo_eval_set_counter))
+    throw std::runtime_error("device_evaluation is set but this build's library has no device-resident evaluation "
+                             "environments (aleppo_eval_env_open is missing)");
   if (cfg.log_tensor_stats && !aleppo_tensor_stats)
     throw std::runtime_error("log_tensor_stats is set but this build's library has no per-tensor statistics "
                              "(aleppo_tensor_stats is missing)");
@@ -410,11 +430,13 @@ static void create_environments(Run &run) {
   // evaluation (eval_interval): full episodes on emulators of its own through the evaluation lanes.  Nothing there touches
   // the training emulators, their flags or the rollout: the lanes have their own stacks, scratch and noise stream.
   if (const size_t L = cfg.eval_interval > 0 ? cfg.eval_environments : 0) {
-    run.eval_set.start.assign(L, 1);
-    run.eval_set.results.resize(L);
-    run.eval_set.what = "evaluation environment";
     check(run.ctx, aleppo_eval_open(run.ctx, (int32_t)L));
-    check(run.ctx, aleppo_host_alloc(run.ctx, L * fbytes, reinterpret_cast<void **>(&run.eval_set.frames)));
+    if (!cfg.device_evaluation) { // (device_evaluation: the lanes' environments are the library's, opened per evaluation)
+      run.eval_set.start.assign(L, 1);
+      run.eval_set.results.resize(L);
+      run.eval_set.what = "evaluation environment";
+      check(run.ctx, aleppo_host_alloc(run.ctx, L * fbytes, reinterpret_cast<void **>(&run.eval_set.frames)));
+    }
   }
 }
 
@@ -781,17 +803,56 @@ static void log_histograms(Run &run, const Update &u, int64_t step) {
 }
 
 // ------------------------------------------------------------------ ... evaluate
+static void log_evaluation(Run &run, int64_t step, const std::vector<float> &returns, const std::vector<size_t> &lengths) {
+  run.logger->add_scalar("eval/episode_return_mean", step, meanf(returns));
+  run.logger->add_scalar("eval/episode_return_max", step, *std::max_element(returns.begin(), returns.end()));
+  run.logger->add_scalar("eval/episode_length_mean", step, meanf(lengths));
+  run.logger->add_scalar("eval/episodes", step, (float)returns.size());
+}
+// device_evaluation: the same episodes from the library's log planes, a chunk of S steps at a time
+static void evaluate_on_device(Run &run, uint64_t seed_base, int64_t step) {
+  const Config &cfg = run.cfg;
+  aleppo_ctx *ctx = run.ctx;
+  const size_t L = cfg.eval_environments, S = cfg.device_evaluation_steps;
+  aleppo_env_config ec{};
+  ec.kind = ALEPPO_ENV_SYNTHETIC;
+  ec.frame_kind = frame_kind(cfg);
+  ec.seed_base = seed_base;
+  ec.max_steps = cfg.max_steps;
+  ec.max_return = (float)cfg.max_return;
+  check(ctx, aleppo_eval_env_open(ctx, &ec, (int32_t)S)); // (again: fresh environments under this evaluation's seeds)
+  check(ctx, aleppo_eval_set_counter(ctx, run.eval_counter));
+  std::vector<float> ret(S * L), returns;
+  std::vector<uint32_t> len(S * L);
+  std::vector<size_t> lengths;
+  while (returns.size() < cfg.eval_episodes) {
+    check(ctx, aleppo_eval_env_run(ctx, eval_rule(cfg), eval_param(cfg), (int32_t)S));
+    check(ctx, aleppo_eval_env_read(ctx, ALEPPO_EEF_EPISODE_RETURNS, ret.data(), ret.size() * sizeof(float)));
+    check(ctx, aleppo_eval_env_read(ctx, ALEPPO_EEF_EPISODE_LENGTHS, len.data(), len.size() * sizeof(uint32_t)));
+    for (size_t s = 0; s < S && returns.size() < cfg.eval_episodes; ++s) { // step, then lane: the host path's order
+      run.eval_counter++; // (the host path acts once more only while episodes are missing)
+      for (size_t i = 0; i < L && returns.size() < cfg.eval_episodes; ++i)
+        if (len[s * L + i]) {
+          returns.push_back(ret[s * L + i]);
+          lengths.push_back(len[s * L + i]);
+        }
+    }
+  }
+  log_evaluation(run, step, returns, lengths);
+}
 static void evaluate(Run &run, size_t round, int64_t step) {
   Profile::Span sp(&run.prof, "evaluate");
   const Config &cfg = run.cfg;
   aleppo_ctx *ctx = run.ctx;
   EnvSet &set = run.eval_set;
-  const size_t L = set.size();
+  const size_t L = cfg.eval_environments;
   // fresh emulators per evaluation, seeded past every rank's training environments (env0 + i < total_environments)
+  const size_t seed_base = cfg.total_environments + (round * (size_t)run.world + (size_t)run.rank) * L;
+  if (cfg.device_evaluation)
+    return evaluate_on_device(run, seed_base, step);
   set.envs.clear();
   for (size_t i = 0; i < L; ++i)
-    set.envs.emplace_back(cfg.total_environments + (round * (size_t)run.world + (size_t)run.rank) * L + i, cfg.max_steps,
-                          cfg.max_return, run.A, cfg.device_preprocess);
+    set.envs.emplace_back(seed_base + i, cfg.max_steps, cfg.max_return, run.A, cfg.device_preprocess);
   std::fill(set.start.begin(), set.start.end(), 1);
   std::vector<float> ret(L, 0.f), returns;
   std::vector<size_t> len(L, 0), lengths;
@@ -822,10 +883,7 @@ static void evaluate(Run &run, size_t round, int64_t step) {
   // the teardown's host_free) touch the buffer (aleppo_eval_read synchronises the context's stream)
   std::vector<float> last_values(L);
   check(ctx, aleppo_eval_read(ctx, ALEPPO_EF_VALUES, last_values.data(), L * sizeof(float)));
-  run.logger->add_scalar("eval/episode_return_mean", step, meanf(returns));
-  run.logger->add_scalar("eval/episode_return_max", step, *std::max_element(returns.begin(), returns.end()));
-  run.logger->add_scalar("eval/episode_length_mean", step, meanf(lengths));
-  run.logger->add_scalar("eval/episodes", step, (float)returns.size());
+  log_evaluation(run, step, returns, lengths);
 }
 
 // ------------------------------------------------------------------ ... checkpoint; and resume, its mirror
