@@ -83,9 +83,19 @@ ENV_STATE_DTYPE = np.dtype([("rng", "<u8"), ("steps", "<u8"), ("ep_len", "<u8"),
                             ("dx", "<i4"), ("dy", "<i4"), ("bricks", "<i4"), ("episode_return", "<f4"), ("reward", "<f4"),
                             ("ep_ret", "<f4"), ("game_ret", "<f4"), ("start", "u1"), ("game_over", "u1"),
                             ("reserved", "u1", (2,))])
+# episode recorders (Engine.rec_open / rec_count / rec_read / rec_clear): aleppo_rec_source, the content bits,
+# aleppo_rec_field, and aleppo_rec_step, 32 bytes without padding (include/aleppo.h)
+REC_ROLLOUT, REC_EVAL = 0, 1
+REC_SOURCES = dict(rollout=REC_ROLLOUT, eval=REC_EVAL)
+REC_FRAMES, REC_OBSERVATION = 1, 2
+REC_FIELDS = dict(steps=0, logits=1, frames=2, observations=3)
+REC_MAX_CAPACITY = 65536
+REC_STEP_DTYPE = np.dtype([("ordinal", "<u8"), ("action", "<i4"), ("reward", "<f4"), ("value", "<f4"), ("start", "u1"),
+                           ("terminated", "u1"), ("truncated", "u1"), ("game_over", "u1"), ("lives", "<i4"),
+                           ("reserved", "<i4")])
 KERNEL_CLASSES = dict(ingest=0, gae=1, head=2, adam=3, conv1_fwd=4, conv2_fwd=5, conv3_fwd=6, fc_fwd=7, fc_dgrad=8,
                       fc_wgrad=9, conv3_dgrad=10, conv3_wgrad=11, conv2_dgrad=12, conv2_wgrad=13, conv1_wgrad=14,
-                      reduce=15, infer_head=16, act_fused=17, conv_fwd=18, conv_bwd=19)
+                      reduce=15, infer_head=16, act_fused=17, conv_fwd=18, conv_bwd=19, rec_capture=20)
 
 # every symbol include/aleppo.h declares (checked by tests/test_abi.py against the header text)
 # aleppo_set_option keys (include/aleppo.h)
@@ -136,6 +146,7 @@ EXPORTS = [
     "aleppo_env_open", "aleppo_env_rollout", "aleppo_env_export_state", "aleppo_env_import_state", "aleppo_env_read",
     "aleppo_eval_env_open", "aleppo_eval_env_run", "aleppo_eval_env_export_state", "aleppo_eval_env_import_state",
     "aleppo_eval_env_read",
+    "aleppo_rec_open", "aleppo_rec_count", "aleppo_rec_read", "aleppo_rec_clear",
 ]
 
 
@@ -161,6 +172,22 @@ class Config(C.Structure):
 class EnvConfig(C.Structure):
     _fields_ = [("kind", C.c_int32), ("frame_kind", C.c_int32), ("seed_base", C.c_uint64), ("max_steps", C.c_uint64),
                 ("max_return", C.c_float), ("reserved", C.c_int32)]
+
+
+class RecConfig(C.Structure):
+    _fields_ = [("source", C.c_int32), ("index", C.c_int32), ("content", C.c_int32), ("capacity", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
+class RecStep(C.Structure):
+    _fields_ = [("ordinal", C.c_uint64), ("action", C.c_int32), ("reward", C.c_float), ("value", C.c_float),
+                ("start", C.c_uint8), ("terminated", C.c_uint8), ("truncated", C.c_uint8), ("game_over", C.c_uint8),
+                ("lives", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RecCounts(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("dropped", C.c_uint64), ("next_ordinal", C.c_uint64), ("capacity", C.c_int32),
+                ("frame_bytes", C.c_int32), ("observation_bytes", C.c_int32), ("actions", C.c_int32)]
 
 
 class MinibatchMetrics(C.Structure):
@@ -826,6 +853,53 @@ class Engine:
         el, gl = self.eval_env_read("episode_lengths").ravel(), self.eval_env_read("game_lengths").ravel()
         return (self.eval_env_read("episode_returns").ravel()[el > 0], el[el > 0],
                 self.eval_env_read("game_returns").ravel()[gl > 0], gl[gl > 0])
+
+    # -- episode recorders --
+    def rec_open(self, source="rollout", index=0, frames=True, observation=True, capacity=None):
+        """aleppo_rec_open: record environment `index` of env_rollout ("rollout") or lane `index` of eval_env_run ("eval")
+        into an append log of `capacity` rows (default: T, or the evaluation environments' run_steps); again with the
+        same arguments: an empty log, ordinal 0"""
+        src = REC_SOURCES[source] if isinstance(source, str) else int(source)
+        if capacity is None:
+            capacity = self.T if src == REC_ROLLOUT else getattr(self, "eval_env_run_steps", 1)
+        cfg = RecConfig(src, int(index), (REC_FRAMES if frames else 0) | (REC_OBSERVATION if observation else 0),
+                        int(capacity))
+        self._c(lib().aleppo_rec_open(self._ctx, C.byref(cfg)))
+
+    def rec_count(self, source="rollout"):
+        """aleppo_rec_count: dict(rows, dropped, next_ordinal, capacity, frame_bytes, observation_bytes, actions); host
+        state, no synchronise"""
+        src = REC_SOURCES[source] if isinstance(source, str) else int(source)
+        n = RecCounts()
+        self._c(lib().aleppo_rec_count(self._ctx, C.c_int(src), C.byref(n)))
+        return {k: int(getattr(n, k)) for k, _ in RecCounts._fields_}
+
+    def rec_read(self, source, name, first=0, rows=None):
+        """aleppo_rec_read: rows [first, first + rows) (default: to the end of the log) of "steps" (REC_STEP_DTYPE
+        [rows]), "logits" (float32 [rows, A]), "frames" (uint8 [rows, 84, 84] or [rows, 2, 210, 160]) or "observations"
+        (uint8 [rows, 84, 84])"""
+        src = REC_SOURCES[source] if isinstance(source, str) else int(source)
+        n = self.rec_count(src)
+        if rows is None:
+            rows = max(n["rows"] - int(first), 0)
+        rows = int(rows)
+        if name == "steps":
+            out = np.zeros(rows, REC_STEP_DTYPE)
+        elif name == "logits":
+            out = np.zeros((rows, self.A), np.float32)
+        elif name == "frames":
+            out = np.zeros((rows, 2, 210, 160) if n["frame_bytes"] == 2 * 210 * 160 else (rows, 84, 84), np.uint8)
+        else:
+            out = np.zeros((rows, 84, 84), np.uint8)
+        buf = out if out.size else np.zeros(1, np.uint8)  # (dst is never null, even for no rows)
+        self._c(lib().aleppo_rec_read(self._ctx, C.c_int(src), C.c_int(REC_FIELDS[name]), C.c_uint64(int(first)),
+                                      C.c_uint64(rows), _ptr(buf), C.c_size_t(out.nbytes)))
+        return out
+
+    def rec_clear(self, source="rollout"):
+        """aleppo_rec_clear: rows = dropped = 0; the ordinal stays"""
+        src = REC_SOURCES[source] if isinstance(source, str) else int(source)
+        self._c(lib().aleppo_rec_clear(self._ctx, C.c_int(src)))
 
     # -- multi GPU --
     @staticmethod

@@ -142,6 +142,10 @@ extern "C" int aleppo_env_rollout(aleppo_ctx *c) {
       c->env_cur ^= 1;
       // slot t's frames -> observation slot t + 1, with the start-at-entry bytes the kernel just wrote into the record
       rc = step_enqueue(c, c->env_blk, kind, ALEPPO_DEVICE, nullptr, nullptr, t, rec + 6 * (size_t)E);
+      // the recorded environment's row: behind the ingest, in front of the next slot's environment kernel (which
+      // overwrites `in`)
+      if (rc == ALEPPO_OK && c->rec[ALEPPO_REC_ROLLOUT].open)
+        rec_capture(c, ALEPPO_REC_ROLLOUT, in, t);
     }
     if (rc == ALEPPO_OK && hipGetLastError() != hipSuccess)
       rc = set_err(c, ALEPPO_ERR_HIP, "a launch failed");

@@ -111,6 +111,7 @@ extern "C" int aleppo_eval_push_frames(aleppo_ctx *c, const uint8_t *frames, int
   launch_ingest(c->stream, kind == ALEPPO_FRAMES_RAW_PAIR, df, c->lut, c->ev_d_start, nullptr, c->ev_obs, c->ev_L, 1, 0, 0);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(c->ev_staged, c->stream));
+  rec_tick(c, ALEPPO_REC_EVAL);
   return ALEPPO_OK;
 }
 

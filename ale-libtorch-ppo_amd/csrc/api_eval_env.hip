@@ -105,6 +105,8 @@ extern "C" int aleppo_eval_env_run(aleppo_ctx *c, int rule, float param, int32_t
     // this step's frames -> the lanes' stacks with the start-at-entry bytes the kernel just wrote: aleppo_eval_push_frames'
     // ingest on a one-slot "rollout"
     launch_ingest(c->stream, kind == ALEPPO_FRAMES_RAW_PAIR, c->ee_blk, c->lut, c->ee_start, nullptr, c->ev_obs, L, 1, 0, 0);
+    if (c->rec[ALEPPO_REC_EVAL].open) // the recorded lane's row, in front of the next step's kernels
+      rec_capture(c, ALEPPO_REC_EVAL, in, 0);
     if (hipGetLastError() != hipSuccess)
       return fail_ctx(c, ALEPPO_ERR_HIP, "aleppo_eval_env_run: a launch failed");
   }

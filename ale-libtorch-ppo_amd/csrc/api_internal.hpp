@@ -1,5 +1,5 @@
 // api_internal.hpp - what the C ABI's translation units share (api_core.hip, api_rollout.hip, api_train.hip,
-// api_batch.hip, api_eval.hip, api_eval_env.hip, api_env.hip, api_state.hip, api_ops.hip): the entry-point guard macros and the host-side helpers.  Host code only; the
+// api_batch.hip, api_eval.hip, api_eval_env.hip, api_env.hip, api_rec.hip, api_state.hip, api_ops.hip): the entry-point guard macros and the host-side helpers.  Host code only; the
 // helpers are defined in api_core.hip unless noted.
 #pragma once
 #include "common.hpp"
@@ -155,6 +155,15 @@ int eval_act_enqueue(aleppo_ctx *c, int rule, float kparam, const float *dn);
 // and what aleppo_env_import_state refuses in one environment's state (null: nothing)
 void env_initial(const aleppo_env_config &cfg, std::vector<aleppo_env_state> &st);
 const char *env_state_invalid(const aleppo_env_state &s);
+// api_rec.hip, for aleppo_env_rollout / aleppo_eval_env_run: one step of `source` has just been enqueued up to and including
+// its ingest - take the next row (the capture launch) or count the step as dropped, and advance the ordinal.  in: the state
+// array the step's environment kernel READ; t: the rollout slot (ALEPPO_REC_ROLLOUT).  Call only where rec[source].open.
+void rec_capture(aleppo_ctx *c, int source, const aleppo_env_state *in, int t);
+// a step of `source` that the host drove: the ordinal advances, no row is taken
+inline void rec_tick(Ctx *c, int source) {
+  if (c->rec[source].open)
+    c->rec[source].ordinal++;
+}
 extern const double RS_INITIAL[RS_BLOCK];
 int ensure_rs_storage(aleppo_ctx *c);
 bool rs_state_valid(const double stats[3]);

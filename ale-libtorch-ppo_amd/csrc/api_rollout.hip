@@ -232,6 +232,7 @@ static int do_record(aleppo_ctx *c, const float *rewards, const uint8_t *termina
   std::memcpy(c->h_step + 6 * (size_t)E, episode_start, E);
   std::memcpy(c->h_rec + (size_t)c->t * c->step_rec_bytes, c->h_step, (size_t)7 * E); // uploaded at finish_rollout
   c->t++;
+  rec_tick(c, ALEPPO_REC_ROLLOUT);
   return ALEPPO_OK;
 }
 
@@ -327,6 +328,7 @@ extern "C" int aleppo_step(aleppo_ctx *c, const uint8_t *frames, int kind, int l
   if (location == ALEPPO_HOST)
     HIPCHK(c, hipEventRecord(c->ev_tmp, c->stream));
   c->t++;
+  rec_tick(c, ALEPPO_REC_ROLLOUT);
   return ALEPPO_OK;
 }
 // Park the main stream: everything enqueued after this runs once the host has stored a number >= the returned sequence
@@ -401,6 +403,7 @@ extern "C" int aleppo_release_step(aleppo_ctx *c, const float *rewards, const ui
   std::memcpy(rec + 5 * (size_t)E, truncated, E);
   std::memcpy(rec + 6 * (size_t)E, c->armed_start, E);
   c->t++;
+  rec_tick(c, ALEPPO_REC_ROLLOUT);
   return ALEPPO_OK;
 }
 extern "C" int aleppo_replay_rollout(aleppo_ctx *c, const uint8_t *frames, int kind, int location,

@@ -299,6 +299,20 @@ struct Ctx {
   int ee_cur = 0;                  // ee_state[ee_cur] is the state between two steps
   float *ee_log = nullptr;         // [4][S][L]: episode returns, episode lengths (u32), game returns, game lengths (u32)
   uint8_t *ee_start = nullptr;     // [L] start-at-entry bytes of the last step
+  // ---- episode recorders (aleppo_rec_open), one per aleppo_rec_source: ONE allocation each - steps [cap] | frames [cap] |
+  // observations [cap] | logits [cap][A], the two middle planes only where they are part of the content; rows / dropped /
+  // ordinal are host state (every step of a source takes exactly one row, so the host addresses the row at enqueue);
+  // nothing is allocated or enqueued on a context that never opens one
+  struct Recorder {
+    bool open = false;
+    aleppo_rec_config cfg{};
+    uint8_t *blk = nullptr;
+    aleppo_rec_step *steps = nullptr;
+    uint8_t *frames = nullptr, *obs = nullptr; // nullptr: not part of cfg.content
+    float *logits = nullptr;
+    size_t frame_bytes = 0;        // of one row of the frames plane (fixed by the source's frame kind)
+    uint64_t rows = 0, dropped = 0, ordinal = 0;
+  } rec[2];
   bool prof_on = false;
   bool serial_update = false; // ALEPPO_OPT_SERIAL_UPDATE: every update kernel on the main stream
   bool dbg_no_publish = false;

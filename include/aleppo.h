@@ -674,6 +674,80 @@ int aleppo_eval_env_import_state(aleppo_ctx *ctx, const aleppo_env_state *states
  * count or an unknown field is ALEPPO_ERR_INVALID_ARGUMENT; before aleppo_eval_env_open ALEPPO_ERR_RUNTIME. */
 int aleppo_eval_env_read(aleppo_ctx *ctx, int field, void *dst, size_t bytes);
 
+/* ------------------------------------------------------------------ episode recorders of the device-resident environments
+ * (the reference's EpisodeRecorder / EpisodeObservationRecorder around environment 0, rollout.cc:149-158)
+ * One recorder per source - ALEPPO_REC_ROLLOUT: environment `index` of aleppo_env_rollout; ALEPPO_REC_EVAL: lane `index` of
+ * aleppo_eval_env_run - each an append log of `capacity` rows in device memory.  Every step of the source that those two
+ * calls run takes row `rows` and increments it: ONE more kernel on the context's stream, directly behind the step's
+ * ingest, writes the row's part of up to four planes:
+ *   steps         one aleppo_rec_step;
+ *   logits        float [A]: the logits of the step's acting decision as the source stores them (ALEPPO_ROLLOUT_FP16: the
+ *                 half values widened, what aleppo_read_batch returns; evaluation lanes store fp32);
+ *   frames        (ALEPPO_REC_FRAMES) the index's part of the frame buffer as the environment kernel left it:
+ *                 uint8 [84,84] or [2,210,160];
+ *   observations  (ALEPPO_REC_OBSERVATION) uint8 [84,84]: the newest plane of the index's stack after the ingest - for raw
+ *                 pairs the frame after the gray LUT, the area resize and the two-frame maximum.
+ * A plane that is not part of `content` is not allocated and not written.  With the log full a step is not captured: no
+ * launch is made and `dropped` is incremented.  `ordinal` advances for every step of the source, captured or not -
+ * host-driven ones included: wherever aleppo_step / aleppo_record_step / aleppo_release_step advance the rollout's slot
+ * (aleppo_replay_rollout: by T), and for every aleppo_eval_push_frames - so a gap in the ordinals of consecutive rows is a
+ * visible discontinuity.
+ * Isolation: the calls change nothing the rollout, the update, the evaluation lanes or either set of environments can
+ * observe: a training run with a recorder open gives bit-identical aleppo_read_batch planes, episode logs, environment
+ * states, aleppo_state_digest and parameters.  The recorder is not part of any checkpoint, is local to a rank and never a
+ * collective, and uses the context's own stream only, no hipFree, no device-wide synchronise.  While a step is armed all
+ * calls but aleppo_rec_count fail with ALEPPO_ERR_RUNTIME.  A context that never calls aleppo_rec_open allocates nothing
+ * and enqueues nothing more. */
+typedef enum { ALEPPO_REC_ROLLOUT = 0, ALEPPO_REC_EVAL = 1 } aleppo_rec_source;
+enum { ALEPPO_REC_FRAMES = 1, ALEPPO_REC_OBSERVATION = 2 }; /* content bits */
+typedef struct {
+  int32_t source;      /* aleppo_rec_source */
+  int32_t index;       /* the environment in [0, E) / the lane in [0, L) that is recorded */
+  int32_t content;     /* ALEPPO_REC_FRAMES | ALEPPO_REC_OBSERVATION, at least one */
+  int32_t capacity;    /* rows, 1..65536 */
+  int32_t reserved[4]; /* 0 */
+} aleppo_rec_config; /* 32 bytes */
+typedef struct {       /* 32 bytes, no padding */
+  uint64_t ordinal;    /*  0: steps the source had taken since aleppo_rec_open, before this one */
+  int32_t action;      /*  8: the head's action (a start step's environment ignores it) */
+  float reward;        /* 12: as recorded, unclamped and unscaled; a start step: the stale one */
+  float value;         /* 16: taken like the logits */
+  uint8_t start, terminated, truncated, game_over; /* 20: start = the flag at entry; game_over = an episode ended here AND
+                                                      the game with it */
+  int32_t lives;       /* 24: after the step */
+  int32_t reserved;    /* 28: 0 */
+} aleppo_rec_step;
+typedef struct {
+  uint64_t rows, dropped, next_ordinal;
+  int32_t capacity;
+  int32_t frame_bytes;       /* bytes of a frames row (7056 or 67200); 0: not part of content */
+  int32_t observation_bytes; /* 7056; 0: not part of content */
+  int32_t actions;           /* A: a logits row is float [A] */
+} aleppo_rec_counts; /* 40 bytes */
+typedef enum {
+  ALEPPO_REC_F_STEPS = 0,       /* aleppo_rec_step [rows] */
+  ALEPPO_REC_F_LOGITS = 1,      /* float [rows, A] */
+  ALEPPO_REC_F_FRAMES = 2,      /* uint8 [rows, 84, 84] or [rows, 2, 210, 160] */
+  ALEPPO_REC_F_OBSERVATIONS = 3 /* uint8 [rows, 84, 84] */
+} aleppo_rec_field;
+/* Needs aleppo_env_open (ALEPPO_REC_ROLLOUT) or aleppo_eval_env_open (ALEPPO_REC_EVAL) first, ALEPPO_ERR_RUNTIME
+ * otherwise: their frame kind fixes the row size.  Allocates one block - in this call and never later - and keeps it until
+ * aleppo_destroy.  Called again with the same config it empties the log and sets the ordinal to 0; with another config for
+ * an open source it is ALEPPO_ERR_RUNTIME.  A null pointer, an unknown source, an index outside the source's range, a
+ * content of 0 or with unknown bits, a capacity outside [1, 65536] or a non-zero reserved word is
+ * ALEPPO_ERR_INVALID_ARGUMENT; a refused call changes nothing. */
+int aleppo_rec_open(aleppo_ctx *ctx, const aleppo_rec_config *cfg);
+/* Host state only: no synchronise, and valid while a step is armed.  A source that was never opened reports zeros.  A
+ * null pointer or an unknown source is ALEPPO_ERR_INVALID_ARGUMENT. */
+int aleppo_rec_count(aleppo_ctx *ctx, int source, aleppo_rec_counts *out);
+/* Copies rows [first_row, first_row + rows) of one aleppo_rec_field to dst; synchronises the context's stream like
+ * aleppo_env_read.  A range outside [0, rows of the log], bytes != rows x the field's row size, an unknown field or source,
+ * a field that is not part of content or a null dst is ALEPPO_ERR_INVALID_ARGUMENT; a source that is not open
+ * ALEPPO_ERR_RUNTIME. */
+int aleppo_rec_read(aleppo_ctx *ctx, int source, int field, uint64_t first_row, uint64_t rows, void *dst, size_t bytes);
+/* rows = dropped = 0; the ordinal stays.  ALEPPO_ERR_RUNTIME for a source that is not open. */
+int aleppo_rec_clear(aleppo_ctx *ctx, int source);
+
 /* ------------------------------------------------------------------ multi-GPU (no reference counterpart)
  * One process per GPU.  Rank 0 creates the id, the launcher broadcasts its bytes, every rank calls
  * aleppo_comm_init.  Gradients (+ mask counts) are all-reduced with RCCL inside aleppo_train. */
@@ -742,7 +816,8 @@ typedef enum {
   ALEPPO_K_ACT_FUSED = 17,  /* frame ingest + conv1-3 of the acting batch in one launch (aleppo_step, bf16) */
   ALEPPO_K_CONV_FWD = 18,   /* conv1 -> conv2 -> conv3 of the update's forward pass in one launch (bf16) */
   ALEPPO_K_CONV_BWD = 19,   /* conv2 dgrad + conv2 wgrad + conv1 wgrad of the update's backward pass in one launch (bf16) */
-  ALEPPO_K_COUNT = 20
+  ALEPPO_K_REC_CAPTURE = 20, /* the episode recorders' capture kernel (aleppo_rec_open), one launch per recorded step */
+  ALEPPO_K_COUNT = 21
 } aleppo_kernel_class;
 int aleppo_profile_enable(aleppo_ctx *ctx, int on);
 int aleppo_profile_read(aleppo_ctx *ctx, int kernel_class, double *avg_ms, int64_t *launches);

@@ -40,6 +40,11 @@ struct Config {
   double eval_temperature = 1.0, eval_epsilon = 0.05;
   // extension: the evaluation's environments live on the device too (aleppo_eval_env_open / aleppo_eval_env_run)
   bool device_evaluation = false;
+  // extension: record_video / record_observation honoured on the device (aleppo_rec_*): environment 0 of rank 0 with
+  // device_environments, lane 0 of every evaluation with record_evaluation (needs device_evaluation); every
+  // record_interval-th episode is written
+  bool record_evaluation = false;
+  size_t record_interval = 1;
   size_t device_evaluation_steps = 32; // the S of the open and the chunk of every run
   // extension: return-based reward scaling in place of the reward clamp (ALEPPO_OPT_REWARD_SCALE / _CLIP)
   bool reward_scaling = false;
@@ -216,6 +221,17 @@ static Config load_config(const std::string &path) { // keys / defaults of src/b
       c.device_evaluation_steps = (size_t)steps;
     }
   }
+  read_key(kv, "record_evaluation", c.record_evaluation);
+  if (c.record_evaluation && !c.device_evaluation)
+    throw std::runtime_error("record_evaluation needs device_evaluation: true");
+  if (kv.count("record_interval")) {
+    const long n = as<long>(kv, "record_interval", 1);
+    if (n < 1)
+      throw std::runtime_error("record_interval must be positive");
+    if (!c.record_video && !c.record_evaluation) // (nothing else reads it)
+      throw std::runtime_error("record_interval needs record_video: true or record_evaluation: true");
+    c.record_interval = (size_t)n;
+  }
   read_key(kv, "checkpoint_path", c.checkpoint_path);
   read_key(kv, "resume", c.resume);
   if (kv.count("checkpoint_interval")) {
@@ -301,6 +317,8 @@ static HParams hparams_of(const Config &c) {
                                        {"eval_epsilon", c.eval_epsilon}});
   if (c.device_evaluation)
     h.numbers.emplace_back("device_evaluation_steps", (double)c.device_evaluation_steps);
+  if (c.record_interval != 1)
+    h.numbers.emplace_back("record_interval", (double)c.record_interval);
   h.flags = {{"record_observation", c.record_observation}, {"record_video", c.record_video},
              {"cuda_graph", c.cuda_graph}, {"deterministic", c.deterministic}};
   const std::pair<const char *, bool> when_set[] = {{"shuffle_minibatches", c.shuffle_minibatches},
@@ -310,7 +328,8 @@ static HParams hparams_of(const Config &c) {
                                                     {"log_tensor_stats", c.log_tensor_stats},
                                                     {"reward_scaling", c.reward_scaling},
                                                     {"device_environments", c.device_environments},
-                                                    {"device_evaluation", c.device_evaluation}};
+                                                    {"device_evaluation", c.device_evaluation},
+                                                    {"record_evaluation", c.record_evaluation}};
   for (const auto &f : when_set)
     if (f.second)
       h.flags.emplace_back(f.first, true);

@@ -91,6 +91,16 @@
 // the step the host path stops at, on environments that are thrown away; the evaluation counter is set back to where the
 // host path would have left it - aleppo_eval_set_counter - so that every later evaluation draws what it draws there and
 // the eval/* scalars are the host path's bit for bit.  A library without the entry points refuses the key at start-up).
+// record_video: true with device_environments: true (without it the key is only noted, as before: the host emulators are
+// not recorded): environment 0 of rank 0 is followed by the library's episode recorder (aleppo_rec_open, capacity =
+// horizon, drained and cleared after every aleppo_env_rollout) and every episode is written into <video dir> as
+// episode_<n>.y4m (uncompressed YUV4MPEG2, no ffmpeg) and episode_<n>.tsv (one line per step), n counting from 1 and, in a
+// resumed run, on from the highest n in the directory; record_observation: true records the 84x84 observation the network
+// sees instead of the frames the emulator renders (the reference's choice, rollout.cc:150-157).  record_evaluation: false
+// (true, needs device_evaluation: the same for lane 0 of every evaluation, files eval_<step>_episode_<n>, the unfinished
+// episode at an evaluation's end discarded).  record_interval: 1 (N: only episodes 1, N + 1, 2 N + 1, ... are written; every
+// step's 32-byte record is read, the frames of the other episodes never leave the device).  recorder.hpp has the formats.
+// The recorders change nothing the run computes; a library without the entry points refuses the keys at start-up.
 // Data parallelism (no reference counterpart): start one process per GPU with RANK / WORLD_SIZE / LOCAL_RANK
 // in the environment (torchrun / mpirun style).  Rank r owns the contiguous environment block
 // [r * E / W, (r + 1) * E / W) and GPU LOCAL_RANK; rank 0 creates the RCCL id, hands it to the others through the file
@@ -106,6 +116,7 @@
 #include "init.hpp"
 #include "pool.hpp"
 #include "profile.hpp"
+#include "recorder.hpp"
 #include <cstdio>
 #include <iostream>
 #include <numeric>
@@ -169,7 +180,7 @@ static int env_int(const char *k, int dflt) {
 // ------------------------------------------------------------------ the run's state: what every phase below works on
 struct Run {
   const int64_t start_time = std::chrono::system_clock::now().time_since_epoch().count();
-  const std::string rom_path, log_arg, group;
+  const std::string rom_path, log_arg, video_dir, group;
   Profile prof; // the optional 6th argument (train.cc:328-335)
   const Config cfg;
   std::string log_path;
@@ -186,13 +197,18 @@ struct Run {
   bool slot_ahead = false;
   std::vector<HyperSchedule> schedules;
   EnvSet eval_set; // the evaluation lanes' environments (empty without eval_interval, and with device_evaluation)
+  uint8_t lut[256]; // the gray table the library was given (device_preprocess), for the recorded raw pairs
+  std::optional<EpisodeWriter> video; // record_video with device_environments: environment 0 of rank 0
+  bool record_training() const { return cfg.record_video && cfg.device_environments && rank == 0; }
+  bool record_evaluation() const { return cfg.record_evaluation && rank == 0; }
+  int record_field() const { return cfg.record_observation ? ALEPPO_REC_F_OBSERVATIONS : ALEPPO_REC_F_FRAMES; }
   uint64_t eval_counter = 0; // device_evaluation: the evaluation counter where the host path would have left it
   size_t first_rollout = 0, rollouts_done = 0;
   std::optional<WorkerPool> pool; // (last: its threads are joined before anything they touch goes away)
 
   // load and validate: the arguments, the config, the launch (RANK / WORLD_SIZE) and the shapes that follow
   Run(int argc, char **argv)
-      : rom_path(argv[1]), log_arg(argv[2]), group(argv[4]), prof(argc > 6 ? argv[6] : ""), cfg(load_config(argv[5])),
+      : rom_path(argv[1]), log_arg(argv[2]), video_dir(argv[3]), group(argv[4]), prof(argc > 6 ? argv[6] : ""), cfg(load_config(argv[5])),
         log_path(argv[2]) {
     { // replace_extension("tfevents.<start-time>") like train.cc:324-325
       const size_t slash = log_path.find_last_of('/'), dot = log_path.find_last_of('.');
@@ -215,8 +231,8 @@ struct Run {
       throw std::runtime_error("Batch size must be divisible by num_mini_batches");
     if (E % cfg.worker_batch_size)
       std::cerr << "warning: total_environments % worker_batch_size != 0 would deadlock the reference's queue\n";
-    if (cfg.record_video)
-      std::cerr << "note: record_video ignored (no ffmpeg / ALE in this build)\n";
+    if (cfg.record_video && !cfg.device_environments)
+      std::cerr << "note: record_video ignored (it needs device_environments: true; the host emulators are not recorded)\n";
     const std::string rank_suffix = world > 1 ? ".rank" + std::to_string(rank) : "";
     ckpt_file = cfg.checkpoint_path.empty() ? "" : cfg.checkpoint_path + rank_suffix;
     resume_file = cfg.resume.empty() ? "" : cfg.resume + rank_suffix;
@@ -273,6 +289,10 @@ static void refuse_missing_entry_points(const Config &cfg) {
                                  aleppo_eval_env_import_state && aleppo_eval_env_read && aleppo_eval_set_counter))
     throw std::runtime_error("device_evaluation is set but this build's library has no device-resident evaluation "
                              "environments (aleppo_eval_env_open is missing)");
+  if (((cfg.record_video && cfg.device_environments) || cfg.record_evaluation) &&
+      !(aleppo_rec_open && aleppo_rec_count && aleppo_rec_read && aleppo_rec_clear))
+    throw std::runtime_error("record_video / record_evaluation are set but this build's library has no episode recorders "
+                             "(aleppo_rec_open is missing)");
   if (cfg.log_tensor_stats && !aleppo_tensor_stats)
     throw std::runtime_error("log_tensor_stats is set but this build's library has no per-tensor statistics "
                              "(aleppo_tensor_stats is missing)");
@@ -409,12 +429,10 @@ static void create_environments(Run &run) {
   set.num_actions = run.eval_set.num_actions = run.A;
   // the workers' frame buffer: page-locked + GPU-mapped, read in place by the ingest kernel (see the file header)
   check(run.ctx, aleppo_host_alloc(run.ctx, E * fbytes, reinterpret_cast<void **>(&set.frames)));
-  if (cfg.device_preprocess) { // ALE's palette -> gray table would go here; the synthetic palette is its own gray value
-    uint8_t lut[256];
-    for (int i = 0; i < 256; ++i)
-      lut[i] = (uint8_t)i;
-    check(run.ctx, aleppo_set_gray_lut(run.ctx, lut));
-  }
+  for (int i = 0; i < 256; ++i) // ALE's palette -> gray table would go here; the synthetic palette is its own gray value
+    run.lut[i] = (uint8_t)i;
+  if (cfg.device_preprocess)
+    check(run.ctx, aleppo_set_gray_lut(run.ctx, run.lut));
   check(run.ctx, aleppo_host_alloc(run.ctx, E, reinterpret_cast<void **>(&run.start_mapped)));
   if (cfg.device_environments) { // the same E emulators on the device; the host instances above only hold checkpoint fields
     aleppo_env_config ec{};
@@ -424,6 +442,16 @@ static void create_environments(Run &run) {
     ec.max_steps = cfg.max_steps;
     ec.max_return = (float)cfg.max_return;
     check(run.ctx, aleppo_env_open(run.ctx, &ec));
+    if (run.record_training()) { // environment 0's episodes: the reference's recorder choice (rollout.cc:150-157)
+      aleppo_rec_config rc{};
+      rc.source = ALEPPO_REC_ROLLOUT;
+      rc.index = 0;
+      rc.content = cfg.record_observation ? ALEPPO_REC_OBSERVATION : ALEPPO_REC_FRAMES;
+      rc.capacity = (int32_t)run.T; // drained after every rollout: nothing is dropped
+      check(run.ctx, aleppo_rec_open(run.ctx, &rc));
+      run.video.emplace(run.video_dir, "episode_", ALEPPO_REC_ROLLOUT, run.record_field(),
+                        cfg.device_preprocess && !cfg.record_observation, run.A, cfg.record_interval, run.lut, true);
+    }
   }
   std::cout << "Creating " << cfg.num_workers << " worker threads." << std::endl;
   run.pool.emplace(cfg.num_workers);
@@ -495,6 +523,8 @@ static EpisodeLog collect_on_device(Run &run) {
     Profile::Span sp(&run.prof, "aleppo_finish_rollout");
     check(ctx, aleppo_finish_rollout(ctx, nullptr));
   }
+  if (run.video) // this rollout's rows of environment 0 -> the episode files; the log is empty again afterwards
+    run.video->drain(ctx, check);
   // the four [T][E] log planes in slot-then-environment order: the order the host loop appends in
   std::vector<float> ep_ret(n), game_ret(n);
   std::vector<uint32_t> ep_len(n), game_len(n);
@@ -822,6 +852,17 @@ static void evaluate_on_device(Run &run, uint64_t seed_base, int64_t step) {
   ec.max_return = (float)cfg.max_return;
   check(ctx, aleppo_eval_env_open(ctx, &ec, (int32_t)S)); // (again: fresh environments under this evaluation's seeds)
   check(ctx, aleppo_eval_set_counter(ctx, run.eval_counter));
+  std::optional<EpisodeWriter> video; // record_evaluation: lane 0 of this evaluation, eval_<step>_episode_<n>
+  if (run.record_evaluation()) {
+    aleppo_rec_config rc{};
+    rc.source = ALEPPO_REC_EVAL;
+    rc.index = 0;
+    rc.content = cfg.record_observation ? ALEPPO_REC_OBSERVATION : ALEPPO_REC_FRAMES;
+    rc.capacity = (int32_t)S; // drained after every chunk
+    check(ctx, aleppo_rec_open(ctx, &rc)); // (again with the same config: an empty log, ordinal 0)
+    video.emplace(run.video_dir, "eval_" + std::to_string(step) + "_episode_", ALEPPO_REC_EVAL, run.record_field(),
+                  cfg.device_preprocess && !cfg.record_observation, run.A, cfg.record_interval, run.lut, false);
+  }
   std::vector<float> ret(S * L), returns;
   std::vector<uint32_t> len(S * L);
   std::vector<size_t> lengths;
@@ -829,6 +870,8 @@ static void evaluate_on_device(Run &run, uint64_t seed_base, int64_t step) {
     check(ctx, aleppo_eval_env_run(ctx, eval_rule(cfg), eval_param(cfg), (int32_t)S));
     check(ctx, aleppo_eval_env_read(ctx, ALEPPO_EEF_EPISODE_RETURNS, ret.data(), ret.size() * sizeof(float)));
     check(ctx, aleppo_eval_env_read(ctx, ALEPPO_EEF_EPISODE_LENGTHS, len.data(), len.size() * sizeof(uint32_t)));
+    if (video)
+      video->drain(ctx, check);
     for (size_t s = 0; s < S && returns.size() < cfg.eval_episodes; ++s) { // step, then lane: the host path's order
       run.eval_counter++; // (the host path acts once more only while episodes are missing)
       for (size_t i = 0; i < L && returns.size() < cfg.eval_episodes; ++i)
@@ -838,6 +881,8 @@ static void evaluate_on_device(Run &run, uint64_t seed_base, int64_t step) {
         }
     }
   }
+  if (video) // the unfinished episode at the end of an evaluation is not kept
+    video->discard();
   log_evaluation(run, step, returns, lengths);
 }
 static void evaluate(Run &run, size_t round, int64_t step) {
