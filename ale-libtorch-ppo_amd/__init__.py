@@ -65,6 +65,15 @@ TENSOR_STATS = dict(size=0, param_norm=1, param_maxabs=2, param_nonfinite=3, gra
                     update_maxabs=7, update_ratio=8, step_nonfinite=9)
 TS_SEC_PARAMS, TS_SEC_STEP = 1, 2
 TENSOR_STATS_SECTIONS = dict(params=TS_SEC_PARAMS, step=TS_SEC_STEP, all=TS_SEC_PARAMS | TS_SEC_STEP)
+# aleppo_forward_activations / aleppo_activation_stats: the hidden layers (channels, positions per channel; fc: H, 1), the
+# rows of the layer table, the columns of aleppo_act_unit_stat and aleppo_act_layer_stat (Engine.forward_activations /
+# Engine.activation_stats)
+ACT_LAYERS = ("conv1", "conv2", "conv3", "fc")
+ACT_LAYER_SHAPES = dict(conv1=(32, 20, 20), conv2=(64, 9, 9), conv3=(64, 7, 7))
+ACT_LAYER_ROWS = ACT_LAYERS + ("total",)
+ACT_UNIT_COLS, ACT_LAYER_COLS = 5, 8
+ACT_UNIT_STATS = dict(mean_abs=0, positive_fraction=1, max_abs=2, score=3, nonfinite=4)
+ACT_LAYER_STATS = dict(units=0, elements=1, mean_abs=2, positive_fraction=3, max_abs=4, dead=5, dormant=6, nonfinite=7)
 # aleppo_eval_rule / aleppo_eval_field: the evaluation lanes (Engine.eval_open / eval_push_frames / eval_act / eval_read)
 EVAL_GREEDY, EVAL_SAMPLE, EVAL_EPSILON_GREEDY = 0, 1, 2
 EVAL_RULES = dict(greedy=EVAL_GREEDY, sample=EVAL_SAMPLE, epsilon=EVAL_EPSILON_GREEDY)
@@ -95,7 +104,8 @@ REC_STEP_DTYPE = np.dtype([("ordinal", "<u8"), ("action", "<i4"), ("reward", "<f
                            ("reserved", "<i4")])
 KERNEL_CLASSES = dict(ingest=0, gae=1, head=2, adam=3, conv1_fwd=4, conv2_fwd=5, conv3_fwd=6, fc_fwd=7, fc_dgrad=8,
                       fc_wgrad=9, conv3_dgrad=10, conv3_wgrad=11, conv2_dgrad=12, conv2_wgrad=13, conv1_wgrad=14,
-                      reduce=15, infer_head=16, act_fused=17, conv_fwd=18, conv_bwd=19, rec_capture=20)
+                      reduce=15, infer_head=16, act_fused=17, conv_fwd=18, conv_bwd=19, rec_capture=20,
+                      act_stats=21)
 
 # every symbol include/aleppo.h declares (checked by tests/test_abi.py against the header text)
 # aleppo_set_option keys (include/aleppo.h)
@@ -143,6 +153,7 @@ EXPORTS = [
     "aleppo_export_reward_scale", "aleppo_import_reward_scale", "aleppo_reward_scale",
     "aleppo_export_rollout_state", "aleppo_import_rollout_state", "aleppo_state_digest",
     "aleppo_tensor_stats",
+    "aleppo_forward_activations", "aleppo_activation_stats",
     "aleppo_env_open", "aleppo_env_rollout", "aleppo_env_export_state", "aleppo_env_import_state", "aleppo_env_read",
     "aleppo_eval_env_open", "aleppo_eval_env_run", "aleppo_eval_env_export_state", "aleppo_eval_env_import_state",
     "aleppo_eval_env_read",
@@ -698,6 +709,40 @@ class Engine:
         values = np.zeros(n, np.float32)
         self._c(lib().aleppo_forward(self._ctx, _ptr(obs), C.c_int64(n), _ptr(logits), _ptr(values)))
         return logits, values
+
+    def forward_activations(self, observations, layers=ACT_LAYERS):
+        """aleppo_forward_activations: {layer: float32 array} of the hidden activations of a forward pass on uint8
+        [n,4,84,84] observations, in the reference's tensor order - conv1 [n,32,20,20], conv2 [n,64,9,9], conv3 [n,64,7,7]
+        (after the ReLU), fc [n,H] (no ReLU: signed).  Only the layers asked for are converted and copied."""
+        obs = _u8(observations)
+        n = obs.shape[0]
+        layers = tuple(layers)
+        if not layers or any(l not in ACT_LAYERS for l in layers):
+            raise AleppoInvalidArgument(f"layers must be a non-empty subset of {ACT_LAYERS}")
+        out = {l: np.zeros((n,) + (ACT_LAYER_SHAPES[l] if l != "fc" else (self.H,)), np.float32) for l in layers}
+        self._c(lib().aleppo_forward_activations(self._ctx, _ptr(obs), C.c_int64(n),
+                                                 *[_ptr(out.get(l)) for l in ACT_LAYERS]))
+        return out
+
+    def activation_stats(self, observations=None, tau=0.025, raw=False):
+        """aleppo_activation_stats: per-unit and per-layer activation statistics reduced on the device - of the batch the
+        context holds (observations=None: what train() would train on now) or of uint8 [n,4,84,84] observations.
+        {"units": {layer: {stat: float64 [units]}}, "layers": {layer: {stat: float}}} over ACT_LAYERS (+ "total") and
+        ACT_UNIT_STATS / ACT_LAYER_STATS; raw=True: the float64 [160 + H, 5] and [5, 8] arrays.  tau: the dormancy
+        threshold of the "dormant" count."""
+        obs = None if observations is None else _u8(observations)
+        n = 0 if obs is None else obs.shape[0]
+        units = np.zeros((160 + self.H, ACT_UNIT_COLS), np.float64)
+        layers = np.zeros((len(ACT_LAYER_ROWS), ACT_LAYER_COLS), np.float64)
+        self._c(lib().aleppo_activation_stats(self._ctx, _ptr(obs), C.c_int64(n), C.c_double(tau), _ptr(units),
+                                              C.c_size_t(units.size), _ptr(layers), C.c_size_t(layers.size)))
+        if raw:
+            return units, layers
+        first = (0, 32, 96, 160, 160 + self.H)
+        return dict(units={l: {s: units[first[k]:first[k + 1], i].copy() for s, i in ACT_UNIT_STATS.items()}
+                           for k, l in enumerate(ACT_LAYERS)},
+                    layers={l: {s: float(layers[k, i]) for s, i in ACT_LAYER_STATS.items()}
+                            for k, l in enumerate(ACT_LAYER_ROWS)})
 
     def read_batch(self, name):
         E, T, A = self.E, self.T, self.A

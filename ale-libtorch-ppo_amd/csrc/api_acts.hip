@@ -1,0 +1,123 @@
+// api_acts.hip - C ABI (include/aleppo.h), the representation: aleppo_forward_activations, aleppo_activation_stats.
+// Both run the network the way aleppo_forward does (same staging, same net_forward, same pre_acted invalidation) and then
+// only read a1 / a2 / a3 / h; nothing here touches what the rollout or a captured update can observe.
+#include "api_internal.hpp"
+
+using namespace aleppo;
+
+// the caller's observations -> packed stacks in c->stage_obs (never the rollout's slots), as aleppo_forward stages them
+static int stage_forward_input(aleppo_ctx *c, const uint8_t *observations, int64_t n, SampleMap *map) {
+  if (int rc = stage_observations(c, observations, n))
+    return rc;
+  const size_t need = (size_t)n * FRAME_PIX * 4;
+  if (need > c->stage_obs_cap) {
+    retire(c, c->stage_obs);
+    c->stage_obs = nullptr;
+    c->stage_obs_cap = 0;
+    HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->stage_obs), need));
+    c->stage_obs_cap = need;
+  }
+  *map = SampleMap{1, (long)FRAME_PIX, 0, 0, 0}; // sample n at stage_obs + n * 7056
+  launch_obs_pack(c->stream, c->stage_u8, c->stage_obs, n, *map);
+  return ALEPPO_OK;
+}
+
+extern "C" int aleppo_forward_activations(aleppo_ctx *c, const uint8_t *observations, int64_t n, float *conv1,
+                                          float *conv2, float *conv3, float *fc) {
+  CHECK_CTX(c);
+  if (!observations)
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "forward_activations: null observations");
+  if (!conv1 && !conv2 && !conv3 && !fc)
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "forward_activations: at least one output must be given");
+  if (n <= 0 || n > c->maxB)
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "forward_activations: n exceeds capacity");
+  float *const out[3] = {conv1, conv2, conv3};
+  const void *const act[3] = {c->a1, c->a2, c->a3};
+  const size_t per[3] = {(size_t)A1_PIX * A1_C, (size_t)A2_PIX * A2_C, (size_t)A3_PIX * A3_C};
+  size_t need = 0;
+  for (int l = 0; l < 3; ++l)
+    need += out[l] ? (size_t)n * per[l] * 4 : 0;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->pre_acted = -1; // a1 / a2 / a3 / h are shared scratch
+  if (need > c->ax_cap) {
+    retire(c, c->ax_buf);
+    c->ax_buf = nullptr;
+    c->ax_cap = 0;
+    HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->ax_buf), need));
+    c->ax_cap = need;
+  }
+  SampleMap map{};
+  if (int rc = stage_forward_input(c, observations, n, &map))
+    return rc;
+  net_forward(c, c->stage_obs, map, n);
+  float *at = c->ax_buf; // (every layer's size is a multiple of 16 bytes: the areas stay aligned)
+  for (int l = 0; l < 3; ++l) {
+    if (!out[l])
+      continue;
+    launch_act_export(c->stream, c->prec, l, act[l], at, n);
+    HIPCHK(c, hipMemcpyAsync(out[l], at, (size_t)n * per[l] * 4, hipMemcpyDeviceToHost, c->stream));
+    at += (size_t)n * per[l];
+  }
+  if (fc)
+    HIPCHK(c, hipMemcpyAsync(fc, c->h, (size_t)n * c->H * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  CHECK_ASYNC(c);
+  return ALEPPO_OK;
+}
+
+extern "C" int aleppo_activation_stats(aleppo_ctx *c, const uint8_t *observations, int64_t n, double tau, double *units,
+                                       size_t unit_count, double *layers, size_t layer_count) {
+  CHECK_CTX(c);
+  const size_t U = (size_t)(A1_C + A2_C + A3_C + c->H);
+  constexpr size_t LAYER_COUNT = (size_t)ALEPPO_ACT_LAYER_ROWS * ALEPPO_ACT_LAYER_COLS;
+  if (!(tau >= 0.0) || !std::isfinite(tau))
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "activation_stats: tau must be finite and non-negative");
+  if (!units || !layers)
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "activation_stats: null argument");
+  if (unit_count != U * ALEPPO_ACT_UNIT_COLS || layer_count != LAYER_COUNT)
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT,
+                   "activation_stats: unit_count must be (160 + H) * 5 and layer_count 40");
+  const bool batch = observations == nullptr;
+  if (batch && n != 0)
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "activation_stats: null observations need n == 0 (the context's batch)");
+  if (!batch && (n <= 0 || n > c->maxB))
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "activation_stats: n exceeds capacity");
+  if (batch && c->batch_n <= 0)
+    return set_err(c, ALEPPO_ERR_RUNTIME, "no batch: call aleppo_finish_rollout or aleppo_set_batch first");
+  const long total = batch ? c->batch_n : (long)n;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->pre_acted = -1; // a1 / a2 / a3 / h are shared scratch
+  // the scratch holds the largest sample count either source can bring (the record count grows with it)
+  if (!c->as_scratch)
+    HIPCHK(c, dalloc(&c->as_scratch, act_stats_plan(c->prec, c->H, std::max(c->N, c->maxB), c->maxB).bytes, c->stream));
+  const ActStatsPlan pl = act_stats_plan(c->prec, c->H, total, c->maxB);
+  const uint32_t *obs = c->obs;
+  SampleMap map = train_map(c, 0);
+  if (!batch) {
+    if (int rc = stage_forward_input(c, observations, n, &map))
+      return rc;
+    obs = c->stage_obs;
+  }
+  size_t done[4] = {0, 0, 0, 0};
+  for (long n0 = 0; n0 < total; n0 += c->maxB) {
+    const long ns = std::min(c->maxB, total - n0);
+    map.n0 = (int)n0;
+    net_forward(c, obs, map, ns);
+    prof_begin(c, ALEPPO_K_ACT_STATS);
+    launch_act_stats_partial(c->stream, c->prec, c->a1, c->a2, c->a3, c->h, c->H, ns, pl, done, c->as_scratch);
+    prof_end(c, ALEPPO_K_ACT_STATS);
+  }
+  const double *units_dev = nullptr, *layers_dev = nullptr;
+  launch_act_stats_final(c->stream, c->H, total, tau, pl, done, c->as_scratch, &units_dev, &layers_dev);
+  HIPCHK(c, hipGetLastError());
+  std::vector<double> hu(U * ALEPPO_ACT_UNIT_COLS);
+  double hl[LAYER_COUNT];
+  HIPCHK(c, hipMemcpyAsync(hu.data(), units_dev, hu.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(hl, layers_dev, sizeof(hl), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  CHECK_ASYNC(c);
+  std::memcpy(units, hu.data(), hu.size() * sizeof(double));
+  std::memcpy(layers, hl, sizeof(hl));
+  return ALEPPO_OK;
+}

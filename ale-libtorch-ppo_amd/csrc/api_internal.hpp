@@ -1,5 +1,5 @@
 // api_internal.hpp - what the C ABI's translation units share (api_core.hip, api_rollout.hip, api_train.hip,
-// api_batch.hip, api_eval.hip, api_eval_env.hip, api_env.hip, api_rec.hip, api_state.hip, api_ops.hip): the entry-point guard macros and the host-side helpers.  Host code only; the
+// api_batch.hip, api_eval.hip, api_eval_env.hip, api_env.hip, api_rec.hip, api_state.hip, api_acts.hip, api_ops.hip): the entry-point guard macros and the host-side helpers.  Host code only; the
 // helpers are defined in api_core.hip unless noted.
 #pragma once
 #include "common.hpp"

@@ -260,6 +260,11 @@ struct Ctx {
   void *ts_scratch = nullptr;
   bool ts_step_valid = false;           // an aleppo_train has succeeded and no load_params / import_optimizer since
   float ts_sched[2] = {0.f, 0.f};       // the two schedule scalars of the last optimizer step that ran
+  // ---- aleppo_forward_activations / aleppo_activation_stats: the NCHW float export staging (grown on demand) and the
+  // statistics' partial records + the two tables (allocated on first use; its size is a function of the context's shape)
+  float *ax_buf = nullptr;
+  size_t ax_cap = 0;                    // bytes
+  void *as_scratch = nullptr;
   // ---- evaluation lanes (aleppo_eval_open): L frame stacks of their own, their own acting scratch, upload staging and
   // action hand-off; nothing below is allocated, and nothing is enqueued for it, on a context that never opens them
   int ev_L = 0;                    // 0: not opened
@@ -463,6 +468,22 @@ size_t tensor_stats_scratch_bytes(const ParamLayout &L);
 void launch_tensor_stats(hipStream_t s, const float *P, const float *G, const float *M1, const float *M2,
                          const ParamLayout &L, int sections, float coef, float step_size, float bc2_sqrt, float eps,
                          void *scratch, const double **out_dev);
+// aleppo_forward_activations / aleppo_activation_stats (activation_stats.hip).  Export: layer 0-2 = a1 / a2 / a3 of ns
+// samples, NHWC of T -> float NCHW.  Statistics: the batch is forwarded in chunks of at most maxB samples; after each
+// forward one read-only launch over a1 / a2 / a3 / h writes one partial record per (workgroup, unit) behind the records of
+// the chunks before it (done[layer]: records written so far, advanced by the launcher); the final launch adds each unit's
+// records in that order and writes double [units][ALEPPO_ACT_UNIT_COLS] and [ALEPPO_ACT_LAYER_ROWS][ALEPPO_ACT_LAYER_COLS]
+// behind the records.  The plan (record areas per layer, scratch bytes) is a function of (precision, H, samples, maxB).
+struct ActStatsPlan {
+  size_t rec_base[4]; // first record of conv1, conv2, conv3, fc
+  size_t records, units, bytes;
+};
+ActStatsPlan act_stats_plan(int prec, int H, long total, long maxB);
+void launch_act_stats_partial(hipStream_t s, int prec, const void *a1, const void *a2, const void *a3, const float *h,
+                              int H, long ns, const ActStatsPlan &pl, size_t done[4], void *scratch);
+void launch_act_stats_final(hipStream_t s, int H, long total, double tau, const ActStatsPlan &pl, const size_t done[4],
+                            void *scratch, const double **units_dev, const double **layers_dev);
+void launch_act_export(hipStream_t s, int prec, int layer, const void *a, float *out, long ns);
 void launch_heads_fwd(hipStream_t s, const float *h, const float *Wh, const float *bh, float *logits, float *values,
                       long n, int H, int A);
 void launch_logsoftmax_rows(hipStream_t s, const float *in, float *out, long rows, int A);

@@ -467,6 +467,78 @@ int aleppo_read_batch(aleppo_ctx *ctx, int field, void *dst, size_t bytes);
  * [n,4,84,84] -> logits float [n,A], values float [n].  n <= max(E, max_minibatch). */
 int aleppo_forward(aleppo_ctx *ctx, const uint8_t *observations, int64_t n, float *logits, float *values);
 
+/* The hidden activations of that forward pass (what a forward hook gives a CleanRL / SB3 user; the reference has none):
+ * for feature rank (SVD of fc), linear probes, embedding plots, and as the ground truth of aleppo_activation_stats.
+ * observations and n as aleppo_forward: host uint8 [n,4,84,84], 1 <= n <= max(E, max_minibatch).  Each output may be NULL
+ * (that layer is neither converted nor copied); at least one must be given.  Outputs, host float, in the reference's
+ * tensor order (NCHW; the channel index is the reference's output-channel index):
+ *   conv1 [n,32,20,20]   conv2 [n,64,9,9]   conv3 [n,64,7,7]   after the ReLU
+ *   fc    [n,H]          the 3136 -> H linear layer's output, bias included; it has NO ReLU, so fc is signed
+ * The values are the stored activations widened exactly: a bf16 context's conv activations are bf16 values in a float; fc
+ * is fp32 on both precisions.  Like aleppo_forward it runs the network in the shared activation scratch, so what
+ * aleppo_step pre-computed for the next aleppo_act is dropped (the act recomputes it: same bits).  The conversion runs on
+ * the context's stream into staging the context keeps until aleppo_destroy.  It changes nothing the rollout or the update
+ * can observe.  Errors: a NULL observations, no output, n out of range: ALEPPO_ERR_INVALID_ARGUMENT; ALEPPO_ERR_RUNTIME
+ * while a step is armed. */
+int aleppo_forward_activations(aleppo_ctx *ctx, const uint8_t *observations, int64_t n, float *conv1, float *conv2,
+                               float *conv3, float *fc);
+
+/* Per-unit and per-layer activation statistics, reduced on the device where the activations are: dormant units (Sokar et
+ * al. 2023, "The Dormant Neuron Phenomenon in Deep RL"), dead units and firing rates (Moalla et al. 2024, "No
+ * Representation, No Trust").  The activations (about 45 KB per sample in bf16 at H = 512) never leave the device.
+ * Samples: observations != NULL: the caller's n observations, as aleppo_forward_activations.  observations == NULL and
+ *   n == 0: THE BATCH THE CONTEXT HOLDS - every sample aleppo_train would train on now (a rollout batch or an
+ *   aleppo_set_batch batch, masked samples included), read in place from the observation slots in logical order, in
+ *   forward chunks of at most max(E, max_minibatch) samples; no observation crosses PCIe.  Never a collective: under data
+ *   parallelism it describes this rank's samples.
+ * units: double [160 + H][ALEPPO_ACT_UNIT_COLS], row-major; unit_count must be (160 + H) * 5.  Rows: conv1 channels 0-31,
+ *   conv2 0-63, conv3 0-63, fc 0..H-1 (the reference's output-channel index, as aleppo_forward_activations exports it).
+ *   A unit of a layer has K = samples * PIX positions, PIX = 400, 81, 49, 1.  Over its finite elements a (a NaN / Inf is
+ *   counted in NONFINITE and left out of everything else): S = sum |a|, P = #{a > 0}, X = max |a|.  Columns:
+ *   aleppo_act_unit_stat.  Because fc is signed, everything is defined with |a|, and POSITIVE_FRACTION of an fc unit is the
+ *   share of samples on which the feature is positive (on conv1-3 it is the ReLU's firing rate).
+ * layers: double [ALEPPO_ACT_LAYER_ROWS][ALEPPO_ACT_LAYER_COLS]; layer_count must be 40.  Rows: conv1, conv2, conv3, fc,
+ *   total.  Columns: aleppo_act_layer_stat.  The total row adds the four rows in row order (UNITS, ELEMENTS, the sums behind
+ *   MEAN_ABS and POSITIVE_FRACTION, DEAD, DORMANT, NONFINITE); its MAX_ABS is the maximum.
+ * tau: the dormancy threshold, finite and >= 0 (Sokar et al. use 0, 0.025 and 0.1).
+ * Arithmetic: every element is widened exactly; S is a double sum whose order is a function of (layer, sample count,
+ *   max(E, max_minibatch), precision) only - per forward chunk a layer [rows][C] is cut into row chunks of 16384 16-byte
+ *   loads (fc: 256 rows), inside a chunk a thread adds its rows in order and the threads of a channel are folded by a fixed
+ *   tree, the chunks are added in index order, then the units of a layer in unit order.  No floating-point atomics; the grid
+ *   does not depend on the device.  Counts, maxima and P / K are exact.  Two calls with nothing in between are bit-identical,
+ *   and with at most max(E, max_minibatch) samples the batch source equals the caller source on the same observations.
+ * Computed WHEN CALLED, on the context's stream: per chunk the forward pass and one launch that only reads, then one small
+ *   finalising launch, the stream's synchronise and two small copies.  Scratch is allocated on first use and kept until
+ *   aleppo_destroy.  Allowed wherever aleppo_forward is - in the middle of a rollout too: the next aleppo_act then
+ *   recomputes what aleppo_step had pre-computed (same bits).  aleppo_train, a captured update (ALEPPO_OPT_UPDATE_GRAPH) and
+ *   every other entry point enqueue nothing for it; calling it neither re-arms a capture nor changes a bit of the run.
+ * Errors: tau negative or not finite, a NULL output, a wrong count, n out of range, NULL observations with n != 0:
+ *   ALEPPO_ERR_INVALID_ARGUMENT.  The batch source without a batch, or any call while a step is armed: ALEPPO_ERR_RUNTIME.
+ *   A failed call writes nothing. */
+#define ALEPPO_ACT_UNIT_COLS 5
+#define ALEPPO_ACT_LAYER_ROWS 5   /* conv1, conv2, conv3, fc, total */
+#define ALEPPO_ACT_LAYER_COLS 8
+typedef enum {
+  ALEPPO_ACT_MEAN_ABS = 0,          /* S / K */
+  ALEPPO_ACT_POSITIVE_FRACTION = 1, /* P / K */
+  ALEPPO_ACT_MAX_ABS = 2,           /* X */
+  ALEPPO_ACT_SCORE = 3,             /* MEAN_ABS_i / ((sum of the layer's MEAN_ABS, in unit order) / units): Sokar et al. eq. 1;
+                                       0 where the layer mean is 0 */
+  ALEPPO_ACT_NONFINITE = 4
+} aleppo_act_unit_stat;
+typedef enum {
+  ALEPPO_ACT_L_UNITS = 0,
+  ALEPPO_ACT_L_ELEMENTS = 1,          /* units * K; total: the sum */
+  ALEPPO_ACT_L_MEAN_ABS = 2,          /* (sum of S, in unit order) / ELEMENTS */
+  ALEPPO_ACT_L_POSITIVE_FRACTION = 3, /* (sum of P) / ELEMENTS */
+  ALEPPO_ACT_L_MAX_ABS = 4,
+  ALEPPO_ACT_L_DEAD = 5,              /* units with X == 0: every finite activation is zero (a ReLU unit that never fired) */
+  ALEPPO_ACT_L_DORMANT = 6,           /* units with SCORE <= tau */
+  ALEPPO_ACT_L_NONFINITE = 7
+} aleppo_act_layer_stat;
+int aleppo_activation_stats(aleppo_ctx *ctx, const uint8_t *observations, int64_t n, double tau, double *units,
+                            size_t unit_count, double *layers, size_t layer_count);
+
 /* ------------------------------------------------------------------ evaluation lanes (the reference has no evaluation
  * loop: SB3's predict(deterministic=True) / EvalCallback, the epsilon-greedy scores of the DQN / PPO papers)
  * L frame stacks of their own, next to the rollout, on which the network acts under one of three rules - so that a
@@ -817,7 +889,8 @@ typedef enum {
   ALEPPO_K_CONV_FWD = 18,   /* conv1 -> conv2 -> conv3 of the update's forward pass in one launch (bf16) */
   ALEPPO_K_CONV_BWD = 19,   /* conv2 dgrad + conv2 wgrad + conv1 wgrad of the update's backward pass in one launch (bf16) */
   ALEPPO_K_REC_CAPTURE = 20, /* the episode recorders' capture kernel (aleppo_rec_open), one launch per recorded step */
-  ALEPPO_K_COUNT = 21
+  ALEPPO_K_ACT_STATS = 21,  /* aleppo_activation_stats' read-only pass over a1 / a2 / a3 / h, one launch per forward chunk */
+  ALEPPO_K_COUNT = 22
 } aleppo_kernel_class;
 int aleppo_profile_enable(aleppo_ctx *ctx, int on);
 int aleppo_profile_read(aleppo_ctx *ctx, int kernel_class, double *avg_ms, int64_t *launches);

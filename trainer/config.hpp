@@ -54,6 +54,10 @@ struct Config {
   long checkpoint_interval = 0; // 0: only after the last rollout
   bool log_batch_stats = false; // extension: explained variance and value / return / advantage statistics (ALEPPO_F_BATCH_STATS)
   bool log_tensor_stats = false; // extension: per-tensor gradient / parameter norms and update ratios (aleppo_tensor_stats)
+  // extension: dormant / dead units and firing rates of the four hidden layers on the batch (aleppo_activation_stats)
+  bool log_activation_stats = false;
+  size_t activation_stats_interval = 1; // after the update of every n-th rollout
+  double dormant_tau = 0.025;           // the dormancy threshold (Sokar et al. 2023)
   // extensions
   std::string precision = "fp32", rollout_precision = "fp32";
   bool device_preprocess = false; // emulators hand over raw frame pairs; gray LUT + resize + max run on the device (N2)
@@ -147,6 +151,19 @@ static Config load_config(const std::string &path) { // keys / defaults of src/b
   read_key(kv, "kl_target", c.kl_target);
   read_key(kv, "log_batch_stats", c.log_batch_stats);
   read_key(kv, "log_tensor_stats", c.log_tensor_stats);
+  read_key(kv, "log_activation_stats", c.log_activation_stats);
+  { // what aleppo_activation_stats would refuse is refused here ("nan" / "inf" do not parse as a number: bad value)
+    const long interval = as<long>(kv, "activation_stats_interval", 1);
+    if (interval < 1)
+      throw std::runtime_error("activation_stats_interval must be positive");
+    c.activation_stats_interval = (size_t)interval;
+    read_key(kv, "dormant_tau", c.dormant_tau);
+    if (!(c.dormant_tau >= 0 && std::isfinite(c.dormant_tau)))
+      throw std::runtime_error("dormant_tau must be finite and non-negative");
+    for (const char *k : {"activation_stats_interval", "dormant_tau"})
+      if (kv.count(k) && !c.log_activation_stats) // (nothing else reads them)
+        throw std::runtime_error(std::string(k) + " needs log_activation_stats: true");
+  }
   c.kl_coef_set = kv.count("kl_coef") != 0;
   c.kl_target_set = kv.count("kl_target") != 0;
   if (!(c.kl_coef >= 0 && c.kl_coef < 3.0e38) || !(c.kl_target >= 0 && c.kl_target < 3.0e38)) // (beta is a float)
@@ -326,6 +343,7 @@ static HParams hparams_of(const Config &c) {
                                                     {"minibatch_advantage_norm", c.minibatch_advantage_norm},
                                                     {"log_batch_stats", c.log_batch_stats},
                                                     {"log_tensor_stats", c.log_tensor_stats},
+                                                    {"log_activation_stats", c.log_activation_stats},
                                                     {"reward_scaling", c.reward_scaling},
                                                     {"device_environments", c.device_environments},
                                                     {"device_evaluation", c.device_evaluation},

@@ -45,7 +45,13 @@
 // is not a collective, and every rank holds the same parameters and all-reduced gradient - reads both sections of
 // aleppo_tensor_stats and logs tensor_stats/<tensor>/grad_norm, /param_norm and /update_ratio for the twelve tensors
 // (conv1.w ... value.b) and total, and tensor_stats/nonfinite, the two non-finite counts of the whole model added; a
-// library without the entry point refuses the key at start-up).  clip_param_final, value_loss_coef_final, entropy_coef_final,
+// library without the entry point refuses the key at start-up).  log_activation_stats: false (true: after the update of
+// every activation_stats_interval-th rollout - default 1 - rank 0 calls aleppo_activation_stats on the batch the context
+// holds, with the dormancy threshold dormant_tau - default 0.025 - and logs, for conv1, conv2, conv3, fc and total,
+// activation_stats/<layer>/dormant_fraction, /dead_fraction, /positive_fraction and /mean_abs, and
+// activation_stats/nonfinite; never a collective: the figures describe rank 0's samples; a library without the entry point
+// refuses the key at start-up, and a dormant_tau that is negative or not a finite number, or an interval below 1, is
+// refused when the config is loaded).  clip_param_final, value_loss_coef_final, entropy_coef_final,
 // max_gradient_norm_final (absent: the value stays what the config says and no option is set; given: rollout i of
 // num_rollouts updates with v0 + (v_final - v0) * i / num_rollouts, computed in double and rounded to float once - the
 // shape of the learning-rate anneal, which never reaches its end value either - set through ALEPPO_OPT_CLIP_PARAM /
@@ -147,6 +153,8 @@
 #pragma weak aleppo_env_read
 // ... and the per-tensor statistics (log_tensor_stats: true)
 #pragma weak aleppo_tensor_stats
+// ... and the per-unit activation statistics (log_activation_stats: true)
+#pragma weak aleppo_activation_stats
 // ... and the device-resident evaluation environments (device_evaluation: true)
 #pragma weak aleppo_eval_env_open
 #pragma weak aleppo_eval_env_run
@@ -296,6 +304,9 @@ static void refuse_missing_entry_points(const Config &cfg) {
   if (cfg.log_tensor_stats && !aleppo_tensor_stats)
     throw std::runtime_error("log_tensor_stats is set but this build's library has no per-tensor statistics "
                              "(aleppo_tensor_stats is missing)");
+  if (cfg.log_activation_stats && !aleppo_activation_stats)
+    throw std::runtime_error("log_activation_stats is set but this build's library has no activation statistics "
+                             "(aleppo_activation_stats is missing)");
 }
 
 // ------------------------------------------------------------------ start-up
@@ -656,6 +667,8 @@ static const std::pair<int, const char *> SAMPLE_FIELDS[5] = {{ALEPPO_M_TOTAL_LO
 static const char *const TENSOR_STAT_NAMES[ALEPPO_TENSOR_STATS_ROWS] = {
     "conv1.w", "conv1.b", "conv2.w", "conv2.b", "conv3.w", "conv3.b", "fc.w", "fc.b", "action.w", "action.b", "value.w",
     "value.b", "total"};
+// the rows of aleppo_activation_stats' layer table
+static const char *const ACT_LAYER_NAMES[ALEPPO_ACT_LAYER_ROWS] = {"conv1", "conv2", "conv3", "fc", "total"};
 // metrics of every epoch that ran: per minibatch, and the per-sample planes of log_data's histograms ([epochs][N])
 struct Update {
   const size_t nmb, N, slots; // minibatches per epoch, samples per epoch, minibatch slots of num_epochs epochs
@@ -668,6 +681,9 @@ struct Update {
   float kl_beta = 0;   // the beta this update ran with ...
   double last_kl = 0;  // ... and the mean exact KL over the minibatches of its last epoch
   double tensor_stats[ALEPPO_TENSOR_STATS_ROWS][ALEPPO_TENSOR_STATS_COLS] = {}; // log_tensor_stats, rank 0: after the update
+  bool act_stats_read = false; // log_activation_stats, rank 0: this rollout is one of the interval's, act_layers is its table
+  double act_layers[ALEPPO_ACT_LAYER_ROWS][ALEPPO_ACT_LAYER_COLS] = {};
+  std::vector<double> act_units; // [(160 + H) * ALEPPO_ACT_UNIT_COLS] (the call fills it; only the layer table is logged)
   explicit Update(const Run &run)
       : nmb((size_t)run.cfg.num_mini_batches), N(run.E * run.T), slots((size_t)run.cfg.num_epochs * nmb), m(slots),
         kl(slots), cf(slots), adv_std(run.cfg.minibatch_advantage_norm ? slots : 0), mean_kl(run.kl_penalty() ? slots : 0),
@@ -726,6 +742,13 @@ static void update(Run &run, size_t r, Update &u) {
     Profile::Span sp(&run.prof, "aleppo_tensor_stats");
     check(ctx, aleppo_tensor_stats(ctx, ALEPPO_TS_SEC_PARAMS | ALEPPO_TS_SEC_STEP, &u.tensor_stats[0][0],
                                    (size_t)ALEPPO_TENSOR_STATS_ROWS * ALEPPO_TENSOR_STATS_COLS));
+  }
+  u.act_stats_read = cfg.log_activation_stats && run.rank == 0 && (r + 1) % cfg.activation_stats_interval == 0;
+  if (u.act_stats_read) { // (not a collective: rank 0's samples, the batch this update trained on, under the new weights)
+    Profile::Span sp(&run.prof, "aleppo_activation_stats");
+    u.act_units.resize((size_t)(160 + cfg.hidden_size) * ALEPPO_ACT_UNIT_COLS);
+    check(ctx, aleppo_activation_stats(ctx, nullptr, 0, cfg.dormant_tau, u.act_units.data(), u.act_units.size(),
+                                       &u.act_layers[0][0], (size_t)ALEPPO_ACT_LAYER_ROWS * ALEPPO_ACT_LAYER_COLS));
   }
 }
 
@@ -797,6 +820,18 @@ static void log_scalars(Run &run, const EpisodeLog &log, const BatchStatistics &
     const double *total = u.tensor_stats[ALEPPO_TENSOR_STATS_ROWS - 1];
     logger.add_scalar("tensor_stats/nonfinite", step,
                       (float)(total[ALEPPO_TS_PARAM_NONFINITE] + total[ALEPPO_TS_STEP_NONFINITE]));
+  }
+  if (u.act_stats_read) { // (of the batch this update trained on; set on rank 0 only)
+    for (int k = 0; k < ALEPPO_ACT_LAYER_ROWS; ++k) {
+      const std::string tag = std::string("activation_stats/") + ACT_LAYER_NAMES[k];
+      const double *row = u.act_layers[k];
+      logger.add_scalar(tag + "/dormant_fraction", step, (float)(row[ALEPPO_ACT_L_DORMANT] / row[ALEPPO_ACT_L_UNITS]));
+      logger.add_scalar(tag + "/dead_fraction", step, (float)(row[ALEPPO_ACT_L_DEAD] / row[ALEPPO_ACT_L_UNITS]));
+      logger.add_scalar(tag + "/positive_fraction", step, (float)row[ALEPPO_ACT_L_POSITIVE_FRACTION]);
+      logger.add_scalar(tag + "/mean_abs", step, (float)row[ALEPPO_ACT_L_MEAN_ABS]);
+    }
+    logger.add_scalar("activation_stats/nonfinite", step,
+                      (float)u.act_layers[ALEPPO_ACT_LAYER_ROWS - 1][ALEPPO_ACT_L_NONFINITE]);
   }
   for (size_t k = 0; k < run.schedules.size(); ++k) // (the values this rollout's update ran with)
     logger.add_scalar(run.schedules[k].name, step, u.hyper_now[k]);
