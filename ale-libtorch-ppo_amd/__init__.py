@@ -74,6 +74,12 @@ ACT_LAYER_ROWS = ACT_LAYERS + ("total",)
 ACT_UNIT_COLS, ACT_LAYER_COLS = 5, 8
 ACT_UNIT_STATS = dict(mean_abs=0, positive_fraction=1, max_abs=2, score=3, nonfinite=4)
 ACT_LAYER_STATS = dict(units=0, elements=1, mean_abs=2, positive_fraction=3, max_abs=4, dead=5, dormant=6, nonfinite=7)
+# aleppo_recycle_units / aleppo_recycle_dormant: the layer bits, the flags and the rows of counts (Engine.recycle_units /
+# Engine.recycle_dormant)
+RECYCLE_COUNTS = 5
+RECYCLE_CONV1, RECYCLE_CONV2, RECYCLE_CONV3, RECYCLE_FC, RECYCLE_ALL = 1, 2, 4, 8, 15
+RECYCLE_LAYERS = dict(conv1=RECYCLE_CONV1, conv2=RECYCLE_CONV2, conv3=RECYCLE_CONV3, fc=RECYCLE_FC, all=RECYCLE_ALL)
+RECYCLE_KEEP_MOMENTS = 1
 # aleppo_eval_rule / aleppo_eval_field: the evaluation lanes (Engine.eval_open / eval_push_frames / eval_act / eval_read)
 EVAL_GREEDY, EVAL_SAMPLE, EVAL_EPSILON_GREEDY = 0, 1, 2
 EVAL_RULES = dict(greedy=EVAL_GREEDY, sample=EVAL_SAMPLE, epsilon=EVAL_EPSILON_GREEDY)
@@ -105,7 +111,7 @@ REC_STEP_DTYPE = np.dtype([("ordinal", "<u8"), ("action", "<i4"), ("reward", "<f
 KERNEL_CLASSES = dict(ingest=0, gae=1, head=2, adam=3, conv1_fwd=4, conv2_fwd=5, conv3_fwd=6, fc_fwd=7, fc_dgrad=8,
                       fc_wgrad=9, conv3_dgrad=10, conv3_wgrad=11, conv2_dgrad=12, conv2_wgrad=13, conv1_wgrad=14,
                       reduce=15, infer_head=16, act_fused=17, conv_fwd=18, conv_bwd=19, rec_capture=20,
-                      act_stats=21)
+                      act_stats=21, recycle=22)
 
 # every symbol include/aleppo.h declares (checked by tests/test_abi.py against the header text)
 # aleppo_set_option keys (include/aleppo.h)
@@ -154,6 +160,7 @@ EXPORTS = [
     "aleppo_export_rollout_state", "aleppo_import_rollout_state", "aleppo_state_digest",
     "aleppo_tensor_stats",
     "aleppo_forward_activations", "aleppo_activation_stats",
+    "aleppo_recycle_units", "aleppo_recycle_dormant",
     "aleppo_env_open", "aleppo_env_rollout", "aleppo_env_export_state", "aleppo_env_import_state", "aleppo_env_read",
     "aleppo_eval_env_open", "aleppo_eval_env_run", "aleppo_eval_env_export_state", "aleppo_eval_env_import_state",
     "aleppo_eval_env_read",
@@ -743,6 +750,42 @@ class Engine:
                            for k, l in enumerate(ACT_LAYERS)},
                     layers={l: {s: float(layers[k, i]) for s, i in ACT_LAYER_STATS.items()}
                             for k, l in enumerate(ACT_LAYER_ROWS)})
+
+    @staticmethod
+    def _recycle_layer_bits(layers):
+        if isinstance(layers, (int, np.integer)):
+            return int(layers)
+        names = (layers,) if isinstance(layers, str) else tuple(layers)
+        if not names or any(l not in RECYCLE_LAYERS for l in names):
+            raise AleppoInvalidArgument(f"layers must be 'all' or a non-empty subset of {ACT_LAYERS}")
+        bits = 0
+        for l in names:
+            bits |= RECYCLE_LAYERS[l]
+        return bits
+
+    def recycle_units(self, mask, key=0, keep_moments=False):
+        """aleppo_recycle_units: recycle (ReDo) the units of a uint8 / bool [160 + H] mask in the unit order of
+        activation_stats - their incoming weights re-initialised from `key`, their outgoing weights zeroed, the Adam
+        moments of both reset unless keep_moments.  {layer: masked units} over ACT_LAYERS and "total"."""
+        m = _u8(mask).reshape(-1)
+        counts = np.zeros(RECYCLE_COUNTS, np.int64)
+        self._c(lib().aleppo_recycle_units(self._ctx, _ptr(m), C.c_size_t(m.size), C.c_uint64(key),
+                                           C.c_int(RECYCLE_KEEP_MOMENTS if keep_moments else 0), _ptr(counts)))
+        return {l: int(counts[k]) for k, l in enumerate(ACT_LAYER_ROWS)}
+
+    def recycle_dormant(self, observations=None, tau=0.025, layers="all", key=0, keep_moments=False):
+        """aleppo_recycle_dormant: score the units as activation_stats does (observations=None: the batch the context
+        holds), recycle those of `layers` ("all", a layer name, a list of names, or RECYCLE_* bits) whose score is <= tau,
+        without the scores leaving the device.  (mask uint8 [160 + H], {layer: recycled units})."""
+        obs = None if observations is None else _u8(observations)
+        n = 0 if obs is None else obs.shape[0]
+        mask = np.zeros(160 + self.H, np.uint8)
+        counts = np.zeros(RECYCLE_COUNTS, np.int64)
+        self._c(lib().aleppo_recycle_dormant(self._ctx, _ptr(obs), C.c_int64(n), C.c_double(tau),
+                                             C.c_int(self._recycle_layer_bits(layers)), C.c_uint64(key),
+                                             C.c_int(RECYCLE_KEEP_MOMENTS if keep_moments else 0), _ptr(mask),
+                                             C.c_size_t(mask.size), _ptr(counts)))
+        return mask, {l: int(counts[k]) for k, l in enumerate(ACT_LAYER_ROWS)}
 
     def read_batch(self, name):
         E, T, A = self.E, self.T, self.A

@@ -66,18 +66,14 @@ extern "C" int aleppo_forward_activations(aleppo_ctx *c, const uint8_t *observat
   return ALEPPO_OK;
 }
 
-extern "C" int aleppo_activation_stats(aleppo_ctx *c, const uint8_t *observations, int64_t n, double tau, double *units,
-                                       size_t unit_count, double *layers, size_t layer_count) {
-  CHECK_CTX(c);
-  const size_t U = (size_t)(A1_C + A2_C + A3_C + c->H);
-  constexpr size_t LAYER_COUNT = (size_t)ALEPPO_ACT_LAYER_ROWS * ALEPPO_ACT_LAYER_COLS;
+namespace aleppo {
+// what aleppo_activation_stats refuses in tau and in its source of samples (aleppo_recycle_dormant measures the same way)
+int act_stats_check_tau(aleppo_ctx *c, double tau) {
   if (!(tau >= 0.0) || !std::isfinite(tau))
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "activation_stats: tau must be finite and non-negative");
-  if (!units || !layers)
-    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "activation_stats: null argument");
-  if (unit_count != U * ALEPPO_ACT_UNIT_COLS || layer_count != LAYER_COUNT)
-    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT,
-                   "activation_stats: unit_count must be (160 + H) * 5 and layer_count 40");
+  return ALEPPO_OK;
+}
+int act_stats_check_source(aleppo_ctx *c, const uint8_t *observations, int64_t n) {
   const bool batch = observations == nullptr;
   if (batch && n != 0)
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "activation_stats: null observations need n == 0 (the context's batch)");
@@ -85,6 +81,13 @@ extern "C" int aleppo_activation_stats(aleppo_ctx *c, const uint8_t *observation
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "activation_stats: n exceeds capacity");
   if (batch && c->batch_n <= 0)
     return set_err(c, ALEPPO_ERR_RUNTIME, "no batch: call aleppo_finish_rollout or aleppo_set_batch first");
+  return ALEPPO_OK;
+}
+// the measurement itself, arguments already checked: the stream's synchronise, the forward chunks with one pass each and the
+// finalising launch, all enqueued; *units_dev / *layers_dev: the two tables in the context's scratch (device memory)
+int act_stats_measure(aleppo_ctx *c, const uint8_t *observations, int64_t n, double tau, const double **units_dev,
+                      const double **layers_dev) {
+  const bool batch = observations == nullptr;
   const long total = batch ? c->batch_n : (long)n;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->pre_acted = -1; // a1 / a2 / a3 / h are shared scratch
@@ -108,9 +111,29 @@ extern "C" int aleppo_activation_stats(aleppo_ctx *c, const uint8_t *observation
     launch_act_stats_partial(c->stream, c->prec, c->a1, c->a2, c->a3, c->h, c->H, ns, pl, done, c->as_scratch);
     prof_end(c, ALEPPO_K_ACT_STATS);
   }
-  const double *units_dev = nullptr, *layers_dev = nullptr;
-  launch_act_stats_final(c->stream, c->H, total, tau, pl, done, c->as_scratch, &units_dev, &layers_dev);
+  launch_act_stats_final(c->stream, c->H, total, tau, pl, done, c->as_scratch, units_dev, layers_dev);
   HIPCHK(c, hipGetLastError());
+  return ALEPPO_OK;
+}
+} // namespace aleppo
+
+extern "C" int aleppo_activation_stats(aleppo_ctx *c, const uint8_t *observations, int64_t n, double tau, double *units,
+                                       size_t unit_count, double *layers, size_t layer_count) {
+  CHECK_CTX(c);
+  const size_t U = (size_t)(A1_C + A2_C + A3_C + c->H);
+  constexpr size_t LAYER_COUNT = (size_t)ALEPPO_ACT_LAYER_ROWS * ALEPPO_ACT_LAYER_COLS;
+  if (int rc = act_stats_check_tau(c, tau))
+    return rc;
+  if (!units || !layers)
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "activation_stats: null argument");
+  if (unit_count != U * ALEPPO_ACT_UNIT_COLS || layer_count != LAYER_COUNT)
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT,
+                   "activation_stats: unit_count must be (160 + H) * 5 and layer_count 40");
+  if (int rc = act_stats_check_source(c, observations, n))
+    return rc;
+  const double *units_dev = nullptr, *layers_dev = nullptr;
+  if (int rc = act_stats_measure(c, observations, n, tau, &units_dev, &layers_dev))
+    return rc;
   std::vector<double> hu(U * ALEPPO_ACT_UNIT_COLS);
   double hl[LAYER_COUNT];
   HIPCHK(c, hipMemcpyAsync(hu.data(), units_dev, hu.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));

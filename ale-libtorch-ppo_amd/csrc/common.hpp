@@ -265,6 +265,8 @@ struct Ctx {
   float *ax_buf = nullptr;
   size_t ax_cap = 0;                    // bytes
   void *as_scratch = nullptr;
+  // ---- aleppo_recycle_units / aleppo_recycle_dormant: the unit mask, uint8 [160 + H] (allocated on first use)
+  uint8_t *rc_mask = nullptr;
   // ---- evaluation lanes (aleppo_eval_open): L frame stacks of their own, their own acting scratch, upload staging and
   // action hand-off; nothing below is allocated, and nothing is enqueued for it, on a context that never opens them
   int ev_L = 0;                    // 0: not opened
@@ -484,6 +486,13 @@ void launch_act_stats_partial(hipStream_t s, int prec, const void *a1, const voi
 void launch_act_stats_final(hipStream_t s, int H, long total, double tau, const ActStatsPlan &pl, const size_t done[4],
                             void *scratch, const double **units_dev, const double **layers_dev);
 void launch_act_export(hipStream_t s, int prec, int layer, const void *a, float *out, long ns);
+// aleppo_recycle_units / aleppo_recycle_dormant (recycle.hip).  mask: uint8 [160 + H] in device memory, 4-byte aligned, in
+// the unit order of aleppo_activation_stats.  launch_recycle_mask forms it from that entry point's device-side unit table
+// (mask[u] = layer bit of u in layers && SCORE_u <= tau); launch_recycle is the one pass over P / M1 / M2 in the internal
+// layout (key: splitmix64 of the call's key); the caller rebuilds the derived copies (refresh_compute_copies).
+void launch_recycle_mask(hipStream_t s, const double *units_dev, int H, double tau, int layers, uint8_t *mask);
+void launch_recycle(hipStream_t s, const ParamLayout &L, const uint8_t *mask, unsigned long long key, bool keep_moments,
+                    float *P, float *M1, float *M2);
 void launch_heads_fwd(hipStream_t s, const float *h, const float *Wh, const float *bh, float *logits, float *values,
                       long n, int H, int A);
 void launch_logsoftmax_rows(hipStream_t s, const float *in, float *out, long rows, int A);

@@ -539,6 +539,61 @@ typedef enum {
 int aleppo_activation_stats(aleppo_ctx *ctx, const uint8_t *observations, int64_t n, double tau, double *units,
                             size_t unit_count, double *layers, size_t layer_count);
 
+/* Recycling units (ReDo, the second half of Sokar et al. 2023; the reference has none): re-initialise the incoming
+ * weights of every masked unit, zero its outgoing weights and reset the Adam moments of both, in place on the device - the
+ * master parameters, both moments and every derived copy (the bf16 compute copy, the data-gradient layouts) follow.
+ * mask / mask_out: uint8 [160 + H] in the unit order of aleppo_activation_stats (conv1 0-31, conv2 0-63, conv3 0-63,
+ *   fc 0..H-1); unit_count must be 160 + H; every mask byte must be 0 or 1.  Let m1, m2, m3, m4 be the four layers' masks.
+ * What a recycle does, in the reference's tensor terms:
+ *   conv1.w[o,c,kh,kw]        re-initialised if m1[o]
+ *   conv2.w[o,c,kh,kw]        zero if m1[c], otherwise re-initialised if m2[o]
+ *   conv3.w[o,c,kh,kw]        zero if m2[c], otherwise re-initialised if m3[o]
+ *   fc.w[o, c*49 + p]         zero if m3[c], otherwise re-initialised if m4[o]
+ *   conv1.b conv2.b conv3.b fc.b [o]   zero if unit o is masked
+ *   action.w[a,j] value.w[0,j]         zero if m4[j]
+ *   action.b value.b          never touched
+ *   ZERO WINS: a weight that is both an outgoing weight of a masked unit and an incoming weight of another masked unit
+ *   becomes zero (the order of ReDo's own implementation).  exp_avg and exp_avg_sq of every element a rule selects become
+ *   +0.0f unless ALEPPO_RECYCLE_KEEP_MOMENTS is set; the Adam step count is unchanged.  The exported gradient, every
+ *   element no rule selects and every alignment pad are not written at all.
+ * The re-initialised value of element i, i its index in the flat aleppo_export_params vector, with splitmix64 as
+ * specified at aleppo_read_sample_order:
+ *   r = splitmix64(splitmix64(key) ^ (uint64)i)
+ *   k = (int32)(r >> 40) - 8388608                       in [-2^23, 2^23)
+ *   w = a_l * ((float)k * 0x1p-23f)                      fp32; the inner product is exact, so one rounding
+ *   a_l = (float)sqrt(6.0 / fan_in), fan_in = 256, 512, 576, 3136 (conv1, conv2, conv3, fc)
+ *   This is He-uniform on [-a_l, a_l): its per-element variance a_l^2 / 3 = 2 / fan_in is the variance of an element of
+ *   the trainer's orthogonal initialisation with gain sqrt 2 (trainer/init.hpp).  It is stateless and every element is
+ *   computed on its own, so any host recomputes it bit for bit, and two ranks given the same mask and key stay identical:
+ *   the key must not contain the rank.
+ * Afterwards aleppo_tensor_stats refuses ALEPPO_TS_SEC_STEP until the next aleppo_train (as after
+ *   aleppo_import_optimizer), and what aleppo_step pre-computed for the next aleppo_act is dropped.  A captured update
+ *   (ALEPPO_OPT_UPDATE_GRAPH) stays valid: no pointer changes.  counts: the masked units of conv1, conv2, conv3, fc and their
+ *   sum.  An all-zero mask runs the pass and changes no bit.
+ * aleppo_recycle_units takes the mask from the caller.  It is deterministic given (mask, key), so it is allowed under data
+ *   parallelism: give every rank the same mask and key.
+ * aleppo_recycle_dormant runs exactly the measurement of aleppo_activation_stats (observations, n and tau as there;
+ *   observations == NULL and n == 0: the batch the context holds), then one small launch forms the mask from the device-side
+ *   unit table - mask[u] = (the layer of u is in layers) && SCORE_u <= tau, the rule ALEPPO_ACT_L_DORMANT counts by - and the
+ *   pass follows; no table crosses to the host in between.  All layers are scored on the parameters as they stood at entry
+ *   and recycled together.  layers: a non-empty set of ALEPPO_RECYCLE_CONV1 ... ALEPPO_RECYCLE_FC bits.  mask_out (may be
+ *   NULL) receives the mask.  Under world_size > 1 the scores describe one rank's samples and the ranks would pick different
+ *   units, so it returns ALEPPO_ERR_RUNTIME there; a collective score is out of scope.
+ * Both run on the context's stream, synchronise that stream only and are never a collective.  A context that never calls
+ *   them enqueues and allocates exactly what it did before.
+ * Errors: a NULL mask or counts, a wrong unit_count, a mask byte above 1, unknown flag bits, layers zero or with other
+ *   bits: ALEPPO_ERR_INVALID_ARGUMENT; what aleppo_activation_stats refuses in tau, observations and n: the code it gives;
+ *   a step is armed: ALEPPO_ERR_RUNTIME.  A failed call changes nothing. */
+#define ALEPPO_RECYCLE_COUNTS 5 /* conv1, conv2, conv3, fc, total */
+enum { ALEPPO_RECYCLE_CONV1 = 1, ALEPPO_RECYCLE_CONV2 = 2, ALEPPO_RECYCLE_CONV3 = 4, ALEPPO_RECYCLE_FC = 8,
+       ALEPPO_RECYCLE_ALL = 15 };
+enum { ALEPPO_RECYCLE_KEEP_MOMENTS = 1 }; /* flags */
+int aleppo_recycle_units(aleppo_ctx *ctx, const uint8_t *mask, size_t unit_count, uint64_t key, int flags,
+                         int64_t counts[ALEPPO_RECYCLE_COUNTS]);
+int aleppo_recycle_dormant(aleppo_ctx *ctx, const uint8_t *observations, int64_t n, double tau, int layers,
+                           uint64_t key, int flags, uint8_t *mask_out, size_t unit_count,
+                           int64_t counts[ALEPPO_RECYCLE_COUNTS]);
+
 /* ------------------------------------------------------------------ evaluation lanes (the reference has no evaluation
  * loop: SB3's predict(deterministic=True) / EvalCallback, the epsilon-greedy scores of the DQN / PPO papers)
  * L frame stacks of their own, next to the rollout, on which the network acts under one of three rules - so that a
@@ -890,7 +945,8 @@ typedef enum {
   ALEPPO_K_CONV_BWD = 19,   /* conv2 dgrad + conv2 wgrad + conv1 wgrad of the update's backward pass in one launch (bf16) */
   ALEPPO_K_REC_CAPTURE = 20, /* the episode recorders' capture kernel (aleppo_rec_open), one launch per recorded step */
   ALEPPO_K_ACT_STATS = 21,  /* aleppo_activation_stats' read-only pass over a1 / a2 / a3 / h, one launch per forward chunk */
-  ALEPPO_K_COUNT = 22
+  ALEPPO_K_RECYCLE = 22,    /* the masked pass of aleppo_recycle_units / aleppo_recycle_dormant over P / M1 / M2, one launch per call */
+  ALEPPO_K_COUNT = 23
 } aleppo_kernel_class;
 int aleppo_profile_enable(aleppo_ctx *ctx, int on);
 int aleppo_profile_read(aleppo_ctx *ctx, int kernel_class, double *avg_ms, int64_t *launches);

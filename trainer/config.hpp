@@ -58,6 +58,13 @@ struct Config {
   bool log_activation_stats = false;
   size_t activation_stats_interval = 1; // after the update of every n-th rollout
   double dormant_tau = 0.025;           // the dormancy threshold (Sokar et al. 2023)
+  // extension: ReDo (Sokar et al. 2023) - recycle the dormant units of the held batch (aleppo_recycle_dormant)
+  bool recycle_dormant = false;
+  // after the update of every n-th rollout.  64: ReDo recycles every 1000 gradient steps; the benched configuration takes
+  // 16 minibatch steps per rollout (1 epoch x 16 minibatches), and 1000 / 16 = 62.5 rounds to 64
+  size_t recycle_interval = 64;
+  double recycle_tau = 0.025;                // the dormancy threshold of the recycle
+  int recycle_layers = ALEPPO_RECYCLE_ALL;   // ALEPPO_RECYCLE_* bits (the key: a list of conv1 / conv2 / conv3 / fc)
   // extensions
   std::string precision = "fp32", rollout_precision = "fp32";
   bool device_preprocess = false; // emulators hand over raw frame pairs; gray LUT + resize + max run on the device (N2)
@@ -163,6 +170,39 @@ static Config load_config(const std::string &path) { // keys / defaults of src/b
     for (const char *k : {"activation_stats_interval", "dormant_tau"})
       if (kv.count(k) && !c.log_activation_stats) // (nothing else reads them)
         throw std::runtime_error(std::string(k) + " needs log_activation_stats: true");
+  }
+  read_key(kv, "recycle_dormant", c.recycle_dormant);
+  { // what aleppo_recycle_dormant would refuse is refused here
+    const long interval = as<long>(kv, "recycle_interval", (long)c.recycle_interval);
+    if (interval < 1)
+      throw std::runtime_error("recycle_interval must be positive");
+    c.recycle_interval = (size_t)interval;
+    read_key(kv, "recycle_tau", c.recycle_tau);
+    if (!(c.recycle_tau >= 0 && std::isfinite(c.recycle_tau)))
+      throw std::runtime_error("recycle_tau must be finite and non-negative");
+    if (kv.count("recycle_layers")) { // "[conv1, fc]" or "conv1, fc"
+      static const std::pair<const char *, int> names[4] = {{"conv1", ALEPPO_RECYCLE_CONV1}, {"conv2", ALEPPO_RECYCLE_CONV2},
+                                                            {"conv3", ALEPPO_RECYCLE_CONV3}, {"fc", ALEPPO_RECYCLE_FC}};
+      std::string list = kv.at("recycle_layers");
+      if (list.size() >= 2 && list.front() == '[' && list.back() == ']')
+        list = list.substr(1, list.size() - 2);
+      c.recycle_layers = 0;
+      std::istringstream ss(list);
+      for (std::string item; std::getline(ss, item, ',');) {
+        int bit = 0;
+        for (const auto &nb : names)
+          if (trim(item) == nb.first)
+            bit = nb.second;
+        if (!bit)
+          throw std::runtime_error("recycle_layers: unknown layer '" + trim(item) + "' (conv1, conv2, conv3, fc)");
+        c.recycle_layers |= bit;
+      }
+      if (!c.recycle_layers)
+        throw std::runtime_error("recycle_layers must name at least one of conv1, conv2, conv3, fc");
+    }
+    for (const char *k : {"recycle_interval", "recycle_tau", "recycle_layers"})
+      if (kv.count(k) && !c.recycle_dormant) // (nothing else reads them)
+        throw std::runtime_error(std::string(k) + " needs recycle_dormant: true");
   }
   c.kl_coef_set = kv.count("kl_coef") != 0;
   c.kl_target_set = kv.count("kl_target") != 0;
@@ -344,6 +384,7 @@ static HParams hparams_of(const Config &c) {
                                                     {"log_batch_stats", c.log_batch_stats},
                                                     {"log_tensor_stats", c.log_tensor_stats},
                                                     {"log_activation_stats", c.log_activation_stats},
+                                                    {"recycle_dormant", c.recycle_dormant},
                                                     {"reward_scaling", c.reward_scaling},
                                                     {"device_environments", c.device_environments},
                                                     {"device_evaluation", c.device_evaluation},

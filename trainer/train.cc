@@ -51,7 +51,14 @@
 // activation_stats/<layer>/dormant_fraction, /dead_fraction, /positive_fraction and /mean_abs, and
 // activation_stats/nonfinite; never a collective: the figures describe rank 0's samples; a library without the entry point
 // refuses the key at start-up, and a dormant_tau that is negative or not a finite number, or an interval below 1, is
-// refused when the config is loaded).  clip_param_final, value_loss_coef_final, entropy_coef_final,
+// refused when the config is loaded).  recycle_dormant: false (true: ReDo, Sokar et al. 2023 - after the update of every
+// recycle_interval-th rollout - default 64: ReDo's 1000 gradient steps at the 16 minibatch steps per rollout of the benched
+// configuration - the trainer calls aleppo_recycle_dormant on the batch the context holds, with the threshold recycle_tau -
+// default 0.025 - on the layers of recycle_layers - a list of conv1 / conv2 / conv3 / fc, default all - and the key
+// splitmix64(seed ^ rollout index), so that a resumed run replays the same recycles; this comes after the statistics above
+// are read, before the iteration's checkpoint is written and before any digest is taken; it logs recycle/<layer>/units and
+// recycle/total; the three other keys without recycle_dormant, a bad tau, interval or layer name, a library without the
+// entry point and WORLD_SIZE > 1 - the scores describe one rank's samples - are refused at start-up).  clip_param_final, value_loss_coef_final, entropy_coef_final,
 // max_gradient_norm_final (absent: the value stays what the config says and no option is set; given: rollout i of
 // num_rollouts updates with v0 + (v_final - v0) * i / num_rollouts, computed in double and rounded to float once - the
 // shape of the learning-rate anneal, which never reaches its end value either - set through ALEPPO_OPT_CLIP_PARAM /
@@ -155,6 +162,8 @@
 #pragma weak aleppo_tensor_stats
 // ... and the per-unit activation statistics (log_activation_stats: true)
 #pragma weak aleppo_activation_stats
+// ... and the recycling of dormant units (recycle_dormant: true)
+#pragma weak aleppo_recycle_dormant
 // ... and the device-resident evaluation environments (device_evaluation: true)
 #pragma weak aleppo_eval_env_open
 #pragma weak aleppo_eval_env_run
@@ -239,6 +248,8 @@ struct Run {
       throw std::runtime_error("Batch size must be divisible by num_mini_batches");
     if (E % cfg.worker_batch_size)
       std::cerr << "warning: total_environments % worker_batch_size != 0 would deadlock the reference's queue\n";
+    if (cfg.recycle_dormant && world > 1) // (each rank would score its own samples and recycle its own units)
+      throw std::runtime_error("recycle_dormant needs WORLD_SIZE 1: the dormancy scores describe one rank's samples");
     if (cfg.record_video && !cfg.device_environments)
       std::cerr << "note: record_video ignored (it needs device_environments: true; the host emulators are not recorded)\n";
     const std::string rank_suffix = world > 1 ? ".rank" + std::to_string(rank) : "";
@@ -307,6 +318,9 @@ static void refuse_missing_entry_points(const Config &cfg) {
   if (cfg.log_activation_stats && !aleppo_activation_stats)
     throw std::runtime_error("log_activation_stats is set but this build's library has no activation statistics "
                              "(aleppo_activation_stats is missing)");
+  if (cfg.recycle_dormant && !aleppo_recycle_dormant)
+    throw std::runtime_error("recycle_dormant is set but this build's library cannot recycle units "
+                             "(aleppo_recycle_dormant is missing)");
 }
 
 // ------------------------------------------------------------------ start-up
@@ -669,6 +683,12 @@ static const char *const TENSOR_STAT_NAMES[ALEPPO_TENSOR_STATS_ROWS] = {
     "value.b", "total"};
 // the rows of aleppo_activation_stats' layer table
 static const char *const ACT_LAYER_NAMES[ALEPPO_ACT_LAYER_ROWS] = {"conv1", "conv2", "conv3", "fc", "total"};
+static uint64_t splitmix64(uint64_t x) { // the permutation of aleppo.h (aleppo_read_sample_order)
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
 // metrics of every epoch that ran: per minibatch, and the per-sample planes of log_data's histograms ([epochs][N])
 struct Update {
   const size_t nmb, N, slots; // minibatches per epoch, samples per epoch, minibatch slots of num_epochs epochs
@@ -684,6 +704,8 @@ struct Update {
   bool act_stats_read = false; // log_activation_stats, rank 0: this rollout is one of the interval's, act_layers is its table
   double act_layers[ALEPPO_ACT_LAYER_ROWS][ALEPPO_ACT_LAYER_COLS] = {};
   std::vector<double> act_units; // [(160 + H) * ALEPPO_ACT_UNIT_COLS] (the call fills it; only the layer table is logged)
+  bool recycled = false; // recycle_dormant: this rollout is one of the interval's, recycle_counts is what it recycled
+  int64_t recycle_counts[ALEPPO_RECYCLE_COUNTS] = {};
   explicit Update(const Run &run)
       : nmb((size_t)run.cfg.num_mini_batches), N(run.E * run.T), slots((size_t)run.cfg.num_epochs * nmb), m(slots),
         kl(slots), cf(slots), adv_std(run.cfg.minibatch_advantage_norm ? slots : 0), mean_kl(run.kl_penalty() ? slots : 0),
@@ -749,6 +771,17 @@ static void update(Run &run, size_t r, Update &u) {
     u.act_units.resize((size_t)(160 + cfg.hidden_size) * ALEPPO_ACT_UNIT_COLS);
     check(ctx, aleppo_activation_stats(ctx, nullptr, 0, cfg.dormant_tau, u.act_units.data(), u.act_units.size(),
                                        &u.act_layers[0][0], (size_t)ALEPPO_ACT_LAYER_ROWS * ALEPPO_ACT_LAYER_COLS));
+  }
+  // ReDo: score the units on the batch this update trained on, under the new weights, and recycle the dormant ones - after
+  // the statistics above have described the update that ran (aleppo_tensor_stats refuses the step section after a recycle)
+  // and before this iteration's checkpoint and digest; the key is a function of the seed
+  // and the rollout index alone, so a resumed run replays the same recycles
+  u.recycled = cfg.recycle_dormant && (r + 1) % cfg.recycle_interval == 0;
+  if (u.recycled) {
+    Profile::Span sp(&run.prof, "aleppo_recycle_dormant");
+    check(ctx, aleppo_recycle_dormant(ctx, nullptr, 0, cfg.recycle_tau, cfg.recycle_layers,
+                                      splitmix64(cfg.seed ^ (uint64_t)r), 0, nullptr, (size_t)(160 + cfg.hidden_size),
+                                      u.recycle_counts));
   }
 }
 
@@ -832,6 +865,11 @@ static void log_scalars(Run &run, const EpisodeLog &log, const BatchStatistics &
     }
     logger.add_scalar("activation_stats/nonfinite", step,
                       (float)u.act_layers[ALEPPO_ACT_LAYER_ROWS - 1][ALEPPO_ACT_L_NONFINITE]);
+  }
+  if (u.recycled) {
+    for (int k = 0; k < 4; ++k)
+      logger.add_scalar(std::string("recycle/") + ACT_LAYER_NAMES[k] + "/units", step, (float)u.recycle_counts[k]);
+    logger.add_scalar("recycle/total", step, (float)u.recycle_counts[4]);
   }
   for (size_t k = 0; k < run.schedules.size(); ++k) // (the values this rollout's update ran with)
     logger.add_scalar(run.schedules[k].name, step, u.hyper_now[k]);
