@@ -80,6 +80,8 @@ RECYCLE_COUNTS = 5
 RECYCLE_CONV1, RECYCLE_CONV2, RECYCLE_CONV3, RECYCLE_FC, RECYCLE_ALL = 1, 2, 4, 8, 15
 RECYCLE_LAYERS = dict(conv1=RECYCLE_CONV1, conv2=RECYCLE_CONV2, conv3=RECYCLE_CONV3, fc=RECYCLE_FC, all=RECYCLE_ALL)
 RECYCLE_KEEP_MOMENTS = 1
+# aleppo_saliency_config's defaults (Engine.saliency / Engine.saliency_perturbed / saliency_tables)
+SALIENCY_STRIDE, SALIENCY_SIGMA_MASK, SALIENCY_SIGMA_BLUR, SALIENCY_PLANES = 5, 5.0, 3.0, 15
 # aleppo_eval_rule / aleppo_eval_field: the evaluation lanes (Engine.eval_open / eval_push_frames / eval_act / eval_read)
 EVAL_GREEDY, EVAL_SAMPLE, EVAL_EPSILON_GREEDY = 0, 1, 2
 EVAL_RULES = dict(greedy=EVAL_GREEDY, sample=EVAL_SAMPLE, epsilon=EVAL_EPSILON_GREEDY)
@@ -111,7 +113,7 @@ REC_STEP_DTYPE = np.dtype([("ordinal", "<u8"), ("action", "<i4"), ("reward", "<f
 KERNEL_CLASSES = dict(ingest=0, gae=1, head=2, adam=3, conv1_fwd=4, conv2_fwd=5, conv3_fwd=6, fc_fwd=7, fc_dgrad=8,
                       fc_wgrad=9, conv3_dgrad=10, conv3_wgrad=11, conv2_dgrad=12, conv2_wgrad=13, conv1_wgrad=14,
                       reduce=15, infer_head=16, act_fused=17, conv_fwd=18, conv_bwd=19, rec_capture=20,
-                      act_stats=21, recycle=22)
+                      act_stats=21, recycle=22, sal_blur=23, sal_perturb=24, sal_score=25)
 
 # every symbol include/aleppo.h declares (checked by tests/test_abi.py against the header text)
 # aleppo_set_option keys (include/aleppo.h)
@@ -161,6 +163,7 @@ EXPORTS = [
     "aleppo_tensor_stats",
     "aleppo_forward_activations", "aleppo_activation_stats",
     "aleppo_recycle_units", "aleppo_recycle_dormant",
+    "aleppo_saliency_tables", "aleppo_saliency", "aleppo_saliency_perturbed",
     "aleppo_env_open", "aleppo_env_rollout", "aleppo_env_export_state", "aleppo_env_import_state", "aleppo_env_read",
     "aleppo_eval_env_open", "aleppo_eval_env_run", "aleppo_eval_env_export_state", "aleppo_eval_env_import_state",
     "aleppo_eval_env_read",
@@ -185,6 +188,10 @@ class Config(C.Structure):
                 ("lambda_", C.c_float), ("clip_param", C.c_float), ("value_loss_coef", C.c_float),
                 ("entropy_coef", C.c_float), ("max_gradient_norm", C.c_float), ("adam_beta1", C.c_float),
                 ("adam_beta2", C.c_float), ("adam_eps", C.c_float), ("seed", C.c_uint64)]
+
+
+class SaliencyConfig(C.Structure):
+    _fields_ = [("stride", C.c_int32), ("planes", C.c_int32), ("sigma_mask", C.c_double), ("sigma_blur", C.c_double)]
 
 
 class EnvConfig(C.Structure):
@@ -239,6 +246,22 @@ def _check(rc, ctx=None):
     if rc == ERR_INVALID_ARGUMENT:
         raise AleppoInvalidArgument(msg)
     raise AleppoError(msg)
+
+
+def saliency_grid(stride=SALIENCY_STRIDE):
+    """G = ceil(84 / stride): the points per axis of the saliency grid (point (gy, gx) has its centre at pixel
+    (gy * stride, gx * stride))"""
+    return (84 + stride - 1) // stride
+
+
+def saliency_tables(stride=SALIENCY_STRIDE, sigma_mask=SALIENCY_SIGMA_MASK, sigma_blur=SALIENCY_SIGMA_BLUR,
+                    planes=SALIENCY_PLANES):
+    """aleppo_saliency_tables: (mask profile uint16 [84], blur taps uint16 [84] - w[0 .. R], zero beyond -, R), the integer
+    tables Engine.saliency perturbs with.  Built on the host: no context, no device."""
+    cfg = SaliencyConfig(stride, planes, sigma_mask, sigma_blur)
+    g, w, r = np.zeros(84, np.uint16), np.zeros(84, np.uint16), C.c_int32()
+    _check(lib().aleppo_saliency_tables(C.byref(cfg), _ptr(g), _ptr(w), C.byref(r)))
+    return g, w, r.value
 
 
 def device_check(device=0):
@@ -786,6 +809,46 @@ class Engine:
                                              C.c_int(RECYCLE_KEEP_MOMENTS if keep_moments else 0), _ptr(mask),
                                              C.c_size_t(mask.size), _ptr(counts)))
         return mask, {l: int(counts[k]) for k, l in enumerate(ACT_LAYER_ROWS)}
+
+    def _saliency_source(self, observations, first, n):
+        obs = None if observations is None else _u8(observations)
+        if obs is not None:
+            n = obs.shape[0] if n is None else n
+        elif n is None:
+            n = self._batch_n - first
+        return obs, int(first), int(n)
+
+    def saliency(self, observations=None, first=0, n=None, stride=SALIENCY_STRIDE, sigma_mask=SALIENCY_SIGMA_MASK,
+                 sigma_blur=SALIENCY_SIGMA_BLUR, planes=SALIENCY_PLANES, outputs=False):
+        """aleppo_saliency: perturbation saliency (Greydanus et al. 2018) of uint8 [n,4,84,84] observations, or
+        (observations=None) of samples [first, first + n) of the batch the context holds, in read_batch's env-major order.
+        {"policy": float32 [n,G,G], "value": float32 [n,G,G]} with G = saliency_grid(stride): 0.5 |z - z'|^2 of the logits
+        and 0.5 (v - v')^2 of the value under a local blur around grid point (gy, gx) = pixel (gy * stride, gx * stride).
+        outputs=True adds "outputs", float32 [n, G*G + 1, A + 1]: row 0 the unperturbed logits and value, row 1 + p those
+        of position p = gy * G + gx."""
+        obs, first, n = self._saliency_source(observations, first, n)
+        G = saliency_grid(stride) if 1 <= stride <= 84 else 1  # (a bad stride is the library's to refuse)
+        res = dict(policy=np.zeros((max(n, 0), G, G), np.float32), value=np.zeros((max(n, 0), G, G), np.float32))
+        if outputs:
+            res["outputs"] = np.zeros((max(n, 0), G * G + 1, self.A + 1), np.float32)
+        cfg = SaliencyConfig(stride, planes, sigma_mask, sigma_blur)
+        self._c(lib().aleppo_saliency(self._ctx, _ptr(obs), C.c_int64(first), C.c_int64(n), C.byref(cfg),
+                                      _ptr(res["policy"]), _ptr(res["value"]), _ptr(res.get("outputs"))))
+        return res
+
+    def saliency_perturbed(self, observations=None, first=0, n=None, stride=SALIENCY_STRIDE,
+                           sigma_mask=SALIENCY_SIGMA_MASK, sigma_blur=SALIENCY_SIGMA_BLUR, planes=SALIENCY_PLANES,
+                           position_first=0, position_count=None):
+        """aleppo_saliency_perturbed: uint8 [n, position_count, 4, 84, 84], the perturbed stacks saliency() forwards for the
+        positions [position_first, position_first + position_count) of each sample (default: to the end of the grid)."""
+        obs, first, n = self._saliency_source(observations, first, n)
+        G = saliency_grid(stride) if 1 <= stride <= 84 else 1
+        count = G * G - position_first if position_count is None else position_count
+        out = np.zeros((max(n, 0), max(count, 0), 4, 84, 84), np.uint8)
+        cfg = SaliencyConfig(stride, planes, sigma_mask, sigma_blur)
+        self._c(lib().aleppo_saliency_perturbed(self._ctx, _ptr(obs), C.c_int64(first), C.c_int64(n), C.byref(cfg),
+                                                C.c_int64(position_first), C.c_int64(count), _ptr(out)))
+        return out
 
     def read_batch(self, name):
         E, T, A = self.E, self.T, self.A

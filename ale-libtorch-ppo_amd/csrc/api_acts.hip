@@ -6,7 +6,7 @@
 using namespace aleppo;
 
 // the caller's observations -> packed stacks in c->stage_obs (never the rollout's slots), as aleppo_forward stages them
-static int stage_forward_input(aleppo_ctx *c, const uint8_t *observations, int64_t n, SampleMap *map) {
+int aleppo::stage_forward_input(aleppo_ctx *c, const uint8_t *observations, int64_t n, SampleMap *map) {
   if (int rc = stage_observations(c, observations, n))
     return rc;
   const size_t need = (size_t)n * FRAME_PIX * 4;

@@ -434,6 +434,7 @@ extern "C" void aleppo_destroy(aleppo_ctx *c) {
                  c->ret_p,  c->mask_p,   c->mask_counts_ep, c->shuf_keys, c->val_n, c->val_p, c->advn_part,
                  c->advn_stats, c->kl_ps, c->kl_beta, c->hyper_blk, c->rs_blk, c->ev_obs, c->ev_a1, c->ev_a2, c->ev_a3, c->ev_hpart,
                  c->ev_logits, c->ev_values, c->ev_actions, c->ev_d_frames, c->ev_d_start, c->ev_d_noise, c->ev_d_done, c->dg_out, c->env_blk, c->ee_blk, c->ts_scratch, c->ax_buf, c->as_scratch, c->rc_mask,
+                 c->sal_blur, c->sal_stage, c->sal_base, c->sal_out, c->sal_u8,
                  c->rec[0].blk, c->rec[1].blk};
   for (void *p : dev)
     if (p)

@@ -1,5 +1,5 @@
 // api_internal.hpp - what the C ABI's translation units share (api_core.hip, api_rollout.hip, api_train.hip,
-// api_batch.hip, api_eval.hip, api_eval_env.hip, api_env.hip, api_rec.hip, api_state.hip, api_acts.hip, api_recycle.hip, api_ops.hip): the entry-point guard macros and the host-side helpers.  Host code only; the
+// api_batch.hip, api_eval.hip, api_eval_env.hip, api_env.hip, api_rec.hip, api_state.hip, api_acts.hip, api_recycle.hip, api_saliency.hip, api_ops.hip): the entry-point guard macros and the host-side helpers.  Host code only; the
 // helpers are defined in api_core.hip unless noted.
 #pragma once
 #include "common.hpp"
@@ -135,6 +135,9 @@ int ensure_metric_storage(aleppo_ctx *c, int epochs, int M, long B);
 // api_batch.hip: NCHW uint8 observations of the caller -> c->stage_u8 (device), grown on demand and kept
 int stage_observations(aleppo_ctx *c, const uint8_t *observations, int64_t n);
 int ensure_val_storage(aleppo_ctx *c);
+// api_acts.hip, also for api_saliency.hip: the caller's observations -> packed stacks in c->stage_obs (never the rollout's
+// slots), as aleppo_forward stages them; *map addresses them
+int stage_forward_input(aleppo_ctx *c, const uint8_t *observations, int64_t n, SampleMap *map);
 // api_acts.hip, also for aleppo_recycle_dormant (api_recycle.hip): what aleppo_activation_stats refuses in tau and in its
 // source of samples, and the measurement itself with the arguments already checked - everything up to and including the
 // finalising launch is enqueued, *units_dev / *layers_dev are the two tables in device memory

@@ -267,6 +267,14 @@ struct Ctx {
   void *as_scratch = nullptr;
   // ---- aleppo_recycle_units / aleppo_recycle_dormant: the unit mask, uint8 [160 + H] (allocated on first use)
   uint8_t *rc_mask = nullptr;
+  // ---- aleppo_saliency / aleppo_saliency_perturbed: nothing below is allocated, and nothing is enqueued for it, on a context
+  // that never calls them; each buffer is allocated on first use, grown on demand like stage_obs and retired like it
+  uint32_t *sal_blur = nullptr;  // packed blurred stacks of the samples one forward chunk touches
+  uint32_t *sal_stage = nullptr; // packed perturbed stacks of one forward chunk (at most maxB)
+  float *sal_base = nullptr;     // [n][A] logits, then [n] values of the unperturbed samples
+  float *sal_out = nullptr;      // [n][P] policy scores, [n][P] value scores, then [n][P + 1][A + 1] outputs when asked for
+  uint8_t *sal_u8 = nullptr;     // NCHW uint8 of one chunk of aleppo_saliency_perturbed
+  size_t sal_blur_cap = 0, sal_stage_cap = 0, sal_base_cap = 0, sal_out_cap = 0, sal_u8_cap = 0; // bytes
   // ---- evaluation lanes (aleppo_eval_open): L frame stacks of their own, their own acting scratch, upload staging and
   // action hand-off; nothing below is allocated, and nothing is enqueued for it, on a context that never opens them
   int ev_L = 0;                    // 0: not opened
@@ -493,6 +501,22 @@ void launch_act_export(hipStream_t s, int prec, int layer, const void *a, float 
 void launch_recycle_mask(hipStream_t s, const double *units_dev, int H, double tau, int layers, uint8_t *mask);
 void launch_recycle(hipStream_t s, const ParamLayout &L, const uint8_t *mask, unsigned long long key, bool keep_moments,
                     float *P, float *M1, float *M2);
+// aleppo_saliency / aleppo_saliency_perturbed (saliency.hip).  SalTables: aleppo_saliency_tables' two tables, passed by value.
+// blur: samples [s0, s0 + count) of the call (sample s of the call is sample map.n0 + s of obs under map) -> blur[0 .. count),
+// lane k only where bit k of planes is set.  perturb: pairs [j0, j0 + ns) of the call, pair j = sample j / per at position
+// p0 + j % per, -> stage[0 .. ns); blur_s0: the sample blur[0] holds.  score: pairs [i0, i0 + ns) with per = P, p0 = 0 - rows
+// [0, ns) of logits / values against row (sample) of base_*, into policy / value [i] and, when not null, outputs [n][P+1][A+1].
+struct SalTables {
+  uint16_t g[84], w[84];
+  int32_t radius;
+};
+void launch_sal_blur(hipStream_t s, const uint32_t *obs, SampleMap map, long s0, long count, const SalTables &tb,
+                     int planes, uint32_t *blur);
+void launch_sal_perturb(hipStream_t s, const uint32_t *obs, SampleMap map, const uint32_t *blur, long blur_s0,
+                        const SalTables &tb, int planes, int stride, int G, long j0, long ns, int per, int p0,
+                        uint32_t *stage);
+void launch_sal_score(hipStream_t s, const float *base_logits, const float *base_values, const float *logits,
+                      const float *values, long i0, long ns, int P, int A, float *policy, float *value, float *outputs);
 void launch_heads_fwd(hipStream_t s, const float *h, const float *Wh, const float *bh, float *logits, float *values,
                       long n, int H, int A);
 void launch_logsoftmax_rows(hipStream_t s, const float *in, float *out, long rows, int A);

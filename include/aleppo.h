@@ -594,6 +594,66 @@ int aleppo_recycle_dormant(aleppo_ctx *ctx, const uint8_t *observations, int64_t
                            uint64_t key, int flags, uint8_t *mask_out, size_t unit_count,
                            int64_t counts[ALEPPO_RECYCLE_COUNTS]);
 
+/* Perturbation saliency maps of the policy and the value (Greydanus et al. 2018, "Visualizing and Understanding Atari
+ * Agents"; the reference has none): blur the observation locally around each point of a grid, run the network on every
+ * perturbed copy and score the point by how far the logits and the value move.  It needs only the forward pass the
+ * context already has; the n * P perturbed stacks (28 KB each) are formed on the device and never cross PCIe.
+ * Parameters (aleppo_saliency_config; a NULL pointer means the defaults): stride d in [2, 84], default 5; sigma_mask sM in
+ *   [0.5, 16], default 5; sigma_blur sA in [0.5, 10], default 3; planes, a bit mask in [1, 15], default 15 - bit k is
+ *   channel k of the NCHW observation, which is byte k of the packed stack.  Anything else (a NaN too):
+ *   ALEPPO_ERR_INVALID_ARGUMENT.
+ * Grid: G = ceil(84 / d) points per axis; point (gy, gx) has its centre at pixel (gy * d, gx * d); P = G * G; the
+ *   position index is p = gy * G + gx.
+ * Tables, built on the host in double by aleppo_saliency_tables (no context, no device); the engine uses exactly these:
+ *   mask profile  g[k] = rint(4096 * exp(-k^2 / (2 sM^2))), k = 0 .. 83; g[0] = 4096
+ *   blur taps     R = (int)(4 sA + 0.5); e_j = exp(-j^2 / (2 sA^2)); w[j] = rint(4096 * e_j / sum), sum = the e_j added in the
+ *                 order j = -R .. R; then w[0] += 4096 - (sum of the w[j], j = -R .. R), so that the taps add up to 4096 exactly.
+ *                 blur_w[j] holds w[j] for j = 0 .. R (w[-j] = w[j]) and is zero beyond R.
+ * All pixel arithmetic is integer arithmetic, so the perturbed observations are defined bit for bit.
+ * Blur B of one plane I (uint8, 84 x 84), separable, the horizontal pass first; an index outside [0, 83] is reflected,
+ *   i < 0 -> -1 - i, i > 83 -> 167 - i (scipy's `reflect`):
+ *   Hh[y][x] = sum_j w[j] * I[y][x + j]     V[y][x] = sum_j w[j] * Hh[y + j][x]     B = (V + 2^23) >> 24
+ *   Everything fits unsigned 32 bits (V <= 255 * 2^24).  A constant plane blurs to itself.
+ * Perturbed plane for the point with centre (cy, cx):
+ *   m = (g[|y - cy|] * g[|x - cx|] + 2^15) >> 16, in [0, 256]       I' = (I * (256 - m) + B * m + 128) >> 8
+ *   Where m = 0 the pixel is unchanged; a plane `planes` does not name is copied unchanged.
+ * Scores: z, v are the logits and value of the unperturbed observation, z', v' those of the perturbed one, all from the
+ *   context's own forward pass in its precision (fp32 outputs).  S_policy = 0.5 * sum_a (z_a - z'_a)^2, each difference,
+ *   square and sum rounded to fp32, added in the order a = 0 .. A-1; S_value = 0.5 * (v - v')^2 likewise.  No softmax variant:
+ *   Greydanus scores the logits, and `outputs` returns the raw numbers for any other metric.
+ * Samples, as for aleppo_activation_stats: observations != NULL: the caller's host uint8 [n,4,84,84], first must be 0,
+ *   1 <= n <= max(E, max_minibatch).  observations == NULL: samples [first, first + n) of THE BATCH THE CONTEXT HOLDS, in
+ *   the env-major order n = e * T + t of aleppo_read_batch, read in place from the observation slots.
+ * aleppo_saliency: policy and value are float [n][G][G]; outputs (may be NULL) is float [n][P + 1][A + 1]: row 0 the
+ *   unperturbed logits and value, row 1 + p those of position p.  Per call: the forward pass and the head on the n samples,
+ *   kept in a buffer of their own; then per chunk of at most max(E, max_minibatch) pairs i = sample * P + p (a chunk
+ *   boundary may fall inside a sample's positions) one blur launch where the chunk touches a sample not blurred yet (the
+ *   blur runs up to 128 samples ahead), one blend launch into a staging buffer, the forward pass, the head and one scoring
+ *   launch (one thread per pair, a fixed order, no atomics).  Two calls with nothing in between return identical bits.
+ * aleppo_saliency_perturbed: out is uint8 [n][position_count][4][84][84], the stacks the forward pass would see for the
+ *   positions [position_first, position_first + position_count) of each sample - for tests, and to look at the perturbation.
+ * Both run on the context's stream only, synchronise it where aleppo_activation_stats does, and are never a collective
+ *   (they work under world_size > 1 and describe this rank's samples).  Staging is allocated on first use, grown on demand
+ *   and kept until aleppo_destroy.  Like aleppo_forward they run the network in the shared activation scratch: what
+ *   aleppo_step pre-computed for the next aleppo_act is dropped (the act recomputes it: same bits).  aleppo_train, a
+ *   captured update (ALEPPO_OPT_UPDATE_GRAPH) and every other entry point enqueue nothing for them; a context that never
+ *   calls them allocates and enqueues exactly what it did before, and calling them changes no bit of the run.
+ * Errors: a parameter out of range, a NULL output, n or [first, first + n) or the positions out of range, first != 0 with
+ *   observations: ALEPPO_ERR_INVALID_ARGUMENT.  The batch source without a batch, or any call while a step is armed:
+ *   ALEPPO_ERR_RUNTIME.  A failed call writes nothing (the results pass through host temporaries). */
+typedef struct {
+  int32_t stride;
+  int32_t planes;
+  double sigma_mask;
+  double sigma_blur;
+} aleppo_saliency_config;
+int aleppo_saliency_tables(const aleppo_saliency_config *cfg, uint16_t mask_g[84], uint16_t blur_w[84], int32_t *radius);
+int aleppo_saliency(aleppo_ctx *ctx, const uint8_t *observations, int64_t first, int64_t n,
+                    const aleppo_saliency_config *cfg, float *policy, float *value, float *outputs);
+int aleppo_saliency_perturbed(aleppo_ctx *ctx, const uint8_t *observations, int64_t first, int64_t n,
+                              const aleppo_saliency_config *cfg, int64_t position_first, int64_t position_count,
+                              uint8_t *out);
+
 /* ------------------------------------------------------------------ evaluation lanes (the reference has no evaluation
  * loop: SB3's predict(deterministic=True) / EvalCallback, the epsilon-greedy scores of the DQN / PPO papers)
  * L frame stacks of their own, next to the rollout, on which the network acts under one of three rules - so that a
@@ -946,7 +1006,10 @@ typedef enum {
   ALEPPO_K_REC_CAPTURE = 20, /* the episode recorders' capture kernel (aleppo_rec_open), one launch per recorded step */
   ALEPPO_K_ACT_STATS = 21,  /* aleppo_activation_stats' read-only pass over a1 / a2 / a3 / h, one launch per forward chunk */
   ALEPPO_K_RECYCLE = 22,    /* the masked pass of aleppo_recycle_units / aleppo_recycle_dormant over P / M1 / M2, one launch per call */
-  ALEPPO_K_COUNT = 23
+  ALEPPO_K_SAL_BLUR = 23,    /* aleppo_saliency's blur of the samples a forward chunk touches */
+  ALEPPO_K_SAL_PERTURB = 24, /* ... its blend of one chunk's perturbed stacks into the staging buffer */
+  ALEPPO_K_SAL_SCORE = 25,   /* ... its scoring launch, one per forward chunk */
+  ALEPPO_K_COUNT = 26
 } aleppo_kernel_class;
 int aleppo_profile_enable(aleppo_ctx *ctx, int on);
 int aleppo_profile_read(aleppo_ctx *ctx, int kernel_class, double *avg_ms, int64_t *launches);

@@ -65,6 +65,11 @@ struct Config {
   size_t recycle_interval = 64;
   double recycle_tau = 0.025;                // the dormancy threshold of the recycle
   int recycle_layers = ALEPPO_RECYCLE_ALL;   // ALEPPO_RECYCLE_* bits (the key: a list of conv1 / conv2 / conv3 / fc)
+  // extension: perturbation saliency videos of environment 0 of rank 0 (aleppo_saliency; trainer/saliency.hpp), after the
+  // update of every saliency_interval-th rollout, with the grid stride and the two sigmas of aleppo_saliency_config
+  bool record_saliency = false;
+  size_t saliency_interval = 1;
+  aleppo_saliency_config saliency{5, 15, 5.0, 3.0};
   // extensions
   std::string precision = "fp32", rollout_precision = "fp32";
   bool device_preprocess = false; // emulators hand over raw frame pairs; gray LUT + resize + max run on the device (N2)
@@ -203,6 +208,26 @@ static Config load_config(const std::string &path) { // keys / defaults of src/b
     for (const char *k : {"recycle_interval", "recycle_tau", "recycle_layers"})
       if (kv.count(k) && !c.recycle_dormant) // (nothing else reads them)
         throw std::runtime_error(std::string(k) + " needs recycle_dormant: true");
+  }
+  read_key(kv, "record_saliency", c.record_saliency);
+  { // what aleppo_saliency would refuse is refused here ("nan" / "inf" do not parse as a number: bad value)
+    const long interval = as<long>(kv, "saliency_interval", (long)c.saliency_interval);
+    if (interval < 1)
+      throw std::runtime_error("saliency_interval must be positive");
+    c.saliency_interval = (size_t)interval;
+    const long stride = as<long>(kv, "saliency_stride", (long)c.saliency.stride);
+    if (stride < 2 || stride > 84)
+      throw std::runtime_error("saliency_stride must be in [2, 84]");
+    c.saliency.stride = (int32_t)stride;
+    read_key(kv, "saliency_sigma_mask", c.saliency.sigma_mask);
+    if (!(c.saliency.sigma_mask >= 0.5 && c.saliency.sigma_mask <= 16.0))
+      throw std::runtime_error("saliency_sigma_mask must be in [0.5, 16]");
+    read_key(kv, "saliency_sigma_blur", c.saliency.sigma_blur);
+    if (!(c.saliency.sigma_blur >= 0.5 && c.saliency.sigma_blur <= 10.0))
+      throw std::runtime_error("saliency_sigma_blur must be in [0.5, 10]");
+    for (const char *k : {"saliency_interval", "saliency_stride", "saliency_sigma_mask", "saliency_sigma_blur"})
+      if (kv.count(k) && !c.record_saliency) // (nothing else reads them)
+        throw std::runtime_error(std::string(k) + " needs record_saliency: true");
   }
   c.kl_coef_set = kv.count("kl_coef") != 0;
   c.kl_target_set = kv.count("kl_target") != 0;
@@ -385,6 +410,7 @@ static HParams hparams_of(const Config &c) {
                                                     {"log_tensor_stats", c.log_tensor_stats},
                                                     {"log_activation_stats", c.log_activation_stats},
                                                     {"recycle_dormant", c.recycle_dormant},
+                                                    {"record_saliency", c.record_saliency},
                                                     {"reward_scaling", c.reward_scaling},
                                                     {"device_environments", c.device_environments},
                                                     {"device_evaluation", c.device_evaluation},

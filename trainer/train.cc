@@ -58,7 +58,14 @@
 // splitmix64(seed ^ rollout index), so that a resumed run replays the same recycles; this comes after the statistics above
 // are read, before the iteration's checkpoint is written and before any digest is taken; it logs recycle/<layer>/units and
 // recycle/total; the three other keys without recycle_dormant, a bad tau, interval or layer name, a library without the
-// entry point and WORLD_SIZE > 1 - the scores describe one rank's samples - are refused at start-up).  clip_param_final, value_loss_coef_final, entropy_coef_final,
+// entry point and WORLD_SIZE > 1 - the scores describe one rank's samples - are refused at start-up).  record_saliency: false
+// (true: after the update of every saliency_interval-th rollout - default 1 - rank 0 calls aleppo_saliency on environment 0's
+// horizon samples of the batch the context holds, with the grid stride saliency_stride - default 5 - and saliency_sigma_mask /
+// saliency_sigma_blur - defaults 5 and 3 -, and writes <video dir>/saliency_<rollout>.y4m, the rollout counted from 1:
+// trainer/saliency.hpp has the format - the newest frame as luma, the actor's saliency in blue, the critic's in red; it comes
+// after the statistics above and before a recycle, so it shows the network the update left; never a collective; the four
+// other keys without record_saliency, values aleppo_saliency would refuse and a library without the entry point are refused
+// at start-up).  clip_param_final, value_loss_coef_final, entropy_coef_final,
 // max_gradient_norm_final (absent: the value stays what the config says and no option is set; given: rollout i of
 // num_rollouts updates with v0 + (v_final - v0) * i / num_rollouts, computed in double and rounded to float once - the
 // shape of the learning-rate anneal, which never reaches its end value either - set through ALEPPO_OPT_CLIP_PARAM /
@@ -130,6 +137,7 @@
 #include "pool.hpp"
 #include "profile.hpp"
 #include "recorder.hpp"
+#include "saliency.hpp"
 #include <cstdio>
 #include <iostream>
 #include <numeric>
@@ -164,6 +172,7 @@
 #pragma weak aleppo_activation_stats
 // ... and the recycling of dormant units (recycle_dormant: true)
 #pragma weak aleppo_recycle_dormant
+// (record_saliency: true - aleppo_saliency is declared weak in saliency.hpp)
 // ... and the device-resident evaluation environments (device_evaluation: true)
 #pragma weak aleppo_eval_env_open
 #pragma weak aleppo_eval_env_run
@@ -321,6 +330,9 @@ static void refuse_missing_entry_points(const Config &cfg) {
   if (cfg.recycle_dormant && !aleppo_recycle_dormant)
     throw std::runtime_error("recycle_dormant is set but this build's library cannot recycle units "
                              "(aleppo_recycle_dormant is missing)");
+  if (cfg.record_saliency && !aleppo_saliency)
+    throw std::runtime_error("record_saliency is set but this build's library has no saliency maps "
+                             "(aleppo_saliency is missing)");
 }
 
 // ------------------------------------------------------------------ start-up
@@ -771,6 +783,11 @@ static void update(Run &run, size_t r, Update &u) {
     u.act_units.resize((size_t)(160 + cfg.hidden_size) * ALEPPO_ACT_UNIT_COLS);
     check(ctx, aleppo_activation_stats(ctx, nullptr, 0, cfg.dormant_tau, u.act_units.data(), u.act_units.size(),
                                        &u.act_layers[0][0], (size_t)ALEPPO_ACT_LAYER_ROWS * ALEPPO_ACT_LAYER_COLS));
+  }
+  // the saliency video of environment 0: the batch this update trained on, under the new weights (not a collective)
+  if (cfg.record_saliency && run.rank == 0 && (r + 1) % cfg.saliency_interval == 0) {
+    Profile::Span sp(&run.prof, "aleppo_saliency");
+    write_saliency_y4m(ctx, check, run.video_dir, r + 1, run.E, run.T, cfg.saliency);
   }
   // ReDo: score the units on the batch this update trained on, under the new weights, and recycle the dormant ones - after
   // the statistics above have described the update that ran (aleppo_tensor_stats refuses the step section after a recycle)
