@@ -5,7 +5,7 @@
 #pragma once
 #include "common.hpp"
 #include "gemm.hpp"       // f32x4
-#include "head_train.hpp" // wave_sum
+#include "block_sum.hpp" // wave_sum
 
 namespace aleppo {
 

@@ -115,21 +115,6 @@ static int feistel_half_width(long N) {
   return (w + 1) / 2;
 }
 
-static bool fuse_tail_env() { // A/B switch: conv1's slab reduce fused into the sum-of-squares pass (default)
-  static const bool v = [] {
-    const char *e = getenv("ALEPPO_FUSE_TAIL_REDUCE");
-    return !e || atoi(e) != 0;
-  }();
-  return v;
-}
-static bool bwd_streams_env() { // process-wide A/B switch, read once
-  static const bool v = [] {
-    const char *e = std::getenv("ALEPPO_BWD_STREAMS");
-    return !(e && std::atoi(e) == 1); // ALEPPO_BWD_STREAMS=1: everything on one stream (A/B testing: 8.80 ms)
-  }();
-  return v;
-}
-
 // Which record of a per-minibatch array (mask counts, advantage statistics) belongs to minibatch i = ep * M + mb: an
 // update over gathered planes keeps one per (epoch, minibatch); a contiguous one reads the same `period` = M slices every
 // epoch and keeps M.  (aleppo_read_sample_order: the same rule over samples, period = N.)
@@ -160,7 +145,7 @@ struct Planes {
 struct UpdatePlan {
   int epochs, M, nm; // nm = epochs * M optimizer steps
   long N, B;
-  bool shuffle, vclip, val_transpose, advn, klpen, dp, two, bwd_fused, fuse_tail;
+  bool shuffle, vclip, val_transpose, advn, klpen, dp, two, bwd_fused;
   hipStream_t s, sw; // main stream; stream of the weight-gradient kernels (== s unless two)
   ncclComm_t comm;
   // The hyper-parameters of this call (ALEPPO_OPT_CLIP_PARAM and its kin), and the device block they are uploaded to:
@@ -238,15 +223,14 @@ static int plan_update(aleppo_ctx *c, int epochs, int M, UpdatePlan *plan) {
   // The three weight-gradient kernels (and the slab reduce of bucket 0) run on their own stream
   // next to the dgrad chain (fc wgrad || fc dgrad, conv3 wgrad || conv3 dgrad, conv2 wgrad || conv2 dgrad -> conv1
   // wgrad).  Every kernel is a latency-bound full-GPU persistent grid: co-scheduling fills the drain / ramp bubbles
-  // between dependent launches.
-  p.two = bwd_streams_env() && !c->serial_update; // (profiling brackets every kernel on the stream it runs on)
+  // between dependent launches (everything on one stream measured 8.80 ms per update).
+  p.two = !c->serial_update; // (ALEPPO_OPT_SERIAL_UPDATE: profiling brackets every kernel on the stream it runs on)
   // (Not with data parallelism: the fused kernel's 512-register workgroups need whole CUs, and bucket 0's all-reduce - whose
   // RCCL kernels are resident on some of them by the time the dgrad chain gets there - is what the conv backward is meant to
   // run BESIDE; the three launches share CUs with it, the fused kernel's workgroups on those CUs would start when it ends.)
   p.bwd_fused = (c->tune.fused_bwd == 2 || (c->tune.fused_bwd == 1 && B >= 2048)) && c->prec == ALEPPO_BF16 &&
                 use_patch_kernels() && !p.dp;
   p.sw = p.two ? c->wg_stream : p.s; // stream of the weight-gradient kernels
-  p.fuse_tail = fuse_tail_env();
 
   // the per-sample planes: position n0 + b of the batch, or of epoch ep's gathered planes (the storage above is final)
   Planes &pl = p.pl;
@@ -516,7 +500,7 @@ static int enqueue_minibatch(aleppo_ctx *c, const UpdatePlan &p, int ep, int mb)
   // conv1's slabs: with data parallelism they are reduced now (the all-reduce needs the whole gradient); on one GPU
   // the sum-of-squares pass below sums them on the fly - one launch less on the serial tail of the minibatch.
   ReduceSeg tail[2] = {{p.sW1, S1, 32 * 256, (long)L.off[P_W1]}, {p.sB1, S1, 32, (long)L.off[P_B1]}};
-  if (p.dp || !p.fuse_tail) {
+  if (p.dp) {
     segs.add(tail[0]);
     segs.add(tail[1]);
     tail[0].slab = tail[1].slab = nullptr;
@@ -540,7 +524,7 @@ static int enqueue_minibatch(aleppo_ctx *c, const UpdatePlan &p, int ep, int mb)
   // (pads between tensors are zero: only [0, off[P_W1]) and the two conv1 tensors contribute)
   const int nblk_norm = launch_sumsq(s, c->G, (long)L.off[P_W1], c->sumsq_part, p.nblk_sq, tail);
   // (the Adam kernel also writes the bf16 compute copy and the dgrad-side transposed layouts W2d / W3d / WfcT)
-  launch_adam(s, c->P, c->G, nullptr, c->M1, c->M2, c->prec == ALEPPO_BF16 ? c->Pc : nullptr, c->WfcT, c->W3d, c->W2d, L,
+  launch_adam(s, c->P, c->G, c->M1, c->M2, c->prec == ALEPPO_BF16 ? c->Pc : nullptr, c->WfcT, c->W3d, c->W2d, L,
               prec, c->sumsq_part, nblk_norm, p.hpd, c->adam_sched + 2 * mi, c->cfg.adam_beta1, c->cfg.adam_beta2,
               c->cfg.adam_eps, c->grad_norms + mi);
   prof_end(c, ALEPPO_K_ADAM);

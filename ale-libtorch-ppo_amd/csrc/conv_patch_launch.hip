@@ -24,7 +24,9 @@ static int num_cus() {
   return n;
 }
 
-// developer switches that select timing-only variants of the fused kernels (a phase left out: WRONG results): say so, loudly
+#ifdef ALEPPO_ABLATIONS
+// developer switches (make ABLATIONS=1 only) that select timing-only variants of the fused kernels (a phase left out:
+// WRONG results): say so, loudly
 static int ablation_switch(const char *name) {
   const char *e = std::getenv(name);
   const int v = e ? std::atoi(e) : 0;
@@ -32,6 +34,7 @@ static int ablation_switch(const char *name) {
     std::fprintf(stderr, "aleppo: %s=%d selects a TIMING-ONLY kernel variant: the update's results are WRONG\n", name, v);
   return v;
 }
+#endif
 
 template <class K> static void allow_smem(K kernel, size_t bytes) {
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -101,19 +104,20 @@ void patch_fwd_fused(hipStream_t s, const uint32_t *obs, SampleMap map, const vo
                      const float *b2, const void *W3, const float *b3, void *a1, void *a2, void *a3, long ns) {
   FwdFusedParams P{obs, map, static_cast<const bf16 *>(W1), static_cast<const bf16 *>(W2), static_cast<const bf16 *>(W3),
                    b1,  b2,  b3, static_cast<bf16 *>(a1), static_cast<bf16 *>(a2), static_cast<bf16 *>(a3), ns};
-  // ALEPPO_FF_ABLATE: timing-only builds of the kernel with one part left out (wrong results; DESIGN.md 4e)
-  static const int abl = ablation_switch("ALEPPO_FF_ABLATE");
   if (map.idx) // (the ablations are contiguous-only)
     return launch_fwd_fused<0, true>(s, P);
+#ifdef ALEPPO_ABLATIONS
+  // ALEPPO_FF_ABLATE: timing-only builds of the kernel with one part left out (wrong results; DESIGN.md 4e)
+  static const int abl = ablation_switch("ALEPPO_FF_ABLATE");
   switch (abl) {
   case 1: return launch_fwd_fused<1>(s, P);
   case 2: return launch_fwd_fused<2>(s, P);
   case 4: return launch_fwd_fused<4>(s, P);
   case 8: return launch_fwd_fused<8>(s, P);
   case 16: return launch_fwd_fused<16>(s, P);
-
-  default: return launch_fwd_fused<0>(s, P);
   }
+#endif
+  launch_fwd_fused<0>(s, P);
 }
 template <int ABL, bool IDX = false> static void launch_conv_bwd(hipStream_t s, const ConvBwdParams &P, int grid) {
   static bool once = false;
@@ -128,44 +132,37 @@ int patch_conv_bwd_fused(hipStream_t s, const void *dz2, const void *a1, const u
   ConvBwdParams P{static_cast<const bf16 *>(dz2), static_cast<const bf16 *>(a1), static_cast<const bf16 *>(W2d), obs, map,
                   sw2, sb2, sw1, sb1, ns, 1.0f / 255.0f};
   const int grid = (int)std::min<long>(ns, std::min(num_cus(), std::min(MAXS_C1, MAXS_C2)));
-  // ALEPPO_CB_ABLATE: timing-only builds of the kernel with one part left out (wrong results; DESIGN.md 4e)
-  static const int abl = ablation_switch("ALEPPO_CB_ABLATE");
   if (map.idx) { // (the ablations are contiguous-only)
     launch_conv_bwd<0, true>(s, P, grid);
     return grid;
   }
+#ifdef ALEPPO_ABLATIONS
+  // ALEPPO_CB_ABLATE: timing-only builds of the kernel with one part left out (wrong results; DESIGN.md 4e)
+  static const int abl = ablation_switch("ALEPPO_CB_ABLATE");
   switch (abl) {
-  case 1: launch_conv_bwd<1>(s, P, grid); break;
-  case 2: launch_conv_bwd<2>(s, P, grid); break;
-  case 4: launch_conv_bwd<4>(s, P, grid); break;
-  case 8: launch_conv_bwd<8>(s, P, grid); break;
-  case 16: launch_conv_bwd<16>(s, P, grid); break;
-  case 31: launch_conv_bwd<31>(s, P, grid); break;
-  default: launch_conv_bwd<0>(s, P, grid); break;
+  case 1: launch_conv_bwd<1>(s, P, grid); return grid;
+  case 2: launch_conv_bwd<2>(s, P, grid); return grid;
+  case 4: launch_conv_bwd<4>(s, P, grid); return grid;
+  case 8: launch_conv_bwd<8>(s, P, grid); return grid;
+  case 16: launch_conv_bwd<16>(s, P, grid); return grid;
+  case 31: launch_conv_bwd<31>(s, P, grid); return grid;
   }
+#endif
+  launch_conv_bwd<0>(s, P, grid);
   return grid;
 }
 void patch_conv3_dgrad(hipStream_t s, const void *dz3, const void *W3d, const void *a2, void *dz2, long ns) {
-  PatchParams P{dz3, static_cast<const bf16 *>(W3d), nullptr, static_cast<const bf16 *>(a2), static_cast<bf16 *>(dz2),
-                ns,  SampleMap{1, 0, 0, 0, 0},       1.0f, nullptr};
-  static const int tile = [] {
-    const char *e = std::getenv("ALEPPO_C3D_TILE"); // =0: the sample-stationary kernel (A/B testing: 46 vs 40 us)
-    return e ? std::atoi(e) : 1;
-  }();
-  if (tile) {
-    static bool once = false;
-    if (!once) {
-      allow_smem(conv3_dgrad_tile_kernel, C3T_SMEM);
-      once = true;
-    }
-    C3TileParams T{static_cast<const bf16 *>(dz3), static_cast<const bf16 *>(W3d), static_cast<const bf16 *>(a2),
-                   static_cast<bf16 *>(dz2), fwd_dummy(), ns};
-    const long ngroups = (ns + C3T_SB - 1) / C3T_SB;
-    hipLaunchKernelGGL(conv3_dgrad_tile_kernel, dim3((unsigned)std::min<long>(ngroups, num_cus())), dim3(512), C3T_SMEM, s,
-                       T);
-    return;
+  // the tile kernel: the sample-stationary conv_patch_kernel measured slower here (46 vs 40 us)
+  static bool once = false;
+  if (!once) {
+    allow_smem(conv3_dgrad_tile_kernel, C3T_SMEM);
+    once = true;
   }
-  launch_patch<LConv3Dgrad, 8, 1>(s, P); // the 4-wave / 2-per-CU variant measured slower here (56 vs 48 us)
+  C3TileParams T{static_cast<const bf16 *>(dz3), static_cast<const bf16 *>(W3d), static_cast<const bf16 *>(a2),
+                 static_cast<bf16 *>(dz2), fwd_dummy(), ns};
+  const long ngroups = (ns + C3T_SB - 1) / C3T_SB;
+  hipLaunchKernelGGL(conv3_dgrad_tile_kernel, dim3((unsigned)std::min<long>(ngroups, num_cus())), dim3(512), C3T_SMEM, s,
+                     T);
 }
 void patch_conv2_dgrad(hipStream_t s, const void *dz2, const void *W2d, const void *a1, void *dz1, long ns) {
   PatchParams P{dz2, static_cast<const bf16 *>(W2d), nullptr, static_cast<const bf16 *>(a1), static_cast<bf16 *>(dz1),
@@ -214,11 +211,8 @@ template <class L> static int launch_wgrad(hipStream_t s, const WgradParams &P) 
   // Half the CUs: every workgroup writes one fp32 slab of the whole dW (147 KB for conv3), and these kernels run on the
   // weight-gradient stream in the shadow of the dgrad chain, so fewer, longer workgroups cost nothing there and halve what
   // the slab reduce reads beside conv1 wgrad (measured per 4096-sample minibatch, same box: 256 workgroups 455 us,
-  // 192: 451, 160: 450, 128: 444, 96: 455; ALEPPO_WG_GRID overrides)
-  static const int cap = [] {
-    const char *e = std::getenv("ALEPPO_WG_GRID");
-    return e ? std::atoi(e) : num_cus() / 2;
-  }();
+  // 192: 451, 160: 450, 128: 444, 96: 455)
+  const int cap = num_cus() / 2;
   const int grid = (int)std::min<long>(ngroups, std::min(std::min(num_cus(), MAXS_C1), cap));
   hipLaunchKernelGGL((conv_wgrad_patch_kernel<L>), dim3(grid), dim3(512), sm, s, P);
   return grid;

@@ -5,16 +5,11 @@
 #include "gemm.hpp"
 #include "gemm_pipe.hpp"
 #include <algorithm>
-#include <cstdlib>
 
 namespace aleppo {
 
-// tile-shape A/B switches: every call site keeps its value in a function-local static (read once per process); the
-// switches the tests flip at run time (fc_pipe, patch_conv) are per-context options (tuning())
-static int tune(const char *name, int dflt) {
-  const char *e = std::getenv(name);
-  return e ? std::atoi(e) : dflt;
-}
+// Tile shapes are the measured best; the routes the tests flip at run time (fc_pipe, patch_conv) are
+// per-context options (tuning())
 static inline dim3 grid2(long M, int BM, long N, int BN, int Z = 1) {
   return dim3((unsigned)((M + BM - 1) / BM), (unsigned)((N + BN - 1) / BN), (unsigned)Z);
 }
@@ -92,14 +87,6 @@ template <int MODE, int NST> static void launch_pipe(hipStream_t s, const PipePa
   const int grid = P.njobs >= cus / 4 ? std::min(cus, ((P.njobs + rounds - 1) / rounds + 7) / 8 * 8) : std::min(P.njobs, cus);
   hipLaunchKernelGGL((gemm_pipe_kernel<MODE, NST>), dim3(grid), dim3(PIPE_THREADS), sm, s, P);
 }
-static bool fc_dma() {
-  static const bool v = tune("ALEPPO_FC_DMA", 1) != 0;
-  return v;
-}
-static bool tn_xcd() {
-  static const bool v = tune("ALEPPO_TN_XCD", 1) != 0;
-  return v;
-}
 static bool use_pipe() { return tuning().fc_pipe; }
 // forward: h partial slabs [parts][ns][H]; parts chosen so that the jobs fill the CUs with the fewest rounds
 static int fc_fwd_pipe(hipStream_t s, const void *a3, const void *Wfc, const float *bfc, float *h, long ns, int H,
@@ -159,38 +146,10 @@ static void fc_fwd_t(hipStream_t s, const void *a3, const void *Wfc, const float
   if (ns <= 256) // acting batch: smaller M tile so more workgroups share the 3136-deep reduction
     hipLaunchKernelGGL((gemm_nt_kernel<T, AL, BL, EP, 32, 32, 2, 2>), grid2(ns, 32, H, 32), dim3(256), 0, s, ap, bp,
                        ep, (int)ns, H, FC_IN);
-  else if (fc_dma() && FC_IN % Atom<T>::KT == 0) {
-    static const int v = tune("ALEPPO_FC_FWD_TILE", 1);
-    const T *a = static_cast<const T *>(a3), *b = static_cast<const T *>(Wfc);
-    if (v == 3 && FC_IN % (2 * Atom<T>::KT) == 0)
-      hipLaunchKernelGGL((gemm_nt_dma_kernel<T, EP, 64, 64, 2, 2, 16>), grid2(ns, 64, H, 64), dim3(256), 0, s, a, FC_IN,
-                         b, FC_IN, ep, (int)ns, H, FC_IN);
-    else if (v == 4 && FC_IN % (2 * Atom<T>::KT) == 0)
-      hipLaunchKernelGGL((gemm_nt_dma_kernel<T, EP, 128, 64, 2, 2, 16>), grid2(ns, 128, H, 64), dim3(256), 0, s, a,
-                         FC_IN, b, FC_IN, ep, (int)ns, H, FC_IN);
-    else if (v == 1)
-      hipLaunchKernelGGL((gemm_nt_dma_kernel<T, EP, 64, 64, 2, 2>), grid2(ns, 64, H, 64), dim3(256), 0, s, a, FC_IN, b,
-                         FC_IN, ep, (int)ns, H, FC_IN);
-    else if (v == 2)
-      hipLaunchKernelGGL((gemm_nt_dma_kernel<T, EP, 128, 128, 2, 2>), grid2(ns, 128, H, 128), dim3(256), 0, s, a,
-                         FC_IN, b, FC_IN, ep, (int)ns, H, FC_IN);
-    else
-      hipLaunchKernelGGL((gemm_nt_dma_kernel<T, EP, 128, 64, 2, 2>), grid2(ns, 128, H, 64), dim3(256), 0, s, a, FC_IN,
-                         b, FC_IN, ep, (int)ns, H, FC_IN);
-  } else {
-    static const int v = tune("ALEPPO_FC_FWD_TILE", 1);
-    if (v == 1)
-      hipLaunchKernelGGL((gemm_nt_kernel<T, AL, BL, EP, 64, 64, 2, 2>), grid2(ns, 64, H, 64), dim3(256), 0, s, ap, bp,
-                         ep, (int)ns, H, FC_IN);
-    else if (v == 2)
-      hipLaunchKernelGGL((gemm_nt_kernel<T, AL, BL, EP, 128, 128, 2, 2>), grid2(ns, 128, H, 128), dim3(256), 0, s, ap,
-                         bp, ep, (int)ns, H, FC_IN);
-    else if (v == 3)
-      hipLaunchKernelGGL((gemm_nt_kernel<T, AL, BL, EP, 64, 128, 2, 2>), grid2(ns, 64, H, 128), dim3(256), 0, s, ap,
-                         bp, ep, (int)ns, H, FC_IN);
-    else
-      hipLaunchKernelGGL((gemm_nt_kernel<T, AL, BL, EP, 128, 64, 2, 2>), grid2(ns, 128, H, 64), dim3(256), 0, s, ap,
-                         bp, ep, (int)ns, H, FC_IN);
+  else { // L2 -> LDS DMA staging: FC_IN is a multiple of both precisions' k-tile
+    static_assert(FC_IN % Atom<T>::KT == 0, "the DMA kernel takes whole k-tiles");
+    hipLaunchKernelGGL((gemm_nt_dma_kernel<T, EP, 64, 64, 2, 2>), grid2(ns, 64, H, 64), dim3(256), 0, s,
+                       static_cast<const T *>(a3), FC_IN, static_cast<const T *>(Wfc), FC_IN, ep, (int)ns, H, FC_IN);
   }
 }
 
@@ -251,12 +210,9 @@ __global__ __launch_bounds__(256) void fc_act_kernel(const bf16 *__restrict__ a3
   }
 }
 void fc_fwd_splitk(hipStream_t s, int prec, const void *a3, const void *Wfc, float *hpart, long ns, int H) {
-  static const bool latency_form = tune("ALEPPO_FC_ACT_LATENCY", 1) != 0; // A/B switch
-  if (prec == ALEPPO_BF16 && latency_form)
+  if (prec == ALEPPO_BF16)
     hipLaunchKernelGGL(fc_act_kernel, grid2(ns, 32, H, 32, FC_SPLITS), dim3(256), 0, s, static_cast<const bf16 *>(a3),
                        static_cast<const bf16 *>(Wfc), hpart, (int)ns, H);
-  else if (prec == ALEPPO_BF16)
-    fc_fwd_splitk_t<bf16>(s, a3, Wfc, hpart, ns, H);
   else
     fc_fwd_splitk_t<float>(s, a3, Wfc, hpart, ns, H);
 }
@@ -270,35 +226,12 @@ static void fc_dgrad_t(hipStream_t s, const void *dh, const void *WfcT, const vo
   typename AL::P ap{static_cast<const T *>(dh), H, 0};
   typename BL::P bp{static_cast<const T *>(WfcT), H, 0};
   typename EP::P ep{static_cast<T *>(dz3), static_cast<const T *>(a3), FC_IN, 0};
-  static const int v = tune("ALEPPO_FC_DGRAD_TILE", 1);
-  if (fc_dma() && H % Atom<T>::KT == 0) {
-    const T *a = static_cast<const T *>(dh), *b = static_cast<const T *>(WfcT);
-    if (v == 3)
-      hipLaunchKernelGGL((gemm_nt_dma_kernel<T, EP, 64, 64, 2, 2, 16>), grid2(ns, 64, FC_IN, 64), dim3(256), 0, s, a, H,
-                         b, H, ep, (int)ns, FC_IN, H);
-    else if (v == 4)
-      hipLaunchKernelGGL((gemm_nt_dma_kernel<T, EP, 128, 64, 2, 2, 16>), grid2(ns, 128, FC_IN, 64), dim3(256), 0, s, a,
-                         H, b, H, ep, (int)ns, FC_IN, H);
-    else if (v == 2)
-      hipLaunchKernelGGL((gemm_nt_dma_kernel<T, EP, 128, 128, 2, 2>), grid2(ns, 128, FC_IN, 128), dim3(256), 0, s, a,
-                         H, b, H, ep, (int)ns, FC_IN, H);
-    else if (v == 0)
-      hipLaunchKernelGGL((gemm_nt_dma_kernel<T, EP, 128, 64, 2, 2>), grid2(ns, 128, FC_IN, 64), dim3(256), 0, s, a, H,
-                         b, H, ep, (int)ns, FC_IN, H);
-    else
-      hipLaunchKernelGGL((gemm_nt_dma_kernel<T, EP, 64, 64, 2, 2>), grid2(ns, 64, FC_IN, 64), dim3(256), 0, s, a, H, b,
-                         H, ep, (int)ns, FC_IN, H);
-    return;
-  }
-  if (v == 1)
+  if (H % Atom<T>::KT == 0)
+    hipLaunchKernelGGL((gemm_nt_dma_kernel<T, EP, 64, 64, 2, 2>), grid2(ns, 64, FC_IN, 64), dim3(256), 0, s,
+                       static_cast<const T *>(dh), H, static_cast<const T *>(WfcT), H, ep, (int)ns, FC_IN, H);
+  else // a partial last k-tile (bf16 H % 64 == 32): the staged kernel masks it
     hipLaunchKernelGGL((gemm_nt_kernel<T, AL, BL, EP, 64, 64, 2, 2>), grid2(ns, 64, FC_IN, 64), dim3(256), 0, s, ap, bp,
                        ep, (int)ns, FC_IN, H);
-  else if (v == 2)
-    hipLaunchKernelGGL((gemm_nt_kernel<T, AL, BL, EP, 128, 128, 2, 2>), grid2(ns, 128, FC_IN, 128), dim3(256), 0, s,
-                       ap, bp, ep, (int)ns, FC_IN, H);
-  else
-    hipLaunchKernelGGL((gemm_nt_kernel<T, AL, BL, EP, 128, 64, 2, 2>), grid2(ns, 128, FC_IN, 64), dim3(256), 0, s, ap,
-                       bp, ep, (int)ns, FC_IN, H);
 }
 template <class T>
 static void conv3_dgrad_t(hipStream_t s, const void *dz3, const void *W3d, const void *a2, void *dz2, long ns) {
@@ -347,38 +280,22 @@ static inline int chunk_for(long Ktot, int S, int KP) {
 // Split-K factor of the fc weight gradient.  2: 400 workgroups of 64 x 128 at H = 512, and two fp32 slabs (12.8 MB) for the
 // reduce to read.  Measured per minibatch on one box (update loop, us): B = 4096: split 2 435.7 / 437.7, 4 438.0 / 438.0,
 // 3 440.3 / 441.3, 8 444.3 / 446.8; B = 1280 (v1.yaml): split 2 232-235, split 4 241-244.
-static int fc_wgrad_split_max() { return tune("ALEPPO_FC_WGRAD_SPLIT", 2); }
+constexpr int FC_WGRAD_SPLIT_MAX = 2;
 
 template <class T> static int fc_wgrad_t(hipStream_t s, const void *dh, const void *a3, float *sw, float *sb, long ns, int H) {
   using AL = DenseLoader<T>;
   using BL = DenseLoader<T>;
   constexpr int KP = Atom<T>::KT;
-  static const int v = tune("ALEPPO_FC_WGRAD_TILE", 0);
-  static const int smax = fc_wgrad_split_max();
   // S == 1: the "slab" IS the gradient tensor (caller passes G); S > 1: split-K slabs reduced by the caller
-  const int S = (int)std::max<long>(1, std::min<long>(std::min(smax, MAXS_FC), ns / (4 * KP)));
+  const int S = (int)std::max<long>(1, std::min<long>(std::min(FC_WGRAD_SPLIT_MAX, MAXS_FC), ns / (4 * KP)));
   const int kc = chunk_for(ns, S, KP);
   typename AL::P ap{static_cast<const T *>(dh), H, 0};
   typename BL::P bp{static_cast<const T *>(a3), FC_IN, 0};
   // contiguous per-XCD work chunks (the m-tiles sharing an a3 stream on one L2) when the block count allows
-  auto swz = [&](const dim3 &g) { return ((g.x * g.y * S) % 8 == 0 && tn_xcd()) ? (int)(g.x | (g.y << 12)) : 0; };
-  auto grid = [&](const dim3 &g, int xsw) { return xsw ? dim3(g.x * g.y * S) : dim3(g.x, g.y, S); };
-  if (v == 1) {
-    const dim3 g = grid2(H, 64, FC_IN, 64);
-    const int xsw = swz(g);
-    hipLaunchKernelGGL((gemm_tn_kernel<T, AL, BL, 64, 64, 2, 2, true>), grid(g, xsw), dim3(256), 0, s, ap, bp, sw,
-                       sb, H, FC_IN, (int)ns, kc, 1.0f, xsw);
-  } else if (v == 2) {
-    const dim3 g = grid2(H, 128, FC_IN, 64);
-    const int xsw = swz(g);
-    hipLaunchKernelGGL((gemm_tn_kernel<T, AL, BL, 128, 64, 2, 2, true>), grid(g, xsw), dim3(256), 0, s, ap, bp,
-                       sw, sb, H, FC_IN, (int)ns, kc, 1.0f, xsw);
-  } else {
-    const dim3 g = grid2(H, 64, FC_IN, 128);
-    const int xsw = swz(g);
-    hipLaunchKernelGGL((gemm_tn_kernel<T, AL, BL, 64, 128, 2, 2, true>), grid(g, xsw), dim3(256), 0, s, ap, bp,
-                       sw, sb, H, FC_IN, (int)ns, kc, 1.0f, xsw);
-  }
+  const dim3 g = grid2(H, 64, FC_IN, 128);
+  const int xsw = (g.x * g.y * S) % 8 == 0 ? (int)(g.x | (g.y << 12)) : 0;
+  hipLaunchKernelGGL((gemm_tn_kernel<T, AL, BL, 64, 128, 2, 2, true>), xsw ? dim3(g.x * g.y * S) : dim3(g.x, g.y, S),
+                     dim3(256), 0, s, ap, bp, sw, sb, H, FC_IN, (int)ns, kc, 1.0f, xsw);
   return S;
 }
 template <class T> static int conv3_wgrad_t(hipStream_t s, const void *dz3, const void *a2, float *sw, float *sb, long ns) {
@@ -478,9 +395,8 @@ void conv2_dgrad(hipStream_t s, int prec, const void *dz2, const void *W2d, cons
   DISPATCH(prec, conv2_dgrad_t<float>(s, dz2, W2d, a1, dz1, ns), conv2_dgrad_t<bf16>(s, dz2, W2d, a1, dz1, ns));
 }
 int fc_wgrad_slices(int prec, long ns) {
-  static const int smax = fc_wgrad_split_max();
   const int KP = prec == ALEPPO_BF16 ? Atom<bf16>::KT : Atom<float>::KT;
-  return (int)std::max<long>(1, std::min<long>(std::min(smax, MAXS_FC), ns / (4 * KP)));
+  return (int)std::max<long>(1, std::min<long>(std::min(FC_WGRAD_SPLIT_MAX, MAXS_FC), ns / (4 * KP)));
 }
 int fc_wgrad(hipStream_t s, int prec, const void *dh, const void *a3, float *sw, float *sb, long ns, int H) {
   if (prec == ALEPPO_BF16)

@@ -1,9 +1,33 @@
 // head_train.hip - the PPO head training kernel's three __global__ entry points and their launcher (the kernel itself is
-// described in kernels.hip, "PPO head, training"; its body is head_train_body.inc).  A translation unit of its own: the
+// described below, "PPO head, training"; its body is head_train_body.inc).  A translation unit of its own: the
 // 96 instantiations compile next to kernels.hip.
 #include "head_train.hpp"
 
 namespace aleppo {
+
+// ================================================================================================
+// PPO head, training.  Fuses: action/value linear layers (train.cc:245-253,262-263), normalize_logits
+// (losses.cc:45-47), losses::compute forward (losses.cc:4-26) with its closed-form backward (SURVEY
+// app. B: autograd's gradient of the masked-mean loss), the head dgrad (dh) and the head wgrad
+// partials.  One wave per sample row, 4 waves per workgroup, rows strided over the grid; every
+// workgroup writes ONE partial slab of head-weight gradients (summed later in fixed order).
+// 1/N_m uses the GLOBAL unmasked count so that an all-reduce SUM over ranks yields the mean (8e).
+// ================================================================================================
+// Wide action sets (AMAX = 18: 19 x 8 wgrad accumulators per lane) run 4 waves per workgroup: one wave per SIMD may
+// use the whole 512-entry register file; with 8 waves the 256-register cap spilled the accumulators (150 us vs 22).
+// VCLIP (ALEPPO_OPT_VALUE_CLIP): the value term is the clipped one of aleppo.h against vold, the values the samples were
+// collected with; without it vold is never read.  ps_kl / ps_cf (approx-KL and clip fraction) are written either way.
+// ADVN (ALEPPO_OPT_ADV_NORM_MINIBATCH): every row's advantage a becomes (a - advs[0]) * advs[1] in fp32, this minibatch's
+// (mean_f, inv_f) from advn_stats_kernel; without it advs is never read.
+// KLPEN (ALEPPO_OPT_KL_PENALTY): the exact KL(pi_old || pi) of every row goes to ps_kle, and with beta = klb[0] != 0 the
+// loss gains beta KL and its gradient beta (p S - q) (include/aleppo.h).  The body is shared by three entry points:
+// head_train_kernel (ADVN and KLPEN off, the default path's instantiations), head_train_advn_kernel (ADVN on) and
+// head_train_kl_kernel (KLPEN on, with advantage normalisation a run-time switch: advs may be null).
+// Waves per workgroup: 8, or 4 where one wave per SIMD needs more than 256 registers - the wide action sets, and with
+// the KL penalty (its S / KL pass and the q_a of the gradient) from AMAX = 10 on (8 waves spilled ~40 registers there).
+// The clip range, the value-clip range and the two loss coefficients are slots 0-3 of the device block of
+// ALEPPO_OPT_CLIP_PARAM and its kin (common.hpp HYPER_*), read once per workgroup: a captured update follows values changed
+// between calls.  The entry points and their launcher, launch_head_train, follow.
 
 template <class T, int AMAX, class RT, bool VCLIP>
 __global__ __launch_bounds__(AMAX > 10 ? 256 : 512) void head_train_kernel(HEAD_PARAMS) {

@@ -1,6 +1,7 @@
 // head_train.hpp - what head_train.hip (the PPO head training kernel's entry points; their body is head_train_body.inc)
-// shares with kernels.hip: the rollout-plane type, the wave sum and the kernel's waves per workgroup.
+// shares with kernels.hip: the rollout-plane type and the kernel's waves per workgroup.
 #pragma once
+#include "block_sum.hpp" // wave_sum
 #include "common.hpp"
 #include "gemm.hpp" // bf16 / vector typedefs
 
@@ -10,14 +11,7 @@ namespace aleppo {
 // "fp16 rollout buffer").  Arithmetic is always fp32: planes are widened on load and rounded (RNE) on store.
 typedef _Float16 f16;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-    v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// Waves per workgroup of the head training kernel (kernels.hip, "PPO head, training")
+// Waves per workgroup of the head training kernel (head_train.hip, "PPO head, training")
 constexpr int head_waves(int amax, bool klpen) { return amax > 10 || (klpen && amax > 6) ? 4 : 8; }
 // The parameters the three entry points share.  hp: the device block of common.hpp's HYPER_* slots
 #define HEAD_PARAMS                                                                                                    \

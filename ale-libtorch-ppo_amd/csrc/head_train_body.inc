@@ -163,7 +163,7 @@
       ent = -ent;
       // ALEPPO_OPT_KL_PENALTY: S = sum q_a and the exact KL(pi_old || pi) = sum q_a (olp_a - lp_a), q_a = exp(olp_a)
       // (written as exp(olp) where it is used, with no second [AMAX] array; the registers it takes are why the
-      // penalty's AMAX = 10 variants run 4 waves per workgroup: head_waves in kernels.hip)
+      // penalty's AMAX = 10 variants run 4 waves per workgroup: head_waves in head_train.hpp)
       float kl_s = 0.f, kl = 0.f;
       if constexpr (KLPEN) {
 #pragma unroll

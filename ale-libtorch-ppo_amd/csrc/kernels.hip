@@ -5,23 +5,12 @@
 // conversions used only at the C-ABI boundary.  Each kernel cites the reference code it replaces.
 #include "common.hpp"
 #include "gemm.hpp" // bf16 / vector typedefs
-#include "head_train.hpp" // f16, wave_sum, and what the head kernel's entry points share
+#include "block_sum.hpp" // wave_sum, block_sum_256
+#include "head_train.hpp" // f16, and what the head kernel's entry points share
 #include "act_head.hpp" // what the acting head's two entry points are built from
 #include <algorithm>
-#include <cstdlib>
 
 namespace aleppo {
-
-// deterministic block reduction (256 threads): wave shuffles, then wave 0 sums the 4 partials in order
-__device__ __forceinline__ float block_sum_256(float v, float *s4) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0)
-    s4[wave] = v;
-  __syncthreads();
-  return (s4[0] + s4[1]) + (s4[2] + s4[3]);
-}
 
 // ================================================================================================
 // Frame ingest.  Replaces, per env-step: gray LUT (environment.cc:48-55) + resize (vision.cc:86-95 on
@@ -559,19 +548,9 @@ void launch_mask_count(hipStream_t s, const uint8_t *mask_n, float *counts, long
 
 // ALEPPO_OPT_ADV_NORM_MINIBATCH: (n, S, Q) = count, sum and sum of squares of the unmasked advantages of one minibatch, in
 // double (aleppo.h), block per minibatch.  Fixed order: thread t sums samples t, t + 256, ... in turn, then the block
-// reduces with the same shuffle tree every time.  a*a of a widened float is exact in double, so a contracted fma is too.
-__device__ __forceinline__ double block_sum_256d(double v, double *s4) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-    v += __shfl_xor(v, o, 64);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0)
-    s4[wave] = v;
-  __syncthreads();
-  return (s4[0] + s4[1]) + (s4[2] + s4[3]);
-}
-// (mean_f, inv_f, std, 0) of aleppo.h from the (all-reduced) sums; n = 0: (0, 1, 0, 0)
+// reduces with the same shuffle tree every time (block_sum_256).  a*a of a widened float is exact in double, so a
+// contracted fma is too.
+// advn_finalise: (mean_f, inv_f, std, 0) of aleppo.h from the (all-reduced) sums; n = 0: (0, 1, 0, 0)
 __device__ __forceinline__ void advn_finalise(double n, double S, double Q, float *out) {
   if (!(n > 0.0)) {
     out[0] = 0.f;
@@ -602,9 +581,9 @@ __global__ __launch_bounds__(256) void advn_stats_kernel(const RT *__restrict__ 
       S += x;
       Q += x * x;
     }
-  n = block_sum_256d(n, s4);
-  S = block_sum_256d(S, s4);
-  Q = block_sum_256d(Q, s4);
+  n = block_sum_256(n, s4);
+  S = block_sum_256(S, s4);
+  Q = block_sum_256(Q, s4);
   if (threadIdx.x == 0) {
     if (part) { // data parallel: the partial sums, all-reduced and then finalised by advn_finalise_kernel
       part[(size_t)blockIdx.x * 4 + 0] = n;
@@ -638,7 +617,7 @@ void launch_advn_finalise(hipStream_t s, const double *part, float *stats, int n
 // ALEPPO_F_BATCH_STATS (aleppo.h): count, sum and sum of squares of the stored values v, returns R, advantages a and of
 // d = R - v over the unmasked samples of the batch, in double, in two stages whose order depends on the sample count only.
 // Stage 1: workgroup b sums the samples [b * BSTAT_CHUNK, (b + 1) * BSTAT_CHUNK): thread t takes t, t + 256, ... in turn,
-// then the block folds with the shuffle tree of block_sum_256d.  x * x of a widened float is exact in double (a
+// then the block folds with the shuffle tree of block_sum_256.  x * x of a widened float is exact in double (a
 // contracted fma is too); d is one rounded double subtraction of two widened floats.  The values of a rollout batch are
 // time-major ([T+1][E], sample n = e*T + t sits at t*E + e: E > 0); those of a caller batch are sample-major (E == 0).
 template <class RT>
@@ -670,7 +649,7 @@ __global__ __launch_bounds__(256) void bstat_partial_kernel(const RT *__restrict
     }
 #pragma unroll
   for (int k = 0; k < BSTAT_SUMS; ++k)
-    acc[k] = block_sum_256d(acc[k], s4);
+    acc[k] = block_sum_256(acc[k], s4);
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int k = 0; k < BSTAT_SUMS; ++k)
@@ -741,7 +720,7 @@ void launch_bstat_finalise(hipStream_t s, const double *sums, double *result) {
 // are loaded together, the next 16 are already in flight, and a chunk is processed branch-free (selects, no per-step
 // branches: see the comment above GaeChunk for what the naive form costs).  G * gamma + r keeps its two roundings
 // (contraction off), so the samples are the bits a host restatement in double gets.  The wave then folds (n, S, Q) with
-// xor butterflies (the wave stage of block_sum_256d) and writes one partial per workgroup.  The order of every addition
+// xor butterflies (the wave stage of block_sum_256) and writes one partial per workgroup.  The order of every addition
 // is a function of (E, T) only.
 // ================================================================================================
 struct RsChunk {
@@ -968,30 +947,6 @@ void launch_shuffle_gather(hipStream_t s, const uint32_t *rk, int h, long N, int
 }
 
 // ================================================================================================
-// PPO head, training.  Fuses: action/value linear layers (train.cc:245-253,262-263), normalize_logits
-// (losses.cc:45-47), losses::compute forward (losses.cc:4-26) with its closed-form backward (SURVEY
-// app. B: autograd's gradient of the masked-mean loss), the head dgrad (dh) and the head wgrad
-// partials.  One wave per sample row, 4 waves per workgroup, rows strided over the grid; every
-// workgroup writes ONE partial slab of head-weight gradients (summed later in fixed order).
-// 1/N_m uses the GLOBAL unmasked count so that an all-reduce SUM over ranks yields the mean (8e).
-// ================================================================================================
-// Wide action sets (AMAX = 18: 19 x 8 wgrad accumulators per lane) run 4 waves per workgroup: one wave per SIMD may
-// use the whole 512-entry register file; with 8 waves the 256-register cap spilled the accumulators (150 us vs 22).
-// VCLIP (ALEPPO_OPT_VALUE_CLIP): the value term is the clipped one of aleppo.h against vold, the values the samples were
-// collected with; without it vold is never read.  ps_kl / ps_cf (approx-KL and clip fraction) are written either way.
-// ADVN (ALEPPO_OPT_ADV_NORM_MINIBATCH): every row's advantage a becomes (a - advs[0]) * advs[1] in fp32, this minibatch's
-// (mean_f, inv_f) from advn_stats_kernel; without it advs is never read.
-// KLPEN (ALEPPO_OPT_KL_PENALTY): the exact KL(pi_old || pi) of every row goes to ps_kle, and with beta = klb[0] != 0 the
-// loss gains beta KL and its gradient beta (p S - q) (include/aleppo.h).  The body is shared by three entry points:
-// head_train_kernel (ADVN and KLPEN off, the default path's instantiations), head_train_advn_kernel (ADVN on) and
-// head_train_kl_kernel (KLPEN on, with advantage normalisation a run-time switch: advs may be null).
-// Waves per workgroup: 8, or 4 where one wave per SIMD needs more than 256 registers - the wide action sets, and with
-// the KL penalty (its S / KL pass and the q_a of the gradient) from AMAX = 10 on (8 waves spilled ~40 registers there).
-// The clip range, the value-clip range and the two loss coefficients are slots 0-3 of the device block of
-// ALEPPO_OPT_CLIP_PARAM and its kin (common.hpp HYPER_*), read once per workgroup: a captured update follows values changed
-// between calls.  The entry points and their launcher, launch_head_train, are head_train.hip.
-
-// ================================================================================================
 // Split-K slab reduction -> flat gradient (fixed summation order => run-to-run deterministic).
 // ================================================================================================
 struct ReduceArgs {
@@ -1007,6 +962,23 @@ struct ReduceArgs {
 //  * wide (the fc weight: 1.6 M outputs, <= 4 slabs): one workgroup per 1024 outputs, every thread sums a
 //    float4 column with 16-byte loads, keeping the same four interleaved partial sums per output.
 // Both give the value ((s0+s4+..) + (s1+s5+..)) + ((s2+..) + (s3+..)) -> identical bits, run-to-run deterministic.
+
+// The narrow shape's sum of output j over S slabs of n floats, for a workgroup of 256 threads that owns 64 consecutive
+// outputs: thread (o = tid & 63, q = tid >> 6) sums slabs q, q + 4, ... of its output j, then the four partials combine
+// through LDS as (p0 + p1) + (p2 + p3).  Every thread of the workgroup calls it (one barrier); j >= n: 0.
+__device__ __forceinline__ float slab_column_sum(const float *slab, int S, long n, long j, float (*part)[64]) {
+  const int o = threadIdx.x & 63, q = threadIdx.x >> 6;
+  float acc = 0.f;
+  if (j < n) {
+    const float *p = slab + j;
+#pragma unroll 4
+    for (int k = q; k < S; k += 4)
+      acc += p[(long)k * n];
+  }
+  part[q][o] = acc;
+  __syncthreads();
+  return (part[0][o] + part[1][o]) + (part[2][o] + part[3][o]);
+}
 __global__ __launch_bounds__(256) void reduce_slabs_kernel(ReduceArgs a, float *G) {
   __shared__ float part[4][64];
   int s = 0;
@@ -1055,24 +1027,12 @@ __global__ __launch_bounds__(256) void reduce_slabs_kernel(ReduceArgs a, float *
     return;
   }
   const long j = (long)((int)blockIdx.x - a.cprefix[s]) * 64 + (threadIdx.x & 63);
-  const int q = threadIdx.x >> 6;
-  float acc = 0.f;
-  if (j < n) {
-    const float *p = a.seg[s].slab + j;
-#pragma unroll 4
-    for (int k = q; k < S; k += 4)
-      acc += p[(long)k * n];
-  }
-  part[q][threadIdx.x & 63] = acc;
-  __syncthreads();
-  if (q == 0 && j < n)
-    G[a.seg[s].dst + j] = (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
+  const float g = slab_column_sum(a.seg[s].slab, S, n, j, part);
+  if (threadIdx.x < 64 && j < n)
+    G[a.seg[s].dst + j] = g;
 }
 void launch_reduce_slabs(hipStream_t s, const ReduceSeg *segs, int nseg, float *G) {
-  static const long wide_min = [] { // A/B switch: smallest segment that takes the 16-byte path
-    const char *e = getenv("ALEPPO_REDUCE_WIDE_MIN");
-    return e ? atol(e) : 1L << 18;
-  }();
+  constexpr long wide_min = 1L << 18; // smallest segment that takes the 16-byte path
   ReduceArgs a;
   a.nseg = nseg;
   a.cprefix[0] = 0;
@@ -1101,11 +1061,11 @@ struct SumsqTail {
   int chunks[2];    // 64-output chunks per tensor
 };
 __global__ __launch_bounds__(256) void sumsq_kernel(float *__restrict__ G, long n, float *partials, int nmain,
-                                                    SumsqTail tail, int boff) {
+                                                    SumsqTail tail) {
   __shared__ float s4[4];
   __shared__ float part[4][64];
   float s = 0.f;
-  const int blk = (int)blockIdx.x + boff; // (a launch may cover only the main blocks or only the tail blocks)
+  const int blk = (int)blockIdx.x;
   if (blk < nmain) {
     const long per = (n + nmain - 1) / nmain;
     const long b = (long)blk * per, e = min(n, b + per);
@@ -1121,18 +1081,10 @@ __global__ __launch_bounds__(256) void sumsq_kernel(float *__restrict__ G, long 
     const int o = threadIdx.x & 63, q = threadIdx.x >> 6;
     const long j = (long)c * 64 + o;
     float g = 0.f;
-    if (sg.slab) { // workgroup-uniform; same order as reduce_slabs_kernel's narrow path
-      float acc = 0.f;
-      if (j < sg.n) {
-        const float *p = sg.slab + j;
-#pragma unroll 4
-        for (int k = q; k < sg.S; k += 4)
-          acc += p[(long)k * sg.n];
-      }
-      part[q][o] = acc;
-      __syncthreads();
+    if (sg.slab) { // workgroup-uniform; reduce_slabs_kernel's narrow path
+      const float sum = slab_column_sum(sg.slab, sg.S, sg.n, j, part);
       if (q == 0 && j < sg.n) {
-        g = (part[0][o] + part[1][o]) + (part[2][o] + part[3][o]);
+        g = sum;
         G[sg.dst + j] = g;
       }
     } else if (q == 0 && j < sg.n) {
@@ -1144,42 +1096,38 @@ __global__ __launch_bounds__(256) void sumsq_kernel(float *__restrict__ G, long 
   if (threadIdx.x == 0)
     partials[blk] = s;
 }
-// which: 0 = every block; 1 = only the blocks of G[0, n_main); 2 = only the tail tensors' blocks (same partials, same
-// order).  Splitting the pass - main blocks on the weight-gradient stream beside conv1 wgrad, tail blocks after the join -
-// measured slower (454.7 vs 450.0 us per minibatch: the tail launch alone still costs 7.8 us and the join gap stays).
-int launch_sumsq(hipStream_t s, float *G, long n_main, float *partials, int nblk_main, const ReduceSeg tail[2],
-                 int which) {
+// One launch covers every block.  Splitting the pass - main blocks on the weight-gradient stream beside conv1 wgrad, tail
+// blocks after the join - measured slower (454.7 vs 450.0 us per minibatch: the tail launch alone still costs 7.8 us and
+// the join gap stays).
+int launch_sumsq(hipStream_t s, float *G, long n_main, float *partials, int nblk_main, const ReduceSeg tail[2]) {
   SumsqTail t;
   for (int i = 0; i < 2; ++i) {
     t.seg[i] = tail[i];
     t.chunks[i] = (int)((tail[i].n + 63) / 64);
   }
   const int ntail = t.chunks[0] + t.chunks[1], nblk = nblk_main + ntail;
-  const int first = which == 2 ? nblk_main : 0, count = which == 1 ? nblk_main : nblk - first;
-  hipLaunchKernelGGL(sumsq_kernel, dim3(count), dim3(256), 0, s, G, n_main, partials, nblk_main, t, first);
+  hipLaunchKernelGGL(sumsq_kernel, dim3(nblk), dim3(256), 0, s, G, n_main, partials, nblk_main, t);
   return nblk; // partials written once every block has run
 }
 
 struct long4_ranges {
   long begin[4], len[4];
 };
-// One Adam step of element i (train.cc:42-44 clip scale always applied; torch::optim::Adam's update form)
+// One Adam step of one element (train.cc:42-44 clip scale always applied; torch::optim::Adam's update form)
 struct AdamScalars {
   float coef, step_size, bc2_sqrt, beta1, beta2, omb1, omb2, eps;
 };
-__device__ __forceinline__ float adam_element(long i, float *P, const float *__restrict__ G, float *Gs, float *M1,
-                                              float *M2, const AdamScalars &a) {
-  const float g = G[i] * a.coef;
-  const float m = M1[i] * a.beta1 + a.omb1 * g;
-  const float v = M2[i] * a.beta2 + a.omb2 * (g * g);
+struct AdamElement {
+  float p, m, v;
+};
+// g: the raw gradient; m1, m2, p0: the element's moments and parameter before the step.  The one copy of the update's
+// arithmetic: both paths of adam_kernel call it, so their bits agree by construction.
+__device__ __forceinline__ AdamElement adam_element(float g, float m1, float m2, float p0, const AdamScalars &a) {
+  g *= a.coef;
+  const float m = m1 * a.beta1 + a.omb1 * g;
+  const float v = m2 * a.beta2 + a.omb2 * (g * g);
   const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-  const float p = P[i] - a.step_size * (m / denom);
-  M1[i] = m;
-  M2[i] = v;
-  P[i] = p;
-  if (Gs)
-    Gs[i] = g;
-  return p;
+  return {p0 - a.step_size * (m / denom), m, v};
 }
 // The dgrad-side weight layouts are TRANSPOSES of three weight tensors (W3d[c][(tap,oc)], W2d[class][c][(ab,oc)],
 // WfcT[j][o]): the blocks that own those tensors walk them in 64-row tiles, write the updated weight to the compute copy
@@ -1195,8 +1143,8 @@ struct AdamTiles {
 // hpd: the device block of the hyper-parameter options (common.hpp HYPER_*): slot HYPER_MAX_NORM is the gradient-norm
 // limit, a device value so that a captured update follows ALEPPO_OPT_MAX_GRAD_NORM
 template <class T>
-__global__ __launch_bounds__(256) void adam_kernel(float *P, const float *__restrict__ G, float *Gs, float *M1, float *M2,
-                                                    T *Pc, T *WfcT, T *W3d, T *W2d, AdamTiles tl, long n_flat,
+__global__ __launch_bounds__(256) void adam_kernel(float *P, const float *__restrict__ G, float *M1, float *M2, T *Pc,
+                                                    T *WfcT, T *W3d, T *W2d, AdamTiles tl, long n_flat,
                                                     long4_ranges fr, const float *__restrict__ partials, int nblk,
                                                     const float *__restrict__ hpd, const float *__restrict__ sched,
                                                     float beta1, float beta2, float eps, float *grad_norm_out) {
@@ -1268,19 +1216,13 @@ __global__ __launch_bounds__(256) void adam_kernel(float *P, const float *__rest
         const int r = r4 + 4 * k;
         if (r < rows) {
           const long i = src + (long)r * rs + c;
-          const float gg = g[k] * a.coef;
-          const float m = m1[k] * a.beta1 + a.omb1 * gg;
-          const float v = m2[k] * a.beta2 + a.omb2 * (gg * gg);
-          const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-          const float p = p0[k] - a.step_size * (m / denom);
-          M1[i] = m;
-          M2[i] = v;
-          P[i] = p;
-          if (Gs)
-            Gs[i] = gg;
+          const AdamElement e = adam_element(g[k], m1[k], m2[k], p0[k], a);
+          M1[i] = e.m;
+          M2[i] = e.v;
+          P[i] = e.p;
           if (Pc)
-            Pc[i] = (T)p;
-          tile[r][c] = p;
+            Pc[i] = (T)e.p;
+          tile[r][c] = e.p;
         }
       }
     }
@@ -1303,12 +1245,15 @@ __global__ __launch_bounds__(256) void adam_kernel(float *P, const float *__rest
       }
       i -= fr.len[q];
     }
-    const float p = adam_element(i, P, G, Gs, M1, M2, a);
+    const AdamElement e = adam_element(G[i], M1[i], M2[i], P[i], a);
+    M1[i] = e.m;
+    M2[i] = e.v;
+    P[i] = e.p;
     if (Pc)
-      Pc[i] = (T)p;
+      Pc[i] = (T)e.p;
   }
 }
-void launch_adam(hipStream_t s, float *P, const float *G_in, float *G_out_scaled, float *M1, float *M2, void *Pc,
+void launch_adam(hipStream_t s, float *P, const float *G_in, float *M1, float *M2, void *Pc,
                  void *WfcT, void *W3d, void *W2d, const ParamLayout &L, int prec, const float *partials, int nblk,
                  const float *hpd, const float *sched, float beta1, float beta2, float eps, float *grad_norm_out) {
   AdamTiles tl;
@@ -1332,12 +1277,12 @@ void launch_adam(hipStream_t s, float *P, const float *G_in, float *G_out_scaled
   }
   const int nb = tl.first[3] + (int)std::min<long>((n_flat + 255) / 256, 1024);
   if (prec == ALEPPO_BF16)
-    hipLaunchKernelGGL(adam_kernel<bf16>, dim3(nb), dim3(256), 0, s, P, G_in, G_out_scaled, M1, M2,
+    hipLaunchKernelGGL(adam_kernel<bf16>, dim3(nb), dim3(256), 0, s, P, G_in, M1, M2,
                        static_cast<bf16 *>(Pc), static_cast<bf16 *>(WfcT), static_cast<bf16 *>(W3d),
                        static_cast<bf16 *>(W2d), tl, n_flat, fr, partials, nblk, hpd, sched, beta1, beta2, eps,
                        grad_norm_out);
   else
-    hipLaunchKernelGGL(adam_kernel<float>, dim3(nb), dim3(256), 0, s, P, G_in, G_out_scaled, M1, M2,
+    hipLaunchKernelGGL(adam_kernel<float>, dim3(nb), dim3(256), 0, s, P, G_in, M1, M2,
                        static_cast<float *>(nullptr), static_cast<float *>(WfcT), static_cast<float *>(W3d),
                        static_cast<float *>(W2d), tl, n_flat, fr, partials, nblk, hpd, sched, beta1, beta2, eps,
                        grad_norm_out);
@@ -1592,18 +1537,6 @@ __device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
 __device__ __forceinline__ unsigned long long digest_term(unsigned long long tagkey, uint32_t i, uint32_t w) {
   return splitmix64(tagkey ^ (((unsigned long long)i << 32) | w));
 }
-// sum of v over the 256 threads of the workgroup, valid in thread 0 (s4: 4 words of LDS; may be reused after a barrier)
-__device__ __forceinline__ unsigned long long digest_block_sum(unsigned long long v, unsigned long long *s4) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-    v += __shfl_down(v, o, 64);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0)
-    s4[wave] = v;
-  __syncthreads();
-  return s4[0] + s4[1] + s4[2] + s4[3];
-}
 // internal parameter layout -> libtorch parameters() index (the inverse of params_to_internal, api_core.hip): tensor k
 // holds `size` elements from internal offset `off`; element j = (oc, kk, c) of a [oc][KK][C] weight is exported at
 // base + (oc * C + c) * KK + kk (C = KK = 1: a plain copy); the stacked heads split at `split` (action rows | value row)
@@ -1647,8 +1580,8 @@ __global__ __launch_bounds__(256) void digest_learner_kernel(const u32x4 *__rest
       }
     }
   }
-  ap = digest_block_sum(ap, s4);
-  am = digest_block_sum(am, s4);
+  ap = block_sum_256(ap, s4);
+  am = block_sum_256(am, s4);
   if (threadIdx.x == 0) {
     if (blockIdx.x == 0)
       am += splitmix64(splitmix64(4) ^ step);
@@ -1672,7 +1605,7 @@ __global__ __launch_bounds__(256) void digest_rollout_kernel(const uint32_t *__r
     for (int k = 0; k < 4; ++k)
       a += digest_term(k5, i + k, w[k]);
   }
-  a = digest_block_sum(a, s4);
+  a = block_sum_256(a, s4);
   if (threadIdx.x == 0) {
     if (blockIdx.x == 0)
       a += splitmix64(splitmix64(6) ^ counter);
@@ -1689,7 +1622,7 @@ __global__ __launch_bounds__(256) void digest_rs_kernel(const double *__restrict
     const unsigned long long b = (unsigned long long)__double_as_longlong(d < 3 ? blk[d] : g[d - 3]);
     a += digest_term(k7, 2u * d, (uint32_t)b) + digest_term(k7, 2u * d + 1u, (uint32_t)(b >> 32));
   }
-  a = digest_block_sum(a, s4);
+  a = block_sum_256(a, s4);
   if (threadIdx.x == 0)
     atomicAdd(out + ALEPPO_DG_REWARD_SCALE, a);
 }

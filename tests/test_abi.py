@@ -165,3 +165,32 @@ def test_plain_bench_run_measures_only_the_headline(tmp_path):
     assert "frame leg" not in r.stderr and "cpu baseline" not in r.stderr
     assert (tmp_path / "params.npy").exists()
     assert float(np.load(tmp_path / "train_loss.npy")[-1, -1]) == d["last_loss"]
+
+
+# every environment variable the library reads: the per-context switches' mirrors (tuning_from_env), the replay-gate
+# reference route and the gate timeout.  An A/B of anything else is two builds (tests/tools/ab.sh).
+DOCUMENTED_ENV = {"ALEPPO_GENERIC_CONV", "ALEPPO_FC_PIPE", "ALEPPO_FWD_FUSED", "ALEPPO_BWD_FUSED", "ALEPPO_FUSED_ACT",
+                  "ALEPPO_REPLAY_GATED", "ALEPPO_GATE_TIMEOUT_MS"}
+ABLATION_ENV = {"ALEPPO_FF_ABLATE", "ALEPPO_CB_ABLATE"}  # read only by a `make ABLATIONS=1` build
+
+
+def _env_names(src):
+    """ALEPPO_* names passed to getenv, directly or through a helper that forwards its `name` argument to getenv"""
+    names = set(re.findall(r"getenv\(\s*\"(ALEPPO_[A-Z0-9_]+)\"", src))
+    for helper in re.findall(r"(\w+)\s*(?:=\s*\[[^\]]*\]\s*)?\(const char \*name[^)]*\)\s*\{[^{}]*getenv\(name\)", src):
+        names |= set(re.findall(rf"\b{helper}\(\s*\"(ALEPPO_[A-Z0-9_]+)\"", src))
+    return names
+
+
+def test_library_reads_only_the_documented_environment():
+    import glob
+    default, ablation = set(), set()
+    paths = sorted(glob.glob(os.path.join(ROOT, "ale-libtorch-ppo_amd", "csrc", "*.h*")))  # *.hip, *.hpp
+    assert len(paths) > 30
+    for path in paths:
+        src = open(path).read()
+        unguarded = re.sub(r"#ifdef ALEPPO_ABLATIONS\n.*?#endif", "", src, flags=re.S)  # what the default build compiles
+        default |= _env_names(unguarded)
+        ablation |= _env_names(src) - _env_names(unguarded)
+    assert default == DOCUMENTED_ENV, sorted(default ^ DOCUMENTED_ENV)
+    assert ablation == ABLATION_ENV, sorted(ablation ^ ABLATION_ENV)

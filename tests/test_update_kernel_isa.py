@@ -93,3 +93,16 @@ def test_fused_kernel_budget_and_indexed_variant(code_objects, tag):
     assert pre1 == pre0, "the indexed variant issues a different number of prefetch loads"
     assert st1 == st0, "the indexed variant issues different global stores"
     assert w1 == w0, f"the indexed variant waits differently: {sorted(set(w0) ^ set(w1))}"
+
+
+@pytest.mark.parametrize("kernel", ["fwd_fused_kernel", "conv_bwd_fused_kernel"])
+def test_default_build_ships_no_ablation_variant(code_objects, kernel):
+    """The timing-only ablations (ABL != 0: a phase left out, wrong results) exist only in a `make ABLATIONS=1` build: the
+    default library holds exactly the contiguous and the indexed instantiation of ABL = 0."""
+    syms = set()
+    for co in code_objects:
+        t = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], check=True, capture_output=True,
+                           text=True).stdout
+        syms |= set(re.findall(rf"\.name:\s+(_ZN6aleppo\d+{kernel}I\S+)", t))
+    assert syms and all(re.match(rf"_ZN6aleppo\d+{kernel}ILi0ELb[01]E", s) for s in syms), sorted(syms)
+    assert sorted(re.match(rf"_ZN6aleppo\d+{kernel}ILi0ELb([01])E", s).group(1) for s in syms) == ["0", "1"], sorted(syms)

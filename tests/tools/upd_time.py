@@ -1,7 +1,8 @@
 """developer tool: wall time of the PPO update alone at the BASELINE configs[1] shape (4 epochs x 4 minibatches of 4096, bf16),
-no per-kernel profiling (no event records between the kernels): `python tests/tools/upd_time.py [reps]`.  A/B switches come from
-the environment (ALEPPO_SCHED, ALEPPO_WG_GRID, ALEPPO_BWD_STREAMS, ...); run it under `rocprofv3 --kernel-trace` +
-tests/tools/timeline.py for the kernel timeline of one minibatch."""
+no per-kernel profiling (no event records between the kernels): `python tests/tools/upd_time.py [reps]`.  The per-context kernel
+switches come from the environment (ALEPPO_FC_PIPE, ALEPPO_FWD_FUSED, ALEPPO_BWD_FUSED, ...), UPD_SERIAL=1 sets
+ALEPPO_OPT_SERIAL_UPDATE (every kernel on the main stream); run it under `rocprofv3 --kernel-trace` + tests/tools/timeline.py
+for the kernel timeline of one minibatch."""
 import json, os, sys, time
 import numpy as np
 _T = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -14,6 +15,8 @@ E, T, A, H, M, EP = 128, 128, int(os.environ.get("KB_A", "4")), 512, int(os.envi
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 eng = pkg.Engine(E, T, A, H, precision=pkg.BF16, max_minibatch=E * T // M)
 eng.load_params(hf.fill_params(310, H, A))
+if os.environ.get("UPD_SERIAL"):
+    eng.set_option(pkg.OPT_SERIAL_UPDATE, 1)
 if os.environ.get("KB_FORCE_COMM"):  # the data-parallel schedule through a 1-rank RCCL communicator
     eng.comm_init(pkg.Engine.comm_unique_id())
     eng.set_option(pkg.OPT_FORCE_COMM, 1)
