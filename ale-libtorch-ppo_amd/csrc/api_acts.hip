@@ -5,18 +5,13 @@
 
 using namespace aleppo;
 
-// the caller's observations -> packed stacks in c->stage_obs (never the rollout's slots), as aleppo_forward stages them
+// the caller's observations -> packed stacks in a staging area of their own, c->stage_obs: the rollout's observation
+// slots are not touched
 int aleppo::stage_forward_input(aleppo_ctx *c, const uint8_t *observations, int64_t n, SampleMap *map) {
   if (int rc = stage_observations(c, observations, n))
     return rc;
   const size_t need = (size_t)n * FRAME_PIX * 4;
-  if (need > c->stage_obs_cap) {
-    retire(c, c->stage_obs);
-    c->stage_obs = nullptr;
-    c->stage_obs_cap = 0;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->stage_obs), need));
-    c->stage_obs_cap = need;
-  }
+  HIPCHK(c, grow(c, &c->stage_obs, &c->stage_obs_cap, need, ALLOC_RAW));
   *map = SampleMap{1, (long)FRAME_PIX, 0, 0, 0}; // sample n at stage_obs + n * 7056
   launch_obs_pack(c->stream, c->stage_u8, c->stage_obs, n, *map);
   return ALEPPO_OK;
@@ -39,13 +34,7 @@ extern "C" int aleppo_forward_activations(aleppo_ctx *c, const uint8_t *observat
     need += out[l] ? (size_t)n * per[l] * 4 : 0;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->pre_acted = -1; // a1 / a2 / a3 / h are shared scratch
-  if (need > c->ax_cap) {
-    retire(c, c->ax_buf);
-    c->ax_buf = nullptr;
-    c->ax_cap = 0;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->ax_buf), need));
-    c->ax_cap = need;
-  }
+  HIPCHK(c, grow(c, &c->ax_buf, &c->ax_cap, need, ALLOC_RAW));
   SampleMap map{};
   if (int rc = stage_forward_input(c, observations, n, &map))
     return rc;
@@ -93,7 +82,7 @@ int act_stats_measure(aleppo_ctx *c, const uint8_t *observations, int64_t n, dou
   c->pre_acted = -1; // a1 / a2 / a3 / h are shared scratch
   // the scratch holds the largest sample count either source can bring (the record count grows with it)
   if (!c->as_scratch)
-    HIPCHK(c, dalloc(&c->as_scratch, act_stats_plan(c->prec, c->H, std::max(c->N, c->maxB), c->maxB).bytes, c->stream));
+    HIPCHK(c, dalloc(c, &c->as_scratch, act_stats_plan(c->prec, c->H, std::max(c->N, c->maxB), c->maxB).bytes));
   const ActStatsPlan pl = act_stats_plan(c->prec, c->H, total, c->maxB);
   const uint32_t *obs = c->obs;
   SampleMap map = train_map(c, 0);

@@ -4,16 +4,10 @@
 
 using namespace aleppo;
 
-// NCHW uint8 observations of the caller -> c->stage_u8 (device), grown on demand and kept
+// NCHW uint8 observations of the caller -> c->stage_u8 (device)
 int aleppo::stage_observations(aleppo_ctx *c, const uint8_t *observations, int64_t n) {
   const size_t bytes = (size_t)n * 4 * FRAME_PIX;
-  if (bytes > c->stage_u8_cap) {
-    retire(c, c->stage_u8);
-    c->stage_u8 = nullptr;
-    c->stage_u8_cap = 0;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->stage_u8), bytes));
-    c->stage_u8_cap = bytes;
-  }
+  HIPCHK(c, grow(c, &c->stage_u8, &c->stage_u8_cap, bytes, ALLOC_RAW));
   HIPCHK(c, copy_sync(c, c->stage_u8, observations, bytes, hipMemcpyHostToDevice));
   return ALEPPO_OK;
 }
@@ -99,20 +93,9 @@ extern "C" int aleppo_forward(aleppo_ctx *c, const uint8_t *observations, int64_
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "forward: n exceeds capacity");
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->pre_acted = -1; // a3 / h are shared scratch
-  int rc = stage_observations(c, observations, n);
-  if (rc)
+  SampleMap map{};
+  if (int rc = stage_forward_input(c, observations, n, &map))
     return rc;
-  // the packed stacks go to a staging area of their own: the rollout's observation slots are not touched
-  const size_t need = (size_t)n * FRAME_PIX * 4;
-  if (need > c->stage_obs_cap) {
-    retire(c, c->stage_obs);
-    c->stage_obs = nullptr;
-    c->stage_obs_cap = 0;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->stage_obs), need));
-    c->stage_obs_cap = need;
-  }
-  const SampleMap map{1, (long)FRAME_PIX, 0, 0, 0}; // sample n at stage_obs + n * 7056
-  launch_obs_pack(c->stream, c->stage_u8, c->stage_obs, n, map);
   net_forward(c, c->stage_obs, map, n);
   launch_heads_fwd(c->stream, c->h, Pf(c, P_WH), Pf(c, P_BH), c->logits_b, c->values_b, n, c->H, c->A);
   HIPCHK(c, hipMemcpyAsync(logits, c->logits_b, (size_t)n * c->A * 4, hipMemcpyDeviceToHost, c->stream));
@@ -130,16 +113,9 @@ extern "C" int aleppo_read_batch(aleppo_ctx *c, int field, void *dst, size_t byt
   const size_t N = (size_t)c->N;
   hipStream_t s = c->stream;
   size_t need = 0;
-  // device scratch owned by the context, grown on demand and never freed before aleppo_destroy (hipFree would wait for
-  // every stream of the device, other contexts' parked ones included: see dalloc)
+  // device scratch owned by the context, grown on demand
   auto scratch = [&](int k, size_t nbytes, void **out) -> int {
-    if (nbytes > c->rb_cap[k]) {
-      retire(c, c->rb_tmp[k]);
-      c->rb_tmp[k] = nullptr;
-      c->rb_cap[k] = 0;
-      HIPCHK(c, hipMalloc(&c->rb_tmp[k], nbytes));
-      c->rb_cap[k] = nbytes;
-    }
+    HIPCHK(c, grow(c, &c->rb_tmp[k], &c->rb_cap[k], nbytes, ALLOC_RAW));
     *out = c->rb_tmp[k];
     return ALEPPO_OK;
   };

@@ -149,14 +149,46 @@ hipError_t copy_sync(Ctx *c, void *dst, const void *src, size_t bytes, hipMemcpy
   hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, c->stream);
   return e == hipSuccess ? hipStreamSynchronize(c->stream) : e;
 }
-// device / pinned-host memory a context has outgrown: kept until aleppo_destroy (see above)
-void retire(Ctx *c, void *dev) {
-  if (dev)
-    c->retired.push_back(dev);
+// memory: allocate and register; aleppo_destroy alone frees (why: api_internal.hpp)
+hipError_t ctx_alloc(Ctx *c, void **p, size_t bytes, AllocForm form) {
+  *p = nullptr;
+  if (form == ALLOC_ZEROED && !bytes)
+    bytes = 16;
+  void *q = nullptr;
+  hipError_t e = hipMalloc(&q, bytes);
+  if (e != hipSuccess)
+    return e;
+  if (q)
+    c->owned_dev.push_back(q);
+  if (form == ALLOC_ZEROED) {
+    e = hipMemsetAsync(q, 0, bytes, c->stream);
+    if (e == hipSuccess)
+      e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess)
+      return e;
+  }
+  *p = q;
+  return hipSuccess;
 }
-void retire_host(Ctx *c, void *host) {
-  if (host)
-    c->retired_host.push_back(host);
+hipError_t ctx_host_alloc(Ctx *c, void **p, size_t bytes, unsigned flags) {
+  *p = nullptr;
+  void *q = nullptr;
+  const hipError_t e = hipHostMalloc(&q, bytes, flags);
+  if (e != hipSuccess)
+    return e;
+  if (q)
+    c->owned_host.push_back(q);
+  *p = q;
+  return hipSuccess;
+}
+hipError_t ctx_grow(Ctx *c, void **p, size_t *cap, size_t need, size_t bytes, AllocForm form) {
+  if (need <= *cap)
+    return hipSuccess;
+  *cap = 0;
+  const hipError_t e = ctx_alloc(c, p, bytes, form);
+  if (e == hipSuccess)
+    *cap = need;
+  return e;
 }
 
 void prof_begin(Ctx *c, int cls, hipStream_t st) {
@@ -320,31 +352,31 @@ extern "C" int aleppo_create(const aleppo_config *cfg, aleppo_ctx **out) {
   CK(hipEventCreateWithFlags(&c->ev_tmp, hipEventDisableTiming));
   for (hipEvent_t *e : {&c->ev_head, &c->ev_dz3, &c->ev_dz2, &c->ev_wg})
     CK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-  CK(dalloc(&c->obs, (size_t)E * (T + 1) * FRAME_PIX * 4, c->stream));
+  CK(dalloc(c, &c->obs, (size_t)E * (T + 1) * FRAME_PIX * 4));
   c->step_rec_bytes = ((size_t)7 * E + 15) / 16 * 16;
-  CK(dalloc(&c->step_rec, c->step_rec_bytes * T, c->stream));
-  CK(dalloc(reinterpret_cast<char **>(&c->values_tm), (size_t)(T + 1) * E * c->rsz, c->stream));
-  CK(dalloc(reinterpret_cast<char **>(&c->logits_tm), (size_t)(T + 1) * E * A * c->rsz, c->stream));
-  CK(dalloc(&c->actions_tm, (size_t)(T + 1) * E * 4, c->stream));
-  CK(dalloc(&c->lut, 256, c->stream));
-  CK(dalloc(&c->d_start, (size_t)E, c->stream));
-  CK(dalloc(&c->d_frames, (size_t)E * 2 * RAW_H * RAW_W, c->stream));
-  CK(dalloc(&c->d_noise, (size_t)2 * E * A * 4, c->stream));
-  CK(dalloc(&c->d_err, 16, c->stream));
-  CK(dalloc(&c->d_done, 16, c->stream));
+  CK(dalloc(c, &c->step_rec, c->step_rec_bytes * T));
+  CK(dalloc(c, &c->values_tm, (size_t)(T + 1) * E * c->rsz));
+  CK(dalloc(c, &c->logits_tm, (size_t)(T + 1) * E * A * c->rsz));
+  CK(dalloc(c, &c->actions_tm, (size_t)(T + 1) * E * 4));
+  CK(dalloc(c, &c->lut, 256));
+  CK(dalloc(c, &c->d_start, (size_t)E));
+  CK(dalloc(c, &c->d_frames, (size_t)E * 2 * RAW_H * RAW_W));
+  CK(dalloc(c, &c->d_noise, (size_t)2 * E * A * 4));
+  CK(dalloc(c, &c->d_err, 16));
+  CK(dalloc(c, &c->d_done, 16));
   {
     uint8_t ident[256];
     for (int i = 0; i < 256; ++i)
       ident[i] = (uint8_t)i;
     CK(copy_sync(c, c->lut, ident, 256, hipMemcpyHostToDevice));
   }
-  CK(hipHostMalloc(reinterpret_cast<void **>(&c->h_actions), (size_t)(E + 8) * 8, hipHostMallocMapped));
-  CK(hipHostMalloc(reinterpret_cast<void **>(&c->h_step), c->step_rec_bytes + E, hipHostMallocDefault));
-  CK(hipHostMalloc(reinterpret_cast<void **>(&c->h_rec), c->step_rec_bytes * T, hipHostMallocDefault));
+  CK(halloc(c, &c->h_actions, (size_t)(E + 8) * 8, hipHostMallocMapped));
+  CK(halloc(c, &c->h_step, c->step_rec_bytes + E, hipHostMallocDefault));
+  CK(halloc(c, &c->h_rec, c->step_rec_bytes * T, hipHostMallocDefault));
   std::memset(c->h_rec, 0, c->step_rec_bytes * T);
-  CK(hipHostMalloc(reinterpret_cast<void **>(&c->h_frames), (size_t)E * 2 * RAW_H * RAW_W, hipHostMallocDefault));
-  CK(hipHostMalloc(reinterpret_cast<void **>(&c->h_noise), (size_t)2 * E * A * 4, hipHostMallocDefault));
-  CK(hipHostMalloc(reinterpret_cast<void **>(&c->h_go), 64, hipHostMallocMapped));
+  CK(halloc(c, &c->h_frames, (size_t)E * 2 * RAW_H * RAW_W, hipHostMallocDefault));
+  CK(halloc(c, &c->h_noise, (size_t)2 * E * A * 4, hipHostMallocDefault));
+  CK(halloc(c, &c->h_go, 64, hipHostMallocMapped));
   std::memset(c->h_go, 0, 64);
   {
     // exit condition of the slot-ahead gate (gate_kernel): an emulator step takes milliseconds, so two minutes mean the
@@ -353,37 +385,37 @@ extern "C" int aleppo_create(const aleppo_config *cfg, aleppo_ctx **out) {
     const double ms = e ? std::max(1.0, std::atof(e)) : 120000.0;
     c->gate_timeout_ticks = (unsigned long long)(ms * 1e5); // 100 MHz wall clock
   }
-  CK(hipHostMalloc(reinterpret_cast<void **>(&c->h_err), 16, hipHostMallocDefault));
+  CK(halloc(c, &c->h_err, 16, hipHostMallocDefault));
   std::memset(c->h_actions, 0, (size_t)(E + 8) * 8);
-  CK(dalloc(reinterpret_cast<char **>(&c->adv_n), (size_t)c->N * c->rsz, c->stream));
-  CK(dalloc(reinterpret_cast<char **>(&c->ret_n), (size_t)c->N * c->rsz, c->stream));
-  CK(dalloc(reinterpret_cast<char **>(&c->oldlp_n), (size_t)c->N * A * c->rsz, c->stream));
-  CK(dalloc(&c->act_n, (size_t)c->N * 4, c->stream));
-  CK(dalloc(&c->mask_n, (size_t)c->N, c->stream));
-  CK(dalloc(&c->mask_counts, 4096 * 4, c->stream));
-  CK(dalloc(&c->P, PT * 4, c->stream));
-  CK(dalloc(&c->G, PT * 4, c->stream));
-  CK(dalloc(&c->M1, PT * 4, c->stream));
-  CK(dalloc(&c->M2, PT * 4, c->stream));
+  CK(dalloc(c, &c->adv_n, (size_t)c->N * c->rsz));
+  CK(dalloc(c, &c->ret_n, (size_t)c->N * c->rsz));
+  CK(dalloc(c, &c->oldlp_n, (size_t)c->N * A * c->rsz));
+  CK(dalloc(c, &c->act_n, (size_t)c->N * 4));
+  CK(dalloc(c, &c->mask_n, (size_t)c->N));
+  CK(dalloc(c, &c->mask_counts, 4096 * 4));
+  CK(dalloc(c, &c->P, PT * 4));
+  CK(dalloc(c, &c->G, PT * 4));
+  CK(dalloc(c, &c->M1, PT * 4));
+  CK(dalloc(c, &c->M2, PT * 4));
   if (c->prec == ALEPPO_BF16)
-    CK(dalloc(reinterpret_cast<char **>(&c->Pc), PT * 2, c->stream));
+    CK(dalloc(c, &c->Pc, PT * 2));
   else
-    c->Pc = c->P;
-  CK(dalloc(reinterpret_cast<char **>(&c->W2d), (size_t)4 * 32 * 256 * ts, c->stream));
-  CK(dalloc(reinterpret_cast<char **>(&c->W3d), (size_t)64 * 576 * ts, c->stream));
-  CK(dalloc(reinterpret_cast<char **>(&c->WfcT), (size_t)FC_IN * H * ts, c->stream));
+    c->Pc = c->P; // (an alias: never registered)
+  CK(dalloc(c, &c->W2d, (size_t)4 * 32 * 256 * ts));
+  CK(dalloc(c, &c->W3d, (size_t)64 * 576 * ts));
+  CK(dalloc(c, &c->WfcT, (size_t)FC_IN * H * ts));
   const size_t mb = (size_t)c->maxB;
-  CK(dalloc(reinterpret_cast<char **>(&c->a1), mb * A1_PIX * A1_C * ts, c->stream));
-  CK(dalloc(reinterpret_cast<char **>(&c->a2), mb * A2_PIX * A2_C * ts, c->stream));
-  CK(dalloc(reinterpret_cast<char **>(&c->a3), mb * FC_IN * ts, c->stream));
-  CK(dalloc(reinterpret_cast<char **>(&c->dz1), mb * A1_PIX * A1_C * ts, c->stream));
-  CK(dalloc(reinterpret_cast<char **>(&c->dz2), mb * A2_PIX * A2_C * ts, c->stream));
-  CK(dalloc(reinterpret_cast<char **>(&c->dz3), mb * FC_IN * ts, c->stream));
-  CK(dalloc(&c->h, (size_t)FC_FWD_MAX_PARTS * mb * H * 4, c->stream)); // up to FC_FWD_MAX_PARTS split-K slabs
-  CK(dalloc(&c->hpart, (size_t)FC_SPLITS * E * H * 4, c->stream));
-  CK(dalloc(reinterpret_cast<char **>(&c->dh), mb * H * ts, c->stream));
-  CK(dalloc(&c->logits_b, mb * A * 4, c->stream));
-  CK(dalloc(&c->values_b, mb * 4, c->stream));
+  CK(dalloc(c, &c->a1, mb * A1_PIX * A1_C * ts));
+  CK(dalloc(c, &c->a2, mb * A2_PIX * A2_C * ts));
+  CK(dalloc(c, &c->a3, mb * FC_IN * ts));
+  CK(dalloc(c, &c->dz1, mb * A1_PIX * A1_C * ts));
+  CK(dalloc(c, &c->dz2, mb * A2_PIX * A2_C * ts));
+  CK(dalloc(c, &c->dz3, mb * FC_IN * ts));
+  CK(dalloc(c, &c->h, (size_t)FC_FWD_MAX_PARTS * mb * H * 4)); // up to FC_FWD_MAX_PARTS split-K slabs
+  CK(dalloc(c, &c->hpart, (size_t)FC_SPLITS * E * H * 4));
+  CK(dalloc(c, &c->dh, mb * H * ts));
+  CK(dalloc(c, &c->logits_b, mb * A * 4));
+  CK(dalloc(c, &c->values_b, mb * 4));
   // slabs: [W1|b1|W2|b2|W3|b3|Wfc|bfc|Wh|bh]
   c->slab_off[0] = 0;
   const size_t sl[10] = {(size_t)MAXS_C1 * 32 * 256,       (size_t)MAXS_C1 * 32, (size_t)MAXS_C2 * 64 * 512,
@@ -393,13 +425,13 @@ extern "C" int aleppo_create(const aleppo_config *cfg, aleppo_ctx **out) {
   for (int i = 0; i < 10; ++i)
     c->slab_off[i + 1] = c->slab_off[i] + align64(sl[i]);
   c->slab_floats = c->slab_off[10];
-  CK(dalloc(&c->slab, c->slab_floats * 4, c->stream));
-  CK(dalloc(&c->sumsq_part, 1024 * 4, c->stream));
-  CK(dalloc(&c->adv_stats, 64, c->stream));
+  CK(dalloc(c, &c->slab, c->slab_floats * 4));
+  CK(dalloc(c, &c->sumsq_part, 1024 * 4));
+  CK(dalloc(c, &c->adv_stats, 64));
   // the hyper-parameter block of ALEPPO_OPT_CLIP_PARAM and its kin, filled and uploaded at each aleppo_train
-  CK(dalloc(&c->hyper_blk, HYPER_BLOCK * 4, c->stream));
-  CK(hipHostMalloc(reinterpret_cast<void **>(&c->h_hyper_blk), HYPER_BLOCK * 4, hipHostMallocDefault));
-  CK(hipStreamSynchronize(c->stream)); // (own streams only: see dalloc)
+  CK(dalloc(c, &c->hyper_blk, HYPER_BLOCK * 4));
+  CK(halloc(c, &c->h_hyper_blk, HYPER_BLOCK * 4, hipHostMallocDefault));
+  CK(hipStreamSynchronize(c->stream)); // (own streams only: api_internal.hpp, memory)
 #undef CK
   *out = c;
   return ALEPPO_OK;
@@ -424,32 +456,9 @@ extern "C" void aleppo_destroy(aleppo_ctx *c) {
     hipGraphDestroy(c->graph);
   if (c->nccl_comm)
     ncclCommDestroy(static_cast<ncclComm_t>(c->nccl_comm));
-  void *dev[] = {c->obs,   c->step_rec, c->values_tm, c->logits_tm, c->actions_tm, c->lut,     c->d_start,
-                 c->d_frames, c->d_noise, c->d_err,  c->d_done, c->adv_n,     c->ret_n,      c->oldlp_n, c->act_n,
-                 c->mask_n, c->mask_counts, c->P,    c->G,         c->M1,      c->M2,
-                 c->W2d,   c->W3d,      c->WfcT,      c->a1,        c->a2,         c->a3,      c->dz1,
-                 c->dz2,   c->dz3,      c->h,         c->hpart,     c->dh,        c->logits_b,   c->values_b, c->slab,
-                 c->sumsq_part, c->metric_ps, c->metric_red, c->grad_norms, c->adv_stats, c->stage_u8, c->stage_obs,
-                 c->adam_sched, c->rb_tmp[0], c->rb_tmp[1], c->order, c->act_p, c->oldlp_p, c->adv_p,
-                 c->ret_p,  c->mask_p,   c->mask_counts_ep, c->shuf_keys, c->val_n, c->val_p, c->advn_part,
-                 c->advn_stats, c->kl_ps, c->kl_beta, c->hyper_blk, c->rs_blk, c->ev_obs, c->ev_a1, c->ev_a2, c->ev_a3, c->ev_hpart,
-                 c->ev_logits, c->ev_values, c->ev_actions, c->ev_d_frames, c->ev_d_start, c->ev_d_noise, c->ev_d_done, c->dg_out, c->env_blk, c->ee_blk, c->ts_scratch, c->ax_buf, c->as_scratch, c->rc_mask,
-                 c->sal_blur, c->sal_stage, c->sal_base, c->sal_out, c->sal_u8,
-                 c->rec[0].blk, c->rec[1].blk};
-  for (void *p : dev)
-    if (p)
-      hipFree(p);
-  for (void *p : c->retired)
+  for (void *p : c->owned_dev)
     hipFree(p);
-  if (c->Pc && c->Pc != c->P)
-    hipFree(c->Pc);
-  void *host[] = {c->h_go, c->h_actions, c->h_step, c->h_rec, c->h_frames, c->h_noise, c->h_err, c->h_metric_red,
-                  c->h_adam_sched, c->h_shuf_keys, c->h_advn_stats, c->h_kl_beta, c->h_hyper_blk, c->ev_h_frames,
-                  c->ev_h_start, c->ev_h_noise, c->ev_h_actions};
-  for (void *p : host)
-    if (p)
-      hipHostFree(p);
-  for (void *p : c->retired_host)
+  for (void *p : c->owned_host)
     hipHostFree(p);
   for (auto &pc : c->prof)
     for (size_t i = 0; i < pc.start.size(); ++i) {
@@ -499,7 +508,7 @@ extern "C" int aleppo_load_params(aleppo_ctx *c, const float *flat, size_t count
   HIPCHK(c, hipMemsetAsync(c->M1, 0, tmp.size() * 4, c->stream));
   HIPCHK(c, hipMemsetAsync(c->M2, 0, tmp.size() * 4, c->stream));
   HIPCHK(c, hipMemsetAsync(c->G, 0, tmp.size() * 4, c->stream));
-  HIPCHK(c, copy_sync(c, c->P, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice)); // (own stream only: see dalloc)
+  HIPCHK(c, copy_sync(c, c->P, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice)); // (own stream only: api_internal.hpp, memory)
   c->adam_step = 0;
   c->ts_step_valid = false; // (aleppo_tensor_stats: the last step can no longer be recomputed)
   c->pre_acted = -1;

@@ -85,9 +85,8 @@ extern "C" int aleppo_env_open(aleppo_ctx *c, const aleppo_env_config *cfg) {
     // frames | state[2][E] | logs [4][T][E]: every part starts 16-byte aligned (88 E and the frame strides are multiples of 8 / 16)
     const size_t fb = (size_t)c->E * env_frame_bytes(c), sb = ((size_t)c->E * sizeof(aleppo_env_state) + 15) / 16 * 16;
     uint8_t *blk = nullptr;
-    const hipError_t e = dalloc(&blk, fb + 2 * sb + 4 * env_plane(c) * 4, c->stream); // (zeroed: empty logs)
+    const hipError_t e = dalloc(c, &blk, fb + 2 * sb + 4 * env_plane(c) * 4); // (zeroed: empty logs)
     if (e != hipSuccess) {
-      retire(c, blk);
       c->env_cfg = keep;
       return set_err(c, ALEPPO_ERR_HIP, std::string("env_open: allocation failed: ") + hipGetErrorString(e));
     }

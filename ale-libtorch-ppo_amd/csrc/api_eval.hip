@@ -23,7 +23,7 @@ extern "C" int aleppo_eval_open(aleppo_ctx *c, int32_t num_lanes) {
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "eval_open: num_lanes must be in [1, 4096]");
   if (c->ev_L && c->ev_L != num_lanes)
     return set_err(c, ALEPPO_ERR_RUNTIME, "eval_open: the evaluation lanes are already open with another lane count");
-  const size_t L = (size_t)num_lanes, ts = tsz(c);
+  const size_t L = (size_t)num_lanes;
   if (c->ev_L) { // reset: zero stacks, the sampling stream from its start, no act to read
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemsetAsync(c->ev_obs, 0, L * FRAME_PIX * 4, c->stream));
@@ -33,43 +33,20 @@ extern "C" int aleppo_eval_open(aleppo_ctx *c, int32_t num_lanes) {
     return ALEPPO_OK;
   }
   const bool unfused = !(c->prec == ALEPPO_BF16 && use_patch_kernels()); // conv1 / conv2 outputs pass through memory
-  const size_t nz = L * (size_t)std::max(c->A, 2) * 4, fb = L * 2 * RAW_H * RAW_W;
+  const size_t ts = tsz(c), nz = L * (size_t)std::max(c->A, 2) * 4, fb = L * 2 * RAW_H * RAW_W;
   hipError_t e = hipSuccess;
-  auto dev = [&](auto **p, size_t bytes) {
-    if (e == hipSuccess)
-      e = dalloc(p, bytes, c->stream);
-  };
-  auto host = [&](auto **p, size_t bytes, unsigned flags) {
-    if (e == hipSuccess)
-      e = hipHostMalloc(reinterpret_cast<void **>(p), bytes, flags);
-  };
-  dev(&c->ev_obs, L * FRAME_PIX * 4);
-  if (unfused) {
-    dev(reinterpret_cast<char **>(&c->ev_a1), L * A1_PIX * A1_C * ts);
-    dev(reinterpret_cast<char **>(&c->ev_a2), L * A2_PIX * A2_C * ts);
-  }
-  dev(reinterpret_cast<char **>(&c->ev_a3), L * FC_IN * ts);
-  dev(&c->ev_hpart, (size_t)FC_SPLITS * L * c->H * 4);
-  dev(&c->ev_logits, L * c->A * 4);
-  dev(&c->ev_values, L * 4);
-  dev(&c->ev_actions, L * 4);
-  dev(&c->ev_d_frames, fb);
-  dev(&c->ev_d_start, L);
-  dev(&c->ev_d_noise, nz);
-  dev(&c->ev_d_done, 16);
-  host(&c->ev_h_frames, fb, hipHostMallocDefault);
-  host(&c->ev_h_start, L, hipHostMallocDefault);
-  host(&c->ev_h_noise, nz, hipHostMallocDefault);
-  host(&c->ev_h_actions, (L + 8) * 8, hipHostMallocMapped);
-  if (e == hipSuccess && !c->ev_staged)
-    e = hipEventCreateWithFlags(&c->ev_staged, hipEventDisableTiming);
-  if (e != hipSuccess) { // keep what was allocated until aleppo_destroy (no hipFree before it) and stay closed
-    for (void *p : {(void *)c->ev_obs, c->ev_a1, c->ev_a2, c->ev_a3, (void *)c->ev_hpart, (void *)c->ev_logits,
-                    (void *)c->ev_values, (void *)c->ev_actions, (void *)c->ev_d_frames, (void *)c->ev_d_start,
-                    (void *)c->ev_d_noise, (void *)c->ev_d_done})
-      retire(c, p);
-    for (void *p : {(void *)c->ev_h_frames, (void *)c->ev_h_start, (void *)c->ev_h_noise, (void *)c->ev_h_actions})
-      retire_host(c, p);
+  const auto ok = [&e](hipError_t r) { return (e = r) == hipSuccess; }; // (the chain below ends at the first failure)
+  ok(dalloc(c, &c->ev_obs, L * FRAME_PIX * 4)) &&
+      (!unfused || (ok(dalloc(c, &c->ev_a1, L * A1_PIX * A1_C * ts)) && ok(dalloc(c, &c->ev_a2, L * A2_PIX * A2_C * ts)))) &&
+      ok(dalloc(c, &c->ev_a3, L * FC_IN * ts)) && ok(dalloc(c, &c->ev_hpart, (size_t)FC_SPLITS * L * c->H * 4)) &&
+      ok(dalloc(c, &c->ev_logits, L * c->A * 4)) && ok(dalloc(c, &c->ev_values, L * 4)) &&
+      ok(dalloc(c, &c->ev_actions, L * 4)) && ok(dalloc(c, &c->ev_d_frames, fb)) && ok(dalloc(c, &c->ev_d_start, L)) &&
+      ok(dalloc(c, &c->ev_d_noise, nz)) && ok(dalloc(c, &c->ev_d_done, 16)) &&
+      ok(halloc(c, &c->ev_h_frames, fb, hipHostMallocDefault)) && ok(halloc(c, &c->ev_h_start, L, hipHostMallocDefault)) &&
+      ok(halloc(c, &c->ev_h_noise, nz, hipHostMallocDefault)) &&
+      ok(halloc(c, &c->ev_h_actions, (L + 8) * 8, hipHostMallocMapped)) &&
+      (c->ev_staged || ok(hipEventCreateWithFlags(&c->ev_staged, hipEventDisableTiming)));
+  if (e != hipSuccess) { // stay closed; what was allocated is the registry's until aleppo_destroy
     c->ev_obs = nullptr;
     c->ev_a1 = c->ev_a2 = c->ev_a3 = nullptr;
     c->ev_hpart = c->ev_logits = c->ev_values = c->ev_d_noise = c->ev_h_noise = nullptr;

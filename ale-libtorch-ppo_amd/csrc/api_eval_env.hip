@@ -51,9 +51,8 @@ extern "C" int aleppo_eval_env_open(aleppo_ctx *c, const aleppo_env_config *cfg,
     // frames | state[2][L] | logs [4][S][L] | start [L]: every part but the last starts 16-byte aligned
     const size_t fb = L * ee_frame_bytes(c), sb = (L * sizeof(aleppo_env_state) + 15) / 16 * 16, lb = 4 * ee_plane(c) * 4;
     uint8_t *blk = nullptr;
-    const hipError_t e = dalloc(&blk, fb + 2 * sb + lb + L, c->stream); // (zeroed: empty logs)
+    const hipError_t e = dalloc(c, &blk, fb + 2 * sb + lb + L); // (zeroed: empty logs)
     if (e != hipSuccess) {
-      retire(c, blk);
       c->ee_cfg = keep;
       c->ee_S = 0;
       return set_err(c, ALEPPO_ERR_HIP, std::string("eval_env_open: allocation failed: ") + hipGetErrorString(e));

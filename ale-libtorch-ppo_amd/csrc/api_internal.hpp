@@ -1,6 +1,7 @@
 // api_internal.hpp - what the C ABI's translation units share (api_core.hip, api_rollout.hip, api_train.hip,
-// api_batch.hip, api_eval.hip, api_eval_env.hip, api_env.hip, api_rec.hip, api_state.hip, api_acts.hip, api_recycle.hip, api_saliency.hip, api_ops.hip): the entry-point guard macros and the host-side helpers.  Host code only; the
-// helpers are defined in api_core.hip unless noted.
+// api_batch.hip, api_eval.hip, api_eval_env.hip, api_env.hip, api_rec.hip, api_state.hip, api_acts.hip, api_recycle.hip, api_saliency.hip, api_ops.hip): the entry-point guard macros, the memory
+// ownership helpers (dalloc / halloc / grow over ctx_alloc / ctx_host_alloc / ctx_grow) and the other host-side helpers.
+// Host code only; the helpers are defined in api_core.hip unless noted.
 #pragma once
 #include "common.hpp"
 #include <algorithm>
@@ -58,25 +59,38 @@ namespace aleppo {
 int fail_ctx(Ctx *c, int code, const std::string &msg);
 
 inline size_t tsz(const Ctx *c) { return c->prec == ALEPPO_BF16 ? 2 : 4; }
-// A context only ever touches its OWN streams after aleppo_create: no null-stream operation, no hipFree, no
-// hipDeviceSynchronize.  Those calls wait for (hipFree / hipHostFree / hipDeviceSynchronize) or are ordered against
-// (null stream) other streams of the device - and another context's stream may be parked behind its release word,
-// which only ITS owner thread lifts (the cause of the two-context hang of round 2).
-template <class T> hipError_t dalloc(T **p, size_t bytes, hipStream_t st) {
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(p), bytes ? bytes : 16);
-  if (e == hipSuccess)
-    e = hipMemsetAsync(*p, 0, bytes ? bytes : 16, st);
-  // the fill is asynchronous: wait for it, or a kernel on another stream of the context could use the buffer first and
-  // have its results wiped afterwards (round 2: a late fill of the ticket counter / the metric planes)
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st);
-  return e;
+// ---- memory.  Everything a context allocates goes through the helpers below, which register the pointer in
+// c->owned_dev / c->owned_host; aleppo_destroy frees the two registries and NOTHING else frees.  A context only ever
+// touches its OWN streams after aleppo_create: no null-stream operation, no hipFree, no hipDeviceSynchronize.  Those calls
+// wait for (hipFree / hipHostFree / hipDeviceSynchronize) or are ordered against (null stream) other streams of the
+// device - and another context's stream may be parked behind its release word, which only ITS owner thread lifts
+// (the cause of the two-context hang of round 2).  So a buffer that is outgrown, or that a failed open leaves
+// behind, simply stays in the registry until destroy.  On failure every helper leaves *p == nullptr.
+enum AllocForm {
+  ALLOC_RAW,   // plain hipMalloc
+  ALLOC_ZEROED // at least 16 bytes, zero-filled on c->stream, and the fill waited for: a kernel on another stream of the
+               // context could otherwise use the buffer first and have its results wiped afterwards (round 2: a late fill of
+               // the ticket counter / the metric planes)
+};
+hipError_t ctx_alloc(Ctx *c, void **p, size_t bytes, AllocForm form);
+hipError_t ctx_host_alloc(Ctx *c, void **p, size_t bytes, unsigned flags);
+// a (pointer, capacity) pair grown on demand: nothing if need <= *cap, else a new buffer of `bytes` bytes and *cap = need
+// (the units of the capacity are the site's); a failure leaves (nullptr, 0)
+hipError_t ctx_grow(Ctx *c, void **p, size_t *cap, size_t need, size_t bytes, AllocForm form);
+template <class T> hipError_t dalloc(Ctx *c, T **p, size_t bytes) {
+  return ctx_alloc(c, reinterpret_cast<void **>(p), bytes, ALLOC_ZEROED);
+}
+template <class T> hipError_t halloc(Ctx *c, T **p, size_t bytes, unsigned flags) {
+  return ctx_host_alloc(c, reinterpret_cast<void **>(p), bytes, flags);
+}
+template <class T> hipError_t grow(Ctx *c, T **p, size_t *cap, size_t need, size_t bytes, AllocForm form) {
+  return ctx_grow(c, reinterpret_cast<void **>(p), cap, need, bytes, form);
+}
+template <class T> hipError_t grow(Ctx *c, T **p, size_t *cap, size_t bytes, AllocForm form) { // a capacity in bytes
+  return ctx_grow(c, reinterpret_cast<void **>(p), cap, bytes, bytes, form);
 }
 // host <-> device copy on the context's main stream, complete when the call returns
 hipError_t copy_sync(Ctx *c, void *dst, const void *src, size_t bytes, hipMemcpyKind kind);
-// device / pinned-host memory a context has outgrown: kept until aleppo_destroy (see above)
-void retire(Ctx *c, void *dev);
-void retire_host(Ctx *c, void *host);
 
 // a failure inside a helper that cannot return a status is kept in the context and reported by CHECK_ASYNC at the end of
 // the entry point (never dropped)
@@ -132,11 +146,11 @@ int select_device(int ordinal);
 // staging of aleppo_set_batch's half planes) and ALEPPO_OPT_VALUE_CLIP's old-values plane; api_rollout.hip:
 // ALEPPO_OPT_REWARD_SCALE's state
 int ensure_metric_storage(aleppo_ctx *c, int epochs, int M, long B);
-// api_batch.hip: NCHW uint8 observations of the caller -> c->stage_u8 (device), grown on demand and kept
+// api_batch.hip: NCHW uint8 observations of the caller -> c->stage_u8 (device)
 int stage_observations(aleppo_ctx *c, const uint8_t *observations, int64_t n);
 int ensure_val_storage(aleppo_ctx *c);
 // api_acts.hip, also for api_saliency.hip: the caller's observations -> packed stacks in c->stage_obs (never the rollout's
-// slots), as aleppo_forward stages them; *map addresses them
+// slots); *map addresses them
 int stage_forward_input(aleppo_ctx *c, const uint8_t *observations, int64_t n, SampleMap *map);
 // api_acts.hip, also for aleppo_recycle_dormant (api_recycle.hip): what aleppo_activation_stats refuses in tau and in its
 // source of samples, and the measurement itself with the arguments already checked - everything up to and including the

@@ -47,9 +47,8 @@ extern "C" int aleppo_rec_open(aleppo_ctx *c, const aleppo_rec_config *cfg) {
     const size_t sb = cap * sizeof(aleppo_rec_step), pf = (cfg->content & ALEPPO_REC_FRAMES) ? cap * fb : 0,
                  po = (cfg->content & ALEPPO_REC_OBSERVATION) ? cap * FRAME_PIX : 0;
     uint8_t *blk = nullptr;
-    const hipError_t e = dalloc(&blk, sb + pf + po + cap * (size_t)c->A * 4, c->stream);
+    const hipError_t e = dalloc(c, &blk, sb + pf + po + cap * (size_t)c->A * 4);
     if (e != hipSuccess) {
-      retire(c, blk);
       return set_err(c, ALEPPO_ERR_HIP, std::string("rec_open: allocation failed: ") + hipGetErrorString(e));
     }
     R.cfg = *cfg;

@@ -16,7 +16,7 @@ static inline size_t unit_total(const aleppo_ctx *c) { return (size_t)(A1_C + A2
 
 static int ensure_mask(aleppo_ctx *c) {
   if (!c->rc_mask)
-    HIPCHK(c, dalloc(&c->rc_mask, unit_total(c), c->stream)); // (160 + H is a multiple of 4: the pass loads 4 bytes)
+    HIPCHK(c, dalloc(c, &c->rc_mask, unit_total(c))); // (160 + H is a multiple of 4: the pass loads 4 bytes)
   return ALEPPO_OK;
 }
 

@@ -478,7 +478,7 @@ int ensure_rs_storage(aleppo_ctx *c) {
     return ALEPPO_OK;
   const size_t E = (size_t)c->E, doubles = RS_BLOCK + 2 * E + (size_t)rs_blocks(c->E) * 4 + 4;
   double *blk = nullptr;
-  HIPCHK(c, dalloc(&blk, doubles * sizeof(double), c->stream)); // (zeroed: G = 0)
+  HIPCHK(c, dalloc(c, &blk, doubles * sizeof(double))); // (zeroed: G = 0)
   HIPCHK(c, copy_sync(c, blk, RS_INITIAL, sizeof(RS_INITIAL), hipMemcpyHostToDevice));
   c->rs_blk = blk;
   c->rs_g[0] = blk + RS_BLOCK;

@@ -57,18 +57,6 @@ extern "C" int aleppo_saliency_tables(const aleppo_saliency_config *cfg, uint16_
 }
 
 namespace {
-// a staging buffer grown like stage_obs: the outgrown one is retired, never freed before aleppo_destroy
-template <class T> int sal_grow(aleppo_ctx *c, T **buf, size_t *cap, size_t need) {
-  if (need <= *cap)
-    return ALEPPO_OK;
-  retire(c, *buf);
-  *buf = nullptr;
-  *cap = 0;
-  HIPCHK(c, hipMalloc(reinterpret_cast<void **>(buf), need));
-  *cap = need;
-  return ALEPPO_OK;
-}
-
 struct SalCall { // a checked call: the parameters, the grid and where the samples are
   aleppo_saliency_config k;
   SalTables tb;
@@ -143,9 +131,9 @@ void sal_perturb_chunk(aleppo_ctx *c, const SalCall &call, SalBlurred *held, lon
 }
 // the staging both calls need: `pairs` pairs in chunks of at most maxB, `per` of them per sample, n samples
 int sal_ensure_staging(aleppo_ctx *c, long pairs, int per, long n) {
-  if (int rc = sal_grow(c, &c->sal_blur, &c->sal_blur_cap, (size_t)sal_blur_room(c, pairs, per, n) * FRAME_PIX * 4))
-    return rc;
-  return sal_grow(c, &c->sal_stage, &c->sal_stage_cap, (size_t)std::min(c->maxB, pairs) * FRAME_PIX * 4);
+  HIPCHK(c, grow(c, &c->sal_blur, &c->sal_blur_cap, (size_t)sal_blur_room(c, pairs, per, n) * FRAME_PIX * 4, ALLOC_RAW));
+  HIPCHK(c, grow(c, &c->sal_stage, &c->sal_stage_cap, (size_t)std::min(c->maxB, pairs) * FRAME_PIX * 4, ALLOC_RAW));
+  return ALEPPO_OK;
 }
 const SampleMap SAL_STAGE_MAP{1, (long)FRAME_PIX, 0, 0, 0}; // pair q of a chunk at sal_stage + q * 7056
 } // namespace
@@ -165,10 +153,8 @@ extern "C" int aleppo_saliency(aleppo_ctx *c, const uint8_t *observations, int64
     return rc;
   if (int rc = sal_ensure_staging(c, pairs, P, (long)n))
     return rc;
-  if (int rc = sal_grow(c, &c->sal_base, &c->sal_base_cap, (size_t)n * (A + 1) * 4))
-    return rc;
-  if (int rc = sal_grow(c, &c->sal_out, &c->sal_out_cap, (2 * (size_t)pairs + (outputs ? out_floats : 0)) * 4))
-    return rc;
+  HIPCHK(c, grow(c, &c->sal_base, &c->sal_base_cap, (size_t)n * (A + 1) * 4, ALLOC_RAW));
+  HIPCHK(c, grow(c, &c->sal_out, &c->sal_out_cap, (2 * (size_t)pairs + (outputs ? out_floats : 0)) * 4, ALLOC_RAW));
   float *base_logits = c->sal_base, *base_values = c->sal_base + (size_t)n * A;
   float *d_policy = c->sal_out, *d_value = d_policy + pairs, *d_outputs = outputs ? d_value + pairs : nullptr;
   // the unperturbed samples first: their outputs are kept in a buffer of their own
@@ -223,8 +209,7 @@ extern "C" int aleppo_saliency_perturbed(aleppo_ctx *c, const uint8_t *observati
     return rc;
   if (int rc = sal_ensure_staging(c, pairs, per, (long)n))
     return rc;
-  if (int rc = sal_grow(c, &c->sal_u8, &c->sal_u8_cap, (size_t)std::min(c->maxB, pairs) * STACK))
-    return rc;
+  HIPCHK(c, grow(c, &c->sal_u8, &c->sal_u8_cap, (size_t)std::min(c->maxB, pairs) * STACK, ALLOC_RAW));
   std::vector<uint8_t> host((size_t)pairs * STACK); // a failed call writes nothing
   SalBlurred held;
   const long room = sal_blur_room(c, pairs, per, (long)n);

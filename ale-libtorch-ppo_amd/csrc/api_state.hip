@@ -68,7 +68,7 @@ extern "C" int aleppo_state_digest(aleppo_ctx *c, uint64_t out[ALEPPO_DIGEST_COU
   if (int rc = ensure_rs_storage(c)) // (before the option was ever used: the initial state)
     return rc;
   if (!c->dg_out)
-    HIPCHK(c, dalloc(&c->dg_out, ALEPPO_DIGEST_COUNT * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, dalloc(c, &c->dg_out, ALEPPO_DIGEST_COUNT * sizeof(unsigned long long)));
   launch_state_digest(c->stream, c->P, c->M1, c->M2, c->L, c->adam_step, c->obs, c->T + 1, current_slot(c), c->E,
                       c->rng_counter, c->rs_blk, c->rs_g[c->rs_cur], c->dg_out);
   HIPCHK(c, hipGetLastError());
@@ -97,7 +97,7 @@ extern "C" int aleppo_tensor_stats(aleppo_ctx *c, int sections, double *out, siz
                    "tensor_stats: the step section needs an aleppo_train on this context with no aleppo_load_params / "
                    "aleppo_import_optimizer since");
   if (!c->ts_scratch)
-    HIPCHK(c, dalloc(&c->ts_scratch, tensor_stats_scratch_bytes(c->L), c->stream));
+    HIPCHK(c, dalloc(c, &c->ts_scratch, tensor_stats_scratch_bytes(c->L)));
   const double *dev = nullptr;
   launch_tensor_stats(c->stream, c->P, c->G, c->M1, c->M2, c->L, sections, step ? last_clip_coef(c) : 1.0f, c->ts_sched[0],
                       c->ts_sched[1], c->cfg.adam_eps, c->ts_scratch, &dev);

@@ -7,68 +7,43 @@ using namespace aleppo;
 // ------------------------------------------------------------------ update
 int aleppo::ensure_metric_storage(aleppo_ctx *c, int epochs, int M, long B) {
   const size_t need = (size_t)epochs * M * B;
-  if (need > c->metric_cap) {
-    retire(c, c->metric_ps); // (never hipFree before aleppo_destroy: see dalloc)
-    c->metric_ps = nullptr;
-    HIPCHK(c, dalloc(&c->metric_ps, need * 7 * 4, c->stream)); // aleppo_metric_field 0-6
-    c->metric_cap = need;
-  }
+  HIPCHK(c, grow(c, &c->metric_ps, &c->metric_cap, need, need * 7 * 4, ALLOC_ZEROED)); // aleppo_metric_field 0-6
   const size_t nm = (size_t)epochs * M;
   if (nm > c->metric_red_cap) {
-    retire(c, c->metric_red);
-    retire(c, c->grad_norms);
-    retire(c, c->adam_sched);
-    retire(c, c->advn_part);
-    retire(c, c->advn_stats);
-    retire_host(c, c->h_metric_red);
-    retire_host(c, c->h_adam_sched);
-    retire_host(c, c->h_advn_stats);
-    c->metric_red = c->grad_norms = c->h_metric_red = c->adam_sched = c->h_adam_sched = nullptr;
-    c->advn_part = nullptr;
-    c->advn_stats = c->h_advn_stats = nullptr;
-    c->last_advn = false; // (its statistics went with the old buffer)
+    c->metric_red_cap = 0; // (the group grows together: until all of it has, the capacity claims nothing)
+    c->last_advn = false;  // (its statistics went with the old buffer)
     c->last_kl = false;   // (and so did the KL means)
-    HIPCHK(c, dalloc(&c->metric_red, nm * METRIC_REC * 4, c->stream));
-    HIPCHK(c, dalloc(&c->grad_norms, nm * 4, c->stream));
-    HIPCHK(c, dalloc(&c->adam_sched, nm * 2 * 4, c->stream));
-    HIPCHK(c, dalloc(&c->advn_part, nm * 4 * 8, c->stream));  // ALEPPO_OPT_ADV_NORM_MINIBATCH (n, S, Q, 0) per minibatch
-    HIPCHK(c, dalloc(&c->advn_stats, nm * 4 * 4, c->stream)); // ... and (mean_f, inv_f, std, 0)
-    HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_metric_red), nm * (METRIC_REC + 1) * 4,
+    HIPCHK(c, dalloc(c, &c->metric_red, nm * METRIC_REC * 4));
+    HIPCHK(c, dalloc(c, &c->grad_norms, nm * 4));
+    HIPCHK(c, dalloc(c, &c->adam_sched, nm * 2 * 4));
+    HIPCHK(c, dalloc(c, &c->advn_part, nm * 4 * 8));  // ALEPPO_OPT_ADV_NORM_MINIBATCH (n, S, Q, 0) per minibatch
+    HIPCHK(c, dalloc(c, &c->advn_stats, nm * 4 * 4)); // ... and (mean_f, inv_f, std, 0)
+    HIPCHK(c, halloc(c, &c->h_metric_red, nm * (METRIC_REC + 1) * 4,
                             hipHostMallocDefault)); // records, then the grad norms
-    HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_adam_sched), nm * 2 * 4, hipHostMallocDefault));
-    HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_advn_stats), nm * 4 * 4, hipHostMallocDefault));
+    HIPCHK(c, halloc(c, &c->h_adam_sched, nm * 2 * 4, hipHostMallocDefault));
+    HIPCHK(c, halloc(c, &c->h_advn_stats, nm * 4 * 4, hipHostMallocDefault));
     c->metric_red_cap = nm;
   }
   return ALEPPO_OK;
 }
 
 // ALEPPO_OPT_MINIBATCH_SHUFFLE: order + gathered planes for epochs x N samples, mask counts and round keys per epoch / minibatch
-// (grown together, like the metric storage; never freed before aleppo_destroy)
+// (grown together, like the metric storage)
 static int ensure_shuffle_storage(aleppo_ctx *c, int epochs, long N) {
   const size_t ns = (size_t)epochs * N;
   if (ns > c->shuf_cap || epochs > c->shuf_epochs_cap) {
-    for (void *p : {(void *)c->order, (void *)c->act_p, c->oldlp_p, c->adv_p, c->ret_p, c->val_p, (void *)c->mask_p,
-                    (void *)c->mask_counts_ep, (void *)c->shuf_keys})
-      retire(c, p);
-    retire_host(c, c->h_shuf_keys);
-    c->order = nullptr;
-    c->act_p = nullptr;
-    c->oldlp_p = c->adv_p = c->ret_p = c->val_p = nullptr;
-    c->mask_p = nullptr;
-    c->mask_counts_ep = nullptr;
-    c->shuf_keys = c->h_shuf_keys = nullptr;
     c->shuf_cap = 0;
     c->shuf_epochs_cap = 0;
-    HIPCHK(c, dalloc(&c->order, ns * 4, c->stream));
-    HIPCHK(c, dalloc(&c->act_p, ns * 4, c->stream));
-    HIPCHK(c, dalloc(&c->oldlp_p, ns * c->A * c->rsz, c->stream));
-    HIPCHK(c, dalloc(&c->adv_p, ns * c->rsz, c->stream));
-    HIPCHK(c, dalloc(&c->ret_p, ns * c->rsz, c->stream));
-    HIPCHK(c, dalloc(&c->val_p, ns * c->rsz, c->stream));
-    HIPCHK(c, dalloc(&c->mask_p, ns, c->stream));
-    HIPCHK(c, dalloc(&c->mask_counts_ep, ns * 4, c->stream)); // (epochs * M <= epochs * N counts)
-    HIPCHK(c, dalloc(&c->shuf_keys, (size_t)epochs * 16, c->stream));
-    HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_shuf_keys), (size_t)epochs * 16, hipHostMallocDefault));
+    HIPCHK(c, dalloc(c, &c->order, ns * 4));
+    HIPCHK(c, dalloc(c, &c->act_p, ns * 4));
+    HIPCHK(c, dalloc(c, &c->oldlp_p, ns * c->A * c->rsz));
+    HIPCHK(c, dalloc(c, &c->adv_p, ns * c->rsz));
+    HIPCHK(c, dalloc(c, &c->ret_p, ns * c->rsz));
+    HIPCHK(c, dalloc(c, &c->val_p, ns * c->rsz));
+    HIPCHK(c, dalloc(c, &c->mask_p, ns));
+    HIPCHK(c, dalloc(c, &c->mask_counts_ep, ns * 4)); // (epochs * M <= epochs * N counts)
+    HIPCHK(c, dalloc(c, &c->shuf_keys, (size_t)epochs * 16));
+    HIPCHK(c, halloc(c, &c->h_shuf_keys, (size_t)epochs * 16, hipHostMallocDefault));
     c->shuf_cap = ns;
     c->shuf_epochs_cap = epochs;
   }
@@ -79,16 +54,12 @@ static int ensure_shuffle_storage(aleppo_ctx *c, int epochs, long N) {
 // plane, as large as one field of metric_ps (regrown with it; the graph key holds its address)
 static int ensure_kl_storage(aleppo_ctx *c) {
   if (!c->kl_beta) {
-    HIPCHK(c, dalloc(&c->kl_beta, 16, c->stream));
-    HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_kl_beta), 16, hipHostMallocDefault));
+    HIPCHK(c, dalloc(c, &c->kl_beta, 16));
+    HIPCHK(c, halloc(c, &c->h_kl_beta, 16, hipHostMallocDefault));
   }
   if (c->kl_cap < c->metric_cap) {
-    retire(c, c->kl_ps);
-    c->kl_ps = nullptr;
-    c->kl_cap = 0;
     c->last_kl = false;
-    HIPCHK(c, dalloc(&c->kl_ps, c->metric_cap * 4, c->stream));
-    c->kl_cap = c->metric_cap;
+    HIPCHK(c, grow(c, &c->kl_ps, &c->kl_cap, c->metric_cap, c->metric_cap * 4, ALLOC_ZEROED));
   }
   return ALEPPO_OK;
 }
@@ -96,7 +67,7 @@ static int ensure_kl_storage(aleppo_ctx *c) {
 // ALEPPO_OPT_VALUE_CLIP: the env-major old-values plane, RT [E*T] (allocated on first use, never moved: graphs bake it)
 int aleppo::ensure_val_storage(aleppo_ctx *c) {
   if (!c->val_n)
-    HIPCHK(c, dalloc(&c->val_n, (size_t)c->N * c->rsz, c->stream));
+    HIPCHK(c, dalloc(c, &c->val_n, (size_t)c->N * c->rsz));
   return ALEPPO_OK;
 }
 

@@ -244,10 +244,10 @@ struct Ctx {
   // ---- profiling ----
   Tuning tune;
   hipError_t async_err = hipSuccess; // first failure of a call whose status could not be returned on the spot
-  // ---- boundary staging (aleppo_set_batch / aleppo_forward / aleppo_read_batch): grown on demand and never freed before
-  // aleppo_destroy - hipFree / hipHostFree wait for EVERY stream of the device, including another context's stream
-  // parked behind its release word, so no entry point but destroy calls them
-  std::vector<void *> retired, retired_host;
+  // ---- every device / pinned-host allocation of the context (api_internal.hpp, memory): aleppo_destroy frees these two
+  // registries, and nothing is freed anywhere else
+  std::vector<void *> owned_dev, owned_host;
+  // ---- boundary staging (aleppo_set_batch / aleppo_forward / aleppo_read_batch), grown on demand
   void *rb_tmp[2] = {nullptr, nullptr}; // aleppo_read_batch scratch
   size_t rb_cap[2] = {0, 0};
   uint8_t *stage_u8 = nullptr;   // NCHW uint8 observations as uploaded
@@ -268,7 +268,7 @@ struct Ctx {
   // ---- aleppo_recycle_units / aleppo_recycle_dormant: the unit mask, uint8 [160 + H] (allocated on first use)
   uint8_t *rc_mask = nullptr;
   // ---- aleppo_saliency / aleppo_saliency_perturbed: nothing below is allocated, and nothing is enqueued for it, on a context
-  // that never calls them; each buffer is allocated on first use, grown on demand like stage_obs and retired like it
+  // that never calls them; each buffer is allocated on first use and grown on demand like stage_obs
   uint32_t *sal_blur = nullptr;  // packed blurred stacks of the samples one forward chunk touches
   uint32_t *sal_stage = nullptr; // packed perturbed stacks of one forward chunk (at most maxB)
   float *sal_base = nullptr;     // [n][A] logits, then [n] values of the unperturbed samples

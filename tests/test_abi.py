@@ -194,3 +194,32 @@ def test_library_reads_only_the_documented_environment():
         ablation |= _env_names(src) - _env_names(unguarded)
     assert default == DOCUMENTED_ENV, sorted(default ^ DOCUMENTED_ENV)
     assert ablation == ABLATION_ENV, sorted(ablation ^ ABLATION_ENV)
+
+
+# Who may allocate or free: a context's memory goes through the ownership helpers of api_core.hip (which register every
+# pointer for aleppo_destroy) and nothing else in the library frees - hipFree / hipHostFree wait for every stream of the
+# device.  api_core.hip also holds aleppo_host_alloc / aleppo_host_free, the caller's memory; the other two
+# are process-wide allocations no context owns.  A feature that allocates behind the registry's back fails here.
+MEMORY_CALLS = {
+    "api_core.hip": {"hipMalloc(": 1, "hipHostMalloc(": 2, "hipFree(": 1, "hipHostFree(": 2},
+    "api_ops.hip": {"hipMalloc(": 1},           # the stateless operators' arena
+    "conv_patch_launch.hip": {"hipMalloc(": 1},  # the per-device 16 KB scratch
+}
+
+
+def test_only_the_ownership_helpers_allocate_or_free():
+    import glob
+    csrc = os.path.join(ROOT, "ale-libtorch-ppo_amd", "csrc")
+    paths = sorted(p for ext in ("*.hip", "*.hpp", "*.inc") for p in glob.glob(os.path.join(csrc, ext)))
+    assert len(paths) > 30
+    found = {}
+    for path in paths:
+        src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+        src = re.sub(r"//[^\n]*", "", src)
+        counts = {tok: len(re.findall(r"\b" + re.escape(tok), src))
+                  for tok in ("hipMalloc(", "hipHostMalloc(", "hipFree(", "hipHostFree(")}
+        counts = {tok: n for tok, n in counts.items() if n}
+        if counts:
+            found[os.path.basename(path)] = counts
+        assert not re.search(r"\bretire(_host)?\(", src), path  # outgrown buffers just stay in the registry
+    assert found == MEMORY_CALLS, found
