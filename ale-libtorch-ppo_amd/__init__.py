@@ -80,6 +80,9 @@ RECYCLE_COUNTS = 5
 RECYCLE_CONV1, RECYCLE_CONV2, RECYCLE_CONV3, RECYCLE_FC, RECYCLE_ALL = 1, 2, 4, 8, 15
 RECYCLE_LAYERS = dict(conv1=RECYCLE_CONV1, conv2=RECYCLE_CONV2, conv3=RECYCLE_CONV3, fc=RECYCLE_FC, all=RECYCLE_ALL)
 RECYCLE_KEEP_MOMENTS = 1
+# aleppo_ema_read: the statistics of the exponentially averaged parameters (Engine.ema_stats)
+EMA_STATS_COUNT = 6
+EMA_STATS = dict(updates=0, decay=1, norm=2, param_norm=3, distance=4, relative_distance=5)
 # aleppo_saliency_config's defaults (Engine.saliency / Engine.saliency_perturbed / saliency_tables)
 SALIENCY_STRIDE, SALIENCY_SIGMA_MASK, SALIENCY_SIGMA_BLUR, SALIENCY_PLANES = 5, 5.0, 3.0, 15
 # aleppo_eval_rule / aleppo_eval_field: the evaluation lanes (Engine.eval_open / eval_push_frames / eval_act / eval_read)
@@ -113,7 +116,7 @@ REC_STEP_DTYPE = np.dtype([("ordinal", "<u8"), ("action", "<i4"), ("reward", "<f
 KERNEL_CLASSES = dict(ingest=0, gae=1, head=2, adam=3, conv1_fwd=4, conv2_fwd=5, conv3_fwd=6, fc_fwd=7, fc_dgrad=8,
                       fc_wgrad=9, conv3_dgrad=10, conv3_wgrad=11, conv2_dgrad=12, conv2_wgrad=13, conv1_wgrad=14,
                       reduce=15, infer_head=16, act_fused=17, conv_fwd=18, conv_bwd=19, rec_capture=20,
-                      act_stats=21, recycle=22, sal_blur=23, sal_perturb=24, sal_score=25)
+                      act_stats=21, recycle=22, sal_blur=23, sal_perturb=24, sal_score=25, ema=26)
 
 # every symbol include/aleppo.h declares (checked by tests/test_abi.py against the header text)
 # aleppo_set_option keys (include/aleppo.h)
@@ -131,6 +134,8 @@ OPT_KL_COEF = 16  # (the value is beta's binary32 bit pattern: Engine.set_kl_coe
 OPT_CLIP_PARAM, OPT_VALUE_CLIP_RANGE, OPT_VALUE_LOSS_COEF, OPT_ENTROPY_COEF, OPT_MAX_GRAD_NORM = 17, 18, 19, 20, 21
 # return-based reward scaling in place of the clamp (Engine.set_reward_scaling); the clip as its binary32 bit pattern
 OPT_REWARD_SCALE, OPT_REWARD_SCALE_CLIP = 23, 24  # (22 is unassigned)
+# which parameters the evaluation lanes act on: 0 live, 1 the averaged set of Engine.ema_open (Engine.eval_use_averaged)
+OPT_EVAL_PARAMS = 25
 HYPER_OPTIONS = dict(clip_param=OPT_CLIP_PARAM, value_clip_range=OPT_VALUE_CLIP_RANGE,
                      value_loss_coef=OPT_VALUE_LOSS_COEF, entropy_coef=OPT_ENTROPY_COEF,
                      max_grad_norm=OPT_MAX_GRAD_NORM)
@@ -163,6 +168,7 @@ EXPORTS = [
     "aleppo_tensor_stats",
     "aleppo_forward_activations", "aleppo_activation_stats",
     "aleppo_recycle_units", "aleppo_recycle_dormant",
+    "aleppo_ema_open", "aleppo_ema_update", "aleppo_ema_read", "aleppo_ema_export", "aleppo_ema_import",
     "aleppo_saliency_tables", "aleppo_saliency", "aleppo_saliency_perturbed",
     "aleppo_env_open", "aleppo_env_rollout", "aleppo_env_export_state", "aleppo_env_import_state", "aleppo_env_read",
     "aleppo_eval_env_open", "aleppo_eval_env_run", "aleppo_eval_env_export_state", "aleppo_eval_env_import_state",
@@ -441,6 +447,7 @@ class Engine:
         self._act_ptr = C.POINTER(C.c_int64)()
         self._act_out = C.byref(self._act_ptr)
         self.actions = None  # view of the pinned action buffer, valid after the first act
+        self._ema_open = False  # ema_open has succeeded (run_state carries the average only then)
 
     def close(self):
         if getattr(self, "_ctx", None):
@@ -509,12 +516,55 @@ class Engine:
         sd = self.state_dict()
         sd["reward_scale"] = self.reward_scale_state()
         sd["rollout"] = self.rollout_state()
+        if self._ema_open:  # (only while the average is open: the keys other callers see stay the same)
+            flat, updates = self.ema_params()
+            sd["ema"] = dict(params=flat, updates=np.int64(updates))
         return sd
 
     def load_run_state(self, sd):
         """what run_state returned"""
         self.load_state_dict(sd)
         self.load_rollout_state(sd["rollout"])
+        if "ema" in sd:
+            if not self._ema_open:
+                self.ema_open()
+            self.load_ema(sd["ema"]["params"], int(sd["ema"]["updates"]))
+
+    # -- exponentially averaged parameters --
+    def ema_open(self):
+        """aleppo_ema_open: allocate the averaged parameters on first use and (re)start them at the live parameters with
+        updates = 0"""
+        self._c(lib().aleppo_ema_open(self._ctx))
+        self._ema_open = True
+
+    def ema_update(self, decay):
+        """aleppo_ema_update: average = decay * average + (1 - decay) * parameters, three fp32 operations per element, on
+        the device; enqueued, not waited for"""
+        self._c(lib().aleppo_ema_update(self._ctx, C.c_double(decay)))
+
+    def ema_stats(self):
+        """aleppo_ema_read: {"updates", "decay", "norm", "param_norm", "distance", "relative_distance"} -> float, as the
+        last open / update / import left them"""
+        out = np.zeros(EMA_STATS_COUNT, np.float64)
+        self._c(lib().aleppo_ema_read(self._ctx, _ptr(out)))
+        return {name: float(out[i]) for name, i in EMA_STATS.items()}
+
+    def ema_params(self):
+        """aleppo_ema_export: (the averaged parameters as flat float32 in libtorch parameters() order, updates)"""
+        out = np.zeros(self.param_count, np.float32)
+        updates = C.c_int64()
+        self._c(lib().aleppo_ema_export(self._ctx, _ptr(out), C.c_size_t(out.size), C.byref(updates)))
+        return out, int(updates.value)
+
+    def load_ema(self, flat, updates=0):
+        """aleppo_ema_import: what ema_params returned"""
+        flat = _f32(flat).ravel()
+        self._c(lib().aleppo_ema_import(self._ctx, _ptr(flat), C.c_size_t(flat.size), C.c_int64(int(updates))))
+
+    def eval_use_averaged(self, on):
+        """ALEPPO_OPT_EVAL_PARAMS: the evaluation lanes (eval_act, eval_env_run) act on the averaged parameters (True) or
+        on the live ones (False, the default); needs ema_open first"""
+        self.set_option(OPT_EVAL_PARAMS, 1 if on else 0)
 
     def state_digest(self):
         """aleppo_state_digest: {"params", "optimizer", "rollout", "reward_scale"} -> int, the 64-bit words of aleppo.h,

@@ -513,10 +513,13 @@ extern "C" int aleppo_load_params(aleppo_ctx *c, const float *flat, size_t count
   c->ts_step_valid = false; // (aleppo_tensor_stats: the last step can no longer be recomputed)
   c->pre_acted = -1;
   refresh_compute_copies(c);
+  if (c->ema_on) // the average restarts at the loaded parameters, as Adam does
+    if (int rc = ema_restart(c))
+      return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return ALEPPO_OK;
 }
-static int export_flat(aleppo_ctx *c, const float *dev, float *flat, size_t count) {
+int aleppo::export_flat(aleppo_ctx *c, const float *dev, float *flat, size_t count) {
   if (!flat || count != c->L.reference_count())
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "export: wrong element count");
   std::vector<float> tmp(c->L.total());
@@ -626,7 +629,8 @@ extern "C" int aleppo_set_option(aleppo_ctx *c, int option, int value) {
                          option == ALEPPO_OPT_MAX_GRAD_NORM;
   // (the two reward-scaling options are read by aleppo_finish_rollout alone: the update does not see them)
   const bool rollout_opt = option == ALEPPO_OPT_REWARD_SCALE || option == ALEPPO_OPT_REWARD_SCALE_CLIP;
-  if (option != ALEPPO_OPT_KL_COEF && !hyper_opt && !rollout_opt) {
+  // (nor does ALEPPO_OPT_EVAL_PARAMS, which the evaluation lanes read alone)
+  if (option != ALEPPO_OPT_KL_COEF && !hyper_opt && !rollout_opt && option != ALEPPO_OPT_EVAL_PARAMS) {
     c->graph_key = Ctx::GraphKey();
     c->warm_key = Ctx::GraphKey();
   }
@@ -703,6 +707,13 @@ extern "C" int aleppo_set_option(aleppo_ctx *c, int option, int value) {
       c->hyper.c_e = f;
     else
       c->hyper.max_norm = f;
+  } else if (option == ALEPPO_OPT_EVAL_PARAMS) {
+    if (value != 0 && value != 1)
+      return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT,
+                     "ALEPPO_OPT_EVAL_PARAMS: 0 (the live parameters) or 1 (the averaged set of aleppo_ema_open)");
+    if (value == 1 && !c->ema_on)
+      return set_err(c, ALEPPO_ERR_RUNTIME, "ALEPPO_OPT_EVAL_PARAMS: no averaged parameters: call aleppo_ema_open first");
+    c->eval_averaged = value != 0;
   } else if (option == ALEPPO_OPT_UPDATE_GRAPH)
     c->update_graph = value != 0;
   else if (option == ALEPPO_OPT_GATE_TIMEOUT_MS)
@@ -740,6 +751,7 @@ extern "C" int aleppo_get_option(aleppo_ctx *c, int option, int64_t *value) {
   case ALEPPO_OPT_GATE_TIMEOUT_MS: *value = (int64_t)(c->gate_timeout_ticks / 100000ull); break;
   case ALEPPO_OPT_REWARD_SCALE: *value = c->reward_scale; break;
   case ALEPPO_OPT_REWARD_SCALE_CLIP: *value = (int64_t)float_bits(c->reward_scale_clip); break;
+  case ALEPPO_OPT_EVAL_PARAMS: *value = c->eval_averaged; break;
   default: return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "unknown option");
   }
   return ALEPPO_OK;

@@ -121,9 +121,11 @@ int aleppo::eval_act_enqueue(aleppo_ctx *c, int rule, float kparam, const float 
   const int L = c->ev_L;
   int64_t *pinned_dev = nullptr;
   HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(&pinned_dev), c->ev_h_actions, 0));
-  // the rollout's acting forward at L samples on the lanes' stacks, into the lanes' scratch
-  act_forward(c, c->ev_obs, eval_map(), c->ev_a1, c->ev_a2, c->ev_a3, c->ev_hpart, L, false);
-  launch_eval_head(c->stream, c->ev_hpart, Pf(c, P_BFC), Pf(c, P_WH), Pf(c, P_BH), dn, c->cfg.seed ^ EVAL_KEY_DOMAIN,
+  // the rollout's acting forward at L samples on the lanes' stacks, into the lanes' scratch, on the live parameters or -
+  // ALEPPO_OPT_EVAL_PARAMS = 1 - on the averaged set of aleppo_ema_open
+  const ParamView pv = eval_view(c);
+  act_forward(c, pv, c->ev_obs, eval_map(), c->ev_a1, c->ev_a2, c->ev_a3, c->ev_hpart, L, false);
+  launch_eval_head(c->stream, c->ev_hpart, Pf(c, pv, P_BFC), Pf(c, pv, P_WH), Pf(c, pv, P_BH), dn, c->cfg.seed ^ EVAL_KEY_DOMAIN,
                    c->ev_counter, rule, kparam, c->ev_logits, c->ev_values, c->ev_actions, pinned_dev, c->ev_d_done,
                    c->ev_ticket + 1, L, c->H, c->A);
   HIPCHK(c, hipGetLastError());

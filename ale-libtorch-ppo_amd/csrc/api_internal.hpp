@@ -1,5 +1,5 @@
 // api_internal.hpp - what the C ABI's translation units share (api_core.hip, api_rollout.hip, api_train.hip,
-// api_batch.hip, api_eval.hip, api_eval_env.hip, api_env.hip, api_rec.hip, api_state.hip, api_acts.hip, api_recycle.hip, api_saliency.hip, api_ops.hip): the entry-point guard macros, the memory
+// api_batch.hip, api_eval.hip, api_eval_env.hip, api_env.hip, api_rec.hip, api_state.hip, api_acts.hip, api_recycle.hip, api_ema.hip, api_saliency.hip, api_ops.hip): the entry-point guard macros, the memory
 // ownership helpers (dalloc / halloc / grow over ctx_alloc / ctx_host_alloc / ctx_grow) and the other host-side helpers.
 // Host code only; the helpers are defined in api_core.hip unless noted.
 #pragma once
@@ -115,12 +115,31 @@ inline void *rp(const Ctx *c, void *plane, size_t i) { return static_cast<char *
 inline const void *Pcw(const Ctx *c, ParamId id) {
   return static_cast<const char *>(c->Pc) + c->L.off[id] * tsz(c);
 }
+// The parameter set an acting forward reads: the fp32 vector (biases, heads) and its compute-type copy (convolution and fc
+// weights), both in the internal layout.  The rollout's acting and the update use the live view; the evaluation lanes
+// (eval_act_enqueue) use eval_view - the averaged set of aleppo_ema_open under ALEPPO_OPT_EVAL_PARAMS = 1.
+struct ParamView {
+  const float *P;
+  const void *Pc;
+};
+inline ParamView live_view(const Ctx *c) { return ParamView{c->P, c->Pc}; }
+inline ParamView eval_view(const Ctx *c) { return c->eval_averaged ? ParamView{c->Pe, c->Pec} : live_view(c); }
+inline const float *Pf(const Ctx *c, const ParamView &v, ParamId id) { return v.P + c->L.off[id]; }
+inline const void *Pcw(const Ctx *c, const ParamView &v, ParamId id) {
+  return static_cast<const char *>(v.Pc) + c->L.off[id] * tsz(c);
+}
 
 // conv stack forward for ns samples addressed by map -> c->h
 // returns the number of split-K partial slabs of h (1 unless max_parts allows the pipelined fc kernel to split)
 int net_forward(Ctx *c, const uint32_t *obs, SampleMap map, long ns, int max_parts = 1);
 
 void refresh_compute_copies(Ctx *c);
+// api_core.hip, also for aleppo_ema_export (api_ema.hip): a vector in the internal layout (device) -> the caller's flat
+// array in the reference's order, with aleppo_export_params' count check; waits for the stream
+int export_flat(aleppo_ctx *c, const float *dev, float *flat, size_t count);
+// api_ema.hip, also for aleppo_load_params: the average restarts at the live parameters (Pe = P, Pec = Pc, updates 0, the
+// statistics of that state), enqueued on the main stream.  Call only where c->ema_on or aleppo_ema_open has allocated.
+int ema_restart(aleppo_ctx *c);
 
 inline uint32_t float_bits(float f) {
   uint32_t u;
@@ -165,8 +184,8 @@ int act_enqueue(aleppo_ctx *c, const float *noise, int slot);
 // api_rollout.hip, also for the evaluation lanes (api_eval.hip): the acting forward up to the head (patch kernels, or
 // conv1 -> conv2 -> conv3; then the split-K fc) at n samples into the given scratch, and where a kernel reads the
 // caller's frames (*dev_frames; null for ALEPPO_HOST, which the caller stages itself)
-void act_forward(aleppo_ctx *c, uint32_t *obs, SampleMap map, void *a1, void *a2, void *a3, float *hpart, int n,
-                 bool profiled);
+void act_forward(aleppo_ctx *c, const ParamView &pv, uint32_t *obs, SampleMap map, void *a1, void *a2, void *a3,
+                 float *hpart, int n, bool profiled);
 int resolve_frames(aleppo_ctx *c, const uint8_t *frames, int location, const uint8_t **dev_frames);
 int step_enqueue(aleppo_ctx *c, const uint8_t *df, int kind, int location, const StartBits *sb, const uint8_t *start_mapped,
                  int t, const uint8_t *start_device = nullptr);

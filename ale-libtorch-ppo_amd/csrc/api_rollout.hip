@@ -6,9 +6,10 @@ using namespace aleppo;
 
 // ------------------------------------------------------------------ rollout
 // The acting forward at n samples of obs addressed by map, into the caller's scratch: conv stack + split-K fc; the head
-// kernel finishes the fc reduction.  profiled: the rollout's launches are bracketed for --profile, evaluation's are not.
-void aleppo::act_forward(aleppo_ctx *c, uint32_t *obs, SampleMap map, void *a1, void *a2, void *a3, float *hpart, int n,
-                         bool profiled) {
+// kernel finishes the fc reduction.  pv: the parameter set it reads (the rollout: live_view; the evaluation lanes:
+// eval_view).  profiled: the rollout's launches are bracketed for --profile, evaluation's are not.
+void aleppo::act_forward(aleppo_ctx *c, const ParamView &pv, uint32_t *obs, SampleMap map, void *a1, void *a2, void *a3,
+                         float *hpart, int n, bool profiled) {
   const auto begin = [&](int cls) {
     if (profiled)
       prof_begin(c, cls);
@@ -19,29 +20,29 @@ void aleppo::act_forward(aleppo_ctx *c, uint32_t *obs, SampleMap map, void *a1, 
   };
   if (c->prec == ALEPPO_BF16 && use_patch_kernels()) { // one launch: a1/a2 never leave LDS
     begin(ALEPPO_K_CONV1_FWD);
-    patch_act_convs(c->stream, obs, map, Pcw(c, P_W1), Pf(c, P_B1), Pcw(c, P_W2), Pf(c, P_B2), Pcw(c, P_W3),
-                    Pf(c, P_B3), a3, n);
+    patch_act_convs(c->stream, obs, map, Pcw(c, pv, P_W1), Pf(c, pv, P_B1), Pcw(c, pv, P_W2), Pf(c, pv, P_B2),
+                    Pcw(c, pv, P_W3), Pf(c, pv, P_B3), a3, n);
     end(ALEPPO_K_CONV1_FWD);
   } else {
     begin(ALEPPO_K_CONV1_FWD);
-    conv1_fwd(c->stream, c->prec, obs, map, Pcw(c, P_W1), Pf(c, P_B1), a1, n);
+    conv1_fwd(c->stream, c->prec, obs, map, Pcw(c, pv, P_W1), Pf(c, pv, P_B1), a1, n);
     end(ALEPPO_K_CONV1_FWD);
     begin(ALEPPO_K_CONV2_FWD);
-    conv2_fwd(c->stream, c->prec, a1, Pcw(c, P_W2), Pf(c, P_B2), a2, n);
+    conv2_fwd(c->stream, c->prec, a1, Pcw(c, pv, P_W2), Pf(c, pv, P_B2), a2, n);
     end(ALEPPO_K_CONV2_FWD);
     begin(ALEPPO_K_CONV3_FWD);
-    conv3_fwd(c->stream, c->prec, a2, Pcw(c, P_W3), Pf(c, P_B3), a3, n);
+    conv3_fwd(c->stream, c->prec, a2, Pcw(c, pv, P_W3), Pf(c, pv, P_B3), a3, n);
     end(ALEPPO_K_CONV3_FWD);
   }
   begin(ALEPPO_K_FC_FWD);
-  fc_fwd_splitk(c->stream, c->prec, a3, Pcw(c, P_WFC), hpart, n, c->H);
+  fc_fwd_splitk(c->stream, c->prec, a3, Pcw(c, pv, P_WFC), hpart, n, c->H);
   end(ALEPPO_K_FC_FWD);
 }
 
 static int do_act(aleppo_ctx *c, const float *noise, int slot, void *logits_dst, void *values_dst, int *actions_dst,
                   bool publish) {
   if (c->pre_acted != slot)
-    act_forward(c, c->obs, slot_map(c, slot), c->a1, c->a2, c->a3, c->hpart, c->E, true);
+    act_forward(c, live_view(c), c->obs, slot_map(c, slot), c->a1, c->a2, c->a3, c->hpart, c->E, true);
   c->pre_acted = -1; // (consumed; a3 / hpart are scratch again)
   const float *dn = nullptr;
   if (noise) { // (two staging halves: with a gated replay the next slot is enqueued before this copy has run)

@@ -267,6 +267,14 @@ struct Ctx {
   void *as_scratch = nullptr;
   // ---- aleppo_recycle_units / aleppo_recycle_dormant: the unit mask, uint8 [160 + H] (allocated on first use)
   uint8_t *rc_mask = nullptr;
+  // ---- aleppo_ema_open: the exponentially averaged parameters; nothing below is allocated, and nothing is enqueued for it,
+  // on a context that never opens them
+  bool ema_on = false;
+  float *Pe = nullptr;             // fp32, internal layout, L.total() floats (pads zero)
+  void *Pec = nullptr;             // compute copy of Pe in T (same layout); == Pe for fp32
+  double *ema_blk = nullptr;       // [EMA_MAX_BLOCKS][3] workgroup partials, then the ALEPPO_EMA_STATS_COUNT doubles
+  int64_t ema_updates = 0;
+  bool eval_averaged = false;      // ALEPPO_OPT_EVAL_PARAMS: the evaluation lanes act on (Pe, Pec)
   // ---- aleppo_saliency / aleppo_saliency_perturbed: nothing below is allocated, and nothing is enqueued for it, on a context
   // that never calls them; each buffer is allocated on first use and grown on demand like stage_obs
   uint32_t *sal_blur = nullptr;  // packed blurred stacks of the samples one forward chunk touches
@@ -516,6 +524,15 @@ void launch_sal_perturb(hipStream_t s, const uint32_t *obs, SampleMap map, const
                         uint32_t *stage);
 void launch_sal_score(hipStream_t s, const float *base_logits, const float *base_values, const float *logits,
                       const float *values, long i0, long ns, int P, int A, float *policy, float *value, float *outputs);
+// aleppo_ema_update (ema.hip).  launch_ema: the one streaming pass over the padded vector - Pe = d * Pe + w * P as three fp32
+// operations (update), Pec = (T)Pe where Pec != Pe, and one (sum Pe^2, sum P^2, sum (P - Pe)^2) partial in double per
+// workgroup into blk; update == false: the sums alone, nothing is stored to Pe / Pec (open, import).  launch_ema_final adds
+// the partials in index order and writes the ALEPPO_EMA_STATS_COUNT doubles at ema_stats(blk).
+constexpr int EMA_MAX_BLOCKS = 2048;
+inline double *ema_stats(double *blk) { return blk + (size_t)EMA_MAX_BLOCKS * 3; }
+constexpr size_t EMA_BLK_BYTES = ((size_t)EMA_MAX_BLOCKS * 3 + ALEPPO_EMA_STATS_COUNT) * sizeof(double);
+int launch_ema(hipStream_t s, bool update, const float *P, float *Pe, void *Pec, long n, float d, float w, double *blk);
+void launch_ema_final(hipStream_t s, int nblk, long long updates, float d, double *blk);
 void launch_heads_fwd(hipStream_t s, const float *h, const float *Wh, const float *bh, float *logits, float *values,
                       long n, int H, int A);
 void launch_logsoftmax_rows(hipStream_t s, const float *in, float *out, long rows, int A);

@@ -594,6 +594,56 @@ int aleppo_recycle_dormant(aleppo_ctx *ctx, const uint8_t *observations, int64_t
                            uint64_t key, int flags, uint8_t *mask_out, size_t unit_count,
                            int64_t counts[ALEPPO_RECYCLE_COUNTS]);
 
+/* Exponentially averaged parameters (an EMA of the weights: torch.optim.swa_utils.AveragedModel / torch_ema, the "EWMA
+ * policy" of Hilton, Cobbe and Schulman 2021; the reference has none): a second copy of the parameters on the device that
+ * follows the live ones by e' = decay * e + (1 - decay) * p after every update the caller chooses, and that the
+ * evaluation lanes can act on (ALEPPO_OPT_EVAL_PARAMS).  It stays out of aleppo_train entirely: the update's launch
+ * sequence and a captured update (ALEPPO_OPT_UPDATE_GRAPH) are what they were, and the learner's state - parameters,
+ * moments, step count, gradients, metrics, aleppo_state_digest - is bit-identical with and without these calls.
+ * aleppo_ema_open allocates, on first use and never later, the averaged set in the private layout (fp32, and in bf16
+ *   contexts its bf16 compute copy) and a small statistics block, then sets the average to the live parameters and
+ *   updates = 0 by device copies on the context's stream.  Called again it re-initialises the same storage the same way
+ *   (the average restarts) and allocates nothing.
+ * aleppo_ema_update(decay): decay finite and 0 <= decay < 1.  With d = (float)decay and w = (float)(1.0 - decay) (the
+ *   subtraction in double), each computed once on the host, every element of the padded vector becomes
+ *     a = d * e;  b = w * p;  e' = a + b          three fp32 operations, each rounded, no fused multiply-add
+ *   so the result is defined bit for bit: any host recomputes it from aleppo_export_params and the previous
+ *   aleppo_ema_export, decay = 0 gives exactly p, and the alignment pads stay zero.  In bf16 contexts the same pass stores
+ *   the compute copy (bf16)e', the conversion the live compute copy is made with.  updates is incremented.  One launch and
+ *   one small finalising launch on the context's main stream; the call enqueues only and never waits for the host.
+ * Statistics, accumulated in double by the same pass (one partial per workgroup, added in index order by the finalising
+ *   launch: deterministic, no atomics), ALEPPO_EMA_STATS_COUNT doubles in device memory, read by aleppo_ema_read (which
+ *   waits for the context's own stream only):
+ *     ALEPPO_EMA_UPDATES            updates since the last open / load / import (the count given to an import)
+ *     ALEPPO_EMA_DECAY              d of the last update, widened (0 before any update and after an import)
+ *     ALEPPO_EMA_NORM               sqrt(sum e'^2)
+ *     ALEPPO_EMA_PARAM_NORM         sqrt(sum p^2)
+ *     ALEPPO_EMA_DISTANCE           sqrt(sum ((double)p - (double)e')^2)
+ *     ALEPPO_EMA_RELATIVE_DISTANCE  sqrt(sum (p - e')^2 / sum p^2), 0 where sum p^2 = 0
+ *   After open and before any update they are (0, 0, |P|, |P|, 0, 0).  The sums describe the sets as they stood when the
+ *   last open / update / import was enqueued, not a later aleppo_train.
+ * aleppo_ema_export / aleppo_ema_import move the averaged set in the order and with the count checks of
+ *   aleppo_export_params / aleppo_load_params, plus the update count (import: updates >= 0); an import rebuilds the compute
+ *   copy and the statistics block.  A checkpoint that stores what export returned and imports it resumes the average bit
+ *   for bit.  aleppo_state_digest does not cover the average.
+ * Interactions: aleppo_load_params on a context with the average open re-initialises it (average = the loaded parameters,
+ *   updates 0), as it resets Adam.  aleppo_recycle_units / aleppo_recycle_dormant leave the average alone: the recycled
+ *   weights enter it like any other change, and it converges to them at the rate of decay.  Under data parallelism the
+ *   parameters are replicated bit for bit, so every rank that makes the same calls holds the same average: no call is a
+ *   collective.  aleppo_forward, the saliency maps and the activation statistics always run on the live parameters.  A
+ *   context that never calls aleppo_ema_open allocates and enqueues exactly what it did before.
+ * Errors: update / read / export / import before aleppo_ema_open: ALEPPO_ERR_RUNTIME (nothing is allocated); a decay that
+ *   is NaN, infinite, negative or >= 1, a NULL pointer, a wrong count, negative updates: ALEPPO_ERR_INVALID_ARGUMENT; a
+ *   step is armed: ALEPPO_ERR_RUNTIME.  A failed call changes nothing. */
+#define ALEPPO_EMA_STATS_COUNT 6
+enum { ALEPPO_EMA_UPDATES = 0, ALEPPO_EMA_DECAY = 1, ALEPPO_EMA_NORM = 2, ALEPPO_EMA_PARAM_NORM = 3,
+       ALEPPO_EMA_DISTANCE = 4, ALEPPO_EMA_RELATIVE_DISTANCE = 5 };
+int aleppo_ema_open(aleppo_ctx *ctx);
+int aleppo_ema_update(aleppo_ctx *ctx, double decay);
+int aleppo_ema_read(aleppo_ctx *ctx, double out[ALEPPO_EMA_STATS_COUNT]);
+int aleppo_ema_export(aleppo_ctx *ctx, float *flat, size_t count, int64_t *updates);
+int aleppo_ema_import(aleppo_ctx *ctx, const float *flat, size_t count, int64_t updates);
+
 /* Perturbation saliency maps of the policy and the value (Greydanus et al. 2018, "Visualizing and Understanding Atari
  * Agents"; the reference has none): blur the observation locally around each point of a grid, run the network on every
  * perturbed copy and score the point by how far the logits and the value move.  It needs only the forward pass the
@@ -687,7 +737,9 @@ int aleppo_eval_open(aleppo_ctx *ctx, int32_t num_lanes);
  * flag is set gets its new frame in all four positions. */
 int aleppo_eval_push_frames(aleppo_ctx *ctx, const uint8_t *frames, int frame_kind, int location,
                             const uint8_t *episode_start);
-/* Eval forward on the lanes' stacks with the parameters as they stand (after the last aleppo_train / aleppo_load_params):
+/* Eval forward on the lanes' stacks with the parameters as they stand (after the last aleppo_train / aleppo_load_params) -
+ * or, under ALEPPO_OPT_EVAL_PARAMS = 1, with the averaged parameters of aleppo_ema_open as they stand, which is then what
+ * aleppo_eval_read returns and what an ALEPPO_REC_EVAL recorder records:
  * aleppo_act's acting kernels, then the evaluation head.  With z the fp32 logits:
  *   ALEPPO_EVAL_GREEDY          the lowest index of the maximum of z.  param must be 0 and noise NULL; nothing is drawn.
  *   ALEPPO_EVAL_SAMPLE          param = the temperature tau, finite and > 0 (and 1 / tau finite in fp32).  With inv = 1 / tau
@@ -1009,7 +1061,8 @@ typedef enum {
   ALEPPO_K_SAL_BLUR = 23,    /* aleppo_saliency's blur of the samples a forward chunk touches */
   ALEPPO_K_SAL_PERTURB = 24, /* ... its blend of one chunk's perturbed stacks into the staging buffer */
   ALEPPO_K_SAL_SCORE = 25,   /* ... its scoring launch, one per forward chunk */
-  ALEPPO_K_COUNT = 26
+  ALEPPO_K_EMA = 26,         /* aleppo_ema_update's streaming pass over P / the averaged set, one launch per call */
+  ALEPPO_K_COUNT = 27
 } aleppo_kernel_class;
 int aleppo_profile_enable(aleppo_ctx *ctx, int on);
 int aleppo_profile_read(aleppo_ctx *ctx, int kernel_class, double *avg_ms, int64_t *launches);
@@ -1181,10 +1234,19 @@ typedef enum {
                                       flags leaves the state as it was.  With data parallelism every rank must set the same
                                       two options (they are not exchanged, as for 17-21).  Read back: ALEPPO_F_REWARD_SCALE;
                                       checkpoint: aleppo_export_reward_scale / aleppo_import_reward_scale */
-  ALEPPO_OPT_REWARD_SCALE_CLIP = 24 /* the clip c of ALEPPO_OPT_REWARD_SCALE as the IEEE-754 binary32 BIT PATTERN, like
+  ALEPPO_OPT_REWARD_SCALE_CLIP = 24, /* the clip c of ALEPPO_OPT_REWARD_SCALE as the IEEE-754 binary32 BIT PATTERN, like
                                       ALEPPO_OPT_KL_COEF (default: the bits of 10.0f).  Valid: finite and > 0; anything else
                                       is ALEPPO_ERR_INVALID_ARGUMENT and leaves the old value in place.  Read at each
                                       aleppo_finish_rollout */
+  ALEPPO_OPT_EVAL_PARAMS = 25       /* which parameters the evaluation lanes act on.  0 (default): the live ones.  1: the
+                                      averaged set of aleppo_ema_open - every weight and bias of aleppo_eval_act's and
+                                      aleppo_eval_env_run's acting forward and of the evaluation head (the compute-type
+                                      copy for the convolution and fc weights, the fp32 set for the biases and the heads).
+                                      The rollout's acting (aleppo_act / aleppo_step / aleppo_env_rollout) and everything
+                                      in aleppo_train keep the live parameters, and a captured update stays valid.  An
+                                      ALEPPO_REC_EVAL recorder then records the AVERAGED policy's logits, values and
+                                      actions.  1 before aleppo_ema_open: ALEPPO_ERR_RUNTIME; any other value:
+                                      ALEPPO_ERR_INVALID_ARGUMENT; both leave the old value in place */
 } aleppo_option;
 int aleppo_set_option(aleppo_ctx *ctx, int option, int value);
 /* Current value of an option; for ALEPPO_OPT_UPDATE_GRAPH the number of graph launches so far (0 = every update ran

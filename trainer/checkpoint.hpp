@@ -16,7 +16,8 @@
 constexpr char CKPT_MAGIC[8] = {'A', 'L', 'E', 'P', 'P', 'O', 'C', 'K'};
 constexpr char CKPT_END[8] = {'A', 'L', 'E', 'P', 'P', 'O', 'E', 'N'};
 constexpr uint32_t CKPT_VERSION = 1;
-enum CkptSection : uint32_t { CK_PARAMS = 1, CK_OPTIMIZER = 2, CK_REWARD_SCALE = 3, CK_ROLLOUT = 4, CK_TRAINER = 5, CK_DIGEST = 6 };
+enum CkptSection : uint32_t { CK_PARAMS = 1, CK_OPTIMIZER = 2, CK_REWARD_SCALE = 3, CK_ROLLOUT = 4, CK_TRAINER = 5, CK_DIGEST = 6,
+                              CK_EMA = 7 }; // (CK_EMA is optional: written only by runs with ema_decay, ignored by runs without)
 static const char *const DIGEST_NAMES[ALEPPO_DIGEST_COUNT] = {"params", "optimizer", "rollout", "reward_scale"};
 struct CkptShape {
   uint32_t E, T, A, H, precision, world, rank, reserved;
@@ -27,6 +28,13 @@ struct Checkpoint {
   std::map<uint32_t, std::string> sections;
 };
 template <class T> static void put(std::string &out, const T &v) { out.append(reinterpret_cast<const char *>(&v), sizeof(T)); }
+// the bytes of the optional section CK_EMA: the averaged parameters (aleppo_ema_export, reference order), then u64 updates.
+// It is outside visit_checkpoint: the format version stays 1 and the files of runs without ema_decay stay byte-identical.
+static std::string ema_section(const std::vector<float> &avg, uint64_t updates) {
+  std::string s(reinterpret_cast<const char *>(avg.data()), avg.size() * sizeof(float));
+  put(s, updates);
+  return s;
+}
 // What the library exports and imports (the learner's sections and the digest) ...
 struct DeviceState {
   std::vector<float> params, exp_avg, exp_avg_sq;

@@ -65,6 +65,11 @@ struct Config {
   size_t recycle_interval = 64;
   double recycle_tau = 0.025;                // the dormancy threshold of the recycle
   int recycle_layers = ALEPPO_RECYCLE_ALL;   // ALEPPO_RECYCLE_* bits (the key: a list of conv1 / conv2 / conv3 / fc)
+  // extension: exponentially averaged parameters (aleppo_ema_open / aleppo_ema_update after every trained rollout's update)
+  bool ema_decay_set = false;  // the key was given (absent: off)
+  double ema_decay = 0;        // in [0, 1)
+  bool ema_warmup = false;     // update n (n updates so far) runs with min(ema_decay, (1 + n) / (10 + n)): TensorFlow / timm
+  bool eval_averaged = false;  // evaluation acts on the averaged parameters (ALEPPO_OPT_EVAL_PARAMS = 1)
   // extension: perturbation saliency videos of environment 0 of rank 0 (aleppo_saliency; trainer/saliency.hpp), after the
   // update of every saliency_interval-th rollout, with the grid stride and the two sigmas of aleppo_saliency_config
   bool record_saliency = false;
@@ -303,6 +308,19 @@ static Config load_config(const std::string &path) { // keys / defaults of src/b
       c.device_evaluation_steps = (size_t)steps;
     }
   }
+  c.ema_decay_set = kv.count("ema_decay") != 0;
+  if (c.ema_decay_set) { // what aleppo_ema_update would refuse is refused here ("nan" / "inf" do not parse: bad value)
+    read_key(kv, "ema_decay", c.ema_decay);
+    if (!(std::isfinite(c.ema_decay) && c.ema_decay >= 0 && c.ema_decay < 1))
+      throw std::runtime_error("ema_decay must be in [0, 1)");
+  }
+  read_key(kv, "ema_warmup", c.ema_warmup);
+  read_key(kv, "eval_averaged", c.eval_averaged);
+  for (const char *k : {"ema_warmup", "eval_averaged"})
+    if (kv.count(k) && !c.ema_decay_set) // (nothing else reads them; given as false too)
+      throw std::runtime_error(std::string(k) + " needs ema_decay");
+  if (kv.count("eval_averaged") && c.eval_interval == 0)
+    throw std::runtime_error("eval_averaged needs eval_interval > 0");
   read_key(kv, "record_evaluation", c.record_evaluation);
   if (c.record_evaluation && !c.device_evaluation)
     throw std::runtime_error("record_evaluation needs device_evaluation: true");
@@ -401,6 +419,8 @@ static HParams hparams_of(const Config &c) {
     h.numbers.emplace_back("device_evaluation_steps", (double)c.device_evaluation_steps);
   if (c.record_interval != 1)
     h.numbers.emplace_back("record_interval", (double)c.record_interval);
+  if (c.ema_decay_set)
+    h.numbers.emplace_back("ema_decay", c.ema_decay);
   h.flags = {{"record_observation", c.record_observation}, {"record_video", c.record_video},
              {"cuda_graph", c.cuda_graph}, {"deterministic", c.deterministic}};
   const std::pair<const char *, bool> when_set[] = {{"shuffle_minibatches", c.shuffle_minibatches},
@@ -414,7 +434,9 @@ static HParams hparams_of(const Config &c) {
                                                     {"reward_scaling", c.reward_scaling},
                                                     {"device_environments", c.device_environments},
                                                     {"device_evaluation", c.device_evaluation},
-                                                    {"record_evaluation", c.record_evaluation}};
+                                                    {"record_evaluation", c.record_evaluation},
+                                                    {"ema_warmup", c.ema_warmup},
+                                                    {"eval_averaged", c.eval_averaged}};
   for (const auto &f : when_set)
     if (f.second)
       h.flags.emplace_back(f.first, true);

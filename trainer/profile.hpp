@@ -42,7 +42,7 @@ public:
                                                 "fc_fwd", "fc_dgrad", "fc_wgrad", "conv3_dgrad", "conv3_wgrad",
                                                 "conv2_dgrad", "conv2_wgrad", "conv1_wgrad", "reduce", "infer_head",
                                                 "act_fused", "conv_fwd", "conv_bwd", "rec_capture", "act_stats",
-                                                "recycle", "sal_blur", "sal_perturb", "sal_score"};
+                                                "recycle", "sal_blur", "sal_perturb", "sal_score", "ema"};
     for (int k = 0; k < ALEPPO_K_COUNT; ++k) {
       double ms = 0;
       int64_t n = 0;

@@ -121,6 +121,14 @@
 // episode at an evaluation's end discarded).  record_interval: 1 (N: only episodes 1, N + 1, 2 N + 1, ... are written; every
 // step's 32-byte record is read, the frames of the other episodes never leave the device).  recorder.hpp has the formats.
 // The recorders change nothing the run computes; a library without the entry points refuses the keys at start-up.
+// ema_decay: <d> (absent: off; 0 <= d < 1: an exponentially averaged copy of the parameters - aleppo_ema_open once the
+// parameters are loaded or resumed, one aleppo_ema_update after the update of every trained rollout, never after the warm
+// rollout; ema_warmup: true runs update n, n the updates so far, with min(ema_decay, (1 + n) / (10 + n)), the TensorFlow /
+// timm rule; eval_averaged: true, needs eval_interval, evaluates the averaged policy - ALEPPO_OPT_EVAL_PARAMS = 1 - host-driven
+// or device_evaluation alike; logs ema_decay, ema_distance and ema_relative_distance per rollout; with checkpoint_path the
+// averaged parameters and their update count go into the optional section 7, which a resume with the key imports and proves
+// by exporting it again, and without which the average starts at the resumed parameters; never a collective; the two other
+// keys without ema_decay, a decay outside [0, 1) and a library without the entry points are refused at start-up).
 // Data parallelism (no reference counterpart): start one process per GPU with RANK / WORLD_SIZE / LOCAL_RANK
 // in the environment (torchrun / mpirun style).  Rank r owns the contiguous environment block
 // [r * E / W, (r + 1) * E / W) and GPU LOCAL_RANK; rank 0 creates the RCCL id, hands it to the others through the file
@@ -173,6 +181,12 @@
 // ... and the recycling of dormant units (recycle_dormant: true)
 #pragma weak aleppo_recycle_dormant
 // (record_saliency: true - aleppo_saliency is declared weak in saliency.hpp)
+// ... and the exponentially averaged parameters (ema_decay)
+#pragma weak aleppo_ema_open
+#pragma weak aleppo_ema_update
+#pragma weak aleppo_ema_read
+#pragma weak aleppo_ema_export
+#pragma weak aleppo_ema_import
 // ... and the device-resident evaluation environments (device_evaluation: true)
 #pragma weak aleppo_eval_env_open
 #pragma weak aleppo_eval_env_run
@@ -229,6 +243,7 @@ struct Run {
   bool record_evaluation() const { return cfg.record_evaluation && rank == 0; }
   int record_field() const { return cfg.record_observation ? ALEPPO_REC_F_OBSERVATIONS : ALEPPO_REC_F_FRAMES; }
   uint64_t eval_counter = 0; // device_evaluation: the evaluation counter where the host path would have left it
+  uint64_t ema_updates = 0;  // ema_decay: the average's updates so far (ema_warmup's n; resumed from the checkpoint)
   size_t first_rollout = 0, rollouts_done = 0;
   std::optional<WorkerPool> pool; // (last: its threads are joined before anything they touch goes away)
 
@@ -330,6 +345,9 @@ static void refuse_missing_entry_points(const Config &cfg) {
   if (cfg.recycle_dormant && !aleppo_recycle_dormant)
     throw std::runtime_error("recycle_dormant is set but this build's library cannot recycle units "
                              "(aleppo_recycle_dormant is missing)");
+  if (cfg.ema_decay_set && !(aleppo_ema_open && aleppo_ema_update && aleppo_ema_read && aleppo_ema_export && aleppo_ema_import))
+    throw std::runtime_error("ema_decay is set but this build's library has no averaged parameters "
+                             "(aleppo_ema_open is missing)");
   if (cfg.record_saliency && !aleppo_saliency)
     throw std::runtime_error("record_saliency is set but this build's library has no saliency maps "
                              "(aleppo_saliency is missing)");
@@ -718,6 +736,8 @@ struct Update {
   std::vector<double> act_units; // [(160 + H) * ALEPPO_ACT_UNIT_COLS] (the call fills it; only the layer table is logged)
   bool recycled = false; // recycle_dormant: this rollout is one of the interval's, recycle_counts is what it recycled
   int64_t recycle_counts[ALEPPO_RECYCLE_COUNTS] = {};
+  double ema_decay_now = 0;                       // ema_decay: the decay this rollout's aleppo_ema_update ran with ...
+  double ema_stats[ALEPPO_EMA_STATS_COUNT] = {};  // ... and the statistics it left
   explicit Update(const Run &run)
       : nmb((size_t)run.cfg.num_mini_batches), N(run.E * run.T), slots((size_t)run.cfg.num_epochs * nmb), m(slots),
         kl(slots), cf(slots), adv_std(run.cfg.minibatch_advantage_norm ? slots : 0), mean_kl(run.kl_penalty() ? slots : 0),
@@ -771,6 +791,16 @@ static void update(Run &run, size_t r, Update &u) {
       else if (d > 1.5 * cfg.kl_target && std::isfinite(2.0f * beta))
         beta *= 2.0f;
     }
+  }
+  // the averaged parameters follow every trained rollout's update (never a collective: the parameters are replicated bit for
+  // bit, so every rank computes the same average); ema_warmup: the TensorFlow / timm rule on the updates so far
+  if (cfg.ema_decay_set) {
+    Profile::Span sp(&run.prof, "aleppo_ema_update");
+    const double n = (double)run.ema_updates;
+    u.ema_decay_now = cfg.ema_warmup ? std::min(cfg.ema_decay, (1.0 + n) / (10.0 + n)) : cfg.ema_decay;
+    check(ctx, aleppo_ema_update(ctx, u.ema_decay_now));
+    run.ema_updates++;
+    check(ctx, aleppo_ema_read(ctx, u.ema_stats));
   }
   if (cfg.log_tensor_stats && run.rank == 0) { // (not a collective: every rank's answer would be the same)
     Profile::Span sp(&run.prof, "aleppo_tensor_stats");
@@ -887,6 +917,11 @@ static void log_scalars(Run &run, const EpisodeLog &log, const BatchStatistics &
     for (int k = 0; k < 4; ++k)
       logger.add_scalar(std::string("recycle/") + ACT_LAYER_NAMES[k] + "/units", step, (float)u.recycle_counts[k]);
     logger.add_scalar("recycle/total", step, (float)u.recycle_counts[4]);
+  }
+  if (cfg.ema_decay_set) { // (only with the key: the event files of existing configs stay byte-identical)
+    logger.add_scalar("ema_decay", step, (float)u.ema_decay_now);
+    logger.add_scalar("ema_distance", step, (float)u.ema_stats[ALEPPO_EMA_DISTANCE]);
+    logger.add_scalar("ema_relative_distance", step, (float)u.ema_stats[ALEPPO_EMA_RELATIVE_DISTANCE]);
   }
   for (size_t k = 0; k < run.schedules.size(); ++k) // (the values this rollout's update ran with)
     logger.add_scalar(run.schedules[k].name, step, u.hyper_now[k]);
@@ -1038,6 +1073,12 @@ static void save_checkpoint(Run &run, size_t next_rollout) {
   ck.shape = run.shape;
   CkptWriter out(ck.sections);
   visit_checkpoint(out, d, run.st);
+  if (run.cfg.ema_decay_set) { // the optional section CK_EMA: the averaged parameters in reference order, then u64 updates
+    std::vector<float> avg(n);
+    int64_t updates = 0;
+    check(ctx, aleppo_ema_export(ctx, avg.data(), n, &updates));
+    ck.sections[CK_EMA] = ema_section(avg, (uint64_t)updates);
+  }
   write_checkpoint_file(run.ckpt_file, ck);
   char line[256];
   std::snprintf(line, sizeof line, "checkpoint rollout %zu digest params=%016llx optimizer=%016llx rollout=%016llx "
@@ -1073,6 +1114,44 @@ static void resume(Run &run) { // import everything, then prove it: the device's
     }
   std::cout << "resumed from " << run.resume_file << " at rollout " << run.first_rollout << " of " << run.cfg.num_rollouts
             << ", state digest verified" << std::endl;
+}
+
+// ema_decay: open the averaged parameters once the live ones are loaded or resumed.  A resumed file's CK_EMA section is
+// imported and proved by exporting it again (the state digest does not cover the average); without the section the average
+// starts at the resumed parameters.  A section in a file resumed without the key is ignored.
+static void open_average(Run &run) {
+  aleppo_ctx *ctx = run.ctx;
+  const size_t n = run.n_params();
+  check(ctx, aleppo_ema_open(ctx));
+  if (!run.resume_file.empty()) {
+    const auto sec = run.resumed.sections.find(CK_EMA);
+    if (sec == run.resumed.sections.end()) {
+      std::cerr << "note: checkpoint " << run.resume_file << " has no averaged parameters (section " << CK_EMA
+                << "): the average starts at the resumed parameters" << std::endl;
+    } else {
+      if (sec->second.size() != n * sizeof(float) + sizeof(uint64_t))
+        throw std::runtime_error("resume: checkpoint " + run.resume_file + " is corrupt (section " + std::to_string(CK_EMA) +
+                                 " has " + std::to_string(sec->second.size()) + " bytes, expected " +
+                                 std::to_string(n * sizeof(float) + sizeof(uint64_t)) + ")");
+      std::vector<float> avg(n);
+      uint64_t updates = 0;
+      std::memcpy(avg.data(), sec->second.data(), n * sizeof(float));
+      std::memcpy(&updates, sec->second.data() + n * sizeof(float), sizeof updates);
+      if (updates > (uint64_t)INT64_MAX)
+        throw std::runtime_error("resume: checkpoint " + run.resume_file + " is corrupt (the average's update count)");
+      check(ctx, aleppo_ema_import(ctx, avg.data(), n, (int64_t)updates));
+      std::vector<float> back(n);
+      int64_t got = 0;
+      check(ctx, aleppo_ema_export(ctx, back.data(), n, &got));
+      if (ema_section(back, (uint64_t)got) != sec->second)
+        throw std::runtime_error("resume: checkpoint " + run.resume_file +
+                                 ": the averaged parameters after the import differ from the file's");
+      run.ema_updates = updates;
+      std::cout << "resumed the averaged parameters at update " << updates << ", verified" << std::endl;
+    }
+  }
+  if (run.cfg.eval_averaged) // (every evaluation, host-driven or device_evaluation, goes through the lanes' acting forward)
+    check(ctx, aleppo_set_option(ctx, ALEPPO_OPT_EVAL_PARAMS, 1));
 }
 
 // ------------------------------------------------------------------ the rollout loop, the summary line, teardown
@@ -1166,6 +1245,8 @@ int main(int argc, char **argv) {
       resume(run);
     else
       collect(run); // the warm rollout before the loop (train.cc:391-396): collected, never trained on
+    if (run.cfg.ema_decay_set)
+      open_average(run);
     train_loop(run);
     teardown(run);
     std::cout << "Success" << std::endl;
