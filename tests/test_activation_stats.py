@@ -23,6 +23,7 @@ import hashfill as hf
 import oracle_lib as orc
 import trainer_helpers
 from conftest import ROOT
+from shared_fixtures import pkg  # noqa: F401
 from __graft_entry__ import load_package
 
 TAU = 0.025
@@ -79,10 +80,7 @@ def test_header_constants_and_prototypes_match_the_python_mirror():
     pkg = load_package()
     hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "aleppo.h")).read(), flags=re.S)
 
-    def const(name):
-        m = re.search(rf"\b{name}\s*=?\s*(\d+)", hdr)
-        assert m, name
-        return int(m.group(1))
+    const = functools.partial(trainer_helpers.header_const, stripped=True)
 
     assert const("ALEPPO_ACT_UNIT_COLS") == pkg.ACT_UNIT_COLS == len(asr.UNIT_STATS) == 5
     assert const("ALEPPO_ACT_LAYER_ROWS") == len(pkg.ACT_LAYER_ROWS) == len(asr.ROWS) == 5
@@ -333,13 +331,6 @@ def test_library_without_the_symbol_refuses_the_key(tmp_path_factory, tmp_path):
 
 
 # ------------------------------------------------------------------ GPU
-@pytest.fixture(scope="module")
-def pkg():
-    p = load_package()
-    p.lib()
-    return p
-
-
 def _prec(pkg, prec):
     return pkg.FP32 if prec == "fp32" else pkg.BF16
 

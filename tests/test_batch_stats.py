@@ -16,8 +16,8 @@ import pytest
 import batch_stats_ref as br
 import hashfill as hf
 import oracle_lib as orc
-import trainer_helpers
-from trainer_helpers import debug_cfg as _debug_cfg, events as _events
+from trainer_helpers import debug_cfg as _debug_cfg, events as _events, header_const as const
+from shared_fixtures import pkg, stub_trainer, trainer  # noqa: F401
 from __graft_entry__ import load_package
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -79,11 +79,6 @@ def test_header_constants_and_python_mirror():
     pkg = load_package()
     hdr = open(os.path.join(ROOT, "include", "aleppo.h")).read()
 
-    def const(name):
-        m = re.search(rf"(?m)^\s*{name}\s*=\s*(\d+)", hdr)
-        assert m, name
-        return int(m.group(1))
-
     assert const("ALEPPO_F_BATCH_STATS") == pkg.FIELDS["batch_stats"] == 13
     m = re.search(r"(?m)^#define ALEPPO_BATCH_STATS_COUNT (\d+)", hdr)
     assert m and int(m.group(1)) == pkg.BATCH_STATS_COUNT == 10 == len(br.NAMES)
@@ -92,11 +87,6 @@ def test_header_constants_and_python_mirror():
     assert len(pkg.BATCH_STATS) == 10
     assert hasattr(pkg.Engine, "batch_stats")
     assert re.search(r"(?m)^#define ALEPPO_ABI_VERSION 2$", hdr) and pkg.ABI_VERSION == 2
-
-
-@pytest.fixture(scope="module")
-def stub_trainer(tmp_path_factory):
-    return trainer_helpers.build_stub_trainer(tmp_path_factory)
 
 
 def _scalar_bits(blob):
@@ -135,13 +125,6 @@ def test_trainer_key_with_the_stub_library(stub_trainer, tmp_path):
 
 
 # ------------------------------------------------------------------ GPU
-@pytest.fixture(scope="module")
-def pkg():
-    p = load_package()
-    p.lib()
-    return p
-
-
 class _DeviceBytes:
     """device copy of a numpy array (no torch in the test process)"""
 
@@ -424,14 +407,6 @@ def test_error_cases(pkg):
     eng.close()
     assert got["count"] == E * (T - 1)
     br.assert_close(got, stats, bounds, "after an armed step")
-
-
-@pytest.fixture(scope="module")
-def trainer():
-    from __graft_entry__ import build
-    build()
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "trainer")])
-    return os.path.join(ROOT, "trainer", "train")
 
 
 @pytest.mark.gpu

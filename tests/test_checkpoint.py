@@ -16,6 +16,7 @@ import pytest
 import checkpoint_ref as cr
 import hashfill as hf
 from conftest import ROOT
+from shared_fixtures import trainer  # noqa: F401
 from __graft_entry__ import load_package
 
 T, A = 4, 4
@@ -58,14 +59,6 @@ def test_reference_digest_of_three_words_by_hand():
 
 
 # ------------------------------------------------------------------ CPU: the trainer's keys and the file
-@pytest.fixture(scope="module")
-def trainer():
-    from __graft_entry__ import build
-    build()
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "trainer")])
-    return os.path.join(ROOT, "trainer", "train")
-
-
 @pytest.fixture(scope="module")
 def trainer_tsan():
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "trainer"), "train_tsan"])

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import hashfill as hf
+from shared_fixtures import pkg  # noqa: F401
 from __graft_entry__ import load_package
 
 E, T, H, A = 4, 8, 32, 4
@@ -22,13 +23,6 @@ LR = 2.5e-4
 SAL = dict(stride=12, sigma_mask=2.0, sigma_blur=1.0)  # G = 7
 SMALL_FIELDS = ("rewards", "logits", "advantages")    # transposed; transposed and widened; widened (fp16 planes)
 MiB = 1 << 20
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    p = load_package()
-    p.lib()
-    return p
 
 
 @functools.lru_cache(maxsize=None)

@@ -18,6 +18,8 @@ import ema_ref as er
 import hashfill as hf
 import oracle_lib as orc
 from conftest import ROOT
+import trainer_helpers
+from shared_fixtures import pkg  # noqa: F401
 from __graft_entry__ import load_package
 
 SHAPES = {"h32": (9100, 32, 4), "h96": (9200, 96, 18)}  # name: (parameter seed, H, A) - the recycle tests' two shapes
@@ -85,10 +87,7 @@ def test_header_constants_and_prototypes_match_the_python_mirror():
     pkg = load_package()
     hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "aleppo.h")).read(), flags=re.S)
 
-    def const(name):
-        m = re.search(rf"\b{name}\s*=?\s*(\d+)", hdr)
-        assert m, name
-        return int(m.group(1))
+    const = functools.partial(trainer_helpers.header_const, stripped=True)
 
     assert const("ALEPPO_EMA_STATS_COUNT") == pkg.EMA_STATS_COUNT == len(er.STATS) == 6
     for name, i in pkg.EMA_STATS.items():
@@ -126,13 +125,6 @@ def test_a_null_context_is_refused_before_any_device_work():
 
 
 # ------------------------------------------------------------------ GPU
-@pytest.fixture(scope="module")
-def pkg():
-    p = load_package()
-    p.lib()
-    return p
-
-
 def _prec(pkg, prec):
     return pkg.FP32 if prec == "fp32" else pkg.BF16
 

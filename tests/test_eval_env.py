@@ -15,6 +15,7 @@ import pytest
 import device_env_ref as ref
 import hashfill as hf
 from conftest import ROOT
+from shared_fixtures import trainer  # noqa: F401
 from __graft_entry__ import load_package
 from test_device_env import LUT, PLANES
 from test_eval_lanes import scalars
@@ -326,14 +327,6 @@ def test_refusals_change_nothing(pkg):
 
 
 # ------------------------------------------------------------------ 6. the trainer
-@pytest.fixture(scope="module")
-def trainer():
-    from __graft_entry__ import build
-    build()
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "trainer")])
-    return os.path.join(ROOT, "trainer", "train")
-
-
 def _train(trainer, d, txt):
     os.makedirs(d / "tb")
     cfg = d / "debug.yaml"

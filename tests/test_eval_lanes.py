@@ -22,18 +22,11 @@ import bf16_check as bc
 import eval_ref as er
 import hashfill as hf
 import oracle_lib as orc
-from __graft_entry__ import load_package
+from shared_fixtures import pkg  # noqa: F401
 from conftest import ROOT
 from test_gpu_at_size import DeviceBytes
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    p = load_package()
-    p.lib()
-    return p
 
 
 def _exp_noise(seed, shape):

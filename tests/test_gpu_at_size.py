@@ -22,17 +22,10 @@ import pytest
 import bf16_check as bc
 import hashfill as hf
 import oracle_lib as orc
-from __graft_entry__ import load_package
+from shared_fixtures import pkg  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    p = load_package()
-    p.lib()
-    return p
 
 
 class DeviceBytes:

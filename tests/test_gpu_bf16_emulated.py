@@ -22,16 +22,9 @@ import pytest
 import bf16_check as bc
 import hashfill as hf
 import oracle_lib as orc
-from __graft_entry__ import load_package
+from shared_fixtures import pkg  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    p = load_package()
-    p.lib()
-    return p
 
 
 # (OPT_FUSED_FWD, OPT_FUSED_BWD / 2, OPT_FC_PIPE, OPT_GENERIC_CONV, OPT_MINIBATCH_SHUFFLE): an L8 array - columns A, B,

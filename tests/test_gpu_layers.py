@@ -43,7 +43,7 @@ import bf16_check as bc
 import hashfill as hf
 import layer_ref as lr
 import oracle_lib as orc
-from __graft_entry__ import load_package
+from shared_fixtures import pkg  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -89,13 +89,6 @@ def row_inputs(n, H, A, modified):
         params = asr.modified_params(params, H, A)
     params.setflags(write=False)
     return params, observations(seed + 50, n)
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    p = load_package()
-    p.lib()
-    return p
 
 
 def _set_route(pkg, eng, route):

@@ -13,16 +13,9 @@ import bf16_check as bc
 import hashfill as hf
 import oracle_lib as orc
 from conftest import GAE_KATS, gae_kat_expected
-from __graft_entry__ import load_package
+from shared_fixtures import pkg  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    p = load_package()
-    p.lib()
-    return p
 
 
 # ------------------------------------------------------------------ GAE (reads like test/ai/gae-test.cc)

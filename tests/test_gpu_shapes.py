@@ -32,17 +32,10 @@ import pytest
 import bf16_check as bc
 import hashfill as hf
 import oracle_lib as orc
-from __graft_entry__ import load_package
+from shared_fixtures import pkg  # noqa: F401
 from test_gpu_at_size import DeviceBytes, _flags, _rollout_vs_oracle
 from test_gpu_bf16_emulated import sweep_batch
 from test_oracle_bf16 import _batch, _check, _run
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    p = load_package()
-    p.lib()
-    return p
 
 
 # ------------------------------------------------------------------ A. the update and forward at every hidden size

@@ -10,13 +10,13 @@ CPU: the header constants against the Python mirror, the wrapper's float <-> bit
 the trainer logs per rollout).
 GPU (-m gpu, everything through the C ABI): the bit equality above in fp32 and bf16, H = 512 and H = 96, A = 4 and 18,
 caller and rollout batches (fp32 and fp16 planes), alone and with shuffling + value clipping + per-minibatch advantage
-normalisation + the KL penalty; a value-clip range of its own against value_clip_ref.py; fp32 against the oracle and
+normalisation + the KL penalty; a value-clip range of its own against update_ref.py; fp32 against the oracle and
 bf16 against the emulation, called with the option values; a schedule under ALEPPO_OPT_UPDATE_GRAPH against the same
 schedule run eagerly; each number's own effect; validation; the 1-rank communicator."""
+import functools
 import os
 import re
 import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -24,8 +24,11 @@ import pytest
 import bf16_check as bc
 import hashfill as hf
 import oracle_lib as orc
-import value_clip_ref as vr
-import trainer_helpers
+import update_harness as uh
+import update_ref as ur
+from shared_fixtures import pkg, stub_trainer  # noqa: F401
+from trainer_helpers import debug_cfg as _debug_cfg, event_scalars, events as _events, header_const as const, run_stub
+from update_harness import assert_identical
 from __graft_entry__ import load_package
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,9 +36,7 @@ LR = 2e-5
 # X: the values under test, all different from the defaults; OTHER: what the second context is created with
 X = dict(clip_param=0.17, value_loss_coef=0.8, entropy_coef=0.03, max_gradient_norm=0.3)
 OTHER = dict(clip_param=0.05, value_loss_coef=0.25, entropy_coef=0.002, max_gradient_norm=7.0)
-PER_SAMPLE = ("total_losses", "clipped_losses", "value_losses", "entropies", "ratio", "approx_kl", "clip_fraction")
-REF_PLANE = dict(total_losses="total_losses", clipped_losses="clipped", value_losses="value_losses",
-                 entropies="entropies", ratio="ratio", approx_kl="approx_kl", clip_fraction="clip_fraction")
+read_state = functools.partial(uh.read_update, state=True)  # (with the Adam moments and the step)
 OPTS = ("OPT_CLIP_PARAM", "OPT_VALUE_CLIP_RANGE", "OPT_VALUE_LOSS_COEF", "OPT_ENTROPY_COEF", "OPT_MAX_GRAD_NORM")
 
 
@@ -51,11 +52,6 @@ def _f32(x):
 def test_header_constants_and_python_mirror():
     pkg = load_package()
     hdr = open(os.path.join(ROOT, "include", "aleppo.h")).read()
-
-    def const(name):
-        m = re.search(rf"(?m)^\s*{name}\s*=\s*(\d+)", hdr)
-        assert m, name
-        return int(m.group(1))
 
     assert const("ALEPPO_OPT_KL_COEF") == 16  # (the five are the next free numbers after it)
     for k, name in enumerate(OPTS):
@@ -104,40 +100,9 @@ def test_float_bits_conversions():
                              entropy_coef=_f32(0.01), max_grad_norm=2.0)
 
 
-@pytest.fixture(scope="module")
-def stub_trainer(tmp_path_factory):
-    return trainer_helpers.build_stub_trainer(tmp_path_factory)
-
-
-def _debug_cfg(tmp_path, extra, rollouts=4):
-    txt = open(os.path.join(ROOT, "trainer", "configs", "debug.yaml")).read()
-    txt = re.sub(r"(?m)^num_rollouts: .*$", f"num_rollouts: {rollouts}", txt)
-    cfg = tmp_path / "cfg.yaml"
-    cfg.write_text(txt + extra)
-    return cfg
-
-
 def _yaml_value(key):
     m = re.search(rf"(?m)^{key}: (\S+)", open(os.path.join(ROOT, "trainer", "configs", "debug.yaml")).read())
     return float(m.group(1))
-
-
-def _events(tmp_path):
-    return b"".join(open(tmp_path / f, "rb").read() for f in sorted(os.listdir(tmp_path)) if "tfevents" in f)
-
-
-def _scalars(data, tag):
-    """the simple_value floats logged under `tag` (tag string, then field 2 as fixed32), in file order"""
-    out, key, i = [], bytes([0x0A, len(tag)]) + tag.encode() + b"\x15", 0
-    while (i := data.find(key, i)) >= 0:
-        out.append(struct.unpack("<f", data[i + len(key):i + len(key) + 4])[0])
-        i += len(key)
-    return out
-
-
-def _train_stub(stub_trainer, tmp_path, cfg):
-    return subprocess.run([stub_trainer, "rom.bin", str(tmp_path / "run.log"), str(tmp_path), "g", str(cfg)],
-                          capture_output=True, text=True, timeout=600)
 
 
 def test_trainer_anneals_the_scheduled_values(stub_trainer, tmp_path):
@@ -145,32 +110,32 @@ def test_trainer_anneals_the_scheduled_values(stub_trainer, tmp_path):
     n = 5
     final = dict(clip_param=0.01, entropy_coef=0.0, value_loss_coef=1.0, max_gradient_norm=0.1)
     extra = "".join(f"{k}_final: {v}\n" for k, v in final.items())
-    r = _train_stub(stub_trainer, tmp_path, _debug_cfg(tmp_path, extra, rollouts=n))
+    r = run_stub(stub_trainer, tmp_path, _debug_cfg(tmp_path, extra, rollouts=n))
     assert r.returncode == 0, r.stderr[-2000:]
     data = _events(tmp_path)
     for k, v1 in final.items():
         v0 = float(np.float32(_yaml_value(k)))  # (the config's values are floats)
-        got = _scalars(data, k)
+        got = event_scalars(data, k)
         want = [_f32(v0 + (v1 - v0) * (i / n)) for i in range(n)]
         assert len(got) == n, (k, got)
         for i in (0, 1, n - 1):
             assert got[i] == want[i], (k, i, got, want)
         assert got == want and got[0] == _f32(v0) and got[-1] != _f32(v1)  # like the learning rate: the end is not reached
         assert (k + "_final").encode() in data  # hparams
-    assert len(_scalars(data, "learning_rate")) == n
+    assert len(event_scalars(data, "learning_rate")) == n
 
 
 def test_trainer_without_the_keys_sets_and_logs_nothing(stub_trainer, tmp_path):
-    r = _train_stub(stub_trainer, tmp_path, _debug_cfg(tmp_path, "", rollouts=2))
+    r = run_stub(stub_trainer, tmp_path, _debug_cfg(tmp_path, "", rollouts=2))
     assert r.returncode == 0, r.stderr[-2000:]
     data = _events(tmp_path)
     for k in ("clip_param", "entropy_coef", "value_loss_coef", "max_gradient_norm"):
-        assert _scalars(data, k) == [] and (k + "_final").encode() not in data
-    assert b"value_clip_range" not in data and len(_scalars(data, "learning_rate")) == 2
+        assert event_scalars(data, k) == [] and (k + "_final").encode() not in data
+    assert b"value_clip_range" not in data and len(event_scalars(data, "learning_rate")) == 2
 
 
 def test_trainer_value_clip_range_is_a_constant_hparam(stub_trainer, tmp_path):
-    r = _train_stub(stub_trainer, tmp_path, _debug_cfg(tmp_path, "clip_value_loss: true\nvalue_clip_range: 0.3\n", 2))
+    r = run_stub(stub_trainer, tmp_path, _debug_cfg(tmp_path, "clip_value_loss: true\nvalue_clip_range: 0.3\n", 2))
     assert r.returncode == 0, r.stderr[-2000:]
     assert b"value_clip_range" in _events(tmp_path)
 
@@ -185,28 +150,13 @@ def test_trainer_value_clip_range_is_a_constant_hparam(stub_trainer, tmp_path):
     ("value_clip_range: 0.2\n", "value_clip_range needs clip_value_loss: true"),
 ])
 def test_trainer_refuses_invalid_values_at_load_time(stub_trainer, tmp_path, extra, msg):
-    r = _train_stub(stub_trainer, tmp_path, _debug_cfg(tmp_path, extra))
+    r = run_stub(stub_trainer, tmp_path, _debug_cfg(tmp_path, extra, rollouts=4))
     assert r.returncode != 0 and msg in r.stdout + r.stderr, (r.returncode, r.stderr[-2000:])
     assert "Rollout 1" not in r.stdout
 
 
 # ------------------------------------------------------------------ GPU
-@pytest.fixture(scope="module")
-def pkg():
-    p = load_package()
-    p.lib()
-    return p
-
-
-def _batch(seed, N, A):
-    obs = hf.hf_bytes(seed, (N, 4, 84, 84))
-    actions = (hf.hf_u32(seed + 1, N) % np.uint32(A)).astype(np.int64)
-    old_lp = orc.log_softmax(hf.hf_range(seed + 2, (N, A), -1, 1))
-    adv = hf.hf_range(seed + 3, (N,), -1, 1)
-    ret = hf.hf_range(seed + 4, (N,), -1, 1)
-    masks = (hf.hf_unit(seed + 5, N) >= np.float32(0.15)).astype(np.uint8)
-    masks[0] = 1
-    return obs, actions, old_lp, adv, ret, masks
+_hashed = functools.partial(uh.hashed_batch, mask_p=0.15)
 
 
 def _set_x(eng, x, value_clip_range=None):
@@ -214,39 +164,12 @@ def _set_x(eng, x, value_clip_range=None):
                   max_grad_norm=x["max_gradient_norm"], value_clip_range=value_clip_range)
 
 
-def _read(eng, m, epochs, M, kl=False):
-    B = eng._batch_n // M
-    sd = eng.state_dict()
-    out = dict(m=m, params=sd["params"], exp_avg=sd["exp_avg"], exp_avg_sq=sd["exp_avg_sq"], step=sd["step"],
-               grads=eng.export_grads(), diag=eng.train_diagnostics(epochs, M))
-    out.update({k: eng.read_train_metric(k, epochs, M, B) for k in PER_SAMPLE})
-    if kl:
-        out["kl"] = eng.read_train_metric("kl", epochs, M, B)
-        out["mean_kl"] = eng.kl_divergence(epochs, M)
-    return out
-
-
-def _assert_identical(a, b, skip=()):
-    assert set(a) == set(b)
-    for k in a["m"]:
-        if k not in skip:
-            np.testing.assert_array_equal(a["m"][k], b["m"][k], err_msg=k)
-    for k in a["diag"]:
-        if k not in skip:
-            np.testing.assert_array_equal(a["diag"][k], b["diag"][k], err_msg=k)
-    for k in a:
-        if k not in ("m", "diag") and k not in skip:
-            np.testing.assert_array_equal(a[k], b[k], err_msg=k)
-
-
 def _pair(pkg, E, T, A, H, prec, prepare, epochs=2, M=2, options=(), kl=False, lr=LR, **kw):
     """(a context created with X, a context created with OTHER and set to X): the outputs of one aleppo_train each.
     prepare(eng) loads the parameters and the batch."""
     outs = []
     for via_options in (False, True):
-        eng = pkg.Engine(E, T, A, H, precision=prec, **(OTHER if via_options else X), **kw)
-        for k, v in options:
-            eng.set_option(k, v)
+        eng = uh.make_engine(pkg, E, T, A, H, prec, options, **(OTHER if via_options else X), **kw)
         if kl:
             eng.set_kl_coef(0.2)
         prepare(eng)
@@ -256,7 +179,7 @@ def _pair(pkg, E, T, A, H, prec, prepare, epochs=2, M=2, options=(), kl=False, l
                                        value_loss_coef=_f32(X["value_loss_coef"]),
                                        entropy_coef=_f32(X["entropy_coef"]),
                                        max_grad_norm=_f32(X["max_gradient_norm"]))
-        outs.append(_read(eng, eng.train(lr, epochs, M), epochs, M, kl=kl))
+        outs.append(read_state(eng, eng.train(lr, epochs, M), epochs, M, kl=kl))
         eng.close()
     return outs
 
@@ -272,7 +195,7 @@ def _all_on(pkg):
 def test_options_equal_config_bit_for_bit_on_a_caller_batch(pkg, prec, H, A):
     E, T = 8, 16
     params = hf.fill_params(7100 + H + A, H, A)
-    batch = _batch(7101, E * T, A)
+    batch = _hashed(7101, E * T, A)
     _, v0 = orc.net_forward(params, H, A, batch[0])
     vold = (v0 + hf.hf_range(7102, (E * T,), -0.3, 0.3)).astype(np.float32)
 
@@ -282,11 +205,11 @@ def test_options_equal_config_bit_for_bit_on_a_caller_batch(pkg, prec, H, A):
 
     p = pkg.BF16 if prec == "bf16" else pkg.FP32
     a, b = _pair(pkg, E, T, A, H, p, prepare)
-    _assert_identical(a, b)
+    assert_identical(a, b)
     assert np.isfinite(a["params"]).all() and (a["exp_avg_sq"] > 0).any() and a["step"] == 4
     # ... and with shuffling + value clipping + per-minibatch advantage normalisation + the KL penalty (beta = 0.2)
     a, b = _pair(pkg, E, T, A, H, p, prepare, options=_all_on(pkg), kl=True)
-    _assert_identical(a, b)
+    assert_identical(a, b)
     assert (a["kl"] > 0).any()
 
 
@@ -313,19 +236,19 @@ def test_options_equal_config_bit_for_bit_on_a_rollout_batch(pkg, prec, rollout_
     for options, kl in (((), False), (_all_on(pkg), True)):
         # (a larger rate than LR: the policy has to leave the rollout's for the clip range to matter)
         a, b = _pair(pkg, E, T, A, H, p, prepare, options=options, kl=kl, lr=2.5e-4, seed=3, rollout_precision=rp)
-        _assert_identical(a, b)
+        assert_identical(a, b)
 
 
 @pytest.mark.gpu
 def test_value_clip_range_of_its_own(pkg):
-    """the value-loss plane and dL/dv follow ALEPPO_OPT_VALUE_CLIP's formulas with c = the range (value_clip_ref.py at
+    """the value-loss plane and dL/dv follow ALEPPO_OPT_VALUE_CLIP's formulas with c = the range (update_ref.py at
     test_value_clip.py's fp32 bounds, 1e-4); the clipped-surrogate plane and the clip fraction are those of a run with
     the range unset, bit for bit"""
     E, T, A, H, epochs, M = 8, 32, 6, 64, 1, 1
     N = E * T
     clip, rng_v = 0.1, 0.03
     params = hf.fill_params(7300, H, A)
-    batch = _batch(7301, N, A)
+    batch = _hashed(7301, N, A)
     _, v0 = orc.net_forward(params, H, A, batch[0])
     vold = (v0 + hf.hf_range(7302, (N,), -0.12, 0.12)).astype(np.float32)
     outs = {}
@@ -340,22 +263,22 @@ def test_value_clip_range_of_its_own(pkg):
         else:
             eng.set_hyper(clip_param=clip)  # (the same setter traffic on both sides; the range follows the clip)
             assert eng.hyper()["value_clip_range"] == _f32(clip)
-        outs[name] = _read(eng, eng.train(LR, epochs, M), epochs, M)
+        outs[name] = read_state(eng, eng.train(LR, epochs, M), epochs, M)
         eng.close()
     s, u = outs["set"], outs["unset"]
     for k in ("clipped_losses", "clip_fraction", "ratio", "entropies", "approx_kl"):
         np.testing.assert_array_equal(s[k], u[k], err_msg=k)
     assert not np.array_equal(s["value_losses"], u["value_losses"])
-    # value_clip_ref with clip = the range gives the value term (its surrogate would clip at the range too, so only the
+    # update_ref's value branch with clip = the range gives the value term (its surrogate would clip at the range too, so only the
     # value plane and the value gradient are taken from it) ...
     logits, values = orc.net_forward(params, H, A, batch[0])
-    lv, dv, zero = vr.value_branch(values, batch[4], vold, rng_v)
-    lv_c, _, zero_c = vr.value_branch(values, batch[4], vold, clip)
+    lv, dv, zero = ur.value_branch(values, batch[4], vold, rng_v)
+    lv_c, _, zero_c = ur.value_branch(values, batch[4], vold, clip)
     mk = batch[5] != 0
     assert (zero & mk).sum() > 10 and ((zero != zero_c) & mk).sum() > 10  # both branches, and the range matters
     np.testing.assert_allclose(s["value_losses"][0, 0], lv, atol=1e-4, rtol=1e-4)
     np.testing.assert_allclose(u["value_losses"][0, 0], lv_c, atol=1e-4, rtol=1e-4)
-    # ... and the whole update against the reference composed with both ranges: value_clip_ref at clip = range for the
+    # ... and the whole update against the reference composed with both ranges: update_ref at clip = range for the
     # value term, the oracle's surrogate at clip_param (composed below from the same pieces)
     o = orc.ppo_loss(logits, batch[2], batch[1], batch[3], values, batch[4], batch[5], clip, 0.5, 0.01)
     nm = np.float32(mk.sum())
@@ -378,7 +301,7 @@ def _x_kw(x):
 def test_fp32_against_the_oracle_called_with_the_option_values(pkg, H, A, N, M):
     """test_gpu_parity.py's test_train_vs_oracle with the oracle's clip, c_v, c_e, max_norm = the options' values"""
     params = hf.fill_params(510, H, A)
-    obs, actions, old_lp, adv, ret, masks = _batch(7400, N, A)
+    obs, actions, old_lp, adv, ret, masks = _hashed(7400, N, A)
     eng = pkg.Engine(N // 8, 8, A, H, precision=pkg.FP32, **OTHER)
     eng.load_params(params)
     eng.set_batch(obs, actions, old_lp, adv, ret, masks)
@@ -400,12 +323,12 @@ def test_fp32_against_the_oracle_called_with_the_option_values(pkg, H, A, N, M):
 def test_bf16_against_the_emulation_called_with_the_option_values(pkg):
     E, T, A, H, epochs, M = 12, 8, 4, 512, 2, 2
     params = hf.fill_params(7500, H, A)
-    batch = _batch(7501, E * T, A)
+    batch = _hashed(7501, E * T, A)
     eng = pkg.Engine(E, T, A, H, precision=pkg.BF16, **OTHER)
     eng.load_params(params)
     eng.set_batch(*batch)
     _set_x(eng, X)
-    out = _read(eng, eng.train(2.5e-4, epochs, M), epochs, M)
+    out = read_state(eng, eng.train(2.5e-4, epochs, M), epochs, M)
     eng.close()
     ref = bc.emulated_train(params, H, A, *batch, epochs, M, **_x_kw(X))
     c = bc.Checker()
@@ -431,7 +354,7 @@ def test_a_schedule_under_the_captured_update(pkg, prec):
     E, T, A, H, epochs, M = 16, 16, 6, 256, 2, 2
     p = pkg.BF16 if prec == "bf16" else pkg.FP32
     params = hf.fill_params(7600, H, A)
-    batch = _batch(7601, E * T, A)
+    batch = _hashed(7601, E * T, A)
     _, v0 = orc.net_forward(params, H, A, batch[0])
     vold = (v0 + hf.hf_range(7602, (E * T,), -0.3, 0.3)).astype(np.float32)
     outs = {}
@@ -449,12 +372,12 @@ def test_a_schedule_under_the_captured_update(pkg, prec):
         res = []
         for k, x in enumerate(SCHEDULE):
             _set_x(eng, x, value_clip_range=0.5 * x["clip_param"])
-            res.append(_read(eng, eng.train(LR, epochs, M), epochs, M))
+            res.append(read_state(eng, eng.train(LR, epochs, M), epochs, M))
             assert eng.get_option(pkg.OPT_UPDATE_GRAPH) == (n0 + k + 1 if graph else 0)
         outs[graph] = res
         eng.close()
     for a, b in zip(outs[0], outs[1]):
-        _assert_identical(a, b)
+        assert_identical(a, b)
     # the settings were followed: the three updates differ from one another in what the numbers govern
     assert not np.array_equal(outs[1][0]["clip_fraction"], outs[1][2]["clip_fraction"]) or \
         not np.array_equal(outs[1][0]["total_losses"], outs[1][2]["total_losses"])
@@ -466,7 +389,7 @@ def test_each_number_bites(pkg):
     E, T, A, H, M = 8, 32, 6, 64, 1
     N = E * T
     params = hf.fill_params(7700, H, A)
-    batch = _batch(7701, N, A)
+    batch = _hashed(7701, N, A)
     eng = pkg.Engine(E, T, A, H, precision=pkg.FP32, clip_param=0.2)
     eng.load_params(params)
     # a batch whose old log-probs are the current policy's: all ratios are 1; one step moves them apart (at 1e-4 the
@@ -480,7 +403,7 @@ def test_each_number_bites(pkg):
     def run(**hyper):
         eng.load_params(p1)  # (resets Adam: every run below is the same step from the same state)
         eng.set_hyper(**hyper)
-        return _read(eng, eng.train(LR, 1, M), 1, M)
+        return read_state(eng, eng.train(LR, 1, M), 1, M)
 
     wide = run(clip_param=0.2)
     mk = batch[5] != 0
@@ -567,7 +490,7 @@ def test_one_rank_communicator_is_bit_identical(pkg, prec):
     E, T, A, H, epochs, M = 16, 32, 4, 256, 2, 2
     p = pkg.BF16 if prec == "bf16" else pkg.FP32
     params = hf.fill_params(7800, H, A)
-    batch = _batch(7801, E * T, A)
+    batch = _hashed(7801, E * T, A)
     _, v0 = orc.net_forward(params, H, A, batch[0])
     vold = (v0 + hf.hf_range(7802, (E * T,), -0.3, 0.3)).astype(np.float32)
     outs = []
@@ -582,6 +505,6 @@ def test_one_rank_communicator_is_bit_identical(pkg, prec):
         eng.load_params(params)
         eng.set_batch(*batch, values=vold)
         _set_x(eng, X, value_clip_range=0.06)
-        outs.append(_read(eng, eng.train(LR, epochs, M), epochs, M, kl=True))
+        outs.append(read_state(eng, eng.train(LR, epochs, M), epochs, M, kl=True))
         eng.close()
-    _assert_identical(outs[0], outs[1])
+    assert_identical(outs[0], outs[1])

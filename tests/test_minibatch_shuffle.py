@@ -5,16 +5,18 @@ trainer's `shuffle_minibatches` key against the host-only library stand-in.
 GPU (-m gpu, everything through the C ABI): the device order equals the mirror (eager, resumed, graph-replayed), a
 shuffled update equals a contiguous update on the host-permuted batch bit for bit on every schedule, and the CPU oracle
 on the permuted batch."""
+import functools
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import hashfill as hf
 import oracle_lib as orc
-import trainer_helpers
+import update_harness as uh
+from shared_fixtures import pkg, stub_trainer  # noqa: F401
+from trainer_helpers import debug_cfg, events, header_const, run_stub
 from __graft_entry__ import load_package
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -83,57 +85,24 @@ def test_mirror_depends_on_step_seed_and_rank():
 def test_header_constant_and_export():
     pkg = load_package()
     hdr = open(os.path.join(ROOT, "include", "aleppo.h")).read()
-    m = re.search(r"(?m)^\s*ALEPPO_OPT_MINIBATCH_SHUFFLE\s*=\s*(\d+)", hdr)
-    assert m and int(m.group(1)) == pkg.OPT_MINIBATCH_SHUFFLE == 12
+    assert header_const("ALEPPO_OPT_MINIBATCH_SHUFFLE") == pkg.OPT_MINIBATCH_SHUFFLE == 12
     assert "aleppo_read_sample_order" in pkg.EXPORTS
     assert re.search(r"int aleppo_read_sample_order\(aleppo_ctx \*ctx, int32_t \*dst, size_t count\);", hdr)
 
 
-@pytest.fixture(scope="module")
-def stub_trainer(tmp_path_factory):
-    return trainer_helpers.build_stub_trainer(tmp_path_factory)
-
-
 @pytest.mark.parametrize("shuffle", [True, False])
 def test_trainer_key_reaches_the_hparams_record(stub_trainer, tmp_path, shuffle):
-    txt = open(os.path.join(ROOT, "trainer", "configs", "debug.yaml")).read()
-    txt = re.sub(r"(?m)^num_rollouts: .*$", "num_rollouts: 2", txt)
-    if shuffle:
-        txt += "shuffle_minibatches: true\n"
-    cfg = tmp_path / "d.yaml"
-    cfg.write_text(txt)
-    r = subprocess.run([stub_trainer, "rom.bin", str(tmp_path / "run.log"), str(tmp_path), "g", str(cfg)],
-                       capture_output=True, text=True, timeout=600)
+    r = run_stub(stub_trainer, tmp_path, debug_cfg(tmp_path, "shuffle_minibatches: true\n" if shuffle else ""))
     assert r.returncode == 0, r.stderr[-2000:]
-    events = [f for f in os.listdir(tmp_path) if ".tfevents." in f]
-    assert len(events) == 1
-    data = open(tmp_path / events[0], "rb").read()
+    data = events(tmp_path)
     assert b"_hparams_/session_start_info" in data and b"cuda_graph" in data
     assert (b"shuffle_minibatches" in data) == shuffle
 
 
 # ------------------------------------------------------------------ GPU
-@pytest.fixture(scope="module")
-def pkg():
-    p = load_package()
-    p.lib()
-    return p
-
-
-def _batch(seed, N, A, distinct=None):
-    if distinct:  # (large batches: byte-permuted copies of a smaller block are cheap to generate)
-        base = hf.hf_bytes(seed, (N // distinct, 4, 84, 84))
-        obs = np.concatenate([base ^ np.uint8(29 * k) for k in range(distinct)])
-    else:
-        obs = hf.hf_bytes(seed, (N, 4, 84, 84))
-    actions = (hf.hf_u32(seed + 1, N) % np.uint32(A)).astype(np.int64)
-    old_lp = orc.log_softmax(hf.hf_range(seed + 2, (N, A), -1, 1))
-    adv, ret = hf.hf_range(seed + 3, (N,), -1, 1), hf.hf_range(seed + 4, (N,), -1, 1)
-    masks = (hf.hf_unit(seed + 5, N) >= np.float32(0.1)).astype(np.uint8)
-    return obs, actions, old_lp, adv, ret, masks
-
-
-METRICS = ("total_losses", "clipped_losses", "value_losses", "entropies", "ratio")
+# (the first sample of each of this file's seeds is unmasked by its hash already: the harness pinning it changes nothing)
+_hashed = functools.partial(uh.hashed_batch, mask_p=0.1)
+METRICS = uh.PER_SAMPLE[:5]
 
 
 @pytest.mark.gpu
@@ -141,7 +110,7 @@ def test_device_order_is_the_documented_one(pkg):
     E, T, A, H, epochs, M, seed = 8, 16, 4, 32, 4, 4, 1234
     N = E * T
     params = hf.fill_params(3100, H, A)
-    batch = _batch(3101, N, A)
+    batch = _hashed(3101, N, A)
     eng = pkg.Engine(E, T, A, H, precision=pkg.FP32, seed=seed)
     eng.load_params(params)
     eng.set_batch(*batch)
@@ -187,16 +156,11 @@ def test_device_order_is_the_documented_one(pkg):
 def _shuffled_vs_contiguous(pkg, E, T, A, H, epochs, M, prec, batch, options=(), comm=False, engine_kw=None,
                             params=None):
     """context A trains shuffled on `batch`; context B trains contiguously on batch[order[e]] one epoch at a time"""
-    kw = dict(precision=prec, **(engine_kw or {}))
     N = E * T
     B = N // M
     out = []
     for shuffled in (True, False):
-        eng = pkg.Engine(E, T, A, H, **kw)
-        if comm:
-            eng.comm_init(pkg.Engine.comm_unique_id())
-        for k, v in options:
-            eng.set_option(k, v)
+        eng = uh.make_engine(pkg, E, T, A, H, prec, options, comm, **(engine_kw or {}))
         eng.load_params(params)
         if shuffled:
             eng.set_option(pkg.OPT_MINIBATCH_SHUFFLE, 1)
@@ -246,7 +210,7 @@ def test_shuffled_equals_contiguous_on_the_permuted_batch(pkg, case):
     if case == "bf16_comm":  # the data-parallel schedule on a 1-rank communicator
         options, comm = [(pkg.OPT_FORCE_COMM, 1)], True
     params = hf.fill_params(3200, H, A)
-    batch = _batch(3201, E * T, A, distinct)
+    batch = _hashed(3201, E * T, A, distinct=distinct)
     _shuffled_vs_contiguous(pkg, E, T, A, H, epochs, M, prec, batch, options, comm, params=params)
 
 
@@ -301,7 +265,7 @@ def test_shuffled_update_vs_oracle_on_the_permuted_batch(pkg, E, T, epochs, M):
     A, H, seed = 6, 512, 99
     N = E * T
     params = hf.fill_params(3500, H, A)
-    batch = _batch(3501, N, A, 8 if N >= 4096 else None)
+    batch = _hashed(3501, N, A, distinct=8 if N >= 4096 else None)
     eng = pkg.Engine(E, T, A, H, precision=pkg.FP32, seed=seed)
     eng.load_params(params)
     eng.set_batch(*batch)

@@ -20,6 +20,8 @@ import hashfill as hf
 import oracle_lib as orc
 import recycle_ref as rr
 from conftest import ROOT
+import trainer_helpers
+from shared_fixtures import pkg  # noqa: F401
 from __graft_entry__ import load_package
 
 TAU = 0.025
@@ -69,10 +71,7 @@ def test_header_constants_and_prototypes_match_the_python_mirror():
     pkg = load_package()
     hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "aleppo.h")).read(), flags=re.S)
 
-    def const(name):
-        m = re.search(rf"\b{name}\s*=?\s*(\d+)", hdr)
-        assert m, name
-        return int(m.group(1))
+    const = functools.partial(trainer_helpers.header_const, stripped=True)
 
     assert const("ALEPPO_RECYCLE_COUNTS") == pkg.RECYCLE_COUNTS == len(rr.ROWS) == 5
     for name in ("conv1", "conv2", "conv3", "fc"):
@@ -251,13 +250,6 @@ def test_recycling_a_dead_unit_leaves_every_output_alone(mirror, shape):
 
 
 # ------------------------------------------------------------------ GPU
-@pytest.fixture(scope="module")
-def pkg():
-    p = load_package()
-    p.lib()
-    return p
-
-
 def _prec(pkg, prec):
     return pkg.FP32 if prec == "fp32" else pkg.BF16
 

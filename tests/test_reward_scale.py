@@ -16,6 +16,8 @@ import pytest
 import hashfill as hf
 import oracle_lib as orc
 import reward_scale_ref as rr
+from trainer_helpers import header_const as const
+from shared_fixtures import pkg  # noqa: F401
 from __graft_entry__ import load_package
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -142,11 +144,6 @@ def test_header_constants_and_python_mirror():
     pkg = load_package()
     hdr = open(os.path.join(ROOT, "include", "aleppo.h")).read()
 
-    def const(name):
-        m = re.search(rf"(?m)^\s*{name}\s*=\s*(\d+)", hdr)
-        assert m, name
-        return int(m.group(1))
-
     assert const("ALEPPO_OPT_REWARD_SCALE") == pkg.OPT_REWARD_SCALE == 23
     assert const("ALEPPO_OPT_REWARD_SCALE_CLIP") == pkg.OPT_REWARD_SCALE_CLIP == 24
     assert const("ALEPPO_F_REWARD_SCALE") == pkg.FIELDS["reward_scale"] == 14
@@ -163,13 +160,6 @@ def test_header_constants_and_python_mirror():
 
 
 # ------------------------------------------------------------------ GPU
-@pytest.fixture(scope="module")
-def pkg():
-    p = load_package()
-    p.lib()
-    return p
-
-
 class _DeviceBytes:
     """device copy of a numpy array (no torch in the test process)"""
 

@@ -7,16 +7,9 @@ import subprocess
 import pytest
 
 from conftest import ROOT
+from shared_fixtures import trainer  # noqa: F401
 
 BASE = "total_environments: 8\nhidden_size: 32\nhorizon: 8\nnum_mini_batches: 4\nnum_rollouts: 1\ndeterministic: true\n"
-
-
-@pytest.fixture(scope="module")
-def trainer():
-    from __graft_entry__ import build
-    build()
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "trainer")])
-    return os.path.join(ROOT, "trainer", "train")
 
 
 @pytest.fixture(scope="module")

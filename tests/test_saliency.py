@@ -12,19 +12,13 @@ import bf16_check as bc
 import hashfill as hf
 import oracle_lib as orc
 import saliency_ref as sr
+from shared_fixtures import pkg  # noqa: F401
 from __graft_entry__ import load_package
 
 SHAPES = {"fp32": (32, 4, 8100), "bf16": (96, 18, 8200)}  # H, A, parameter seed
 E, T, MAXB = 4, 8, 32
 COARSE = dict(stride=12, sigma_mask=2.0, sigma_blur=1.0)  # G = 7, P = 49
 FINE = dict(stride=5, sigma_mask=5.0, sigma_blur=3.0)     # G = 17, P = 289
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    p = load_package()
-    p.lib()
-    return p
 
 
 @functools.lru_cache(maxsize=None)

@@ -22,6 +22,7 @@ import hashfill as hf
 import tensor_stats_ref as tr
 import trainer_helpers
 from conftest import ROOT
+from shared_fixtures import pkg  # noqa: F401
 from __graft_entry__ import load_package
 
 LR = 2.5e-4
@@ -33,10 +34,7 @@ def test_header_constants_match_the_python_mirror():
     pkg = load_package()
     hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "aleppo.h")).read(), flags=re.S)
 
-    def const(name):
-        m = re.search(rf"\b{name}\s*=?\s*(\d+)", hdr)
-        assert m, name
-        return int(m.group(1))
+    const = functools.partial(trainer_helpers.header_const, stripped=True)
 
     assert const("ALEPPO_TENSOR_STATS_ROWS") == pkg.TENSOR_STATS_ROWS == tr.ROWS == 13
     assert const("ALEPPO_TENSOR_STATS_COLS") == pkg.TENSOR_STATS_COLS == tr.COLS == 10
@@ -182,13 +180,6 @@ def test_library_without_the_symbol_refuses_the_key(tmp_path_factory, tmp_path):
 
 
 # ------------------------------------------------------------------ GPU
-@pytest.fixture(scope="module")
-def pkg():
-    p = load_package()
-    p.lib()
-    return p
-
-
 def _prec(pkg, prec):
     return pkg.FP32 if prec == "fp32" else pkg.BF16
 

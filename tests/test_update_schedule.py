@@ -16,19 +16,12 @@ import numpy as np
 import pytest
 
 import hashfill as hf
-from __graft_entry__ import load_package
+from shared_fixtures import pkg  # noqa: F401
 
 E, T, H, EPOCHS, M = 8, 8, 32, 2, 2
 N = E * T
 LR = 2.5e-4
 UPDATES = 3
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    p = load_package()
-    p.lib()
-    return p
 
 
 @pytest.fixture(scope="module")

@@ -1,14 +1,13 @@
 """ALEPPO_OPT_VALUE_CLIP (value-function clipping) and the approx-KL / clip-fraction diagnostics of aleppo_train.
 
-CPU: the header constants against the Python mirror, the composed reference (value_clip_ref.py) against orc.train with
-clipping off, and the trainer's `clip_value_loss` / `target_kl` keys against the host-only library stand-in.
+CPU: the header constants against the Python mirror, the composed reference (update_ref.py) against orc.train with
+every option off, and the trainer's `clip_value_loss` / `target_kl` keys against the host-only library stand-in.
 GPU (-m gpu, everything through the C ABI): the clipped update against the composed reference in fp32 and in bf16 (at
 BASELINE configs[1]'s update), on a rollout batch with fp32 and fp16 planes; shuffled, graph-replayed and 1-rank
 communicator schedules bit-identical to the plain one; the option off restores the default bit for bit; the error
 cases; one call of E epochs equals E one-epoch calls; the trainer's target_kl on the device."""
 import os
 import re
-import struct
 import subprocess
 
 import numpy as np
@@ -17,9 +16,11 @@ import pytest
 import bf16_check as bc
 import hashfill as hf
 import oracle_lib as orc
-import value_clip_ref as vr
-import trainer_helpers
-from trainer_helpers import debug_cfg as _debug_cfg, events as _events
+import update_harness as uh
+import update_ref as ur
+from shared_fixtures import pkg, stub_trainer, trainer  # noqa: F401
+from trainer_helpers import debug_cfg as _debug_cfg, event_scalars, events as _events, header_const as const, run_stub
+from update_harness import PER_SAMPLE, assert_identical
 from __graft_entry__ import load_package
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,21 +28,12 @@ CLIP = 0.1  # Engine's default clip_param
 # learning rate of the GPU tests: small enough that the values stay near where v_old was drawn over the 8 Adam steps of
 # a 2 x 4 update (at 2.5e-4 they drift by ~0.8, far past the clip range, and the clipped branch stops winning)
 LR = 2e-5
-PER_SAMPLE = ("total_losses", "clipped_losses", "value_losses", "entropies", "ratio", "approx_kl", "clip_fraction")
-REF_PLANE = dict(total_losses="total_losses", clipped_losses="clipped", value_losses="value_losses",
-                 entropies="entropies", ratio="ratio", approx_kl="approx_kl", clip_fraction="clip_fraction")
 
 
 # ------------------------------------------------------------------ CPU
 def test_header_constants_and_export():
     pkg = load_package()
     hdr = open(os.path.join(ROOT, "include", "aleppo.h")).read()
-
-    def const(name):
-        m = re.search(rf"(?m)^\s*{name}\s*=\s*(\d+)", hdr)
-        assert m, name
-        return int(m.group(1))
-
     assert const("ALEPPO_OPT_VALUE_CLIP") == pkg.OPT_VALUE_CLIP == 13
     assert const("ALEPPO_M_APPROX_KL") == pkg.METRIC_FIELDS["approx_kl"] == 5
     assert const("ALEPPO_M_CLIP_FRACTION") == pkg.METRIC_FIELDS["clip_fraction"] == 6
@@ -52,18 +44,9 @@ def test_header_constants_and_export():
     assert hasattr(pkg.lib(), "aleppo_set_batch_values")
 
 
-def _batch(seed, N, A, distinct=None):
-    if distinct:  # (large batches: byte-permuted copies of a smaller block)
-        base = hf.hf_bytes(seed, (N // distinct, 4, 84, 84))
-        obs = np.concatenate([base ^ np.uint8(29 * k) for k in range(distinct)])
-    else:
-        obs = hf.hf_bytes(seed, (N, 4, 84, 84))
-    actions = (hf.hf_u32(seed + 1, N) % np.uint32(A)).astype(np.int64)
-    old_lp = orc.log_softmax(hf.hf_range(seed + 2, (N, A), -1, 1))
-    adv = hf.hf_range(seed + 3, (N,), -1, 1)
-    masks = (hf.hf_unit(seed + 5, N) >= np.float32(0.1)).astype(np.uint8)
-    masks[0] = 1
-    return obs, actions, old_lp, adv, masks
+def _planes(seed, N, A, distinct=None):
+    """(obs, actions, old_lp, adv, masks): the returns come from _values_and_returns"""
+    return uh.hashed_batch(seed, N, A, mask_p=0.1, with_ret=False, distinct=distinct)
 
 
 def _values_and_returns(seed, values):
@@ -77,13 +60,13 @@ def _values_and_returns(seed, values):
 
 @pytest.mark.parametrize("bf16", [False, True])
 def test_composed_reference_without_clipping_is_the_oracle(bf16):
-    """value_clip_ref.composed_train with vold=None is orc.train, bit for bit (same oracle calls in the same order)"""
+    """update_ref.composed_train with every option off is orc.train, bit for bit (same oracle calls in the same order)"""
     H, A, N, epochs, M = 32, 6, 48, 2, 3
     params = hf.fill_params(4100, H, A)
-    obs, actions, old_lp, adv, masks = _batch(4101, N, A)
+    obs, actions, old_lp, adv, masks = _planes(4101, N, A)
     ret = hf.hf_range(4106, (N,), -1, 1)
     ref = orc.train(params, H, A, obs, actions, old_lp, adv, ret, masks, epochs, M, emulate_bf16=bf16)
-    got = vr.composed_train(params, H, A, obs, actions, old_lp, adv, ret, masks, epochs, M, emulate_bf16=bf16)
+    got = ur.composed_train(params, H, A, obs, actions, old_lp, adv, ret, masks, epochs, M, emulate_bf16=bf16)
     for k in ("params", "loss", "grad_norm", "last_grads", "total_losses", "ratio", "entropies", "value_losses",
               "clipped"):
         np.testing.assert_array_equal(got[k], ref[k], err_msg=k)
@@ -93,100 +76,43 @@ def test_composed_reference_without_clipping_is_the_oracle(bf16):
     assert (got["params"] != params).any()
     # and the value branch reduces to the reference's where v_old = v (|d| = 0 <= c: the select keeps v)
     _, values = orc.net_forward(params, H, A, obs[:N // M])
-    lv, dv, zero = vr.value_branch(values, ret[:N // M], values, CLIP)
+    lv, dv, zero = ur.value_branch(values, ret[:N // M], values, CLIP)
     np.testing.assert_array_equal(lv, 0.5 * (values.astype(np.float64) - ret[:N // M]) ** 2)
     assert not zero.any()
 
 
-@pytest.fixture(scope="module")
-def stub_trainer(tmp_path_factory):
-    return trainer_helpers.build_stub_trainer(tmp_path_factory)
-
-
-def _scalars(blob, tag):
-    """every value of scalar `tag` (Summary.Value{1: tag, 2: simple_value}) in the event file, in order"""
-    t = tag.encode()
-    key = b"\x0a" + bytes([len(t)]) + t + b"\x15"
-    return [struct.unpack("<f", blob[m.end():m.end() + 4])[0] for m in re.finditer(re.escape(key), blob)]
-
-
 def test_trainer_keys_with_the_stub_library(stub_trainer, tmp_path):
     cfg = _debug_cfg(tmp_path, "clip_value_loss: true\ntarget_kl: 0.01\n")
-    r = subprocess.run([stub_trainer, "rom.bin", str(tmp_path / "run.log"), str(tmp_path), "g", str(cfg)],
-                       capture_output=True, text=True, timeout=600)
+    r = run_stub(stub_trainer, tmp_path, cfg)
     assert r.returncode == 0, r.stderr[-2000:]
     data = _events(tmp_path)
     assert b"_hparams_/session_start_info" in data and b"clip_value_loss" in data
     for tag in ("mean_approx_kl", "mean_clip_fraction", "update_epochs"):
-        assert len(_scalars(data, tag)) == 2, tag
-    assert _scalars(data, "update_epochs") == [2.0, 2.0]  # (the stand-in reports zero approx-KL: every epoch runs)
+        assert len(event_scalars(data, tag)) == 2, tag
+    assert event_scalars(data, "update_epochs") == [2.0, 2.0]  # (the stand-in reports zero approx-KL: every epoch runs)
 
 
 # ------------------------------------------------------------------ GPU
-@pytest.fixture(scope="module")
-def pkg():
-    p = load_package()
-    p.lib()
-    return p
-
-
-def _engine_run(pkg, E, T, A, H, prec, params, batch, ret, vold, epochs, M, clip_on=True, options=(), comm=False,
-                calls=1, **kw):
-    """one context: options, set_batch (+ values), `calls` aleppo_train calls; returns the last call's outputs"""
-    eng = pkg.Engine(E, T, A, H, precision=prec, **kw)
-    if comm:
-        eng.comm_init(pkg.Engine.comm_unique_id())
-    for k, v in options:
-        eng.set_option(k, v)
-    if clip_on:
-        eng.set_option(pkg.OPT_VALUE_CLIP, 1)
-    eng.load_params(params)
-    obs, actions, old_lp, adv, masks = batch
-    eng.set_batch(obs, actions, old_lp, adv, ret, masks, values=vold)
-    for _ in range(calls):
-        m = eng.train(LR, epochs, M)
-    out = _read(eng, m, epochs, M)
-    eng.close()
-    return out
-
-
-def _read(eng, m, epochs, M):
-    B = eng._batch_n // M
-    out = dict(m=m, params=eng.export_params(), grads=eng.export_grads(), diag=eng.train_diagnostics(epochs, M))
-    out.update({k: eng.read_train_metric(k, epochs, M, B) for k in PER_SAMPLE})
-    return out
-
-
-def _assert_identical(a, b):
-    for k in a["m"]:
-        np.testing.assert_array_equal(a["m"][k], b["m"][k], err_msg=k)
-    for k in ("approx_kl", "clip_fraction"):
-        np.testing.assert_array_equal(a["diag"][k], b["diag"][k], err_msg=k)
-    for k in PER_SAMPLE + ("params", "grads"):
-        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+def _run(pkg, E, T, A, H, prec, params, batch, ret, vold, epochs, M, clip_on=True, options=(), **kw):
+    """uh.run_update at LR, with the option set (after `options`) unless clip_on is False"""
+    clip = [(pkg.OPT_VALUE_CLIP, 1)] if clip_on else []
+    return uh.run_update(pkg, E, T, A, H, params, batch[:4] + (ret, batch[4]), epochs, M, LR, vold=vold, prec=prec,
+                         options=list(options) + clip, **kw)
 
 
 def _check_fp32(out, ref, masks_ep, clip=CLIP, tol=1e-4, params0=None):
     """engine outputs vs the composed reference at the fp32 bounds"""
-    m = out["m"]
-    np.testing.assert_allclose(m["loss"], ref["loss"], atol=tol, rtol=tol)
-    np.testing.assert_allclose(m["grad_norm"], ref["grad_norm"], rtol=tol)
-    for k in PER_SAMPLE:
-        if k == "clip_fraction":
-            continue
-        np.testing.assert_allclose(out[k], ref[REF_PLANE[k]], atol=tol, rtol=tol, err_msg=k)
+    uh.check_against(out, ref, tol, [k for k in PER_SAMPLE if k != "clip_fraction"],
+                     extra=[(out["diag"]["approx_kl"], "mean_approx_kl")])
     # clip fraction: exact except where |rho - 1| is within 1e-6 of the clip
     near = np.abs(np.abs(ref["ratio"].astype(np.float64) - 1) - clip) <= 1e-6
     assert ((out["clip_fraction"] != ref["clip_fraction"]) & ~near).sum() == 0
     assert set(np.unique(out["clip_fraction"])) <= {0.0, 1.0}
-    np.testing.assert_allclose(out["diag"]["approx_kl"], ref["mean_approx_kl"], atol=tol, rtol=tol)
     np.testing.assert_allclose(out["diag"]["clip_fraction"], ref["mean_clip_fraction"], atol=tol)
     # the means are the masked means of the planes the engine returned
     for k in ("approx_kl", "clip_fraction"):
         mine = (out[k].astype(np.float64) * masks_ep).sum(-1) / masks_ep.sum(-1)
         np.testing.assert_allclose(out["diag"][k], mine, rtol=1e-5, atol=1e-7)
-    np.testing.assert_allclose(out["grads"], ref["last_grads"], atol=tol)
-    np.testing.assert_allclose(out["params"], ref["params"], atol=tol)
     if params0 is not None:  # (the update itself, relative: at LR the parameters move by ~1e-4)
         du, dr = out["params"].astype(np.float64) - params0, ref["params"].astype(np.float64) - params0
         assert np.linalg.norm(du - dr) <= 1e-3 * np.linalg.norm(dr) and np.linalg.norm(dr) > 0
@@ -196,7 +122,7 @@ def _fp32_case(pkg):
     E, T, A, H, epochs, M = 8, 32, 6, 64, 2, 4
     N = E * T
     params = hf.fill_params(4200, H, A)
-    obs, actions, old_lp, adv, masks = _batch(4201, N, A)
+    obs, actions, old_lp, adv, masks = _planes(4201, N, A)
     _, v0 = orc.net_forward(params, H, A, obs)
     vold, ret = _values_and_returns(4210, v0)
     return E, T, A, H, epochs, M, params, (obs, actions, old_lp, adv, masks), ret, vold
@@ -207,16 +133,16 @@ def test_fp32_clipped_update_vs_composed_reference(pkg):
     E, T, A, H, epochs, M, params, batch, ret, vold = _fp32_case(pkg)
     obs, actions, old_lp, adv, masks = batch
     B = E * T // M
-    ref = vr.composed_train(params, H, A, obs, actions, old_lp, adv, ret, masks, epochs, M, vold=vold, lr=LR)
+    ref = ur.composed_train(params, H, A, obs, actions, old_lp, adv, ret, masks, epochs, M, vold=vold, lr=LR)
     share = ref["zero_branch"].sum() / (epochs * masks.sum())
     assert 0.2 <= share <= 0.8, share  # the test has teeth: the clipped branch wins for a real share of the samples
-    out = _engine_run(pkg, E, T, A, H, pkg.FP32, params, batch, ret, vold, epochs, M)
+    out = _run(pkg, E, T, A, H, pkg.FP32, params, batch, ret, vold, epochs, M)
     masks_ep = np.broadcast_to(masks.reshape(M, B), (epochs, M, B)).astype(np.float64)
     _check_fp32(out, ref, masks_ep, params0=params)
     assert out["clip_fraction"].sum() > 0 and (out["approx_kl"] >= -1e-6).all()
     # on the first minibatch (same parameters on both sides) the clipped value loss is never below the unclipped one,
     # and differs from it where the clipped branch won
-    unclipped = vr.composed_train(params, H, A, obs, actions, old_lp, adv, ret, masks, 1, M, lr=LR)
+    unclipped = ur.composed_train(params, H, A, obs, actions, old_lp, adv, ret, masks, 1, M, lr=LR)
     # (up to one ulp: the reference's clipped branch is float64, the oracle's unclipped one fp32)
     assert (ref["value_losses"][0, 0] >= unclipped["value_losses"][0, 0] * (1 - 1e-6)).all()
     assert np.abs(out["value_losses"][0, 0] - unclipped["value_losses"][0, 0]).max() > 1e-3
@@ -228,16 +154,16 @@ def test_bf16_clipped_update_at_the_benched_shape_vs_emulated_reference(pkg):
     E, T, A, H, epochs, M = 128, 128, 4, 512, 1, 4
     N = E * T
     params = hf.fill_params(4300, H, A)
-    obs, actions, old_lp, adv, masks = _batch(4301, N, A, distinct=8)
+    obs, actions, old_lp, adv, masks = _planes(4301, N, A, distinct=8)
     eng = pkg.Engine(E, T, A, H, precision=pkg.BF16)
     eng.load_params(params)
     _, v0 = eng.forward(obs)  # (where the values are: the inputs only need to straddle them)
     eng.close()
     vold, ret = _values_and_returns(4310, v0)
-    ref = vr.composed_train(params, H, A, obs, actions, old_lp, adv, ret, masks, epochs, M, vold=vold, lr=LR,
+    ref = ur.composed_train(params, H, A, obs, actions, old_lp, adv, ret, masks, epochs, M, vold=vold, lr=LR,
                             emulate_bf16=True, floor=True)
     assert 0.2 <= ref["zero_branch"].sum() / (epochs * masks.sum()) <= 0.8
-    out = _engine_run(pkg, E, T, A, H, pkg.BF16, params, (obs, actions, old_lp, adv, masks), ret, vold, epochs, M)
+    out = _run(pkg, E, T, A, H, pkg.BF16, params, (obs, actions, old_lp, adv, masks), ret, vold, epochs, M)
     c = bc.Checker()
     planes = {ours: out[ours] for ours, _ in bc.PLANES}
     c.train(H, A, out["m"], planes, None, ref, params0=params, params=out["params"])
@@ -280,11 +206,11 @@ def test_rollout_batch_takes_v_old_from_the_values_plane(pkg, rollout_precision)
                                          "values")}
     eng.set_option(pkg.OPT_VALUE_CLIP, 1)
     m = eng.train(LR, epochs, M)
-    out = _read(eng, m, epochs, M)
+    out = uh.read_update(eng, m, epochs, M)
     eng.close()
     obs = b["observations"].reshape(N, 4, 84, 84)
     vold = b["values"].ravel()  # env-major [E, T], fp16-rounded with fp16 planes
-    ref = vr.composed_train(params, H, A, obs, b["actions"].ravel(), b["log_probs"].reshape(N, A),
+    ref = ur.composed_train(params, H, A, obs, b["actions"].ravel(), b["log_probs"].reshape(N, A),
                             b["advantages"].ravel(), b["returns"].ravel(), b["masks"].ravel(), epochs, M, vold=vold,
                             lr=LR, clip=clip)
     # (the values were stored by this network, so the first minibatch sees v_old = v up to the fp16 rounding; the
@@ -303,20 +229,20 @@ def test_schedules_are_bit_identical_with_clipping(pkg, case):
     else:
         E, T, A, H, epochs, M, prec = 32, 64, 4, 512, 2, 1, pkg.BF16  # (minibatches of 2048: fused backward on)
         params = hf.fill_params(4500, H, A)
-        batch = _batch(4501, E * T, A, distinct=8)
+        batch = _planes(4501, E * T, A, distinct=8)
         vold, ret = _values_and_returns(4510, np.zeros(E * T, np.float32))
     N = E * T
-    run = lambda **kw: _engine_run(pkg, E, T, A, H, prec, params, batch, ret, vold, epochs, M, **kw)  # noqa: E731
+    run = lambda **kw: _run(pkg, E, T, A, H, prec, params, batch, ret, vold, epochs, M, **kw)  # noqa: E731
     base = run()
     # the 1-rank communicator (data-parallel schedule).  (bf16: data parallelism never runs the fused backward kernel,
     # whose summation order differs from the three launches it replaces, so both sides run those)
     if prec == pkg.BF16:
         nofuse = [(pkg.OPT_FUSED_BWD, 0)]
-        _assert_identical(run(options=nofuse + [(pkg.OPT_FORCE_COMM, 1)], comm=True), run(options=nofuse))
+        assert_identical(run(options=nofuse + [(pkg.OPT_FORCE_COMM, 1)], comm=True), run(options=nofuse))
     else:
-        _assert_identical(run(options=[(pkg.OPT_FORCE_COMM, 1)], comm=True), base)
+        assert_identical(run(options=[(pkg.OPT_FORCE_COMM, 1)], comm=True), base)
     # graph replay: eager (warm-up), capture + launch, replay == three eager calls
-    _assert_identical(run(options=[(pkg.OPT_UPDATE_GRAPH, 1)], calls=3), run(calls=3))
+    assert_identical(run(options=[(pkg.OPT_UPDATE_GRAPH, 1)], calls=3), run(calls=3))
     # shuffled == contiguous on the host-permuted batch, values permuted with it
     eng = pkg.Engine(E, T, A, H, precision=prec)
     eng.set_option(pkg.OPT_VALUE_CLIP, 1)
@@ -326,7 +252,7 @@ def test_schedules_are_bit_identical_with_clipping(pkg, case):
     eng.set_batch(obs, actions, old_lp, adv, ret, masks, values=vold)
     m = eng.train(LR, epochs, M)
     order = eng.sample_order(epochs)
-    shuf = _read(eng, m, epochs, M)
+    shuf = uh.read_update(eng, m, epochs, M)
     eng.close()
     assert (order != np.arange(N)[None]).any()
     eng = pkg.Engine(E, T, A, H, precision=prec)
@@ -336,7 +262,7 @@ def test_schedules_are_bit_identical_with_clipping(pkg, case):
         o = order[e]
         eng.set_batch(obs[o], actions[o], old_lp[o], adv[o], ret[o], masks[o], values=vold[o])
         me = eng.train(LR, 1, M)
-        ce = _read(eng, me, 1, M)
+        ce = uh.read_update(eng, me, 1, M)
         for k in me:
             np.testing.assert_array_equal(me[k][0], shuf["m"][k][e], err_msg=k)
         for k in PER_SAMPLE:
@@ -363,7 +289,7 @@ def test_toggling_between_graph_replays_matches_a_fresh_eager_context(pkg):
         for v in seq:
             if eng.get_option(pkg.OPT_VALUE_CLIP) != v:
                 eng.set_option(pkg.OPT_VALUE_CLIP, v)
-            outs.append(_read(eng, eng.train(LR, epochs, M), epochs, M))
+            outs.append(uh.read_update(eng, eng.train(LR, epochs, M), epochs, M))
         replays = eng.get_option(pkg.OPT_UPDATE_GRAPH)
         eng.close()
         return outs, replays
@@ -372,14 +298,14 @@ def test_toggling_between_graph_replays_matches_a_fresh_eager_context(pkg):
     e, _ = drive(False)
     assert replays >= 4  # (per run of equal settings: eager, capture + launch, replay)
     for a, b in zip(g, e):
-        _assert_identical(a, b)
+        assert_identical(a, b)
     assert (g[2]["value_losses"] != g[3]["value_losses"]).any()
 
 
 @pytest.mark.gpu
 def test_option_off_restores_the_default(pkg):
     E, T, A, H, epochs, M, params, batch, ret, vold = _fp32_case(pkg)
-    never = _engine_run(pkg, E, T, A, H, pkg.FP32, params, batch, ret, None, epochs, M, clip_on=False)
+    never = _run(pkg, E, T, A, H, pkg.FP32, params, batch, ret, None, epochs, M, clip_on=False)
     eng = pkg.Engine(E, T, A, H, precision=pkg.FP32)
     assert eng.get_option(pkg.OPT_VALUE_CLIP) == 0
     eng.set_option(pkg.OPT_VALUE_CLIP, 1)
@@ -391,11 +317,11 @@ def test_option_off_restores_the_default(pkg):
     eng.load_params(params)
     obs, actions, old_lp, adv, masks = batch
     eng.set_batch(obs, actions, old_lp, adv, ret, masks, values=vold)  # (values given, clipping off: unused)
-    toggled = _read(eng, eng.train(LR, epochs, M), epochs, M)
+    toggled = uh.read_update(eng, eng.train(LR, epochs, M), epochs, M)
     eng.close()
-    _assert_identical(toggled, never)
+    assert_identical(toggled, never)
     # the diagnostics with clipping off against the reference (= orc.train for everything else)
-    ref = vr.composed_train(params, H, A, obs, actions, old_lp, adv, ret, masks, epochs, M, lr=LR)
+    ref = ur.composed_train(params, H, A, obs, actions, old_lp, adv, ret, masks, epochs, M, lr=LR)
     B = E * T // M
     _check_fp32(never, ref, np.broadcast_to(masks.reshape(M, B), (epochs, M, B)).astype(np.float64), params0=params)
 
@@ -404,7 +330,7 @@ def test_option_off_restores_the_default(pkg):
 def test_error_cases(pkg):
     E, T, A, H = 4, 8, 4, 32
     N = E * T
-    obs, actions, old_lp, adv, masks = _batch(4600, N, A)
+    obs, actions, old_lp, adv, masks = _planes(4600, N, A)
     ret = hf.hf_range(4606, (N,), -1, 1)
     eng = pkg.Engine(E, T, A, H, precision=pkg.FP32)
     eng.load_params(hf.fill_params(4601, H, A))
@@ -435,7 +361,7 @@ def test_one_call_equals_one_epoch_calls(pkg, prec, shuffle):
     N = E * T
     p = pkg.BF16 if prec == "bf16" else pkg.FP32
     params = hf.fill_params(4700, H, A)
-    obs, actions, old_lp, adv, masks = _batch(4701, N, A)
+    obs, actions, old_lp, adv, masks = _planes(4701, N, A)
     _, v0 = orc.net_forward(params, H, A, obs)
     vold, ret = _values_and_returns(4710, v0)
     outs = []
@@ -446,24 +372,12 @@ def test_one_call_equals_one_epoch_calls(pkg, prec, shuffle):
         eng.load_params(params)
         eng.set_batch(obs, actions, old_lp, adv, ret, masks, values=vold)
         if split:
-            parts = [_read(eng, eng.train(LR, 1, M), 1, M) for _ in range(4)]
-            o = dict(m={k: np.concatenate([q["m"][k] for q in parts]) for k in parts[0]["m"]},
-                     diag={k: np.concatenate([q["diag"][k] for q in parts]) for k in ("approx_kl", "clip_fraction")},
-                     params=parts[-1]["params"], grads=parts[-1]["grads"])
-            o.update({k: np.concatenate([q[k] for q in parts]) for k in PER_SAMPLE})
+            o = uh.concat_updates([uh.read_update(eng, eng.train(LR, 1, M), 1, M) for _ in range(4)])
         else:
-            o = _read(eng, eng.train(LR, 4, M), 4, M)
+            o = uh.read_update(eng, eng.train(LR, 4, M), 4, M)
         outs.append(o)
         eng.close()
-    _assert_identical(outs[0], outs[1])
-
-
-@pytest.fixture(scope="module")
-def trainer():
-    from __graft_entry__ import build
-    build()
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "trainer")])
-    return os.path.join(ROOT, "trainer", "train")
+    assert_identical(outs[0], outs[1])
 
 
 @pytest.mark.gpu
@@ -477,7 +391,7 @@ def test_trainer_target_kl_on_the_device(trainer, tmp_path, target_kl, epochs):
     assert r.returncode == 0, r.stderr[-2000:]
     blob = _events(tmp_path / "tb")
     assert b"clip_value_loss" in blob
-    assert _scalars(blob, "update_epochs") == [float(epochs)] * 3
-    kl = _scalars(blob, "mean_approx_kl")
+    assert event_scalars(blob, "update_epochs") == [float(epochs)] * 3
+    kl = event_scalars(blob, "mean_approx_kl")
     assert len(kl) == 3 and all(np.isfinite(kl)) and min(kl) > 0
-    assert len(_scalars(blob, "mean_clip_fraction")) == 3
+    assert len(event_scalars(blob, "mean_clip_fraction")) == 3
