@@ -85,6 +85,10 @@ EMA_STATS_COUNT = 6
 EMA_STATS = dict(updates=0, decay=1, norm=2, param_norm=3, distance=4, relative_distance=5)
 # aleppo_saliency_config's defaults (Engine.saliency / Engine.saliency_perturbed / saliency_tables)
 SALIENCY_STRIDE, SALIENCY_SIGMA_MASK, SALIENCY_SIGMA_BLUR, SALIENCY_PLANES = 5, 5.0, 3.0, 15
+# aleppo_feature_rank: the indices of its ALEPPO_FR_COUNT doubles (aleppo_feature_rank_stat; Engine.feature_rank)
+FR_COUNT = 11
+FR_STATS = dict(rows=0, nonfinite_rows=1, sigma_max=2, sigma_min=3, mean_sq_norm=4, effective_rank=5, srank=6, pca_rank=7,
+                threshold_rank=8, stable_rank=9, numerical_rank=10)
 # aleppo_eval_rule / aleppo_eval_field: the evaluation lanes (Engine.eval_open / eval_push_frames / eval_act / eval_read)
 EVAL_GREEDY, EVAL_SAMPLE, EVAL_EPSILON_GREEDY = 0, 1, 2
 EVAL_RULES = dict(greedy=EVAL_GREEDY, sample=EVAL_SAMPLE, epsilon=EVAL_EPSILON_GREEDY)
@@ -170,6 +174,7 @@ EXPORTS = [
     "aleppo_recycle_units", "aleppo_recycle_dormant",
     "aleppo_ema_open", "aleppo_ema_update", "aleppo_ema_read", "aleppo_ema_export", "aleppo_ema_import",
     "aleppo_saliency_tables", "aleppo_saliency", "aleppo_saliency_perturbed",
+    "aleppo_feature_rank",
     "aleppo_env_open", "aleppo_env_rollout", "aleppo_env_export_state", "aleppo_env_import_state", "aleppo_env_read",
     "aleppo_eval_env_open", "aleppo_eval_env_run", "aleppo_eval_env_export_state", "aleppo_eval_env_import_state",
     "aleppo_eval_env_read",
@@ -198,6 +203,10 @@ class Config(C.Structure):
 
 class SaliencyConfig(C.Structure):
     _fields_ = [("stride", C.c_int32), ("planes", C.c_int32), ("sigma_mask", C.c_double), ("sigma_blur", C.c_double)]
+
+
+class FeatureRankConfig(C.Structure):
+    _fields_ = [("delta", C.c_float), ("eps", C.c_float), ("centered", C.c_int32), ("reserved", C.c_int32)]
 
 
 class EnvConfig(C.Structure):
@@ -859,6 +868,24 @@ class Engine:
                                              C.c_int(RECYCLE_KEEP_MOMENTS if keep_moments else 0), _ptr(mask),
                                              C.c_size_t(mask.size), _ptr(counts)))
         return mask, {l: int(counts[k]) for k, l in enumerate(ACT_LAYER_ROWS)}
+
+    def feature_rank(self, observations=None, delta=0.01, eps=0.01, centered=False, spectrum=False, gram=False):
+        """aleppo_feature_rank: the rank measures of the fc features from a Gram matrix formed on the device - of the batch
+        the context holds (observations=None) or of uint8 [n,4,84,84] observations.  {"stats": {name: float} over FR_STATS,
+        "sigma": float64 [H] (descending) with spectrum=True, "gram": float64 [H,H] and "colsum": float64 [H] with
+        gram=True; None otherwise}.  centered: the spectrum of the centred features (PCA); "gram" is never centred."""
+        obs = None if observations is None else _u8(observations)
+        n = 0 if obs is None else obs.shape[0]
+        cfg = FeatureRankConfig(delta, eps, int(centered), 0)
+        stats = np.zeros(FR_COUNT, np.float64)
+        sg = np.zeros(self.H, np.float64) if spectrum else None
+        g = np.zeros((self.H, self.H), np.float64) if gram else None
+        cs = np.zeros(self.H, np.float64) if gram else None
+        self._c(lib().aleppo_feature_rank(self._ctx, _ptr(obs), C.c_int64(n), C.byref(cfg), _ptr(stats),
+                                          C.c_size_t(stats.size), _ptr(sg), C.c_size_t(0 if sg is None else sg.size),
+                                          _ptr(g), C.c_size_t(0 if g is None else g.size), _ptr(cs),
+                                          C.c_size_t(0 if cs is None else cs.size)))
+        return dict(stats={k: float(stats[i]) for k, i in FR_STATS.items()}, sigma=sg, gram=g, colsum=cs)
 
     def _saliency_source(self, observations, first, n):
         obs = None if observations is None else _u8(observations)

@@ -265,6 +265,9 @@ struct Ctx {
   float *ax_buf = nullptr;
   size_t ax_cap = 0;                    // bytes
   void *as_scratch = nullptr;
+  // ---- aleppo_feature_rank: the Gram blocks, column sums, split partials and row flags (allocated on first use; its size
+  // is a function of (H, maxB))
+  void *fr_scratch = nullptr;
   // ---- aleppo_recycle_units / aleppo_recycle_dormant: the unit mask, uint8 [160 + H] (allocated on first use)
   uint8_t *rc_mask = nullptr;
   // ---- aleppo_ema_open: the exponentially averaged parameters; nothing below is allocated, and nothing is enqueued for it,
@@ -501,6 +504,21 @@ void launch_act_stats_partial(hipStream_t s, int prec, const void *a1, const voi
 void launch_act_stats_final(hipStream_t s, int H, long total, double tau, const ActStatsPlan &pl, const size_t done[4],
                             void *scratch, const double **units_dev, const double **layers_dev);
 void launch_act_export(hipStream_t s, int prec, int layer, const void *a, float *out, long ns);
+// aleppo_feature_rank (feature_rank.hip).  The plan is a function of (H, maxB): nb 64-column blocks, tiles = nb (nb + 1) / 2
+// upper blocks of 4096 doubles.  Scratch: the result - double [tiles][64][64] blocks of G, [H] column sums, [2] (the rows
+// left out, a pad) - then the partial results of up to FR_MAX_SPLITS row splits in the same form, then the row flags
+// (uint32 [maxB], 1 = every feature of the row is finite).  launch_feature_rank_chunk: the three launches of one forward
+// chunk h [ns][H] - flags, Gram + column sums per split, the reduce that adds the splits in order and sets (first) or adds
+// to the result.  fr_tile: the block of G that holds element (i, j), i <= j.
+constexpr int FR_MAX_SPLITS = 16, FR_SPLIT_ROWS = 256;
+struct FeatureRankPlan {
+  int H, nb, tiles;
+  size_t result_doubles; // tiles * 4096 + H + 2
+  size_t bytes;
+};
+FeatureRankPlan feature_rank_plan(int H, long maxB);
+inline size_t fr_tile(int nb, int bi, int bj) { return (size_t)bi * nb - (size_t)bi * (bi - 1) / 2 + (size_t)(bj - bi); }
+void launch_feature_rank_chunk(hipStream_t s, const float *h, long ns, bool first, const FeatureRankPlan &pl, void *scratch);
 // aleppo_recycle_units / aleppo_recycle_dormant (recycle.hip).  mask: uint8 [160 + H] in device memory, 4-byte aligned, in
 // the unit order of aleppo_activation_stats.  launch_recycle_mask forms it from that entry point's device-side unit table
 // (mask[u] = layer bit of u in layers && SCORE_u <= tau); launch_recycle is the one pass over P / M1 / M2 in the internal

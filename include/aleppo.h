@@ -468,7 +468,8 @@ int aleppo_read_batch(aleppo_ctx *ctx, int field, void *dst, size_t bytes);
 int aleppo_forward(aleppo_ctx *ctx, const uint8_t *observations, int64_t n, float *logits, float *values);
 
 /* The hidden activations of that forward pass (what a forward hook gives a CleanRL / SB3 user; the reference has none):
- * for feature rank (SVD of fc), linear probes, embedding plots, and as the ground truth of aleppo_activation_stats.
+ * for linear probes, embedding plots, a feature rank of one's own (aleppo_feature_rank has the usual ones), and as the
+ * ground truth of aleppo_activation_stats.
  * observations and n as aleppo_forward: host uint8 [n,4,84,84], 1 <= n <= max(E, max_minibatch).  Each output may be NULL
  * (that layer is neither converted nor copied); at least one must be given.  Outputs, host float, in the reference's
  * tensor order (NCHW; the channel index is the reference's output-channel index):
@@ -703,6 +704,80 @@ int aleppo_saliency(aleppo_ctx *ctx, const uint8_t *observations, int64_t first,
 int aleppo_saliency_perturbed(aleppo_ctx *ctx, const uint8_t *observations, int64_t first, int64_t n,
                               const aleppo_saliency_config *cfg, int64_t position_first, int64_t position_count,
                               uint8_t *out);
+
+/* Feature rank: the spectrum of the penultimate features from a Gram matrix formed on the device (Kumar et al. 2021,
+ * "Implicit Under-Parameterization"; Lyle et al. 2022, "Understanding and Preventing Capacity Loss"; Moalla et al. 2024,
+ * whose feature-rank collapse precedes PPO's; the reference has none).  Phi is the fc output [rows, H] as stored: fp32 on
+ * both precisions, bias included, no ReLU - what aleppo_forward_activations exports as fc.  Neither an observation of the
+ * batch nor a feature leaves the device: only G = Phi^T Phi (H x H doubles) and the H column sums do.
+ * Samples: exactly those of aleppo_activation_stats.  observations == NULL and n == 0: the batch the context holds,
+ *   masked samples included, read in place in logical order in forward chunks of at most maxB = max(E, max_minibatch);
+ *   otherwise the caller's n <= maxB observations.  Never a collective: under data parallelism it describes this rank's
+ *   samples.
+ * On the device: a row with any non-finite feature is counted (NONFINITE_ROWS) and left out; it contributes nothing to
+ *   G, to the column sums or to n.  Over the n rows that remain
+ *     G[i][j] = sum_r (double)Phi[r][i] * (double)Phi[r][j]        s[i] = sum_r (double)Phi[r][i]
+ *   A product of two widened fp32 values is exact in double, so only the order of the additions matters, and that order
+ *   is a function of (row count, maxB, H) only:
+ *     - per forward chunk of ns rows: S = min(16, ceil(ns / 256)) row splits of R = 4 * ceil(ceil(ns / S) / 4) rows each
+ *       (the last may be shorter);
+ *     - inside a split the rows enter four at a time, in row order, through v_mfma_f64_16x16x4_f64 (D = A B + C: the four
+ *       products of one instruction are added to the accumulator by the hardware in its fixed order); a left-out row
+ *       and a row past the split's end enter as zeros and are never read.  s: thread q of four adds rows q, q + 4, ...
+ *       of the split in order, then the four are added as ((0 + 1) + 2) + 3;
+ *     - a reduce launch adds the S partial results of the chunk in split order, t = ((p0 + p1) + p2) + ..., and carries
+ *       the total across the forward chunks in chunk order: G = t for the first chunk, G = G + t for every later one.
+ *   Only 64 x 64 blocks with i-block <= j-block are computed (and of a diagonal block only the 32 x 32 quarters on or
+ *   above the diagonal); every G[i][j] with i > j is a copy of G[j][i]: the same bits.  No floating-point atomics; the
+ *   grid does not depend on the device.  Two calls with nothing in between are bit-identical, and with at most maxB
+ *   samples the batch source equals the caller source on the same observations, bit for bit.
+ * On the host, inside the library (plain C++ in double, single-threaded, no LAPACK; csrc/feature_rank_host.hpp):
+ *   centered != 0: Gc[i][j] = G[i][j] - (s[i] * s[j]) / n, in this order of operations - PCA of the features.  The
+ *   eigenvalues lambda_1 >= ... >= lambda_H of G (or Gc) come from Householder tridiagonalisation and implicit-shift QL
+ *   (values only), on the matrix scaled by an exact power of two; deterministic.  sigma_i = sqrt(max(lambda_i, 0)) are the
+ *   singular values of Phi (of the centred Phi).  With S1 = sum sigma_i and S2 = sum sigma_i * sigma_i, both in index
+ *   order, the stats are those of aleppo_feature_rank_stat.  With n == 0 or S1 == 0 every rank is 0 and every other stat
+ *   but ROWS and NONFINITE_ROWS is 0.
+ * Accuracy: the Gram route squares the condition number - an eigenvalue carries an absolute error of about
+ *   H * 2^-53 * lambda_1, so singular values below about sqrt(H * 2^-53) * sigma_1 (2.4e-7 sigma_1 at H = 512) are rounding
+ *   noise.  That is below the 2^-24 relative precision fp32 features carry, and far below every threshold above.
+ * cfg: NULL means delta = 0.01, eps = 0.01, centered = 0.  stats: double [ALEPPO_FR_COUNT].  sigma: NULL or double [H],
+ *   descending.  gram: NULL or double [H * H], row-major, the full symmetric matrix G (never Gc).  colsum: NULL or double
+ *   [H], s.
+ * Computed WHEN CALLED, on the context's stream: the stream's synchronise; per forward chunk the forward pass, one launch
+ *   that flags the non-finite rows, one Gram launch and one reduce launch; one copy of G and s; the host solve.  Like
+ *   aleppo_forward it runs the network in the shared activation scratch, so what aleppo_step pre-computed for the next
+ *   aleppo_act is dropped (the act recomputes it: same bits).  Scratch (20.1 MB at H = 512, 0.6 MB at H = 32) is allocated on first use and kept
+ *   until aleppo_destroy.  aleppo_train, a captured update (ALEPPO_OPT_UPDATE_GRAPH) and every other entry point enqueue
+ *   nothing for it; a context that never calls it allocates and enqueues exactly what it did before, and calling it
+ *   changes no bit of the run.
+ * Errors: a NULL stats or stat_count != ALEPPO_FR_COUNT, a non-NULL output with a wrong count, delta not in (0, 1), eps
+ *   negative or not finite, centered not 0 or 1, reserved != 0, and what aleppo_activation_stats refuses in observations and
+ *   n: ALEPPO_ERR_INVALID_ARGUMENT.  The batch source without a batch, or any call while a step is armed:
+ *   ALEPPO_ERR_RUNTIME.  A failed call writes nothing. */
+typedef struct {
+  float delta;      /* the share of the spectrum SRANK and PCA_RANK may leave out, in (0, 1) */
+  float eps;        /* THRESHOLD_RANK's threshold on sigma_i / sqrt(n), finite and >= 0 */
+  int32_t centered; /* 0: the spectrum of G; 1: of Gc */
+  int32_t reserved; /* must be 0 */
+} aleppo_feature_rank_config; /* 16 bytes */
+typedef enum {
+  ALEPPO_FR_ROWS = 0,           /* n: the rows that entered */
+  ALEPPO_FR_NONFINITE_ROWS = 1, /* rows left out */
+  ALEPPO_FR_SIGMA_MAX = 2,      /* sigma_1 */
+  ALEPPO_FR_SIGMA_MIN = 3,      /* sigma_H */
+  ALEPPO_FR_MEAN_SQ_NORM = 4,   /* (sum of G's diagonal, in index order) / n: the mean squared feature norm (Moalla et al.) */
+  ALEPPO_FR_EFFECTIVE_RANK = 5, /* exp(-sum p_i ln p_i), p_i = sigma_i / S1, 0 ln 0 = 0 (Roy & Vetterli 2007) */
+  ALEPPO_FR_SRANK = 6,          /* smallest k with sum_{i<=k} sigma_i >= (1 - delta) S1 (Kumar et al. 2021) */
+  ALEPPO_FR_PCA_RANK = 7,       /* smallest k with sum_{i<=k} sigma_i^2 >= (1 - delta) S2 (Yang et al. 2020) */
+  ALEPPO_FR_THRESHOLD_RANK = 8, /* #{i : sigma_i / sqrt(n) > eps} (Lyle et al. 2022) */
+  ALEPPO_FR_STABLE_RANK = 9,    /* S2 / sigma_1^2 */
+  ALEPPO_FR_NUMERICAL_RANK = 10 /* #{i : sigma_i > max(n, H) * 2^-23 * sigma_1} (numpy.linalg.matrix_rank on float32) */
+} aleppo_feature_rank_stat;
+#define ALEPPO_FR_COUNT 11
+int aleppo_feature_rank(aleppo_ctx *ctx, const uint8_t *observations, int64_t n, const aleppo_feature_rank_config *cfg,
+                        double *stats, size_t stat_count, double *sigma, size_t sigma_count, double *gram,
+                        size_t gram_count, double *colsum, size_t colsum_count);
 
 /* ------------------------------------------------------------------ evaluation lanes (the reference has no evaluation
  * loop: SB3's predict(deterministic=True) / EvalCallback, the epsilon-greedy scores of the DQN / PPO papers)
@@ -1056,7 +1131,8 @@ typedef enum {
   ALEPPO_K_CONV_FWD = 18,   /* conv1 -> conv2 -> conv3 of the update's forward pass in one launch (bf16) */
   ALEPPO_K_CONV_BWD = 19,   /* conv2 dgrad + conv2 wgrad + conv1 wgrad of the update's backward pass in one launch (bf16) */
   ALEPPO_K_REC_CAPTURE = 20, /* the episode recorders' capture kernel (aleppo_rec_open), one launch per recorded step */
-  ALEPPO_K_ACT_STATS = 21,  /* aleppo_activation_stats' read-only pass over a1 / a2 / a3 / h, one launch per forward chunk */
+  ALEPPO_K_ACT_STATS = 21,  /* the read-only passes over the activations, one bracket per forward chunk: aleppo_activation_stats' launch,
+                               aleppo_feature_rank's three (flags, Gram, reduce) */
   ALEPPO_K_RECYCLE = 22,    /* the masked pass of aleppo_recycle_units / aleppo_recycle_dormant over P / M1 / M2, one launch per call */
   ALEPPO_K_SAL_BLUR = 23,    /* aleppo_saliency's blur of the samples a forward chunk touches */
   ALEPPO_K_SAL_PERTURB = 24, /* ... its blend of one chunk's perturbed stacks into the staging buffer */

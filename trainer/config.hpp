@@ -58,6 +58,10 @@ struct Config {
   bool log_activation_stats = false;
   size_t activation_stats_interval = 1; // after the update of every n-th rollout
   double dormant_tau = 0.025;           // the dormancy threshold (Sokar et al. 2023)
+  // extension: the rank measures of the fc features on the batch (aleppo_feature_rank), after the update of every n-th rollout
+  bool log_feature_rank = false;
+  size_t feature_rank_interval = 1;
+  aleppo_feature_rank_config feature_rank{0.01f, 0.01f, 0, 0}; // delta, eps, centered
   // extension: ReDo (Sokar et al. 2023) - recycle the dormant units of the held batch (aleppo_recycle_dormant)
   bool recycle_dormant = false;
   // after the update of every n-th rollout.  64: ReDo recycles every 1000 gradient steps; the benched configuration takes
@@ -180,6 +184,23 @@ static Config load_config(const std::string &path) { // keys / defaults of src/b
     for (const char *k : {"activation_stats_interval", "dormant_tau"})
       if (kv.count(k) && !c.log_activation_stats) // (nothing else reads them)
         throw std::runtime_error(std::string(k) + " needs log_activation_stats: true");
+  }
+  read_key(kv, "log_feature_rank", c.log_feature_rank);
+  { // what aleppo_feature_rank would refuse is refused here ("nan" / "inf" do not parse as a number: bad value)
+    const long interval = as<long>(kv, "feature_rank_interval", 1);
+    if (interval < 1)
+      throw std::runtime_error("feature_rank_interval must be positive");
+    c.feature_rank_interval = (size_t)interval;
+    read_key(kv, "feature_rank_delta", c.feature_rank.delta);
+    if (!(c.feature_rank.delta > 0 && c.feature_rank.delta < 1))
+      throw std::runtime_error("feature_rank_delta must be in (0, 1)");
+    read_key(kv, "feature_rank_eps", c.feature_rank.eps);
+    if (!(c.feature_rank.eps >= 0 && std::isfinite(c.feature_rank.eps)))
+      throw std::runtime_error("feature_rank_eps must be finite and non-negative");
+    c.feature_rank.centered = as_bool(kv, "feature_rank_centered", false) ? 1 : 0;
+    for (const char *k : {"feature_rank_interval", "feature_rank_delta", "feature_rank_eps", "feature_rank_centered"})
+      if (kv.count(k) && !c.log_feature_rank) // (nothing else reads them)
+        throw std::runtime_error(std::string(k) + " needs log_feature_rank: true");
   }
   read_key(kv, "recycle_dormant", c.recycle_dormant);
   { // what aleppo_recycle_dormant would refuse is refused here
@@ -429,6 +450,7 @@ static HParams hparams_of(const Config &c) {
                                                     {"log_batch_stats", c.log_batch_stats},
                                                     {"log_tensor_stats", c.log_tensor_stats},
                                                     {"log_activation_stats", c.log_activation_stats},
+                                                    {"log_feature_rank", c.log_feature_rank},
                                                     {"recycle_dormant", c.recycle_dormant},
                                                     {"record_saliency", c.record_saliency},
                                                     {"reward_scaling", c.reward_scaling},

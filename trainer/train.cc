@@ -65,6 +65,12 @@
 // trainer/saliency.hpp has the format - the newest frame as luma, the actor's saliency in blue, the critic's in red; it comes
 // after the statistics above and before a recycle, so it shows the network the update left; never a collective; the four
 // other keys without record_saliency, values aleppo_saliency would refuse and a library without the entry point are refused
+// at start-up).  log_feature_rank: false (true: after the update of every feature_rank_interval-th rollout - default 1 - rank 0
+// calls aleppo_feature_rank on the batch the context holds, with feature_rank_delta - default 0.01 -, feature_rank_eps -
+// default 0.01 - and feature_rank_centered - default false -, and logs feature_rank/effective, /srank, /pca, /threshold,
+// /stable, /numerical, /sigma_max, /sigma_min, /mean_sq_norm and /nonfinite_rows; it comes after the activation statistics
+// and before a recycle, which changes the weights; never a collective: the figures describe rank 0's samples; the four other
+// keys without log_feature_rank, values aleppo_feature_rank would refuse and a library without the entry point are refused
 // at start-up).  clip_param_final, value_loss_coef_final, entropy_coef_final,
 // max_gradient_norm_final (absent: the value stays what the config says and no option is set; given: rollout i of
 // num_rollouts updates with v0 + (v_final - v0) * i / num_rollouts, computed in double and rounded to float once - the
@@ -180,6 +186,8 @@
 #pragma weak aleppo_activation_stats
 // ... and the recycling of dormant units (recycle_dormant: true)
 #pragma weak aleppo_recycle_dormant
+// ... and the feature rank (log_feature_rank: true)
+#pragma weak aleppo_feature_rank
 // (record_saliency: true - aleppo_saliency is declared weak in saliency.hpp)
 // ... and the exponentially averaged parameters (ema_decay)
 #pragma weak aleppo_ema_open
@@ -348,6 +356,9 @@ static void refuse_missing_entry_points(const Config &cfg) {
   if (cfg.ema_decay_set && !(aleppo_ema_open && aleppo_ema_update && aleppo_ema_read && aleppo_ema_export && aleppo_ema_import))
     throw std::runtime_error("ema_decay is set but this build's library has no averaged parameters "
                              "(aleppo_ema_open is missing)");
+  if (cfg.log_feature_rank && !aleppo_feature_rank)
+    throw std::runtime_error("log_feature_rank is set but this build's library has no feature rank "
+                             "(aleppo_feature_rank is missing)");
   if (cfg.record_saliency && !aleppo_saliency)
     throw std::runtime_error("record_saliency is set but this build's library has no saliency maps "
                              "(aleppo_saliency is missing)");
@@ -734,6 +745,8 @@ struct Update {
   bool act_stats_read = false; // log_activation_stats, rank 0: this rollout is one of the interval's, act_layers is its table
   double act_layers[ALEPPO_ACT_LAYER_ROWS][ALEPPO_ACT_LAYER_COLS] = {};
   std::vector<double> act_units; // [(160 + H) * ALEPPO_ACT_UNIT_COLS] (the call fills it; only the layer table is logged)
+  bool feature_rank_read = false; // log_feature_rank, rank 0: this rollout is one of the interval's, feature_rank holds it
+  double feature_rank[ALEPPO_FR_COUNT] = {};
   bool recycled = false; // recycle_dormant: this rollout is one of the interval's, recycle_counts is what it recycled
   int64_t recycle_counts[ALEPPO_RECYCLE_COUNTS] = {};
   double ema_decay_now = 0;                       // ema_decay: the decay this rollout's aleppo_ema_update ran with ...
@@ -813,6 +826,13 @@ static void update(Run &run, size_t r, Update &u) {
     u.act_units.resize((size_t)(160 + cfg.hidden_size) * ALEPPO_ACT_UNIT_COLS);
     check(ctx, aleppo_activation_stats(ctx, nullptr, 0, cfg.dormant_tau, u.act_units.data(), u.act_units.size(),
                                        &u.act_layers[0][0], (size_t)ALEPPO_ACT_LAYER_ROWS * ALEPPO_ACT_LAYER_COLS));
+  }
+  // the feature rank of the batch this update trained on, under the new weights (not a collective: rank 0's samples)
+  u.feature_rank_read = cfg.log_feature_rank && run.rank == 0 && (r + 1) % cfg.feature_rank_interval == 0;
+  if (u.feature_rank_read) {
+    Profile::Span sp(&run.prof, "aleppo_feature_rank");
+    check(ctx, aleppo_feature_rank(ctx, nullptr, 0, &cfg.feature_rank, u.feature_rank, ALEPPO_FR_COUNT, nullptr, 0, nullptr,
+                                   0, nullptr, 0));
   }
   // the saliency video of environment 0: the batch this update trained on, under the new weights (not a collective)
   if (cfg.record_saliency && run.rank == 0 && (r + 1) % cfg.saliency_interval == 0) {
@@ -912,6 +932,15 @@ static void log_scalars(Run &run, const EpisodeLog &log, const BatchStatistics &
     }
     logger.add_scalar("activation_stats/nonfinite", step,
                       (float)u.act_layers[ALEPPO_ACT_LAYER_ROWS - 1][ALEPPO_ACT_L_NONFINITE]);
+  }
+  if (u.feature_rank_read) { // (of the batch this update trained on; set on rank 0 only)
+    static const std::pair<const char *, int> tags[] = {
+        {"effective", ALEPPO_FR_EFFECTIVE_RANK}, {"srank", ALEPPO_FR_SRANK}, {"pca", ALEPPO_FR_PCA_RANK},
+        {"threshold", ALEPPO_FR_THRESHOLD_RANK}, {"stable", ALEPPO_FR_STABLE_RANK}, {"numerical", ALEPPO_FR_NUMERICAL_RANK},
+        {"sigma_max", ALEPPO_FR_SIGMA_MAX}, {"sigma_min", ALEPPO_FR_SIGMA_MIN}, {"mean_sq_norm", ALEPPO_FR_MEAN_SQ_NORM},
+        {"nonfinite_rows", ALEPPO_FR_NONFINITE_ROWS}};
+    for (const auto &t : tags)
+      logger.add_scalar(std::string("feature_rank/") + t.first, step, (float)u.feature_rank[t.second]);
   }
   if (u.recycled) {
     for (int k = 0; k < 4; ++k)
