@@ -89,6 +89,16 @@ SALIENCY_STRIDE, SALIENCY_SIGMA_MASK, SALIENCY_SIGMA_BLUR, SALIENCY_PLANES = 5, 
 FR_COUNT = 11
 FR_STATS = dict(rows=0, nonfinite_rows=1, sigma_max=2, sigma_min=3, mean_sq_norm=4, effective_rank=5, srank=6, pca_rank=7,
                 threshold_rank=8, stable_rank=9, numerical_rank=10)
+# aleppo_snapshot_take / aleppo_policy_diff: the parameter sets, the indices of the ALEPPO_PD_COUNT doubles
+# (aleppo_policy_diff_stat) and the columns of a per-sample row (Engine.snapshot_take / Engine.policy_diff)
+SET_LIVE, SET_AVERAGED, SET_SNAPSHOT = 0, 1, 2
+SETS = dict(live=SET_LIVE, averaged=SET_AVERAGED, snapshot=SET_SNAPSHOT)
+PD_COUNT = 16
+PD_ROW = 8
+PD_STATS = dict(rows=0, nonfinite_rows=1, churn=2, mean_kl_ab=3, max_kl_ab=4, mean_kl_ba=5, mean_tv=6, max_tv=7,
+                mean_abs_dv=8, max_abs_dv=9, rms_dv=10, mean_entropy_a=11, mean_entropy_b=12, mean_feature_cos=13,
+                min_feature_cos=14, feature_rel_change=15)
+PD_COLUMNS = dict(kl_ab=0, kl_ba=1, tv=2, dv=3, cos=4, dh2=5, g_a=6, g_b=7)
 # aleppo_eval_rule / aleppo_eval_field: the evaluation lanes (Engine.eval_open / eval_push_frames / eval_act / eval_read)
 EVAL_GREEDY, EVAL_SAMPLE, EVAL_EPSILON_GREEDY = 0, 1, 2
 EVAL_RULES = dict(greedy=EVAL_GREEDY, sample=EVAL_SAMPLE, epsilon=EVAL_EPSILON_GREEDY)
@@ -175,6 +185,7 @@ EXPORTS = [
     "aleppo_ema_open", "aleppo_ema_update", "aleppo_ema_read", "aleppo_ema_export", "aleppo_ema_import",
     "aleppo_saliency_tables", "aleppo_saliency", "aleppo_saliency_perturbed",
     "aleppo_feature_rank",
+    "aleppo_snapshot_take", "aleppo_snapshot_export", "aleppo_snapshot_import", "aleppo_policy_diff",
     "aleppo_env_open", "aleppo_env_rollout", "aleppo_env_export_state", "aleppo_env_import_state", "aleppo_env_read",
     "aleppo_eval_env_open", "aleppo_eval_env_run", "aleppo_eval_env_export_state", "aleppo_eval_env_import_state",
     "aleppo_eval_env_read",
@@ -886,6 +897,51 @@ class Engine:
                                           _ptr(g), C.c_size_t(0 if g is None else g.size), _ptr(cs),
                                           C.c_size_t(0 if cs is None else cs.size)))
         return dict(stats={k: float(stats[i]) for k, i in FR_STATS.items()}, sigma=sg, gram=g, colsum=cs)
+
+    @staticmethod
+    def _set(name):
+        if isinstance(name, (int, np.integer)):
+            return int(name)
+        if name not in SETS:
+            raise AleppoInvalidArgument(f"a parameter set is one of {tuple(SETS)}")
+        return SETS[name]
+
+    def snapshot_take(self, source="live"):
+        """aleppo_snapshot_take: snapshot = the "live" or the "averaged" parameters, by device copies (enqueued only)"""
+        self._c(lib().aleppo_snapshot_take(self._ctx, C.c_int(self._set(source))))
+
+    def snapshot_params(self):
+        """aleppo_snapshot_export: the snapshot as flat float32 in libtorch parameters() order"""
+        out = np.zeros(self.param_count, np.float32)
+        self._c(lib().aleppo_snapshot_export(self._ctx, _ptr(out), C.c_size_t(out.size)))
+        return out
+
+    def load_snapshot(self, flat):
+        """aleppo_snapshot_import: flat float32 parameters (a checkpoint, export_params of another run) -> the snapshot"""
+        flat = _f32(flat).ravel()
+        self._c(lib().aleppo_snapshot_import(self._ctx, _ptr(flat), C.c_size_t(flat.size)))
+
+    def policy_diff(self, a="snapshot", b="live", observations=None, per_sample=False, transitions=False,
+                    outputs=False):
+        """aleppo_policy_diff: how far parameter set b's policy, value and fc features are from set a's ("live",
+        "averaged", "snapshot") - on the batch the context holds (observations=None) or on uint8 [n,4,84,84]
+        observations; both forward passes and the comparison run on the device.  {"stats": {name: float} over PD_STATS,
+        "per_sample": float64 [rows, PD_ROW] (columns PD_COLUMNS; a left-out row is NaN) with per_sample=True,
+        "transitions": int64 [A, A] ([i, j]: rows whose greedy action went from i to j) with transitions=True,
+        "outputs": float32 [2, rows, A + 1] (logits then value, set a first) with outputs=True; None otherwise}."""
+        obs = None if observations is None else _u8(observations)
+        n = 0 if obs is None else obs.shape[0]
+        rows = self._batch_n if obs is None else n
+        stats = np.zeros(PD_COUNT, np.float64)
+        ps = np.zeros((rows, PD_ROW), np.float64) if per_sample else None
+        tr = np.zeros((self.A, self.A), np.int64) if transitions else None
+        out = np.zeros((2, rows, self.A + 1), np.float32) if outputs else None
+        self._c(lib().aleppo_policy_diff(self._ctx, _ptr(obs), C.c_int64(n), C.c_int(self._set(a)), C.c_int(self._set(b)),
+                                         _ptr(stats), C.c_size_t(stats.size), _ptr(ps),
+                                         C.c_size_t(0 if ps is None else ps.size), _ptr(tr),
+                                         C.c_size_t(0 if tr is None else tr.size), _ptr(out),
+                                         C.c_size_t(0 if out is None else out.size)))
+        return dict(stats={k: float(stats[i]) for k, i in PD_STATS.items()}, per_sample=ps, transitions=tr, outputs=out)
 
     def _saliency_source(self, observations, first, n):
         obs = None if observations is None else _u8(observations)

@@ -216,32 +216,55 @@ void prof_end(Ctx *c, int cls, hipStream_t st) { // same stream as the matching 
   p.used++;
 }
 
-// conv stack forward for ns samples addressed by map -> c->h
+// conv stack forward for ns samples addressed by map -> c->h, on the parameter set pv
 // returns the number of split-K partial slabs of h (1 unless max_parts allows the pipelined fc kernel to split)
-int net_forward(Ctx *c, const uint32_t *obs, SampleMap map, long ns, int max_parts) {
+int net_forward(Ctx *c, const ParamView &pv, const uint32_t *obs, SampleMap map, long ns, int max_parts) {
   if (c->prec == ALEPPO_BF16 && use_patch_kernels() && tuning().fused_fwd) { // one launch: a1 / a2 are only written
     prof_begin(c, ALEPPO_K_CONV_FWD);
-    patch_fwd_fused(c->stream, obs, map, Pcw(c, P_W1), Pf(c, P_B1), Pcw(c, P_W2), Pf(c, P_B2), Pcw(c, P_W3), Pf(c, P_B3),
-                    c->a1, c->a2, c->a3, ns);
+    patch_fwd_fused(c->stream, obs, map, Pcw(c, pv, P_W1), Pf(c, pv, P_B1), Pcw(c, pv, P_W2), Pf(c, pv, P_B2),
+                    Pcw(c, pv, P_W3), Pf(c, pv, P_B3), c->a1, c->a2, c->a3, ns);
     prof_end(c, ALEPPO_K_CONV_FWD);
     prof_begin(c, ALEPPO_K_FC_FWD);
-    const int parts = fc_fwd(c->stream, c->prec, c->a3, Pcw(c, P_WFC), Pf(c, P_BFC), c->h, ns, c->H, max_parts);
+    const int parts = fc_fwd(c->stream, c->prec, c->a3, Pcw(c, pv, P_WFC), Pf(c, pv, P_BFC), c->h, ns, c->H, max_parts);
     prof_end(c, ALEPPO_K_FC_FWD);
     return parts;
   }
   prof_begin(c, ALEPPO_K_CONV1_FWD);
-  conv1_fwd(c->stream, c->prec, obs, map, Pcw(c, P_W1), Pf(c, P_B1), c->a1, ns);
+  conv1_fwd(c->stream, c->prec, obs, map, Pcw(c, pv, P_W1), Pf(c, pv, P_B1), c->a1, ns);
   prof_end(c, ALEPPO_K_CONV1_FWD);
   prof_begin(c, ALEPPO_K_CONV2_FWD);
-  conv2_fwd(c->stream, c->prec, c->a1, Pcw(c, P_W2), Pf(c, P_B2), c->a2, ns);
+  conv2_fwd(c->stream, c->prec, c->a1, Pcw(c, pv, P_W2), Pf(c, pv, P_B2), c->a2, ns);
   prof_end(c, ALEPPO_K_CONV2_FWD);
   prof_begin(c, ALEPPO_K_CONV3_FWD);
-  conv3_fwd(c->stream, c->prec, c->a2, Pcw(c, P_W3), Pf(c, P_B3), c->a3, ns);
+  conv3_fwd(c->stream, c->prec, c->a2, Pcw(c, pv, P_W3), Pf(c, pv, P_B3), c->a3, ns);
   prof_end(c, ALEPPO_K_CONV3_FWD);
   prof_begin(c, ALEPPO_K_FC_FWD);
-  const int parts = fc_fwd(c->stream, c->prec, c->a3, Pcw(c, P_WFC), Pf(c, P_BFC), c->h, ns, c->H, max_parts);
+  const int parts = fc_fwd(c->stream, c->prec, c->a3, Pcw(c, pv, P_WFC), Pf(c, pv, P_BFC), c->h, ns, c->H, max_parts);
   prof_end(c, ALEPPO_K_FC_FWD);
   return parts;
+}
+
+int net_forward(Ctx *c, const uint32_t *obs, SampleMap map, long ns, int max_parts) {
+  return net_forward(c, live_view(c), obs, map, ns, max_parts);
+}
+
+int set_view(aleppo_ctx *c, int set, ParamView *view) {
+  switch (set) {
+  case ALEPPO_SET_LIVE:
+    *view = live_view(c);
+    return ALEPPO_OK;
+  case ALEPPO_SET_AVERAGED:
+    if (!c->ema_on)
+      return set_err(c, ALEPPO_ERR_RUNTIME, "no averaged parameters: call aleppo_ema_open first");
+    *view = ParamView{c->Pe, c->Pec};
+    return ALEPPO_OK;
+  case ALEPPO_SET_SNAPSHOT:
+    if (!c->snap_on)
+      return set_err(c, ALEPPO_ERR_RUNTIME, "no snapshot: call aleppo_snapshot_take or aleppo_snapshot_import first");
+    *view = ParamView{c->Ps, c->Psc};
+    return ALEPPO_OK;
+  }
+  return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "unknown parameter set (ALEPPO_SET_LIVE / _AVERAGED / _SNAPSHOT)");
 }
 
 void refresh_compute_copies(Ctx *c) {

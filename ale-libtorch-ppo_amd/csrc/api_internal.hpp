@@ -1,5 +1,5 @@
 // api_internal.hpp - what the C ABI's translation units share (api_core.hip, api_rollout.hip, api_train.hip,
-// api_batch.hip, api_eval.hip, api_eval_env.hip, api_env.hip, api_rec.hip, api_state.hip, api_acts.hip, api_recycle.hip, api_ema.hip, api_saliency.hip, api_feature_rank.hip, api_ops.hip): the entry-point guard macros, the memory
+// api_batch.hip, api_eval.hip, api_eval_env.hip, api_env.hip, api_rec.hip, api_state.hip, api_acts.hip, api_recycle.hip, api_ema.hip, api_saliency.hip, api_feature_rank.hip, api_policy_diff.hip, api_ops.hip): the entry-point guard macros, the memory
 // ownership helpers (dalloc / halloc / grow over ctx_alloc / ctx_host_alloc / ctx_grow) and the other host-side helpers.
 // Host code only; the helpers are defined in api_core.hip unless noted.
 #pragma once
@@ -131,7 +131,11 @@ inline const void *Pcw(const Ctx *c, const ParamView &v, ParamId id) {
 
 // conv stack forward for ns samples addressed by map -> c->h
 // returns the number of split-K partial slabs of h (1 unless max_parts allows the pipelined fc kernel to split)
-int net_forward(Ctx *c, const uint32_t *obs, SampleMap map, long ns, int max_parts = 1);
+int net_forward(Ctx *c, const uint32_t *obs, SampleMap map, long ns, int max_parts = 1); // on the live parameters
+int net_forward(Ctx *c, const ParamView &pv, const uint32_t *obs, SampleMap map, long ns, int max_parts = 1);
+// the view of ALEPPO_SET_LIVE / _AVERAGED / _SNAPSHOT (aleppo_snapshot_take, aleppo_policy_diff): ALEPPO_ERR_RUNTIME for a
+// set that does not exist yet, ALEPPO_ERR_INVALID_ARGUMENT for an unknown one; *view is written on success only
+int set_view(aleppo_ctx *c, int set, ParamView *view);
 
 void refresh_compute_copies(Ctx *c);
 // api_core.hip, also for aleppo_ema_export (api_ema.hip): a vector in the internal layout (device) -> the caller's flat

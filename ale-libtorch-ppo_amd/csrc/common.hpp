@@ -278,6 +278,13 @@ struct Ctx {
   double *ema_blk = nullptr;       // [EMA_MAX_BLOCKS][3] workgroup partials, then the ALEPPO_EMA_STATS_COUNT doubles
   int64_t ema_updates = 0;
   bool eval_averaged = false;      // ALEPPO_OPT_EVAL_PARAMS: the evaluation lanes act on (Pe, Pec)
+  // ---- aleppo_snapshot_take / aleppo_snapshot_import: the caller's third parameter set, and aleppo_policy_diff's scratch
+  // (policy_diff_plan); each is allocated on first use and never again, nothing is enqueued for them on a context that
+  // never makes the calls
+  bool snap_on = false;            // a take or an import has succeeded
+  float *Ps = nullptr;             // fp32, internal layout, L.total() floats
+  void *Psc = nullptr;             // compute copy of Ps in T; == Ps for fp32
+  void *pd_scratch = nullptr;
   // ---- aleppo_saliency / aleppo_saliency_perturbed: nothing below is allocated, and nothing is enqueued for it, on a context
   // that never calls them; each buffer is allocated on first use and grown on demand like stage_obs
   uint32_t *sal_blur = nullptr;  // packed blurred stacks of the samples one forward chunk touches
@@ -519,6 +526,29 @@ struct FeatureRankPlan {
 FeatureRankPlan feature_rank_plan(int H, long maxB);
 inline size_t fr_tile(int nb, int bi, int bj) { return (size_t)bi * nb - (size_t)bi * (bi - 1) / 2 + (size_t)(bj - bi); }
 void launch_feature_rank_chunk(hipStream_t s, const float *h, long ns, bool first, const FeatureRankPlan &pl, void *scratch);
+// aleppo_policy_diff (policy_diff.hip).  The plan is a function of (H, A, cap, maxB), cap = the most rows a call can bring.
+// Scratch, every area 256-byte aligned: logits [2][cap][A] and values [2][cap] of the two sets (fp32), set a's h
+// [maxB][H], the per-sample table double [cap][ALEPPO_PD_ROW], the workgroup partials double [PD_PART][PD_MAX_BLOCKS], the
+// running totals double [PD_PART], the ALEPPO_PD_COUNT stats, the transition counts uint64 [MAX_ACTIONS][MAX_ACTIONS].
+// A partial / total record: PD_SUMS sums (pd_sum), then the four order-free extrema (pd_ext).
+// launch_policy_diff_chunk: the two launches of one forward chunk of ns rows that start at row n0 - the comparison (one
+// wave per row, grid = min(ceil(ns / 4), PD_MAX_BLOCKS), a function of ns alone) and the finalising launch that adds the
+// partials in index order and sets (first) or adds to the totals.  launch_policy_diff_stats, after the last chunk: the
+// stats from the totals.  The transition counts are only added to: the caller clears them before the first chunk.
+constexpr int PD_MAX_BLOCKS = 1024, PD_SUMS = 13, PD_PART = 17;
+enum pd_sum { PD_S_ROWS, PD_S_NONFINITE, PD_S_CHURN, PD_S_KL_AB, PD_S_KL_BA, PD_S_TV, PD_S_ABS_DV, PD_S_DV2, PD_S_ENT_A,
+              PD_S_ENT_B, PD_S_COS, PD_S_DH2, PD_S_HA2 };
+enum pd_ext { PD_X_MAX_KL_AB = PD_SUMS, PD_X_MAX_TV, PD_X_MAX_ABS_DV, PD_X_MIN_COS };
+struct PolicyDiffPlan {
+  int H, A;
+  long cap;
+  size_t logits[2], values[2], h_a, rows, part, total, stats, trans; // byte offsets
+  size_t bytes;
+};
+PolicyDiffPlan policy_diff_plan(int H, int A, long cap, long maxB);
+void launch_policy_diff_chunk(hipStream_t s, const float *h_b, long n0, long ns, bool first, const PolicyDiffPlan &pl,
+                              void *scratch);
+void launch_policy_diff_stats(hipStream_t s, const PolicyDiffPlan &pl, void *scratch);
 // aleppo_recycle_units / aleppo_recycle_dormant (recycle.hip).  mask: uint8 [160 + H] in device memory, 4-byte aligned, in
 // the unit order of aleppo_activation_stats.  launch_recycle_mask forms it from that entry point's device-side unit table
 // (mask[u] = layer bit of u in layers && SCORE_u <= tau); launch_recycle is the one pass over P / M1 / M2 in the internal

@@ -779,6 +779,83 @@ int aleppo_feature_rank(aleppo_ctx *ctx, const uint8_t *observations, int64_t n,
                         double *stats, size_t stat_count, double *sigma, size_t sigma_count, double *gram,
                         size_t gram_count, double *colsum, size_t colsum_count);
 
+/* Policy churn: how far one parameter set's policy, value and fc features are from another's on the same states
+ * (Schaul et al. 2022, "The Phenomenon of Policy Churn": the share of states whose greedy action an update changes;
+ * Sokar et al. 2023 claim a recycle moves the outputs by almost nothing; Hilton, Cobbe & Schulman 2021 reason about the
+ * distance of the averaged policy from the live one; the reference has none of it).  Both forward passes and the
+ * comparison run on the device; only the ALEPPO_PD_COUNT doubles - and what the caller asks for - leave it.
+ * Parameter sets: ALEPPO_SET_LIVE, the parameters aleppo_train updates; ALEPPO_SET_AVERAGED, the set of aleppo_ema_open;
+ *   ALEPPO_SET_SNAPSHOT, a third set only the three calls below write.  It lives in the private layout like the averaged set
+ *   (fp32, and in bf16 contexts its bf16 compute copy), is allocated on the first take or import and never again.
+ * aleppo_snapshot_take(source_set): snapshot = the live or the averaged set, two device-to-device copies on the context's
+ *   main stream, so the compute copy is the source's bit for bit; the call enqueues only.
+ * aleppo_snapshot_import / aleppo_snapshot_export move the snapshot in the order and with the count checks of
+ *   aleppo_load_params / aleppo_export_params (an import rebuilds the compute copy with the conversion the live one is
+ *   made with): a checkpoint from disk can be compared with the running policy.
+ * Interactions: aleppo_load_params, aleppo_train, aleppo_recycle_units / aleppo_recycle_dormant and the aleppo_ema_* calls
+ *   never touch the snapshot - that is the point of it.  aleppo_state_digest does not cover it.  No call is a collective.
+ *   While a step is armed every call is refused.  A failed call changes nothing.
+ * aleppo_policy_diff(set_a, set_b): samples exactly as for aleppo_feature_rank - observations == NULL and n == 0: the
+ *   batch the context holds, in forward chunks of at most maxB = max(E, max_minibatch); otherwise the caller's n <= maxB
+ *   observations.  Per chunk: the forward pass and the heads on set a (the forward pass of aleppo_forward, reading that
+ *   set), one device copy that keeps its fc rows, the forward pass and the heads on set b, then the comparison launch and
+ *   a small finalising launch.  set_a == set_b is allowed.
+ * Per row, all in double, from the fp32 logits l, value v and fc row h of each set, widened:
+ *     m = max l;  z = l - m;  lse = log(sum exp z);  logp = z - lse;  p = exp(logp)
+ *     g = the lowest index of the maximum of l (the ALEPPO_EVAL_GREEDY rule)
+ *   A row in which any logit, value or fc element of either set is not finite is counted (NONFINITE_ROWS) and left out of
+ *   everything else.  per_sample: double [rows][ALEPPO_PD_ROW], a left-out row all NaN -
+ *     0 kl_ab = sum p_a (logp_a - logp_b)     1 kl_ba = sum p_b (logp_b - logp_a)     2 tv = 0.5 sum |p_a - p_b|
+ *     3 dv = v_b - v_a     4 cos = <h_a,h_b> / sqrt(|h_a|^2 |h_b|^2), 1 where either norm is 0     5 dh2 = |h_b - h_a|^2
+ *     6 g_a     7 g_b
+ * stats: double [ALEPPO_PD_COUNT], aleppo_policy_diff_stat; a mean is the sum over the rows that entered divided by ROWS.
+ *   With ROWS == 0 every stat but ROWS and NONFINITE_ROWS is 0.
+ * transitions: NULL or int64 [A][A], [i][j] = the rows with g_a = i and g_b = j.  outputs: NULL or float [2][rows][A + 1],
+ *   the logits then the value of every row, set a's block first - left-out rows included, as computed.
+ * Order: one wave per row adds the H products across its lanes in a fixed tree; the sums go to one double record per
+ *   workgroup (the grid is a function of the chunk's row count alone), a finalising launch adds the records in index order
+ *   and the chunks are accumulated in order; extrema are order-free and the transition counts are integer adds.  No
+ *   floating-point atomics: two calls on the same state return the same bits.
+ * Computed WHEN CALLED, on the context's stream, like aleppo_feature_rank: the stream's synchronise, the launches above,
+ *   one copy of the results.  It runs the network in the shared activation scratch, so what aleppo_step pre-computed for
+ *   the next aleppo_act is dropped (the act recomputes it: same bits).  Scratch (set a's fc rows of one chunk, the logits,
+ *   values and per-sample table of max(E * horizon, maxB) rows) is allocated on first use and kept until aleppo_destroy.
+ *   It only reads the parameter sets: aleppo_train, a captured update (ALEPPO_OPT_UPDATE_GRAPH) and every other entry point
+ *   enqueue nothing for it; a context that never calls it allocates and enqueues exactly what it did before, and calling
+ *   it changes no bit of the run.
+ * Errors: a set that is none of the three, ALEPPO_SET_SNAPSHOT as the source of a take, a NULL stats or flat, a wrong
+ *   count (stat_count != ALEPPO_PD_COUNT, a non-NULL output whose count is not rows * ALEPPO_PD_ROW, A * A,
+ *   2 * rows * (A + 1)), and what aleppo_activation_stats refuses in observations and n: ALEPPO_ERR_INVALID_ARGUMENT.
+ *   ALEPPO_SET_AVERAGED before aleppo_ema_open, ALEPPO_SET_SNAPSHOT (and aleppo_snapshot_export) before any take or import,
+ *   the batch source without a batch, any call while a step is armed: ALEPPO_ERR_RUNTIME.  A failed call writes nothing. */
+enum { ALEPPO_SET_LIVE = 0, ALEPPO_SET_AVERAGED = 1, ALEPPO_SET_SNAPSHOT = 2 };
+typedef enum {
+  ALEPPO_PD_ROWS = 0,               /* the rows that entered */
+  ALEPPO_PD_NONFINITE_ROWS = 1,     /* rows left out */
+  ALEPPO_PD_CHURN = 2,              /* the share of rows with g_a != g_b */
+  ALEPPO_PD_MEAN_KL_AB = 3,
+  ALEPPO_PD_MAX_KL_AB = 4,
+  ALEPPO_PD_MEAN_KL_BA = 5,
+  ALEPPO_PD_MEAN_TV = 6,
+  ALEPPO_PD_MAX_TV = 7,
+  ALEPPO_PD_MEAN_ABS_DV = 8,
+  ALEPPO_PD_MAX_ABS_DV = 9,
+  ALEPPO_PD_RMS_DV = 10,            /* sqrt(mean dv^2) */
+  ALEPPO_PD_MEAN_ENTROPY_A = 11,    /* mean of -sum p_a logp_a */
+  ALEPPO_PD_MEAN_ENTROPY_B = 12,
+  ALEPPO_PD_MEAN_FEATURE_COS = 13,
+  ALEPPO_PD_MIN_FEATURE_COS = 14,
+  ALEPPO_PD_FEATURE_REL_CHANGE = 15 /* sqrt(sum dh2 / sum |h_a|^2), 0 where the denominator is 0 */
+} aleppo_policy_diff_stat;
+#define ALEPPO_PD_COUNT 16
+#define ALEPPO_PD_ROW 8
+int aleppo_snapshot_take(aleppo_ctx *ctx, int source_set);
+int aleppo_snapshot_export(aleppo_ctx *ctx, float *flat, size_t count);
+int aleppo_snapshot_import(aleppo_ctx *ctx, const float *flat, size_t count);
+int aleppo_policy_diff(aleppo_ctx *ctx, const uint8_t *observations, int64_t n, int set_a, int set_b, double *stats,
+                       size_t stat_count, double *per_sample, size_t per_sample_count, int64_t *transitions,
+                       size_t transition_count, float *outputs, size_t output_count);
+
 /* ------------------------------------------------------------------ evaluation lanes (the reference has no evaluation
  * loop: SB3's predict(deterministic=True) / EvalCallback, the epsilon-greedy scores of the DQN / PPO papers)
  * L frame stacks of their own, next to the rollout, on which the network acts under one of three rules - so that a

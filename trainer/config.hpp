@@ -62,6 +62,11 @@ struct Config {
   bool log_feature_rank = false;
   size_t feature_rank_interval = 1;
   aleppo_feature_rank_config feature_rank{0.01f, 0.01f, 0, 0}; // delta, eps, centered
+  // extension: policy churn (Schaul et al. 2022) - a snapshot before the update of every n-th rollout, aleppo_policy_diff
+  // (snapshot, live) after it on the batch it trained on; policy_churn_averaged: also (averaged, live), needs ema_decay
+  bool log_policy_churn = false;
+  size_t policy_churn_interval = 1;
+  bool policy_churn_averaged = false;
   // extension: ReDo (Sokar et al. 2023) - recycle the dormant units of the held batch (aleppo_recycle_dormant)
   bool recycle_dormant = false;
   // after the update of every n-th rollout.  64: ReDo recycles every 1000 gradient steps; the benched configuration takes
@@ -342,6 +347,19 @@ static Config load_config(const std::string &path) { // keys / defaults of src/b
       throw std::runtime_error(std::string(k) + " needs ema_decay");
   if (kv.count("eval_averaged") && c.eval_interval == 0)
     throw std::runtime_error("eval_averaged needs eval_interval > 0");
+  read_key(kv, "log_policy_churn", c.log_policy_churn);
+  {
+    const long interval = as<long>(kv, "policy_churn_interval", 1);
+    if (interval < 1)
+      throw std::runtime_error("policy_churn_interval must be positive");
+    c.policy_churn_interval = (size_t)interval;
+    read_key(kv, "policy_churn_averaged", c.policy_churn_averaged);
+    for (const char *k : {"policy_churn_interval", "policy_churn_averaged"})
+      if (kv.count(k) && !c.log_policy_churn) // (nothing else reads them; given as false too)
+        throw std::runtime_error(std::string(k) + " needs log_policy_churn: true");
+    if (c.policy_churn_averaged && !c.ema_decay_set)
+      throw std::runtime_error("policy_churn_averaged needs ema_decay");
+  }
   read_key(kv, "record_evaluation", c.record_evaluation);
   if (c.record_evaluation && !c.device_evaluation)
     throw std::runtime_error("record_evaluation needs device_evaluation: true");
@@ -442,6 +460,8 @@ static HParams hparams_of(const Config &c) {
     h.numbers.emplace_back("record_interval", (double)c.record_interval);
   if (c.ema_decay_set)
     h.numbers.emplace_back("ema_decay", c.ema_decay);
+  if (c.log_policy_churn)
+    h.numbers.emplace_back("policy_churn_interval", (double)c.policy_churn_interval);
   h.flags = {{"record_observation", c.record_observation}, {"record_video", c.record_video},
              {"cuda_graph", c.cuda_graph}, {"deterministic", c.deterministic}};
   const std::pair<const char *, bool> when_set[] = {{"shuffle_minibatches", c.shuffle_minibatches},
@@ -451,6 +471,8 @@ static HParams hparams_of(const Config &c) {
                                                     {"log_tensor_stats", c.log_tensor_stats},
                                                     {"log_activation_stats", c.log_activation_stats},
                                                     {"log_feature_rank", c.log_feature_rank},
+                                                    {"log_policy_churn", c.log_policy_churn},
+                                                    {"policy_churn_averaged", c.policy_churn_averaged},
                                                     {"recycle_dormant", c.recycle_dormant},
                                                     {"record_saliency", c.record_saliency},
                                                     {"reward_scaling", c.reward_scaling},

@@ -71,7 +71,14 @@
 // /stable, /numerical, /sigma_max, /sigma_min, /mean_sq_norm and /nonfinite_rows; it comes after the activation statistics
 // and before a recycle, which changes the weights; never a collective: the figures describe rank 0's samples; the four other
 // keys without log_feature_rank, values aleppo_feature_rank would refuse and a library without the entry point are refused
-// at start-up).  clip_param_final, value_loss_coef_final, entropy_coef_final,
+// at start-up).  log_policy_churn: false (true: on every policy_churn_interval-th rollout - default 1 - rank 0 calls
+// aleppo_snapshot_take(ALEPPO_SET_LIVE) before the update and aleppo_policy_diff(ALEPPO_SET_SNAPSHOT, ALEPPO_SET_LIVE) after
+// it, on the batch it trained on, and logs policy_churn/churn - the share of states whose greedy action the update changed,
+// Schaul et al. 2022 -, /kl, /kl_reverse, /tv, /value_change - RMS -, /feature_cos and /feature_change;
+// policy_churn_averaged: true, needs ema_decay, also logs policy_churn/ema_churn and /ema_kl from (ALEPPO_SET_AVERAGED,
+// ALEPPO_SET_LIVE) after the EMA update; never a collective; the two other keys without log_policy_churn, a non-positive
+// interval, policy_churn_averaged without ema_decay and a library without the entry points are refused at start-up).
+// clip_param_final, value_loss_coef_final, entropy_coef_final,
 // max_gradient_norm_final (absent: the value stays what the config says and no option is set; given: rollout i of
 // num_rollouts updates with v0 + (v_final - v0) * i / num_rollouts, computed in double and rounded to float once - the
 // shape of the learning-rate anneal, which never reaches its end value either - set through ALEPPO_OPT_CLIP_PARAM /
@@ -188,6 +195,9 @@
 #pragma weak aleppo_recycle_dormant
 // ... and the feature rank (log_feature_rank: true)
 #pragma weak aleppo_feature_rank
+// ... and the policy churn (log_policy_churn: true)
+#pragma weak aleppo_snapshot_take
+#pragma weak aleppo_policy_diff
 // (record_saliency: true - aleppo_saliency is declared weak in saliency.hpp)
 // ... and the exponentially averaged parameters (ema_decay)
 #pragma weak aleppo_ema_open
@@ -356,6 +366,9 @@ static void refuse_missing_entry_points(const Config &cfg) {
   if (cfg.ema_decay_set && !(aleppo_ema_open && aleppo_ema_update && aleppo_ema_read && aleppo_ema_export && aleppo_ema_import))
     throw std::runtime_error("ema_decay is set but this build's library has no averaged parameters "
                              "(aleppo_ema_open is missing)");
+  if (cfg.log_policy_churn && !(aleppo_snapshot_take && aleppo_policy_diff))
+    throw std::runtime_error("log_policy_churn is set but this build's library has no policy churn "
+                             "(aleppo_snapshot_take / aleppo_policy_diff are missing)");
   if (cfg.log_feature_rank && !aleppo_feature_rank)
     throw std::runtime_error("log_feature_rank is set but this build's library has no feature rank "
                              "(aleppo_feature_rank is missing)");
@@ -747,6 +760,8 @@ struct Update {
   std::vector<double> act_units; // [(160 + H) * ALEPPO_ACT_UNIT_COLS] (the call fills it; only the layer table is logged)
   bool feature_rank_read = false; // log_feature_rank, rank 0: this rollout is one of the interval's, feature_rank holds it
   double feature_rank[ALEPPO_FR_COUNT] = {};
+  bool churn_read = false; // log_policy_churn, rank 0: this rollout is one of the interval's, churn / ema_churn hold it
+  double churn[ALEPPO_PD_COUNT] = {}, ema_churn[ALEPPO_PD_COUNT] = {};
   bool recycled = false; // recycle_dormant: this rollout is one of the interval's, recycle_counts is what it recycled
   int64_t recycle_counts[ALEPPO_RECYCLE_COUNTS] = {};
   double ema_decay_now = 0;                       // ema_decay: the decay this rollout's aleppo_ema_update ran with ...
@@ -773,6 +788,12 @@ static void update(Run &run, size_t r, Update &u) {
   u.kl_beta = run.st.kl_beta;
   if (run.kl_penalty())
     set_float_option(ctx, ALEPPO_OPT_KL_COEF, u.kl_beta);
+  // policy churn: the parameters this update starts from, kept on the device (not a collective: rank 0's samples)
+  u.churn_read = cfg.log_policy_churn && run.rank == 0 && (r + 1) % cfg.policy_churn_interval == 0;
+  if (u.churn_read) {
+    Profile::Span sp(&run.prof, "aleppo_snapshot_take");
+    check(ctx, aleppo_snapshot_take(ctx, ALEPPO_SET_LIVE));
+  }
   while (u.epochs_run < (size_t)cfg.num_epochs) {
     const size_t e0 = u.epochs_run;
     {
@@ -814,6 +835,15 @@ static void update(Run &run, size_t r, Update &u) {
     check(ctx, aleppo_ema_update(ctx, u.ema_decay_now));
     run.ema_updates++;
     check(ctx, aleppo_ema_read(ctx, u.ema_stats));
+  }
+  // ... and how far the update moved the policy, the value and the features on the batch it trained on
+  if (u.churn_read) {
+    Profile::Span sp(&run.prof, "aleppo_policy_diff");
+    check(ctx, aleppo_policy_diff(ctx, nullptr, 0, ALEPPO_SET_SNAPSHOT, ALEPPO_SET_LIVE, u.churn, ALEPPO_PD_COUNT, nullptr, 0,
+                                  nullptr, 0, nullptr, 0));
+    if (cfg.policy_churn_averaged) // (after the EMA update above: the averaged policy against the live one)
+      check(ctx, aleppo_policy_diff(ctx, nullptr, 0, ALEPPO_SET_AVERAGED, ALEPPO_SET_LIVE, u.ema_churn, ALEPPO_PD_COUNT,
+                                    nullptr, 0, nullptr, 0, nullptr, 0));
   }
   if (cfg.log_tensor_stats && run.rank == 0) { // (not a collective: every rank's answer would be the same)
     Profile::Span sp(&run.prof, "aleppo_tensor_stats");
@@ -941,6 +971,18 @@ static void log_scalars(Run &run, const EpisodeLog &log, const BatchStatistics &
         {"nonfinite_rows", ALEPPO_FR_NONFINITE_ROWS}};
     for (const auto &t : tags)
       logger.add_scalar(std::string("feature_rank/") + t.first, step, (float)u.feature_rank[t.second]);
+  }
+  if (u.churn_read) { // (of the batch this update trained on; set on rank 0 only)
+    static const std::pair<const char *, int> tags[] = {
+        {"churn", ALEPPO_PD_CHURN}, {"kl", ALEPPO_PD_MEAN_KL_AB}, {"kl_reverse", ALEPPO_PD_MEAN_KL_BA},
+        {"tv", ALEPPO_PD_MEAN_TV}, {"value_change", ALEPPO_PD_RMS_DV}, {"feature_cos", ALEPPO_PD_MEAN_FEATURE_COS},
+        {"feature_change", ALEPPO_PD_FEATURE_REL_CHANGE}};
+    for (const auto &t : tags)
+      logger.add_scalar(std::string("policy_churn/") + t.first, step, (float)u.churn[t.second]);
+    if (cfg.policy_churn_averaged) {
+      logger.add_scalar("policy_churn/ema_churn", step, (float)u.ema_churn[ALEPPO_PD_CHURN]);
+      logger.add_scalar("policy_churn/ema_kl", step, (float)u.ema_churn[ALEPPO_PD_MEAN_KL_AB]);
+    }
   }
   if (u.recycled) {
     for (int k = 0; k < 4; ++k)
