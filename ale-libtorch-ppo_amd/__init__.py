@@ -71,6 +71,11 @@ TENSOR_STATS_SECTIONS = dict(params=TS_SEC_PARAMS, step=TS_SEC_STEP, all=TS_SEC_
 ACT_LAYERS = ("conv1", "conv2", "conv3", "fc")
 ACT_LAYER_SHAPES = dict(conv1=(32, 20, 20), conv2=(64, 9, 9), conv3=(64, 7, 7))
 ACT_LAYER_ROWS = ACT_LAYERS + ("total",)
+# aleppo_export_backward: the outputs in argument order with their aleppo_bwd_tensor bits, and the layer whose shape each
+# has (Engine.export_backward)
+BWD_TENSORS = dict(conv1=1, conv2=2, conv3=4, fc=8, dfc=16, dconv3=32, dconv2=64, dconv1=128)
+BWD_SHAPE_OF = dict(conv1="conv1", conv2="conv2", conv3="conv3", fc="fc", dfc="fc", dconv3="conv3", dconv2="conv2",
+                    dconv1="conv1")
 ACT_UNIT_COLS, ACT_LAYER_COLS = 5, 8
 ACT_UNIT_STATS = dict(mean_abs=0, positive_fraction=1, max_abs=2, score=3, nonfinite=4)
 ACT_LAYER_STATS = dict(units=0, elements=1, mean_abs=2, positive_fraction=3, max_abs=4, dead=5, dormant=6, nonfinite=7)
@@ -180,7 +185,7 @@ EXPORTS = [
     "aleppo_export_reward_scale", "aleppo_import_reward_scale", "aleppo_reward_scale",
     "aleppo_export_rollout_state", "aleppo_import_rollout_state", "aleppo_state_digest",
     "aleppo_tensor_stats",
-    "aleppo_forward_activations", "aleppo_activation_stats",
+    "aleppo_forward_activations", "aleppo_activation_stats", "aleppo_export_backward",
     "aleppo_recycle_units", "aleppo_recycle_dormant",
     "aleppo_ema_open", "aleppo_ema_update", "aleppo_ema_read", "aleppo_ema_export", "aleppo_ema_import",
     "aleppo_saliency_tables", "aleppo_saliency", "aleppo_saliency_perturbed",
@@ -467,6 +472,7 @@ class Engine:
         self._act_ptr = C.POINTER(C.c_int64)()
         self._act_out = C.byref(self._act_ptr)
         self.actions = None  # view of the pinned action buffer, valid after the first act
+        self._last_B = 1  # samples per minibatch of the last train() (export_backward's default capacity)
         self._ema_open = False  # ema_open has succeeded (run_state carries the average only then)
 
     def close(self):
@@ -719,6 +725,7 @@ class Engine:
     def train(self, lr, epochs, num_mini_batches):
         out = (MinibatchMetrics * (epochs * num_mini_batches))()
         self._c(lib().aleppo_train(self._ctx, C.c_double(lr), epochs, num_mini_batches, out))
+        self._last_B = self._batch_n // num_mini_batches
         keys = [f[0] for f in MinibatchMetrics._fields_]
         return {k: np.array([getattr(m, k) for m in out], np.float32).reshape(epochs, num_mini_batches) for k in keys}
 
@@ -823,6 +830,24 @@ class Engine:
         self._c(lib().aleppo_forward_activations(self._ctx, _ptr(obs), C.c_int64(n),
                                                  *[_ptr(out.get(l)) for l in ACT_LAYERS]))
         return out
+
+    def export_backward(self, tensors=tuple(BWD_TENSORS), capacity=None):
+        """aleppo_export_backward: ({name: float32 array}, B, stored) of what the last minibatch of the last train() left -
+        the activations conv1 / conv2 / conv3 / fc and the stored gradients dfc [B,H], dconv3, dconv2, dconv1 (the shapes of
+        their activations), B samples each; stored: the BWD_TENSORS bits of what the route kept in memory.  A tensor that was
+        asked for and not stored (dconv1 on the fused backward tail) is left out of the dict.  capacity: the samples to make
+        room for (default: the minibatch of the last train())."""
+        tensors = tuple(tensors)
+        if any(t not in BWD_TENSORS for t in tensors):
+            raise AleppoInvalidArgument(f"tensors must be a subset of {tuple(BWD_TENSORS)}")
+        cap = int(capacity) if capacity is not None else self._last_B
+        shape = lambda t: ACT_LAYER_SHAPES[BWD_SHAPE_OF[t]] if BWD_SHAPE_OF[t] != "fc" else (self.H,)
+        out = {t: np.zeros((max(cap, 0),) + shape(t), np.float32) for t in tensors}
+        n, stored = C.c_int64(0), C.c_uint32(0)
+        self._c(lib().aleppo_export_backward(self._ctx, C.c_int64(cap), *[_ptr(out.get(t)) for t in BWD_TENSORS],
+                                             C.byref(n), C.byref(stored)))
+        return ({t: a[:n.value] for t, a in out.items() if stored.value & BWD_TENSORS[t]}, int(n.value),
+                int(stored.value))
 
     def activation_stats(self, observations=None, tau=0.025, raw=False):
         """aleppo_activation_stats: per-unit and per-layer activation statistics reduced on the device - of the batch the

@@ -417,6 +417,33 @@ __global__ __launch_bounds__(256) void act_export_kernel(const uint4 *__restrict
   }
 }
 
+// groups 16-byte groups of T in row-major order -> the same elements as float
+template <class T>
+__global__ __launch_bounds__(256) void plane_export_kernel(const uint4 *__restrict__ a, float4 *__restrict__ out,
+                                                           long groups) {
+  constexpr int G = AsGroup<T>::G;
+  const long g = (long)blockIdx.x * 256 + threadIdx.x;
+  if (g >= groups)
+    return;
+  float e[G];
+  AsGroup<T>::widen(a[g], e);
+#pragma unroll
+  for (int k = 0; k < G / 4; ++k)
+    out[g * (G / 4) + k] = make_float4(e[4 * k], e[4 * k + 1], e[4 * k + 2], e[4 * k + 3]);
+}
+
+void launch_plane_export(hipStream_t s, int prec, const void *src, float *out, long n) {
+  const bool bf = prec == ALEPPO_BF16;
+  const long groups = n / (bf ? 8 : 4); // (n is a multiple of 8: whole groups)
+  const dim3 grid((unsigned)((groups + 255) / 256)), block(256);
+  if (bf)
+    hipLaunchKernelGGL(plane_export_kernel<uint16_t>, grid, block, 0, s, static_cast<const uint4 *>(src),
+                       reinterpret_cast<float4 *>(out), groups);
+  else
+    hipLaunchKernelGGL(plane_export_kernel<float>, grid, block, 0, s, static_cast<const uint4 *>(src),
+                       reinterpret_cast<float4 *>(out), groups);
+}
+
 void launch_act_export(hipStream_t s, int prec, int layer, const void *a, float *out, long ns) {
   const uint4 *src = static_cast<const uint4 *>(a);
   float4 *dst = reinterpret_cast<float4 *>(out);

@@ -1,6 +1,7 @@
-// api_acts.hip - C ABI (include/aleppo.h), the representation: aleppo_forward_activations, aleppo_activation_stats.
-// Both run the network the way aleppo_forward does (same staging, same net_forward, same pre_acted invalidation) and then
-// only read a1 / a2 / a3 / h; nothing here touches what the rollout or a captured update can observe.
+// api_acts.hip - C ABI (include/aleppo.h), the representation: aleppo_forward_activations, aleppo_activation_stats,
+// aleppo_export_backward.  The first two run the network the way aleppo_forward does (same staging, same net_forward, same
+// pre_acted invalidation) and then only read a1 / a2 / a3 / h; the third runs nothing and reads what the last update left
+// there and in dh / dz3 / dz2 / dz1.  Nothing here touches what the rollout or a captured update can observe.
 #include "api_internal.hpp"
 
 using namespace aleppo;
@@ -52,6 +53,60 @@ extern "C" int aleppo_forward_activations(aleppo_ctx *c, const uint8_t *observat
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
   CHECK_ASYNC(c);
+  return ALEPPO_OK;
+}
+
+// What the last minibatch of the last aleppo_train left: the stored tensors of both passes, read and converted, nothing
+// else.  One staging area in ax_buf, as large as the largest tensor asked for, reused tensor by tensor (stream order).
+extern "C" int aleppo_export_backward(aleppo_ctx *c, int64_t capacity, float *conv1, float *conv2, float *conv3, float *fc,
+                                      float *dfc, float *dconv3, float *dconv2, float *dconv1, int64_t *n,
+                                      uint32_t *stored) {
+  CHECK_CTX(c);
+  if (!conv1 && !conv2 && !conv3 && !fc && !dfc && !dconv3 && !dconv2 && !dconv1)
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "export_backward: at least one output must be given");
+  const Ctx::BwdMark m = c->bwd;
+  if (m.B <= 0)
+    return set_err(c, ALEPPO_ERR_RUNTIME,
+                   "export_backward: no update has run, or something else has run the network since the last one");
+  if (capacity < m.B)
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "export_backward: capacity is smaller than the minibatch");
+  const size_t B = (size_t)m.B, H = (size_t)c->H;
+  const size_t per[3] = {(size_t)A1_PIX * A1_C, (size_t)A2_PIX * A2_C, (size_t)A3_PIX * A3_C};
+  // (layer of launch_act_export, source, destination) - the gradients have their activations' shapes
+  struct Conv {
+    int layer;
+    const void *src;
+    float *dst;
+  } const convs[6] = {{0, c->a1, conv1},  {1, c->a2, conv2},  {2, c->a3, conv3},
+                      {2, c->dz3, dconv3}, {1, c->dz2, dconv2}, {0, m.dz1 ? c->dz1 : nullptr, dconv1}};
+  size_t need = (fc || dfc) ? B * H * 4 : 0;
+  for (const Conv &t : convs)
+    if (t.src && t.dst)
+      need = std::max(need, B * per[t.layer] * 4);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, grow(c, &c->ax_buf, &c->ax_cap, need, ALLOC_RAW));
+  for (const Conv &t : convs) {
+    if (!t.src || !t.dst)
+      continue;
+    launch_act_export(c->stream, c->prec, t.layer, t.src, c->ax_buf, m.B);
+    HIPCHK(c, hipMemcpyAsync(t.dst, c->ax_buf, B * per[t.layer] * 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  if (fc) {
+    launch_h_export(c->stream, c->h, m.hparts, m.B, c->H, c->ax_buf);
+    HIPCHK(c, hipMemcpyAsync(fc, c->ax_buf, B * H * 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  if (dfc) {
+    launch_plane_export(c->stream, c->prec, c->dh, c->ax_buf, (long)(B * H));
+    HIPCHK(c, hipMemcpyAsync(dfc, c->ax_buf, B * H * 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  CHECK_ASYNC(c);
+  if (n)
+    *n = m.B;
+  if (stored)
+    *stored = ALEPPO_BWD_CONV1 | ALEPPO_BWD_CONV2 | ALEPPO_BWD_CONV3 | ALEPPO_BWD_FC | ALEPPO_BWD_DFC | ALEPPO_BWD_DCONV3 |
+              ALEPPO_BWD_DCONV2 | (m.dz1 ? ALEPPO_BWD_DCONV1 : 0);
   return ALEPPO_OK;
 }
 

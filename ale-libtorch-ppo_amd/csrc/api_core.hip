@@ -219,6 +219,7 @@ void prof_end(Ctx *c, int cls, hipStream_t st) { // same stream as the matching 
 // conv stack forward for ns samples addressed by map -> c->h, on the parameter set pv
 // returns the number of split-K partial slabs of h (1 unless max_parts allows the pipelined fc kernel to split)
 int net_forward(Ctx *c, const ParamView &pv, const uint32_t *obs, SampleMap map, long ns, int max_parts) {
+  c->bwd.B = 0; // a1 / a2 / a3 / h no longer hold an update's last minibatch (aleppo_train sets the mark after its last)
   if (c->prec == ALEPPO_BF16 && use_patch_kernels() && tuning().fused_fwd) { // one launch: a1 / a2 are only written
     prof_begin(c, ALEPPO_K_CONV_FWD);
     patch_fwd_fused(c->stream, obs, map, Pcw(c, pv, P_W1), Pf(c, pv, P_B1), Pcw(c, pv, P_W2), Pf(c, pv, P_B2),

@@ -41,6 +41,7 @@ void aleppo::act_forward(aleppo_ctx *c, const ParamView &pv, uint32_t *obs, Samp
 
 static int do_act(aleppo_ctx *c, const float *noise, int slot, void *logits_dst, void *values_dst, int *actions_dst,
                   bool publish) {
+  c->bwd.B = 0; // (a1 / a2 / a3 are the acting scratch too: aleppo_export_backward has nothing to read any more)
   if (c->pre_acted != slot)
     act_forward(c, live_view(c), c->obs, slot_map(c, slot), c->a1, c->a2, c->a3, c->hpart, c->E, true);
   c->pre_acted = -1; // (consumed; a3 / hpart are scratch again)
@@ -254,6 +255,7 @@ int aleppo::step_enqueue(aleppo_ctx *c, const uint8_t *df, int kind, int locatio
   // (measured: 5.01 vs 5.10 ms per rollout).
   const bool fuse = c->prec == ALEPPO_BF16 && use_patch_kernels() && c->tune.fused_act &&
                     !(kind == ALEPPO_FRAMES_RAW_PAIR && location != ALEPPO_HOST_MAPPED && c->tune.fused_act < 2);
+  c->bwd.B = 0; // (as in do_act: the fused launch below writes a3)
   if (fuse) {
     // ONE launch forms slot t+1's stack from the new frames AND runs conv1 -> conv2 -> conv3 on it, then the split-K fc:
     // when the next aleppo_act (or aleppo_finish_rollout's bootstrap) arrives only the head + sampling kernel is left.

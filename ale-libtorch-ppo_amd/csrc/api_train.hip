@@ -138,6 +138,7 @@ static int plan_update(aleppo_ctx *c, int epochs, int M, UpdatePlan *plan) {
   if (N <= 0)
     return set_err(c, ALEPPO_ERR_RUNTIME, "no batch: call aleppo_finish_rollout or aleppo_set_batch first");
   c->pre_acted = -1; // the update's activations overwrite the acting scratch, and the weights change
+  c->bwd.B = 0;      // (aleppo_export_backward: valid again once this update has run)
   if (N % M != 0)
     return set_err(c, ALEPPO_ERR_RUNTIME, "Batch size must be divisible by num_mini_batches"); // train.h:140-143
   const long B = N / M;
@@ -417,6 +418,7 @@ static int enqueue_minibatch(aleppo_ctx *c, const UpdatePlan &p, int ep, int mb)
   SampleMap map = train_map(c, (long)mb * B);
   map.idx = p.pl.idx(ep);
   const int hparts = net_forward(c, c->obs, map, B, FC_FWD_MAX_PARTS);
+  c->bwd_enq = Ctx::BwdMark{B, hparts, !p.bwd_fused}; // (aleppo_export_backward: what this minibatch leaves; host only)
   enqueue_head(c, p, ep, mb, hparts);
   HIPCHK(c, fork_wgrad_stream(p, c->ev_head)); // dh is ready
   prof_begin(c, ALEPPO_K_FC_DGRAD);
@@ -557,6 +559,7 @@ static int run_update(aleppo_ctx *c, const UpdatePlan &p) {
   if (want_graph && c->graph_exec && c->graph_key == key) {
     HIPCHK(c, hipGraphLaunch(c->graph_exec, s));
     c->graph_replays++;
+    c->bwd_enq = c->bwd_graph;
   } else if (want_graph && c->warm_key == key) {
     if (c->graph_exec)
       HIPCHK(c, hipGraphExecDestroy(c->graph_exec));
@@ -584,6 +587,7 @@ static int run_update(aleppo_ctx *c, const UpdatePlan &p) {
     }
     c->graph = g;
     c->graph_key = key;
+    c->bwd_graph = c->bwd_enq;
     HIPCHK(c, hipGraphLaunch(c->graph_exec, s));
     c->graph_replays++;
   } else {
@@ -618,6 +622,7 @@ static int read_back_metrics(aleppo_ctx *c, const UpdatePlan &p, aleppo_minibatc
   c->ts_sched[0] = c->h_adam_sched[2 * (nm - 1)]; // (aleppo_tensor_stats recomputes the last step from these)
   c->ts_sched[1] = c->h_adam_sched[2 * (nm - 1) + 1];
   c->ts_step_valid = true;
+  c->bwd = c->bwd_enq; // the last minibatch's stored tensors are there to be read until something else runs the network
   if (out)
     for (int i = 0; i < nm; ++i) {
       const float *r = c->h_metric_red + (size_t)i * METRIC_REC;

@@ -265,6 +265,15 @@ struct Ctx {
   float *ax_buf = nullptr;
   size_t ax_cap = 0;                    // bytes
   void *as_scratch = nullptr;
+  // ---- aleppo_export_backward: host marks only.  What the last minibatch of an update leaves in a1 .. a3 / h / dh /
+  // dz3 .. dz1: its sample count (0: nothing to export), the split-K slabs of h, whether the route stored dz1.  bwd_enq is
+  // what enqueue_minibatch noted last (a capture keeps its copy in bwd_graph for the replays); aleppo_train makes it bwd
+  // once the update has run, and whatever else writes the activation scratch (net_forward, the acting forward) clears bwd
+  struct BwdMark {
+    long B = 0;
+    int hparts = 1;
+    bool dz1 = false;
+  } bwd, bwd_enq, bwd_graph;
   // ---- aleppo_feature_rank: the Gram blocks, column sums, split partials and row flags (allocated on first use; its size
   // is a function of (H, maxB))
   void *fr_scratch = nullptr;
@@ -511,6 +520,11 @@ void launch_act_stats_partial(hipStream_t s, int prec, const void *a1, const voi
 void launch_act_stats_final(hipStream_t s, int H, long total, double tau, const ActStatsPlan &pl, const size_t done[4],
                             void *scratch, const double **units_dev, const double **layers_dev);
 void launch_act_export(hipStream_t s, int prec, int layer, const void *a, float *out, long ns);
+// aleppo_export_backward: a row-major plane of T (dh), n elements (a multiple of 8) -> float, widened exactly
+// (activation_stats.hip); h as the head training kernel sees it, the hparts split-K slabs [hparts][B][H] added in its
+// order -> float [B][H] (head_train.hip: the same device function)
+void launch_plane_export(hipStream_t s, int prec, const void *src, float *out, long n);
+void launch_h_export(hipStream_t s, const float *h, int hparts, long B, int H, float *out);
 // aleppo_feature_rank (feature_rank.hip).  The plan is a function of (H, maxB): nb 64-column blocks, tiles = nb (nb + 1) / 2
 // upper blocks of 4096 doubles.  Scratch: the result - double [tiles][64][64] blocks of G, [H] column sums, [2] (the rows
 // left out, a pad) - then the partial results of up to FR_MAX_SPLITS row splits in the same form, then the row flags

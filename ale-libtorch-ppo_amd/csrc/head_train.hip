@@ -99,6 +99,27 @@ template <class T, class RT> static void head_train_vclip(hipStream_t s, const H
   else
     head_train_amax<T, RT, false>(s, a, hp);
 }
+// aleppo_export_backward: row r of h as the kernels above fetch it (their zero, their add_h_slabs) -> out [B][H].  One wave
+// per row, four rows per workgroup; reads only.
+__global__ __launch_bounds__(256) void h_export_kernel(const float *__restrict__ h, int hparts, long B, int H,
+                                                       float *__restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= B || lane * 8 >= H)
+    return;
+  float acc[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+    acc[i] = 0.f;
+  add_h_slabs(h, hparts, B, r, H, lane, acc);
+  float *dst = out + (size_t)r * H + lane * 4;
+  *reinterpret_cast<f32x4 *>(dst) = f32x4{acc[0], acc[1], acc[2], acc[3]};
+  *reinterpret_cast<f32x4 *>(dst + H / 2) = f32x4{acc[4], acc[5], acc[6], acc[7]};
+}
+void launch_h_export(hipStream_t s, const float *h, int hparts, long B, int H, float *out) {
+  hipLaunchKernelGGL(h_export_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, h, hparts, B, H, out);
+}
+
 void launch_head_train(hipStream_t s, const HeadTrainArgs &a, const float *hp) {
   if (a.prec == ALEPPO_BF16) {
     if (a.rt16)

@@ -33,17 +33,8 @@
 #pragma unroll
     for (int i = 0; i < HPL; ++i)
       hnext[i] = 0.f;
-    if (ok && lane * 8 < H) { // h arrives as `hparts` split-K partial slabs [hparts][B][H] (slab 0 carries the bias)
-      for (int p = 0; p < hparts; ++p) {
-        const float *src = h + ((size_t)p * B + r) * H + lane * 4;
-        const f32x4 v0 = *reinterpret_cast<const f32x4 *>(src), v1 = *reinterpret_cast<const f32x4 *>(src + H / 2);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          hnext[i] += v0[i];
-          hnext[4 + i] += v1[i];
-        }
-      }
-    }
+    if (ok && lane * 8 < H) // h arrives as `hparts` split-K partial slabs [hparts][B][H] (slab 0 carries the bias)
+      add_h_slabs(h, hparts, B, r, H, lane, hnext);
 #pragma unroll
     for (int a = 0; a < AMAX; ++a)
       olp_n[a] = (ok && a < A) ? (float)oldlp[(size_t)r * A + a] : 0.f;

@@ -484,6 +484,37 @@ int aleppo_forward(aleppo_ctx *ctx, const uint8_t *observations, int64_t n, floa
 int aleppo_forward_activations(aleppo_ctx *ctx, const uint8_t *observations, int64_t n, float *conv1, float *conv2,
                                float *conv3, float *fc);
 
+/* The stored tensors of both passes as the LAST minibatch of the last aleppo_train left them: what a per-layer check of the
+ * backward pass starts from (tests/backward_ref.py).  It runs nothing of the network and writes nothing the update reads:
+ * conversion kernels and copies on the context's stream into the staging aleppo_forward_activations uses.  aleppo_train
+ * enqueues what it enqueued before; it only notes on the host that, and with how many samples B = N / num_mini_batches, its
+ * last minibatch ran.  A context that never calls this runs what it ran before.
+ * Outputs, host float, `capacity` samples each (>= B; B samples are written), each may be NULL, at least one must be given;
+ * tensor order and widening as aleppo_forward_activations:
+ *   conv1 [B,32,20,20]  conv2 [B,64,9,9]  conv3 [B,64,7,7]   the activations a1, a2, a3
+ *   fc [B,H]            h as the head kernel read it: its split-K slabs added in the head kernel's order
+ *   dfc [B,H]           dL/dh as the head kernel stored it (bf16 on a bf16 context)
+ *   dconv3 [B,64,7,7]  dconv2 [B,64,9,9]  dconv1 [B,32,20,20]   dL/d(pre-activation) of conv3, conv2, conv1 as stored
+ * Sample b is the b-th sample of that minibatch: sample (M - 1) B + b of the batch, or, after a shuffled update, of the last
+ * epoch's order (aleppo_read_sample_order).  *n = B; *stored = the aleppo_bwd_tensor bits of what the route stored: all but
+ * ALEPPO_BWD_DCONV1 on the fused backward tail (ALEPPO_OPT_FUSED_BWD), which keeps dz1 on the CU - dconv1 is then left
+ * untouched.  n and stored may be NULL.
+ * Errors: no output, capacity < B: ALEPPO_ERR_INVALID_ARGUMENT; before any aleppo_train, after anything else has run the
+ * network since (aleppo_act / aleppo_step, aleppo_forward and every call that forwards as it does) or while a step is
+ * armed: ALEPPO_ERR_RUNTIME. */
+typedef enum {
+  ALEPPO_BWD_CONV1 = 1,
+  ALEPPO_BWD_CONV2 = 2,
+  ALEPPO_BWD_CONV3 = 4,
+  ALEPPO_BWD_FC = 8,
+  ALEPPO_BWD_DFC = 16,
+  ALEPPO_BWD_DCONV3 = 32,
+  ALEPPO_BWD_DCONV2 = 64,
+  ALEPPO_BWD_DCONV1 = 128
+} aleppo_bwd_tensor;
+int aleppo_export_backward(aleppo_ctx *ctx, int64_t capacity, float *conv1, float *conv2, float *conv3, float *fc,
+                           float *dfc, float *dconv3, float *dconv2, float *dconv1, int64_t *n, uint32_t *stored);
+
 /* Per-unit and per-layer activation statistics, reduced on the device where the activations are: dormant units (Sokar et
  * al. 2023, "The Dormant Neuron Phenomenon in Deep RL"), dead units and firing rates (Moalla et al. 2024, "No
  * Representation, No Trust").  The activations (about 45 KB per sample in bf16 at H = 512) never leave the device.

@@ -386,8 +386,10 @@ static void backward_one(const float *prm, const size_t *po, int H, int A, const
   conv_wgrad(da1, cols, 32, 256, 400, g + po[0], g + po[1]);
 }
 
-void oracle_net_backward(const float *params, int H, int A, int N, const float *acts, const float *dlogits,
-                         const float *dvalues, float *grads) {
+/* dacts (may be NULL): per sample the stored gradients [H + 3136 + 5184 + 12800] = dh, dz3, dz2, dz1 (NCHW, after the
+ * gates) - backward_one's scratch, kept */
+static void net_backward_stored(const float *params, int H, int A, int N, const float *acts, const float *dlogits,
+                                const float *dvalues, float *grads, float *dacts) {
   size_t po[13];
   oracle_param_offsets(H, A, po);
   const size_t np = po[12], aps = oracle_acts_per_sample(H);
@@ -402,11 +404,12 @@ void oracle_net_backward(const float *params, int H, int A, int N, const float *
 #endif
     float *cols = (float *)malloc(sizeof(float) * COLS_MAX);
     float *dcols = (float *)malloc(sizeof(float) * COLS_MAX);
-    float *scratch = (float *)malloc(sizeof(float) * ((size_t)H + A3 + A2 + A1));
+    const size_t dps = (size_t)H + A3 + A2 + A1;
+    float *scratch = (float *)malloc(sizeof(float) * dps);
 #pragma omp for schedule(static)
     for (int n = 0; n < N; ++n)
       backward_one(params, po, H, A, acts + (size_t)n * aps, dlogits + (size_t)n * A, dvalues[n],
-                   part + (size_t)tid * np, cols, dcols, scratch);
+                   part + (size_t)tid * np, cols, dcols, dacts ? dacts + (size_t)n * dps : scratch);
     free(cols);
     free(dcols);
     free(scratch);
@@ -418,6 +421,11 @@ void oracle_net_backward(const float *params, int H, int A, int N, const float *
     grads[i] = s;
   }
   free(part);
+}
+
+void oracle_net_backward(const float *params, int H, int A, int N, const float *acts, const float *dlogits,
+                         const float *dvalues, float *grads) {
+  net_backward_stored(params, H, A, N, acts, dlogits, dvalues, grads, NULL);
 }
 
 /* ------------------------------------------------------------------ bf16 emulation (rounding points: oracle.h) */
@@ -466,14 +474,18 @@ void oracle_net_forward_ex(const float *params, int H, int A, const uint8_t *obs
   else
     oracle_net_forward(params, H, A, obs, N, logits, values, acts);
 }
+void oracle_net_backward_stored(const float *params, int H, int A, int N, const float *acts, const float *dlogits,
+                                const float *dvalues, float *grads, float *dacts, int mode) {
+  if (mode == ORACLE_BF16)
+    emu_net_backward_d(params, H, A, N, acts, dlogits, dvalues, grads, dacts);
+  else if (mode == ORACLE_BF16_F32SUM)
+    emu_net_backward_f(params, H, A, N, acts, dlogits, dvalues, grads, dacts);
+  else
+    net_backward_stored(params, H, A, N, acts, dlogits, dvalues, grads, dacts);
+}
 void oracle_net_backward_ex(const float *params, int H, int A, int N, const float *acts, const float *dlogits,
                             const float *dvalues, float *grads, int mode) {
-  if (mode == ORACLE_BF16)
-    emu_net_backward_d(params, H, A, N, acts, dlogits, dvalues, grads);
-  else if (mode == ORACLE_BF16_F32SUM)
-    emu_net_backward_f(params, H, A, N, acts, dlogits, dvalues, grads);
-  else
-    oracle_net_backward(params, H, A, N, acts, dlogits, dvalues, grads);
+  oracle_net_backward_stored(params, H, A, N, acts, dlogits, dvalues, grads, NULL, mode);
 }
 
 /* ------------------------------------------------------------------ PPO loss: src/ai/ppo/losses.cc:4-43 */

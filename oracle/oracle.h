@@ -141,6 +141,10 @@ void oracle_net_forward_ex(const float *params, int H, int A, const uint8_t *obs
                            float *acts, int mode);
 void oracle_net_backward_ex(const float *params, int H, int A, int N, const float *acts, const float *dlogits,
                             const float *dvalues, float *grads, int mode);
+/* the same, and (dacts != NULL) what the backward pass stores on its way: per sample [H + 3136 + 5184 + 12800] floats =
+ * dh, dz3, dz2, dz1 in the reference's tensor order (NCHW), after the gates (and, in the emulated modes, the roundings) */
+void oracle_net_backward_stored(const float *params, int H, int A, int N, const float *acts, const float *dlogits,
+                                const float *dvalues, float *grads, float *dacts, int mode);
 int oracle_train_ex(float *params, float *adam_m, float *adam_v, int64_t *adam_step, int H, int A, const uint8_t *obs,
                     const int64_t *actions, const float *old_logp, const float *adv, const float *returns,
                     const uint8_t *masks, int N, int epochs, int M, double lr, float clip, float c_v, float c_e,

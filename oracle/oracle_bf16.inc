@@ -170,7 +170,7 @@ static void EMU(net_forward)(const float *params, int H, int A, const uint8_t *o
 }
 
 static void EMU(net_backward)(const float *params, int H, int A, int N, const float *acts, const float *dlogits,
-                              const float *dvalues, float *grads) {
+                              const float *dvalues, float *grads, float *dacts) {
   size_t po[13];
   oracle_param_offsets(H, A, po);
   const size_t np = po[12], aps = oracle_acts_per_sample(H);
@@ -187,11 +187,12 @@ static void EMU(net_backward)(const float *params, int H, int A, int N, const fl
     float *cols = (float *)malloc(sizeof(float) * COLS_MAX);
     ACC *dcols = (ACC *)malloc(sizeof(ACC) * COLS_MAX);
     ACC *din = (ACC *)malloc(sizeof(ACC) * A1);
-    float *scratch = (float *)malloc(sizeof(float) * ((size_t)H + A3 + A2 + A1));
+    const size_t dps = (size_t)H + A3 + A2 + A1; /* dacts: as oracle_net_backward_stored (the scratch, kept) */
+    float *scratch = (float *)malloc(sizeof(float) * dps);
 #pragma omp for schedule(static)
     for (int n = 0; n < N; ++n)
       EMU(backward_one)(pb, po, H, A, acts + (size_t)n * aps, dlogits + (size_t)n * A, dvalues[n],
-                        part + (size_t)tid * np, cols, dcols, din, scratch);
+                        part + (size_t)tid * np, cols, dcols, din, dacts ? dacts + (size_t)n * dps : scratch);
     free(cols);
     free(dcols);
     free(din);

@@ -218,13 +218,20 @@ def measured_ratio(ref, value):
     return float((d[ok] / (U * ref.Sa[ok])).max()) if ok.any() else 0.0
 
 
-def fp32_check(ref, got):
+def fp32_bound(ref):
+    """(c)'s bound per element, and R = the "blas" evaluation's ratio it is built on"""
+    R = ref.memo("R", lambda: measured_ratio(ref, ref.z32["blas"]))
+    return np.minimum(FLOOR_FACTOR * R * U * ref.Sa + 2 * U * np.abs(ref.z), ref.eps()), R
+
+
+def fp32_check(ref, got, extra=0.0):
     """check (c): dict(violations = indices of the elements outside the bound, R = the "blas" evaluation's ratio, ratio = the
-    same measurement of got, worst = the largest |got - act(z)| / bound)"""
+    same measurement of got, worst = the largest |got - act(z)| / bound); extra: more room per element, added to the bound
+    (tests/backward_ref.py: what a stated uncertainty of an input can move)"""
     got = np.asarray(got, np.float64)
     assert got.shape == ref.z.shape, (got.shape, ref.z.shape)
-    R = ref.memo("R", lambda: measured_ratio(ref, ref.z32["blas"]))
-    bound = np.minimum(FLOOR_FACTOR * R * U * ref.Sa + 2 * U * np.abs(ref.z), ref.eps())
+    bound, R = fp32_bound(ref)
+    bound = bound + extra
     d = np.abs(got - ref.act(ref.z))
     ok = ref.Sa > 0
     with np.errstate(invalid="ignore", divide="ignore"):

@@ -165,13 +165,21 @@ def net_forward(params, H, A, obs, want_acts=False, emulate_bf16=False, sums="do
     return (logits, values, acts) if want_acts else (logits, values)
 
 
-def net_backward(params, H, A, acts, dlogits, dvalues, emulate_bf16=False, sums="double"):
+def net_backward(params, H, A, acts, dlogits, dvalues, emulate_bf16=False, sums="double", want_stored=False):
+    """want_stored: also {"dfc" [N,H], "dconv3" [N,64,7,7], "dconv2" [N,64,9,9], "dconv1" [N,32,20,20]}, the gradients the
+    backward pass stores on its way (dh, dz3, dz2, dz1)"""
     params, acts, dlogits, dvalues = cf(params), cf(acts), cf(dlogits), cf(dvalues)
     g = np.zeros(param_count(H, A), np.float32)
-    lib().oracle_net_backward_ex(_p(params, C.c_float), H, A, acts.shape[0], _p(acts, C.c_float),
-                                 _p(dlogits, C.c_float), _p(dvalues, C.c_float), _p(g, C.c_float),
-                                 _mode(emulate_bf16, sums))
-    return g
+    N = acts.shape[0]
+    d = np.zeros((N, H + 3136 + 5184 + 12800), np.float32) if want_stored else None
+    lib().oracle_net_backward_stored(_p(params, C.c_float), H, A, N, _p(acts, C.c_float), _p(dlogits, C.c_float),
+                                     _p(dvalues, C.c_float), _p(g, C.c_float), _p(d, C.c_float),
+                                     _mode(emulate_bf16, sums))
+    if not want_stored:
+        return g
+    o = np.cumsum([0, H, 3136, 5184, 12800])
+    shapes = dict(dfc=(H,), dconv3=(64, 7, 7), dconv2=(64, 9, 9), dconv1=(32, 20, 20))
+    return g, {k: np.ascontiguousarray(d[:, o[i]:o[i + 1]]).reshape((N,) + shapes[k]) for i, k in enumerate(shapes)}
 
 
 def ppo_loss(logits, old_logp, actions, adv, values, returns, masks, clip=0.1, c_v=0.5, c_e=0.01, n_mask=0.0):
