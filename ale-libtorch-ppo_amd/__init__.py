@@ -85,6 +85,8 @@ RECYCLE_COUNTS = 5
 RECYCLE_CONV1, RECYCLE_CONV2, RECYCLE_CONV3, RECYCLE_FC, RECYCLE_ALL = 1, 2, 4, 8, 15
 RECYCLE_LAYERS = dict(conv1=RECYCLE_CONV1, conv2=RECYCLE_CONV2, conv3=RECYCLE_CONV3, fc=RECYCLE_FC, all=RECYCLE_ALL)
 RECYCLE_KEEP_MOMENTS = 1
+# aleppo_shrink_perturb: its flag (Engine.shrink_perturb)
+SP_RESET_MOMENTS = 1
 # aleppo_ema_read: the statistics of the exponentially averaged parameters (Engine.ema_stats)
 EMA_STATS_COUNT = 6
 EMA_STATS = dict(updates=0, decay=1, norm=2, param_norm=3, distance=4, relative_distance=5)
@@ -155,6 +157,10 @@ OPT_CLIP_PARAM, OPT_VALUE_CLIP_RANGE, OPT_VALUE_LOSS_COEF, OPT_ENTROPY_COEF, OPT
 OPT_REWARD_SCALE, OPT_REWARD_SCALE_CLIP = 23, 24  # (22 is unassigned)
 # which parameters the evaluation lanes act on: 0 live, 1 the averaged set of Engine.ema_open (Engine.eval_use_averaged)
 OPT_EVAL_PARAMS = 25
+# decoupled weight decay and the pull toward the anchor inside the optimizer step, each as its binary32 bit pattern
+# (Engine.set_regularization / Engine.regularization)
+OPT_WEIGHT_DECAY, OPT_ANCHOR_COEF = 26, 27
+REG_OPTIONS = dict(weight_decay=OPT_WEIGHT_DECAY, anchor_coef=OPT_ANCHOR_COEF)
 HYPER_OPTIONS = dict(clip_param=OPT_CLIP_PARAM, value_clip_range=OPT_VALUE_CLIP_RANGE,
                      value_loss_coef=OPT_VALUE_LOSS_COEF, entropy_coef=OPT_ENTROPY_COEF,
                      max_grad_norm=OPT_MAX_GRAD_NORM)
@@ -191,6 +197,7 @@ EXPORTS = [
     "aleppo_saliency_tables", "aleppo_saliency", "aleppo_saliency_perturbed",
     "aleppo_feature_rank",
     "aleppo_snapshot_take", "aleppo_snapshot_export", "aleppo_snapshot_import", "aleppo_policy_diff",
+    "aleppo_anchor_take", "aleppo_anchor_import", "aleppo_anchor_export", "aleppo_shrink_perturb",
     "aleppo_env_open", "aleppo_env_rollout", "aleppo_env_export_state", "aleppo_env_import_state", "aleppo_env_read",
     "aleppo_eval_env_open", "aleppo_eval_env_run", "aleppo_eval_env_export_state", "aleppo_eval_env_import_state",
     "aleppo_eval_env_read",
@@ -474,6 +481,7 @@ class Engine:
         self.actions = None  # view of the pinned action buffer, valid after the first act
         self._last_B = 1  # samples per minibatch of the last train() (export_backward's default capacity)
         self._ema_open = False  # ema_open has succeeded (run_state carries the average only then)
+        self._anchor_on = False  # an anchor_take / load_anchor has succeeded (run_state carries the anchor only then)
 
     def close(self):
         if getattr(self, "_ctx", None):
@@ -545,6 +553,8 @@ class Engine:
         if self._ema_open:  # (only while the average is open: the keys other callers see stay the same)
             flat, updates = self.ema_params()
             sd["ema"] = dict(params=flat, updates=np.int64(updates))
+        if self._anchor_on:  # (only once there is an anchor)
+            sd["anchor"] = self.anchor_params()
         return sd
 
     def load_run_state(self, sd):
@@ -555,6 +565,8 @@ class Engine:
             if not self._ema_open:
                 self.ema_open()
             self.load_ema(sd["ema"]["params"], int(sd["ema"]["updates"]))
+        if "anchor" in sd:
+            self.load_anchor(sd["anchor"])
 
     # -- exponentially averaged parameters --
     def ema_open(self):
@@ -786,6 +798,43 @@ class Engine:
         """the five current float32 values: {clip_param, value_clip_range, value_loss_coef, entropy_coef,
         max_grad_norm} (the config's until set; value_clip_range follows clip_param until set itself)"""
         return {name: bits_float(self.get_option(opt)) for name, opt in HYPER_OPTIONS.items()}
+
+    def set_regularization(self, weight_decay=None, anchor_coef=None):
+        """OPT_WEIGHT_DECAY / OPT_ANCHOR_COEF: decoupled weight decay (torch.optim.AdamW's weight_decay) and the strength of
+        the pull toward the anchor (L2 Init) of the next train() calls (None: leave as it is).  Each is rounded to float32
+        and passed as its bits; both must be finite and >= 0.  anchor_coef > 0 needs an anchor (anchor_take / load_anchor)
+        before train().  Under data parallelism every rank sets the same values and the same anchor."""
+        given = dict(weight_decay=weight_decay, anchor_coef=anchor_coef)
+        for name, x in given.items():
+            if x is not None:
+                self.set_option(REG_OPTIONS[name], float_bits(x))
+
+    def regularization(self):
+        """the two current float32 values: {weight_decay, anchor_coef} (0.0 until set)"""
+        return {name: bits_float(self.get_option(opt)) for name, opt in REG_OPTIONS.items()}
+
+    def anchor_take(self, source="live"):
+        """aleppo_anchor_take: anchor = the "live", "averaged" or "snapshot" parameters, by a device copy (enqueued only)"""
+        self._c(lib().aleppo_anchor_take(self._ctx, C.c_int(self._set(source))))
+        self._anchor_on = True
+
+    def load_anchor(self, flat):
+        """aleppo_anchor_import: flat float32 parameters in libtorch parameters() order -> the anchor"""
+        flat = _f32(flat).ravel()
+        self._c(lib().aleppo_anchor_import(self._ctx, _ptr(flat), C.c_size_t(flat.size)))
+        self._anchor_on = True
+
+    def anchor_params(self):
+        """aleppo_anchor_export: the anchor as flat float32 in libtorch parameters() order"""
+        out = np.zeros(self.param_count, np.float32)
+        self._c(lib().aleppo_anchor_export(self._ctx, _ptr(out), C.c_size_t(out.size)))
+        return out
+
+    def shrink_perturb(self, shrink, sigma, key=0, reset_moments=False):
+        """aleppo_shrink_perturb: every parameter p becomes shrink * p + sigma * xi, xi a fresh He-uniform draw from `key`
+        (recycle_units' draw; 0 for a bias), in place on the device; reset_moments zeroes both Adam moments."""
+        self._c(lib().aleppo_shrink_perturb(self._ctx, C.c_double(shrink), C.c_double(sigma), C.c_uint64(key),
+                                            C.c_int(SP_RESET_MOMENTS if reset_moments else 0)))
 
     def sample_order(self, epochs):
         """aleppo_read_sample_order: int32 [epochs, N], row e = the logical samples of epoch e in minibatch order

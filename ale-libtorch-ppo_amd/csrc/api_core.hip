@@ -654,7 +654,10 @@ extern "C" int aleppo_set_option(aleppo_ctx *c, int option, int value) {
   // (the two reward-scaling options are read by aleppo_finish_rollout alone: the update does not see them)
   const bool rollout_opt = option == ALEPPO_OPT_REWARD_SCALE || option == ALEPPO_OPT_REWARD_SCALE_CLIP;
   // (nor does ALEPPO_OPT_EVAL_PARAMS, which the evaluation lanes read alone)
-  if (option != ALEPPO_OPT_KL_COEF && !hyper_opt && !rollout_opt && option != ALEPPO_OPT_EVAL_PARAMS) {
+  // ALEPPO_OPT_WEIGHT_DECAY / ALEPPO_OPT_ANCHOR_COEF are device values too; what they select - adam_kernel where both are zero,
+  // reg_step_kernel otherwise - is part of the graph key (api_train.hip), so only a change of that choice re-arms the capture
+  const bool reg_opt = option == ALEPPO_OPT_WEIGHT_DECAY || option == ALEPPO_OPT_ANCHOR_COEF;
+  if (option != ALEPPO_OPT_KL_COEF && !hyper_opt && !rollout_opt && !reg_opt && option != ALEPPO_OPT_EVAL_PARAMS) {
     c->graph_key = Ctx::GraphKey();
     c->warm_key = Ctx::GraphKey();
   }
@@ -708,6 +711,12 @@ extern "C" int aleppo_set_option(aleppo_ctx *c, int option, int value) {
       return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT,
                      "ALEPPO_OPT_KL_COEF: the binary32 bits of a finite non-negative float (not -0.0, Inf or NaN)");
     c->kl_coef_bits = (uint32_t)value;
+  } else if (reg_opt) {
+    if (value < 0 || value >= 0x7F800000) // as for ALEPPO_OPT_KL_COEF
+      return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT,
+                     "ALEPPO_OPT_WEIGHT_DECAY / ALEPPO_OPT_ANCHOR_COEF: the binary32 bits of a finite non-negative float "
+                     "(not -0.0, Inf or NaN)");
+    (option == ALEPPO_OPT_WEIGHT_DECAY ? c->wd_bits : c->anchor_coef_bits) = (uint32_t)value;
   } else if (hyper_opt) {
     // the bits of a finite float, > 0 or (the two coefficients) >= 0: as an int, [1 or 0, 0x7F800000) - see above
     const bool zero_ok = option == ALEPPO_OPT_VALUE_LOSS_COEF || option == ALEPPO_OPT_ENTROPY_COEF;
@@ -776,6 +785,8 @@ extern "C" int aleppo_get_option(aleppo_ctx *c, int option, int64_t *value) {
   case ALEPPO_OPT_REWARD_SCALE: *value = c->reward_scale; break;
   case ALEPPO_OPT_REWARD_SCALE_CLIP: *value = (int64_t)float_bits(c->reward_scale_clip); break;
   case ALEPPO_OPT_EVAL_PARAMS: *value = c->eval_averaged; break;
+  case ALEPPO_OPT_WEIGHT_DECAY: *value = (int64_t)c->wd_bits; break;
+  case ALEPPO_OPT_ANCHOR_COEF: *value = (int64_t)c->anchor_coef_bits; break;
   default: return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "unknown option");
   }
   return ALEPPO_OK;

@@ -117,6 +117,8 @@ struct UpdatePlan {
   int epochs, M, nm; // nm = epochs * M optimizer steps
   long N, B;
   bool shuffle, vclip, val_transpose, advn, klpen, dp, two, bwd_fused;
+  bool reg;            // ALEPPO_OPT_WEIGHT_DECAY / ALEPPO_OPT_ANCHOR_COEF: either is non-zero - reg_step_kernel, not adam_kernel
+  const float *anchor; // ... the anchor it reads (nullptr: none, and then the anchor coefficient is zero)
   hipStream_t s, sw; // main stream; stream of the weight-gradient kernels (== s unless two)
   ncclComm_t comm;
   // The hyper-parameters of this call (ALEPPO_OPT_CLIP_PARAM and its kin), and the device block they are uploaded to:
@@ -137,6 +139,9 @@ static int plan_update(aleppo_ctx *c, int epochs, int M, UpdatePlan *plan) {
   const long N = c->batch_n;
   if (N <= 0)
     return set_err(c, ALEPPO_ERR_RUNTIME, "no batch: call aleppo_finish_rollout or aleppo_set_batch first");
+  if (c->anchor_coef_bits != 0 && !c->anchor_on)
+    return set_err(c, ALEPPO_ERR_RUNTIME,
+                   "ALEPPO_OPT_ANCHOR_COEF > 0 needs an anchor: call aleppo_anchor_take or aleppo_anchor_import first");
   c->pre_acted = -1; // the update's activations overwrite the acting scratch, and the weights change
   c->bwd.B = 0;      // (aleppo_export_backward: valid again once this update has run)
   if (N % M != 0)
@@ -163,6 +168,8 @@ static int plan_update(aleppo_ctx *c, int epochs, int M, UpdatePlan *plan) {
   p.shuffle = c->shuffle;
   p.advn = c->adv_norm_mb; // ALEPPO_OPT_ADV_NORM_MINIBATCH (statistics in advn_stats, grown with the metrics)
   p.klpen = c->kl_pen;     // ALEPPO_OPT_KL_PENALTY (the exact-KL plane kl_ps, beta in kl_beta)
+  p.reg = c->wd_bits != 0 || c->anchor_coef_bits != 0; // (valid patterns are >= +0.0f: non-zero bits are a value > 0)
+  p.anchor = p.reg && c->anchor_on ? c->Pa : nullptr;
   if (p.klpen && (rc = ensure_kl_storage(c)))
     return rc;
   if (p.shuffle && (rc = ensure_shuffle_storage(c, epochs, N)))
@@ -243,6 +250,13 @@ static int upload_call_scalars(aleppo_ctx *c, const UpdatePlan &p, double lr) {
   b[HYPER_CV] = p.hp.c_v;
   b[HYPER_CE] = p.hp.c_e;
   b[HYPER_MAX_NORM] = p.hp.max_norm;
+  // the decoupled terms' factors f_wd = lr * wd and f_an = lr * la, formed in double and rounded once (aleppo.h); both are
+  // uploaded by every call, and only reg_step_kernel reads them
+  float wd, la;
+  std::memcpy(&wd, &c->wd_bits, 4);
+  std::memcpy(&la, &c->anchor_coef_bits, 4);
+  b[HYPER_WD] = (float)(lr * (double)wd);
+  b[HYPER_ANCHOR] = (float)(lr * (double)la);
   HIPCHK(c, hipMemcpyAsync(c->hyper_blk, c->h_hyper_blk, HYPER_BLOCK * 4, hipMemcpyHostToDevice, s));
   // ... and, with ALEPPO_OPT_KL_PENALTY, beta: the head kernel reads it from device memory for the same reason
   if (p.klpen) {
@@ -499,7 +513,7 @@ static int enqueue_minibatch(aleppo_ctx *c, const UpdatePlan &p, int ep, int mb)
   // (the Adam kernel also writes the bf16 compute copy and the dgrad-side transposed layouts W2d / W3d / WfcT)
   launch_adam(s, c->P, c->G, c->M1, c->M2, c->prec == ALEPPO_BF16 ? c->Pc : nullptr, c->WfcT, c->W3d, c->W2d, L,
               prec, c->sumsq_part, nblk_norm, p.hpd, c->adam_sched + 2 * mi, c->cfg.adam_beta1, c->cfg.adam_beta2,
-              c->cfg.adam_eps, c->grad_norms + mi);
+              c->cfg.adam_eps, c->grad_norms + mi, p.reg, p.anchor);
   prof_end(c, ALEPPO_K_ADAM);
   return ALEPPO_OK;
 }
@@ -546,6 +560,8 @@ static Ctx::GraphKey graph_key(const UpdatePlan &p, const aleppo_ctx *c) {
   key.advn = p.advn ? c->advn_stats : nullptr;
   key.klpen = p.klpen ? 1 : 0;
   key.kl_ps = p.klpen ? c->kl_ps : nullptr;
+  key.reg = p.reg ? 1 : 0;
+  key.anchor = p.anchor;
   return key;
 }
 

@@ -68,8 +68,11 @@ struct Hyper {
 // The kernels read them, and the value-clip range, from a DEVICE block (ALEPPO_OPT_CLIP_PARAM, ALEPPO_OPT_VALUE_CLIP_RANGE,
 // ALEPPO_OPT_VALUE_LOSS_COEF, ALEPPO_OPT_ENTROPY_COEF, ALEPPO_OPT_MAX_GRAD_NORM): float [HYPER_BLOCK], 16-byte aligned,
 // uploaded in front of every update, so that a captured update follows values changed between calls.  The head kernels
-// read slots 0-3 as one 16-byte load, the Adam kernel slot 4.
-enum { HYPER_CLIP = 0, HYPER_VCLIP = 1, HYPER_CV = 2, HYPER_CE = 3, HYPER_MAX_NORM = 4, HYPER_BLOCK = 8 };
+// read slots 0-3 as one 16-byte load, the Adam kernel slot 4.  Slots 5-6: f_wd = (float)(lr * weight decay) and f_an =
+// (float)(lr * anchor coefficient) of the call (ALEPPO_OPT_WEIGHT_DECAY, ALEPPO_OPT_ANCHOR_COEF), which reg_step_kernel
+// alone reads.
+enum { HYPER_CLIP = 0, HYPER_VCLIP = 1, HYPER_CV = 2, HYPER_CE = 3, HYPER_MAX_NORM = 4, HYPER_WD = 5, HYPER_ANCHOR = 6,
+       HYPER_BLOCK = 8 };
 
 // Kernel-selection switches of ONE context (aleppo_set_option; initial values from the environment, read once in
 // aleppo_create).  The launch helpers read them through tuning(): a thread-local pointer that every stateful entry
@@ -211,6 +214,13 @@ struct Ctx {
   bool vclip_range_set = false;
   float last_max_norm = 0.f;                     // hyper.max_norm of the last aleppo_train (aleppo_export_grads)
   float *hyper_blk = nullptr, *h_hyper_blk = nullptr; // [HYPER_BLOCK], uploaded at each aleppo_train (device / pinned)
+  // ---- ALEPPO_OPT_WEIGHT_DECAY / ALEPPO_OPT_ANCHOR_COEF: the two coefficients as binary32 bit patterns (finite, >= 0), and
+  // the anchor of aleppo_anchor_take / aleppo_anchor_import: a fourth parameter set, fp32 only, never forwarded, allocated
+  // on first use and written by those two calls alone.  Either coefficient non-zero: the update launches reg_step_kernel
+  // in adam_kernel's place
+  uint32_t wd_bits = 0, anchor_coef_bits = 0;
+  bool anchor_on = false;          // a take or an import has succeeded
+  float *Pa = nullptr;             // fp32, internal layout, L.total() floats (pads zero)
   // ---- ALEPPO_OPT_REWARD_SCALE / _CLIP: device storage allocated on first use (ensure_rs_storage), never moved
   bool reward_scale = false;
   float reward_scale_clip = 10.0f;
@@ -232,10 +242,12 @@ struct Ctx {
     const void *advn = nullptr;  // ALEPPO_OPT_ADV_NORM_MINIBATCH: the statistics storage (nullptr: off)
     int klpen = 0;               // ALEPPO_OPT_KL_PENALTY (beta is a device value and not part of the key)
     const void *kl_ps = nullptr; // ... its per-sample plane (nullptr: off)
+    int reg = 0;                 // reg_step_kernel in adam_kernel's place (the coefficients are device values, not part of the key)
+    const void *anchor = nullptr; // ... the anchor it reads (nullptr: none yet, or adam_kernel)
     bool operator==(const GraphKey &o) const {
       return epochs == o.epochs && M == o.M && two == o.two && N == o.N && metric_ps == o.metric_ps &&
              metric_red == o.metric_red && order == o.order && vclip == o.vclip && advn == o.advn &&
-             klpen == o.klpen && kl_ps == o.kl_ps;
+             klpen == o.klpen && kl_ps == o.kl_ps && reg == o.reg && anchor == o.anchor;
     }
   } graph_key, warm_key;
   long graph_replays = 0;
@@ -477,7 +489,10 @@ void launch_adam(hipStream_t s, float *P, const float *G_in, float *M1, float *M
                  void *WfcT, void *W3d, void *W2d, const ParamLayout &L, int prec, const float *partials, int nblk,
                  const float *hpd,   // the device block of the hyper-parameter options: slot HYPER_MAX_NORM is the limit
                  const float *sched, // device: { lr / (1 - beta1^t), sqrt(1 - beta2^t) } of this step
-                 float beta1, float beta2, float eps, float *grad_norm_out);
+                 float beta1, float beta2, float eps, float *grad_norm_out,
+                 // reg: reg_step_kernel instead of adam_kernel - the same step, then p -= f_wd * p0 + f_an * (p0 - a) with the
+                 // factors of slots HYPER_WD / HYPER_ANCHOR and a = anchor[i] (nullptr: +0.0f)
+                 bool reg = false, const float *anchor = nullptr);
 void launch_pack_dgrad(hipStream_t s, const float *P, const ParamLayout &L, void *W2d, void *W3d, void *WfcT,
                        int prec);
 void launch_cast_params(hipStream_t s, const float *P, void *Pc, long n);
@@ -570,6 +585,9 @@ void launch_policy_diff_stats(hipStream_t s, const PolicyDiffPlan &pl, void *scr
 void launch_recycle_mask(hipStream_t s, const double *units_dev, int H, double tau, int layers, uint8_t *mask);
 void launch_recycle(hipStream_t s, const ParamLayout &L, const uint8_t *mask, unsigned long long key, bool keep_moments,
                     float *P, float *M1, float *M2);
+// aleppo_shrink_perturb (recycle.hip: it shares the draw and the layout-to-export index map with the pass above): one pass
+// over P, p' = lam * p + sg * xi as three fp32 operations; key: splitmix64 of the call's key.  Pads are not written.
+void launch_shrink_perturb(hipStream_t s, const ParamLayout &L, unsigned long long key, float lam, float sg, float *P);
 // aleppo_saliency / aleppo_saliency_perturbed (saliency.hip).  SalTables: aleppo_saliency_tables' two tables, passed by value.
 // blur: samples [s0, s0 + count) of the call (sample s of the call is sample map.n0 + s of obs under map) -> blur[0 .. count),
 // lane k only where bit k of planes is set.  perturb: pairs [j0, j0 + ns) of the call, pair j = sample j / per at position

@@ -1121,13 +1121,18 @@ struct AdamElement {
   float p, m, v;
 };
 // g: the raw gradient; m1, m2, p0: the element's moments and parameter before the step.  The one copy of the update's
-// arithmetic: both paths of adam_kernel call it, so their bits agree by construction.
+// arithmetic: both paths of both entry points call it, so their bits agree by construction.  The three fused
+// multiply-adds are WRITTEN OUT and contraction is off: m = fma(m1, beta1, fl(omb1 g)), v = fma(m2, beta2, fl(omb2 fl(g g))),
+// p = fma(-step_size, fl(m / denom), p0).  These are the forms hipcc chose at every site of adam_kernel while the
+// expressions were left to it; which product of a sum of two it fuses is its choice, and it chose the other one for v at
+// 30 of 34 sites once this function was inlined through optimizer_step - one ulp in v, and a different run.
 __device__ __forceinline__ AdamElement adam_element(float g, float m1, float m2, float p0, const AdamScalars &a) {
+#pragma clang fp contract(off)
   g *= a.coef;
-  const float m = m1 * a.beta1 + a.omb1 * g;
-  const float v = m2 * a.beta2 + a.omb2 * (g * g);
+  const float m = __builtin_fmaf(m1, a.beta1, a.omb1 * g);
+  const float v = __builtin_fmaf(m2, a.beta2, a.omb2 * (g * g));
   const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-  return {p0 - a.step_size * (m / denom), m, v};
+  return {__builtin_fmaf(-a.step_size, m / denom, p0), m, v};
 }
 // The dgrad-side weight layouts are TRANSPOSES of three weight tensors (W3d[c][(tap,oc)], W2d[class][c][(ab,oc)],
 // WfcT[j][o]): the blocks that own those tensors walk them in 64-row tiles, write the updated weight to the compute copy
@@ -1140,15 +1145,30 @@ struct AdamTiles {
   int first[4];     // first tile index of each tensor (+ total)
   int H;
 };
+// ALEPPO_OPT_WEIGHT_DECAY / ALEPPO_OPT_ANCHOR_COEF (aleppo.h): the decoupled terms r = f_wd * p0 + f_an * (p0 - a) leave the
+// parameter Adam produced, q.  They never pass through the clip or the moments.  The one copy of their arithmetic.
+__device__ __forceinline__ float reg_element(float q, float p0, float a, float f_wd, float f_an) {
+#pragma clang fp contract(off) // (as in adam_element: the one fused multiply-add is written out)
+  const float r = __builtin_fmaf(f_wd, p0, f_an * (p0 - a));
+  return q - r;
+}
+// The optimizer step, the body of both entry points below.  REG = false is adam_kernel as it always was: anchor and the
+// two hyper slots are never read and no instruction of the decoupled terms exists in it.  REG = true (reg_step_kernel)
+// also reads slots HYPER_WD / HYPER_ANCHOR and, where there is one, the anchor (nullptr: a reads as +0.0f, and f_an is 0).
 // hpd: the device block of the hyper-parameter options (common.hpp HYPER_*): slot HYPER_MAX_NORM is the gradient-norm
 // limit, a device value so that a captured update follows ALEPPO_OPT_MAX_GRAD_NORM
-template <class T>
-__global__ __launch_bounds__(256) void adam_kernel(float *P, const float *__restrict__ G, float *M1, float *M2, T *Pc,
-                                                    T *WfcT, T *W3d, T *W2d, AdamTiles tl, long n_flat,
-                                                    long4_ranges fr, const float *__restrict__ partials, int nblk,
-                                                    const float *__restrict__ hpd, const float *__restrict__ sched,
-                                                    float beta1, float beta2, float eps, float *grad_norm_out) {
+template <class T, bool REG>
+__device__ __forceinline__ void optimizer_step(float *P, const float *G, float *M1, float *M2, T *Pc, T *WfcT, T *W3d,
+                                               T *W2d, const AdamTiles &tl, long n_flat, const long4_ranges &fr,
+                                               const float *partials, int nblk, const float *hpd, const float *sched,
+                                               float beta1, float beta2, float eps, float *grad_norm_out,
+                                               const float *anchor) { // (__restrict__: on the entry points' parameters)
   const float max_norm = hpd[HYPER_MAX_NORM];
+  float f_wd = 0.f, f_an = 0.f;
+  if constexpr (REG) {
+    f_wd = hpd[HYPER_WD];
+    f_an = hpd[HYPER_ANCHOR];
+  }
   __shared__ float s4[4];
   __shared__ float tile[64][65];
   float s = 0.f;
@@ -1200,8 +1220,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float *P, const float *__rest
     if (c < cols) {
       // all 64 loads of a thread's 16 elements are issued before the first store (P / M1 / M2 are read and written through
       // the same pointers, so the compiler may not hoist them itself; a dependent load-compute-store chain per element made
-      // this kernel latency-bound: 23 vs 13 us)
-      float g[16], m1[16], m2[16], p0[16];
+      // this kernel latency-bound: 23 vs 13 us).  REG: the 16 anchor loads join the batch - issued after the first store
+      // they would wait behind it, one more dependent round trip per element
+      float g[16], m1[16], m2[16], p0[16], an[REG ? 16 : 1];
 #pragma unroll
       for (int k = 0; k < 16; ++k) {
         const int r = r4 + 4 * k;
@@ -1210,13 +1231,17 @@ __global__ __launch_bounds__(256) void adam_kernel(float *P, const float *__rest
         m1[k] = M1[i];
         m2[k] = M2[i];
         p0[k] = P[i];
+        if constexpr (REG)
+          an[k] = anchor ? anchor[i] : 0.f;
       }
 #pragma unroll
       for (int k = 0; k < 16; ++k) {
         const int r = r4 + 4 * k;
         if (r < rows) {
           const long i = src + (long)r * rs + c;
-          const AdamElement e = adam_element(g[k], m1[k], m2[k], p0[k], a);
+          AdamElement e = adam_element(g[k], m1[k], m2[k], p0[k], a);
+          if constexpr (REG)
+            e.p = reg_element(e.p, p0[k], an[k], f_wd, f_an);
           M1[i] = e.m;
           M2[i] = e.v;
           P[i] = e.p;
@@ -1245,7 +1270,14 @@ __global__ __launch_bounds__(256) void adam_kernel(float *P, const float *__rest
       }
       i -= fr.len[q];
     }
-    const AdamElement e = adam_element(G[i], M1[i], M2[i], P[i], a);
+    float p0 = 0.f, an = 0.f;
+    if constexpr (REG) { // (both loads before the stores below, like the tile path's)
+      p0 = P[i];
+      an = anchor ? anchor[i] : 0.f;
+    }
+    AdamElement e = adam_element(G[i], M1[i], M2[i], P[i], a);
+    if constexpr (REG)
+      e.p = reg_element(e.p, p0, an, f_wd, f_an);
     M1[i] = e.m;
     M2[i] = e.v;
     P[i] = e.p;
@@ -1253,9 +1285,32 @@ __global__ __launch_bounds__(256) void adam_kernel(float *P, const float *__rest
       Pc[i] = (T)e.p;
   }
 }
+template <class T>
+__global__ __launch_bounds__(256) void adam_kernel(float *P, const float *__restrict__ G, float *M1, float *M2, T *Pc,
+                                                    T *WfcT, T *W3d, T *W2d, AdamTiles tl, long n_flat,
+                                                    long4_ranges fr, const float *__restrict__ partials, int nblk,
+                                                    const float *__restrict__ hpd, const float *__restrict__ sched,
+                                                    float beta1, float beta2, float eps, float *grad_norm_out) {
+  optimizer_step<T, false>(P, G, M1, M2, Pc, WfcT, W3d, W2d, tl, n_flat, fr, partials, nblk, hpd, sched, beta1, beta2,
+                           eps, grad_norm_out, nullptr);
+}
+// adam_kernel with the decoupled terms of ALEPPO_OPT_WEIGHT_DECAY / ALEPPO_OPT_ANCHOR_COEF: launched in its place by a
+// context in which either coefficient is not zero, and by no other
+template <class T>
+__global__ __launch_bounds__(256) void reg_step_kernel(float *P, const float *__restrict__ G, float *M1, float *M2, T *Pc,
+                                                        T *WfcT, T *W3d, T *W2d, AdamTiles tl, long n_flat,
+                                                        long4_ranges fr, const float *__restrict__ partials, int nblk,
+                                                        const float *__restrict__ hpd,
+                                                        const float *__restrict__ sched, float beta1, float beta2,
+                                                        float eps, float *grad_norm_out,
+                                                        const float *__restrict__ anchor) {
+  optimizer_step<T, true>(P, G, M1, M2, Pc, WfcT, W3d, W2d, tl, n_flat, fr, partials, nblk, hpd, sched, beta1, beta2, eps,
+                          grad_norm_out, anchor);
+}
 void launch_adam(hipStream_t s, float *P, const float *G_in, float *M1, float *M2, void *Pc,
                  void *WfcT, void *W3d, void *W2d, const ParamLayout &L, int prec, const float *partials, int nblk,
-                 const float *hpd, const float *sched, float beta1, float beta2, float eps, float *grad_norm_out) {
+                 const float *hpd, const float *sched, float beta1, float beta2, float eps, float *grad_norm_out,
+                 bool reg, const float *anchor) {
   AdamTiles tl;
   tl.off[0] = (long)L.off[P_WFC];
   tl.off[1] = (long)L.off[P_W3];
@@ -1276,6 +1331,18 @@ void launch_adam(hipStream_t s, float *P, const float *G_in, float *M1, float *M
     n_flat += fr.len[q];
   }
   const int nb = tl.first[3] + (int)std::min<long>((n_flat + 255) / 256, 1024);
+  if (reg) { // same grid, same arguments, and the anchor behind them
+    if (prec == ALEPPO_BF16)
+      hipLaunchKernelGGL(reg_step_kernel<bf16>, dim3(nb), dim3(256), 0, s, P, G_in, M1, M2, static_cast<bf16 *>(Pc),
+                         static_cast<bf16 *>(WfcT), static_cast<bf16 *>(W3d), static_cast<bf16 *>(W2d), tl, n_flat, fr,
+                         partials, nblk, hpd, sched, beta1, beta2, eps, grad_norm_out, anchor);
+    else
+      hipLaunchKernelGGL(reg_step_kernel<float>, dim3(nb), dim3(256), 0, s, P, G_in, M1, M2,
+                         static_cast<float *>(nullptr), static_cast<float *>(WfcT), static_cast<float *>(W3d),
+                         static_cast<float *>(W2d), tl, n_flat, fr, partials, nblk, hpd, sched, beta1, beta2, eps,
+                         grad_norm_out, anchor);
+    return;
+  }
   if (prec == ALEPPO_BF16)
     hipLaunchKernelGGL(adam_kernel<bf16>, dim3(nb), dim3(256), 0, s, P, G_in, M1, M2,
                        static_cast<bf16 *>(Pc), static_cast<bf16 *>(WfcT), static_cast<bf16 *>(W3d),

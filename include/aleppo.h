@@ -626,6 +626,46 @@ int aleppo_recycle_dormant(aleppo_ctx *ctx, const uint8_t *observations, int64_t
                            uint64_t key, int flags, uint8_t *mask_out, size_t unit_count,
                            int64_t counts[ALEPPO_RECYCLE_COUNTS]);
 
+/* The anchor of ALEPPO_OPT_ANCHOR_COEF: the parameters the optimizer step pulls toward (L2 Init: the initial ones).  A
+ * fourth parameter set in the private layout, fp32 only, never forwarded, allocated on the first take or import through
+ * the context's memory registry and never again; only these calls write it.  It is NOT a set aleppo_policy_diff or
+ * aleppo_snapshot_take accept: their ALEPPO_SET_* stay the three they were.
+ * aleppo_anchor_take(source_set): anchor = ALEPPO_SET_LIVE, ALEPPO_SET_AVERAGED or ALEPPO_SET_SNAPSHOT as it stands, one
+ *   device-to-device copy on the context's main stream; the call enqueues only.
+ * aleppo_anchor_import / aleppo_anchor_export move it in the order and with the count checks of aleppo_snapshot_import /
+ *   aleppo_snapshot_export (aleppo_load_params / aleppo_export_params).
+ * Interactions: aleppo_load_params, aleppo_recycle_units / aleppo_recycle_dormant, aleppo_shrink_perturb, the aleppo_ema_*
+ *   and aleppo_snapshot_* calls never touch the anchor; aleppo_train only reads it.  aleppo_state_digest does not cover it:
+ *   a checkpoint stores it with aleppo_anchor_export.  No call is a collective; under data parallelism every rank gives
+ *   itself the same anchor.
+ * Errors: an unknown source set, a NULL flat or a wrong count: ALEPPO_ERR_INVALID_ARGUMENT; a source set that does not
+ *   exist yet, aleppo_anchor_export before any take or import, any call while a step is armed: ALEPPO_ERR_RUNTIME.  A failed
+ *   call changes nothing. */
+int aleppo_anchor_take(aleppo_ctx *ctx, int source_set);
+int aleppo_anchor_import(aleppo_ctx *ctx, const float *flat, size_t count);
+int aleppo_anchor_export(aleppo_ctx *ctx, float *flat, size_t count);
+
+/* Shrink and perturb (Ash & Adams 2020), one shot, outside the update: every parameter is scaled and a fraction of a fresh
+ * initialisation is added, in place on the device; every derived copy (the bf16 compute copy, the data-gradient layouts)
+ * follows, as after aleppo_recycle_units.  Per element, lam = (float)shrink, sg = (float)sigma:
+ *     p' = fl(fl(lam * p) + fl(sg * xi))             three fp32 operations, no fused multiply-add
+ *   xi = the draw of aleppo_recycle_units at the same place: a_l * ((float)k * 0x1p-23f) with
+ *     r = splitmix64(splitmix64(key) ^ (uint64)i), k = (int32)(r >> 40) - 8388608, i the element's index in the flat
+ *     aleppo_export_params vector, a_l = (float)sqrt(6.0 / fan_in): fan_in = 256, 512, 576, 3136 for the conv1, conv2, conv3
+ *     and fc weights, H for the action and the value weight rows.  xi = 0 for every bias: biases only shrink.
+ *   Any host recomputes it bit for bit.  Alignment pads are not written.
+ * flags: ALEPPO_SP_RESET_MOMENTS sets exp_avg and exp_avg_sq of every element to +0.0f; without it they are kept.  The Adam
+ *   step count, the gradient, the averaged set, the snapshot and the anchor are never touched.
+ * Afterwards aleppo_tensor_stats refuses ALEPPO_TS_SEC_STEP until the next aleppo_train and what aleppo_step pre-computed
+ *   for the next aleppo_act is dropped, as after a recycle.  A captured update stays valid: no pointer changes.
+ *   shrink = 1, sigma = 0 runs the pass and changes no bit.
+ * It is deterministic in (key, i), so it is allowed under data parallelism: every rank passes the same arguments (the key
+ *   must not contain the rank).  It runs on the context's stream, synchronises that stream only and is never a collective.
+ * Errors: shrink not finite or outside [0, 1], sigma not finite, negative or beyond a float, unknown flag bits:
+ *   ALEPPO_ERR_INVALID_ARGUMENT; a step is armed: ALEPPO_ERR_RUNTIME.  A failed call changes nothing. */
+enum { ALEPPO_SP_RESET_MOMENTS = 1 }; /* flags */
+int aleppo_shrink_perturb(aleppo_ctx *ctx, double shrink, double sigma, uint64_t key, int flags);
+
 /* Exponentially averaged parameters (an EMA of the weights: torch.optim.swa_utils.AveragedModel / torch_ema, the "EWMA
  * policy" of Hilton, Cobbe and Schulman 2021; the reference has none): a second copy of the parameters on the device that
  * follows the live ones by e' = decay * e + (1 - decay) * p after every update the caller chooses, and that the
@@ -1221,7 +1261,7 @@ typedef enum {
   ALEPPO_K_INGEST = 0,      /* preprocess + frame stack + rollout-slot write */
   ALEPPO_K_GAE = 1,         /* reward clamp (or ALEPPO_OPT_REWARD_SCALE's scan and merge) + GAE + returns + old log-probs */
   ALEPPO_K_HEAD = 2,        /* heads + PPO loss forward/backward */
-  ALEPPO_K_ADAM = 3,        /* sum of squares + clip + Adam + dgrad weight repack */
+  ALEPPO_K_ADAM = 3,        /* sum of squares + clip + Adam (with ALEPPO_OPT_WEIGHT_DECAY / _ANCHOR_COEF: its regularised form) + dgrad weight repack */
   ALEPPO_K_CONV1_FWD = 4,
   ALEPPO_K_CONV2_FWD = 5,
   ALEPPO_K_CONV3_FWD = 6,
@@ -1422,7 +1462,7 @@ typedef enum {
                                       ALEPPO_OPT_KL_COEF (default: the bits of 10.0f).  Valid: finite and > 0; anything else
                                       is ALEPPO_ERR_INVALID_ARGUMENT and leaves the old value in place.  Read at each
                                       aleppo_finish_rollout */
-  ALEPPO_OPT_EVAL_PARAMS = 25       /* which parameters the evaluation lanes act on.  0 (default): the live ones.  1: the
+  ALEPPO_OPT_EVAL_PARAMS = 25,      /* which parameters the evaluation lanes act on.  0 (default): the live ones.  1: the
                                       averaged set of aleppo_ema_open - every weight and bias of aleppo_eval_act's and
                                       aleppo_eval_env_run's acting forward and of the evaluation head (the compute-type
                                       copy for the convolution and fc weights, the fp32 set for the biases and the heads).
@@ -1431,6 +1471,36 @@ typedef enum {
                                       ALEPPO_REC_EVAL recorder then records the AVERAGED policy's logits, values and
                                       actions.  1 before aleppo_ema_open: ALEPPO_ERR_RUNTIME; any other value:
                                       ALEPPO_ERR_INVALID_ARGUMENT; both leave the old value in place */
+  /* 26-27: decoupled regularisation INSIDE the optimizer step.  Each carries the IEEE-754 binary32 BIT PATTERN of its float in
+     `value`, like ALEPPO_OPT_KL_COEF: valid are exactly the finite non-negative floats, value in [0, 0x7F800000); anything else
+     is ALEPPO_ERR_INVALID_ARGUMENT and leaves the old value in place; the default is 0 = +0.0f; aleppo_get_option returns the
+     bits.  With wd the weight decay and la the anchor coefficient, every optimizer step of an aleppo_train(lr, ...) call uses
+       f_wd = (float)((double)lr * (double)wd)        f_an = (float)((double)lr * (double)la)
+     uploaded into two slots of the device hyper-parameter block at the start of the call, next to the five values of 17-21.
+     For every element of the parameters (all 12 tensors), p0 the parameter before the step and a the anchor's element:
+       q = the parameter Adam's step produces from p0, exactly as without the options (moments, clip factor, step size)
+       r = fma(f_wd, p0, fl(f_an * fl(p0 - a)))       fp32: one fused multiply-add, written out
+       p = fl(q - r)
+     and p is what the master parameters, the bf16 compute copy and the data-gradient layouts receive, in the same launch.
+     The terms are DECOUPLED: they never pass through the gradient-norm clip or Adam's moments, so the moments, the reported
+     grad_norm, aleppo_export_grads and every metric are what they are without the options.  With la = 0 this is
+     torch.optim.AdamW (Loshchilov & Hutter 2019): p0 (1 - lr wd) - step.  With wd = 0 it is the decoupled form of L2 Init /
+     regenerative regularisation (Kumar, Marklund & Van Roy 2023).  The coupled form (the gradient grows by wd * p before the
+     norm) and a per-tensor selection (no decay on biases) are out of scope.
+     The anchor a is a fourth parameter set: aleppo_anchor_take / aleppo_anchor_import below.  aleppo_train with la > 0 and no
+     anchor is ALEPPO_ERR_RUNTIME and changes nothing; weight decay alone needs no anchor and allocates nothing (a reads as
+     +0.0f, f_an is 0).
+     A context whose two coefficients are both zero launches the Adam kernel it always launched and nothing else: it is
+     bit-identical and equally fast whether the options were never set or set back to zero.  Otherwise a second entry point
+     over the same step is launched in its place, which also reads the anchor: one more fp32 stream.  Every schedule works -
+     eager or ALEPPO_OPT_UPDATE_GRAPH, fp32 or bf16, ALEPPO_OPT_MINIBATCH_SHUFFLE, ALEPPO_OPT_VALUE_CLIP,
+     ALEPPO_OPT_ADV_NORM_MINIBATCH, ALEPPO_OPT_KL_PENALTY, one GPU or data parallel.  A captured update follows coefficients
+     changed between calls and equals the eager update bit for bit; only a change of WHICH kernel runs (both zero <-> not, or
+     the first anchor) re-arms the capture.  aleppo_tensor_stats' STEP section keeps recomputing Adam's term from the moments
+     and does not include r.  With data parallelism EVERY RANK MUST SET THE SAME VALUES AND THE SAME ANCHOR before the same
+     update (they are not exchanged: ranks that decay differently apply different steps and drift apart). */
+  ALEPPO_OPT_WEIGHT_DECAY = 26,    /* wd, torch.optim.AdamW's weight_decay.  Valid: finite and >= 0 */
+  ALEPPO_OPT_ANCHOR_COEF = 27      /* la, the strength of the pull toward the anchor.  Valid: finite and >= 0 */
 } aleppo_option;
 int aleppo_set_option(aleppo_ctx *ctx, int option, int value);
 /* Current value of an option; for ALEPPO_OPT_UPDATE_GRAPH the number of graph launches so far (0 = every update ran

@@ -17,7 +17,8 @@ constexpr char CKPT_MAGIC[8] = {'A', 'L', 'E', 'P', 'P', 'O', 'C', 'K'};
 constexpr char CKPT_END[8] = {'A', 'L', 'E', 'P', 'P', 'O', 'E', 'N'};
 constexpr uint32_t CKPT_VERSION = 1;
 enum CkptSection : uint32_t { CK_PARAMS = 1, CK_OPTIMIZER = 2, CK_REWARD_SCALE = 3, CK_ROLLOUT = 4, CK_TRAINER = 5, CK_DIGEST = 6,
-                              CK_EMA = 7 }; // (CK_EMA is optional: written only by runs with ema_decay, ignored by runs without)
+                              CK_EMA = 7,   // (CK_EMA is optional: written only by runs with ema_decay, ignored by runs without)
+                              CK_ANCHOR = 8 }; // (optional like CK_EMA: written only by runs with l2_init_coef > 0, which need it to resume)
 static const char *const DIGEST_NAMES[ALEPPO_DIGEST_COUNT] = {"params", "optimizer", "rollout", "reward_scale"};
 struct CkptShape {
   uint32_t E, T, A, H, precision, world, rank, reserved;
@@ -34,6 +35,11 @@ static std::string ema_section(const std::vector<float> &avg, uint64_t updates) 
   std::string s(reinterpret_cast<const char *>(avg.data()), avg.size() * sizeof(float));
   put(s, updates);
   return s;
+}
+// the bytes of the optional section CK_ANCHOR: the anchor of l2_init_coef (aleppo_anchor_export, reference order).  Outside
+// visit_checkpoint like CK_EMA: the files of runs without the key stay byte-identical.
+static std::string anchor_section(const std::vector<float> &anchor) {
+  return std::string(reinterpret_cast<const char *>(anchor.data()), anchor.size() * sizeof(float));
 }
 // What the library exports and imports (the learner's sections and the digest) ...
 struct DeviceState {

@@ -79,6 +79,13 @@ struct Config {
   double ema_decay = 0;        // in [0, 1)
   bool ema_warmup = false;     // update n (n updates so far) runs with min(ema_decay, (1 + n) / (10 + n)): TensorFlow / timm
   bool eval_averaged = false;  // evaluation acts on the averaged parameters (ALEPPO_OPT_EVAL_PARAMS = 1)
+  // extension: regularisation inside the optimizer step (ALEPPO_OPT_WEIGHT_DECAY / ALEPPO_OPT_ANCHOR_COEF) and shrink and
+  // perturb after the update of every n-th rollout (aleppo_shrink_perturb)
+  double weight_decay = 0;     // torch.optim.AdamW's weight_decay (absent or 0: off)
+  double l2_init_coef = 0;     // the pull toward the INITIAL parameters (L2 Init); > 0: the anchor is taken before the first update
+  size_t shrink_perturb_interval = 0; // 0: off
+  double shrink_perturb_shrink = 1.0; // in [0, 1]
+  double shrink_perturb_sigma = 0.0;  // >= 0
   // extension: perturbation saliency videos of environment 0 of rank 0 (aleppo_saliency; trainer/saliency.hpp), after the
   // update of every saliency_interval-th rollout, with the grid stride and the two sigmas of aleppo_saliency_config
   bool record_saliency = false;
@@ -347,6 +354,28 @@ static Config load_config(const std::string &path) { // keys / defaults of src/b
       throw std::runtime_error(std::string(k) + " needs ema_decay");
   if (kv.count("eval_averaged") && c.eval_interval == 0)
     throw std::runtime_error("eval_averaged needs eval_interval > 0");
+  // what aleppo_set_option / aleppo_shrink_perturb would refuse is refused here ("nan" / "inf" do not parse: bad value)
+  for (const auto &k : {std::make_pair("weight_decay", &c.weight_decay), std::make_pair("l2_init_coef", &c.l2_init_coef)}) {
+    read_key(kv, k.first, *k.second);
+    const float f = (float)*k.second;
+    if (!(std::isfinite(*k.second) && *k.second >= 0 && std::isfinite(f)))
+      throw std::runtime_error(std::string(k.first) + " must be finite and non-negative");
+  }
+  if (kv.count("shrink_perturb_interval")) {
+    const long interval = as<long>(kv, "shrink_perturb_interval", 0);
+    if (interval < 1)
+      throw std::runtime_error("shrink_perturb_interval must be positive");
+    c.shrink_perturb_interval = (size_t)interval;
+  }
+  read_key(kv, "shrink_perturb_shrink", c.shrink_perturb_shrink);
+  read_key(kv, "shrink_perturb_sigma", c.shrink_perturb_sigma);
+  if (!(std::isfinite(c.shrink_perturb_shrink) && c.shrink_perturb_shrink >= 0 && c.shrink_perturb_shrink <= 1))
+    throw std::runtime_error("shrink_perturb_shrink must be in [0, 1]");
+  if (!(std::isfinite(c.shrink_perturb_sigma) && c.shrink_perturb_sigma >= 0 && std::isfinite((float)c.shrink_perturb_sigma)))
+    throw std::runtime_error("shrink_perturb_sigma must be finite and non-negative");
+  for (const char *k : {"shrink_perturb_shrink", "shrink_perturb_sigma"})
+    if (kv.count(k) && !c.shrink_perturb_interval) // (nothing else reads them)
+      throw std::runtime_error(std::string(k) + " needs shrink_perturb_interval");
   read_key(kv, "log_policy_churn", c.log_policy_churn);
   {
     const long interval = as<long>(kv, "policy_churn_interval", 1);
@@ -462,6 +491,14 @@ static HParams hparams_of(const Config &c) {
     h.numbers.emplace_back("ema_decay", c.ema_decay);
   if (c.log_policy_churn)
     h.numbers.emplace_back("policy_churn_interval", (double)c.policy_churn_interval);
+  if (c.weight_decay > 0)
+    h.numbers.emplace_back("weight_decay", c.weight_decay);
+  if (c.l2_init_coef > 0)
+    h.numbers.emplace_back("l2_init_coef", c.l2_init_coef);
+  if (c.shrink_perturb_interval)
+    h.numbers.insert(h.numbers.end(), {{"shrink_perturb_interval", (double)c.shrink_perturb_interval},
+                                       {"shrink_perturb_shrink", c.shrink_perturb_shrink},
+                                       {"shrink_perturb_sigma", c.shrink_perturb_sigma}});
   h.flags = {{"record_observation", c.record_observation}, {"record_video", c.record_video},
              {"cuda_graph", c.cuda_graph}, {"deterministic", c.deterministic}};
   const std::pair<const char *, bool> when_set[] = {{"shuffle_minibatches", c.shuffle_minibatches},

@@ -142,6 +142,16 @@
 // averaged parameters and their update count go into the optional section 7, which a resume with the key imports and proves
 // by exporting it again, and without which the average starts at the resumed parameters; never a collective; the two other
 // keys without ema_decay, a decay outside [0, 1) and a library without the entry points are refused at start-up).
+// weight_decay: <wd> (absent or 0: off; ALEPPO_OPT_WEIGHT_DECAY, torch.optim.AdamW's decoupled decay inside every optimizer
+// step).  l2_init_coef: <la> (absent or 0: off; L2 Init, Kumar et al. 2023 - ALEPPO_OPT_ANCHOR_COEF with the INITIAL parameters
+// as the anchor: aleppo_anchor_take(live) once, right after the initial parameters are loaded and before the first update;
+// with checkpoint_path the anchor goes into the optional section 8, which a resume with the key REQUIRES, imports and proves
+// by exporting it again, and which a run without the key ignores).  shrink_perturb_interval: <n> (absent: off; Ash & Adams
+// 2020 - after the update of every n-th rollout, after a recycle, aleppo_shrink_perturb with shrink_perturb_shrink - default
+// 1 - and shrink_perturb_sigma - default 0 - and the key splitmix64(seed ^ rollout index), the way recycle_dormant derives
+// its key, so a resumed run replays the same perturbations; the moments are kept).  Under data parallelism every rank
+// computes the same values, anchor and keys; none of the calls is a collective.  Negative or non-finite values, the two
+// other shrink_perturb keys without the interval and a library without the entry points are refused at start-up.
 // Data parallelism (no reference counterpart): start one process per GPU with RANK / WORLD_SIZE / LOCAL_RANK
 // in the environment (torchrun / mpirun style).  Rank r owns the contiguous environment block
 // [r * E / W, (r + 1) * E / W) and GPU LOCAL_RANK; rank 0 creates the RCCL id, hands it to the others through the file
@@ -205,6 +215,11 @@
 #pragma weak aleppo_ema_read
 #pragma weak aleppo_ema_export
 #pragma weak aleppo_ema_import
+// ... and the anchor and shrink and perturb (l2_init_coef, shrink_perturb_interval)
+#pragma weak aleppo_anchor_take
+#pragma weak aleppo_anchor_import
+#pragma weak aleppo_anchor_export
+#pragma weak aleppo_shrink_perturb
 // ... and the device-resident evaluation environments (device_evaluation: true)
 #pragma weak aleppo_eval_env_open
 #pragma weak aleppo_eval_env_run
@@ -366,6 +381,11 @@ static void refuse_missing_entry_points(const Config &cfg) {
   if (cfg.ema_decay_set && !(aleppo_ema_open && aleppo_ema_update && aleppo_ema_read && aleppo_ema_export && aleppo_ema_import))
     throw std::runtime_error("ema_decay is set but this build's library has no averaged parameters "
                              "(aleppo_ema_open is missing)");
+  if (cfg.l2_init_coef > 0 && !(aleppo_anchor_take && aleppo_anchor_import && aleppo_anchor_export))
+    throw std::runtime_error("l2_init_coef is set but this build's library has no anchor (aleppo_anchor_take is missing)");
+  if (cfg.shrink_perturb_interval && !aleppo_shrink_perturb)
+    throw std::runtime_error("shrink_perturb_interval is set but this build's library cannot shrink and perturb "
+                             "(aleppo_shrink_perturb is missing)");
   if (cfg.log_policy_churn && !(aleppo_snapshot_take && aleppo_policy_diff))
     throw std::runtime_error("log_policy_churn is set but this build's library has no policy churn "
                              "(aleppo_snapshot_take / aleppo_policy_diff are missing)");
@@ -880,6 +900,12 @@ static void update(Run &run, size_t r, Update &u) {
                                       splitmix64(cfg.seed ^ (uint64_t)r), 0, nullptr, (size_t)(160 + cfg.hidden_size),
                                       u.recycle_counts));
   }
+  // shrink and perturb: after the statistics and a recycle, before this iteration's checkpoint and digest; the key as above
+  if (cfg.shrink_perturb_interval && (r + 1) % cfg.shrink_perturb_interval == 0) {
+    Profile::Span sp(&run.prof, "aleppo_shrink_perturb");
+    check(ctx, aleppo_shrink_perturb(ctx, cfg.shrink_perturb_shrink, cfg.shrink_perturb_sigma,
+                                     splitmix64(cfg.seed ^ (uint64_t)r), 0));
+  }
 }
 
 // ------------------------------------------------------------------ ... log (log_data, train.cc:163-210)
@@ -1150,6 +1176,11 @@ static void save_checkpoint(Run &run, size_t next_rollout) {
     check(ctx, aleppo_ema_export(ctx, avg.data(), n, &updates));
     ck.sections[CK_EMA] = ema_section(avg, (uint64_t)updates);
   }
+  if (run.cfg.l2_init_coef > 0) { // the optional section CK_ANCHOR: the anchor in reference order
+    std::vector<float> anchor(n);
+    check(ctx, aleppo_anchor_export(ctx, anchor.data(), n));
+    ck.sections[CK_ANCHOR] = anchor_section(anchor);
+  }
   write_checkpoint_file(run.ckpt_file, ck);
   char line[256];
   std::snprintf(line, sizeof line, "checkpoint rollout %zu digest params=%016llx optimizer=%016llx rollout=%016llx "
@@ -1223,6 +1254,46 @@ static void open_average(Run &run) {
   }
   if (run.cfg.eval_averaged) // (every evaluation, host-driven or device_evaluation, goes through the lanes' acting forward)
     check(ctx, aleppo_set_option(ctx, ALEPPO_OPT_EVAL_PARAMS, 1));
+}
+
+// weight_decay / l2_init_coef: the two coefficients, and the anchor before the first update.  A fresh run anchors at the
+// parameters it starts from (call this while they are still the initial ones); a resumed run REQUIRES the file's CK_ANCHOR
+// section - the initial parameters are gone - imports it and proves it by exporting it again (the state digest does not
+// cover the anchor).  A section in a file resumed without the key is ignored.
+static void apply_regularization(Run &run) {
+  aleppo_ctx *ctx = run.ctx;
+  const Config &cfg = run.cfg;
+  auto bits = [](double v) {
+    const float f = (float)v;
+    int32_t b;
+    std::memcpy(&b, &f, 4);
+    return b;
+  };
+  if (cfg.weight_decay > 0)
+    check(ctx, aleppo_set_option(ctx, ALEPPO_OPT_WEIGHT_DECAY, bits(cfg.weight_decay)));
+  if (!(cfg.l2_init_coef > 0))
+    return;
+  const size_t n = run.n_params();
+  if (run.resume_file.empty()) {
+    check(ctx, aleppo_anchor_take(ctx, ALEPPO_SET_LIVE));
+  } else {
+    const auto sec = run.resumed.sections.find(CK_ANCHOR);
+    if (sec == run.resumed.sections.end())
+      throw std::runtime_error("resume: checkpoint " + run.resume_file + " has no anchor (section " +
+                               std::to_string(CK_ANCHOR) + "): it was written by a run without l2_init_coef");
+    if (sec->second.size() != n * sizeof(float))
+      throw std::runtime_error("resume: checkpoint " + run.resume_file + " is corrupt (section " + std::to_string(CK_ANCHOR) +
+                               " has " + std::to_string(sec->second.size()) + " bytes, expected " +
+                               std::to_string(n * sizeof(float)) + ")");
+    std::vector<float> anchor(n), back(n);
+    std::memcpy(anchor.data(), sec->second.data(), n * sizeof(float));
+    check(ctx, aleppo_anchor_import(ctx, anchor.data(), n));
+    check(ctx, aleppo_anchor_export(ctx, back.data(), n));
+    if (anchor_section(back) != sec->second)
+      throw std::runtime_error("resume: checkpoint " + run.resume_file + ": the anchor after the import differs from the file's");
+    std::cout << "resumed the anchor, verified" << std::endl;
+  }
+  check(ctx, aleppo_set_option(ctx, ALEPPO_OPT_ANCHOR_COEF, bits(cfg.l2_init_coef)));
 }
 
 // ------------------------------------------------------------------ the rollout loop, the summary line, teardown
@@ -1307,6 +1378,7 @@ int main(int argc, char **argv) {
     load_initial_params(run);
     run.logger.emplace(run.rank == 0 ? run.log_path : run.log_path + ".rank" + std::to_string(run.rank)); // rank 0: THE log
     apply_options(run.ctx, run.cfg);
+    apply_regularization(run); // (the live parameters are still the initial ones: a fresh run's anchor)
     if (run.prof.on())
       check(run.ctx, aleppo_profile_enable(run.ctx, 1));
     const HParams hp = hparams_of(run.cfg);
