@@ -56,7 +56,10 @@ twice the plain count of roundings, on the term magnitudes, plus the input's own
     delta_v = m c_v (E_v + 8u |v - ret|)        v - ret, c_v, 1 / N_mask, m: four operations
 A masked row has m = 0: delta = 0, g = 0, and every stored gradient of that sample must be exactly 0.
 restate_f32() is a float32 numpy restatement of the same formulas from float32 logits; tests/test_backward_ref_cpu.py
-asserts that it stays within delta / FLOOR_FACTOR on every row's inputs."""
+asserts that it stays within delta / FLOOR_FACTOR on every row's inputs.
+head() and restate_f32() also take the kernel's options - value clipping, the KL penalty, per-minibatch advantage
+normalisation - and an absolute term for probabilities below the smallest fp32 normal; tests/head_ref.py derives what each
+adds to delta, and the per-sample planes and means with their bounds.  With every option off nothing above changes."""
 import hashlib
 
 import numpy as np
@@ -212,19 +215,32 @@ def _logits_bound(h, wh, bh):
     return lr.fp32_bound(ref)[0], ref
 
 
-def head(h, wh, bh, batch, hyper, n_mask):
+def head(h, wh, bh, batch, hyper, n_mask, *, vold=None, beta=None, advs=None, exact_logits=False):
     """h [B, H] as exported; wh [A + 1, H], bh [A + 1] fp32 (layer_ref.split_params "heads"); batch: dict(actions [B],
-    old_lp [B, A], adv [B], ret [B], masks [B]) of the minibatch's samples; hyper: dict(clip, c_v, c_e); n_mask: the
-    minibatch's unmasked count"""
+    old_lp [B, A], adv [B], ret [B], masks [B]) of the minibatch's samples; hyper: dict(clip, c_v, c_e[, vclip]); n_mask:
+    the minibatch's unmasked count.  The options of tests/head_ref.py, whose docstring derives what they add to delta
+    (every default leaves each number as it was, bit for bit): vold [B]: the value-clip select against these old values
+    at hyper["vclip"] (default: clip); beta: the exact KL and, where beta != 0, its gradient (None: the option off);
+    advs = (mean_f, inv_f): the advantage is fp32((a - mean_f) * inv_f); exact_logits: E = 0 (the identity head of the
+    stateless operator)"""
     h = np.asarray(h, np.float32)
     wh, bh = np.asarray(wh, np.float32), np.asarray(bh, np.float32)
     B, A = h.shape[0], wh.shape[0] - 1
     clip, c_v, c_e = (float(np.float32(hyper[k])) for k in ("clip", "c_v", "c_e"))
     E, fwd = _logits_bound(h, wh, bh)  # (R of the "blas" evaluation alone, as the forward check of the heads has it)
+    if exact_logits:
+        E = np.zeros_like(E)
     z, v = fwd.z[:, :A], fwd.z[:, A]
     act = np.asarray(batch["actions"], np.int64)
     olp = np.asarray(batch["old_lp"], np.float32).astype(np.float64)
     adv, ret = (np.asarray(batch[k], np.float32).astype(np.float64) for k in ("adv", "ret"))
+    e_adv = None
+    if advs is not None:  # head_ref: "Advantage normalisation"
+        mean_f, inv_f = np.float32(advs[0]), np.float32(advs[1])
+        a32 = np.asarray(batch["adv"], np.float32)
+        adv = ((a32 - mean_f) * inv_f).astype(np.float64)
+        e_adv = (float(inv_f) * float(np.spacing(np.abs(mean_f))) + np.abs(a32.astype(np.float64) - float(mean_f)) * float(
+            np.spacing(np.abs(inv_f)))) * (1 + 4 * U) + 4 * U * np.abs(adv)
     m = np.where(np.asarray(batch["masks"]) != 0, float(np.float32(1.0) / np.float32(n_mask)), 0.0)
     idx = np.arange(B)
     mx = z.max(axis=1)
@@ -239,28 +255,86 @@ def head(h, wh, bh, batch, hyper, n_mask):
     onehot = np.zeros((B, A))
     onehot[idx, act] = 1.0
     t2 = c_e * p * np.abs(lp + ent[:, None])
-    g = np.concatenate([m[:, None] * (gs[:, None] * (onehot - p) + c_e * p * (lp + ent[:, None])),
-                        (m * c_v * (v - ret))[:, None]], axis=1)
+    g_a = m[:, None] * (gs[:, None] * (onehot - p) + c_e * p * (lp + ent[:, None]))
+    dv = v - ret
+    o = Head()
+    if vold is None:
+        dvg = dv
+    else:  # head_ref: "Value clipping"
+        c = float(np.float32(hyper.get("vclip", hyper["clip"])))
+        vo = np.asarray(vold, np.float32).astype(np.float64)
+        d = v - vo
+        vc = np.where(np.abs(d) <= c, v, vo + np.copysign(c, d))
+        dc = vc - ret
+        lu, lc = dv * dv, dc * dc
+        dvg = np.where(lu >= lc, dv, 0.0)
+        o.vclip = dict(c=c, vo=vo, d=d, vc=vc, dc=dc, lu=lu, lc=lc, zero=lu < lc)
+    # the underflow term (head_ref: "Underflow"): 2^-126 on the rows where some p (or q) is below 2^-100, else 0
+    q = np.exp(olp) if beta is not None else None
+    small = p.min(axis=1) < 2.0 ** -100 if A else np.zeros(B, bool)
+    if q is not None and A:
+        small = small | (q.min(axis=1) < 2.0 ** -100)
+    T = np.where(small, 2.0 ** -126, 0.0)
+    b64 = 0.0 if beta is None else float(np.float32(beta))
+    if q is not None:
+        S = q.sum(axis=1)
+        kl = (q * (olp - lp)).sum(axis=1)
+        if b64 != 0.0:
+            g_a = g_a + m[:, None] * b64 * (p * S[:, None] - q)
+    g = np.concatenate([g_a, (m * c_v * dvg)[:, None]], axis=1)
     # delta (the module's docstring)
     E_l, E_v = E[:, :A].max(axis=1), E[:, A]
     e_lp = 2 * (A + 5) * U * (np.abs(z).max(axis=1) + np.abs(lse) + 1)
     dl = 2 * E_l + e_lp
+    if T.any():
+        dl = dl + A * T
     rp = np.expm1(dl) + 2 * U
     de = rp * ent + (1 + rp) * dl + 2 * (A + 1) * U * ent
+    if T.any():
+        de = de + T * np.abs(lp).sum(axis=1)
     rr = np.expm1(dl + 2 * U * np.abs(logr)) + 4 * U
     edge = np.where(adv >= 0, 1 + clip, 1 - clip)
-    dgs = np.abs(adv) * rho * (rr + (np.abs(rho - edge) <= rr * rho))
+    near = np.abs(rho - edge) <= rr * rho
+    dgs = np.abs(adv) * rho * (rr + near)
     # (where the select went the other way |gs| may be |adv| rho instead of 0: dgs covers the difference, and the terms
     # proportional to |gs| below use the larger of the two)
-    gs_hi = np.maximum(np.abs(gs), np.where(np.abs(rho - edge) <= rr * rho, np.abs(adv) * rho, 0.0))
+    gs_hi = np.maximum(np.abs(gs), np.where(near, np.abs(adv) * rho, 0.0))
+    if e_adv is not None:
+        flip = np.abs(adv) <= e_adv  # the device's advantage may have the other sign: it reads the other edge
+        near = near | flip
+        dgs = dgs + rho * e_adv * (1 + rr) + np.where(flip, rho * np.abs(adv), 0.0)
+        gs_hi = np.maximum(gs_hi, np.where(flip, rho * np.abs(adv), 0.0)) + rho * e_adv
     t1_hi = gs_hi[:, None] * np.abs(onehot - p)
     delta_a = m[:, None] * (dgs[:, None] * np.abs(onehot - p) + gs_hi[:, None] * p * rp[:, None]
                             + c_e * p * (rp[:, None] * np.abs(lp + ent[:, None]) + (1 + rp[:, None]) * (dl + de)[:, None])) \
         + 18 * U * m[:, None] * (t1_hi + t2)
-    delta_v = m * c_v * (E_v + 8 * U * np.abs(v - ret))
+    if T.any():
+        delta_a = delta_a + m[:, None] * T[:, None] * (gs_hi[:, None] + c_e * (np.abs(lp + ent[:, None]) + (dl + de)[:, None]))
+    if q is not None:
+        dS = 2 * (A + 1) * U * S + A * T
+        o.kl = dict(q=q, S=S, kl=kl, dS=dS, beta=b64)
+        if b64 != 0.0:
+            delta_a = delta_a + m[:, None] * b64 * (
+                p * (rp * S + (1 + rp) * dS)[:, None] + 2 * U * q + T[:, None] * (S + dS + 1)[:, None]
+                + 12 * U * (p * S[:, None] + q)) + 2 * U * m[:, None] * (t1_hi + t2)
+    delta_v = m * c_v * (E_v + 8 * U * np.abs(dv))
+    if vold is not None:
+        w = o.vclip
+        e_d = E_v + 2 * U * (np.abs(v) + np.abs(w["vo"]))
+        e_dv = E_v + 2 * U * np.abs(dv)
+        e_dc = 2 * U * (np.abs(w["vc"]) + np.abs(dc))  # (outside the range v_c does not depend on v)
+        err = (2 * np.abs(dv) * e_dv + e_dv ** 2 + 2 * U * lu) + (2 * np.abs(dc) * e_dc + e_dc ** 2 + 2 * U * lc)
+        outside = np.abs(d) > c
+        w["ambiguous"] = (np.abs(np.abs(d) - c) <= e_d) | (outside & (np.abs(lu - lc) <= err))
+        w["e_vc"] = E_v + 2 * U * (np.abs(v) + np.abs(w["vo"]) + c)
+        delta_v = delta_v + np.where(w["ambiguous"], m * c_v * (np.abs(dv) + E_v), 0.0)
     delta = np.concatenate([delta_a, delta_v[:, None]], axis=1)
-    o = Head()
     o.fwd, o.z, o.v, o.lp, o.p, o.ent, o.rho, o.g, o.delta, o.m = fwd, z, v, lp, p, ent, rho, g, delta, m
+    # (what tests/head_ref.py builds the per-sample planes and their bounds from)
+    o.A, o.act, o.olp, o.adv, o.ret, o.lse, o.logr = A, act, olp, adv, ret, lse, logr
+    o.active, o.near, o.e_adv, o.T = active, near, e_adv, T
+    o.E_l, o.E_v, o.e_lp, o.dl, o.rp, o.de, o.rr = E_l, E_v, e_lp, dl, rp, de, rr
+    o.hyper = dict(clip=clip, c_v=c_v, c_e=c_e)
     # dh = Wh^T g: g is not an fp32 value, so the float32 evaluations start from its float32 rounding (their own error)
     w64 = wh.astype(np.float64)
     g32 = g.astype(np.float32)
@@ -281,39 +355,85 @@ def head(h, wh, bh, batch, hyper, n_mask):
     return o
 
 
-def restate_f32(h, wh, bh, batch, hyper, n_mask):
-    """g [B, A + 1] as a float32 numpy restatement of head_train_body.inc forms it, from layer_ref's float32 logits ("blas")"""
+def restate_f32(h, wh, bh, batch, hyper, n_mask, *, vold=None, beta=None, advs=None, flush=False, planes=False, z32=None):
+    """g [B, A + 1] as a float32 numpy restatement of head_train_body.inc forms it, from layer_ref's float32 logits ("blas").
+    vold / beta / advs: head()'s options; flush: every exp result below the smallest fp32 normal becomes 0 (default:
+    numpy's gradual underflow); planes: return (g, {plane: float32 [B]}) - the eight per-sample planes in the engine's
+    names; z32 [B, A + 1]: these float32 logits and values instead"""
     f = np.float32
     h, wh, bh = np.asarray(h, f), np.asarray(wh, f), np.asarray(bh, f)
     B, A = h.shape[0], wh.shape[0] - 1
     clip, c_v, c_e = (f(hyper[k]) for k in ("clip", "c_v", "c_e"))
-    zz = lr.evaluate("heads", h, wh, bh).z32["blas"]  # (the float32 evaluation E's floor is measured on)
+    # (the float32 evaluation E's floor is measured on)
+    zz = lr.evaluate("heads", h, wh, bh).z32["blas"] if z32 is None else np.asarray(z32, f)
     z, v = zz[:, :A], zz[:, A]
     act = np.asarray(batch["actions"], np.int64)
     olp, adv, ret = (np.asarray(batch[k], f) for k in ("old_lp", "adv", "ret"))
+    if advs is not None:
+        adv = (adv - f(advs[0])) * f(advs[1])
+    if flush:
+        def exp(x):
+            with np.errstate(under="ignore"):
+                r = np.exp(x)
+            return np.where(r < f(2.0 ** -126), f(0), r).astype(f)
+    else:
+        def exp(x):
+            with np.errstate(under="ignore"):
+                return np.exp(x)
     m = np.where(np.asarray(batch["masks"]) != 0, f(1.0) / f(n_mask), f(0.0)).astype(f)
     idx = np.arange(B)
     mx = z.max(axis=1)
     se = np.zeros(B, f)
     for a in range(A):
-        se = se + np.exp(z[:, a] - mx)
+        se = se + exp(z[:, a] - mx)
     lse = mx + np.log(se)
     lp = z - lse[:, None]
-    p = np.exp(lp)
+    p = exp(lp)
     ent = np.zeros(B, f)
     for a in range(A):
         ent = ent + p[:, a] * lp[:, a]
     ent = -ent
-    rho = np.exp(lp[idx, act] - olp[idx, act])
+    logr = lp[idx, act] - olp[idx, act]
+    rho = exp(logr)
     active = np.where(adv >= 0, rho <= f(1) + clip, rho >= f(1) - clip)
     gs = np.where(active, -rho * adv, f(0)).astype(f)
     onehot = np.zeros((B, A), f)
     onehot[idx, act] = 1
     ga = m[:, None] * (gs[:, None] * (onehot - p) + c_e * p * (lp + ent[:, None]))
-    gv = m * c_v * (v - ret)
+    dv = v - ret
+    if vold is None:
+        lv, dvg = f(0.5) * (dv * dv), dv
+    else:
+        c = f(hyper.get("vclip", hyper["clip"]))
+        vo = np.asarray(vold, f)
+        d = v - vo
+        vc = np.where(np.abs(d) <= c, v, vo + np.copysign(c, d)).astype(f)
+        dc = vc - ret
+        lu, lc = dv * dv, dc * dc
+        lv, dvg = f(0.5) * np.maximum(lu, lc), np.where(lu >= lc, dv, f(0)).astype(f)
+    kl = np.zeros(B, f)
+    if beta is not None:
+        S = np.zeros(B, f)
+        for a in range(A):
+            q = exp(olp[:, a])
+            S = S + q
+            kl = kl + q * (olp[:, a] - lp[:, a])
+        if f(beta) != 0:
+            ga = ga + (m * f(beta))[:, None] * (p * S[:, None] - exp(olp))
+    gv = m * c_v * dvg
     out = np.concatenate([ga, gv[:, None]], axis=1)
     assert out.dtype == f
-    return out
+    if not planes:
+        return out
+    crho = np.minimum(np.maximum(rho, f(1) - clip), f(1) + clip)
+    obj = np.minimum(rho * adv, crho * adv)
+    total = -obj + c_v * lv - c_e * ent
+    if beta is not None and f(beta) != 0:
+        total = total + f(beta) * kl
+    pl = dict(total_losses=total, clipped_losses=obj, value_losses=lv, entropies=ent, ratio=rho,
+              approx_kl=(rho - f(1)) - logr, clip_fraction=(np.abs(rho - f(1)) > clip).astype(f), kl=kl)
+    assert all(x.dtype == f for x in pl.values())
+    return out, pl
 
 
 # ------------------------------------------------------------------ a whole export
@@ -343,11 +463,12 @@ def masked_rows(exp, masks):
     return bad
 
 
-def check_backward(params, H, A, bf16, obs, batch, hyper, n_mask, exp, grads, cache=None, only=None):
+def check_backward(params, H, A, bf16, obs, batch, hyper, n_mask, exp, grads, cache=None, only=None, head_opts=None):
     """every stored gradient of an export `exp` (aleppo_export_backward's dict, "dconv1" absent on the fused tail) and every
     tensor of `grads` (aleppo_export_grads of the same minibatch, clip factor 1) on the export's own inputs.  obs / batch:
     the minibatch's samples in its order.  only: the check names to run (default all).  cache: a dict kept for ONE set of
     parameters, one precision and one batch - a reference whose inputs have the same bytes is not evaluated again.
+    head_opts: head()'s keyword options (tests/head_ref.py; None: all off).
     Returns (failures, report, results): failures a list of strings that begin with the check's name, report {check:
     text}, results {check: dicts / Layers}.  Check names: "head", "d<activation>" for the data gradients, "<layer>.w/.b"."""
     p = lr.split_params(params, H, A, bf16)
@@ -397,7 +518,10 @@ def check_backward(params, H, A, bf16, obs, batch, hyper, n_mask, exp, grads, ca
 
     # the head: dh, dWh, dbh
     if want("head"):
-        hd = memo(("head", _key(exp["fc"])), lambda: head(exp["fc"], *p["heads"], batch, hyper, n_mask))
+        hopts = dict(head_opts or {})
+        okey = tuple((k, None if x is None else _key(np.asarray(x, np.float64))) for k, x in sorted(hopts.items()))
+        hd = memo(("head", _key(exp["fc"])) + ((okey, repr(sorted(hyper.items()))) if hopts else ()),
+                  lambda: head(exp["fc"], *p["heads"], batch, hyper, n_mask, **hopts))
         results["head"] = dict(head=hd)
         if bf16:
             check_a("dfc", hd.dh, exp["dfc"], False)
