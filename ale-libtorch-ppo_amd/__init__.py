@@ -106,6 +106,10 @@ PD_STATS = dict(rows=0, nonfinite_rows=1, churn=2, mean_kl_ab=3, max_kl_ab=4, me
                 mean_abs_dv=8, max_abs_dv=9, rms_dv=10, mean_entropy_a=11, mean_entropy_b=12, mean_feature_cos=13,
                 min_feature_cos=14, feature_rel_change=15)
 PD_COLUMNS = dict(kl_ab=0, kl_ba=1, tv=2, dv=3, cos=4, dh2=5, g_a=6, g_b=7)
+# aleppo_refresh_advantages: the indices of its ALEPPO_REFRESH_STATS_COUNT doubles - the ten of BATCH_STATS on the fresh
+# values, then aleppo_refresh_stat (Engine.refresh_advantages / Engine.refresh_values)
+REFRESH_STATS_COUNT = 13
+REFRESH_STATS = dict(BATCH_STATS, value_change_mean=10, value_change_std=11, value_change_maxabs=12)
 # aleppo_eval_rule / aleppo_eval_field: the evaluation lanes (Engine.eval_open / eval_push_frames / eval_act / eval_read)
 EVAL_GREEDY, EVAL_SAMPLE, EVAL_EPSILON_GREEDY = 0, 1, 2
 EVAL_RULES = dict(greedy=EVAL_GREEDY, sample=EVAL_SAMPLE, epsilon=EVAL_EPSILON_GREEDY)
@@ -197,6 +201,7 @@ EXPORTS = [
     "aleppo_saliency_tables", "aleppo_saliency", "aleppo_saliency_perturbed",
     "aleppo_feature_rank",
     "aleppo_snapshot_take", "aleppo_snapshot_export", "aleppo_snapshot_import", "aleppo_policy_diff",
+    "aleppo_refresh_advantages", "aleppo_refresh_read",
     "aleppo_anchor_take", "aleppo_anchor_import", "aleppo_anchor_export", "aleppo_shrink_perturb",
     "aleppo_env_open", "aleppo_env_rollout", "aleppo_env_export_state", "aleppo_env_import_state", "aleppo_env_read",
     "aleppo_eval_env_open", "aleppo_eval_env_run", "aleppo_eval_env_export_state", "aleppo_eval_env_import_state",
@@ -1016,6 +1021,26 @@ class Engine:
                                          C.c_size_t(0 if tr is None else tr.size), _ptr(out),
                                          C.c_size_t(0 if out is None else out.size)))
         return dict(stats={k: float(stats[i]) for k, i in PD_STATS.items()}, per_sample=ps, transitions=tr, outputs=out)
+
+    def refresh_advantages(self, source="live", stats=True):
+        """aleppo_refresh_advantages: between two train() calls on one rollout batch, forward the batch and the post-rollout
+        observation under parameter set `source` ("live", "averaged", "snapshot") on the device, keep the values in a
+        second plane (refresh_values) and overwrite advantages / returns with a new GAE scan on them (with the
+        normalisation of finish_rollout under advantage_norm: then a collective with a communicator).  {name: float} over
+        REFRESH_STATS with stats=True - the BATCH_STATS layout with the fresh values against the returns and advantages as
+        they stood at entry, then mean / std / max-abs of v_fresh - v_collected (this rank's samples) - else None."""
+        st = np.zeros(REFRESH_STATS_COUNT, np.float64) if stats else None
+        self._c(lib().aleppo_refresh_advantages(self._ctx, C.c_int(self._set(source)), _ptr(st),
+                                                C.c_size_t(0 if st is None else st.size)))
+        return None if st is None else {name: float(st[i]) for name, i in REFRESH_STATS.items()}
+
+    def refresh_values(self):
+        """aleppo_refresh_read: (values float32 [E,T], next_values float32 [E]) of the last refresh_advantages, as stored
+        (rounded to half with ROLLOUT_FP16)"""
+        v = np.zeros((self.E, self.T), np.float32)
+        nv = np.zeros(self.E, np.float32)
+        self._c(lib().aleppo_refresh_read(self._ctx, _ptr(v), C.c_size_t(v.size), _ptr(nv), C.c_size_t(nv.size)))
+        return v, nv
 
     def _saliency_source(self, observations, first, n):
         obs = None if observations is None else _u8(observations)

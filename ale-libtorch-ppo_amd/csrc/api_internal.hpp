@@ -1,5 +1,5 @@
 // api_internal.hpp - what the C ABI's translation units share (api_core.hip, api_rollout.hip, api_train.hip,
-// api_batch.hip, api_eval.hip, api_eval_env.hip, api_env.hip, api_rec.hip, api_state.hip, api_acts.hip, api_recycle.hip, api_ema.hip, api_saliency.hip, api_feature_rank.hip, api_policy_diff.hip, api_reg.hip, api_ops.hip): the entry-point guard macros, the memory
+// api_batch.hip, api_eval.hip, api_eval_env.hip, api_env.hip, api_rec.hip, api_state.hip, api_acts.hip, api_recycle.hip, api_ema.hip, api_saliency.hip, api_feature_rank.hip, api_policy_diff.hip, api_refresh.hip, api_reg.hip, api_ops.hip): the entry-point guard macros, the memory
 // ownership helpers (dalloc / halloc / grow over ctx_alloc / ctx_host_alloc / ctx_grow) and the other host-side helpers.
 // Host code only; the helpers are defined in api_core.hip unless noted.
 #pragma once

@@ -559,6 +559,8 @@ extern "C" int aleppo_finish_rollout(aleppo_ctx *c, const float *noise) {
   c->batch_n = c->N;
   c->caller_batch = false;
   c->val_src = Ctx::VAL_ROLLOUT; // (values_tm; any values supplied for a caller batch are forgotten)
+  c->fresh_valid = false;        // (aleppo_refresh_advantages' plane belongs to the batch this one replaces)
+  c->batch_refused = *c->h_err != 0;
   if (rs_on && !*c->h_err)
     c->rs_cur ^= 1; // the scan's output is the running return now (a refused rollout leaves the state as it was)
   if (*c->h_err)

@@ -306,6 +306,13 @@ struct Ctx {
   float *Ps = nullptr;             // fp32, internal layout, L.total() floats
   void *Psc = nullptr;             // compute copy of Ps in T; == Ps for fp32
   void *pd_scratch = nullptr;
+  // ---- aleppo_refresh_advantages: the second values plane, RT [T+1][E] time-major like values_tm (which it never
+  // replaces), and the statistics' scratch; each is allocated on first use and never again, nothing is enqueued for them on
+  // a context that never makes the call
+  void *fresh_tm = nullptr;
+  bool fresh_valid = false;        // fresh_tm belongs to the batch the context holds (aleppo_refresh_read)
+  bool batch_refused = false;      // the last aleppo_finish_rollout refused its flags (its planes are not refreshed)
+  double *rf_scratch = nullptr;    // [16] results | [RSTAT_SUMS] sums | [bstat_blocks(N)][RSTAT_SUMS] partials
   // ---- aleppo_saliency / aleppo_saliency_perturbed: nothing below is allocated, and nothing is enqueued for it, on a context
   // that never calls them; each buffer is allocated on first use and grown on demand like stage_obs
   uint32_t *sal_blur = nullptr;  // packed blurred stacks of the samples one forward chunk touches
@@ -441,6 +448,19 @@ void launch_bstat_partial(hipStream_t s, const void *val, const void *ret, const
                           int E, int T, double *part, bool rt16);
 void launch_bstat_reduce(hipStream_t s, const double *part, int nblk, double *sums, double *result);
 void launch_bstat_finalise(hipStream_t s, const double *sums, double *result);
+// aleppo_refresh_advantages' statistics, siblings of the two stages above with the same order: val is the fresh plane and
+// val0 the collected one (both time-major [T+1][E]); a partial is the nine sums, then S and Q of d' = val - val0 and the
+// maximum of |d'|.  Stage 2 adds (takes the maximum of) the partials in index order and writes
+// result[ALEPPO_REFRESH_STATS_COUNT]: the ten of ALEPPO_F_BATCH_STATS, then the mean, population std and maximum of d'.
+constexpr int RSTAT_SUMS = 12;
+void launch_rstat_partial(hipStream_t s, const void *val, const void *val0, const void *ret, const void *adv,
+                          const uint8_t *mask, long n, int E, int T, double *part, bool rt16);
+void launch_rstat_reduce(hipStream_t s, const double *part, int nblk, double *result);
+// aleppo_refresh_advantages (refresh.hip): the value head alone on the ns fc rows of one forward chunk, rounded to RT and
+// stored time-major - sample n = n0 + r = e*T + t at fresh_tm[t*E + e], or (boot: the post-rollout observations, r = e) at
+// row T.  wv / bv: the value row of the head weights and its bias
+void launch_value_refresh(hipStream_t s, const float *h, const float *wv, const float *bv, void *fresh_tm, long n0,
+                          long ns, int H, int E, int T, bool boot, bool rt16);
 // ALEPPO_OPT_MINIBATCH_SHUFFLE: order[e][i] = the keyed bijection of aleppo.h (round keys rk[e][4], domain 2^(2h)) and the
 // per-sample planes gathered into that order: act / oldlp / adv / ret / mask_p[e][i] = plane[order[e][i]]
 // (val_n != nullptr, ALEPPO_OPT_VALUE_CLIP: also val_p[e][i] = val_n[order[e][i]])

@@ -620,16 +620,21 @@ void launch_advn_finalise(hipStream_t s, const double *part, float *stats, int n
 // then the block folds with the shuffle tree of block_sum_256.  x * x of a widened float is exact in double (a
 // contracted fma is too); d is one rounded double subtraction of two widened floats.  The values of a rollout batch are
 // time-major ([T+1][E], sample n = e*T + t sits at t*E + e: E > 0); those of a caller batch are sample-major (E == 0).
-template <class RT>
-__global__ __launch_bounds__(256) void bstat_partial_kernel(const RT *__restrict__ val, const RT *__restrict__ ret,
-                                                            const RT *__restrict__ adv, const uint8_t *__restrict__ mask,
-                                                            long n, int E, int T, double *__restrict__ part) {
+// REFRESH (aleppo_refresh_advantages): val0 is the collected plane next to the fresh one in val, and a partial grows by S
+// and Q of d' = v - v0 and the maximum of |d'| (RSTAT_SUMS); everything it adds is behind `if constexpr`.
+template <class RT, bool REFRESH>
+__device__ __forceinline__ void bstat_partial(const RT *__restrict__ val, const RT *__restrict__ val0,
+                                              const RT *__restrict__ ret, const RT *__restrict__ adv,
+                                              const uint8_t *__restrict__ mask, long n, int E, int T,
+                                              double *__restrict__ part) {
   __shared__ double s4[4];
+  constexpr int SUMS = REFRESH ? RSTAT_SUMS - 1 : BSTAT_SUMS, REC = REFRESH ? RSTAT_SUMS : BSTAT_SUMS;
   const long i0 = (long)blockIdx.x * BSTAT_CHUNK;
   const long i1 = i0 + BSTAT_CHUNK < n ? i0 + BSTAT_CHUNK : n;
-  double acc[BSTAT_SUMS];
+  double acc[SUMS];
+  [[maybe_unused]] double mx = 0.0;
 #pragma unroll
-  for (int k = 0; k < BSTAT_SUMS; ++k)
+  for (int k = 0; k < SUMS; ++k)
     acc[k] = 0.0;
   for (long i = i0 + threadIdx.x; i < i1; i += 256)
     if (mask[i]) {
@@ -646,15 +651,46 @@ __global__ __launch_bounds__(256) void bstat_partial_kernel(const RT *__restrict
       acc[6] += a * a;
       acc[7] += d;
       acc[8] += d * d;
+      if constexpr (REFRESH) {
+        const double dp = v - (double)(float)val0[iv];
+        acc[9] += dp;
+        acc[10] += dp * dp;
+        mx = fmax(mx, fabs(dp));
+      }
     }
 #pragma unroll
-  for (int k = 0; k < BSTAT_SUMS; ++k)
+  for (int k = 0; k < SUMS; ++k)
     acc[k] = block_sum_256(acc[k], s4);
+  if constexpr (REFRESH) { // the maximum is order-free: the butterfly, then the four waves through LDS
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1)
+      mx = fmax(mx, __shfl_xor(mx, o, 64));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0)
+      s4[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    mx = fmax(fmax(s4[0], s4[1]), fmax(s4[2], s4[3]));
+  }
   if (threadIdx.x == 0) {
 #pragma unroll
-    for (int k = 0; k < BSTAT_SUMS; ++k)
-      part[(size_t)blockIdx.x * BSTAT_SUMS + k] = acc[k];
+    for (int k = 0; k < SUMS; ++k)
+      part[(size_t)blockIdx.x * REC + k] = acc[k];
+    if constexpr (REFRESH)
+      part[(size_t)blockIdx.x * REC + SUMS] = mx;
   }
+}
+template <class RT>
+__global__ __launch_bounds__(256) void bstat_partial_kernel(const RT *__restrict__ val, const RT *__restrict__ ret,
+                                                            const RT *__restrict__ adv, const uint8_t *__restrict__ mask,
+                                                            long n, int E, int T, double *__restrict__ part) {
+  bstat_partial<RT, false>(val, nullptr, ret, adv, mask, n, E, T, part);
+}
+template <class RT>
+__global__ __launch_bounds__(256) void rstat_partial_kernel(const RT *__restrict__ val, const RT *__restrict__ val0,
+                                                            const RT *__restrict__ ret, const RT *__restrict__ adv,
+                                                            const uint8_t *__restrict__ mask, long n, int E, int T,
+                                                            double *__restrict__ part) {
+  bstat_partial<RT, true>(val, val0, ret, adv, mask, n, E, T, part);
 }
 // The ten results of aleppo.h from the nine (all-reduced) sums: population variance max(0, Q / n - mean^2), without
 // contraction so that every instance of this function rounds alike; n == 0: zeros and a NaN explained variance.
@@ -690,6 +726,31 @@ __global__ __launch_bounds__(64) void bstat_reduce_kernel(const double *__restri
   if (threadIdx.x == 0 && result)
     bstat_finalise(sums, result);
 }
+// aleppo_refresh_advantages' stage 2: thread k < 11 adds sum k of the nblk partials in index order, thread 11 takes the
+// maximum; then the ten results of bstat_finalise and the mean, population std and maximum of d'
+__global__ __launch_bounds__(64) void rstat_reduce_kernel(const double *__restrict__ part, int nblk, double *result) {
+#pragma clang fp contract(off)
+  __shared__ double sums[RSTAT_SUMS];
+  if (threadIdx.x < RSTAT_SUMS) {
+    const bool is_max = threadIdx.x == RSTAT_SUMS - 1;
+    double acc = 0.0;
+    for (int b = 0; b < nblk; ++b) {
+      const double x = part[(size_t)b * RSTAT_SUMS + threadIdx.x];
+      acc = is_max ? fmax(acc, x) : acc + x;
+    }
+    sums[threadIdx.x] = acc;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    bstat_finalise(sums, result);
+    const double n = sums[0];
+    const double mean = n > 0.0 ? sums[9] / n : 0.0;
+    const double var = n > 0.0 ? fmax(0.0, sums[10] / n - mean * mean) : 0.0;
+    result[ALEPPO_REFRESH_VALUE_CHANGE_MEAN] = mean;
+    result[ALEPPO_REFRESH_VALUE_CHANGE_STD] = sqrt(var);
+    result[ALEPPO_REFRESH_VALUE_CHANGE_MAXABS] = sums[RSTAT_SUMS - 1];
+  }
+}
 __global__ __launch_bounds__(64) void bstat_finalise_kernel(const double *sums, double *result) {
   if (threadIdx.x == 0 && blockIdx.x == 0)
     bstat_finalise(sums, result);
@@ -704,6 +765,21 @@ void launch_bstat_partial(hipStream_t s, const void *val, const void *ret, const
   else
     hipLaunchKernelGGL(bstat_partial_kernel<float>, grid, dim3(256), 0, s, static_cast<const float *>(val),
                        static_cast<const float *>(ret), static_cast<const float *>(adv), mask, n, E, T, part);
+}
+void launch_rstat_partial(hipStream_t s, const void *val, const void *val0, const void *ret, const void *adv,
+                          const uint8_t *mask, long n, int E, int T, double *part, bool rt16) {
+  const dim3 grid((unsigned)bstat_blocks(n));
+  if (rt16)
+    hipLaunchKernelGGL(rstat_partial_kernel<f16>, grid, dim3(256), 0, s, static_cast<const f16 *>(val),
+                       static_cast<const f16 *>(val0), static_cast<const f16 *>(ret), static_cast<const f16 *>(adv), mask,
+                       n, E, T, part);
+  else
+    hipLaunchKernelGGL(rstat_partial_kernel<float>, grid, dim3(256), 0, s, static_cast<const float *>(val),
+                       static_cast<const float *>(val0), static_cast<const float *>(ret), static_cast<const float *>(adv),
+                       mask, n, E, T, part);
+}
+void launch_rstat_reduce(hipStream_t s, const double *part, int nblk, double *result) {
+  hipLaunchKernelGGL(rstat_reduce_kernel, dim3(1), dim3(64), 0, s, part, nblk, result);
 }
 void launch_bstat_reduce(hipStream_t s, const double *part, int nblk, double *sums, double *result) {
   hipLaunchKernelGGL(bstat_reduce_kernel, dim3(1), dim3(64), 0, s, part, nblk, sums, result);

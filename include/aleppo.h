@@ -927,6 +927,61 @@ int aleppo_policy_diff(aleppo_ctx *ctx, const uint8_t *observations, int64_t n, 
                        size_t stat_count, double *per_sample, size_t per_sample_count, int64_t *transitions,
                        size_t transition_count, float *outputs, size_t output_count);
 
+/* Per-epoch advantage recomputation (Andrychowicz et al. 2021, "What Matters in On-Policy RL", choice C.5: recompute the
+ * advantages before every pass over the data; what a CleanRL / SB3 user writes as "re-run compute_gae inside the epoch
+ * loop"; the reference has none of it).  After the first epoch of an update the critic has moved, so the advantages and
+ * returns aleppo_finish_rollout left are stale.  aleppo_refresh_advantages is a call BETWEEN two aleppo_train calls on one
+ * rollout batch: it forwards the batch on the device, scans again and overwrites the two planes; aleppo_train, its
+ * schedules and a captured update (ALEPPO_OPT_UPDATE_GRAPH) are what they were and simply read the new planes.
+ * Valid when the context holds a ROLLOUT batch: aleppo_finish_rollout has succeeded, and neither an aleppo_set_batch nor
+ *   the first aleppo_act / aleppo_step / aleppo_env_rollout of the next rollout has come since (that act carries the
+ *   post-rollout observation into slot 0 and the time axis is gone).  A caller batch has no time axis and is refused.
+ * Fresh values: for every sample (e, t) of the batch, and for the post-rollout observation of every environment (the bytes
+ *   of ALEPPO_F_CURRENT_OBS), the value head's output under `set` (ALEPPO_SET_LIVE / _AVERAGED / _SNAPSHOT) - the forward
+ *   pass of aleppo_forward over the observation slots in place, in chunks of at most maxB = max(E, max_minibatch) samples
+ *   in logical order, then the E post-rollout observations as one chunk.  The fp32 value is bit for bit what
+ *   aleppo_forward returns for those observations in the same chunks (one wave per row sums the H products lane-strided,
+ *   then the fixed butterfly, then + bias, as the forward-only head does).  Each is rounded to the rollout plane type (IEEE
+ *   half under ALEPPO_ROLLOUT_FP16) and stored in a SECOND plane [T+1][E], allocated on first use and kept until
+ *   aleppo_destroy.  The collected plane is not written: ALEPPO_F_VALUES, ALEPPO_F_NEXT_VALUES, the v of
+ *   ALEPPO_F_BATCH_STATS and the v_old of ALEPPO_OPT_VALUE_CLIP keep meaning "as collected".
+ * Advantages and returns: the GAE scan of aleppo_finish_rollout (the same kernel) on the stored rewards AS THEY STAND -
+ *   already clamped, or scaled and clipped by ALEPPO_OPT_REWARD_SCALE, in place; they are not transformed again and the
+ *   reward-scale state is neither read nor written - the stored flags, config.gamma / lambda and the fresh plane.  It
+ *   overwrites ALEPPO_F_ADVANTAGES and ALEPPO_F_RETURNS (= a + v_fresh) and rewrites the same ALEPPO_F_MASKS.  With
+ *   config.advantage_norm = 1 the normalisation of aleppo_finish_rollout follows, with its all-reduce under a communicator
+ *   (world_size > 1, or ALEPPO_OPT_FORCE_COMM): the call is then a COLLECTIVE like aleppo_finish_rollout, and never one
+ *   otherwise.  Old log-probs, actions, logits, rewards, observations, the frame stacks, the sampling counter, parameters
+ *   and moments are untouched; aleppo_state_digest is the same before and after.
+ * stats: NULL (stat_count 0) or double [ALEPPO_REFRESH_STATS_COUNT], THIS RANK's samples, never all-reduced, computed
+ *   before the scan overwrites anything, in double over the unmasked samples with ALEPPO_F_BATCH_STATS's arithmetic and
+ *   order (chunks of 4096 logical samples, 256 strided accumulators, a fixed tree, chunks in index order):
+ *     [0..9]  the aleppo_batch_stat layout with v := the fresh values as stored, and R and a := the returns and
+ *             advantages AS THEY STOOD AT ENTRY: how well the updated critic explains the targets the last epoch trained on
+ *     [10]    mean of d' = v_fresh - v_collected      [11] population std of d'      [12] max |d'| (exact)
+ * aleppo_refresh_read: the fresh plane in reference layout, float [E,T] and float [E] (either pointer may be NULL with a
+ *   count of 0, not both).  A function and not two more aleppo_field values: a field is readable straight after
+ *   aleppo_finish_rollout, this plane only once the batch the context holds has been refreshed.
+ * Computed WHEN CALLED, on the context's stream: the stream's synchronise, the forward chunks (their own profiling
+ *   classes) each followed by the value launch, the statistics' two launches (ALEPPO_K_ACT_STATS, the class
+ *   of the read-only passes over the activations: one bracket per chunk), the scan (ALEPPO_K_GAE),
+ *   the normalisation, one synchronise.  It runs the network in the shared activation scratch: what aleppo_step
+ *   pre-computed for the next aleppo_act is dropped (the act recomputes it: same bits) and aleppo_export_backward refuses
+ *   afterwards.  A context that never makes the calls allocates and enqueues exactly what it did before.
+ * Errors: a set that is none of the three, a stat_count that is neither 0 with NULL nor ALEPPO_REFRESH_STATS_COUNT, wrong
+ *   counts or two NULLs in aleppo_refresh_read: ALEPPO_ERR_INVALID_ARGUMENT.  No rollout batch (none yet, a caller batch,
+ *   a rollout whose flags aleppo_finish_rollout refused, the next rollout begun), a set that does not exist yet, a step
+ *   armed, world_size > 1 without aleppo_comm_init, aleppo_refresh_read before the batch the context holds was refreshed:
+ *   ALEPPO_ERR_RUNTIME.  A failed call changes nothing. */
+#define ALEPPO_REFRESH_STATS_COUNT 13
+typedef enum {
+  ALEPPO_REFRESH_VALUE_CHANGE_MEAN = 10,  /* [0..9]: aleppo_batch_stat */
+  ALEPPO_REFRESH_VALUE_CHANGE_STD = 11,
+  ALEPPO_REFRESH_VALUE_CHANGE_MAXABS = 12
+} aleppo_refresh_stat;
+int aleppo_refresh_advantages(aleppo_ctx *ctx, int set, double *stats, size_t stat_count); /* stats may be NULL (count 0) */
+int aleppo_refresh_read(aleppo_ctx *ctx, float *values, size_t value_count, float *next_values, size_t next_count);
+
 /* ------------------------------------------------------------------ evaluation lanes (the reference has no evaluation
  * loop: SB3's predict(deterministic=True) / EvalCallback, the epsilon-greedy scores of the DQN / PPO papers)
  * L frame stacks of their own, next to the rollout, on which the network acts under one of three rules - so that a
@@ -1280,7 +1335,8 @@ typedef enum {
   ALEPPO_K_CONV_BWD = 19,   /* conv2 dgrad + conv2 wgrad + conv1 wgrad of the update's backward pass in one launch (bf16) */
   ALEPPO_K_REC_CAPTURE = 20, /* the episode recorders' capture kernel (aleppo_rec_open), one launch per recorded step */
   ALEPPO_K_ACT_STATS = 21,  /* the read-only passes over the activations, one bracket per forward chunk: aleppo_activation_stats' launch,
-                               aleppo_feature_rank's three (flags, Gram, reduce) */
+                               aleppo_feature_rank's three (flags, Gram, reduce), aleppo_refresh_advantages' value launch (the last
+                               bracket of a call also holds its two statistics launches) */
   ALEPPO_K_RECYCLE = 22,    /* the masked pass of aleppo_recycle_units / aleppo_recycle_dormant over P / M1 / M2, one launch per call */
   ALEPPO_K_SAL_BLUR = 23,    /* aleppo_saliency's blur of the samples a forward chunk touches */
   ALEPPO_K_SAL_PERTURB = 24, /* ... its blend of one chunk's perturbed stacks into the staging buffer */

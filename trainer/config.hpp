@@ -53,6 +53,8 @@ struct Config {
   std::string checkpoint_path, resume;
   long checkpoint_interval = 0; // 0: only after the last rollout
   bool log_batch_stats = false; // extension: explained variance and value / return / advantage statistics (ALEPPO_F_BATCH_STATS)
+  // extension: aleppo_refresh_advantages before every epoch of an update but the first (one aleppo_train call per epoch)
+  bool recompute_advantages = false;
   bool log_tensor_stats = false; // extension: per-tensor gradient / parameter norms and update ratios (aleppo_tensor_stats)
   // extension: dormant / dead units and firing rates of the four hidden layers on the batch (aleppo_activation_stats)
   bool log_activation_stats = false;
@@ -183,6 +185,7 @@ static Config load_config(const std::string &path) { // keys / defaults of src/b
   read_key(kv, "kl_coef", c.kl_coef);
   read_key(kv, "kl_target", c.kl_target);
   read_key(kv, "log_batch_stats", c.log_batch_stats);
+  read_key(kv, "recompute_advantages", c.recompute_advantages);
   read_key(kv, "log_tensor_stats", c.log_tensor_stats);
   read_key(kv, "log_activation_stats", c.log_activation_stats);
   { // what aleppo_activation_stats would refuse is refused here ("nan" / "inf" do not parse as a number: bad value)
@@ -505,6 +508,7 @@ static HParams hparams_of(const Config &c) {
                                                     {"clip_value_loss", c.clip_value_loss},
                                                     {"minibatch_advantage_norm", c.minibatch_advantage_norm},
                                                     {"log_batch_stats", c.log_batch_stats},
+                                                    {"recompute_advantages", c.recompute_advantages},
                                                     {"log_tensor_stats", c.log_tensor_stats},
                                                     {"log_activation_stats", c.log_activation_stats},
                                                     {"log_feature_rank", c.log_feature_rank},

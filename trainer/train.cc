@@ -152,6 +152,11 @@
 // its key, so a resumed run replays the same perturbations; the moments are kept).  Under data parallelism every rank
 // computes the same values, anchor and keys; none of the calls is a collective.  Negative or non-finite values, the two
 // other shrink_perturb keys without the interval and a library without the entry points are refused at start-up.
+// recompute_advantages: false (true: Andrychowicz et al. 2021, choice C.5 - the update runs one epoch per aleppo_train call,
+// as with target_kl, and every rank calls aleppo_refresh_advantages on the live parameters before every epoch but the first,
+// so each later epoch trains on advantages and returns recomputed from the current critic; an early target_kl stop leaves no
+// trailing refresh; rank 0 logs its last refresh of the update as refresh/explained_variance, refresh/value_change_std and
+// refresh/value_change_maxabs; a library without the entry point refuses the key at start-up).
 // Data parallelism (no reference counterpart): start one process per GPU with RANK / WORLD_SIZE / LOCAL_RANK
 // in the environment (torchrun / mpirun style).  Rank r owns the contiguous environment block
 // [r * E / W, (r + 1) * E / W) and GPU LOCAL_RANK; rank 0 creates the RCCL id, hands it to the others through the file
@@ -206,6 +211,7 @@
 // ... and the feature rank (log_feature_rank: true)
 #pragma weak aleppo_feature_rank
 // ... and the policy churn (log_policy_churn: true)
+#pragma weak aleppo_refresh_advantages
 #pragma weak aleppo_snapshot_take
 #pragma weak aleppo_policy_diff
 // (record_saliency: true - aleppo_saliency is declared weak in saliency.hpp)
@@ -378,6 +384,8 @@ static void refuse_missing_entry_points(const Config &cfg) {
   if (cfg.recycle_dormant && !aleppo_recycle_dormant)
     throw std::runtime_error("recycle_dormant is set but this build's library cannot recycle units "
                              "(aleppo_recycle_dormant is missing)");
+  if (cfg.recompute_advantages && !aleppo_refresh_advantages)
+    throw std::runtime_error("recompute_advantages is set but this build's library has no aleppo_refresh_advantages");
   if (cfg.ema_decay_set && !(aleppo_ema_open && aleppo_ema_update && aleppo_ema_read && aleppo_ema_export && aleppo_ema_import))
     throw std::runtime_error("ema_decay is set but this build's library has no averaged parameters "
                              "(aleppo_ema_open is missing)");
@@ -784,6 +792,8 @@ struct Update {
   double churn[ALEPPO_PD_COUNT] = {}, ema_churn[ALEPPO_PD_COUNT] = {};
   bool recycled = false; // recycle_dormant: this rollout is one of the interval's, recycle_counts is what it recycled
   int64_t recycle_counts[ALEPPO_RECYCLE_COUNTS] = {};
+  bool refreshed = false; // recompute_advantages: a refresh ran in this update, refresh holds the last one's statistics
+  double refresh[ALEPPO_REFRESH_STATS_COUNT] = {};
   double ema_decay_now = 0;                       // ema_decay: the decay this rollout's aleppo_ema_update ran with ...
   double ema_stats[ALEPPO_EMA_STATS_COUNT] = {};  // ... and the statistics it left
   explicit Update(const Run &run)
@@ -800,7 +810,10 @@ static void update(Run &run, size_t r, Update &u) {
   // one call of num_epochs epochs, or - with target_kl - one call per epoch until an epoch's last minibatch is over
   // the target (the Adam schedule and the shuffle keys follow the Adam step, so the calls add up to the same update)
   u.epochs_run = 0;
-  const size_t per_call = cfg.target_kl > 0 ? 1 : (size_t)cfg.num_epochs;
+  // recompute_advantages: one call per epoch too, with aleppo_refresh_advantages on the live parameters in front of every
+  // epoch but the first - on every rank (a collective under advantage_norm); an early stop leaves no trailing refresh
+  const size_t per_call = (cfg.target_kl > 0 || cfg.recompute_advantages) ? 1 : (size_t)cfg.num_epochs;
+  u.refreshed = false;
   for (size_t k = 0; k < run.schedules.size(); ++k) { // (a function of r alone: the same on every rank)
     u.hyper_now[k] = run.schedules[k].at(r, cfg.num_rollouts);
     set_float_option(ctx, run.schedules[k].option, u.hyper_now[k]);
@@ -816,6 +829,11 @@ static void update(Run &run, size_t r, Update &u) {
   }
   while (u.epochs_run < (size_t)cfg.num_epochs) {
     const size_t e0 = u.epochs_run;
+    if (cfg.recompute_advantages && e0 > 0) {
+      Profile::Span sp(&run.prof, "aleppo_refresh_advantages");
+      check(ctx, aleppo_refresh_advantages(ctx, ALEPPO_SET_LIVE, u.refresh, ALEPPO_REFRESH_STATS_COUNT));
+      u.refreshed = true;
+    }
     {
       Profile::Span sp(&run.prof, "aleppo_train");
       check(ctx, aleppo_train(ctx, u.lr, (int)per_call, (int)nmb, u.m.data() + e0 * nmb));
@@ -965,6 +983,11 @@ static void log_scalars(Run &run, const EpisodeLog &log, const BatchStatistics &
     logger.add_scalar("std_return", step, (float)s.batch[ALEPPO_BS_RETURN_STD]);
     logger.add_scalar("mean_advantage", step, (float)s.batch[ALEPPO_BS_ADVANTAGE_MEAN]);
     logger.add_scalar("std_advantage", step, (float)s.batch[ALEPPO_BS_ADVANTAGE_STD]);
+  }
+  if (u.refreshed && run.rank == 0) { // recompute_advantages: the last refresh of this update (rank 0's samples)
+    logger.add_scalar("refresh/explained_variance", step, (float)u.refresh[ALEPPO_BS_EXPLAINED_VARIANCE]);
+    logger.add_scalar("refresh/value_change_std", step, (float)u.refresh[ALEPPO_REFRESH_VALUE_CHANGE_STD]);
+    logger.add_scalar("refresh/value_change_maxabs", step, (float)u.refresh[ALEPPO_REFRESH_VALUE_CHANGE_MAXABS]);
   }
   if (cfg.log_tensor_stats && run.rank == 0) { // (of the last minibatch's gradient and the last optimizer step)
     for (int k = 0; k < ALEPPO_TENSOR_STATS_ROWS; ++k) {
