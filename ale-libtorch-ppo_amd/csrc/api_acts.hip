@@ -1,22 +1,10 @@
 // api_acts.hip - C ABI (include/aleppo.h), the representation: aleppo_forward_activations, aleppo_activation_stats,
-// aleppo_export_backward.  The first two run the network the way aleppo_forward does (same staging, same net_forward, same
-// pre_acted invalidation) and then only read a1 / a2 / a3 / h; the third runs nothing and reads what the last update left
-// there and in dh / dz3 / dz2 / dz1.  Nothing here touches what the rollout or a captured update can observe.
+// aleppo_export_backward.  The first two run the network over a SampleSource (api_internal.hpp), as aleppo_forward does,
+// and then only read a1 / a2 / a3 / h; the third runs nothing and reads what the last update left there and in dh / dz3 /
+// dz2 / dz1.  Nothing here touches what the rollout or a captured update can observe.
 #include "api_internal.hpp"
 
 using namespace aleppo;
-
-// the caller's observations -> packed stacks in a staging area of their own, c->stage_obs: the rollout's observation
-// slots are not touched
-int aleppo::stage_forward_input(aleppo_ctx *c, const uint8_t *observations, int64_t n, SampleMap *map) {
-  if (int rc = stage_observations(c, observations, n))
-    return rc;
-  const size_t need = (size_t)n * FRAME_PIX * 4;
-  HIPCHK(c, grow(c, &c->stage_obs, &c->stage_obs_cap, need, ALLOC_RAW));
-  *map = SampleMap{1, (long)FRAME_PIX, 0, 0, 0}; // sample n at stage_obs + n * 7056
-  launch_obs_pack(c->stream, c->stage_u8, c->stage_obs, n, *map);
-  return ALEPPO_OK;
-}
 
 extern "C" int aleppo_forward_activations(aleppo_ctx *c, const uint8_t *observations, int64_t n, float *conv1,
                                           float *conv2, float *conv3, float *fc) {
@@ -33,13 +21,11 @@ extern "C" int aleppo_forward_activations(aleppo_ctx *c, const uint8_t *observat
   size_t need = 0;
   for (int l = 0; l < 3; ++l)
     need += out[l] ? (size_t)n * per[l] * 4 : 0;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->pre_acted = -1; // a1 / a2 / a3 / h are shared scratch
   HIPCHK(c, grow(c, &c->ax_buf, &c->ax_cap, need, ALLOC_RAW));
-  SampleMap map{};
-  if (int rc = stage_forward_input(c, observations, n, &map))
+  SampleSource src;
+  if (int rc = source_open(c, observations, 0, n, &src))
     return rc;
-  net_forward(c, c->stage_obs, map, n);
+  net_forward(c, src.obs, src.map, n); // (one chunk: n <= maxB)
   float *at = c->ax_buf; // (every layer's size is a multiple of 16 bytes: the areas stay aligned)
   for (int l = 0; l < 3; ++l) {
     if (!out[l])
@@ -111,51 +97,32 @@ extern "C" int aleppo_export_backward(aleppo_ctx *c, int64_t capacity, float *co
 }
 
 namespace aleppo {
-// what aleppo_activation_stats refuses in tau and in its source of samples (aleppo_recycle_dormant measures the same way)
+// what aleppo_activation_stats refuses in tau (aleppo_recycle_dormant measures the same way)
 int act_stats_check_tau(aleppo_ctx *c, double tau) {
   if (!(tau >= 0.0) || !std::isfinite(tau))
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "activation_stats: tau must be finite and non-negative");
   return ALEPPO_OK;
 }
-int act_stats_check_source(aleppo_ctx *c, const uint8_t *observations, int64_t n) {
-  const bool batch = observations == nullptr;
-  if (batch && n != 0)
-    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "activation_stats: null observations need n == 0 (the context's batch)");
-  if (!batch && (n <= 0 || n > c->maxB))
-    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "activation_stats: n exceeds capacity");
-  if (batch && c->batch_n <= 0)
-    return set_err(c, ALEPPO_ERR_RUNTIME, "no batch: call aleppo_finish_rollout or aleppo_set_batch first");
-  return ALEPPO_OK;
-}
-// the measurement itself, arguments already checked: the stream's synchronise, the forward chunks with one pass each and the
-// finalising launch, all enqueued; *units_dev / *layers_dev: the two tables in the context's scratch (device memory)
+// the measurement itself, arguments already checked (source_check): the source's open, the forward chunks with one pass each
+// and the finalising launch, all enqueued; *units_dev / *layers_dev: the two tables in the context's scratch (device memory)
 int act_stats_measure(aleppo_ctx *c, const uint8_t *observations, int64_t n, double tau, const double **units_dev,
                       const double **layers_dev) {
-  const bool batch = observations == nullptr;
-  const long total = batch ? c->batch_n : (long)n;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->pre_acted = -1; // a1 / a2 / a3 / h are shared scratch
   // the scratch holds the largest sample count either source can bring (the record count grows with it)
   if (!c->as_scratch)
     HIPCHK(c, dalloc(c, &c->as_scratch, act_stats_plan(c->prec, c->H, std::max(c->N, c->maxB), c->maxB).bytes));
-  const ActStatsPlan pl = act_stats_plan(c->prec, c->H, total, c->maxB);
-  const uint32_t *obs = c->obs;
-  SampleMap map = train_map(c, 0);
-  if (!batch) {
-    if (int rc = stage_forward_input(c, observations, n, &map))
-      return rc;
-    obs = c->stage_obs;
-  }
+  SampleSource src;
+  if (int rc = source_open(c, observations, 0, n, &src))
+    return rc;
+  const ActStatsPlan pl = act_stats_plan(c->prec, c->H, src.total, c->maxB);
   size_t done[4] = {0, 0, 0, 0};
-  for (long n0 = 0; n0 < total; n0 += c->maxB) {
-    const long ns = std::min(c->maxB, total - n0);
-    map.n0 = (int)n0;
-    net_forward(c, obs, map, ns);
+  source_walk(c, src, [&](const SampleMap &map, long, long ns) {
+    net_forward(c, src.obs, map, ns);
     prof_begin(c, ALEPPO_K_ACT_STATS);
     launch_act_stats_partial(c->stream, c->prec, c->a1, c->a2, c->a3, c->h, c->H, ns, pl, done, c->as_scratch);
     prof_end(c, ALEPPO_K_ACT_STATS);
-  }
-  launch_act_stats_final(c->stream, c->H, total, tau, pl, done, c->as_scratch, units_dev, layers_dev);
+    return ALEPPO_OK;
+  });
+  launch_act_stats_final(c->stream, c->H, src.total, tau, pl, done, c->as_scratch, units_dev, layers_dev);
   HIPCHK(c, hipGetLastError());
   return ALEPPO_OK;
 }
@@ -173,7 +140,7 @@ extern "C" int aleppo_activation_stats(aleppo_ctx *c, const uint8_t *observation
   if (unit_count != U * ALEPPO_ACT_UNIT_COLS || layer_count != LAYER_COUNT)
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT,
                    "activation_stats: unit_count must be (160 + H) * 5 and layer_count 40");
-  if (int rc = act_stats_check_source(c, observations, n))
+  if (int rc = source_check(c, observations, n))
     return rc;
   const double *units_dev = nullptr, *layers_dev = nullptr;
   if (int rc = act_stats_measure(c, observations, n, tau, &units_dev, &layers_dev))

@@ -91,12 +91,10 @@ extern "C" int aleppo_forward(aleppo_ctx *c, const uint8_t *observations, int64_
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "null argument");
   if (n <= 0 || n > c->maxB)
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "forward: n exceeds capacity");
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->pre_acted = -1; // a3 / h are shared scratch
-  SampleMap map{};
-  if (int rc = stage_forward_input(c, observations, n, &map))
+  SampleSource src;
+  if (int rc = source_open(c, observations, 0, n, &src))
     return rc;
-  net_forward(c, c->stage_obs, map, n);
+  net_forward(c, src.obs, src.map, n); // (one chunk: n <= maxB)
   launch_heads_fwd(c->stream, c->h, Pf(c, P_WH), Pf(c, P_BH), c->logits_b, c->values_b, n, c->H, c->A);
   HIPCHK(c, hipMemcpyAsync(logits, c->logits_b, (size_t)n * c->A * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(values, c->values_b, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));

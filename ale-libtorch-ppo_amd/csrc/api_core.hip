@@ -255,23 +255,125 @@ int set_view(aleppo_ctx *c, int set, ParamView *view) {
     *view = live_view(c);
     return ALEPPO_OK;
   case ALEPPO_SET_AVERAGED:
-    if (!c->ema_on)
-      return set_err(c, ALEPPO_ERR_RUNTIME, "no averaged parameters: call aleppo_ema_open first");
-    *view = ParamView{c->Pe, c->Pec};
+  case ALEPPO_SET_SNAPSHOT: { // (the anchor is never a view: fp32 only, never forwarded)
+    const bool avg = set == ALEPPO_SET_AVERAGED;
+    const ParamSet &s = avg ? c->averaged : c->snapshot;
+    if (!s.on)
+      return set_err(c, ALEPPO_ERR_RUNTIME, avg ? NO_AVERAGED : NO_SNAPSHOT);
+    *view = ParamView{s.P, s.Pc};
     return ALEPPO_OK;
-  case ALEPPO_SET_SNAPSHOT:
-    if (!c->snap_on)
-      return set_err(c, ALEPPO_ERR_RUNTIME, "no snapshot: call aleppo_snapshot_take or aleppo_snapshot_import first");
-    *view = ParamView{c->Ps, c->Psc};
-    return ALEPPO_OK;
+  }
   }
   return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "unknown parameter set (ALEPPO_SET_LIVE / _AVERAGED / _SNAPSHOT)");
 }
 
-void refresh_compute_copies(Ctx *c) {
+void params_rewritten(Ctx *c) {
   if (c->prec == ALEPPO_BF16)
     launch_cast_params(c->stream, c->P, c->Pc, (long)c->L.total());
   launch_pack_dgrad(c->stream, c->P, c->L, c->W2d, c->W3d, c->WfcT, c->prec);
+  c->pre_acted = -1;
+  c->ts_step_valid = false;
+}
+
+int export_flat(aleppo_ctx *c, const float *dev, float *flat, size_t count) {
+  if (!flat || count != c->L.reference_count())
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "export: wrong element count");
+  std::vector<float> tmp(c->L.total());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, copy_sync(c, tmp.data(), dev, tmp.size() * 4, hipMemcpyDeviceToHost));
+  params_to_reference(c->L, tmp.data(), flat);
+  return ALEPPO_OK;
+}
+int upload_flat(aleppo_ctx *c, float *dev, const float *flat, size_t count, const char *refusal,
+                std::initializer_list<float *> zero_first) {
+  if (!flat || count != c->L.reference_count())
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, refusal);
+  std::vector<float> tmp(c->L.total());
+  params_to_internal(c->L, flat, tmp.data());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (float *z : zero_first)
+    HIPCHK(c, hipMemsetAsync(z, 0, tmp.size() * 4, c->stream));
+  HIPCHK(c, copy_sync(c, dev, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice)); // (own stream only: api_internal.hpp, memory)
+  return ALEPPO_OK;
+}
+
+int param_set_storage(aleppo_ctx *c, ParamSet *s, bool compute_copy, const char *who, void **extra, size_t extra_bytes) {
+  if (s->P)
+    return ALEPPO_OK;
+  const size_t n = c->L.total();
+  const bool own_copy = compute_copy && c->prec == ALEPPO_BF16;
+  float *p = nullptr;
+  void *pc = nullptr, *x = nullptr;
+  hipError_t e = dalloc(c, &p, n * 4);
+  if (e == hipSuccess && own_copy)
+    e = dalloc(c, &pc, n * 2);
+  if (e == hipSuccess && extra)
+    e = dalloc(c, &x, extra_bytes);
+  if (e != hipSuccess)
+    return set_err(c, ALEPPO_ERR_HIP, std::string(who) + ": allocation failed: " + hipGetErrorString(e));
+  s->P = p;
+  s->Pc = own_copy ? pc : compute_copy ? static_cast<void *>(p) : nullptr;
+  if (extra)
+    *extra = x;
+  return ALEPPO_OK;
+}
+static bool own_compute_copy(const ParamSet &s) { return s.Pc && s.Pc != static_cast<const void *>(s.P); }
+int param_set_copy(aleppo_ctx *c, ParamSet *s, const ParamView &src) {
+  const size_t n = c->L.total();
+  HIPCHK(c, hipMemcpyAsync(s->P, src.P, n * 4, hipMemcpyDeviceToDevice, c->stream));
+  if (own_compute_copy(*s))
+    HIPCHK(c, hipMemcpyAsync(s->Pc, src.Pc, n * 2, hipMemcpyDeviceToDevice, c->stream));
+  return ALEPPO_OK;
+}
+int param_set_upload(aleppo_ctx *c, ParamSet *s, const float *flat, size_t count, const char *refusal) {
+  if (int rc = upload_flat(c, s->P, flat, count, refusal))
+    return rc;
+  if (own_compute_copy(*s))
+    launch_cast_params(c->stream, s->P, s->Pc, (long)c->L.total());
+  return ALEPPO_OK;
+}
+int param_set_export(aleppo_ctx *c, const ParamSet &s, const char *none, float *flat, size_t count) {
+  if (!s.on)
+    return set_err(c, ALEPPO_ERR_RUNTIME, none);
+  return export_flat(c, s.P, flat, count);
+}
+
+// ------------------------------------------------------------------ sample sources (api_internal.hpp)
+int source_check(aleppo_ctx *c, const uint8_t *observations, int64_t n) {
+  const bool batch = observations == nullptr;
+  if (batch && n != 0)
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "activation_stats: null observations need n == 0 (the context's batch)");
+  if (!batch && (n <= 0 || n > c->maxB))
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "activation_stats: n exceeds capacity");
+  if (batch && c->batch_n <= 0)
+    return set_err(c, ALEPPO_ERR_RUNTIME, "no batch: call aleppo_finish_rollout or aleppo_set_batch first");
+  return ALEPPO_OK;
+}
+int source_check_window(aleppo_ctx *c, const uint8_t *observations, int64_t first, int64_t n) {
+  if (!observations) {
+    if (c->batch_n <= 0)
+      return set_err(c, ALEPPO_ERR_RUNTIME, "no batch: call aleppo_finish_rollout or aleppo_set_batch first");
+    if (first < 0 || n <= 0 || first > c->batch_n || n > c->batch_n - first)
+      return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "saliency: [first, first + n) must lie inside the batch");
+  } else if (first != 0 || n <= 0 || n > c->maxB) {
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, first != 0 ? "saliency: first must be 0 with observations"
+                                                              : "saliency: n exceeds capacity");
+  }
+  return ALEPPO_OK;
+}
+int source_open(aleppo_ctx *c, const uint8_t *observations, int64_t first, int64_t n, SampleSource *src) {
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->pre_acted = -1;
+  if (!observations) { // sample n = e*T + t of the batch lives in slot (e, t) of obs
+    *src = SampleSource{c->obs, train_map(c, (long)first), n ? (long)n : c->batch_n - (long)first};
+    return ALEPPO_OK;
+  }
+  if (int rc = stage_observations(c, observations, n))
+    return rc;
+  HIPCHK(c, grow(c, &c->stage_obs, &c->stage_obs_cap, (size_t)n * FRAME_PIX * 4, ALLOC_RAW));
+  *src = SampleSource{c->stage_obs, SampleMap{1, (long)FRAME_PIX, 0, 0, 0}, (long)n}; // sample i at stage_obs + i * 7056
+  launch_obs_pack(c->stream, c->stage_u8, c->stage_obs, n, src->map);
+  return ALEPPO_OK;
 }
 
 } // namespace aleppo
@@ -524,32 +626,14 @@ extern "C" int aleppo_param_count(const aleppo_ctx *c, size_t *count) {
 }
 extern "C" int aleppo_load_params(aleppo_ctx *c, const float *flat, size_t count) {
   CHECK_CTX(c);
-  if (!flat || count != c->L.reference_count())
-    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "load_params: wrong element count");
-  std::vector<float> tmp(c->L.total());
-  params_to_internal(c->L, flat, tmp.data());
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemsetAsync(c->M1, 0, tmp.size() * 4, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->M2, 0, tmp.size() * 4, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->G, 0, tmp.size() * 4, c->stream));
-  HIPCHK(c, copy_sync(c, c->P, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice)); // (own stream only: api_internal.hpp, memory)
+  if (int rc = upload_flat(c, c->P, flat, count, "load_params: wrong element count", {c->M1, c->M2, c->G}))
+    return rc;
   c->adam_step = 0;
-  c->ts_step_valid = false; // (aleppo_tensor_stats: the last step can no longer be recomputed)
-  c->pre_acted = -1;
-  refresh_compute_copies(c);
-  if (c->ema_on) // the average restarts at the loaded parameters, as Adam does
+  params_rewritten(c);
+  if (c->averaged.on) // the average restarts at the loaded parameters, as Adam does
     if (int rc = ema_restart(c))
       return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  return ALEPPO_OK;
-}
-int aleppo::export_flat(aleppo_ctx *c, const float *dev, float *flat, size_t count) {
-  if (!flat || count != c->L.reference_count())
-    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "export: wrong element count");
-  std::vector<float> tmp(c->L.total());
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, copy_sync(c, tmp.data(), dev, tmp.size() * 4, hipMemcpyDeviceToHost));
-  params_to_reference(c->L, tmp.data(), flat);
   return ALEPPO_OK;
 }
 extern "C" int aleppo_export_params(aleppo_ctx *c, float *flat, size_t count) {
@@ -587,14 +671,13 @@ extern "C" int aleppo_export_optimizer(aleppo_ctx *c, float *exp_avg, float *exp
 extern "C" int aleppo_import_optimizer(aleppo_ctx *c, const float *exp_avg, const float *exp_avg_sq, int64_t step,
                                        size_t count) {
   CHECK_CTX(c);
-  if (!exp_avg || !exp_avg_sq || count != c->L.reference_count() || step < 0)
-    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "import_optimizer: bad argument");
-  std::vector<float> tmp(c->L.total());
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  params_to_internal(c->L, exp_avg, tmp.data());
-  HIPCHK(c, copy_sync(c, c->M1, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice));
-  params_to_internal(c->L, exp_avg_sq, tmp.data());
-  HIPCHK(c, copy_sync(c, c->M2, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice));
+  static const char *const refusal = "import_optimizer: bad argument";
+  if (!exp_avg || !exp_avg_sq || count != c->L.reference_count() || step < 0) // (before the first moment is written)
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, refusal);
+  if (int rc = upload_flat(c, c->M1, exp_avg, count, refusal))
+    return rc;
+  if (int rc = upload_flat(c, c->M2, exp_avg_sq, count, refusal))
+    return rc;
   c->adam_step = step;
   c->ts_step_valid = false; // (aleppo_tensor_stats: these moments are not the last step's)
   return ALEPPO_OK;
@@ -744,8 +827,8 @@ extern "C" int aleppo_set_option(aleppo_ctx *c, int option, int value) {
     if (value != 0 && value != 1)
       return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT,
                      "ALEPPO_OPT_EVAL_PARAMS: 0 (the live parameters) or 1 (the averaged set of aleppo_ema_open)");
-    if (value == 1 && !c->ema_on)
-      return set_err(c, ALEPPO_ERR_RUNTIME, "ALEPPO_OPT_EVAL_PARAMS: no averaged parameters: call aleppo_ema_open first");
+    if (value == 1 && !c->averaged.on)
+      return set_err(c, ALEPPO_ERR_RUNTIME, std::string("ALEPPO_OPT_EVAL_PARAMS: ") + NO_AVERAGED);
     c->eval_averaged = value != 0;
   } else if (option == ALEPPO_OPT_UPDATE_GRAPH)
     c->update_graph = value != 0;

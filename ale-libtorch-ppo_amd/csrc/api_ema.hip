@@ -1,5 +1,5 @@
 // api_ema.hip - C ABI (include/aleppo.h), the exponentially averaged parameters: aleppo_ema_open, aleppo_ema_update,
-// aleppo_ema_read, aleppo_ema_export, aleppo_ema_import.  The averaged set (Pe, and its compute copy Pec in bf16 contexts)
+// aleppo_ema_read, aleppo_ema_export, aleppo_ema_import.  The averaged set (c->averaged, a ParamSet with a compute copy)
 // lives next to the live parameters in the same layout; the pass is ema.hip.  Nothing here touches P, the moments, the
 // gradient or anything aleppo_train reads, and everything goes onto the context's main stream only.
 #include "api_internal.hpp"
@@ -9,21 +9,20 @@ using namespace aleppo;
 #define CHECK_EMA(c)                                                                                                   \
   do {                                                                                                                 \
     CHECK_CTX(c);                                                                                                      \
-    if (!(c)->ema_on)                                                                                                  \
-      return set_err((c), ALEPPO_ERR_RUNTIME, "no averaged parameters: call aleppo_ema_open first");                  \
+    if (!(c)->averaged.on)                                                                                             \
+      return set_err((c), ALEPPO_ERR_RUNTIME, NO_AVERAGED);                                                            \
   } while (0)
 
 // the sums of the two sets as they stand and the six doubles; d: what ALEPPO_EMA_DECAY reports
 static void ema_stats_enqueue(aleppo_ctx *c, float d) {
-  const int nblk = launch_ema(c->stream, false, c->P, c->Pe, c->Pec, (long)c->L.total(), 0.f, 0.f, c->ema_blk);
+  const int nblk =
+      launch_ema(c->stream, false, c->P, c->averaged.P, c->averaged.Pc, (long)c->L.total(), 0.f, 0.f, c->ema_blk);
   launch_ema_final(c->stream, nblk, (long long)c->ema_updates, d, c->ema_blk);
 }
 
 int aleppo::ema_restart(aleppo_ctx *c) {
-  const size_t n = c->L.total();
-  HIPCHK(c, hipMemcpyAsync(c->Pe, c->P, n * 4, hipMemcpyDeviceToDevice, c->stream));
-  if (c->Pec != static_cast<void *>(c->Pe))
-    HIPCHK(c, hipMemcpyAsync(c->Pec, c->Pc, n * 2, hipMemcpyDeviceToDevice, c->stream));
+  if (int rc = param_set_copy(c, &c->averaged, live_view(c)))
+    return rc;
   c->ema_updates = 0;
   ema_stats_enqueue(c, 0.f);
   HIPCHK(c, hipGetLastError());
@@ -32,25 +31,14 @@ int aleppo::ema_restart(aleppo_ctx *c) {
 
 extern "C" int aleppo_ema_open(aleppo_ctx *c) {
   CHECK_CTX(c);
-  if (!c->Pe) { // first use; a later call re-initialises the same storage
-    const size_t n = c->L.total();
-    float *pe = nullptr;
-    void *pec = nullptr;
-    double *blk = nullptr;
-    hipError_t e = dalloc(c, &pe, n * 4);
-    if (e == hipSuccess && c->prec == ALEPPO_BF16)
-      e = dalloc(c, &pec, n * 2);
-    if (e == hipSuccess)
-      e = dalloc(c, &blk, EMA_BLK_BYTES);
-    if (e != hipSuccess) // stay closed; what was allocated is the registry's until aleppo_destroy
-      return set_err(c, ALEPPO_ERR_HIP, std::string("ema_open: allocation failed: ") + hipGetErrorString(e));
-    c->Pe = pe;
-    c->Pec = c->prec == ALEPPO_BF16 ? pec : static_cast<void *>(pe); // (an alias in fp32, like Pc / P)
-    c->ema_blk = blk;
-  }
+  void *blk = nullptr; // first use: the set and its block in one step; a later call re-initialises the same storage
+  if (int rc = param_set_storage(c, &c->averaged, true, "ema_open", &blk, EMA_BLK_BYTES))
+    return rc; // (stays closed)
+  if (blk)
+    c->ema_blk = static_cast<double *>(blk);
   if (int rc = ema_restart(c))
     return rc;
-  c->ema_on = true;
+  c->averaged.on = true;
   CHECK_ASYNC(c);
   return ALEPPO_OK;
 }
@@ -61,7 +49,8 @@ extern "C" int aleppo_ema_update(aleppo_ctx *c, double decay) {
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "ema_update: decay must be finite and in [0, 1)");
   const float d = (float)decay, w = (float)(1.0 - decay);
   prof_begin(c, ALEPPO_K_EMA);
-  const int nblk = launch_ema(c->stream, true, c->P, c->Pe, c->Pec, (long)c->L.total(), d, w, c->ema_blk);
+  const int nblk =
+      launch_ema(c->stream, true, c->P, c->averaged.P, c->averaged.Pc, (long)c->L.total(), d, w, c->ema_blk);
   prof_end(c, ALEPPO_K_EMA);
   c->ema_updates++;
   launch_ema_final(c->stream, nblk, (long long)c->ema_updates, d, c->ema_blk);
@@ -84,7 +73,7 @@ extern "C" int aleppo_ema_export(aleppo_ctx *c, float *flat, size_t count, int64
   CHECK_EMA(c);
   if (!updates)
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "ema_export: null updates");
-  if (int rc = export_flat(c, c->Pe, flat, count))
+  if (int rc = param_set_export(c, c->averaged, NO_AVERAGED, flat, count))
     return rc;
   *updates = c->ema_updates;
   return ALEPPO_OK;
@@ -92,16 +81,13 @@ extern "C" int aleppo_ema_export(aleppo_ctx *c, float *flat, size_t count, int64
 
 extern "C" int aleppo_ema_import(aleppo_ctx *c, const float *flat, size_t count, int64_t updates) {
   CHECK_EMA(c);
-  if (!flat || count != c->L.reference_count())
-    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "ema_import: wrong element count");
+  static const char *const refusal = "ema_import: wrong element count";
+  if (!flat || count != c->L.reference_count()) // (here too: it comes before the refusal of updates)
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, refusal);
   if (updates < 0)
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "ema_import: updates must not be negative");
-  std::vector<float> tmp(c->L.total());
-  params_to_internal(c->L, flat, tmp.data());
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, copy_sync(c, c->Pe, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice));
-  if (c->Pec != static_cast<void *>(c->Pe))
-    launch_cast_params(c->stream, c->Pe, c->Pec, (long)c->L.total());
+  if (int rc = param_set_upload(c, &c->averaged, flat, count, refusal))
+    return rc;
   c->ema_updates = updates;
   ema_stats_enqueue(c, 0.f);
   HIPCHK(c, hipGetLastError());

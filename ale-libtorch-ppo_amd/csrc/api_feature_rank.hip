@@ -1,6 +1,5 @@
-// api_feature_rank.hip - C ABI (include/aleppo.h), the representation: aleppo_feature_rank.  It stages and forwards the way
-// aleppo_activation_stats does (same sources, same net_forward, same pre_acted invalidation), reads h with the kernels of
-// feature_rank.hip, copies the Gram blocks and the column sums once and solves on the host (feature_rank_host.hpp).
+// api_feature_rank.hip - C ABI (include/aleppo.h), the representation: aleppo_feature_rank.  It walks a SampleSource
+// (api_internal.hpp: aleppo_activation_stats' sources) on the live parameters, reads h with the kernels of feature_rank.hip, copies the Gram blocks and the column sums once and solves on the host (feature_rank_host.hpp).
 #include "api_internal.hpp"
 #include "feature_rank_host.hpp"
 
@@ -28,30 +27,21 @@ extern "C" int aleppo_feature_rank(aleppo_ctx *c, const uint8_t *observations, i
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "feature_rank: eps must be finite and non-negative");
   if ((k.centered != 0 && k.centered != 1) || k.reserved != 0)
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "feature_rank: centered must be 0 or 1 and reserved 0");
-  if (int rc = act_stats_check_source(c, observations, n))
+  if (int rc = source_check(c, observations, n))
     return rc;
-  const bool batch = observations == nullptr;
-  const long total = batch ? c->batch_n : (long)n;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->pre_acted = -1; // a1 / a2 / a3 / h are shared scratch
   const FeatureRankPlan pl = feature_rank_plan(c->H, c->maxB);
   if (!c->fr_scratch)
     HIPCHK(c, dalloc(c, &c->fr_scratch, pl.bytes));
-  const uint32_t *obs = c->obs;
-  SampleMap map = train_map(c, 0);
-  if (!batch) {
-    if (int rc = stage_forward_input(c, observations, n, &map))
-      return rc;
-    obs = c->stage_obs;
-  }
-  for (long n0 = 0; n0 < total; n0 += c->maxB) {
-    const long ns = std::min(c->maxB, total - n0);
-    map.n0 = (int)n0;
-    net_forward(c, obs, map, ns);
+  SampleSource src;
+  if (int rc = source_open(c, observations, 0, n, &src))
+    return rc;
+  source_walk(c, src, [&](const SampleMap &map, long n0, long ns) {
+    net_forward(c, src.obs, map, ns);
     prof_begin(c, ALEPPO_K_ACT_STATS); // (the class of the read-only passes over the activations)
     launch_feature_rank_chunk(c->stream, c->h, ns, n0 == 0, pl, c->fr_scratch);
     prof_end(c, ALEPPO_K_ACT_STATS);
-  }
+    return ALEPPO_OK;
+  });
   HIPCHK(c, hipGetLastError());
   std::vector<double> res(pl.result_doubles);
   HIPCHK(c, hipMemcpyAsync(res.data(), c->fr_scratch, res.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -66,7 +56,7 @@ extern "C" int aleppo_feature_rank(aleppo_ctx *c, const uint8_t *observations, i
       g[j * H + i] = v;
     }
   const double *s = res.data() + (size_t)pl.tiles * 4096;
-  const double left_out = s[H], rows = (double)total - left_out;
+  const double left_out = s[H], rows = (double)src.total - left_out;
   if (!aleppo_fr::solve(g.data(), s, (int)H, rows, left_out, k.centered != 0, (double)k.delta, (double)k.eps, st.data(),
                         sg.data()))
     return set_err(c, ALEPPO_ERR_RUNTIME, "feature_rank: the eigenvalue iteration did not converge");

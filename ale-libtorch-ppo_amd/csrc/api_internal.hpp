@@ -11,6 +11,7 @@
 #include <thread>
 #include <mutex>
 #include <cstring>
+#include <initializer_list>
 #include <rccl/rccl.h>
 
 // ------------------------------------------------------------------ helpers
@@ -123,7 +124,9 @@ struct ParamView {
   const void *Pc;
 };
 inline ParamView live_view(const Ctx *c) { return ParamView{c->P, c->Pc}; }
-inline ParamView eval_view(const Ctx *c) { return c->eval_averaged ? ParamView{c->Pe, c->Pec} : live_view(c); }
+inline ParamView eval_view(const Ctx *c) {
+  return c->eval_averaged ? ParamView{c->averaged.P, c->averaged.Pc} : live_view(c);
+}
 inline const float *Pf(const Ctx *c, const ParamView &v, ParamId id) { return v.P + c->L.off[id]; }
 inline const void *Pcw(const Ctx *c, const ParamView &v, ParamId id) {
   return static_cast<const char *>(v.Pc) + c->L.off[id] * tsz(c);
@@ -136,14 +139,47 @@ int net_forward(Ctx *c, const ParamView &pv, const uint32_t *obs, SampleMap map,
 // the view of ALEPPO_SET_LIVE / _AVERAGED / _SNAPSHOT (aleppo_snapshot_take, aleppo_policy_diff): ALEPPO_ERR_RUNTIME for a
 // set that does not exist yet, ALEPPO_ERR_INVALID_ARGUMENT for an unknown one; *view is written on success only
 int set_view(aleppo_ctx *c, int set, ParamView *view);
+// what a call refuses on a set that no take, import or open has filled yet (set_view, the exports, ALEPPO_OPT_EVAL_PARAMS)
+constexpr const char *NO_AVERAGED = "no averaged parameters: call aleppo_ema_open first";
+constexpr const char *NO_SNAPSHOT = "no snapshot: call aleppo_snapshot_take or aleppo_snapshot_import first";
+constexpr const char *NO_ANCHOR = "no anchor: call aleppo_anchor_take or aleppo_anchor_import first";
 
-void refresh_compute_copies(Ctx *c);
-// api_core.hip, also for aleppo_ema_export (api_ema.hip): a vector in the internal layout (device) -> the caller's flat
-// array in the reference's order, with aleppo_export_params' count check; waits for the stream
+// P was rewritten in place (aleppo_load_params, the recycle pass, aleppo_shrink_perturb): the compute copy and the packed
+// dgrad weights are rebuilt on the main stream, and what aleppo_step pre-computed (pre_acted) and aleppo_tensor_stats'
+// last step (ts_step_valid) are forgotten
+void params_rewritten(Ctx *c);
+// a vector in the internal layout (device) -> the caller's flat array in the reference's order, with aleppo_export_params'
+// count check; waits for the stream
 int export_flat(aleppo_ctx *c, const float *dev, float *flat, size_t count);
-// api_ema.hip, also for aleppo_load_params: the average restarts at the live parameters (Pe = P, Pec = Pc, updates 0, the
-// statistics of that state), enqueued on the main stream.  Call only where c->ema_on or aleppo_ema_open has allocated.
+// the reverse: `refusal` (ALEPPO_ERR_INVALID_ARGUMENT) unless flat holds the reference's element count, then the
+// permutation, the stream's synchronise, a zero fill of each of zero_first (device vectors of L.total() floats) and the
+// copy; complete when it returns.  A call that has more to refuse, or storage to allocate, checks the count itself first.
+int upload_flat(aleppo_ctx *c, float *dev, const float *flat, size_t count, const char *refusal,
+                std::initializer_list<float *> zero_first = {});
+// ---- the stored parameter sets (ParamSet, common.hpp).  None of the helpers sets s->on: the entry point does, last.
+// Storage on first use, zero-filled: the fp32 vector and - compute_copy - its copy in T, a second allocation in bf16
+// contexts and an alias in fp32 ones (like Pc / P); *extra, where given, is allocated with them (aleppo_ema_open's
+// block).  All or nothing: a failure ("<who>: allocation failed: ...") assigns nothing, and what was allocated stays in
+// the registry until aleppo_destroy.  A set that has storage: nothing, and *extra is left alone.
+int param_set_storage(aleppo_ctx *c, ParamSet *s, bool compute_copy, const char *who, void **extra = nullptr,
+                      size_t extra_bytes = 0);
+// s = src, device to device on the main stream (the compute copy only where s has one of its own)
+int param_set_copy(aleppo_ctx *c, ParamSet *s, const ParamView &src);
+// s = flat (upload_flat), then the cast into a compute copy of its own (enqueued)
+int param_set_upload(aleppo_ctx *c, ParamSet *s, const float *flat, size_t count, const char *refusal);
+// ALEPPO_ERR_RUNTIME with `none` while !s.on, else export_flat
+int param_set_export(aleppo_ctx *c, const ParamSet &s, const char *none, float *flat, size_t count);
+// api_ema.hip, also for aleppo_load_params: the average restarts at the live parameters (the set's copy, updates 0, the
+// statistics of that state), enqueued on the main stream.  Call only where c->averaged has storage.
 int ema_restart(aleppo_ctx *c);
+
+// the permutation of aleppo.h (aleppo_read_sample_order), also what the keyed passes mix the caller's key with
+inline uint64_t splitmix64(uint64_t x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
 
 inline uint32_t float_bits(float f) {
   uint32_t u;
@@ -172,14 +208,40 @@ int ensure_metric_storage(aleppo_ctx *c, int epochs, int M, long B);
 // api_batch.hip: NCHW uint8 observations of the caller -> c->stage_u8 (device)
 int stage_observations(aleppo_ctx *c, const uint8_t *observations, int64_t n);
 int ensure_val_storage(aleppo_ctx *c);
-// api_acts.hip, also for api_saliency.hip: the caller's observations -> packed stacks in c->stage_obs (never the rollout's
-// slots); *map addresses them
-int stage_forward_input(aleppo_ctx *c, const uint8_t *observations, int64_t n, SampleMap *map);
-// api_acts.hip, also for aleppo_recycle_dormant (api_recycle.hip): what aleppo_activation_stats refuses in tau and in its
-// source of samples, and the measurement itself with the arguments already checked - everything up to and including the
-// finalising launch is enqueued, *units_dev / *layers_dev are the two tables in device memory
+// ---- a source of samples for net_forward, checked and opened: the caller's observations staged into c->stage_obs (never
+// the rollout's slots), or - null observations - samples of the batch the context holds, in place.  Every call that
+// forwards samples outside the rollout and the update goes check -> open -> walk; nothing else sets a walk up by hand.
+struct SampleSource {
+  const uint32_t *obs = nullptr; // the packed stacks
+  SampleMap map{};               // ... and where sample i of the source lies in them: map.n0 is the source's first sample
+  long total = 0;                // samples
+};
+// The check refuses and enqueues nothing.  source_check: null observations need n == 0 and mean the whole batch, the
+// caller's come n at a time, at most maxB (the messages are aleppo_activation_stats', the first of the callers).
+// source_check_window (saliency): samples [first, first + n) of the batch, or n observations with first == 0.
+int source_check(aleppo_ctx *c, const uint8_t *observations, int64_t n);
+int source_check_window(aleppo_ctx *c, const uint8_t *observations, int64_t first, int64_t n);
+// The open, arguments already checked: the stream's synchronise, pre_acted = -1 (a1 / a2 / a3 / h are shared scratch, and
+// net_forward drops aleppo_export_backward's mark itself), then the upload and the pack of the caller's n observations,
+// or the batch's slots from sample `first` (n == 0: all that follow).
+int source_open(aleppo_ctx *c, const uint8_t *observations, int64_t first, int64_t n, SampleSource *src);
+// The walk: chunks of at most maxB samples in order; body(map, n0, ns) -> int gets the map of samples [n0, n0 + ns) of
+// the source, forwards them on whatever parameter sets it needs (net_forward(c, view, src.obs, map, ns)) and enqueues its
+// pass over the activations; a non-zero return ends the walk and is returned.
+template <class Body> int source_walk(aleppo_ctx *c, const SampleSource &src, Body body) {
+  for (long n0 = 0; n0 < src.total; n0 += c->maxB) {
+    const long ns = std::min(c->maxB, src.total - n0);
+    SampleMap map = src.map;
+    map.n0 += (int)n0;
+    if (int rc = body(map, n0, ns))
+      return rc;
+  }
+  return ALEPPO_OK;
+}
+// api_acts.hip, also for aleppo_recycle_dormant (api_recycle.hip): what aleppo_activation_stats refuses in tau, and the
+// measurement itself with the arguments already checked - everything up to and including the finalising launch is
+// enqueued, *units_dev / *layers_dev are the two tables in device memory
 int act_stats_check_tau(aleppo_ctx *c, double tau);
-int act_stats_check_source(aleppo_ctx *c, const uint8_t *observations, int64_t n);
 int act_stats_measure(aleppo_ctx *c, const uint8_t *observations, int64_t n, double tau, const double **units_dev,
                       const double **layers_dev);
 // api_rollout.hip, for aleppo_env_rollout (api_env.hip): slot `slot`'s acting kernels and head, and the GPU side of a step

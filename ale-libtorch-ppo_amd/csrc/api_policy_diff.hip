@@ -1,29 +1,12 @@
 // api_policy_diff.hip - C ABI (include/aleppo.h), policy churn: aleppo_snapshot_take, aleppo_snapshot_export,
-// aleppo_snapshot_import, aleppo_policy_diff.  The snapshot (Ps, and its compute copy Psc in bf16 contexts) lives next to
-// the live and the averaged parameters in the same layout and only these calls write it.  aleppo_policy_diff stages and
-// forwards the way aleppo_feature_rank does (same sources, same pre_acted invalidation), once per set through
-// net_forward's ParamView form, and compares with the kernels of policy_diff.hip.  Nothing here writes P, the moments, the
+// aleppo_snapshot_import, aleppo_policy_diff.  The snapshot (c->snapshot, a ParamSet with a compute copy) lives next to
+// the live and the averaged parameters in the same layout and only these calls write it.  aleppo_policy_diff walks a
+// SampleSource (api_internal.hpp), forwards each chunk once per set through net_forward's ParamView form and compares
+// with the kernels of policy_diff.hip.  Nothing here writes P, the moments, the
 // gradient, the averaged set or anything aleppo_train reads, and everything goes onto the context's main stream only.
 #include "api_internal.hpp"
 
 using namespace aleppo;
-
-// first use: the snapshot's storage, zero-filled; a failure leaves the context without one
-static int snapshot_storage(aleppo_ctx *c) {
-  if (c->Ps)
-    return ALEPPO_OK;
-  const size_t n = c->L.total();
-  float *ps = nullptr;
-  void *psc = nullptr;
-  hipError_t e = dalloc(c, &ps, n * 4);
-  if (e == hipSuccess && c->prec == ALEPPO_BF16)
-    e = dalloc(c, &psc, n * 2);
-  if (e != hipSuccess) // (what was allocated is the registry's until aleppo_destroy)
-    return set_err(c, ALEPPO_ERR_HIP, std::string("snapshot: allocation failed: ") + hipGetErrorString(e));
-  c->Ps = ps;
-  c->Psc = c->prec == ALEPPO_BF16 ? psc : static_cast<void *>(ps); // (an alias in fp32, like Pc / P)
-  return ALEPPO_OK;
-}
 
 extern "C" int aleppo_snapshot_take(aleppo_ctx *c, int source_set) {
   CHECK_CTX(c);
@@ -32,38 +15,31 @@ extern "C" int aleppo_snapshot_take(aleppo_ctx *c, int source_set) {
   ParamView src{};
   if (int rc = set_view(c, source_set, &src))
     return rc;
-  if (int rc = snapshot_storage(c))
+  if (int rc = param_set_storage(c, &c->snapshot, true, "snapshot"))
     return rc;
-  const size_t n = c->L.total();
-  HIPCHK(c, hipMemcpyAsync(c->Ps, src.P, n * 4, hipMemcpyDeviceToDevice, c->stream));
-  if (c->Psc != static_cast<void *>(c->Ps))
-    HIPCHK(c, hipMemcpyAsync(c->Psc, src.Pc, n * 2, hipMemcpyDeviceToDevice, c->stream));
-  c->snap_on = true;
+  if (int rc = param_set_copy(c, &c->snapshot, src))
+    return rc;
+  c->snapshot.on = true;
   CHECK_ASYNC(c);
   return ALEPPO_OK;
 }
 
 extern "C" int aleppo_snapshot_export(aleppo_ctx *c, float *flat, size_t count) {
   CHECK_CTX(c);
-  if (!c->snap_on)
-    return set_err(c, ALEPPO_ERR_RUNTIME, "no snapshot: call aleppo_snapshot_take or aleppo_snapshot_import first");
-  return export_flat(c, c->Ps, flat, count);
+  return param_set_export(c, c->snapshot, NO_SNAPSHOT, flat, count);
 }
 
 extern "C" int aleppo_snapshot_import(aleppo_ctx *c, const float *flat, size_t count) {
   CHECK_CTX(c);
-  if (!flat || count != c->L.reference_count())
-    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "snapshot_import: wrong element count");
-  if (int rc = snapshot_storage(c))
+  static const char *const refusal = "snapshot_import: wrong element count";
+  if (!flat || count != c->L.reference_count()) // (here too: a refused call allocates nothing)
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, refusal);
+  if (int rc = param_set_storage(c, &c->snapshot, true, "snapshot"))
     return rc;
-  std::vector<float> tmp(c->L.total());
-  params_to_internal(c->L, flat, tmp.data());
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, copy_sync(c, c->Ps, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice));
-  if (c->Psc != static_cast<void *>(c->Ps))
-    launch_cast_params(c->stream, c->Ps, c->Psc, (long)c->L.total());
+  if (int rc = param_set_upload(c, &c->snapshot, flat, count, refusal))
+    return rc;
   HIPCHK(c, hipGetLastError());
-  c->snap_on = true;
+  c->snapshot.on = true;
   CHECK_ASYNC(c);
   return ALEPPO_OK;
 }
@@ -80,18 +56,14 @@ extern "C" int aleppo_policy_diff(aleppo_ctx *c, const uint8_t *observations, in
     return rc;
   if (int rc = set_view(c, set_b, &view[1]))
     return rc;
-  if (int rc = act_stats_check_source(c, observations, n))
+  if (int rc = source_check(c, observations, n))
     return rc;
-  const bool batch = observations == nullptr;
-  const long total = batch ? c->batch_n : (long)n;
-  const size_t rows = (size_t)total;
+  const size_t rows = (size_t)(observations ? n : c->batch_n);
   if ((per_sample && per_sample_count != rows * ALEPPO_PD_ROW) || (transitions && transition_count != A * A) ||
       (outputs && output_count != 2 * rows * (A + 1)))
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT,
                    "policy_diff: per_sample_count must be rows * ALEPPO_PD_ROW, transition_count A * A, output_count "
                    "2 * rows * (A + 1)");
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->pre_acted = -1; // a1 / a2 / a3 / h are shared scratch
   // the scratch holds the largest sample count either source can bring (aleppo_set_batch takes at most N samples)
   const PolicyDiffPlan pl = policy_diff_plan(c->H, c->A, std::max(c->N, c->maxB), c->maxB);
   if (!c->pd_scratch)
@@ -99,18 +71,12 @@ extern "C" int aleppo_policy_diff(aleppo_ctx *c, const uint8_t *observations, in
   char *base = static_cast<char *>(c->pd_scratch);
   auto fl = [&](size_t off) { return reinterpret_cast<float *>(base + off); };
   HIPCHK(c, hipMemsetAsync(base + pl.trans, 0, MAX_ACTIONS * MAX_ACTIONS * sizeof(unsigned long long), c->stream));
-  const uint32_t *obs = c->obs;
-  SampleMap map = train_map(c, 0);
-  if (!batch) {
-    if (int rc = stage_forward_input(c, observations, n, &map))
-      return rc;
-    obs = c->stage_obs;
-  }
-  for (long n0 = 0; n0 < total; n0 += c->maxB) {
-    const long ns = std::min(c->maxB, total - n0);
-    map.n0 = (int)n0;
+  SampleSource src;
+  if (int rc = source_open(c, observations, 0, n, &src))
+    return rc;
+  const int rc = source_walk(c, src, [&](const SampleMap &map, long n0, long ns) -> int {
     for (int k = 0; k < 2; ++k) {
-      net_forward(c, view[k], obs, map, ns);
+      net_forward(c, view[k], src.obs, map, ns);
       launch_heads_fwd(c->stream, c->h, Pf(c, view[k], P_WH), Pf(c, view[k], P_BH), fl(pl.logits[k]) + (size_t)n0 * A,
                        fl(pl.values[k]) + n0, ns, c->H, c->A);
       if (k == 0) // set b's forward overwrites h
@@ -119,7 +85,10 @@ extern "C" int aleppo_policy_diff(aleppo_ctx *c, const uint8_t *observations, in
     prof_begin(c, ALEPPO_K_ACT_STATS); // (the class of the read-only passes over the activations)
     launch_policy_diff_chunk(c->stream, c->h, n0, ns, n0 == 0, pl, c->pd_scratch);
     prof_end(c, ALEPPO_K_ACT_STATS);
-  }
+    return ALEPPO_OK;
+  });
+  if (rc)
+    return rc;
   launch_policy_diff_stats(c->stream, pl, c->pd_scratch);
   HIPCHK(c, hipGetLastError());
   // the results pass through host temporaries: a failed call writes nothing

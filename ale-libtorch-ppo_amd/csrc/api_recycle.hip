@@ -1,16 +1,9 @@
 // api_recycle.hip - C ABI (include/aleppo.h), acting on the representation: aleppo_recycle_units, aleppo_recycle_dormant
 // (ReDo, Sokar et al. 2023).  Both rewrite P / M1 / M2 in place by one masked pass (recycle.hip) and rebuild every derived
-// copy the way aleppo_load_params does; no pointer changes, so a captured update stays valid.  Own stream only.
+// copy the way aleppo_load_params does (params_rewritten); no pointer changes, so a captured update stays valid.  Own stream only.
 #include "api_internal.hpp"
 
 using namespace aleppo;
-
-static uint64_t splitmix64(uint64_t x) { // the permutation of aleppo.h (aleppo_read_sample_order)
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
 
 static inline size_t unit_total(const aleppo_ctx *c) { return (size_t)(A1_C + A2_C + A3_C + c->H); }
 
@@ -26,9 +19,7 @@ static void recycle_enqueue(aleppo_ctx *c, uint64_t key, int flags) {
   launch_recycle(c->stream, c->L, c->rc_mask, splitmix64(key), (flags & ALEPPO_RECYCLE_KEEP_MOMENTS) != 0, c->P, c->M1,
                  c->M2);
   prof_end(c, ALEPPO_K_RECYCLE);
-  refresh_compute_copies(c);
-  c->pre_acted = -1;        // (what aleppo_step pre-computed used the old parameters)
-  c->ts_step_valid = false; // (aleppo_tensor_stats: these moments are not the last step's)
+  params_rewritten(c);
 }
 
 static void count_units(const aleppo_ctx *c, const uint8_t *mask, int64_t counts[ALEPPO_RECYCLE_COUNTS]) {
@@ -83,7 +74,7 @@ extern "C" int aleppo_recycle_dormant(aleppo_ctx *c, const uint8_t *observations
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "recycle_dormant: layers must be a non-empty set of ALEPPO_RECYCLE_* bits");
   if (int rc = act_stats_check_tau(c, tau))
     return rc;
-  if (int rc = act_stats_check_source(c, observations, n))
+  if (int rc = source_check(c, observations, n))
     return rc;
   if (c->world > 1) // each rank would score its own samples and pick its own units: the replicas would part
     return set_err(c, ALEPPO_ERR_RUNTIME,

@@ -44,20 +44,19 @@ extern "C" int aleppo_refresh_advantages(aleppo_ctx *c, int set, double *stats, 
     HIPCHK(c, dalloc(c, &c->fresh_tm, (size_t)(T + 1) * E * c->rsz));
   if (stats && !c->rf_scratch)
     HIPCHK(c, dalloc(c, &c->rf_scratch, (32 + (size_t)nblk * RSTAT_SUMS) * sizeof(double)));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->pre_acted = -1; // a1 / a2 / a3 / h are shared scratch (net_forward drops aleppo_export_backward's mark itself)
+  SampleSource src; // the whole batch (refresh_check_batch: batch_n == N), in place
+  if (int rc = source_open(c, nullptr, 0, 0, &src))
+    return rc;
   c->fresh_valid = false;
   const float *wv = Pf(c, view, P_WH) + (size_t)A * H, *bv = Pf(c, view, P_BH) + A;
   // the batch in logical order, then the post-rollout observation of every environment (slot T)
-  SampleMap map = train_map(c, 0);
-  for (long n0 = 0; n0 < c->N; n0 += c->maxB) {
-    const long ns = std::min(c->maxB, c->N - n0);
-    map.n0 = (int)n0;
-    net_forward(c, view, c->obs, map, ns);
+  source_walk(c, src, [&](const SampleMap &map, long n0, long ns) {
+    net_forward(c, view, src.obs, map, ns);
     prof_begin(c, ALEPPO_K_ACT_STATS); // (the class of the read-only passes over the activations)
     launch_value_refresh(c->stream, c->h, wv, bv, c->fresh_tm, n0, ns, H, E, T, false, c->rt16);
     prof_end(c, ALEPPO_K_ACT_STATS);
-  }
+    return ALEPPO_OK;
+  });
   net_forward(c, view, c->obs, slot_map(c, T), E);
   prof_begin(c, ALEPPO_K_ACT_STATS);
   launch_value_refresh(c->stream, c->h, wv, bv, c->fresh_tm, 0, E, H, E, T, true, c->rt16);

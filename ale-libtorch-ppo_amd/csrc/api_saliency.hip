@@ -1,6 +1,6 @@
 // api_saliency.hip - C ABI (include/aleppo.h), perturbation saliency: aleppo_saliency_tables, aleppo_saliency,
-// aleppo_saliency_perturbed.  The two stateful calls stage and forward the way aleppo_activation_stats does (same
-// synchronise points, same net_forward, same pre_acted invalidation) and only read the learner; what they write is their own
+// aleppo_saliency_perturbed.  The two stateful calls open a SampleSource (api_internal.hpp) over a window of the
+// batch or the caller's observations, walk it for the unperturbed outputs, and only read the learner; what they write is their own
 // staging, the shared activation scratch and logits_b / values_b.
 #include "api_internal.hpp"
 
@@ -57,12 +57,11 @@ extern "C" int aleppo_saliency_tables(const aleppo_saliency_config *cfg, uint16_
 }
 
 namespace {
-struct SalCall { // a checked call: the parameters, the grid and where the samples are
+struct SalCall { // a checked call: the parameters, the grid and - once opened - where the samples are
   aleppo_saliency_config k;
   SalTables tb;
   int G = 0, P = 0;
-  const uint32_t *obs = nullptr;
-  SampleMap map{};
+  SampleSource src;
 };
 
 // what both calls refuse in cfg and in their source of samples (nothing is enqueued or written)
@@ -71,33 +70,11 @@ int sal_check(aleppo_ctx *c, const uint8_t *observations, int64_t first, int64_t
   call->k = cfg ? *cfg : SAL_DEFAULT;
   if (const char *bad = sal_config_invalid(call->k))
     return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, bad);
-  if (!observations) {
-    if (c->batch_n <= 0)
-      return set_err(c, ALEPPO_ERR_RUNTIME, "no batch: call aleppo_finish_rollout or aleppo_set_batch first");
-    if (first < 0 || n <= 0 || first > c->batch_n || n > c->batch_n - first)
-      return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "saliency: [first, first + n) must lie inside the batch");
-  } else if (first != 0 || n <= 0 || n > c->maxB) {
-    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, first != 0 ? "saliency: first must be 0 with observations"
-                                                              : "saliency: n exceeds capacity");
-  }
+  if (int rc = source_check_window(c, observations, first, n))
+    return rc;
   sal_tables(call->k, call->tb.g, call->tb.w, &call->tb.radius);
   call->G = (84 + call->k.stride - 1) / call->k.stride;
   call->P = call->G * call->G;
-  return ALEPPO_OK;
-}
-
-// the stream's synchronise and the source: the caller's observations staged, or the batch's slots in place
-int sal_source(aleppo_ctx *c, const uint8_t *observations, int64_t first, int64_t n, SalCall *call) {
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->pre_acted = -1; // a1 / a2 / a3 / h are shared scratch
-  if (observations) {
-    if (int rc = stage_forward_input(c, observations, n, &call->map))
-      return rc;
-    call->obs = c->stage_obs;
-  } else {
-    call->obs = c->obs;
-    call->map = train_map(c, (long)first);
-  }
   return ALEPPO_OK;
 }
 
@@ -120,13 +97,13 @@ void sal_perturb_chunk(aleppo_ctx *c, const SalCall &call, SalBlurred *held, lon
   if (lo < held->lo || hi > held->hi) {
     const long count = std::min(room, n - lo); // (>= hi - lo + 1: room covers what a chunk can touch)
     prof_begin(c, ALEPPO_K_SAL_BLUR);
-    launch_sal_blur(c->stream, call.obs, call.map, lo, count, call.tb, call.k.planes, c->sal_blur);
+    launch_sal_blur(c->stream, call.src.obs, call.src.map, lo, count, call.tb, call.k.planes, c->sal_blur);
     prof_end(c, ALEPPO_K_SAL_BLUR);
     held->lo = lo, held->hi = lo + count - 1;
   }
   prof_begin(c, ALEPPO_K_SAL_PERTURB);
-  launch_sal_perturb(c->stream, call.obs, call.map, c->sal_blur, held->lo, call.tb, call.k.planes, call.k.stride, call.G, j0,
-                     ns, per, p0, c->sal_stage);
+  launch_sal_perturb(c->stream, call.src.obs, call.src.map, c->sal_blur, held->lo, call.tb, call.k.planes, call.k.stride,
+                     call.G, j0, ns, per, p0, c->sal_stage);
   prof_end(c, ALEPPO_K_SAL_PERTURB);
 }
 // the staging both calls need: `pairs` pairs in chunks of at most maxB, `per` of them per sample, n samples
@@ -149,7 +126,7 @@ extern "C" int aleppo_saliency(aleppo_ctx *c, const uint8_t *observations, int64
   const int P = call.P, A = c->A;
   const long pairs = (long)n * P;
   const size_t out_floats = (size_t)n * (P + 1) * (A + 1);
-  if (int rc = sal_source(c, observations, first, n, &call))
+  if (int rc = source_open(c, observations, first, n, &call.src))
     return rc;
   if (int rc = sal_ensure_staging(c, pairs, P, (long)n))
     return rc;
@@ -158,14 +135,12 @@ extern "C" int aleppo_saliency(aleppo_ctx *c, const uint8_t *observations, int64
   float *base_logits = c->sal_base, *base_values = c->sal_base + (size_t)n * A;
   float *d_policy = c->sal_out, *d_value = d_policy + pairs, *d_outputs = outputs ? d_value + pairs : nullptr;
   // the unperturbed samples first: their outputs are kept in a buffer of their own
-  for (long n0 = 0; n0 < n; n0 += c->maxB) {
-    const long ns = std::min(c->maxB, (long)n - n0);
-    SampleMap m = call.map;
-    m.n0 += (int)n0;
-    net_forward(c, call.obs, m, ns);
+  source_walk(c, call.src, [&](const SampleMap &map, long n0, long ns) {
+    net_forward(c, call.src.obs, map, ns);
     launch_heads_fwd(c->stream, c->h, Pf(c, P_WH), Pf(c, P_BH), base_logits + (size_t)n0 * A, base_values + n0, ns, c->H,
                      A);
-  }
+    return ALEPPO_OK;
+  });
   SalBlurred held;
   const long room = sal_blur_room(c, pairs, P, (long)n);
   for (long i0 = 0; i0 < pairs; i0 += c->maxB) { // a chunk boundary may fall inside one sample's positions
@@ -205,7 +180,7 @@ extern "C" int aleppo_saliency_perturbed(aleppo_ctx *c, const uint8_t *observati
   const int per = (int)position_count, p0 = (int)position_first;
   const long pairs = (long)n * per;
   constexpr size_t STACK = (size_t)4 * FRAME_PIX; // bytes of one stack, packed or NCHW
-  if (int rc = sal_source(c, observations, first, n, &call))
+  if (int rc = source_open(c, observations, first, n, &call.src))
     return rc;
   if (int rc = sal_ensure_staging(c, pairs, per, (long)n))
     return rc;

@@ -71,12 +71,6 @@ int aleppo::ensure_val_storage(aleppo_ctx *c) {
   return ALEPPO_OK;
 }
 
-static uint64_t splitmix64(uint64_t x) { // the permutation of aleppo.h (aleppo_read_sample_order)
-  uint64_t z = x + 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 // half width h of the Feistel network over [0, 2^(2h)) for N samples: 2h = ceil(log2 N), at least 2, rounded up to even
 static int feistel_half_width(long N) {
   int w = 0;
@@ -139,7 +133,7 @@ static int plan_update(aleppo_ctx *c, int epochs, int M, UpdatePlan *plan) {
   const long N = c->batch_n;
   if (N <= 0)
     return set_err(c, ALEPPO_ERR_RUNTIME, "no batch: call aleppo_finish_rollout or aleppo_set_batch first");
-  if (c->anchor_coef_bits != 0 && !c->anchor_on)
+  if (c->anchor_coef_bits != 0 && !c->anchor.on)
     return set_err(c, ALEPPO_ERR_RUNTIME,
                    "ALEPPO_OPT_ANCHOR_COEF > 0 needs an anchor: call aleppo_anchor_take or aleppo_anchor_import first");
   c->pre_acted = -1; // the update's activations overwrite the acting scratch, and the weights change
@@ -169,7 +163,7 @@ static int plan_update(aleppo_ctx *c, int epochs, int M, UpdatePlan *plan) {
   p.advn = c->adv_norm_mb; // ALEPPO_OPT_ADV_NORM_MINIBATCH (statistics in advn_stats, grown with the metrics)
   p.klpen = c->kl_pen;     // ALEPPO_OPT_KL_PENALTY (the exact-KL plane kl_ps, beta in kl_beta)
   p.reg = c->wd_bits != 0 || c->anchor_coef_bits != 0; // (valid patterns are >= +0.0f: non-zero bits are a value > 0)
-  p.anchor = p.reg && c->anchor_on ? c->Pa : nullptr;
+  p.anchor = p.reg && c->anchor.on ? c->anchor.P : nullptr;
   if (p.klpen && (rc = ensure_kl_storage(c)))
     return rc;
   if (p.shuffle && (rc = ensure_shuffle_storage(c, epochs, N)))

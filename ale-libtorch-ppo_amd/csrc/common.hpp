@@ -40,6 +40,13 @@ struct ParamLayout {
 // reference (libtorch parameters() order, NCHW) <-> internal (NHWC-k order) permutation, on the host
 void params_to_internal(const ParamLayout &L, const float *ref, float *internal);
 void params_to_reference(const ParamLayout &L, const float *internal, float *ref);
+// A stored parameter set next to the live one (P / Pc), in the same layout: the averaged set, the snapshot, the anchor.
+// Allocated on first use and written only through the param_set_* helpers of api_internal.hpp.
+struct ParamSet {
+  float *P = nullptr; // fp32, internal layout, L.total() floats (pads zero)
+  void *Pc = nullptr; // compute copy of P in T (same layout); == P for fp32; nullptr for a set that is never forwarded
+  bool on = false;    // a take or an import has succeeded
+};
 
 // sample n of a batch lives in obs slot  (n / TP) * s1 + (n % TP) * s0 + base   (units: u32 pixels)
 // idx != nullptr (ALEPPO_OPT_MINIBATCH_SHUFFLE): logical sample n is first replaced by idx[n].  The kernels that read
@@ -219,8 +226,7 @@ struct Ctx {
   // on first use and written by those two calls alone.  Either coefficient non-zero: the update launches reg_step_kernel
   // in adam_kernel's place
   uint32_t wd_bits = 0, anchor_coef_bits = 0;
-  bool anchor_on = false;          // a take or an import has succeeded
-  float *Pa = nullptr;             // fp32, internal layout, L.total() floats (pads zero)
+  ParamSet anchor;                 // (no compute copy: Pc stays nullptr)
   // ---- ALEPPO_OPT_REWARD_SCALE / _CLIP: device storage allocated on first use (ensure_rs_storage), never moved
   bool reward_scale = false;
   float reward_scale_clip = 10.0f;
@@ -293,18 +299,14 @@ struct Ctx {
   uint8_t *rc_mask = nullptr;
   // ---- aleppo_ema_open: the exponentially averaged parameters; nothing below is allocated, and nothing is enqueued for it,
   // on a context that never opens them
-  bool ema_on = false;
-  float *Pe = nullptr;             // fp32, internal layout, L.total() floats (pads zero)
-  void *Pec = nullptr;             // compute copy of Pe in T (same layout); == Pe for fp32
+  ParamSet averaged;               // (on: aleppo_ema_open has succeeded)
   double *ema_blk = nullptr;       // [EMA_MAX_BLOCKS][3] workgroup partials, then the ALEPPO_EMA_STATS_COUNT doubles
   int64_t ema_updates = 0;
-  bool eval_averaged = false;      // ALEPPO_OPT_EVAL_PARAMS: the evaluation lanes act on (Pe, Pec)
+  bool eval_averaged = false;      // ALEPPO_OPT_EVAL_PARAMS: the evaluation lanes act on the averaged set
   // ---- aleppo_snapshot_take / aleppo_snapshot_import: the caller's third parameter set, and aleppo_policy_diff's scratch
   // (policy_diff_plan); each is allocated on first use and never again, nothing is enqueued for them on a context that
   // never makes the calls
-  bool snap_on = false;            // a take or an import has succeeded
-  float *Ps = nullptr;             // fp32, internal layout, L.total() floats
-  void *Psc = nullptr;             // compute copy of Ps in T; == Ps for fp32
+  ParamSet snapshot;
   void *pd_scratch = nullptr;
   // ---- aleppo_refresh_advantages: the second values plane, RT [T+1][E] time-major like values_tm (which it never
   // replaces), and the statistics' scratch; each is allocated on first use and never again, nothing is enqueued for them on
@@ -601,7 +603,7 @@ void launch_policy_diff_stats(hipStream_t s, const PolicyDiffPlan &pl, void *scr
 // aleppo_recycle_units / aleppo_recycle_dormant (recycle.hip).  mask: uint8 [160 + H] in device memory, 4-byte aligned, in
 // the unit order of aleppo_activation_stats.  launch_recycle_mask forms it from that entry point's device-side unit table
 // (mask[u] = layer bit of u in layers && SCORE_u <= tau); launch_recycle is the one pass over P / M1 / M2 in the internal
-// layout (key: splitmix64 of the call's key); the caller rebuilds the derived copies (refresh_compute_copies).
+// layout (key: splitmix64 of the call's key); the caller rebuilds the derived copies (params_rewritten).
 void launch_recycle_mask(hipStream_t s, const double *units_dev, int H, double tau, int layers, uint8_t *mask);
 void launch_recycle(hipStream_t s, const ParamLayout &L, const uint8_t *mask, unsigned long long key, bool keep_moments,
                     float *P, float *M1, float *M2);
