@@ -77,6 +77,9 @@ BWD_TENSORS = dict(conv1=1, conv2=2, conv3=4, fc=8, dfc=16, dconv3=32, dconv2=64
 BWD_SHAPE_OF = dict(conv1="conv1", conv2="conv2", conv3="conv3", fc="fc", dfc="fc", dconv3="conv3", dconv2="conv2",
                     dconv1="conv1")
 ACT_UNIT_COLS, ACT_LAYER_COLS = 5, 8
+# aleppo_export_acting: the outputs in argument order with their aleppo_acting_tensor bits (Engine.export_acting)
+ACTING_TENSORS = dict(conv1=1, conv2=2, conv3=4, fc_parts=8)
+FC_SPLITS = 7
 ACT_UNIT_STATS = dict(mean_abs=0, positive_fraction=1, max_abs=2, score=3, nonfinite=4)
 ACT_LAYER_STATS = dict(units=0, elements=1, mean_abs=2, positive_fraction=3, max_abs=4, dead=5, dormant=6, nonfinite=7)
 # aleppo_recycle_units / aleppo_recycle_dormant: the layer bits, the flags and the rows of counts (Engine.recycle_units /
@@ -164,6 +167,8 @@ OPT_EVAL_PARAMS = 25
 # decoupled weight decay and the pull toward the anchor inside the optimizer step, each as its binary32 bit pattern
 # (Engine.set_regularization / Engine.regularization)
 OPT_WEIGHT_DECAY, OPT_ANCHOR_COEF = 26, 27
+# test hook: the fused bf16 acting launch also stores conv1 / conv2 for Engine.export_acting
+OPT_ACT_STORE = 28
 REG_OPTIONS = dict(weight_decay=OPT_WEIGHT_DECAY, anchor_coef=OPT_ANCHOR_COEF)
 HYPER_OPTIONS = dict(clip_param=OPT_CLIP_PARAM, value_clip_range=OPT_VALUE_CLIP_RANGE,
                      value_loss_coef=OPT_VALUE_LOSS_COEF, entropy_coef=OPT_ENTROPY_COEF,
@@ -195,7 +200,7 @@ EXPORTS = [
     "aleppo_export_reward_scale", "aleppo_import_reward_scale", "aleppo_reward_scale",
     "aleppo_export_rollout_state", "aleppo_import_rollout_state", "aleppo_state_digest",
     "aleppo_tensor_stats",
-    "aleppo_forward_activations", "aleppo_activation_stats", "aleppo_export_backward",
+    "aleppo_forward_activations", "aleppo_activation_stats", "aleppo_export_backward", "aleppo_export_acting",
     "aleppo_recycle_units", "aleppo_recycle_dormant",
     "aleppo_ema_open", "aleppo_ema_update", "aleppo_ema_read", "aleppo_ema_export", "aleppo_ema_import",
     "aleppo_saliency_tables", "aleppo_saliency", "aleppo_saliency_perturbed",
@@ -901,6 +906,27 @@ class Engine:
         self._c(lib().aleppo_export_backward(self._ctx, C.c_int64(cap), *[_ptr(out.get(t)) for t in BWD_TENSORS],
                                              C.byref(n), C.byref(stored)))
         return ({t: a[:n.value] for t, a in out.items() if stored.value & BWD_TENSORS[t]}, int(n.value),
+                int(stored.value))
+
+    def export_acting(self, tensors=tuple(ACTING_TENSORS), capacity=None):
+        """aleppo_export_acting: ({name: float32 array}, n, stored) of what the rollout's last acting forward left - conv1
+        [n,32,20,20] and conv2 [n,64,9,9] where the route stored them (OPT_ACT_STORE on the fused bf16 launch), conv3
+        [n,64,7,7] and fc_parts [FC_SPLITS,n,H], the fc layer's split-K slices; stored: the ACTING_TENSORS bits.  A tensor
+        that was asked for and not stored is left out of the dict.  capacity: the samples to make room for (default E)."""
+        tensors = tuple(tensors)
+        if any(t not in ACTING_TENSORS for t in tensors):
+            raise AleppoInvalidArgument(f"tensors must be a subset of {tuple(ACTING_TENSORS)}")
+        cap = int(capacity) if capacity is not None else self.E
+        room = max(cap, 0)
+        out = {t: np.zeros((FC_SPLITS, room, self.H) if t == "fc_parts" else (room,) + ACT_LAYER_SHAPES[t], np.float32)
+               for t in tensors}
+        n, stored = C.c_int64(0), C.c_uint32(0)
+        self._c(lib().aleppo_export_acting(self._ctx, C.c_int64(cap), *[_ptr(out.get(t)) for t in ACTING_TENSORS],
+                                           C.byref(n), C.byref(stored)))
+        m = int(n.value)
+        if "fc_parts" in out:  # (packed with n, at the front of its room)
+            out["fc_parts"] = out["fc_parts"].ravel()[:FC_SPLITS * m * self.H].reshape(FC_SPLITS, m, self.H)
+        return ({t: (a if t == "fc_parts" else a[:m]) for t, a in out.items() if stored.value & ACTING_TENSORS[t]}, m,
                 int(stored.value))
 
     def activation_stats(self, observations=None, tau=0.025, raw=False):

@@ -1,7 +1,8 @@
 // api_acts.hip - C ABI (include/aleppo.h), the representation: aleppo_forward_activations, aleppo_activation_stats,
-// aleppo_export_backward.  The first two run the network over a SampleSource (api_internal.hpp), as aleppo_forward does,
-// and then only read a1 / a2 / a3 / h; the third runs nothing and reads what the last update left there and in dh / dz3 /
-// dz2 / dz1.  Nothing here touches what the rollout or a captured update can observe.
+// aleppo_export_backward, aleppo_export_acting.  The first two run the network over a SampleSource (api_internal.hpp), as
+// aleppo_forward does, and then only read a1 / a2 / a3 / h; the third runs nothing and reads what the last update left there
+// and in dh / dz3 / dz2 / dz1, the fourth what the rollout's last acting forward left in a1 / a2 / a3 / hpart.  Nothing here
+// touches what the rollout or a captured update can observe.
 #include "api_internal.hpp"
 
 using namespace aleppo;
@@ -93,6 +94,53 @@ extern "C" int aleppo_export_backward(aleppo_ctx *c, int64_t capacity, float *co
   if (stored)
     *stored = ALEPPO_BWD_CONV1 | ALEPPO_BWD_CONV2 | ALEPPO_BWD_CONV3 | ALEPPO_BWD_FC | ALEPPO_BWD_DFC | ALEPPO_BWD_DCONV3 |
               ALEPPO_BWD_DCONV2 | (m.dz1 ? ALEPPO_BWD_DCONV1 : 0);
+  return ALEPPO_OK;
+}
+
+// What the rollout's last acting forward left (Ctx::acted): a1 / a2 where the route stored them, a3 and the split-K slices
+// of fc, read and converted, nothing else - the acting twin of aleppo_export_backward, with its staging.
+static_assert(ALEPPO_FC_SPLITS == FC_SPLITS, "include/aleppo.h states the number of split-K slices");
+extern "C" int aleppo_export_acting(aleppo_ctx *c, int64_t capacity, float *conv1, float *conv2, float *conv3,
+                                    float *fc_parts, int64_t *n, uint32_t *stored) {
+  CHECK_CTX(c);
+  if (!conv1 && !conv2 && !conv3 && !fc_parts)
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "export_acting: at least one output must be given");
+  const Ctx::ActMark m = c->acted;
+  if (m.n <= 0)
+    return set_err(c, ALEPPO_ERR_RUNTIME,
+                   "export_acting: no acting forward has run, or something else has run the network or replaced the "
+                   "parameters since the last one");
+  if (capacity < m.n)
+    return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT, "export_acting: capacity is smaller than num_envs");
+  const size_t ns = (size_t)m.n;
+  const size_t per[3] = {(size_t)A1_PIX * A1_C, (size_t)A2_PIX * A2_C, (size_t)A3_PIX * A3_C};
+  struct Conv {
+    int layer;
+    const void *src;
+    float *dst;
+  } const convs[3] = {{0, m.a12 ? c->a1 : nullptr, conv1}, {1, m.a12 ? c->a2 : nullptr, conv2}, {2, c->a3, conv3}};
+  size_t need = 0;
+  for (const Conv &t : convs)
+    if (t.src && t.dst)
+      need = std::max(need, ns * per[t.layer] * 4);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (need)
+    HIPCHK(c, grow(c, &c->ax_buf, &c->ax_cap, need, ALLOC_RAW));
+  for (const Conv &t : convs) {
+    if (!t.src || !t.dst)
+      continue;
+    launch_act_export(c->stream, c->prec, t.layer, t.src, c->ax_buf, (long)ns);
+    HIPCHK(c, hipMemcpyAsync(t.dst, c->ax_buf, ns * per[t.layer] * 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  if (fc_parts) // fp32 already, [FC_SPLITS][n][H] with n = E: one copy
+    HIPCHK(c, hipMemcpyAsync(fc_parts, c->hpart, (size_t)FC_SPLITS * ns * c->H * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  CHECK_ASYNC(c);
+  if (n)
+    *n = m.n;
+  if (stored)
+    *stored = ALEPPO_ACTING_CONV3 | ALEPPO_ACTING_FC_PARTS | (m.a12 ? ALEPPO_ACTING_CONV1 | ALEPPO_ACTING_CONV2 : 0);
   return ALEPPO_OK;
 }
 

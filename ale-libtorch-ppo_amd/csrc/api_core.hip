@@ -220,6 +220,7 @@ void prof_end(Ctx *c, int cls, hipStream_t st) { // same stream as the matching 
 // returns the number of split-K partial slabs of h (1 unless max_parts allows the pipelined fc kernel to split)
 int net_forward(Ctx *c, const ParamView &pv, const uint32_t *obs, SampleMap map, long ns, int max_parts) {
   c->bwd.B = 0; // a1 / a2 / a3 / h no longer hold an update's last minibatch (aleppo_train sets the mark after its last)
+  acted_clear(c);
   if (c->prec == ALEPPO_BF16 && use_patch_kernels() && tuning().fused_fwd) { // one launch: a1 / a2 are only written
     prof_begin(c, ALEPPO_K_CONV_FWD);
     patch_fwd_fused(c->stream, obs, map, Pcw(c, pv, P_W1), Pf(c, pv, P_B1), Pcw(c, pv, P_W2), Pf(c, pv, P_B2),
@@ -273,6 +274,7 @@ void params_rewritten(Ctx *c) {
   launch_pack_dgrad(c->stream, c->P, c->L, c->W2d, c->W3d, c->WfcT, c->prec);
   c->pre_acted = -1;
   c->ts_step_valid = false;
+  acted_clear(c);
 }
 
 int export_flat(aleppo_ctx *c, const float *dev, float *flat, size_t count) {
@@ -364,6 +366,7 @@ int source_check_window(aleppo_ctx *c, const uint8_t *observations, int64_t firs
 int source_open(aleppo_ctx *c, const uint8_t *observations, int64_t first, int64_t n, SampleSource *src) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->pre_acted = -1;
+  acted_clear(c);
   if (!observations) { // sample n = e*T + t of the batch lives in slot (e, t) of obs
     *src = SampleSource{c->obs, train_map(c, (long)first), n ? (long)n : c->batch_n - (long)first};
     return ALEPPO_OK;
@@ -752,6 +755,12 @@ extern "C" int aleppo_set_option(aleppo_ctx *c, int option, int value) {
     c->tune.fused_act = value; // 0: never, 1: where it is faster (default), 2: always
   else if (option == ALEPPO_OPT_FUSED_FWD)
     c->tune.fused_fwd = value != 0;
+  else if (option == ALEPPO_OPT_ACT_STORE) {
+    if (value != 0 && value != 1)
+      return set_err(c, ALEPPO_ERR_INVALID_ARGUMENT,
+                     "ALEPPO_OPT_ACT_STORE: 0 (off) or 1 (the fused acting launch also stores conv1 / conv2)");
+    c->act_store = value != 0;
+  }
   else if (option == ALEPPO_OPT_FUSED_BWD)
     c->tune.fused_bwd = value; // 0: never, 1: at minibatches >= 2048 samples (default), 2: always
   else if (option == ALEPPO_OPT_DEBUG_NO_PUBLISH)
@@ -850,6 +859,7 @@ extern "C" int aleppo_get_option(aleppo_ctx *c, int option, int64_t *value) {
   case ALEPPO_OPT_FC_PIPE: *value = c->tune.fc_pipe; break;
   case ALEPPO_OPT_FUSED_ACT: *value = c->tune.fused_act; break;
   case ALEPPO_OPT_FUSED_FWD: *value = c->tune.fused_fwd; break;
+  case ALEPPO_OPT_ACT_STORE: *value = c->act_store; break;
   case ALEPPO_OPT_FUSED_BWD: *value = c->tune.fused_bwd; break;
   case ALEPPO_OPT_UPDATE_GRAPH: *value = c->graph_replays; break;
   case ALEPPO_OPT_MINIBATCH_SHUFFLE: *value = c->shuffle; break;

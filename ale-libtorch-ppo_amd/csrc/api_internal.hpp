@@ -148,6 +148,9 @@ constexpr const char *NO_ANCHOR = "no anchor: call aleppo_anchor_take or aleppo_
 // dgrad weights are rebuilt on the main stream, and what aleppo_step pre-computed (pre_acted) and aleppo_tensor_stats'
 // last step (ts_step_valid) are forgotten
 void params_rewritten(Ctx *c);
+// the acting scratch (a1 .. a3 / hpart) no longer holds the rollout's last acting forward on the parameters as they stand:
+// aleppo_export_acting has nothing to read (net_forward, source_open, the update, params_rewritten, an imported rollout state)
+inline void acted_clear(Ctx *c) { c->acted = Ctx::ActMark(); }
 // a vector in the internal layout (device) -> the caller's flat array in the reference's order, with aleppo_export_params'
 // count check; waits for the stream
 int export_flat(aleppo_ctx *c, const float *dev, float *flat, size_t count);

@@ -18,12 +18,19 @@ void aleppo::act_forward(aleppo_ctx *c, const ParamView &pv, uint32_t *obs, Samp
     if (profiled)
       prof_end(c, cls);
   };
-  if (c->prec == ALEPPO_BF16 && use_patch_kernels()) { // one launch: a1/a2 never leave LDS
+  const bool rollout = a3 == c->a3; // (the evaluation lanes bring scratch of their own: no mark, no ALEPPO_OPT_ACT_STORE)
+  if (c->prec == ALEPPO_BF16 && use_patch_kernels()) { // one launch: a1/a2 never leave LDS (but ALEPPO_OPT_ACT_STORE)
+    const bool store = rollout && c->act_store;
     begin(ALEPPO_K_CONV1_FWD);
     patch_act_convs(c->stream, obs, map, Pcw(c, pv, P_W1), Pf(c, pv, P_B1), Pcw(c, pv, P_W2), Pf(c, pv, P_B2),
-                    Pcw(c, pv, P_W3), Pf(c, pv, P_B3), a3, n);
+                    Pcw(c, pv, P_W3), Pf(c, pv, P_B3), a3, n, 0, nullptr, nullptr, nullptr, 0, nullptr,
+                    store ? a1 : nullptr, store ? a2 : nullptr);
     end(ALEPPO_K_CONV1_FWD);
+    if (rollout)
+      c->acted = Ctx::ActMark{n, store};
   } else {
+    if (rollout)
+      c->acted = Ctx::ActMark{n, true};
     begin(ALEPPO_K_CONV1_FWD);
     conv1_fwd(c->stream, c->prec, obs, map, Pcw(c, pv, P_W1), Pf(c, pv, P_B1), a1, n);
     end(ALEPPO_K_CONV1_FWD);
@@ -264,7 +271,8 @@ int aleppo::step_enqueue(aleppo_ctx *c, const uint8_t *df, int kind, int locatio
     prof_begin(c, ALEPPO_K_ACT_FUSED);
     patch_act_convs(c->stream, c->obs, map, Pcw(c, P_W1), Pf(c, P_B1), Pcw(c, P_W2), Pf(c, P_B2), Pcw(c, P_W3),
                     Pf(c, P_B3), c->a3, E, kind == ALEPPO_FRAMES_RAW_PAIR ? 2 : 1, df, c->lut, sb, -(long)FRAME_PIX,
-                    start_dev);
+                    start_dev, c->act_store ? c->a1 : nullptr, c->act_store ? c->a2 : nullptr);
+    c->acted = Ctx::ActMark{E, c->act_store};
     prof_end(c, ALEPPO_K_ACT_FUSED);
     prof_begin(c, ALEPPO_K_FC_FWD);
     fc_fwd_splitk(c->stream, c->prec, c->a3, Pcw(c, P_WFC), c->hpart, E, c->H);

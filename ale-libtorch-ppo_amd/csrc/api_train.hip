@@ -138,6 +138,7 @@ static int plan_update(aleppo_ctx *c, int epochs, int M, UpdatePlan *plan) {
                    "ALEPPO_OPT_ANCHOR_COEF > 0 needs an anchor: call aleppo_anchor_take or aleppo_anchor_import first");
   c->pre_acted = -1; // the update's activations overwrite the acting scratch, and the weights change
   c->bwd.B = 0;      // (aleppo_export_backward: valid again once this update has run)
+  acted_clear(c);    // (aleppo_export_acting: nothing to read until the next acting forward)
   if (N % M != 0)
     return set_err(c, ALEPPO_ERR_RUNTIME, "Batch size must be divisible by num_mini_batches"); // train.h:140-143
   const long B = N / M;

@@ -292,6 +292,15 @@ struct Ctx {
     int hparts = 1;
     bool dz1 = false;
   } bwd, bwd_enq, bwd_graph;
+  // ---- aleppo_export_acting: host marks only, like bwd.  What the last acting forward of the rollout (aleppo_act's,
+  // aleppo_step's pre-computed one, aleppo_finish_rollout's bootstrap) left in a1 .. a3 / hpart: its sample count (0: nothing
+  // to export) and whether the route stored a1 / a2.  act_forward on the rollout's scratch and aleppo_step's fused launch
+  // set it; whatever else runs the network in that scratch or replaces the parameters clears it (acted_clear)
+  struct ActMark {
+    int n = 0;
+    bool a12 = false;
+  } acted;
+  bool act_store = false; // ALEPPO_OPT_ACT_STORE: the fused acting launch also writes a1 / a2 (act_conv_kernel<MODE, true>)
   // ---- aleppo_feature_rank: the Gram blocks, column sums, split partials and row flags (allocated on first use; its size
   // is a function of (H, maxB))
   void *fr_scratch = nullptr;
@@ -682,7 +691,8 @@ int patch_conv_bwd_fused(hipStream_t s, const void *dz2, const void *a1, const u
 void patch_act_convs(hipStream_t s, uint32_t *obs, SampleMap map, const void *W1, const float *b1, const void *W2,
                      const float *b2, const void *W3, const float *b3, void *a3, long ns, int ingest_mode = 0,
                      const uint8_t *frames = nullptr, const uint8_t *lut = nullptr, const StartBits *sbits = nullptr,
-                     long src_delta = 0, const uint8_t *start_bytes = nullptr);
+                     long src_delta = 0, const uint8_t *start_bytes = nullptr, void *a1_store = nullptr,
+                     void *a2_store = nullptr); // a1_store / a2_store (both or neither): the storing instantiation
 int patch_conv1_wgrad(hipStream_t s, const void *dz1, const uint32_t *obs, SampleMap map, float *sw, float *sb,
                       long ns);
 int patch_conv2_wgrad(hipStream_t s, const void *dz2, const void *a1, float *sw, float *sb, long ns);

@@ -447,6 +447,15 @@ struct ActIngestParams {
                               // the emulator has produced them (aleppo_arm_step)
 };
 
+// act_conv_kernel<MODE, true, ActStoreParams> alone (ALEPPO_OPT_ACT_STORE, the test hook behind aleppo_export_acting): where
+// conv1 / conv2 also write their packed results, in the training layout [ns][400][32] / [ns][81][64].  A third kernel
+// argument that only the storing instantiations HAVE (a parameter pack, empty otherwise): the production kernels keep
+// their two arguments, so P, G and the launch's hidden arguments stay where they were (even an empty record would move
+// the hidden ones by eight bytes).
+struct ActStoreParams {
+  bf16 *a1, *a2;
+};
+
 // Acting phases use ONE 16-channel atom per wave (8 waves = MA channel atoms x 8/MA pixel lanes): the weights
 // of all three layers then fit in registers together (8 + 16 + 18 fragments = 168 VGPRs) and are loaded once,
 // at kernel start, overlapped with staging the observation - no exposed weight round trip between phases.
@@ -516,8 +525,15 @@ constexpr size_t ACT_SMEM = 160 * 1024; // the rest of the LDS stages the layer 
 // at kernel start) and hands it to the waves through LDS regions that are free at that point: conv1's weights in the
 // tail of the LDS, conv2's in the tail + the stack region (dead after conv1), conv3's over stack + a1 (dead after
 // conv2).  Rows are padded by 16 B in LDS (conflict-free fragment reads).
-template <int MODE> // 0: act on the stored stack; 1: ingest a given 84x84 frame first; 2: ingest a raw frame pair first
-__global__ __launch_bounds__(512) void act_conv_kernel(ActConvParams P, ActIngestParams G) {
+// STORE: conv1 / conv2 additionally write what they hand on through LDS to S.a1 / S.a2 (the same packed words); everything
+// it adds sits behind if constexpr, so the three STORE = false instantiations are the kernels they were.
+// MODE 0: act on the stored stack; 1: ingest a given 84x84 frame first; 2: ingest a raw frame pair first
+template <int MODE, bool STORE = false, class... StoreArg> // StoreArg: ActStoreParams iff STORE
+__global__ __launch_bounds__(512) void act_conv_kernel(ActConvParams P, ActIngestParams G, StoreArg... store) {
+  static_assert(sizeof...(StoreArg) == (STORE ? 1 : 0), "the storing instantiation, and it alone, takes ActStoreParams");
+  [[maybe_unused]] ActStoreParams S{nullptr, nullptr};
+  if constexpr (STORE)
+    S = (store, ...);
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   bf16 *sx = reinterpret_cast<bf16 *>(smem), *s1 = sx + ACT_X_ELEMS, *s2 = s1 + ACT_A1_ELEMS;
   uint8_t *tail = smem + ACT_ACT_BYTES; // 60 KB
@@ -652,14 +668,18 @@ __global__ __launch_bounds__(512) void act_conv_kernel(ActConvParams P, ActInges
       }
     }
   };
-  auto conv1 = [&]() {
+  auto conv1 = [&](long n) {
     act_phase<LConv1Full>(sx, W1, 1.0f / 255.0f, wave, lane, [&](int q, int oc, u32x2 v) {
       *reinterpret_cast<u32x2 *>(s1 + (q / 20) * PatchGeom<LConv2Fwd>::RP + (q % 20) * LConv2Fwd::CP + oc) = v;
+      if constexpr (STORE)
+        *reinterpret_cast<u32x2 *>(S.a1 + n * (long)(A1_PIX * A1_C) + q * A1_C + oc) = v;
     });
   };
-  auto conv2 = [&]() {
+  auto conv2 = [&](long n) {
     act_phase<LConv2FwdSmall>(s1, W2, 1.0f, wave, lane, [&](int q, int oc, u32x2 v) {
       *reinterpret_cast<u32x2 *>(s2 + (q / 9) * PatchGeom<LConv3Fwd>::RP + (q % 9) * LConv3Fwd::CP + oc) = v;
+      if constexpr (STORE)
+        *reinterpret_cast<u32x2 *>(S.a2 + n * (long)(A2_PIX * A2_C) + q * A2_C + oc) = v;
     });
   };
   auto conv3 = [&](long n) {
@@ -705,7 +725,7 @@ __global__ __launch_bounds__(512) void act_conv_kernel(ActConvParams P, ActInges
     *reinterpret_cast<u32x4 *>(tail + img_off(tid + 512 * i, 32, A1::PITCH)) = S1[i];
   __syncthreads();
   W1.load_lds(tail + (wave % A1::MA) * 16 * A1::PITCH, lane);
-  conv1();
+  conv1(n);
   __syncthreads(); // stack and conv1's weight image are dead
 #pragma unroll
   for (int i = 0; i < 8; ++i) { // conv2 weights [64][512]: rows 0-31 -> tail, rows 32-63 -> stack region
@@ -718,7 +738,7 @@ __global__ __launch_bounds__(512) void act_conv_kernel(ActConvParams P, ActInges
     const int og = wave % A2::MA;
     W2.load_lds((og < 2 ? tail : smem - 32 * A2::PITCH) + og * 16 * A2::PITCH, lane);
   }
-  conv2();
+  conv2(n);
   __syncthreads(); // a1 and conv2's weight image are dead
 #pragma unroll
   for (int i = 0; i < 9; ++i) // conv3 weights [64][576] -> stack + a1 region
@@ -735,9 +755,9 @@ __global__ __launch_bounds__(512) void act_conv_kernel(ActConvParams P, ActInges
       ingest(n);
     widen();
     __syncthreads();
-    conv1();
+    conv1(n);
     __syncthreads();
-    conv2();
+    conv2(n);
     __syncthreads();
     conv3(n);
     __syncthreads();

@@ -173,12 +173,15 @@ void patch_conv2_dgrad(hipStream_t s, const void *dz2, const void *W2d, const vo
 void patch_act_convs(hipStream_t s, uint32_t *obs, SampleMap map, const void *W1, const float *b1, const void *W2,
                      const float *b2, const void *W3, const float *b3, void *a3, long ns, int ingest_mode,
                      const uint8_t *frames, const uint8_t *lut, const StartBits *sbits, long src_delta,
-                     const uint8_t *start_bytes) {
+                     const uint8_t *start_bytes, void *a1_store, void *a2_store) {
   static bool once = false;
   if (!once) {
     allow_smem(act_conv_kernel<0>, ACT_SMEM);
     allow_smem(act_conv_kernel<1>, ACT_SMEM);
     allow_smem(act_conv_kernel<2>, ACT_SMEM);
+    allow_smem(act_conv_kernel<0, true, ActStoreParams>, ACT_SMEM);
+    allow_smem(act_conv_kernel<1, true, ActStoreParams>, ACT_SMEM);
+    allow_smem(act_conv_kernel<2, true, ActStoreParams>, ACT_SMEM);
     once = true;
   }
   ActConvParams P{obs, map, static_cast<const bf16 *>(W1), static_cast<const bf16 *>(W2), static_cast<const bf16 *>(W3),
@@ -192,7 +195,15 @@ void patch_act_convs(hipStream_t s, uint32_t *obs, SampleMap map, const void *W1
     G.sbits = *sbits;
   G.start_bytes = start_bytes;
   const dim3 g((unsigned)std::min<long>(ns, num_cus())), b(512);
-  if (ingest_mode == 1)
+  if (a1_store && a2_store) { // ALEPPO_OPT_ACT_STORE: the same launch, a1 / a2 written as well
+    const ActStoreParams S{static_cast<bf16 *>(a1_store), static_cast<bf16 *>(a2_store)};
+    if (ingest_mode == 1)
+      hipLaunchKernelGGL((act_conv_kernel<1, true, ActStoreParams>), g, b, ACT_SMEM, s, P, G, S);
+    else if (ingest_mode == 2)
+      hipLaunchKernelGGL((act_conv_kernel<2, true, ActStoreParams>), g, b, ACT_SMEM, s, P, G, S);
+    else
+      hipLaunchKernelGGL((act_conv_kernel<0, true, ActStoreParams>), g, b, ACT_SMEM, s, P, G, S);
+  } else if (ingest_mode == 1)
     hipLaunchKernelGGL(act_conv_kernel<1>, g, b, ACT_SMEM, s, P, G);
   else if (ingest_mode == 2)
     hipLaunchKernelGGL(act_conv_kernel<2>, g, b, ACT_SMEM, s, P, G);

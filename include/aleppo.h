@@ -353,7 +353,15 @@ int aleppo_tensor_stats(aleppo_ctx *ctx, int sections, double *out, size_t count
  * captured stream bit-exactly, or NULL for the built-in counter-based generator.
  * *actions_pinned: int64 [E] in page-locked host memory owned by ctx, valid when the call returns and
  * until the next aleppo_act; env worker threads may read it concurrently (replaces the per-env
- * actions[i].item<int64_t>() of rollout.cc:312-313).  Stores logits/values for slot t. */
+ * actions[i].item<int64_t>() of rollout.cc:312-313).  Stores logits/values for slot t.
+ * Built-in generator (noise == NULL): Philox4x32-10 under the key config.seed itself (key words seed lo, seed hi; the
+ *   evaluation lanes' key differs, see aleppo_eval_act).  Counter words { n lo, n hi, e, k / 4 } for environment e and
+ *   action k, output words c[0..3]: q_k = -logf(U(c[k % 4])), U(x) = ((x >> 8) + 0.5) / 2^24 in fp32.
+ *   n is the acting counter: 0 at aleppo_create, + 1 for EVERY acting head that is enqueued, whether it draws or takes the
+ *   caller's noise - each aleppo_act (also the one aleppo_arm_step enqueues ahead, and each slot of aleppo_replay_rollout
+ *   and aleppo_env_rollout) and aleppo_finish_rollout's bootstrap call, whose draw is discarded.  A rollout of T slots
+ *   therefore uses n0 .. n0 + T - 1 for its slots and n0 + T for the bootstrap, and the next rollout starts at n0 + T + 1.
+ *   The counter is words[0] of aleppo_export_rollout_state. */
 int aleppo_act(aleppo_ctx *ctx, const float *noise, const int64_t **actions_pinned);
 
 /* Rollout::update_observations (rollout.cc:184-196) fused with Buffer::add's observation copy
@@ -514,6 +522,38 @@ typedef enum {
 } aleppo_bwd_tensor;
 int aleppo_export_backward(aleppo_ctx *ctx, int64_t capacity, float *conv1, float *conv2, float *conv3, float *fc,
                            float *dfc, float *dconv3, float *dconv2, float *dconv1, int64_t *n, uint32_t *stored);
+
+/* What the LAST ACTING FORWARD of the rollout left in the context's scratch: what a per-link check of the acting path starts
+ * from (tests/acting_ref.py).  That forward is aleppo_act's, the one aleppo_step pre-computed for the coming slot (fused
+ * ingest: an export between aleppo_step and aleppo_act returns the coming slot's), or aleppo_finish_rollout's bootstrap;
+ * aleppo_env_rollout's slots are aleppo_act's.  A test hook like aleppo_export_backward: it runs nothing but conversion
+ * kernels and copies, into the staging aleppo_forward_activations uses, and writes nothing the rollout or the update reads.
+ * The acting calls enqueue what they enqueued before and only note on the host that, and with how many samples, they ran.
+ * Outputs, host float, each may be NULL, at least one must be given; n = num_envs samples are written, `capacity` (>= n) is
+ * the samples the conv outputs have room for; tensor order and widening as aleppo_forward_activations:
+ *   conv1 [n,32,20,20]  conv2 [n,64,9,9]   where the route stored them: the generic and fp32 routes, and the fused bf16
+ *                                          launch under ALEPPO_OPT_ACT_STORE = 1; otherwise left untouched
+ *   conv3 [n,64,7,7]
+ *   fc_parts [ALEPPO_FC_SPLITS,n,H]        the split-K slices of the fc layer, fp32, no bias: slice z is the product of
+ *                                          columns [448 z, 448 (z + 1)) of conv3 in its stored order (pixel-major, channel
+ *                                          last: row z of the 7x7 map) with the matching fc weights.  The acting head adds
+ *                                          them to the fc bias one after the other, z = 0 .. 6, in fp32, and never stores
+ *                                          the sum.  Packed with n (not capacity); room for ALEPPO_FC_SPLITS * n * H floats
+ * *n = num_envs; *stored = the aleppo_acting_tensor bits of what was there to read.  n and stored may be NULL.
+ * The evaluation lanes have scratch of their own and are not exported (their bits equal aleppo_act's).
+ * Errors: no output, capacity < n: ALEPPO_ERR_INVALID_ARGUMENT; before any acting forward, after anything else has run the
+ * network in the scratch or replaced the parameters since (aleppo_train, aleppo_forward and every call that forwards as it
+ * does - the diagnostics, aleppo_refresh_advantages -, aleppo_load_params, a recycle, aleppo_shrink_perturb) or while a step
+ * is armed: ALEPPO_ERR_RUNTIME.  A refused call changes nothing. */
+#define ALEPPO_FC_SPLITS 7
+typedef enum {
+  ALEPPO_ACTING_CONV1 = 1,
+  ALEPPO_ACTING_CONV2 = 2,
+  ALEPPO_ACTING_CONV3 = 4,
+  ALEPPO_ACTING_FC_PARTS = 8
+} aleppo_acting_tensor;
+int aleppo_export_acting(aleppo_ctx *ctx, int64_t capacity, float *conv1, float *conv2, float *conv3, float *fc_parts,
+                         int64_t *n, uint32_t *stored);
 
 /* Per-unit and per-layer activation statistics, reduced on the device where the activations are: dormant units (Sokar et
  * al. 2023, "The Dormant Neuron Phenomenon in Deep RL"), dead units and firing rates (Moalla et al. 2024, "No
@@ -1556,7 +1596,13 @@ typedef enum {
      and does not include r.  With data parallelism EVERY RANK MUST SET THE SAME VALUES AND THE SAME ANCHOR before the same
      update (they are not exchanged: ranks that decay differently apply different steps and drift apart). */
   ALEPPO_OPT_WEIGHT_DECAY = 26,    /* wd, torch.optim.AdamW's weight_decay.  Valid: finite and >= 0 */
-  ALEPPO_OPT_ANCHOR_COEF = 27      /* la, the strength of the pull toward the anchor.  Valid: finite and >= 0 */
+  ALEPPO_OPT_ANCHOR_COEF = 27,     /* la, the strength of the pull toward the anchor.  Valid: finite and >= 0 */
+  ALEPPO_OPT_ACT_STORE = 28        /* test hook of aleppo_export_acting.  0 (default): the fused acting launch of a bf16
+                                      context keeps conv1 / conv2 in LDS.  1: a storing instantiation of the same kernel
+                                      also writes them to the activation scratch, in the training layout; conv3, the fc
+                                      slices, logits, values and actions keep their bits.  Any other value is
+                                      ALEPPO_ERR_INVALID_ARGUMENT; like every option it is refused while a step is armed.
+                                      The generic and fp32 routes store conv1 / conv2 anyway and do not read it */
 } aleppo_option;
 int aleppo_set_option(aleppo_ctx *ctx, int option, int value);
 /* Current value of an option; for ALEPPO_OPT_UPDATE_GRAPH the number of graph launches so far (0 = every update ran

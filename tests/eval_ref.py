@@ -5,7 +5,8 @@ The rules take the ENGINE's fp32 logits (read with aleppo_eval_read), so no forw
   epsilon_greedy(z, eps, uw)  u < eps ? min((int)(w * A), A - 1), w * A rounded once in fp32 : greedy
   sample(z, tau, q)         float64: e = exp((z - max z) * inv), inv = fp32(1 / tau); p = e / sum e; argmax p / q, and the
                             relative gap between the two largest p / q (the test skips a lane only when it is < 1e-5)
-philox4x32_10 / eval_noise restate the generator: key = seed ^ 0x4556414C4C414E45, counter words {n lo, n hi, lane, block}.
+philox4x32_10 / philox_noise restate the generator under any key, counter words {n lo, n hi, lane, block}; eval_noise is the
+lanes' stream, key = seed ^ 0x4556414C4C414E45 (aleppo_act's key is the seed itself: tests/acting_ref.py).
 """
 import numpy as np
 
@@ -55,10 +56,10 @@ def _unit(w):
     return ((w >> np.uint32(8)).astype(np.float32) + np.float32(0.5)) * np.float32(1.0 / 16777216.0)
 
 
-def eval_noise(seed, n, L, A, rule):
-    """the built-in draws of evaluation call n: rule "sample" -> Exp(1) q float32 [L, A] (up to logf's last bits: numpy's
-    float32 log), rule "epsilon" -> uniforms (u, w) float32 [L, 2] (exact)"""
-    key = (seed ^ EVAL_KEY_DOMAIN) & 0xFFFFFFFFFFFFFFFF
+def philox_noise(key, n, L, A, rule):
+    """the built-in draws of call n under the 64-bit key: rule "sample" -> Exp(1) q float32 [L, A] (up to logf's last bits:
+    numpy's float32 log), rule "epsilon" -> uniforms (u, w) float32 [L, 2] (exact)"""
+    key &= 0xFFFFFFFFFFFFFFFF
     k0, k1 = key & 0xFFFFFFFF, key >> 32
     nb = (A + 3) // 4 if rule == "sample" else 1
     lane, blk = np.meshgrid(np.arange(L, dtype=np.uint32), np.arange(nb, dtype=np.uint32), indexing="ij")
@@ -68,3 +69,8 @@ def eval_noise(seed, n, L, A, rule):
     if rule == "sample":
         return (-np.log(_unit(w[:, :A]))).astype(np.float32)
     return _unit(w[:, :2])
+
+
+def eval_noise(seed, n, L, A, rule):
+    """the built-in draws of evaluation call n: philox_noise under the lanes' key"""
+    return philox_noise(seed ^ EVAL_KEY_DOMAIN, n, L, A, rule)

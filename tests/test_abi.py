@@ -108,6 +108,7 @@ def test_option_and_location_constants_match_the_header(pkg):
                       ("ALEPPO_OPT_FUSED_ACT", pkg.OPT_FUSED_ACT), ("ALEPPO_OPT_GATE_TIMEOUT_MS", pkg.OPT_GATE_TIMEOUT_MS),
                       ("ALEPPO_OPT_UPDATE_GRAPH", pkg.OPT_UPDATE_GRAPH), ("ALEPPO_OPT_FUSED_FWD", pkg.OPT_FUSED_FWD), ("ALEPPO_OPT_FUSED_BWD", pkg.OPT_FUSED_BWD),
                       ("ALEPPO_OPT_SERIAL_UPDATE", pkg.OPT_SERIAL_UPDATE), ("ALEPPO_OPT_FORCE_COMM", pkg.OPT_FORCE_COMM),
+                      ("ALEPPO_OPT_ACT_STORE", pkg.OPT_ACT_STORE), ("ALEPPO_FC_SPLITS", pkg.FC_SPLITS),
                       ("ALEPPO_HOST_MAPPED", pkg.HOST_MAPPED), ("ALEPPO_ROLLOUT_FP16", pkg.ROLLOUT_FP16),
                       ("ALEPPO_ABI_VERSION", pkg.ABI_VERSION)):
         m = re.search(rf"\b{name}\s*=?\s*(\d+)", txt)

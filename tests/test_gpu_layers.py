@@ -6,8 +6,9 @@ docstring): (a) every bf16 element inside bf16(relu(z -+ eps)), (b) the per-chan
 bf16(relu(z)) under four times what the float32 reference evaluations show, (c) every fp32 element within four times the
 float32 reference evaluation's own error.  The logits and values of aleppo_forward on the same observations are checked
 against the exported fc in the same way.  Scope: the training-side forward kernels (conv_fwd_fused.hpp, conv_patch.hpp,
-gemm.hpp, gemm_pipe.hpp and the head forward).  The acting kernels (act_conv_kernel, act_head.hpp) export nothing and stay
-out of scope here; tests/test_gpu_shapes.py part B checks their outputs.
+gemm.hpp, gemm_pipe.hpp and the head forward).  The acting kernels (act_conv_kernel, fc_act_kernel, act_head.hpp) are checked
+in the same way, link by link on aleppo_export_acting, by tests/test_gpu_acting.py; tests/test_gpu_shapes.py part B checks
+their outputs end to end.
 
 Measured on the MI355X (how much room the kernels really use).  On every bf16 row all routes - fused, three launches,
 generic, each with the pipelined and the small-tile fc - gave the same numbers:
