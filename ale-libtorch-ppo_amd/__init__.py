@@ -109,6 +109,12 @@ PD_STATS = dict(rows=0, nonfinite_rows=1, churn=2, mean_kl_ab=3, max_kl_ab=4, me
                 mean_abs_dv=8, max_abs_dv=9, rms_dv=10, mean_entropy_a=11, mean_entropy_b=12, mean_feature_cos=13,
                 min_feature_cos=14, feature_rel_change=15)
 PD_COLUMNS = dict(kl_ab=0, kl_ba=1, tv=2, dv=3, cos=4, dh2=5, g_a=6, g_b=7)
+# gradient probes: the slots, aleppo_grad_take's sources and the rows of a Gram - the 12 tensors, then the whole model
+# (Engine.grad_probe / grad_take / grad_vector / load_grad / grad_gram)
+GRAD_SLOTS = 4
+GRAD_SRC_EXP_AVG, GRAD_SRC_PARAM_DELTA = 0, 1
+GRAD_SOURCES = dict(exp_avg=GRAD_SRC_EXP_AVG, delta=GRAD_SRC_PARAM_DELTA)
+GRAM_NAMES = TENSOR_NAMES[:12] + ("all",)
 # aleppo_refresh_advantages: the indices of its ALEPPO_REFRESH_STATS_COUNT doubles - the ten of BATCH_STATS on the fresh
 # values, then aleppo_refresh_stat (Engine.refresh_advantages / Engine.refresh_values)
 REFRESH_STATS_COUNT = 13
@@ -207,6 +213,7 @@ EXPORTS = [
     "aleppo_feature_rank",
     "aleppo_snapshot_take", "aleppo_snapshot_export", "aleppo_snapshot_import", "aleppo_policy_diff",
     "aleppo_refresh_advantages", "aleppo_refresh_read",
+    "aleppo_grad_probe", "aleppo_grad_take", "aleppo_grad_export", "aleppo_grad_import", "aleppo_grad_gram",
     "aleppo_anchor_take", "aleppo_anchor_import", "aleppo_anchor_export", "aleppo_shrink_perturb",
     "aleppo_env_open", "aleppo_env_rollout", "aleppo_env_export_state", "aleppo_env_import_state", "aleppo_env_read",
     "aleppo_eval_env_open", "aleppo_eval_env_run", "aleppo_eval_env_export_state", "aleppo_eval_env_import_state",
@@ -240,6 +247,11 @@ class SaliencyConfig(C.Structure):
 
 class FeatureRankConfig(C.Structure):
     _fields_ = [("delta", C.c_float), ("eps", C.c_float), ("centered", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GradProbeConfig(C.Structure):
+    _fields_ = [("policy_term", C.c_int32), ("value_loss_coef", C.c_float), ("entropy_coef", C.c_float),
+                ("reserved", C.c_int32)]
 
 
 class EnvConfig(C.Structure):
@@ -1047,6 +1059,130 @@ class Engine:
                                          C.c_size_t(0 if tr is None else tr.size), _ptr(out),
                                          C.c_size_t(0 if out is None else out.size)))
         return dict(stats={k: float(stats[i]) for k, i in PD_STATS.items()}, per_sample=ps, transitions=tr, outputs=out)
+
+    # -- gradient probes --
+    def grad_probe(self, slot, first=0, n=None, policy=True, value_loss_coef=None, entropy_coef=None):
+        """aleppo_grad_probe: gradient slot `slot` = the gradient train() would hand the optimizer for the minibatch of
+        samples [first, first + n) of the batch (n=None: to its end), at the live parameters, without a step.  With
+        policy=True and both coefficients None the loss is the one train() uses as the options stand (cfg = NULL); else
+        policy switches the policy term, and a coefficient left None is the current option's.  Returns the slice's
+        unmasked count.  Never a collective: this rank's slice."""
+        n = self._batch_n - first if n is None else n
+        cfg = None
+        if not policy or value_loss_coef is not None or entropy_coef is not None:
+            hyper = self.hyper()
+            cfg = GradProbeConfig(1 if policy else 0,
+                                  hyper["value_loss_coef"] if value_loss_coef is None else value_loss_coef,
+                                  hyper["entropy_coef"] if entropy_coef is None else entropy_coef, 0)
+        count = C.c_int64()
+        self._c(lib().aleppo_grad_probe(self._ctx, C.c_int(slot), C.c_int64(first), C.c_int64(n),
+                                        None if cfg is None else C.byref(cfg), C.byref(count)))
+        return int(count.value)
+
+    def grad_take(self, slot, source="exp_avg", set="snapshot"):
+        """aleppo_grad_take: slot = Adam's first moment as it stands ("exp_avg"), or float32(live - set) per element
+        ("delta", set "snapshot" or "averaged"); enqueued only"""
+        if source not in GRAD_SOURCES:
+            raise AleppoInvalidArgument(f"a gradient source is one of {tuple(GRAD_SOURCES)}")
+        which = self._set(set) if source == "delta" else 0
+        self._c(lib().aleppo_grad_take(self._ctx, C.c_int(slot), C.c_int(GRAD_SOURCES[source]), C.c_int(which)))
+
+    def grad_vector(self, slot):
+        """aleppo_grad_export: the slot as flat float32 in libtorch parameters() order"""
+        out = np.zeros(self.param_count, np.float32)
+        self._c(lib().aleppo_grad_export(self._ctx, C.c_int(slot), _ptr(out), C.c_size_t(out.size)))
+        return out
+
+    def load_grad(self, slot, flat):
+        """aleppo_grad_import: a flat float32 vector in libtorch parameters() order -> the slot"""
+        flat = _f32(flat).ravel()
+        self._c(lib().aleppo_grad_import(self._ctx, C.c_int(slot), _ptr(flat), C.c_size_t(flat.size)))
+
+    def grad_gram(self, slots, raw=False):
+        """aleppo_grad_gram: the inner products of the k = len(slots) named slots per tensor, reduced on the device in
+        double.  {tensor: float64 [k, k]} over GRAM_NAMES (the 12 tensors, then "all"), plus "nonfinite": {tensor: int},
+        the element indices left out because one of the slots is NaN / Inf there; raw=True: (float64 [13, k, k],
+        int64 [13])."""
+        idx = np.ascontiguousarray(slots, dtype=np.int32).ravel()
+        k = int(idx.size)
+        gram = np.zeros((TENSOR_STATS_ROWS, k, k), np.float64)
+        nf = np.zeros(TENSOR_STATS_ROWS, np.int64)
+        self._c(lib().aleppo_grad_gram(self._ctx, _ptr(idx), C.c_int(k), _ptr(gram), C.c_size_t(gram.size), _ptr(nf),
+                                       C.c_size_t(nf.size)))
+        if raw:
+            return gram, nf
+        out = {t: gram[r] for r, t in enumerate(GRAM_NAMES)}
+        out["nonfinite"] = {t: int(nf[r]) for r, t in enumerate(GRAM_NAMES)}
+        return out
+
+    @staticmethod
+    def _gram_rows(gram):
+        """(names, float64 [rows, k, k]) of what grad_gram returned in either form"""
+        if isinstance(gram, dict):
+            names = [t for t in gram if t != "nonfinite"]
+            return names, np.stack([np.asarray(gram[t], np.float64) for t in names])
+        g = np.asarray(gram[0] if isinstance(gram, tuple) else gram, np.float64)
+        return list(GRAM_NAMES[:g.shape[0]]), g
+
+    @staticmethod
+    def grad_cosines(gram):
+        """per tensor G_ij / sqrt(G_ii G_jj) of a Gram (grad_gram's dict, or a float64 [rows, k, k] array); NaN where a
+        norm is 0.  Host arithmetic only.  The same form as the argument."""
+        names, g = Engine._gram_rows(gram)
+        d = np.einsum("rii->ri", g)
+        den = np.sqrt(d[:, :, None] * d[:, None, :])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            cos = np.where(den > 0, g / den, np.nan)
+        return {t: cos[r] for r, t in enumerate(names)} if isinstance(gram, dict) else cos
+
+    @staticmethod
+    def noise_scale_from_gram(gram, b_small, b_big):
+        """McCandlish et al. 2018, Appendix A, per tensor from the Gram of (g_small, g_big), the gradients of nested slices
+        with b_small < b_big unmasked samples: |G|^2 = (b_big |g_big|^2 - b_small |g_small|^2) / (b_big - b_small),
+        S = (|g_small|^2 - |g_big|^2) / (1 / b_small - 1 / b_big), B_simple = S / |G|^2.  {"g2", "s", "b_simple"}, each
+        in the form of the argument.  Host arithmetic only."""
+        if not 0 < b_small < b_big:
+            raise AleppoInvalidArgument("the noise scale needs 0 < b_small < b_big unmasked samples")
+        names, g = Engine._gram_rows(gram)
+        small, big = g[:, 0, 0], g[:, 1, 1]
+        g2 = (b_big * big - b_small * small) / (b_big - b_small)
+        s = (small - big) / (1.0 / b_small - 1.0 / b_big)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            res = dict(g2=g2, s=s, b_simple=s / g2)
+        if isinstance(gram, dict):
+            return {k: {t: float(v[r]) for r, t in enumerate(names)} for k, v in res.items()}
+        return res
+
+    @staticmethod
+    def interference_from_gram(gram):
+        """from the Gram of the three pure probes (policy, value, entropy): their per-tensor norms and the three pairwise
+        cosines.  {"norms": {term: ...}, "cosines": {"policy_value", "policy_entropy", "value_entropy"}}, each entry in
+        the form of the argument.  Host arithmetic only."""
+        names, g = Engine._gram_rows(gram)
+        cos = Engine.grad_cosines(g)
+        form = (lambda v: {t: float(v[r]) for r, t in enumerate(names)}) if isinstance(gram, dict) else (lambda v: v)
+        return dict(norms={t: form(np.sqrt(g[:, i, i])) for i, t in enumerate(("policy", "value", "entropy"))},
+                    cosines=dict(policy_value=form(cos[:, 0, 1]), policy_entropy=form(cos[:, 0, 2]),
+                                 value_entropy=form(cos[:, 1, 2])))
+
+    def gradient_noise_scale(self, n_small, n_big, first=0, slots=(0, 1)):
+        """two probes (the loss as the options stand) on the nested slices [first, first + n_small) and [first, first +
+        n_big) into `slots`, then noise_scale_from_gram with their unmasked counts as the batch sizes: {"g2", "s",
+        "b_simple"} per tensor and for "all", plus "counts"."""
+        b_small = self.grad_probe(slots[0], first, n_small)
+        b_big = self.grad_probe(slots[1], first, n_big)
+        res = self.noise_scale_from_gram(self.grad_gram(slots), b_small, b_big)
+        res["counts"] = (b_small, b_big)
+        return res
+
+    def gradient_interference(self, first=0, n=None, slots=(0, 1, 2)):
+        """three probes on samples [first, first + n) into `slots` - the policy term alone {1, 0, 0}, the value term alone
+        {0, 1, 0}, the entropy term alone {0, 0, 1} - then interference_from_gram: the per-tensor norms and the three
+        pairwise cosines (policy_value < 0 in the trunk: the critic pulls against the actor there)."""
+        self.grad_probe(slots[0], first, n, policy=True, value_loss_coef=0.0, entropy_coef=0.0)
+        self.grad_probe(slots[1], first, n, policy=False, value_loss_coef=1.0, entropy_coef=0.0)
+        self.grad_probe(slots[2], first, n, policy=False, value_loss_coef=0.0, entropy_coef=1.0)
+        return self.interference_from_gram(self.grad_gram(slots))
 
     def refresh_advantages(self, source="live", stats=True):
         """aleppo_refresh_advantages: between two train() calls on one rollout batch, forward the batch and the post-rollout

@@ -1,5 +1,5 @@
 // api_internal.hpp - what the C ABI's translation units share (api_core.hip, api_rollout.hip, api_train.hip,
-// api_batch.hip, api_eval.hip, api_eval_env.hip, api_env.hip, api_rec.hip, api_state.hip, api_acts.hip, api_recycle.hip, api_ema.hip, api_saliency.hip, api_feature_rank.hip, api_policy_diff.hip, api_refresh.hip, api_reg.hip, api_ops.hip): the entry-point guard macros, the memory
+// api_batch.hip, api_eval.hip, api_eval_env.hip, api_env.hip, api_rec.hip, api_state.hip, api_acts.hip, api_recycle.hip, api_ema.hip, api_saliency.hip, api_feature_rank.hip, api_policy_diff.hip, api_refresh.hip, api_reg.hip, api_grad_probe.hip, api_ops.hip): the entry-point guard macros, the memory
 // ownership helpers (dalloc / halloc / grow over ctx_alloc / ctx_host_alloc / ctx_grow) and the other host-side helpers.
 // Host code only; the helpers are defined in api_core.hip unless noted.
 #pragma once
@@ -276,6 +276,13 @@ inline void rec_tick(Ctx *c, int source) {
   if (c->rec[source].open)
     c->rec[source].ordinal++;
 }
+// api_train.hip, for aleppo_grad_probe (api_grad_probe.hip): what aleppo_train's prologue and the gradient half of its
+// minibatch (enqueue_gradient) enqueue for ONE contiguous minibatch of n samples from batch sample `first`, on the routes a
+// minibatch of n samples takes, with the gradient landing in dst and conv1's slabs reduced into it.  Arguments already
+// checked.  blk: the probe's device block (common.hpp GP_*), uploaded - its count and, with policy and
+// ALEPPO_OPT_ADV_NORM_MINIBATCH, its advantage record are written here; !policy: the head goes through the
+// advantage-record entry point and reads the record as uploaded.  ps: [8][maxB] per-sample planes.  Never a collective.
+int grad_probe_enqueue(aleppo_ctx *c, long first, long n, bool policy, float *blk, float *ps, float *dst);
 extern const double RS_INITIAL[RS_BLOCK];
 int ensure_rs_storage(aleppo_ctx *c);
 bool rs_state_valid(const double stats[3]);

@@ -121,9 +121,39 @@ struct UpdatePlan {
   const float *hpd;
   int shuf_h, nblk_head, nblk_sq;
   size_t fs; // field stride of the per-sample metric arrays
+  // What the head kernel writes and reads per minibatch: the per-sample metric planes, the advantage statistics, beta and
+  // the exact-KL plane - the context's for aleppo_train, private ones for aleppo_grad_probe - and the batch sample the
+  // first minibatch starts at (0 for aleppo_train)
+  float *metric_ps, *kl_ps;
+  const float *advn_stats, *kl_beta;
+  long n0;
   float *sW1, *sB1, *sW2, *sB2, *sW3, *sB3, *sWfc, *sBfc, *sWh, *sBh; // split-K gradient slabs
   Planes pl;
 };
+
+// The kernel routes of a minibatch of p.B samples: the slabs, the grids of the head and the norm pass, one stream or two, the
+// fused or the split tail of the conv backward.  whole_cus: nothing else (an all-reduce) shares the CUs with the backward
+static void plan_routes(aleppo_ctx *c, UpdatePlan &p, bool whole_cus) {
+  const long B = p.B;
+  p.sW1 = c->slab + c->slab_off[0], p.sB1 = c->slab + c->slab_off[1], p.sW2 = c->slab + c->slab_off[2];
+  p.sB2 = c->slab + c->slab_off[3], p.sW3 = c->slab + c->slab_off[4], p.sB3 = c->slab + c->slab_off[5];
+  p.sWfc = c->slab + c->slab_off[6], p.sBfc = c->slab + c->slab_off[7], p.sWh = c->slab + c->slab_off[8];
+  p.sBh = c->slab + c->slab_off[9];
+  p.nblk_head = (int)std::min<long>(MAXS_HEAD, (B + 15) / 16);
+  p.nblk_sq = (int)std::min<size_t>(800, (c->L.off[P_W1] + 4095) / 4096); // + 129 conv1 chunks <= 1024 partials
+
+  // The three weight-gradient kernels (and the slab reduce of bucket 0) run on their own stream
+  // next to the dgrad chain (fc wgrad || fc dgrad, conv3 wgrad || conv3 dgrad, conv2 wgrad || conv2 dgrad -> conv1
+  // wgrad).  Every kernel is a latency-bound full-GPU persistent grid: co-scheduling fills the drain / ramp bubbles
+  // between dependent launches (everything on one stream measured 8.80 ms per update).
+  p.two = !c->serial_update; // (ALEPPO_OPT_SERIAL_UPDATE: profiling brackets every kernel on the stream it runs on)
+  // (Not with data parallelism: the fused kernel's 512-register workgroups need whole CUs, and bucket 0's all-reduce - whose
+  // RCCL kernels are resident on some of them by the time the dgrad chain gets there - is what the conv backward is meant to
+  // run BESIDE; the three launches share CUs with it, the fused kernel's workgroups on those CUs would start when it ends.)
+  p.bwd_fused = (c->tune.fused_bwd == 2 || (c->tune.fused_bwd == 1 && B >= 2048)) && c->prec == ALEPPO_BF16 &&
+                use_patch_kernels() && whole_cus;
+  p.sw = p.two ? c->wg_stream : p.s; // stream of the weight-gradient kernels
+}
 
 // Argument checks, storage, lazy stream creation and every flag decision of one call.
 static int plan_update(aleppo_ctx *c, int epochs, int M, UpdatePlan *plan) {
@@ -186,25 +216,10 @@ static int plan_update(aleppo_ctx *c, int epochs, int M, UpdatePlan *plan) {
   p.hpd = c->hyper_blk;
   p.shuf_h = feistel_half_width(N);
 
-  p.sW1 = c->slab + c->slab_off[0], p.sB1 = c->slab + c->slab_off[1], p.sW2 = c->slab + c->slab_off[2];
-  p.sB2 = c->slab + c->slab_off[3], p.sW3 = c->slab + c->slab_off[4], p.sB3 = c->slab + c->slab_off[5];
-  p.sWfc = c->slab + c->slab_off[6], p.sBfc = c->slab + c->slab_off[7], p.sWh = c->slab + c->slab_off[8];
-  p.sBh = c->slab + c->slab_off[9];
   p.fs = c->metric_cap;
-  p.nblk_head = (int)std::min<long>(MAXS_HEAD, (B + 15) / 16);
-  p.nblk_sq = (int)std::min<size_t>(800, (c->L.off[P_W1] + 4095) / 4096); // + 129 conv1 chunks <= 1024 partials
-
-  // The three weight-gradient kernels (and the slab reduce of bucket 0) run on their own stream
-  // next to the dgrad chain (fc wgrad || fc dgrad, conv3 wgrad || conv3 dgrad, conv2 wgrad || conv2 dgrad -> conv1
-  // wgrad).  Every kernel is a latency-bound full-GPU persistent grid: co-scheduling fills the drain / ramp bubbles
-  // between dependent launches (everything on one stream measured 8.80 ms per update).
-  p.two = !c->serial_update; // (ALEPPO_OPT_SERIAL_UPDATE: profiling brackets every kernel on the stream it runs on)
-  // (Not with data parallelism: the fused kernel's 512-register workgroups need whole CUs, and bucket 0's all-reduce - whose
-  // RCCL kernels are resident on some of them by the time the dgrad chain gets there - is what the conv backward is meant to
-  // run BESIDE; the three launches share CUs with it, the fused kernel's workgroups on those CUs would start when it ends.)
-  p.bwd_fused = (c->tune.fused_bwd == 2 || (c->tune.fused_bwd == 1 && B >= 2048)) && c->prec == ALEPPO_BF16 &&
-                use_patch_kernels() && !p.dp;
-  p.sw = p.two ? c->wg_stream : p.s; // stream of the weight-gradient kernels
+  p.metric_ps = c->metric_ps, p.kl_ps = c->kl_ps, p.advn_stats = c->advn_stats, p.kl_beta = c->kl_beta;
+  p.n0 = 0;
+  plan_routes(c, p, !p.dp);
 
   // the per-sample planes: position n0 + b of the batch, or of epoch ep's gathered planes (the storage above is final)
   Planes &pl = p.pl;
@@ -318,7 +333,7 @@ static void enqueue_head(aleppo_ctx *c, const UpdatePlan &p, int ep, int mb, int
   const Planes &pl = p.pl;
   const int mi = ep * p.M + mb, A = c->A;
   const size_t p0 = pl.offset(ep, mb), fs = p.fs;
-  float *const mps = c->metric_ps + (size_t)mi * p.B; // this minibatch's slice of every per-sample metric plane
+  float *const mps = p.metric_ps + (size_t)mi * p.B; // this minibatch's slice of every per-sample metric plane
   HeadTrainArgs ha{};
   ha.h = c->h;
   ha.Wh = Pf(c, P_WH);
@@ -342,9 +357,9 @@ static void enqueue_head(aleppo_ctx *c, const UpdatePlan &p, int ep, int mb, int
   ha.A = A;
   ha.hparts = hparts;
   ha.rt16 = c->rt16;
-  ha.advs = p.advn ? c->advn_stats + pl.record(ep, mb) * 4 : nullptr;
-  ha.klb = p.klpen ? c->kl_beta : nullptr;
-  ha.ps_kle = p.klpen ? c->kl_ps + (size_t)mi * p.B : nullptr;
+  ha.advs = p.advn ? p.advn_stats + pl.record(ep, mb) * 4 : nullptr;
+  ha.klb = p.klpen ? p.kl_beta : nullptr;
+  ha.ps_kle = p.klpen ? p.kl_ps + (size_t)mi * p.B : nullptr;
   launch_head_train(p.s, ha, p.hpd);
   prof_end(c, ALEPPO_K_HEAD);
 }
@@ -361,27 +376,27 @@ struct SegList {
 };
 // With two streams the weight-gradient stream reduces every slab group that is complete while the main stream runs the
 // last link of the dgrad chain; on one stream they stay listed for the reduce after it.
-static void reduce_beside(aleppo_ctx *c, const UpdatePlan &p, SegList &segs) {
+static void reduce_beside(aleppo_ctx *c, const UpdatePlan &p, SegList &segs, float *dst) {
   if (!p.two)
     return;
   prof_begin(c, ALEPPO_K_REDUCE, p.sw);
-  launch_reduce_slabs(p.sw, segs.seg, segs.n, c->G);
+  launch_reduce_slabs(p.sw, segs.seg, segs.n, dst);
   prof_end(c, ALEPPO_K_REDUCE, p.sw);
   segs.n = 0;
 }
 
 // The two tails of the conv backward, after conv3's dgrad and wgrad (S3 slices).  late0: bucket 0's slab groups where
 // they were not reduced early (empty with data parallelism).  Both leave in segs what is still to be reduced on the main
-// stream and return conv1's slice count in *S1.
+// stream and return conv1's slice count in *S1.  dst: the gradient vector the slab groups are reduced into.
 static int enqueue_conv_bwd_fused(aleppo_ctx *c, const UpdatePlan &p, const SampleMap &map, int S3,
-                                  const SegList &late0, SegList &segs, int *S1) {
+                                  const SegList &late0, SegList &segs, int *S1, float *dst) {
   const ParamLayout &L = c->L;
   // conv2 dgrad + conv2 wgrad + conv1 wgrad in ONE launch on the main stream (conv_bwd_fused.hpp: dz1 never leaves the
   // CU).  Meanwhile the weight-gradient stream reduces the slab groups that are complete (conv3, heads + fc).
   segs.add(ReduceSeg{p.sW3, S3, 64 * 576, (long)L.off[P_W3]});
   segs.add(ReduceSeg{p.sB3, S3, 64, (long)L.off[P_B3]});
   segs.add(late0);
-  reduce_beside(c, p, segs);
+  reduce_beside(c, p, segs, dst);
   prof_begin(c, ALEPPO_K_CONV_BWD);
   const int S2 = *S1 = patch_conv_bwd_fused(p.s, c->dz2, c->a1, c->obs, map, c->W2d, p.sW2, p.sB2, p.sW1, p.sB1, p.B);
   prof_end(c, ALEPPO_K_CONV_BWD);
@@ -390,7 +405,7 @@ static int enqueue_conv_bwd_fused(aleppo_ctx *c, const UpdatePlan &p, const Samp
   return ALEPPO_OK;
 }
 static int enqueue_conv_bwd_split(aleppo_ctx *c, const UpdatePlan &p, const SampleMap &map, int S3,
-                                  const SegList &late0, SegList &segs, int *S1) {
+                                  const SegList &late0, SegList &segs, int *S1, float *dst) {
   const ParamLayout &L = c->L;
   const int prec = c->prec;
   HIPCHK(c, fork_wgrad_stream(p, c->ev_dz2)); // dz2 is ready
@@ -409,22 +424,24 @@ static int enqueue_conv_bwd_split(aleppo_ctx *c, const UpdatePlan &p, const Samp
   segs.add(ReduceSeg{p.sW2, S2, 64 * 512, (long)L.off[P_W2]});
   segs.add(ReduceSeg{p.sB2, S2, 64, (long)L.off[P_B2]});
   segs.add(late0);
-  reduce_beside(c, p, segs);
+  reduce_beside(c, p, segs, dst);
   prof_begin(c, ALEPPO_K_CONV1_WGRAD);
   *S1 = conv1_wgrad(p.s, prec, c->dz1, c->obs, map, p.sW1, p.sB1, p.B);
   prof_end(c, ALEPPO_K_CONV1_WGRAD);
   return ALEPPO_OK;
 }
 
-// One optimizer step: forward, head, fork, fc dgrad || fc wgrad, bucket 0, conv3, the conv backward's tail, join, tail
-// reduce, bucket 1, sum of squares and Adam.
-static int enqueue_minibatch(aleppo_ctx *c, const UpdatePlan &p, int ep, int mb) {
-  const int H = c->H, A = c->A, prec = c->prec, mi = ep * p.M + mb;
+// The gradient half of one optimizer step: forward, head, fork, fc dgrad || fc wgrad, bucket 0, conv3, the conv backward's
+// tail, join, tail reduce.  dst: the gradient vector (internal layout) it lands in - c->G for aleppo_train, a gradient slot
+// for aleppo_grad_probe.  tail: conv1's two slab groups, which are NOT reduced yet unless their slab comes back nullptr
+// (data parallelism: the all-reduce needs the whole gradient) - the norm pass, or the probe's own reduce, sums them.
+static int enqueue_gradient(aleppo_ctx *c, const UpdatePlan &p, int ep, int mb, float *dst, ReduceSeg tail[2]) {
+  const int H = c->H, A = c->A, prec = c->prec;
   const ParamLayout &L = c->L;
   const long B = p.B;
   hipStream_t s = p.s, sw = p.sw;
   // contiguous env-major slices unless shuffling (the reference's randperm is unused, Q1)
-  SampleMap map = train_map(c, (long)mb * B);
+  SampleMap map = train_map(c, p.n0 + (long)mb * B);
   map.idx = p.pl.idx(ep);
   const int hparts = net_forward(c, c->obs, map, B, FC_FWD_MAX_PARTS);
   c->bwd_enq = Ctx::BwdMark{B, hparts, !p.bwd_fused}; // (aleppo_export_backward: what this minibatch leaves; host only)
@@ -436,8 +453,8 @@ static int enqueue_minibatch(aleppo_ctx *c, const UpdatePlan &p, int ep, int mb)
   prof_begin(c, ALEPPO_K_FC_WGRAD, sw);
   // split-K slabs (or, with one slice, straight into the gradient tensor)
   const bool fc_direct = fc_wgrad_slices(prec, B) == 1;
-  const int Sfc = fc_wgrad(sw, prec, c->dh, c->a3, fc_direct ? c->G + L.off[P_WFC] : p.sWfc,
-                           fc_direct ? c->G + L.off[P_BFC] : p.sBfc, B, H);
+  const int Sfc = fc_wgrad(sw, prec, c->dh, c->a3, fc_direct ? dst + L.off[P_WFC] : p.sWfc,
+                           fc_direct ? dst + L.off[P_BFC] : p.sBfc, B, H);
   prof_end(c, ALEPPO_K_FC_WGRAD, sw);
   // bucket 0 = heads + fc.  With data parallelism it is reduced now so that its all-reduce overlaps the conv
   // backward; on one GPU all ten slab groups are reduced by ONE launch after the conv wgrads.
@@ -457,9 +474,9 @@ static int enqueue_minibatch(aleppo_ctx *c, const UpdatePlan &p, int ep, int mb)
     HIPCHK(c, hipEventRecord(c->ev_bucket0, sw));
     HIPCHK(c, hipStreamWaitEvent(c->comm_stream, c->ev_bucket0, 0));
     prof_begin(c, ALEPPO_K_REDUCE, c->comm_stream);
-    launch_reduce_slabs(c->comm_stream, segs0.seg, segs0.n, c->G);
+    launch_reduce_slabs(c->comm_stream, segs0.seg, segs0.n, dst);
     prof_end(c, ALEPPO_K_REDUCE, c->comm_stream);
-    NCCLCHK(c, ncclAllReduce(c->G, c->G, L.bucket0_end, ncclFloat, ncclSum, p.comm, c->comm_stream));
+    NCCLCHK(c, ncclAllReduce(dst, dst, L.bucket0_end, ncclFloat, ncclSum, p.comm, c->comm_stream));
     HIPCHK(c, hipEventRecord(c->ev_comm0, c->comm_stream));
     segs0.n = 0; // (reduced: nothing of bucket 0 is left for the late reduce)
   }
@@ -472,8 +489,8 @@ static int enqueue_minibatch(aleppo_ctx *c, const UpdatePlan &p, int ep, int mb)
   prof_end(c, ALEPPO_K_CONV3_WGRAD, sw);
   int S1 = 0;
   SegList segs;
-  if (int rc = p.bwd_fused ? enqueue_conv_bwd_fused(c, p, map, S3, segs0, segs, &S1)
-                           : enqueue_conv_bwd_split(c, p, map, S3, segs0, segs, &S1))
+  if (int rc = p.bwd_fused ? enqueue_conv_bwd_fused(c, p, map, S3, segs0, segs, &S1, dst)
+                           : enqueue_conv_bwd_split(c, p, map, S3, segs0, segs, &S1, dst))
     return rc;
   if (p.two) { // join: sumsq / Adam read the whole gradient
     HIPCHK(c, hipEventRecord(c->ev_wg, sw));
@@ -481,7 +498,8 @@ static int enqueue_minibatch(aleppo_ctx *c, const UpdatePlan &p, int ep, int mb)
   }
   // conv1's slabs: with data parallelism they are reduced now (the all-reduce needs the whole gradient); on one GPU
   // the sum-of-squares pass below sums them on the fly - one launch less on the serial tail of the minibatch.
-  ReduceSeg tail[2] = {{p.sW1, S1, 32 * 256, (long)L.off[P_W1]}, {p.sB1, S1, 32, (long)L.off[P_B1]}};
+  tail[0] = ReduceSeg{p.sW1, S1, 32 * 256, (long)L.off[P_W1]};
+  tail[1] = ReduceSeg{p.sB1, S1, 32, (long)L.off[P_B1]};
   if (p.dp) {
     segs.add(tail[0]);
     segs.add(tail[1]);
@@ -489,9 +507,20 @@ static int enqueue_minibatch(aleppo_ctx *c, const UpdatePlan &p, int ep, int mb)
   }
   if (segs.n) {
     prof_begin(c, ALEPPO_K_REDUCE);
-    launch_reduce_slabs(s, segs.seg, segs.n, c->G);
+    launch_reduce_slabs(s, segs.seg, segs.n, dst);
     prof_end(c, ALEPPO_K_REDUCE);
   }
+  return ALEPPO_OK;
+}
+
+// One optimizer step: the gradient into c->G, bucket 1, sum of squares and Adam.
+static int enqueue_minibatch(aleppo_ctx *c, const UpdatePlan &p, int ep, int mb) {
+  const int prec = c->prec, mi = ep * p.M + mb;
+  const ParamLayout &L = c->L;
+  hipStream_t s = p.s;
+  ReduceSeg tail[2];
+  if (int rc = enqueue_gradient(c, p, ep, mb, c->G, tail))
+    return rc;
   if (p.dp) {
     // Bucket 1 (the conv tensors, 0.35 MB) is on the critical path whatever stream carries it - nothing is left to
     // overlap it with - so it runs on the MAIN stream: a round trip through the communication stream cost two more
@@ -510,6 +539,54 @@ static int enqueue_minibatch(aleppo_ctx *c, const UpdatePlan &p, int ep, int mb)
               prec, c->sumsq_part, nblk_norm, p.hpd, c->adam_sched + 2 * mi, c->cfg.adam_beta1, c->cfg.adam_beta2,
               c->cfg.adam_eps, c->grad_norms + mi, p.reg, p.anchor);
   prof_end(c, ALEPPO_K_ADAM);
+  return ALEPPO_OK;
+}
+
+// aleppo_grad_probe's front (api_internal.hpp): a plan of one epoch and one minibatch whose planes start at sample `first`
+// and whose head reads and writes the probe's private storage, the prologue's launches for that slice, enqueue_gradient
+// into dst, and conv1's slabs by the narrow path of the slab reduce - slab_column_sum, the norm pass's own sum.
+int aleppo::grad_probe_enqueue(aleppo_ctx *c, long first, long n, bool policy, float *blk, float *ps, float *dst) {
+  UpdatePlan p{};
+  p.epochs = p.M = p.nm = 1;
+  p.N = c->batch_n;
+  p.B = n;
+  p.vclip = c->value_clip;
+  if (p.vclip)
+    if (int rc = ensure_val_storage(c))
+      return rc;
+  p.val_transpose = p.vclip && c->val_src == Ctx::VAL_ROLLOUT;
+  p.advn = !policy || c->adv_norm_mb; // (!policy: the record is (0, 0) and every advantage becomes a * 0)
+  p.klpen = c->kl_pen;
+  if (!c->wg_stream)
+    HIPCHK(c, hipStreamCreateWithFlags(&c->wg_stream, hipStreamNonBlocking));
+  p.s = c->stream;
+  p.hp = c->hyper;
+  p.hpd = blk + GP_HYPER;
+  p.fs = (size_t)c->maxB;
+  p.metric_ps = ps, p.kl_ps = ps + 7 * p.fs, p.advn_stats = blk + GP_ADVS, p.kl_beta = blk + GP_BETA;
+  p.n0 = first;
+  // (the routes of the context's own minibatches: under data parallelism aleppo_train keeps the split tail)
+  plan_routes(c, p, !(c->world > 1 || (c->nccl_comm && c->force_comm)));
+  Planes &pl = p.pl;
+  pl.B = n;
+  pl.M = 1;
+  pl.act = c->act_n + first, pl.oldlp = rp(c, c->oldlp_n, (size_t)first * c->A), pl.adv = rp(c, c->adv_n, first);
+  pl.ret = rp(c, c->ret_n, first), pl.vold = p.vclip ? rp(c, c->val_n, first) : nullptr;
+  pl.mask = c->mask_n + first, pl.order = nullptr, pl.counts = blk + GP_COUNT;
+  pl.ncounts = 1;
+  pl.epoch_stride = 0;
+  hipStream_t s = p.s;
+  if (p.val_transpose)
+    launch_transpose_tm_pitched(s, c->values_tm, (size_t)c->E * c->rsz, c->val_n, c->E, c->T, 1, (int)c->rsz);
+  launch_mask_count(s, pl.mask, pl.counts, n, 1);
+  if (policy && c->adv_norm_mb)
+    launch_advn_stats(s, pl.adv, pl.mask, n, 1, nullptr, blk + GP_ADVS, c->rt16);
+  ReduceSeg tail[2];
+  if (int rc = enqueue_gradient(c, p, 0, 0, dst, tail))
+    return rc;
+  prof_begin(c, ALEPPO_K_REDUCE);
+  launch_reduce_slabs(s, tail, 2, dst);
+  prof_end(c, ALEPPO_K_REDUCE);
   return ALEPPO_OK;
 }
 

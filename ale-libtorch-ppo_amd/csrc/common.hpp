@@ -317,6 +317,16 @@ struct Ctx {
   // never makes the calls
   ParamSet snapshot;
   void *pd_scratch = nullptr;
+  // ---- gradient probes (aleppo_grad_probe / _take / _import / _gram): the ALEPPO_GRAD_SLOTS gradient slots, ONE allocation
+  // of that many padded vectors made by the first call that writes one; the probe's private blocks - GP_BLOCK floats the
+  // head reads (device / pinned) and the per-sample planes it writes, [8][maxB]: the seven metric fields and the exact KL -
+  // and the Gram's partial records and results.  Each is allocated on first use and never again; nothing is enqueued for
+  // them on a context that never makes the calls, aleppo_train never reads them and aleppo_state_digest does not cover them
+  float *grad_slots = nullptr;
+  bool grad_written[ALEPPO_GRAD_SLOTS] = {false, false, false, false};
+  float *gp_blk = nullptr, *h_gp_blk = nullptr;
+  float *gp_ps = nullptr;
+  void *gg_scratch = nullptr;
   // ---- aleppo_refresh_advantages: the second values plane, RT [T+1][E] time-major like values_tm (which it never
   // replaces), and the statistics' scratch; each is allocated on first use and never again, nothing is enqueued for them on
   // a context that never makes the call
@@ -546,10 +556,45 @@ void launch_state_digest(hipStream_t s, const float *P, const float *M1, const f
 // records.  sections: aleppo_tensor_stats_section bits; without ALEPPO_TS_SEC_STEP only P is read.  coef: the clip factor
 // of aleppo_export_grads; step_size / bc2_sqrt / eps: adam_element's scalars of the last optimizer step.
 constexpr int TS_CHUNK = 4096;
+// the chunk grid the two passes of this structure share (aleppo_tensor_stats, aleppo_grad_gram)
+struct TsLayout {
+  uint32_t off[P_COUNT], size[P_COUNT]; // in floats, of the internal tensors
+  uint32_t split[P_COUNT];              // first element of the tensor's second exported row (== size: there is none)
+  uint32_t first[P_COUNT + 1];          // first chunk of each tensor; first[P_COUNT] = the grid
+};
+// exported row r = (internal tensor, which side of its split)
+struct TsRow {
+  int tensor, half;
+};
+__host__ __device__ inline TsRow ts_row(int r) {
+  constexpr int T[12] = {P_W1, P_B1, P_W2, P_B2, P_W3, P_B3, P_WFC, P_BFC, P_WH, P_BH, P_WH, P_BH};
+  return TsRow{T[r], r >= 10 ? 1 : 0};
+}
+TsLayout ts_layout(const ParamLayout &L);
+__device__ __forceinline__ bool ts_finite(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
+// sum over the 64 lanes by a fixed tree, valid in lane 0
+__device__ __forceinline__ double ts_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+    v += __shfl_down(v, o, 64);
+  return v;
+}
 size_t tensor_stats_scratch_bytes(const ParamLayout &L);
 void launch_tensor_stats(hipStream_t s, const float *P, const float *G, const float *M1, const float *M2,
                          const ParamLayout &L, int sections, float coef, float step_size, float bc2_sqrt, float eps,
                          void *scratch, const double **out_dev);
+// aleppo_grad_gram (grad_gram.hip): the Gram of K <= ALEPPO_GRAD_SLOTS padded vectors per exported tensor, over the chunk grid
+// above (one workgroup and one pair of partial records per chunk), then one small launch that adds the partials per
+// exported tensor in index order and writes double [ALEPPO_TENSOR_STATS_ROWS][K][K], then int64 [ALEPPO_TENSOR_STATS_ROWS]
+// (the left-out element indices), behind the records.  It only reads the vectors.
+size_t grad_gram_scratch_bytes(const ParamLayout &L);
+void launch_grad_gram(hipStream_t s, const float *const *vec, int K, const ParamLayout &L, void *scratch,
+                      const double **out_dev);
+// aleppo_grad_take's ALEPPO_GRAD_SRC_PARAM_DELTA: out = a - b, one fp32 subtraction per element of the padded vectors
+void launch_grad_delta(hipStream_t s, const float *a, const float *b, float *out, long n);
+// The probe's private device block: the hyper block the head reads (HYPER_BLOCK floats, 16-byte aligned), the advantage
+// record (mean_f, inv_f, std, 0), beta, and the slice's unmasked count
+enum { GP_HYPER = 0, GP_ADVS = 8, GP_BETA = 12, GP_COUNT = 16, GP_BLOCK = 20 };
 // aleppo_forward_activations / aleppo_activation_stats (activation_stats.hip).  Export: layer 0-2 = a1 / a2 / a3 of ns
 // samples, NHWC of T -> float NCHW.  Statistics: the batch is forwarded in chunks of at most maxB samples; after each
 // forward one read-only launch over a1 / a2 / a3 / h writes one partial record per (workgroup, unit) behind the records of

@@ -25,20 +25,7 @@ struct TsRecord { // what one chunk contributes to one exported tensor
 };
 static_assert(sizeof(TsRecord) == 48, "TsRecord layout"); // (whole 16-byte words: the reduction copies them as such)
 
-struct TsLayout {
-  uint32_t off[P_COUNT], size[P_COUNT]; // in floats, of the internal tensors
-  uint32_t split[P_COUNT];              // first element of the tensor's second exported row (== size: there is none)
-  uint32_t first[P_COUNT + 1];          // first chunk of each tensor; first[P_COUNT] = the grid
-};
-// exported row r = (internal tensor, which side of its split)
-struct TsRow {
-  int tensor, half;
-};
-__host__ __device__ inline TsRow ts_row(int r) {
-  constexpr int T[12] = {P_W1, P_B1, P_W2, P_B2, P_W3, P_B3, P_WFC, P_BFC, P_WH, P_BH, P_WH, P_BH};
-  return TsRow{T[r], r >= 10 ? 1 : 0};
-}
-static TsLayout ts_layout(const ParamLayout &L) {
+TsLayout ts_layout(const ParamLayout &L) {
   TsLayout t{};
   uint32_t chunks = 0;
   for (int k = 0; k < P_COUNT; ++k) {
@@ -57,14 +44,6 @@ size_t tensor_stats_scratch_bytes(const ParamLayout &L) {
          (size_t)ALEPPO_TENSOR_STATS_ROWS * ALEPPO_TENSOR_STATS_COLS * sizeof(double);
 }
 
-__device__ __forceinline__ bool ts_finite(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
-// sum over the 64 lanes by a fixed tree, valid in lane 0
-__device__ __forceinline__ double ts_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-    v += __shfl_down(v, o, 64);
-  return v;
-}
 __device__ __forceinline__ float ts_wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1)

@@ -967,6 +967,82 @@ int aleppo_policy_diff(aleppo_ctx *ctx, const uint8_t *observations, int64_t n, 
                        size_t stat_count, double *per_sample, size_t per_sample_count, int64_t *transitions,
                        size_t transition_count, float *outputs, size_t output_count);
 
+/* Gradient probes: the gradient as a DIRECTION, on the device.  aleppo_tensor_stats gives the norm of the last minibatch's
+ * gradient; these calls compute the gradient of any slice of the batch the context holds WITHOUT an optimizer step, keep a
+ * few of them next to G, and reduce their inner products per tensor.  What they answer: the gradient noise scale
+ * (McCandlish et al. 2018, "An Empirical Model of Large-Batch Training", B_simple from the norms at two batch sizes);
+ * whether the critic fights the actor in the shared trunk (the per-tensor cosine of the policy term's and the value term's
+ * gradient - the motivation of Phasic Policy Gradient, Cobbe et al. 2021); how much minibatches interfere (Lyle et al.
+ * 2023); whether Adam's momentum still points where a fresh gradient points.  The reference has none of it; the route
+ * without these calls is aleppo_train(lr = 0), which still advances Adam's moments and step count and overwrites the
+ * per-sample metric planes, then aleppo_export_grads over PCIe, per question - and it cannot separate the loss terms.
+ * Slots: ALEPPO_GRAD_SLOTS vectors in the private padded layout of G (fp32, zero-filled, pads stay zero), allocated
+ *   together through the context's memory registry by the first call that writes one and kept until aleppo_destroy.
+ *   aleppo_state_digest does not cover them, no checkpoint holds them, aleppo_train never reads them.
+ * aleppo_grad_probe(slot, first, n, cfg, unmasked_out): slot = the gradient the optimizer step of aleppo_train would have
+ *   been given for the minibatch of samples [first, first + n) of the batch, in logical (env-major, contiguous) order, at
+ *   the live parameters; no clip, no Adam.  1 <= n <= maxB = max(E, max_minibatch).
+ *   cfg: NULL = { 1, the current ALEPPO_OPT_VALUE_LOSS_COEF, the current ALEPPO_OPT_ENTROPY_COEF, 0 }; policy_term 0 or
+ *     1, the two coefficients finite and >= 0, reserved 0.  Everything else is as aleppo_train would do it for a
+ *     contiguous minibatch of n samples: the clip range and the value-clip range, ALEPPO_OPT_VALUE_CLIP (with the rollout
+ *     batch's value transpose), ALEPPO_OPT_ADV_NORM_MINIBATCH with the statistics of THIS slice, ALEPPO_OPT_KL_PENALTY
+ *     with the current beta, the masked mean over this slice's unmasked count, the kernel routes a minibatch of n
+ *     samples takes (fused forward; the fused or split backward tail by the ALEPPO_OPT_FUSED_BWD rule; the pipelined or
+ *     small-tile fc; the two streams), the same slab reduction with conv1's slabs summed as the norm pass sums them.
+ *     ALEPPO_OPT_MINIBATCH_SHUFFLE is not consulted: a probe names its samples itself.
+ *   The head: with policy_term = 1 the entry point and arguments of aleppo_train; with policy_term = 0 the
+ *     advantage-record entry point with a private record (mean_f, inv_f) = (+0.0f, +0.0f), so every advantage is a * 0 and
+ *     the policy term's gradient is exactly zero - no kernel knows about probes.  The head reads a private hyper block
+ *     (clip ranges from the context, c_v / c_e from cfg) and writes its per-sample planes to private scratch.  With
+ *     (n = N / M, first = mb * n) and cfg = NULL the slot is bit for bit the G that aleppo_train(M) leaves for minibatch mb.
+ *   Linear combinations: in exact arithmetic g(1, c_v, c_e) = g_pi + c_v g_v + c_e g_e with the three pure probes
+ *     g_pi = g(1, 0, 0), g_v = g(0, 1, 0), g_e = g(0, 0, 1), and the Gram is bilinear: a host forms the inner product of
+ *     ANY two combinations from the 3 x 3 Gram of the pure probes.  That is why there is no per-term slot arithmetic on
+ *     the device.  (In fp32 / bf16 the identity holds to rounding, not bit for bit.)
+ *   Afterwards aleppo_export_grads, aleppo_tensor_stats, aleppo_read_train_metric, aleppo_state_digest, the parameters,
+ *     both moments and the step count are bit for bit what they were; a captured update (ALEPPO_OPT_UPDATE_GRAPH) replays
+ *     without a re-capture; the next aleppo_train gives the bits of a context that never probed.  It does run the network
+ *     in the shared activation scratch: like aleppo_policy_diff it drops what aleppo_step pre-computed, and
+ *     aleppo_export_backward / aleppo_export_acting refuse afterwards.
+ *   Data parallelism: NEVER a collective.  The slot is THIS rank's slice with THIS rank's unmasked count (and this rank's
+ *     advantage statistics), unlike aleppo_train's all-reduced G: ranks may probe different slices, or only one may probe.
+ *   Computed WHEN CALLED: the stream's synchronise, the launches, one synchronise.  *unmasked_out (NULL: not wanted)
+ *     receives the slice's unmasked count.
+ * aleppo_grad_take(slot, source, set): ALEPPO_GRAD_SRC_EXP_AVG - the slot becomes Adam's first moment as it stands (set
+ *   must be 0); ALEPPO_GRAD_SRC_PARAM_DELTA - the slot becomes fl(p_live - p_set), one fp32 subtraction per element that
+ *   a host recomputes bit for bit from the two exports, set = ALEPPO_SET_AVERAGED or ALEPPO_SET_SNAPSHOT.  Enqueues only.
+ * aleppo_grad_export / aleppo_grad_import move a slot in the order and with the count checks of aleppo_export_params /
+ *   aleppo_load_params: a stored direction (a checkpointed gradient, another run's update) becomes comparable.
+ * aleppo_grad_gram(slots, k): slots names 1 <= k <= ALEPPO_GRAD_SLOTS written slots x_0 .. x_{k-1}, repeats allowed.
+ *   gram: double [ALEPPO_TENSOR_STATS_ROWS][k][k], the rows of aleppo_tensor_stats (the 12 tensors in libtorch
+ *   parameters() order, then the whole model); [r][i][j] = the sum over the elements e of tensor r of
+ *   (double)x_i[e] * (double)x_j[e].  The products are exact in double; the additions are in an order that is a function
+ *   of (H, A, k) only - aleppo_tensor_stats' chunks, thread order and fixed tree, the chunks in index order, row 12 the
+ *   twelve rows in row order - so two calls return the same bits, and [r][i][j] and [r][j][i] are the same bits.  An
+ *   element index at which ANY of the k named slots is NaN / Inf is left out of every entry and counted once in
+ *   nonfinite[r] (NULL, or int64 [ALEPPO_TENSOR_STATS_ROWS], row 12 the total).  No atomics; it only reads the slots.
+ *   Under aleppo_profile_enable its two launches are one bracket of class ALEPPO_K_ACT_STATS (the class the read-only
+ *   diagnostic passes share); a probe's launches fall into the update's classes, as aleppo_train's do.
+ * Errors: a slot outside [0, ALEPPO_GRAD_SLOTS), n < 1, n > maxB, first < 0, first + n past the batch, bad cfg values, a
+ *   source or set the call does not take, a NULL or a wrong count: ALEPPO_ERR_INVALID_ARGUMENT.  No batch, a caller batch
+ *   without values under ALEPPO_OPT_VALUE_CLIP, a set that does not exist yet, exporting or naming in a Gram a slot that
+ *   nothing has written, any call while a step is armed: ALEPPO_ERR_RUNTIME.  A failed call changes nothing. */
+#define ALEPPO_GRAD_SLOTS 4
+enum { ALEPPO_GRAD_SRC_EXP_AVG = 0, ALEPPO_GRAD_SRC_PARAM_DELTA = 1 };
+typedef struct {
+  int32_t policy_term;   /* 1: the policy term is part of the loss; 0: it is switched off exactly */
+  float value_loss_coef; /* c_v, finite and >= 0 */
+  float entropy_coef;    /* c_e, finite and >= 0 */
+  int32_t reserved;      /* 0 */
+} aleppo_grad_probe_config;
+int aleppo_grad_probe(aleppo_ctx *ctx, int slot, int64_t first, int64_t n, const aleppo_grad_probe_config *cfg,
+                      int64_t *unmasked_out);
+int aleppo_grad_take(aleppo_ctx *ctx, int slot, int source, int set);
+int aleppo_grad_export(aleppo_ctx *ctx, int slot, float *flat, size_t count);
+int aleppo_grad_import(aleppo_ctx *ctx, int slot, const float *flat, size_t count);
+int aleppo_grad_gram(aleppo_ctx *ctx, const int32_t *slots, int k, double *gram, size_t gram_count, int64_t *nonfinite,
+                     size_t nonfinite_count);
+
 /* Per-epoch advantage recomputation (Andrychowicz et al. 2021, "What Matters in On-Policy RL", choice C.5: recompute the
  * advantages before every pass over the data; what a CleanRL / SB3 user writes as "re-run compute_gae inside the epoch
  * loop"; the reference has none of it).  After the first epoch of an update the critic has moved, so the advantages and
@@ -1376,7 +1452,9 @@ typedef enum {
   ALEPPO_K_REC_CAPTURE = 20, /* the episode recorders' capture kernel (aleppo_rec_open), one launch per recorded step */
   ALEPPO_K_ACT_STATS = 21,  /* the read-only passes over the activations, one bracket per forward chunk: aleppo_activation_stats' launch,
                                aleppo_feature_rank's three (flags, Gram, reduce), aleppo_refresh_advantages' value launch (the last
-                               bracket of a call also holds its two statistics launches) */
+                               bracket of a call also holds its two statistics launches); and the read-only diagnostic passes
+                               that have no class of their own: aleppo_policy_diff's comparison, one bracket per chunk, and
+                               aleppo_grad_gram's two launches, one bracket per call */
   ALEPPO_K_RECYCLE = 22,    /* the masked pass of aleppo_recycle_units / aleppo_recycle_dormant over P / M1 / M2, one launch per call */
   ALEPPO_K_SAL_BLUR = 23,    /* aleppo_saliency's blur of the samples a forward chunk touches */
   ALEPPO_K_SAL_PERTURB = 24, /* ... its blend of one chunk's perturbed stacks into the staging buffer */

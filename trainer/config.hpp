@@ -69,6 +69,12 @@ struct Config {
   bool log_policy_churn = false;
   size_t policy_churn_interval = 1;
   bool policy_churn_averaged = false;
+  // extension: gradient probes - before the update of every n-th rollout, the gradient noise scale (McCandlish et al. 2018)
+  // from aleppo_grad_probe at gradient_stats_small_batch samples and at one minibatch, the per-tensor cosine of the policy
+  // term's and the value term's gradient, and the cosine of Adam's first moment with the fresh gradient (aleppo_grad_gram)
+  bool log_gradient_stats = false;
+  size_t gradient_stats_interval = 1;
+  size_t gradient_stats_small_batch = 0; // 0: a quarter of the minibatch
   // extension: ReDo (Sokar et al. 2023) - recycle the dormant units of the held batch (aleppo_recycle_dormant)
   bool recycle_dormant = false;
   // after the update of every n-th rollout.  64: ReDo recycles every 1000 gradient steps; the benched configuration takes
@@ -392,6 +398,20 @@ static Config load_config(const std::string &path) { // keys / defaults of src/b
     if (c.policy_churn_averaged && !c.ema_decay_set)
       throw std::runtime_error("policy_churn_averaged needs ema_decay");
   }
+  read_key(kv, "log_gradient_stats", c.log_gradient_stats);
+  {
+    const long interval = as<long>(kv, "gradient_stats_interval", 1);
+    if (interval < 1)
+      throw std::runtime_error("gradient_stats_interval must be positive");
+    c.gradient_stats_interval = (size_t)interval;
+    const long small = as<long>(kv, "gradient_stats_small_batch", 0);
+    if (kv.count("gradient_stats_small_batch") && small < 1)
+      throw std::runtime_error("gradient_stats_small_batch must be positive");
+    c.gradient_stats_small_batch = (size_t)small;
+    for (const char *k : {"gradient_stats_interval", "gradient_stats_small_batch"})
+      if (kv.count(k) && !c.log_gradient_stats) // (nothing else reads them; given as false too)
+        throw std::runtime_error(std::string(k) + " needs log_gradient_stats: true");
+  }
   read_key(kv, "record_evaluation", c.record_evaluation);
   if (c.record_evaluation && !c.device_evaluation)
     throw std::runtime_error("record_evaluation needs device_evaluation: true");
@@ -494,6 +514,11 @@ static HParams hparams_of(const Config &c) {
     h.numbers.emplace_back("ema_decay", c.ema_decay);
   if (c.log_policy_churn)
     h.numbers.emplace_back("policy_churn_interval", (double)c.policy_churn_interval);
+  if (c.log_gradient_stats) {
+    h.numbers.emplace_back("gradient_stats_interval", (double)c.gradient_stats_interval);
+    if (c.gradient_stats_small_batch)
+      h.numbers.emplace_back("gradient_stats_small_batch", (double)c.gradient_stats_small_batch);
+  }
   if (c.weight_decay > 0)
     h.numbers.emplace_back("weight_decay", c.weight_decay);
   if (c.l2_init_coef > 0)
@@ -514,6 +539,7 @@ static HParams hparams_of(const Config &c) {
                                                     {"log_feature_rank", c.log_feature_rank},
                                                     {"log_policy_churn", c.log_policy_churn},
                                                     {"policy_churn_averaged", c.policy_churn_averaged},
+                                                    {"log_gradient_stats", c.log_gradient_stats},
                                                     {"recycle_dormant", c.recycle_dormant},
                                                     {"record_saliency", c.record_saliency},
                                                     {"reward_scaling", c.reward_scaling},

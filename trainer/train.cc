@@ -78,6 +78,17 @@
 // policy_churn_averaged: true, needs ema_decay, also logs policy_churn/ema_churn and /ema_kl from (ALEPPO_SET_AVERAGED,
 // ALEPPO_SET_LIVE) after the EMA update; never a collective; the two other keys without log_policy_churn, a non-positive
 // interval, policy_churn_averaged without ema_decay and a library without the entry points are refused at start-up).
+// log_gradient_stats: false (true: BEFORE the update of every gradient_stats_interval-th rollout - default 1 - rank 0 probes
+// the gradient of the first minibatch's samples without a step: aleppo_grad_probe with the loss as it stands at
+// gradient_stats_small_batch samples - default a quarter of the minibatch - and at the whole minibatch, the policy term alone
+// and the value term alone at the minibatch, aleppo_grad_take of Adam's first moment, and two aleppo_grad_gram calls; logs
+// gradients/noise_scale - B_simple of McCandlish et al. 2018 with the unmasked counts as the batch sizes -,
+// gradients/policy_value_cosine/conv1, /conv2, /conv3, /fc - the weight tensors - and /all, and gradients/momentum_cosine
+// - not on the first update, where the moment is zero; likewise no noise scale where the two slices have the same unmasked
+// count or the estimate of |G|^2 is not positive, and no cosine of a tensor whose gradient is zero; the probes change nothing the update reads, so the run is
+// bit-identical to the run without the key; never a collective: rank 0's samples; the two other keys without
+// log_gradient_stats, a non-positive interval, a small batch that is not smaller than the minibatch and a library without
+// the entry points are refused at start-up).
 // clip_param_final, value_loss_coef_final, entropy_coef_final,
 // max_gradient_norm_final (absent: the value stays what the config says and no option is set; given: rollout i of
 // num_rollouts updates with v0 + (v_final - v0) * i / num_rollouts, computed in double and rounded to float once - the
@@ -214,6 +225,10 @@
 #pragma weak aleppo_refresh_advantages
 #pragma weak aleppo_snapshot_take
 #pragma weak aleppo_policy_diff
+// ... and the gradient probes (log_gradient_stats: true)
+#pragma weak aleppo_grad_probe
+#pragma weak aleppo_grad_take
+#pragma weak aleppo_grad_gram
 // (record_saliency: true - aleppo_saliency is declared weak in saliency.hpp)
 // ... and the exponentially averaged parameters (ema_decay)
 #pragma weak aleppo_ema_open
@@ -311,6 +326,12 @@ struct Run {
       throw std::runtime_error("Batch size must be divisible by num_mini_batches");
     if (E % cfg.worker_batch_size)
       std::cerr << "warning: total_environments % worker_batch_size != 0 would deadlock the reference's queue\n";
+    if (cfg.log_gradient_stats) { // (the minibatch is this rank's: known only here)
+      const size_t B = E * T / (size_t)cfg.num_mini_batches;
+      if (cfg.gradient_stats_small_batch >= B || B < 2)
+        throw std::runtime_error("gradient_stats_small_batch must be smaller than the minibatch (" + std::to_string(B) +
+                                 " samples)");
+    }
     if (cfg.recycle_dormant && world > 1) // (each rank would score its own samples and recycle its own units)
       throw std::runtime_error("recycle_dormant needs WORLD_SIZE 1: the dormancy scores describe one rank's samples");
     if (cfg.record_video && !cfg.device_environments)
@@ -397,6 +418,9 @@ static void refuse_missing_entry_points(const Config &cfg) {
   if (cfg.log_policy_churn && !(aleppo_snapshot_take && aleppo_policy_diff))
     throw std::runtime_error("log_policy_churn is set but this build's library has no policy churn "
                              "(aleppo_snapshot_take / aleppo_policy_diff are missing)");
+  if (cfg.log_gradient_stats && !(aleppo_grad_probe && aleppo_grad_take && aleppo_grad_gram))
+    throw std::runtime_error("log_gradient_stats is set but this build's library has no gradient probes "
+                             "(aleppo_grad_probe / aleppo_grad_take / aleppo_grad_gram are missing)");
   if (cfg.log_feature_rank && !aleppo_feature_rank)
     throw std::runtime_error("log_feature_rank is set but this build's library has no feature rank "
                              "(aleppo_feature_rank is missing)");
@@ -790,6 +814,11 @@ struct Update {
   double feature_rank[ALEPPO_FR_COUNT] = {};
   bool churn_read = false; // log_policy_churn, rank 0: this rollout is one of the interval's, churn / ema_churn hold it
   double churn[ALEPPO_PD_COUNT] = {}, ema_churn[ALEPPO_PD_COUNT] = {};
+  bool grad_read = false; // log_gradient_stats, rank 0: this rollout is one of the interval's, the fields below hold it
+  double noise_scale = 0, pv_cosine[5] = {}, momentum_cosine = 0; // pv_cosine: conv1.w, conv2.w, conv3.w, fc.w, all
+  // ... and which of them exist: the two counts differ and the estimate of |G|^2 is positive; neither norm of a tensor
+  // is zero; the moment is not zero (a figure that does not exist is not logged)
+  bool noise_read = false, pv_read[5] = {}, momentum_read = false;
   bool recycled = false; // recycle_dormant: this rollout is one of the interval's, recycle_counts is what it recycled
   int64_t recycle_counts[ALEPPO_RECYCLE_COUNTS] = {};
   bool refreshed = false; // recompute_advantages: a refresh ran in this update, refresh holds the last one's statistics
@@ -802,6 +831,41 @@ struct Update {
         planes(5, std::vector<float>((size_t)run.cfg.num_epochs * N)), hyper_now(run.schedules.size()) {}
   size_t nrun() const { return epochs_run * nmb; } // minibatches that ran
 };
+// log_gradient_stats: four probes of the first minibatch's samples, the moment, two Grams (the header's gradient probes);
+// slots 0 .. 3 = the small slice (then the moment), the minibatch, the policy term alone, the value term alone
+static void probe_gradients(Run &run, Update &u) {
+  const Config &cfg = run.cfg;
+  aleppo_ctx *ctx = run.ctx;
+  Profile::Span sp(&run.prof, "aleppo_grad_probe");
+  const int64_t B = (int64_t)(u.N / u.nmb);
+  const int64_t small = cfg.gradient_stats_small_batch ? (int64_t)cfg.gradient_stats_small_batch : std::max<int64_t>(1, B / 4);
+  int64_t b_small = 0, b_big = 0;
+  check(ctx, aleppo_grad_probe(ctx, 0, 0, small, nullptr, &b_small));
+  check(ctx, aleppo_grad_probe(ctx, 1, 0, B, nullptr, &b_big));
+  const int32_t pair[2] = {0, 1}, all[4] = {0, 1, 2, 3};
+  const size_t rows = ALEPPO_TENSOR_STATS_ROWS;
+  double g2[ALEPPO_TENSOR_STATS_ROWS][2][2], g4[ALEPPO_TENSOR_STATS_ROWS][4][4];
+  check(ctx, aleppo_grad_gram(ctx, pair, 2, &g2[0][0][0], rows * 4, nullptr, 0));
+  // McCandlish et al. 2018, Appendix A, on the whole model: |G|^2 and S from the two squared norms, B_simple = S / |G|^2
+  const double s2 = g2[rows - 1][0][0], l2 = g2[rows - 1][1][1], bs = (double)b_small, bl = (double)b_big;
+  const double G2 = (bl * l2 - bs * s2) / (bl - bs), S = (s2 - l2) / (1.0 / bs - 1.0 / bl);
+  u.noise_read = b_small > 0 && b_small < b_big && G2 > 0 && std::isfinite(S / G2);
+  u.noise_scale = u.noise_read ? S / G2 : 0.0;
+  const aleppo_grad_probe_config policy{1, 0.f, 0.f, 0}, value{0, 1.f, 0.f, 0};
+  check(ctx, aleppo_grad_probe(ctx, 2, 0, B, &policy, nullptr));
+  check(ctx, aleppo_grad_probe(ctx, 3, 0, B, &value, nullptr));
+  check(ctx, aleppo_grad_take(ctx, 0, ALEPPO_GRAD_SRC_EXP_AVG, 0));
+  check(ctx, aleppo_grad_gram(ctx, all, 4, &g4[0][0][0], rows * 16, nullptr, 0));
+  static const int weight_rows[5] = {0, 2, 4, 6, ALEPPO_TENSOR_STATS_ROWS - 1};
+  for (int k = 0; k < 5; ++k) {
+    const auto &g = g4[weight_rows[k]];
+    u.pv_read[k] = g[2][2] > 0 && g[3][3] > 0;
+    u.pv_cosine[k] = u.pv_read[k] ? g[2][3] / std::sqrt(g[2][2] * g[3][3]) : 0.0;
+  }
+  const auto &g = g4[rows - 1];
+  u.momentum_read = g[0][0] > 0 && g[1][1] > 0;
+  u.momentum_cosine = u.momentum_read ? g[0][1] / std::sqrt(g[0][0] * g[1][1]) : 0.0;
+}
 static void update(Run &run, size_t r, Update &u) {
   const Config &cfg = run.cfg;
   aleppo_ctx *ctx = run.ctx;
@@ -821,6 +885,11 @@ static void update(Run &run, size_t r, Update &u) {
   u.kl_beta = run.st.kl_beta;
   if (run.kl_penalty())
     set_float_option(ctx, ALEPPO_OPT_KL_COEF, u.kl_beta);
+  // the gradient as a direction, at the parameters this update starts from (not a collective: rank 0's samples; after the
+  // options above, so that the probed loss is the one the update uses)
+  u.grad_read = cfg.log_gradient_stats && run.rank == 0 && (r + 1) % cfg.gradient_stats_interval == 0;
+  if (u.grad_read)
+    probe_gradients(run, u);
   // policy churn: the parameters this update starts from, kept on the device (not a collective: rank 0's samples)
   u.churn_read = cfg.log_policy_churn && run.rank == 0 && (r + 1) % cfg.policy_churn_interval == 0;
   if (u.churn_read) {
@@ -1032,6 +1101,16 @@ static void log_scalars(Run &run, const EpisodeLog &log, const BatchStatistics &
       logger.add_scalar("policy_churn/ema_churn", step, (float)u.ema_churn[ALEPPO_PD_CHURN]);
       logger.add_scalar("policy_churn/ema_kl", step, (float)u.ema_churn[ALEPPO_PD_MEAN_KL_AB]);
     }
+  }
+  if (u.grad_read) { // (of the first minibatch's samples, before the update; set on rank 0 only)
+    if (u.noise_read)
+      logger.add_scalar("gradients/noise_scale", step, (float)u.noise_scale);
+    static const char *const names[5] = {"conv1", "conv2", "conv3", "fc", "all"};
+    for (int k = 0; k < 5; ++k)
+      if (u.pv_read[k])
+        logger.add_scalar(std::string("gradients/policy_value_cosine/") + names[k], step, (float)u.pv_cosine[k]);
+    if (u.momentum_read)
+      logger.add_scalar("gradients/momentum_cosine", step, (float)u.momentum_cosine);
   }
   if (u.recycled) {
     for (int k = 0; k < 4; ++k)
